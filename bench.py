@@ -5,9 +5,10 @@ One "step" = one pass of the hot path over one batch of synthetic input: fold a 
 flow_record_t (already resident in HBM) into the flow table and evict it.
 
 N = 1 (default): BASELINE.json configs[1] — 100 M records, 1 M unique flows, hash-aggregate only: ONE
-  nfagg_ingest_device call + one nfagg_evict_device per step. After the timed steps the same run measures, bounded to a few
-  seconds, the other legs the reference's users care about (`extra`): the PCIe-inclusive host path, configs[2] (+ Count-Min
-  + HLL), the configs[4] shape (dedup merge on, 90 % of the records one flow) and the reference's default CACHE_MAX_FLOWS.
+  nfagg_ingest_device call + one nfagg_evict_device per step. With --full, after the timed steps the same run measures, bounded
+  to a few seconds, the other legs the reference's users care about (`extra`): the PCIe-inclusive host path, configs[2]
+  (+ Count-Min + HLL), the configs[4] shape (dedup merge on, 90 % of the records one flow) and the reference's default
+  CACHE_MAX_FLOWS.
 
 N > 1: BASELINE.json configs[3] — ONE common stream of N x 125 M records over N x 1.25 M flows, Count-Min + HLL on, one
   process per GPU (torch.distributed, backend nccl = RCCL). Slice r of the stream (arrival positions [r n, (r+1) n)) is
@@ -20,9 +21,14 @@ N > 1: BASELINE.json configs[3] — ONE common stream of N x 125 M records over 
   torch.distributed.run it is one of them. --presharded keeps round 2's communication-free line (every rank folds a
   private stream over its own shard's population: linear by construction) for comparison.
 
-Prints ONE JSON line on rank 0 (see the task contract): metric/value/unit, `roofline` (HBM-bound: algorithmic bytes /
-ingest-kernel time measured with HIP events on the kernel's stream) and, at N = 1, `cpu_baseline` (the CPU oracle — a C
-restatement of pkg/flow.Accounter — timed on a bounded sample of the same stream).
+Prints ONE JSON line on rank 0: metric/value/unit, ms_per_step (one timed step), `roofline` (HBM-bound: algorithmic bytes /
+ingest-kernel time measured with HIP events on the kernel's stream, from the timed steps themselves).
+
+A plain run (`--gpus 1 --steps K --warmup W`) does only that: set up, W warm-up steps, K timed steps, the line. --full adds what
+takes runs of its own: at N = 1 `cpu_baseline` (the CPU oracle — a C restatement of pkg/flow.Accounter — timed on a bounded
+sample of the same stream), `extra` and the HBM yardsticks (roofline.hbm_*); at N > 1 the instrumented windows of
+config.exchange. --dump-outputs DIR writes what the last timed step evicted (dump_outputs); the stream is seeded, so the same
+arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -59,10 +65,16 @@ def parse_args(argv=None):
     ap.add_argument("--variant", type=int, default=0, help="ingest kernel variant (DESIGN.md)")
     ap.add_argument("--dedup", action="store_true", help="configs[4]: NFAGG_MODE_KERNEL_DEDUP, every flow seen on two interfaces (stream variant 2)")
     ap.add_argument("--chunk", type=int, default=0, help="records per nfagg_ingest_device call (0 = whole stream)")
-    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="records of the stream the CPU oracle is timed on (0 = skip; default: the whole "
-                    "100 M-record stream of configs[1] — ~10 s on one core, ~4 s more for the multi-core variants)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the bench measures: the CPU baseline (cpu_baseline), "
+                    "the extra legs (extra), the HBM yardsticks (roofline.hbm_*) and, at N > 1, the instrumented exchange windows (config.exchange). "
+                    "Off by default: a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step evicted to "
+                    "DIR/<name>.npy (float64, key-sorted, a fixed seeded sample of at most 64 MB in all; see dump_outputs)")
+    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="with --full: records of the stream the CPU oracle is timed on (0 = skip; default: "
+                    "the whole 100 M-record stream of configs[1] — ~10 s on one core, ~4 s more for the multi-core variants)")
     ap.add_argument("--max-entries", type=int, default=0)
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the bounded extra legs (e2e host path, configs[2], configs[4] shape, CACHE_MAX_FLOWS 5000)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full at N = 1: skip the bounded extra legs (e2e host path, configs[2], configs[4] shape, "
+                    "CACHE_MAX_FLOWS 5000)")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1 (local fold): window k's tick (sketch all-reduce, partials export, all-to-all, "
                     "merge, eviction) strictly after its fold and before the next window's — round 5's line. Default: the tick of window k runs "
                     "beside the fold of window k + 1 (two tables per rank, a host thread for the tick)")
@@ -84,7 +96,12 @@ def parse_args(argv=None):
                     "runs): comma-separated HIP ordinals, e.g. 0,1,2,3,4,5,6,7 — or 0,0,0,0 to rehearse four members on one GPU. One COMMON "
                     "stream (slice i arrives on member i's device), partitioned on the device and routed by key hash; not the torchrun contract path")
     ap.add_argument("--print-spawn", action="store_true", help="print the command line --gpus N would spawn and exit (no GPU needed)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def free_port():
@@ -159,6 +176,26 @@ def resolve_sizes(args, world):
     n = args.records or (100_000_000 if world == 1 else 125_000_000)
     keys = args.flows or (1_000_000 if world == 1 else 1_250_000)
     return n, keys
+
+
+DUMP_MAX_FLOWS = 1 << 17    # 36 float64 words per flow: 36 MiB of flows + 1 MiB of indices, under 64 MB for a whole run
+
+
+def dump_outputs(out_dir, name, raw, parts=1):
+    """--dump-outputs: what the caller of the timed path receives from its last step — the evicted flows, 144-byte flow_record_t —
+    in a form that two builds can be compared by. Key-sorted (the eviction order of a hash table is not part of the result), each
+    record as its 36 little-endian 32-bit words in float64 (exact): DIR/<name>.npy, shape (flows, 36). Above DUMP_MAX_FLOWS / parts
+    flows (parts: how many processes or members write beside this one) a fixed sample of them, drawn with seed 0;
+    DIR/<name>_index.npy holds the positions of the rows in the key-sorted eviction, DIR/<name>_count.npy the number of flows."""
+    import netobserv_ebpf_agent_amd as nf
+    os.makedirs(out_dir, exist_ok=True)
+    recs = nf.sort_by_key(np.ascontiguousarray(raw).view(nf.FLOW_RECORD))
+    k, cap = len(recs), max(1, DUMP_MAX_FLOWS // max(parts, 1))
+    idx = np.arange(k) if k <= cap else np.sort(np.random.default_rng(0).choice(k, cap, replace=False))
+    words = recs[idx].view(np.uint8).reshape(-1, 144).view("<u4")
+    np.save(os.path.join(out_dir, name + ".npy"), words.astype(np.float64))
+    np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, name + "_count.npy"), np.array([k], dtype=np.float64))
 
 
 def next_pow2(v):
@@ -410,6 +447,8 @@ def rank_main(args):
     dt = time.perf_counter() - t0
     if args.dump_evictions:
         d_out[: flows * 144].cpu().numpy().tofile("%s.%d" % (args.dump_evictions, rank))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "evicted_flows" if world == 1 else "evicted_flows_rank%d" % rank, d_out[: flows * 144].cpu().numpy(), world)
     class _Sum:                                     # the tables' stats, added up (two tables when the windows alternate)
         pass
     st = _Sum()
@@ -429,6 +468,7 @@ def rank_main(args):
         rf = [torch.zeros(1, dtype=torch.int64, device=mdev) for _ in range(world)]
         dist.all_gather(rf, torch.tensor([int(st.records_ingested)], dtype=torch.int64, device=mdev))
         records_folded = [int(x.item()) for x in rf]
+    if dist_on and args.full:
         # one more, instrumented window (outside the timed region), everything in sequence: what each phase costs on its own ...
         step(timed=phase)
         barrier()
@@ -443,7 +483,7 @@ def rank_main(args):
                                    "tick_ms_beside_a_fold": round(ov.get("tick_ms_beside_a_fold", 0.0) / 3, 3),
                                    "what": "window w's tick (all-reduce, export, all-to-all, merge, evict) on a host thread beside window w + 1's fold; "
                                            "the exchange is hidden when wall_ms_per_window is about max(fold, tick), not their sum"}
-    else:
+    if not dist_on:
         flows_total = flows
 
     if rank == 0:
@@ -533,6 +573,7 @@ def rank_main(args):
             out["config"]["member_records_folded"] = records_folded
             if local_fold:
                 out["config"]["unique_flows_total"] = keys_total
+            if local_fold and args.full:
                 out["config"]["exchange"] = {
                     "what": "rank 0, one instrumented step after the timed ones (host clock, device synchronised between the phases)",
                     **{k: (round(v, 3) if isinstance(v, float) else v) for k, v in phase.items()},
@@ -573,14 +614,14 @@ def rank_main(args):
         if sketch_sep_ms:
             rf["sketch_launch_in_launch_ms"] = True
         # ---- CPU baseline: the oracle (C restatement of pkg/flow.Accounter), 1 core, bounded sample
-        if args.cpu_sample > 0 and not dist_on:     # rank 0 at N=1 only
+        if args.full and args.cpu_sample > 0 and not dist_on:     # rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(args, d_recs, n, max_entries)
         # ---- the chip's copy bandwidth in this very run (state the peak used, confirm it with a D2D copy):
         # up to 4 GiB device-to-device (the stream's first half over its second: nothing reads the stream after this point),
         # read + written bytes over the time of the copy
         default_workload = (not dist_on and not args.dedup and not args.sketches and not args.hot_permille and args.variant == 0
                             and not args.chunk and not args.max_entries)
-        if default_workload and not args.no_extras:
+        if args.full and default_workload and not args.no_extras:
             # the extra legs regenerate streams into d_recs: before the copy test overwrites half of it
             for tb in tabs:
                 tb.close()
@@ -590,34 +631,35 @@ def rank_main(args):
                 out["extra"] = extras(args, torch, nf, synth, d_recs, d_out, gen_stream, n, keys)
             except Exception as exc:                      # never a reason to lose the bench line
                 out["extra"] = {"error": repr(exc)[:300]}
-        try:
-            # The chip's own yardsticks, in this very run, from kernels shaped like the fold's — csrc/nfagg_synth.hip
-            # y_read_records / y_read_stream / y_copy, HIP events around three passes each (round 5 timed torch.Tensor.copy_, a
-            # library blit at 4.8 TB/s; the guide's float4 copy kernel does 6.3): the stream's first 4 GiB read as records (seven
-            # 16-byte loads of every 144-byte record: whole lines cross the fabric), read as a plain 16-byte stream, and copied onto
-            # its second half (nothing reads the stream after this point).
-            nb = min(4 << 30, (n * 144) // 2 // 2304 * 2304)
-            sink = torch.zeros(2, dtype=torch.int64, device="cuda")
-            torch.cuda.synchronize()
-            a_ptr, b_ptr = d_recs.data_ptr(), d_recs.data_ptr() + nb
-            ms_rr = synth.yardstick(0, a_ptr, 0, nb, sink.data_ptr())
-            ms_rs = synth.yardstick(1, a_ptr, 0, nb, sink.data_ptr())
-            ms_cp = synth.yardstick(2, a_ptr, b_ptr, nb, sink.data_ptr())
-            rf = out["roofline"]
-            rf["hbm_read_records_measured_GBs"] = round(nb / (ms_rr * 1e-3) / 1e9, 1)
-            rf["hbm_read_stream_measured_GBs"] = round(nb / (ms_rs * 1e-3) / 1e9, 1)
-            rf["hbm_copy_measured_GBs"] = round(2 * nb / (ms_cp * 1e-3) / 1e9, 1)
-            rf["hbm_yardsticks"] = "own kernels (csrc/nfagg_synth.hip y_*), %d bytes, HIP events, 3 passes after 1" % nb
-            if rf.get("traffic"):
-                # the call's counter traffic is ~95 % reads (pass 1 streams the records, pass 2 gathers the spilled ones): the
-                # yardstick that matches its mix is the read stream, not the copy
-                tr = rf["traffic"]
-                rf["traffic_over_measured_read_stream"] = round(tr / rf["hbm_read_stream_measured_GBs"], 4)
-                rf["traffic_over_measured_read_records"] = round(tr / rf["hbm_read_records_measured_GBs"], 4)
-                rf["traffic_over_measured_copy"] = round(tr / rf["hbm_copy_measured_GBs"], 4)
-        except Exception as exc:                      # a diagnostic, never a reason to lose the bench line
-            out["roofline"]["hbm_copy_measured_GBs"] = None
-            out["roofline"]["hbm_copy_error"] = str(exc)[:100]
+        if args.full:
+            try:
+                # The chip's own yardsticks, in this very run, from kernels shaped like the fold's — csrc/nfagg_synth.hip
+                # y_read_records / y_read_stream / y_copy, HIP events around three passes each (round 5 timed torch.Tensor.copy_, a
+                # library blit at 4.8 TB/s; the guide's float4 copy kernel does 6.3): the stream's first 4 GiB read as records (seven
+                # 16-byte loads of every 144-byte record: whole lines cross the fabric), read as a plain 16-byte stream, and copied onto
+                # its second half (nothing reads the stream after this point).
+                nb = min(4 << 30, (n * 144) // 2 // 2304 * 2304)
+                sink = torch.zeros(2, dtype=torch.int64, device="cuda")
+                torch.cuda.synchronize()
+                a_ptr, b_ptr = d_recs.data_ptr(), d_recs.data_ptr() + nb
+                ms_rr = synth.yardstick(0, a_ptr, 0, nb, sink.data_ptr())
+                ms_rs = synth.yardstick(1, a_ptr, 0, nb, sink.data_ptr())
+                ms_cp = synth.yardstick(2, a_ptr, b_ptr, nb, sink.data_ptr())
+                rf = out["roofline"]
+                rf["hbm_read_records_measured_GBs"] = round(nb / (ms_rr * 1e-3) / 1e9, 1)
+                rf["hbm_read_stream_measured_GBs"] = round(nb / (ms_rs * 1e-3) / 1e9, 1)
+                rf["hbm_copy_measured_GBs"] = round(2 * nb / (ms_cp * 1e-3) / 1e9, 1)
+                rf["hbm_yardsticks"] = "own kernels (csrc/nfagg_synth.hip y_*), %d bytes, HIP events, 3 passes after 1" % nb
+                if rf.get("traffic"):
+                    # the call's counter traffic is ~95 % reads (pass 1 streams the records, pass 2 gathers the spilled ones): the
+                    # yardstick that matches its mix is the read stream, not the copy
+                    tr = rf["traffic"]
+                    rf["traffic_over_measured_read_stream"] = round(tr / rf["hbm_read_stream_measured_GBs"], 4)
+                    rf["traffic_over_measured_read_records"] = round(tr / rf["hbm_read_records_measured_GBs"], 4)
+                    rf["traffic_over_measured_copy"] = round(tr / rf["hbm_copy_measured_GBs"], 4)
+            except Exception as exc:                      # a diagnostic, never a reason to lose the bench line
+                out["roofline"]["hbm_copy_measured_GBs"] = None
+                out["roofline"]["hbm_copy_error"] = str(exc)[:100]
         quiet.emit(json.dumps(out))
     for tb in tabs:
         tb.close()
@@ -1128,6 +1170,7 @@ def group_main(args, torch):
     grp = nf.FlowGroup(devs, max_entries=max_entries, sketches=sk_flags, profile=True, local_fold=args.group_local_fold)
     out_cap = [o.numel() // 144 for o in outs]
     threads = args.group_threads
+    last_got = []                       # flows each member evicted in the latest step
 
     def feed(i):
         rc, c = grp.ingest_device(i, slices[i].data_ptr(), n)
@@ -1150,6 +1193,7 @@ def group_main(args, torch):
         if args.sketches:
             for m in grp.members:
                 m.sketch_reset()
+        last_got[:] = got
         return sum(got)
 
     def sync_all():
@@ -1165,6 +1209,9 @@ def group_main(args, torch):
         flows = step()
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        for i, (o, k) in enumerate(zip(outs, last_got)):
+            dump_outputs(args.dump_outputs, "evicted_flows_member%d" % i, o[: k * 144].cpu().numpy(), D)
     steps = max(args.steps, 1)
     sts = [m.stats() for m in grp.members]
     fold_ms = [st.ingest_kernel_ms / max(st.ingest_launches, 1) for st in sts]

@@ -323,7 +323,7 @@ def test_bench_gpus_2_dedup_runs_the_common_stream_rehearsed_on_one_gpu(nf, O):
     from netobserv_ebpf_agent_amd import synth
     n, keys = 500_000, 30_000
     j = _bench("--gpus", "2", "--dedup", "--hot-permille", "900", "--no-sketches", "--same-device", "--backend", "gloo", "--records", str(n),
-               "--flows", str(keys), "--steps", "2", "--warmup", "1")
+               "--flows", str(keys), "--steps", "2", "--warmup", "1", "--full")
     assert j["n_gpus"] == 2 and j["value"] > 0
     c = j["config"]
     assert "configs[4]" in c["workload"] and "local fold" in c["parallelism"] and "REHEARSAL" in c["parallelism"]

@@ -32,7 +32,7 @@ def test_bench_world_1_through_the_rccl_path(nf, dedup):
     """configs[3] (and, with --dedup, configs[4]) as one rank: the same step the scaling curve times."""
     n, keys = 600_000, 30_000
     j = _bench("--gpus", "1", "--force-dist", "--backend", "nccl", "--records", str(n), "--flows", str(keys), "--steps", "2", "--warmup", "1",
-               *(("--dedup", "--hot-permille", "900") if dedup else ()))
+               "--full", *(("--dedup", "--hot-permille", "900") if dedup else ()))
     c = j["config"]
     assert j["n_gpus"] == 1 and c["rccl_ranks"] == 1 and c["backend"] == "nccl" and "REHEARSAL" not in c["parallelism"]
     assert ("configs[4]" if dedup else "configs[3]") in c["workload"] and "local fold" in c["parallelism"]

@@ -180,6 +180,36 @@ def test_bench_stdout_carries_the_json_line_only():
         assert s in p.stderr
 
 
+def test_bench_options_and_output_dump(nf, tmp_path, monkeypatch):
+    """A plain run measures the headline only (--full is off by default), --steps is the number of timed steps (at least one), and
+    --dump-outputs writes the evicted flows key-sorted as exact float64 words: all of them, or the same seeded sample every time."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    assert bench.parse_args(["--full", "--dump-outputs", str(tmp_path)]).full
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    rng = np.random.default_rng(3)
+    recs = np.zeros(1000, dtype=nf.FLOW_RECORD)
+    recs.view(np.uint8).reshape(-1, 144)[:] = rng.integers(0, 256, (1000, 144), dtype=np.uint8)
+    want = nf.sort_by_key(recs).view(np.uint8).reshape(-1, 144)
+    shuffled = recs[rng.permutation(1000)]                       # eviction order is not part of the result
+    bench.dump_outputs(str(tmp_path / "all"), "flows", shuffled.view(np.uint8))
+    words = np.load(tmp_path / "all" / "flows.npy")
+    assert words.dtype == np.float64 and words.shape == (1000, 36)
+    assert np.array_equal(words.astype(np.uint32).view(np.uint8).reshape(-1, 144), want)
+    assert np.array_equal(np.load(tmp_path / "all" / "flows_index.npy"), np.arange(1000))
+    assert np.load(tmp_path / "all" / "flows_count.npy").tolist() == [1000.0]
+    monkeypatch.setattr(bench, "DUMP_MAX_FLOWS", 256)
+    for d, src in (("s1", shuffled), ("s2", recs)):
+        bench.dump_outputs(str(tmp_path / d), "flows", src.view(np.uint8), parts=2)
+    idx = np.load(tmp_path / "s1" / "flows_index.npy")
+    assert len(idx) == 128 and np.array_equal(idx, np.load(tmp_path / "s2" / "flows_index.npy")) and np.all(np.diff(idx) > 0)
+    words = np.load(tmp_path / "s1" / "flows.npy")
+    assert np.array_equal(words, np.load(tmp_path / "s2" / "flows.npy"))
+    assert np.array_equal(words.astype(np.uint32).view(np.uint8).reshape(-1, 144), want[idx.astype(np.int64)])
+
+
 def test_bench_line_never_reports_a_fraction_above_one():
     """bench.py frac_of_a_real_bound: SURVEY 8(d)'s algorithmic bytes over the launch time are a model; where the model exceeds the
     peak the line's achieved / frac are those of a real bound (counter traffic if a fresh PMC file exists, else the stream floor)."""

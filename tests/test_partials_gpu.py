@@ -188,7 +188,8 @@ def test_bench_gpus_2_as_a_plain_process_rehearsed_on_one_gpu(nf):
     ranks itself. Rehearsed with both ranks on cuda:0 over gloo (RCCL refuses two ranks on one device); the workload must be
     configs[3]'s: one common stream, sketches all-reduced and flows exchanged inside the timed step."""
     n, keys = 600_000, 30_000
-    j = _bench("--gpus", "2", "--same-device", "--backend", "gloo", "--records", str(n), "--flows", str(keys), "--steps", "2", "--warmup", "1")
+    j = _bench("--gpus", "2", "--same-device", "--backend", "gloo", "--records", str(n), "--flows", str(keys), "--steps", "2", "--warmup", "1",
+               "--full")
     assert j["n_gpus"] == 2 and j["metric"].startswith("flow-records/s") and j["value"] > 0
     c = j["config"]
     assert "configs[3]" in c["workload"] and "local fold" in c["parallelism"] and "REHEARSAL" in c["parallelism"]
@@ -214,7 +215,7 @@ def test_bench_gpus_2_evictions_equal_one_accounter(nf, O, overlap, dedup, tmp_p
     n, keys = 500_000, 40_000
     dump = str(tmp_path / "ev")
     argv = ["--gpus", "2", "--same-device", "--backend", "gloo", "--records", str(n), "--flows", str(keys), "--steps", "3", "--warmup", "1",
-            "--dump-evictions", dump] + ([] if overlap else ["--no-overlap"]) + (["--dedup", "--hot-permille", "900"] if dedup else [])
+            "--dump-evictions", dump] + (["--full"] if overlap else ["--no-overlap"]) + (["--dedup", "--hot-permille", "900"] if dedup else [])
     j = _bench(*argv)
     assert j["config"]["windows_overlapped"] is overlap
     from netobserv_ebpf_agent_amd import synth
@@ -238,9 +239,27 @@ def test_bench_presharded_line_still_runs(nf):
     assert j["n_gpus"] == 2 and "key-hash shards x2" in j["config"]["parallelism"]
 
 
+def test_bench_n1_plain_line_and_its_dumped_outputs(nf, O, tmp_path):
+    """A plain N = 1 run: the headline and nothing that takes runs of its own, and --dump-outputs writes what its last timed step
+    evicted — all of the flows at this size — bit-identical to ONE oracle Accounter over the same seeded stream."""
+    import bench
+    n, keys = 3_000_000, 100_000
+    j = _bench("--gpus", "1", "--records", str(n), "--flows", str(keys), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert j["unit"] == "Mrecords/s" and j["higher_is_better"] is True and j["dtype"] == "u64"
+    assert "extra" not in j and "cpu_baseline" not in j and "hbm_copy_measured_GBs" not in j["roofline"]
+    from netobserv_ebpf_agent_amd import synth
+    whole = synth.stream_host(n, seed=2, n_keys=keys, thresholds=synth.zipf_thresholds(keys, 1.1))
+    want = O.run_accounter(whole, bench.DEFAULT_MAX_ENTRIES)[0][1]
+    words = np.load(tmp_path / "evicted_flows.npy")
+    assert words.dtype == np.float64 and len(want) == len(words) == j["config"]["evicted_flows_per_step"] <= bench.DUMP_MAX_FLOWS
+    assert np.load(tmp_path / "evicted_flows_count.npy").tolist() == [len(want)]
+    assert_records_equal(words.astype(np.uint32).view(nf.FLOW_RECORD).reshape(-1), want, "bench.py --dump-outputs vs ONE Accounter")
+
+
 def test_bench_n1_line_carries_the_extra_legs(nf):
-    """N = 1 default route at reduced size: roofline + cpu_baseline + the bounded extra legs in ONE line."""
-    j = _bench("--records", "3000000", "--flows", "100000", "--steps", "2", "--warmup", "1", "--cpu-sample", "500000")
+    """N = 1 default route at reduced size, --full: roofline + cpu_baseline + the bounded extra legs in ONE line."""
+    j = _bench("--records", "3000000", "--flows", "100000", "--steps", "2", "--warmup", "1", "--cpu-sample", "500000", "--full")
     assert j["n_gpus"] == 1 and j["roofline"]["frac"] > 0 and j["cpu_baseline"]["kind"] == "port"
     ex = j["extra"]
     assert "error" not in ex, ex

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r03d; mkdir -p $OUT
 timeout -k 5 300 python -m pytest tests/test_account_gpu.py -x -q -m gpu > $OUT/pytest.txt 2>&1
 echo "pytest rc $?"; tail -25 $OUT/pytest.txt
-timeout -k 5 200 python bench.py --steps 3 --warmup 1 --cpu-sample 0 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 5 200 python bench.py --full --steps 3 --warmup 1 --cpu-sample 0 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc $?"; python - <<'PY'
 import json
 j = json.load(open("gpurun_out/r03d/bench.json"))

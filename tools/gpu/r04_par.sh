@@ -7,7 +7,7 @@ timeout 200 python -m pytest tests/test_account_par_gpu.py tests/test_account_gp
 cat $O/tests.txt
 (cd /tmp && timeout 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o t -- python $GRAFT_REPO_ROOT/tools/account_5000_prof.py --steps 3 --variant 31 > $O/prof_run.json 2> $O/prof_err.txt)
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -16 "$f" | cut -c1-200 > $O/kernel_stats_head.csv; cat $O/kernel_stats_head.csv
-timeout 300 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc $?"
+timeout 300 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc $?"
 python - <<'PY'
 import json
 j=json.loads([l for l in open('gpurun_out/r04par/bench_n1.json') if l.startswith('{')][0])

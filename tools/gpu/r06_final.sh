@@ -15,7 +15,7 @@ timeout 1800 python -m pytest tests -q -m gpu --durations=12 > $O/pytest_gpu.txt
 echo "pytest rc $?" >> $O/pytest_gpu.txt
 grep -v amdgpu $O/pytest_gpu.txt | tail -20
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu | tail -2
-timeout 500 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+timeout 500 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 echo "bench rc $?"; python - <<'PY'
 import json
 j=json.loads([l for l in open('gpurun_out/r06z/bench_n1.json') if l.startswith('{')][0])

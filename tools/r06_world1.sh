@@ -4,7 +4,7 @@
 exec < /dev/null
 set -u
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/r06w1; mkdir -p $O; cd $R
-b() { name=$1; shift; timeout -k 5 400 python bench.py "$@" 2>$O/bench_$name.err | grep '^{' > $O/bench_$name.json; python -c "import json; j=json.load(open('$O/bench_$name.json')); print('$name', j['value'], j['ms_per_step'], j['roofline'].get('frac'), j['config'].get('exchange'))"; }
+b() { name=$1; shift; timeout -k 5 400 python bench.py --full "$@" 2>$O/bench_$name.err | grep '^{' > $O/bench_$name.json; python -c "import json; j=json.load(open('$O/bench_$name.json')); print('$name', j['value'], j['ms_per_step'], j['roofline'].get('frac'), j['config'].get('exchange'))"; }
 b world1_nccl_configs3_100m --gpus 1 --force-dist --backend nccl --records 100000000 --flows 1000000 --steps 5 --warmup 1
 b world1_nccl_configs3_100m_no_overlap --gpus 1 --force-dist --backend nccl --records 100000000 --flows 1000000 --steps 5 --warmup 1 --no-overlap
 b world1_nccl_configs4_100m --gpus 1 --force-dist --backend nccl --dedup --hot-permille 900 --records 100000000 --flows 1000000 --steps 5 --warmup 1
