@@ -721,6 +721,56 @@ int nfagg_encode_pb_content_device(nfagg_handle* h, const void* d_records, size_
                                    uint32_t* d_body_len, void* d_kafka_keys, size_t* out_bytes);
 
 /* ------------------------------------------------------------------ */
+/* IPFIX export — replaces, for evicted records, the IPFIX exporter     */
+/* (EXPORT=ipfix+udp / ipfix+tcp, pkg/exporter/ipfix.go) and go-ipfix's */
+/* message encoding: one IPFIX message (RFC 7011) per flow, holding one */
+/* data record of the v4 or v6 template of StartIPFIXExporter.          */
+/* ------------------------------------------------------------------ */
+
+typedef struct nfagg_ipfix_options {
+    uint32_t struct_size;        /* sizeof(nfagg_ipfix_options)                                   */
+    uint32_t n_names;
+    int64_t  now_unix_ns;        /* as nfagg_pb_options                                           */
+    uint64_t mono_now_ns;
+    const nfagg_intf_name* names;/* HOST memory: same table and lookup rule as nfagg_pb_options (the UDN is not used) */
+    char     unknown_name[16];   /* the namer's answer for an unknown interface                   */
+    uint8_t  unknown_len;
+    uint8_t  pad_[3];
+    uint32_t export_time_s;      /* message header Export Time: one value for every message of a call */
+    uint32_t seq0;               /* sequence number of message 0; message i carries seq0 + i (mod 2^32) */
+    uint32_t obs_domain_id;      /* Observation Domain ID: 1 in the reference (ipfix.go:229)      */
+    uint16_t template_id_v4;     /* 256 in the reference (NewTemplateID starts at 255)            */
+    uint16_t template_id_v6;     /* 257                                                           */
+} nfagg_ipfix_options;
+
+/* The template message StartIPFIXExporter sends (ipfix.go:220-262): 100 bytes,
+ * header (Export Time = export_time_s, Sequence Number = seq0: the number of
+ * data records sent so far, a template does not advance it), one template set
+ * (ID 2) with the 19 field specifiers of the v4 (v6 == 0) or v6 template, in
+ * ipfix.go's order. Host only: no handle, no device. Returns NFAGG_TRUNCATED
+ * with *n_out = 100 when cap is smaller (nothing written). */
+int nfagg_ipfix_template(const nfagg_ipfix_options* opt, int v6, void* out, size_t cap, size_t* n_out);
+
+/* Encode n evicted flow_record_t as n IPFIX messages, as IPFIX.ExportFlows
+ * sends them (ipfix.go:364-383): message i = out[msg_offsets[i],
+ * msg_offsets[i+1]), msg_offsets[n] = *out_bytes; each is one UDP datagram or
+ * one TCP write. Template v6 iff eth_protocol == 0x86DD; on v4 an address that
+ * is not v4-mapped is sent as 0.0.0.0 (model.IP.To4() == nil); times and the
+ * interface name as model.NewRecord derives them (record.go:82-106).
+ * One difference from the reference, by design: the reference reads the clock
+ * for every message's Export Time, here one export_time_s covers the whole
+ * call; the bytes are identical whenever the reference's messages of a batch
+ * fall within one second. Returns NFAGG_TRUNCATED with *out_bytes = bytes
+ * needed when out_cap is too small (nothing written). All pointers HOST memory: */
+int nfagg_encode_ipfix(nfagg_handle* h, const void* records, size_t n, const nfagg_ipfix_options* opt,
+                       void* out, size_t out_cap, uint64_t* msg_offsets, size_t* out_bytes);
+/* Same with d_records / d_out / d_msg_offsets in DEVICE memory (d_records and
+ * d_out 16-byte aligned), e.g. straight from nfagg_evict_device. d_out may be
+ * NULL to ask for the size. */
+int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_ipfix_options* opt,
+                              void* d_out, size_t out_cap, uint64_t* d_msg_offsets, size_t* out_bytes);
+
+/* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */
 /* ------------------------------------------------------------------ */
 

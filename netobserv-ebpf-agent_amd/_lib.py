@@ -62,6 +62,16 @@ class PbOptions(C.Structure):
     ]
 
 
+class IpfixOptions(C.Structure):
+    """nfagg_ipfix_options (include/nfagg.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_names", C.c_uint32), ("now_unix_ns", C.c_int64), ("mono_now_ns", C.c_uint64),
+        ("names", C.c_void_p), ("unknown_name", C.c_char * 16), ("unknown_len", C.c_uint8), ("pad_", C.c_uint8 * 3),
+        ("export_time_s", C.c_uint32), ("seq0", C.c_uint32), ("obs_domain_id", C.c_uint32),
+        ("template_id_v4", C.c_uint16), ("template_id_v6", C.c_uint16),
+    ]
+
+
 class MapView(C.Structure):
     """nfagg_map_view (include/nfagg.h)."""
     _fields_ = [("ids", C.c_void_p), ("values", C.c_void_p), ("n", C.c_size_t)]
@@ -141,6 +151,9 @@ SIGNATURES = {
     "nfagg_map_merge_device": (C.c_int, [_vp, C.POINTER(MapView), C.POINTER(MapView), _sz, C.POINTER(MergedFlows), _sz, _psz, _psz]),
     "nfagg_encode_pb_content": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), C.POINTER(PbOptions), _vp, _sz, _vp, _vp, _vp, _psz]),
     "nfagg_encode_pb_content_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), C.POINTER(PbOptions), _vp, _sz, _vp, _vp, _vp, _psz]),
+    "nfagg_ipfix_template": (C.c_int, [C.POINTER(IpfixOptions), C.c_int, _vp, _sz, _psz]),
+    "nfagg_encode_ipfix": (C.c_int, [_vp, _vp, _sz, C.POINTER(IpfixOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_encode_ipfix_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(IpfixOptions), _vp, _sz, _vp, _psz]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

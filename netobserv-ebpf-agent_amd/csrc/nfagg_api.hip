@@ -19,6 +19,7 @@
 #include "nfagg_internal.h"
 #include "nfagg_hostpool.h"
 #include "nfagg_pb.h"
+#include "nfagg_ipfix.h"
 
 using namespace nfagg;
 
@@ -84,6 +85,9 @@ struct nfagg_handle {
     std::vector<nfagg_intf_name> pb_names;   // host copy of the namer table, sorted (kept until the stream has consumed it)
     void* d_pb[15] = {};
     size_t d_pb_cap[15] = {};
+    // IPFIX encode scratch: name rows, local offsets, block sums, block bases, namer table, (host variant) records/out/offsets
+    void* d_ipfix[8] = {};
+    size_t d_ipfix_cap[8] = {};
     // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
     void* d_opt[4] = {};
     size_t d_opt_cap[4] = {};
@@ -858,6 +862,7 @@ void nfagg_destroy(nfagg_handle* h) {
     if (h->tv.spill.xp) hipFree(h->tv.spill.xp);
     for (int k = 0; k < 4; k++) if (h->d_opt[k]) hipFree(h->d_opt[k]);
     for (int k = 0; k < 15; k++) if (h->d_pb[k]) hipFree(h->d_pb[k]);
+    for (int k = 0; k < 8; k++) if (h->d_ipfix[k]) hipFree(h->d_ipfix[k]);
     for (int k = 0; k < 2; k++) if (h->d_sort[k]) hipFree(h->d_sort[k]);
     for (int k = 0; k < 7; k++) if (h->d_hh[k]) hipFree(h->d_hh[k]);
     for (int k = 0; k < 28; k++) if (h->d_mm[k]) hipFree(h->d_mm[k]);
@@ -2293,6 +2298,104 @@ int nfagg_encode_pb_content(nfagg_handle* h, const void* records, size_t n, cons
                             uint32_t* body_len, void* kafka_keys, size_t* out_bytes) {
     if (!features) return fail(h, NFAGG_EINVAL, "null features (use nfagg_encode_pb)");
     return encode_pb_host_core(h, records, n, features, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
+}
+
+// ---- record -> IPFIX (nfagg_ipfix.hip)
+static const uint16_t kIpfixTemplateV4[19][2] = {   // ipfix.go:89-135 + AddRecordValuesToTemplate; IDs and lengths: registry_IANA.go
+    {256, 2}, {61, 1}, {56, 6}, {80, 6}, {8, 4}, {12, 4}, {4, 1}, {7, 2}, {11, 2}, {176, 1}, {177, 1},
+    {1, 8}, {6, 2}, {150, 4}, {152, 8}, {151, 4}, {153, 8}, {2, 8}, {82, 65535}};
+static const uint16_t kIpfixTemplateV6[19][2] = {   // ipfix.go:158-204 + AddRecordValuesToTemplate
+    {256, 2}, {61, 1}, {56, 6}, {80, 6}, {27, 16}, {28, 16}, {193, 1}, {7, 2}, {11, 2}, {178, 1}, {179, 1},
+    {1, 8}, {6, 2}, {150, 4}, {152, 8}, {151, 4}, {153, 8}, {2, 8}, {82, 65535}};
+static constexpr size_t kIpfixTemplateBytes = 16 + 4 + 4 + 19 * 4;
+
+static void put_be16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 8); p[1] = (uint8_t)v; }
+static void put_be32(uint8_t* p, uint32_t v) { put_be16(p, v >> 16); put_be16(p + 2, v); }
+
+int nfagg_ipfix_template(const nfagg_ipfix_options* opt, int v6, void* out, size_t cap, size_t* n_out) {
+    if (!opt || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
+    if (opt->struct_size != sizeof(nfagg_ipfix_options)) return fail(nullptr, NFAGG_EINVAL, "nfagg_ipfix_options.struct_size mismatch");
+    *n_out = kIpfixTemplateBytes;
+    if (!out || cap < kIpfixTemplateBytes) return NFAGG_TRUNCATED;
+    uint8_t* p = (uint8_t*)out;
+    put_be16(p, 10); put_be16(p + 2, (uint32_t)kIpfixTemplateBytes); put_be32(p + 4, opt->export_time_s);
+    put_be32(p + 8, opt->seq0); put_be32(p + 12, opt->obs_domain_id);
+    put_be16(p + 16, 2); put_be16(p + 18, (uint32_t)kIpfixTemplateBytes - 16);                // template set
+    put_be16(p + 20, v6 ? opt->template_id_v6 : opt->template_id_v4); put_be16(p + 22, 19);  // template record header
+    const uint16_t (*f)[2] = v6 ? kIpfixTemplateV6 : kIpfixTemplateV4;
+    for (int k = 0; k < 19; k++) { put_be16(p + 24 + 4 * k, f[k][0]); put_be16(p + 26 + 4 * k, f[k][1]); }   // enterprise bit never set
+    return NFAGG_OK;
+}
+
+// The options are checked first, before the handle: a caller learns of a bad table without any device work.
+static int encode_ipfix_check(nfagg_handle* h, const nfagg_ipfix_options* opt) {
+    if (!opt) return fail(h, NFAGG_EINVAL, "null options");
+    if (opt->struct_size != sizeof(nfagg_ipfix_options)) return fail(h, NFAGG_EINVAL, "nfagg_ipfix_options.struct_size mismatch");
+    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");
+    for (uint32_t k = 0; k < opt->n_names; k++)
+        if (opt->names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
+    return NFAGG_OK;
+}
+
+int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_ipfix_options* opt,
+                              void* d_out, size_t out_cap, uint64_t* d_msg_offsets, size_t* out_bytes) {
+    int rc = encode_ipfix_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !out_bytes || !d_msg_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->device));
+    *out_bytes = 0;
+    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_msg_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
+    const size_t blocks = (n + 1023) / 1024;
+    if ((rc = ensure_bytes(h, &h->d_ipfix[0], &h->d_ipfix_cap[0], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_ipfix[1], &h->d_ipfix_cap[1], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_ipfix[2], &h->d_ipfix_cap[2], blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_ipfix[3], &h->d_ipfix_cap[3], (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_ipfix[4], &h->d_ipfix_cap[4], (size_t)(opt->n_names + 1) * sizeof(nfagg_intf_name))) != NFAGG_OK) return rc;
+    if (opt->n_names) {   // the kernels binary-search the table: stable sort by if_index keeps the scan-in-table-order answer
+        h->pb_names.assign(opt->names, opt->names + opt->n_names);
+        std::stable_sort(h->pb_names.begin(), h->pb_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
+        HIP_TRY(h, hipMemcpyAsync(h->d_ipfix[4], h->pb_names.data(), opt->n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
+    }
+    IpfixParams P{};
+    P.now_sec = opt->now_unix_ns / 1000000000ll; P.now_nsec = opt->now_unix_ns % 1000000000ll;
+    if (P.now_nsec < 0) { P.now_nsec += 1000000000ll; P.now_sec -= 1; }
+    P.mono_now = opt->mono_now_ns;
+    P.names = (const nfagg_intf_name*)h->d_ipfix[4]; P.n_names = opt->n_names;
+    P.unknown_len = opt->unknown_len; memcpy(P.unknown_w, opt->unknown_name, 16);
+    P.export_time = opt->export_time_s; P.seq0 = opt->seq0; P.obs_domain = opt->obs_domain_id;
+    P.tid_v4 = opt->template_id_v4; P.tid_v6 = opt->template_id_v6;
+    hipError_t e = launch_ipfix_size(d_records, n, P, (uint32_t*)h->d_ipfix[0], (uint32_t*)h->d_ipfix[1], (uint32_t*)h->d_ipfix[2],
+                                     (uint64_t*)h->d_ipfix[3], h->stream);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "IPFIX size launch failed: %s", hipGetErrorString(e));
+    uint64_t total = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)h->d_ipfix[3] + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *out_bytes = (size_t)total;
+    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
+    e = launch_ipfix_write(d_records, n, P, (const uint32_t*)h->d_ipfix[0], (const uint32_t*)h->d_ipfix[1], (const uint64_t*)h->d_ipfix[3],
+                           d_out, d_msg_offsets, h->stream);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "IPFIX write launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+int nfagg_encode_ipfix(nfagg_handle* h, const void* records, size_t n, const nfagg_ipfix_options* opt,
+                       void* out, size_t out_cap, uint64_t* msg_offsets, size_t* out_bytes) {
+    int rc = encode_ipfix_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !out_bytes || !msg_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = ensure_bytes(h, &h->d_ipfix[5], &h->d_ipfix_cap[5], n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_ipfix[6], &h->d_ipfix_cap[6], out_cap + 32)) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_ipfix[7], &h->d_ipfix_cap[7], (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_ipfix[5], records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+    rc = nfagg_encode_ipfix_device(h, h->d_ipfix[5], n, opt, out ? h->d_ipfix[6] : nullptr, out_cap, (uint64_t*)h->d_ipfix[7], out_bytes);
+    if (rc != NFAGG_OK) return rc;
+    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, h->d_ipfix[6], *out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(msg_offsets, h->d_ipfix[7], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
 }
 
 #ifdef NFAGG_DIAG

@@ -1,0 +1,88 @@
+// nfagg_encode.h — device pieces the export encoders share (nfagg_pb.hip: protobuf, nfagg_ipfix.hip: IPFIX):
+// byte sinks, the flow's wall-clock time, the interface-namer lookup and its LDS staging, address words.
+#pragma once
+#include "nfagg_device.h"
+
+namespace nfagg {
+
+// ---- byte sinks: one counts, one writes (LDS or global bytes)
+struct CountSink {
+    uint32_t n = 0;
+    NF_DEV void put(uint8_t) { n++; }
+};
+// Writes only the bytes whose position (relative to the wave's LDS image) falls into [lo, lo + len):
+// a frame that straddles two windows is encoded once per window.
+struct WindowSink {
+    uint8_t* lds;      // window base
+    uint32_t pos;      // position of the next byte in the wave image
+    uint32_t lo, len;
+    NF_DEV void put(uint8_t b) { const uint32_t k = pos - lo; if (k < len) lds[k] = b; pos++; }
+};
+
+// A 16-byte address as four little-endian dwords in registers, never as a byte pointer: a byte loop over global
+// memory is one exposed load latency per byte.
+struct Ip4w { uint32_t w[4]; };
+NF_DEV uint8_t ip_byte(const Ip4w& a, int k) { return (uint8_t)(a.w[k >> 2] >> (8 * (k & 3))); }
+
+// currentTime.Add(-Duration(mono_now - ts)) (record.go:90-97) as time.Time's (sec, nsec), 0 <= nsec < 1e9.
+// now_sec / now_nsec: currentTime, normalised.
+struct TimeParts { int64_t sec, nsec; };
+NF_DEV TimeParts flow_time(int64_t now_sec, int64_t now_nsec, uint64_t mono_now, uint64_t ts) {
+    const int64_t delta = (int64_t)(mono_now - ts);
+    const int64_t d = (int64_t)(0ull - (uint64_t)delta);
+    int64_t dsec = d / 1000000000ll, nsec = now_nsec + d % 1000000000ll;   // time.Time.Add
+    if (nsec >= 1000000000ll) { dsec++; nsec -= 1000000000ll; } else if (nsec < 0) { dsec--; nsec += 1000000000ll; }
+    return TimeParts{now_sec + dsec, nsec};
+}
+
+// interfaceNamer(ifIndex, mac) + udnsCache lookup, as a table: exact (index, MAC) row first,
+// then the first row of that index that matches any MAC; no row -> the "unknown" name, no UDN. The host hands the
+// table over STABLY SORTED by if_index (rows of one index keep their order, so the answer is that of a scan in table
+// order): binary search for the first row of the index, then only that index's rows. `tab` is a flat pointer: the
+// kernels stage the table in LDS when it fits (kNamesLdsRows rows), so a lookup costs LDS latencies, not HBM ones.
+// Row layout (nfagg_intf_name, 92 bytes): if_index@0 mac@4 has_mac@10 name_len@11 name@12 udn_len@28 udn@29.
+constexpr uint32_t kNameRowBytes = sizeof(nfagg_intf_name);
+constexpr uint32_t kNamesLdsRows = 96;
+static_assert(kNameRowBytes == 92 && kNameRowBytes % 4 == 0, "nfagg_intf_name layout");
+NF_DEV const uint8_t* lookup_name(const uint8_t* tab, uint32_t n_names, uint32_t if_index, uint64_t mac48) {
+    uint32_t lo = 0, hi = n_names;
+    while (lo < hi) {                                   // first row with if_index >= the one looked for
+        const uint32_t mid = (lo + hi) >> 1;
+        if (*reinterpret_cast<const uint32_t*>(tab + (size_t)mid * kNameRowBytes) < if_index) lo = mid + 1; else hi = mid;
+    }
+    const uint8_t* any = nullptr;
+    for (uint32_t k = lo; k < n_names; k++) {
+        const uint8_t* e = tab + (size_t)k * kNameRowBytes;
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(e);
+        const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
+        if (w0 != if_index) break;
+        if ((w2 >> 16) & 0xffu) {                       // has_mac: mac bytes 4..9, byte 4 most significant
+            const uint64_t m = ((uint64_t)__builtin_bswap32(w1) << 16) | (uint64_t)((w2 & 0xffu) << 8) | (uint64_t)((w2 >> 8) & 0xffu);
+            if (m == mac48) return e;
+        } else if (!any) any = e;
+    }
+    return any;
+}
+
+// Copy the namer table (device memory, n_names rows) into LDS if it fits; returns the pointer the lookups use.
+template <int THREADS>
+NF_DEV const uint8_t* stage_names(const nfagg_intf_name* names, uint32_t n_names, uint32_t* lds_words) {
+    if (n_names > kNamesLdsRows) return reinterpret_cast<const uint8_t*>(names);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(names);
+    const uint32_t words = n_names * (kNameRowBytes / 4);
+    for (uint32_t k = threadIdx.x; k < words; k += THREADS) lds_words[k] = src[k];
+    __syncthreads();
+    return reinterpret_cast<const uint8_t*>(lds_words);
+}
+
+NF_DEV uint64_t mac_be(uint64_t mac_le48) {   // Rec::smac() holds byte 0 in the low bits; macToUint64 (proto.go:246-253) wants it on top
+    uint64_t v = 0;
+    for (int b = 0; b < 6; b++) v = (v << 8) | ((mac_le48 >> (8 * b)) & 0xff);
+    return v;
+}
+
+// Both encoders' size kernels run kScanBlock records per workgroup and scan the message lengths inside it; the
+// block sums go through launch_scan_block_sums (nfagg_internal.h).
+constexpr int kScanBlock = 1024;
+
+}  // namespace nfagg

@@ -21,24 +21,10 @@
 // encodes its 64 records into LDS at their final relative byte positions (consecutive records are
 // contiguous in the output), one 16 KiB window of the output at a time, and copies each window out
 // with aligned 16-byte stores.
-#include "nfagg_device.h"
+#include "nfagg_encode.h"
 #include "nfagg_pb.h"
 
 namespace nfagg {
-
-// ---- byte sinks: one counts, one writes (LDS or global bytes)
-struct CountSink {
-    uint32_t n = 0;
-    NF_DEV void put(uint8_t) { n++; }
-};
-// Writes only the bytes whose position (relative to the wave's LDS image) falls into [lo, lo + len):
-// a frame that straddles two windows is encoded once per window.
-struct WindowSink {
-    uint8_t* lds;      // window base
-    uint32_t pos;      // position of the next byte in the wave image
-    uint32_t lo, len;
-    NF_DEV void put(uint8_t b) { const uint32_t k = pos - lo; if (k < len) lds[k] = b; pos++; }
-};
 
 NF_DEV uint32_t varint_len(uint64_t v) {
     uint32_t n = 1;
@@ -54,10 +40,7 @@ template <typename S> NF_DEV void put_uint(S& s, uint32_t field, uint64_t v) { i
 NF_DEV uint32_t uint_len(uint32_t field, uint64_t v) { return v ? varint_len((uint64_t)field << 3) + varint_len(v) : 0; }
 
 // message IP { oneof { fixed32 ipv4 = 1; bytes ipv6 = 2; } } as a sub-message of `field`
-// The address travels as four little-endian dwords in registers, never as a byte pointer: a byte loop over global
-// memory is one exposed load latency per byte.
-struct Ip4w { uint32_t w[4]; };
-NF_DEV uint8_t ip_byte(const Ip4w& a, int k) { return (uint8_t)(a.w[k >> 2] >> (8 * (k & 3))); }
+// The address travels as an Ip4w (nfagg_encode.h).
 template <typename S> NF_DEV void put_ip(S& s, uint32_t field, const Ip4w& ip, bool v6) {
     put_tag(s, field, 2);
     if (v6) {
@@ -70,60 +53,12 @@ template <typename S> NF_DEV void put_ip(S& s, uint32_t field, const Ip4w& ip, b
     }
 }
 
-// google.protobuf.Timestamp of currentTime.Add(-Duration(mono_now - ts)) (record.go:90-97, proto.go:61-68)
-struct TimeParts { int64_t sec, nsec; };
-NF_DEV TimeParts flow_time(const PbParams& P, uint64_t ts) {
-    const int64_t delta = (int64_t)(P.mono_now - ts);
-    const int64_t d = (int64_t)(0ull - (uint64_t)delta);
-    int64_t dsec = d / 1000000000ll, nsec = P.now_nsec + d % 1000000000ll;   // time.Time.Add
-    if (nsec >= 1000000000ll) { dsec++; nsec -= 1000000000ll; } else if (nsec < 0) { dsec--; nsec += 1000000000ll; }
-    return TimeParts{P.now_sec + dsec, nsec};
-}
+// google.protobuf.Timestamp of flow_time (record.go:90-97, proto.go:61-68)
 template <typename S> NF_DEV void put_time(S& s, uint32_t field, const TimeParts& t) {
     put_tag(s, field, 2);
     s.put((uint8_t)(uint_len(1, (uint64_t)t.sec) + uint_len(2, (uint64_t)t.nsec)));
     put_uint(s, 1, (uint64_t)t.sec);      // int64: a negative value takes ten bytes
     put_uint(s, 2, (uint64_t)t.nsec);
-}
-
-// interfaceNamer(ifIndex, mac) + udnsCache lookup, as a table: exact (index, MAC) row first,
-// then the first row of that index that matches any MAC; no row -> the "unknown" name, no UDN. The host hands the
-// table over STABLY SORTED by if_index (rows of one index keep their order, so the answer is that of a scan in table
-// order): binary search for the first row of the index, then only that index's rows. `tab` is a flat pointer: the
-// kernels stage the table in LDS when it fits (kNamesLdsRows rows), so a lookup costs LDS latencies, not HBM ones.
-// Row layout (nfagg_intf_name, 92 bytes): if_index@0 mac@4 has_mac@10 name_len@11 name@12 udn_len@28 udn@29.
-constexpr uint32_t kNameRowBytes = sizeof(nfagg_intf_name);
-constexpr uint32_t kNamesLdsRows = 96;
-static_assert(kNameRowBytes == 92 && kNameRowBytes % 4 == 0, "nfagg_intf_name layout");
-NF_DEV const uint8_t* lookup_name(const uint8_t* tab, uint32_t n_names, uint32_t if_index, uint64_t mac48) {
-    uint32_t lo = 0, hi = n_names;
-    while (lo < hi) {                                   // first row with if_index >= the one looked for
-        const uint32_t mid = (lo + hi) >> 1;
-        if (*reinterpret_cast<const uint32_t*>(tab + (size_t)mid * kNameRowBytes) < if_index) lo = mid + 1; else hi = mid;
-    }
-    const uint8_t* any = nullptr;
-    for (uint32_t k = lo; k < n_names; k++) {
-        const uint8_t* e = tab + (size_t)k * kNameRowBytes;
-        const uint32_t* p = reinterpret_cast<const uint32_t*>(e);
-        const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
-        if (w0 != if_index) break;
-        if ((w2 >> 16) & 0xffu) {                       // has_mac: mac bytes 4..9, byte 4 most significant
-            const uint64_t m = ((uint64_t)__builtin_bswap32(w1) << 16) | (uint64_t)((w2 & 0xffu) << 8) | (uint64_t)((w2 >> 8) & 0xffu);
-            if (m == mac48) return e;
-        } else if (!any) any = e;
-    }
-    return any;
-}
-
-// Copy the namer table into LDS if it fits; returns the pointer the lookups use.
-template <int THREADS>
-NF_DEV const uint8_t* stage_names(const PbParams& P, uint32_t* lds_words) {
-    if (P.n_names > kNamesLdsRows) return reinterpret_cast<const uint8_t*>(P.names);
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(P.names);
-    const uint32_t words = P.n_names * (kNameRowBytes / 4);
-    for (uint32_t k = threadIdx.x; k < words; k += THREADS) lds_words[k] = src[k];
-    __syncthreads();
-    return reinterpret_cast<const uint8_t*>(lds_words);
 }
 
 // message DupMapEntry { string interface = 1; Direction direction = 2; string udn = 3; } as Record.dup_list (26)
@@ -142,12 +77,6 @@ template <typename S> NF_DEV void put_dup(S& s, const PbParams& P, const uint8_t
     }
     put_uint(s, 2, dir);
     if (ulen) { s.put(0x1A); s.put((uint8_t)ulen); for (uint32_t k = 0; k < ulen; k++) s.put(e[29 + k]); }
-}
-
-NF_DEV uint64_t mac_be(uint64_t mac_le48) {   // Rec::smac() holds byte 0 in the low bits; macToUint64 (proto.go:246-253) wants it on top
-    uint64_t v = 0;
-    for (int b = 0; b < 6; b++) v = (v << 8) | ((mac_le48 >> (8 * b)) & 0xff);
-    return v;
 }
 
 // google.protobuf.Duration = durationpb.New(time.Duration(d)): secs = d / 1e9 truncating, nanos = d - secs*1e9,
@@ -212,8 +141,8 @@ template <typename S> NF_DEV void encode_record(S& s, const Rec& r, const PbPara
     const uint32_t dirn = r.d[24] & 0xffu;
     put_uint(s, 1, eth);
     put_uint(s, 2, dirn);
-    put_time(s, 3, flow_time(P, r.start()));
-    put_time(s, 4, flow_time(P, r.end()));
+    put_time(s, 3, flow_time(P.now_sec, P.now_nsec, P.mono_now, r.start()));
+    put_time(s, 4, flow_time(P.now_sec, P.now_nsec, P.mono_now, r.end()));
     const uint64_t smac = mac_be(r.smac()), dmac = mac_be(r.dmac());
     put_tag(s, 5, 2); s.put((uint8_t)(uint_len(1, smac) + uint_len(2, dmac)));
     put_uint(s, 1, smac); put_uint(s, 2, dmac);
@@ -294,8 +223,6 @@ template <typename S> NF_DEV void encode_record(S& s, const Rec& r, const PbPara
     }
 }
 
-constexpr int kScanBlock = 1024;
-
 // ---- kernel 1: body length per record, frame length, block-local exclusive scan of the frame lengths
 __global__ __launch_bounds__(kScanBlock) void k_pb_size(const void* __restrict__ recs, uint64_t n, PbParams P, PbFeat F,
                                                         uint32_t* __restrict__ body_len, uint32_t* __restrict__ local_off,
@@ -303,7 +230,7 @@ __global__ __launch_bounds__(kScanBlock) void k_pb_size(const void* __restrict__
     __shared__ uint32_t wave_tot[kScanBlock / 64];
     __shared__ __align__(4) uint8_t name_lds[kScanBlock][32];
     __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
-    const uint8_t* tab = stage_names<kScanBlock>(P, tab_lds);
+    const uint8_t* tab = stage_names<kScanBlock>(P.names, P.n_names, tab_lds);
     const uint64_t i = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x;
     uint32_t frame = 0;
     if (i < n) {
@@ -358,7 +285,7 @@ __global__ __launch_bounds__(64) void k_pb_write(const void* __restrict__ recs, 
     __shared__ __align__(16) unsigned char lds[kPbWindow];
     __shared__ __align__(4) uint8_t name_lds[64][32];
     __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
-    const uint8_t* tab = stage_names<64>(P, tab_lds);
+    const uint8_t* tab = stage_names<64>(P.names, P.n_names, tab_lds);
     const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
     const uint64_t wave_base = block_base[i0 / kScanBlock] + local_off[i0];
     const uint32_t shift = (uint32_t)(wave_base & 15);       // the LDS image has the alignment of the destination

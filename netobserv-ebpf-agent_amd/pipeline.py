@@ -6,6 +6,7 @@ BASELINE configs[0] ("10k flow_record_t, 1k 5-tuples, Accounter via direct-flp s
                                       record (what the Accounter evicts) produces
   DirectFLPStdout.ExportFlows(in)     pkg/exporter/direct_flp.go + flowlogs-pipeline write_stdout.go:37-51
                                       with `format: json` (one JSON object per flow, keys sorted)
+  IPFIX / StartIPFIXExporter          pkg/exporter/ipfix.go over the GPU encoder (nfagg_encode_ipfix)
 
 Plumbing only — no flow state is touched here; the records come from libnfagg (accounter.py). The
 string tables of the feature branch (TCP states, drop causes, DNS rcodes, TLS names) stay with the Go
@@ -15,8 +16,13 @@ import json
 import queue
 import sys
 import time
+from typing import Callable
+
+import numpy as np
 
 from .accounter import CLOSE, Record
+from .records import INTF_NAME
+from .table import IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6, ipfix_template
 
 
 class CapacityLimiter:                                    # limiter.go:19-26
@@ -208,3 +214,76 @@ def FlowsToPBMessages(buf, frame_offsets, max_len: int):
     n = len(frame_offsets) - 1
     raw = memoryview(np.ascontiguousarray(buf))
     return [raw[int(frame_offsets[a]):int(frame_offsets[min(a + max_len, n)])] for a in range(0, n, max_len)]
+
+
+class IPFIX:                                              # pkg/exporter/ipfix.go:33-42
+    """The IPFIX exporter (EXPORT=ipfix+udp / ipfix+tcp) over the GPU encoder (FlowTable.encode_ipfix): evicted records go
+    straight to IPFIX messages, no Record per flow. `send(message)` writes one message: one UDP datagram or one TCP write
+    (the `send` of a socket the caller has connected; nothing here opens a socket). The state is go-ipfix's exporting
+    process: seqNumber counts the data records sent (process.go:504-506), templates do not advance it.
+
+    Differences from the reference, both by design: one Export Time per encode call (nfagg_encode_ipfix), and the UDP
+    template refresh (every TempRefTimeout = 1 s, process.go:284-321) is sent in a fixed order, v4 then v6, before the
+    first data message that finds 1 s or more passed since the last template send — the reference's ticker sends them in
+    Go map order (random) from its own goroutine."""
+    TEMPLATE_REFRESH_NS = 1_000_000_000
+
+    def __init__(self, table, send: Callable, transport: str = "udp", names=None, unknown: bytes = b"unknown",
+                 clock: Callable[[], int] = None, mono_clock: Callable[[], int] = None, obs_domain_id: int = 1, encode=None):
+        if transport not in ("udp", "tcp"):
+            raise ValueError("transport is 'udp' or 'tcp'")
+        self.table, self.send, self.transport = table, send, transport
+        self.names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
+        self.unknown, self.obsDomainID = unknown, obs_domain_id
+        self.clock = clock or time.time_ns                # () -> unix ns (time.Now())
+        self.monoClock = mono_clock or time.monotonic_ns  # () -> monotonic ns
+        self.templateIDv4, self.templateIDv6 = IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6
+        self.seqNumber = 0
+        self.templatesSentAt = None
+        # encode(raw, now_ns, mono_ns, names, export_time_s, seq0, unknown, obs_domain_id) -> (buf, msg_offsets)
+        self._encode = encode or table.encode_ipfix
+
+    def _export_time(self) -> int:                        # time.Now().Unix() as the message header's uint32
+        return (self.clock() // 1_000_000_000) & 0xFFFFFFFF
+
+    def sendTemplates(self):                              # SendTemplateRecordv4, SendTemplateRecordv6 (ipfix.go:240-251)
+        self.templatesSentAt = self.clock()
+        t = (self.templatesSentAt // 1_000_000_000) & 0xFFFFFFFF
+        for v6 in (False, True):
+            self.send(ipfix_template(v6, t, self.seqNumber, self.obsDomainID, (self.templateIDv4, self.templateIDv6)))
+
+    def ExportEvicted(self, raw, now_ns: int, mono_ns: int) -> int:
+        """sendDataRecord for every evicted record of one eviction (ipfix.go:364-383): encoded on the GPU, one message per flow.
+        now_ns / mono_ns: the eviction's currentTime / monotonicCurrentTime (account.go:103-104). Returns the messages sent."""
+        n = len(raw)
+        if n == 0:
+            return 0
+        self._refresh()
+        buf, off = self._encode(raw, now_ns, mono_ns & ((1 << 64) - 1), self.names, self._export_time(), self.seqNumber,
+                                self.unknown, self.obsDomainID)
+        raw_buf = memoryview(np.ascontiguousarray(buf))
+        for i in range(n):
+            if i:
+                self._refresh()
+            self.send(raw_buf[int(off[i]):int(off[i + 1])])
+            self.seqNumber = (self.seqNumber + 1) & 0xFFFFFFFF
+        return n
+
+    def _refresh(self):
+        if self.transport == "udp" and self.clock() - self.templatesSentAt >= self.TEMPLATE_REFRESH_NS:
+            self.sendTemplates()
+
+    def ExportFlows(self, inp: "queue.Queue"):            # ipfix.go:364-383: items (raw records, now_ns, mono_ns) until CLOSE
+        while True:
+            item = inp.get()
+            if item is CLOSE:
+                return
+            raw, now_ns, mono_ns = item
+            self.ExportEvicted(raw, now_ns, mono_ns)
+
+
+def StartIPFIXExporter(table, send: Callable, transport: str = "udp", names=None, clock=None, mono_clock=None, **kw) -> IPFIX:
+    """ipfix.go:220-262: the exporter, after it has sent the v4 template, then the v6 one."""
+    ipf = IPFIX(table, send, transport, names=names, clock=clock, mono_clock=mono_clock, **kw)
+    ipf.sendTemplates()
+    return ipf

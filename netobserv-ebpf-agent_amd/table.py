@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .records import FLOW_RECORD, ROLLUP_KINDS, FLOW_METRICS
+from .records import FLOW_RECORD, ROLLUP_KINDS, FLOW_METRICS, INTF_NAME
 
 
 class NfaggError(RuntimeError):
@@ -409,6 +409,39 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, need.value
 
+    # -- export encode (record -> IPFIX messages), nfagg_encode_ipfix
+    def encode_ipfix(self, records: np.ndarray, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, export_time_s: int,
+                     seq0: int, unknown: bytes = b"unknown", obs_domain_id: int = 1):
+        """IPFIX.ExportFlows' messages for evicted records, encoded on the GPU (one message per flow, template v6 iff
+        eth_protocol == 0x86DD). Returns (buf, msg_offsets): message i is buf[msg_offsets[i]:msg_offsets[i + 1]] and
+        carries sequence number seq0 + i (mod 2**32); every message has Export Time export_time_s."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        o, keep = ipfix_options(now_unix_ns, mono_now_ns, names, export_time_s, seq0, unknown, obs_domain_id)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        need = C.c_size_t(0)
+        cap = max(120 * n, 64)
+        while True:
+            buf = np.zeros(cap, dtype=np.uint8)
+            rc = L.lib.nfagg_encode_ipfix(self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(o), buf.ctypes.data_as(C.c_void_p), cap,
+                                          off.ctypes.data_as(C.c_void_p), C.byref(need))
+            if rc == L.TRUNCATED:
+                cap = need.value
+                continue
+            self._check(rc)
+            break
+        return buf[: need.value], off
+
+    def encode_ipfix_device(self, d_records: int, n: int, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, export_time_s: int,
+                            seq0: int, d_out: int, out_cap: int, d_msg_offsets: int, unknown: bytes = b"unknown", obs_domain_id: int = 1):
+        """Device-resident variant (raw device pointers; d_out = 0 asks for the size). Returns (rc, bytes needed/written)."""
+        o, keep = ipfix_options(now_unix_ns, mono_now_ns, names, export_time_s, seq0, unknown, obs_domain_id)
+        need = C.c_size_t(0)
+        rc = L.lib.nfagg_encode_ipfix_device(self._h, C.c_void_p(d_records), n, C.byref(o), C.c_void_p(d_out or None), out_cap,
+                                             C.c_void_p(d_msg_offsets), C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -567,6 +600,36 @@ class FlowGroup:
             raise NfaggError(rc, "device buffers too small, needed %s" % [int(x) for x in n])
         self._check(rc)
         return [int(x) for x in n]
+
+
+IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6 = 256, 257      # go-ipfix NewTemplateID() from 255: v4 is created first
+
+
+def ipfix_options(now_unix_ns=0, mono_now_ns=0, names=None, export_time_s=0, seq0=0, unknown=b"unknown", obs_domain_id=1,
+                  template_ids=(IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6)):
+    """nfagg_ipfix_options; returns (options, the names array the options point into: keep it alive for the call)."""
+    o = L.IpfixOptions()
+    o.struct_size = C.sizeof(L.IpfixOptions)
+    o.now_unix_ns, o.mono_now_ns = now_unix_ns, mono_now_ns
+    names = np.ascontiguousarray(names if names is not None else np.zeros(0, dtype=INTF_NAME))
+    o.names, o.n_names = (names.ctypes.data if len(names) else None), len(names)
+    o.unknown_name, o.unknown_len = unknown, len(unknown)
+    o.export_time_s, o.seq0, o.obs_domain_id = export_time_s & 0xFFFFFFFF, seq0 & 0xFFFFFFFF, obs_domain_id
+    o.template_id_v4, o.template_id_v6 = template_ids
+    return o, names
+
+
+def ipfix_template(v6: bool, export_time_s: int, seq: int, obs_domain_id: int = 1,
+                   template_ids=(IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6)) -> bytes:
+    """nfagg_ipfix_template: the 100-byte template message StartIPFIXExporter sends for the v4 or v6 template, with
+    Export Time export_time_s and Sequence Number seq (the data records sent so far)."""
+    o, _ = ipfix_options(export_time_s=export_time_s, seq0=seq, obs_domain_id=obs_domain_id, template_ids=template_ids)
+    buf = (C.c_uint8 * 128)()
+    n = C.c_size_t(0)
+    rc = L.lib.nfagg_ipfix_template(C.byref(o), 1 if v6 else 0, buf, len(buf), C.byref(n))
+    if rc != L.OK:
+        raise NfaggError(rc, "nfagg_ipfix_template")
+    return bytes(buf[: n.value])
 
 
 def key_hash(flow_id_bytes: bytes) -> int:

@@ -1,0 +1,271 @@
+"""Record -> IPFIX messages on the GPU (csrc/nfagg_ipfix.hip) through the C ABI: byte parity with the restatement of
+tests/ipfix_ref.py on seeded streams (v4, v6, v4-template flows with addresses that are not v4-mapped, every namer-table
+case), the LDS staging limit of the namer table, truncation, chained calls, the device-resident path, the decoded fields
+against the product's host mirror of model.NewRecord, the exporter over a local datagram socket pair, and 1 M flows."""
+import ctypes as C
+import os
+import socket
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ipfix_ref as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+# as test_pb_gpu.NAMES: NOT sorted by index, several rows per index, MAC-specific rows, an empty name
+NAMES = [(8, None, "x" * 16, "u" * 63), (3, bytes.fromhex("020000000001"), "veth3a", "udn-blue"), (1, None, "lo", ""),
+         (3, None, "veth3", ""), (2, None, "eth0", "default"), (3, None, "veth3-second-any", "never"),
+         (3, bytes.fromhex("aabbccddeeff"), "veth3b", "udn-late"), (4, None, "ovn-k8s-mp0", "t"), (6, None, "", "nameless"),
+         (2, bytes.fromhex("020000000002"), "eth0-mac", "")]
+NOW, MONO = 1_700_000_000_123_456_789, 2_500_000
+EXPORT = 1_700_000_000
+
+
+def rows(names):
+    return [(i, m, n.encode()) for (i, m, n, _) in names]
+
+
+def stream(nf, O, n, seed):
+    """Scrambled records (variant 1: interfaces 1..8, both directions, zero and non-zero times); every 5th is IPv6,
+    every 7th an eth 0x0800 flow whose addresses are not v4-mapped (the v4 template sends 0.0.0.0)."""
+    if n == 0:
+        return np.zeros(0, dtype=nf.FLOW_RECORD)
+    recs = O.gen_stream(n, seed=seed, n_keys=997, variant=1).view(nf.FLOW_RECORD)
+    m, ids = recs["metrics"], recs["id"]
+    m["eth_protocol"][::5] = 0x86DD
+    m["eth_protocol"][3::7] = 0x0800
+    ids["src_ip"][3::7, 0] = 0x20
+    ids["dst_ip"][3::7, 10] = 0x12
+    return recs
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 1023, 1025, 50_000])
+def test_stream_parity_with_restatement(nf, O, n):
+    recs = stream(nf, O, n, seed=n + 1)
+    want, want_off = R.encode(recs, NOW, MONO, rows(NAMES), EXPORT, 0xFFFFFF00 + n)
+    with nf.FlowTable(max_entries=64) as tab:
+        buf, off = tab.encode_ipfix(recs, NOW, MONO, nf.intf_table(NAMES), EXPORT, 0xFFFFFF00 + n)
+    assert off.tolist() == want_off.tolist()
+    assert buf.tobytes() == want
+
+
+def test_namer_table_larger_than_lds(nf, O):
+    """More rows than the size kernel stages in LDS (96): the lookups go to the table in HBM, same bytes."""
+    names = [(1000 + k, None, "if%d" % k, "") for k in range(150)] + NAMES
+    recs = stream(nf, O, 3000, seed=8)
+    recs["metrics"]["if_index_first_seen"][::2] = 1000 + (np.arange(1500) % 150)
+    recs["metrics"]["src_mac"][::3] = np.frombuffer(bytes.fromhex("aabbccddeeff"), dtype=np.uint8)
+    recs["metrics"]["dst_mac"][::3] = np.frombuffer(bytes.fromhex("020000000002"), dtype=np.uint8)
+    want, _ = R.encode(recs, NOW, MONO, rows(names), EXPORT, 9, unknown=b"?")
+    with nf.FlowTable(max_entries=64) as tab:
+        buf, _ = tab.encode_ipfix(recs, NOW, MONO, nf.intf_table(names), EXPORT, 9, unknown=b"?")
+        few, _ = tab.encode_ipfix(recs, NOW, MONO, nf.intf_table(names[140:]), EXPORT, 9, unknown=b"?")
+    assert buf.tobytes() == want
+    assert few.tobytes() == R.encode(recs, NOW, MONO, rows(names[140:]), EXPORT, 9, unknown=b"?")[0]
+
+
+def test_truncated_then_written(nf, O):
+    import torch
+    recs = stream(nf, O, 300, seed=3)
+    names = nf.intf_table(NAMES)
+    want, want_off = R.encode(recs, NOW, MONO, rows(NAMES), EXPORT, 5)
+    with nf.FlowTable(max_entries=64) as tab:
+        # host entry point
+        o, keep = nf.ipfix_options(NOW, MONO, names, EXPORT, 5)
+        need = C.c_size_t(0)
+        small = np.full(len(want) - 1, 0xAB, dtype=np.uint8)
+        off = np.zeros(301, dtype=np.uint64)
+        rc = nf._lib.lib.nfagg_encode_ipfix(tab._h, recs.ctypes.data_as(C.c_void_p), 300, C.byref(o), small.ctypes.data_as(C.c_void_p),
+                                            len(small), off.ctypes.data_as(C.c_void_p), C.byref(need))
+        assert rc == nf.TRUNCATED and need.value == len(want) and (small == 0xAB).all() and not off.any()
+        # device entry point: the first call says how much, writes nothing; the second writes it
+        d_recs = torch.from_numpy(recs.view(np.uint8).copy()).cuda()
+        d_out = torch.full((len(want) + 64,), 0xAB, dtype=torch.uint8, device="cuda")
+        d_off = torch.zeros(301, dtype=torch.int64, device="cuda")
+        rc, got = tab.encode_ipfix_device(d_recs.data_ptr(), 300, NOW, MONO, names, EXPORT, 5, d_out.data_ptr(), len(want) - 1, d_off.data_ptr())
+        torch.cuda.synchronize()
+        assert rc == nf.TRUNCATED and got == len(want)
+        assert (d_out.cpu().numpy() == 0xAB).all() and not d_off.cpu().numpy().any()
+        rc, got = tab.encode_ipfix_device(d_recs.data_ptr(), 300, NOW, MONO, names, EXPORT, 5, d_out.data_ptr(), len(want), d_off.data_ptr())
+        torch.cuda.synchronize()
+        assert rc == nf.OK and got == len(want)
+        out = d_out.cpu().numpy()
+        assert out[: len(want)].tobytes() == want and (out[len(want):] == 0xAB).all()
+        assert d_off.cpu().numpy().astype(np.uint64).tolist() == want_off.tolist()
+
+
+def test_chained_calls_equal_one_call(nf, O):
+    recs = stream(nf, O, 5000, seed=4)
+    names = nf.intf_table(NAMES)
+    with nf.FlowTable(max_entries=64) as tab:
+        whole, _ = tab.encode_ipfix(recs, NOW, MONO, names, EXPORT, 0xFFFFF000)
+        a, _ = tab.encode_ipfix(recs[:3333], NOW, MONO, names, EXPORT, 0xFFFFF000)
+        b, _ = tab.encode_ipfix(recs[3333:], NOW, MONO, names, EXPORT, (0xFFFFF000 + 3333) & 0xFFFFFFFF)
+    assert a.tobytes() + b.tobytes() == whole.tobytes()
+
+
+def test_device_resident_evict_then_encode(nf, O):
+    """nfagg_evict_device -> nfagg_encode_ipfix_device without leaving HBM, against nfagg_encode_ipfix on the host copy."""
+    import torch
+    th = O.zipf_thresholds(3000, 1.1)
+    recs = O.gen_stream(100_000, seed=12, n_keys=3000, thresholds=th, variant=1)
+    recs["metrics"]["eth_protocol"][::5] = 0x86DD
+    names = nf.intf_table(NAMES)
+    with nf.FlowTable(max_entries=1 << 16) as tab:
+        assert tab.ingest(recs.view(nf.FLOW_RECORD)) == (nf.OK, len(recs))
+        d_ev = torch.empty(3000 * 144 + 16, dtype=torch.uint8, device="cuda")
+        n = tab.evict_device(d_ev.data_ptr(), 3000)
+        assert 0 < n <= 3000
+        d_off = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+        rc, need = tab.encode_ipfix_device(d_ev.data_ptr(), n, NOW, MONO, names, EXPORT, 77, 0, 0, d_off.data_ptr())
+        assert rc == nf.TRUNCATED and need > 0                   # size query
+        d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+        rc, wrote = tab.encode_ipfix_device(d_ev.data_ptr(), n, NOW, MONO, names, EXPORT, 77, d_out.data_ptr(), need, d_off.data_ptr())
+        assert rc == nf.OK and wrote == need
+        ev = d_ev[: n * 144].cpu().numpy().view(nf.FLOW_RECORD)
+        got, got_off = d_out[:need].cpu().numpy(), d_off.cpu().numpy().astype(np.uint64)
+        host, host_off = tab.encode_ipfix(ev, NOW, MONO, names, EXPORT, 77)
+    assert got.tobytes() == host.tobytes() and got_off.tolist() == host_off.tolist()
+    assert got.tobytes() == R.encode(ev, NOW, MONO, rows(NAMES), EXPORT, 77)[0]
+
+
+def _namer(names):
+    """The table's rule as an interface namer: the (index, MAC) row, else the first row of the index without a MAC."""
+    def namer(if_index, mac):
+        for i, m, n, _ in names:
+            if i == if_index and m is not None and bytes(m) == bytes(mac):
+                return n
+        for i, m, n, _ in names:
+            if i == if_index and m is None:
+                return n
+        return "unknown"
+    return namer
+
+
+def test_decoded_fields_equal_the_host_mirror_record(nf, O):
+    """What ipfix.go:272-322 takes from accounter.NewRecord(...), field by field, read back through the collector's decoder."""
+    recs = stream(nf, O, 2000, seed=5)
+    with nf.FlowTable(max_entries=64) as tab:
+        buf, off = tab.encode_ipfix(recs, NOW, MONO, nf.intf_table(NAMES), EXPORT, 1000)
+    nf.SetInterfaceNamer(_namer(NAMES))
+    try:
+        col = R.Collector()
+        col.decode(R.template_message(False, EXPORT, 1000))
+        col.decode(R.template_message(True, EXPORT, 1000))
+        raw = buf.tobytes()
+        for i, r in enumerate(recs):
+            rec = nf.NewRecord(r["id"], r["metrics"], NOW, MONO)
+            d = col.decode(raw[int(off[i]):int(off[i + 1])])
+            v6 = int(rec.Metrics["eth_protocol"]) == 0x86DD
+            assert (d["seq"], d["export_time"], d["domain"], d["set_id"]) == (1000 + i, EXPORT, 1, 257 if v6 else 256)
+            f = d["records"][0]
+            sip, dip = bytes(rec.ID["src_ip"]), bytes(rec.ID["dst_ip"])
+            if v6:
+                assert (f["sourceIPv6Address"], f["destinationIPv6Address"]) == (sip, dip)
+                assert (f["nextHeaderIPv6"], f["icmpTypeIPv6"], f["icmpCodeIPv6"]) == (
+                    int(rec.ID["transport_protocol"]), int(rec.ID["icmp_type"]), int(rec.ID["icmp_code"]))
+            else:
+                to4 = lambda a: a[12:] if a[:12] == bytes(10) + b"\xff\xff" else bytes(4)   # noqa: E731
+                assert (f["sourceIPv4Address"], f["destinationIPv4Address"]) == (to4(sip), to4(dip))
+                assert (f["protocolIdentifier"], f["icmpTypeIPv4"], f["icmpCodeIPv4"]) == (
+                    int(rec.ID["transport_protocol"]), int(rec.ID["icmp_type"]), int(rec.ID["icmp_code"]))
+            assert f["ethernetType"] == int(rec.Metrics["eth_protocol"])
+            assert f["flowDirection"] == rec.Interfaces[0].Direction
+            assert f["interfaceName"] == rec.Interfaces[0].Interface
+            assert (f["sourceMacAddress"], f["destinationMacAddress"]) == (bytes(rec.Metrics["src_mac"]), bytes(rec.Metrics["dst_mac"]))
+            assert (f["sourceTransportPort"], f["destinationTransportPort"]) == (int(rec.ID["src_port"]), int(rec.ID["dst_port"]))
+            assert f["octetDeltaCount"] == int(rec.Metrics["bytes"]) and f["packetDeltaCount"] == int(rec.Metrics["packets"])
+            assert f["tcpControlBits"] == int(rec.Metrics["flags"])
+            assert f["flowStartSeconds"] == (rec.TimeFlowStart // 10**9) & 0xFFFFFFFF
+            assert f["flowStartMilliseconds"] == (rec.TimeFlowStart // 10**6) % 2**64
+            assert f["flowEndSeconds"] == (rec.TimeFlowEnd // 10**9) & 0xFFFFFFFF
+            assert f["flowEndMilliseconds"] == (rec.TimeFlowEnd // 10**6) % 2**64
+    finally:
+        nf.SetInterfaceNamer(nf.accounter._default_namer)
+
+
+def test_exporter_over_a_datagram_socket_pair(nf, O):
+    """StartIPFIXExporter -> ExportEvicted over socket.socketpair(AF_UNIX, SOCK_DGRAM): two template datagrams, then one
+    datagram per flow, each decoding to its flow and sequence number. No network socket is opened."""
+    recs = stream(nf, O, 200, seed=6)
+    a, b = socket.socketpair(socket.AF_UNIX, socket.SOCK_DGRAM)
+    got = []
+
+    def send(m):              # the exporter's send is the socket's; each datagram is read back at once (a short queue)
+        assert a.send(m) == len(m)
+        got.append(b.recv(65536))
+
+    try:
+        b.settimeout(10)
+        with nf.FlowTable(max_entries=64) as tab:
+            t = [NOW]
+            ipf = nf.StartIPFIXExporter(tab, send, "udp", names=nf.intf_table(NAMES), clock=lambda: t[0], mono_clock=lambda: MONO)
+            assert got == [R.template_message(False, 1_700_000_000, 0), R.template_message(True, 1_700_000_000, 0)]
+            del got[:]
+            assert ipf.ExportEvicted(recs[:120], NOW, MONO) == 120
+            t[0] += 1_000_000_000
+            assert ipf.ExportEvicted(recs[120:], NOW, MONO) == 80
+            assert len(got) == 120 + 2 + 80
+    finally:
+        a.close()
+        b.close()
+    assert got[120] == R.template_message(False, 1_700_000_001, 120) and got[121] == R.template_message(True, 1_700_000_001, 120)
+    data = got[:120] + got[122:]
+    want, want_off = R.encode(recs[:120], NOW, MONO, rows(NAMES), 1_700_000_000, 0)
+    want2, want_off2 = R.encode(recs[120:], NOW, MONO, rows(NAMES), 1_700_000_001, 120)
+    assert data == [want[int(want_off[i]):int(want_off[i + 1])] for i in range(120)] + \
+        [want2[int(want_off2[i]):int(want_off2[i + 1])] for i in range(80)]
+    col = R.Collector()
+    col.decode(got[120])
+    col.decode(got[121])
+    for i, m in enumerate(data):
+        d = col.decode(m)
+        assert d["seq"] == i and d["records"][0]["sourceTransportPort"] == int(recs[i]["id"]["src_port"])
+
+
+def test_one_million_flows_evicted_and_encoded_on_the_device(nf, O):
+    import torch
+    from netobserv_ebpf_agent_amd import synth
+    flows, n = 1_000_000, 8_000_000
+    d_th = torch.from_numpy(synth.zipf_thresholds(flows, 1.1).view(np.int64)).cuda()
+    d = torch.empty(n * 144, dtype=torch.uint8, device="cuda")
+    synth.stream_device(d.data_ptr(), n, seed=2, n_keys=flows, d_thresholds=d_th.data_ptr(), variant=1)
+    names = nf.intf_table(NAMES)
+    with nf.FlowTable(max_entries=1 << 21) as tab:
+        assert tab.ingest_device(d.data_ptr(), n) == (nf.OK, n)
+        d_ev = torch.empty(flows * 144 + 16, dtype=torch.uint8, device="cuda")
+        m = tab.evict_device(d_ev.data_ptr(), flows)
+        assert m > 500_000
+        d_off = torch.empty(m + 1, dtype=torch.int64, device="cuda")
+        rc, need = tab.encode_ipfix_device(d_ev.data_ptr(), m, NOW, MONO, names, EXPORT, 0xFFFF0000, 0, 0, d_off.data_ptr())
+        d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+        rc, wrote = tab.encode_ipfix_device(d_ev.data_ptr(), m, NOW, MONO, names, EXPORT, 0xFFFF0000, d_out.data_ptr(), need, d_off.data_ptr())
+        assert rc == nf.OK and wrote == need
+        ev = d_ev[: m * 144].cpu().numpy().view(nf.FLOW_RECORD)
+        got, got_off = d_out[:need].cpu().numpy(), d_off.cpu().numpy().astype(np.uint64)
+    want, want_off = R.encode(ev, NOW, MONO, rows(NAMES), EXPORT, 0xFFFF0000)
+    assert got_off.tolist() == want_off.tolist()
+    assert got.tobytes() == want
+
+
+def test_c_driver_matches_restatement(nf, O, tmp_path):
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    libdir = os.path.join(root, "netobserv-ebpf-agent_amd", "lib")
+    exe = str(tmp_path / "nfagg_ipfix_cdriver")
+    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(root, "include"),
+                           os.path.join(root, "tools", "c", "nfagg_ipfix_cdriver.c"), "-o", exe, "-L", libdir, "-lnfagg", "-Wl,-rpath," + libdir])
+    recs = stream(nf, O, 2000, seed=11)
+    recs["metrics"]["if_index_first_seen"][::4] = 3
+    (tmp_path / "in.bin").write_bytes(recs.tobytes())
+    out = subprocess.check_output([exe, str(tmp_path / "in.bin"), str(tmp_path / "o"), str(NOW), str(MONO), str(EXPORT), "4294967290"],
+                                  text=True, timeout=120)
+    names = [(2, None, b"eth0"), (3, bytes.fromhex("020000000001"), b"veth3a"), (3, None, b"veth3")]
+    want, want_off = R.encode(recs, NOW, MONO, names, EXPORT, 4294967290)
+    assert out.split() == ["templates", "200", "messages", "2000", "bytes", str(len(want))]
+    got = (tmp_path / "o.ipfix").read_bytes()
+    assert got == R.template_message(False, EXPORT, 4294967290) + R.template_message(True, EXPORT, 4294967290) + want
+    assert np.fromfile(tmp_path / "o.off", dtype=np.uint64).tolist() == want_off.tolist()
