@@ -771,6 +771,57 @@ int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, 
                               void* d_out, size_t out_cap, uint64_t* d_msg_offsets, size_t* out_bytes);
 
 /* ------------------------------------------------------------------ */
+/* direct-FLP export — replaces, for evicted records, the direct-FLP    */
+/* exporter (EXPORT=direct-flp, pkg/exporter/direct_flp.go) in front of */
+/* a `write: stdout, format: json` stage: decode.RecordToMap per flow   */
+/* and its JSON line, keys sorted (write_stdout.go:37-51, reorder).     */
+/* ------------------------------------------------------------------ */
+
+typedef struct nfagg_flp_options {
+    uint32_t struct_size;        /* sizeof(nfagg_flp_options)                                     */
+    uint32_t n_names;
+    int64_t  now_unix_ns;        /* as nfagg_pb_options                                           */
+    uint64_t mono_now_ns;
+    const nfagg_intf_name* names;/* HOST memory: same table and lookup rule as nfagg_pb_options; names and UDNs are arbitrary bytes */
+    char     unknown_name[16];   /* the namer's answer for an unknown interface                   */
+    uint8_t  unknown_len;
+    uint8_t  agent_ip_nil;       /* non-zero: Record.AgentIP is nil, printed as "<nil>"; agent_ip is not read */
+    uint8_t  pad_[6];
+    uint8_t  agent_ip[16];       /* Record.AgentIP as a 16-byte net.IP                            */
+    int64_t  time_received_s;    /* "TimeReceived": one value for every line of a call            */
+} nfagg_flp_options;
+
+/* Encode n evicted flow_record_t as n JSON lines: line i = out[line_offsets[i],
+ * line_offsets[i+1]), its '\n' included, line_offsets[n] = *out_bytes. Line i
+ * is jsoniter.Config{SortMapKeys: true}.Marshal(decode.RecordToMap(
+ * model.NewRecord(...))) + "\n" for a record that carries only BpfFlowMetrics
+ * (decode_protobuf.go:57-127): compact, keys in byte order, strings escaped as
+ * jsoniter's WriteString (no HTML escaping, bytes from 0x80 up copied as they
+ * are), addresses as net.IP.String() of the 16-byte slice, MACs as
+ * net.HardwareAddr.String(), times and interfaces as model.NewRecord derives
+ * them (record.go:82-114; nb_observed_intf above 6 counts as 6).
+ * Deferred records: TLSVersion, TLSCipherSuite and TLSGroup take their text
+ * from Go's crypto/tls, which is not restated here. A record whose
+ * ssl_version, tls_cipher_suite or tls_key_share is non-zero gets an EMPTY
+ * line (line_offsets[i+1] == line_offsets[i]); deferred[i] (optional, n bytes)
+ * is 1 for it and 0 otherwise, *n_deferred (optional) is their count. The
+ * caller formats those records itself.
+ * One difference from the reference, by design: the reference reads the clock
+ * for every flow's TimeReceived, here one time_received_s covers the call.
+ * Returns NFAGG_TRUNCATED with *out_bytes = bytes needed (and *n_deferred)
+ * when out_cap is too small: out, line_offsets and deferred are not written.
+ * All pointers HOST memory: */
+int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
+                          void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
+                          size_t* n_deferred, size_t* out_bytes);
+/* Same with d_records / d_out / d_line_offsets / d_deferred in DEVICE memory
+ * (d_records and d_out 16-byte aligned), e.g. straight from
+ * nfagg_evict_device. d_out may be NULL to ask for the size. */
+int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
+                                 void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
+                                 size_t* n_deferred, size_t* out_bytes);
+
+/* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */
 /* ------------------------------------------------------------------ */
 

@@ -72,6 +72,15 @@ class IpfixOptions(C.Structure):
     ]
 
 
+class FlpOptions(C.Structure):
+    """nfagg_flp_options (include/nfagg.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_names", C.c_uint32), ("now_unix_ns", C.c_int64), ("mono_now_ns", C.c_uint64),
+        ("names", C.c_void_p), ("unknown_name", C.c_char * 16), ("unknown_len", C.c_uint8), ("agent_ip_nil", C.c_uint8),
+        ("pad_", C.c_uint8 * 6), ("agent_ip", C.c_uint8 * 16), ("time_received_s", C.c_int64),
+    ]
+
+
 class MapView(C.Structure):
     """nfagg_map_view (include/nfagg.h)."""
     _fields_ = [("ids", C.c_void_p), ("values", C.c_void_p), ("n", C.c_size_t)]
@@ -154,6 +163,8 @@ SIGNATURES = {
     "nfagg_ipfix_template": (C.c_int, [C.POINTER(IpfixOptions), C.c_int, _vp, _sz, _psz]),
     "nfagg_encode_ipfix": (C.c_int, [_vp, _vp, _sz, C.POINTER(IpfixOptions), _vp, _sz, _vp, _psz]),
     "nfagg_encode_ipfix_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(IpfixOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_encode_flp_json": (C.c_int, [_vp, _vp, _sz, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
+    "nfagg_encode_flp_json_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

@@ -20,6 +20,7 @@
 #include "nfagg_hostpool.h"
 #include "nfagg_pb.h"
 #include "nfagg_ipfix.h"
+#include "nfagg_flp.h"
 
 using namespace nfagg;
 
@@ -88,6 +89,11 @@ struct nfagg_handle {
     // IPFIX encode scratch: name rows, local offsets, block sums, block bases, namer table, (host variant) records/out/offsets
     void* d_ipfix[8] = {};
     size_t d_ipfix_cap[8] = {};
+    // direct-FLP JSON encode scratch: interface rows + lengths, local offsets, block sums, block bases, namer table, escaped table,
+    // deferred counter, (host variant) records/out/offsets/deferred flags
+    void* d_flp[11] = {};
+    size_t d_flp_cap[11] = {};
+    std::vector<uint8_t> flp_esc;            // host copy of the escaped namer table (kept until the stream has consumed it)
     // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
     void* d_opt[4] = {};
     size_t d_opt_cap[4] = {};
@@ -863,6 +869,7 @@ void nfagg_destroy(nfagg_handle* h) {
     for (int k = 0; k < 4; k++) if (h->d_opt[k]) hipFree(h->d_opt[k]);
     for (int k = 0; k < 15; k++) if (h->d_pb[k]) hipFree(h->d_pb[k]);
     for (int k = 0; k < 8; k++) if (h->d_ipfix[k]) hipFree(h->d_ipfix[k]);
+    for (int k = 0; k < 11; k++) if (h->d_flp[k]) hipFree(h->d_flp[k]);
     for (int k = 0; k < 2; k++) if (h->d_sort[k]) hipFree(h->d_sort[k]);
     for (int k = 0; k < 7; k++) if (h->d_hh[k]) hipFree(h->d_hh[k]);
     for (int k = 0; k < 28; k++) if (h->d_mm[k]) hipFree(h->d_mm[k]);
@@ -2394,6 +2401,124 @@ int nfagg_encode_ipfix(nfagg_handle* h, const void* records, size_t n, const nfa
     if (rc != NFAGG_OK) return rc;
     if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, h->d_ipfix[6], *out_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(msg_offsets, h->d_ipfix[7], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+// ---- record -> direct-FLP JSON lines (nfagg_flp.hip)
+// jsoniter's Stream.WriteString without HTML escaping (stream_str.go:311-372): the quotes, \" \\ \n \r \t, any other byte
+// below 0x20 as \u00xx in lower-case hex, every other byte (0x7f and everything from 0x80 up) as it is. Returns the length.
+static uint32_t flp_escape(const char* src, uint32_t len, uint8_t* dst) {
+    static const char hex[] = "0123456789abcdef";
+    uint32_t o = 0;
+    dst[o++] = '"';
+    for (uint32_t k = 0; k < len; k++) {
+        const uint8_t b = (uint8_t)src[k];
+        if (b == '"' || b == '\\') { dst[o++] = '\\'; dst[o++] = b; }
+        else if (b == '\n') { dst[o++] = '\\'; dst[o++] = 'n'; }
+        else if (b == '\r') { dst[o++] = '\\'; dst[o++] = 'r'; }
+        else if (b == '\t') { dst[o++] = '\\'; dst[o++] = 't'; }
+        else if (b < 0x20) { memcpy(dst + o, "\\u00", 4); o += 4; dst[o++] = (uint8_t)hex[b >> 4]; dst[o++] = (uint8_t)hex[b & 15]; }
+        else dst[o++] = b;
+    }
+    dst[o++] = '"';
+    return o;
+}
+
+static void flp_escape_row(uint8_t* row, const char* name, uint32_t name_len, const char* udn, uint32_t udn_len) {
+    const uint16_t nl = (uint16_t)flp_escape(name, name_len, row + kFlpEscNameOff), ul = (uint16_t)flp_escape(udn, udn_len, row + kFlpEscUdnOff);
+    memcpy(row, &nl, 2); memcpy(row + 2, &ul, 2);
+}
+
+// The options are checked first, before the handle: a caller learns of a bad table without any device work.
+static int encode_flp_check(nfagg_handle* h, const nfagg_flp_options* opt) {
+    if (!opt) return fail(h, NFAGG_EINVAL, "null options");
+    if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
+    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");
+    for (uint32_t k = 0; k < opt->n_names; k++) {
+        if (opt->names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
+        if (opt->names[k].udn_len > 63) return fail(h, NFAGG_EINVAL, "namer row %u: udn too long", k);
+    }
+    return NFAGG_OK;
+}
+
+int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
+                                 void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
+                                 size_t* n_deferred, size_t* out_bytes) {
+    int rc = encode_flp_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !out_bytes || !d_line_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->device));
+    *out_bytes = 0;
+    if (n_deferred) *n_deferred = 0;
+    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_line_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
+    const size_t blocks = (n + 1023) / 1024;
+    const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
+    if ((rc = ensure_bytes(h, &h->d_flp[0], &h->d_flp_cap[0], n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[1], &h->d_flp_cap[1], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[2], &h->d_flp_cap[2], blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[3], &h->d_flp_cap[3], (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[4], &h->d_flp_cap[4], (size_t)(opt->n_names + 1) * sizeof(nfagg_intf_name))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[5], &h->d_flp_cap[5], esc_bytes)) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[6], &h->d_flp_cap[6], 16)) != NFAGG_OK) return rc;
+    // the kernels binary-search the table: stable sort by if_index keeps the scan-in-table-order answer. Names and UDNs
+    // are escaped here, once per row: neither kernel escapes per flow.
+    h->pb_names.assign(opt->names, opt->names + opt->n_names);
+    std::stable_sort(h->pb_names.begin(), h->pb_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
+    h->flp_esc.assign(esc_bytes, 0);
+    flp_escape_row(h->flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
+    for (uint32_t k = 0; k < opt->n_names; k++) {
+        const nfagg_intf_name& e = h->pb_names[k];
+        flp_escape_row(h->flp_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
+    }
+    if (opt->n_names)
+        HIP_TRY(h, hipMemcpyAsync(h->d_flp[4], h->pb_names.data(), opt->n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_flp[5], h->flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->d_flp[6], 0, 16, h->stream));
+    FlpParams P{};
+    P.now_sec = opt->now_unix_ns / 1000000000ll; P.now_nsec = opt->now_unix_ns % 1000000000ll;
+    if (P.now_nsec < 0) { P.now_nsec += 1000000000ll; P.now_sec -= 1; }
+    P.mono_now = opt->mono_now_ns;
+    P.time_received = opt->time_received_s;
+    P.names = (const nfagg_intf_name*)h->d_flp[4]; P.esc = (const uint8_t*)h->d_flp[5]; P.n_names = opt->n_names;
+    P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
+    hipError_t e = launch_flp_size(d_records, n, P, (uint32_t*)h->d_flp[0], (uint32_t*)h->d_flp[1], (uint32_t*)h->d_flp[2],
+                                   (uint64_t*)h->d_flp[3], (uint32_t*)h->d_flp[6], h->stream);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "FLP JSON size launch failed: %s", hipGetErrorString(e));
+    uint64_t total = 0;
+    uint32_t deferred = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)h->d_flp[3] + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&deferred, h->d_flp[6], sizeof deferred, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *out_bytes = (size_t)total;
+    if (n_deferred) *n_deferred = deferred;
+    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
+    e = launch_flp_write(d_records, n, P, (const uint32_t*)h->d_flp[0], (const uint32_t*)h->d_flp[1], (const uint64_t*)h->d_flp[3],
+                         d_out, d_line_offsets, d_deferred, h->stream);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "FLP JSON write launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
+                          void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
+                          size_t* n_deferred, size_t* out_bytes) {
+    int rc = encode_flp_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = ensure_bytes(h, &h->d_flp[7], &h->d_flp_cap[7], n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[8], &h->d_flp_cap[8], out_cap + 32)) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[9], &h->d_flp_cap[9], (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_bytes(h, &h->d_flp[10], &h->d_flp_cap[10], n + 16)) != NFAGG_OK) return rc;
+    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_flp[7], records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+    rc = nfagg_encode_flp_json_device(h, h->d_flp[7], n, opt, out ? h->d_flp[8] : nullptr, out_cap, (uint64_t*)h->d_flp[9],
+                                      deferred ? (uint8_t*)h->d_flp[10] : nullptr, n_deferred, out_bytes);
+    if (rc != NFAGG_OK) return rc;
+    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, h->d_flp[8], *out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(line_offsets, h->d_flp[9], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    if (deferred && n) HIP_TRY(h, hipMemcpyAsync(deferred, h->d_flp[10], n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
 }

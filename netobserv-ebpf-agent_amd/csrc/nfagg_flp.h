@@ -1,0 +1,36 @@
+// nfagg_flp.h — launch interface of the record -> direct-FLP JSON line kernels (nfagg_flp.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/nfagg.h"
+
+namespace nfagg {
+
+// One row of the escaped namer table the host builds when it stages the table (nfagg_api.hip): the row's name and UDN
+// as JSON strings, quotes included, escaped once per call and not per flow. Row 0 is the unknown name (UDN ""), row
+// k + 1 is row k of the sorted table. name: at most 2 + 6 x 16 bytes, udn: at most 2 + 6 x 63.
+constexpr uint32_t kFlpEscRowBytes = 512;
+constexpr uint32_t kFlpEscNameOff = 16, kFlpEscNameMax = 98;      // name_len (u16) @0, udn_len (u16) @2
+constexpr uint32_t kFlpEscUdnOff = 128, kFlpEscUdnMax = 380;
+static_assert(kFlpEscNameOff + kFlpEscNameMax <= kFlpEscUdnOff && kFlpEscUdnOff + kFlpEscUdnMax <= kFlpEscRowBytes, "escaped row layout");
+
+struct FlpParams {
+    int64_t now_sec, now_nsec;    // currentTime, normalised (0 <= nsec < 1e9)
+    uint64_t mono_now;
+    int64_t time_received;
+    const nfagg_intf_name* names; // device copy of the namer table, stably sorted by if_index
+    const uint8_t* esc;           // device copy of the escaped table, n_names + 1 rows of kFlpEscRowBytes
+    uint32_t n_names;
+    uint32_t agent_nil;           // Record.AgentIP == nil: "<nil>"
+    uint32_t agent_ip_w[4];       // Record.AgentIP as a 16-byte net.IP, four little-endian dwords
+};
+
+// Line lengths (0 = deferred) and the seven resolved interface rows per record (d_rows: 8 dwords per record, rows 0..6
+// and the length), block-local scan, scan of the block sums: d_block_base[ceil(n / 1024)] = total bytes afterwards.
+// *d_n_deferred (zeroed by the caller) counts the deferred records.
+hipError_t launch_flp_size(const void* d_recs, uint64_t n, const FlpParams& P, uint32_t* d_rows, uint32_t* d_local_off,
+                           uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s);
+hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, const uint32_t* d_rows, const uint32_t* d_local_off,
+                            const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, uint8_t* d_deferred, hipStream_t s);
+
+}  // namespace nfagg

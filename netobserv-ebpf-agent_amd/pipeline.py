@@ -7,6 +7,7 @@ BASELINE configs[0] ("10k flow_record_t, 1k 5-tuples, Accounter via direct-flp s
   DirectFLPStdout.ExportFlows(in)     pkg/exporter/direct_flp.go + flowlogs-pipeline write_stdout.go:37-51
                                       with `format: json` (one JSON object per flow, keys sorted)
   IPFIX / StartIPFIXExporter          pkg/exporter/ipfix.go over the GPU encoder (nfagg_encode_ipfix)
+  DirectFLPJSON / StartDirectFLPJSON  DirectFLPStdout's lines from the GPU encoder (nfagg_encode_flp_json)
 
 Plumbing only — no flow state is touched here; the records come from libnfagg (accounter.py). The
 string tables of the feature branch (TCP states, drop causes, DNS rcodes, TLS names) stay with the Go
@@ -287,3 +288,64 @@ def StartIPFIXExporter(table, send: Callable, transport: str = "udp", names=None
     ipf = IPFIX(table, send, transport, names=names, clock=clock, mono_clock=mono_clock, **kw)
     ipf.sendTemplates()
     return ipf
+
+
+def _no_fallback(record, now_ns, mono_ns):
+    raise NotImplementedError("TLS name tables (crypto/tls) stay with the Go decoder")
+
+
+class DirectFLPJSON:                                      # pkg/exporter/direct_flp.go + write_stdout.go:37-51
+    """The direct-FLP exporter in front of a lone `write: stdout, format: json` stage, over the GPU encoder
+    (FlowTable.encode_flp_json): evicted records go straight to the JSON lines DirectFLPStdout prints, no Record and no dict
+    per flow. Lines are written to `stream` (binary: anything with write(bytes)) in record order. A record the encoder
+    defers (TLS version / cipher suite / key share set) is formatted by `fallback(record, now_ns, mono_ns) -> bytes`, the
+    whole line with its newline, and written at its place; the default raises, as RecordToMap does for such a record.
+
+    One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
+
+    def __init__(self, table, stream, names=None, agent_ip=None, unknown: bytes = b"unknown", time_received: Callable[[], int] = None,
+                 fallback: Callable = None, encode=None):
+        self.table, self.stream = table, stream
+        self.names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
+        self.agent_ip, self.unknown = agent_ip, unknown
+        self.time_received = time_received or (lambda: int(time.time()))   # time.Now().Unix()
+        self.fallback = fallback or _no_fallback
+        self.lines = self.deferred = 0
+        # encode(raw, now_ns, mono_ns, names, agent_ip, time_received, unknown) -> (buf, line_offsets, deferred)
+        self._encode = encode or table.encode_flp_json
+
+    def ExportEvicted(self, raw, now_ns: int, mono_ns: int) -> int:
+        """One eviction's lines. now_ns / mono_ns: the eviction's currentTime / monotonicCurrentTime (account.go:103-104).
+        Returns the lines written."""
+        n = len(raw)
+        if n == 0:
+            return 0
+        buf, off, deferred = self._encode(raw, now_ns, mono_ns & ((1 << 64) - 1), self.names, self.agent_ip, self.time_received(),
+                                          self.unknown)
+        raw_buf = memoryview(np.ascontiguousarray(buf))
+        held = np.flatnonzero(deferred)
+        start = 0
+        for i in held:                                    # runs of encoded lines between deferred records: one write each
+            i = int(i)
+            if int(off[i]) > start:
+                self.stream.write(raw_buf[start:int(off[i])])
+            self.stream.write(self.fallback(raw[i], now_ns, mono_ns))
+            start = int(off[i])
+        if int(off[n]) > start:
+            self.stream.write(raw_buf[start:int(off[n])])
+        self.lines += n
+        self.deferred += len(held)
+        return n
+
+    def ExportFlows(self, inp: "queue.Queue"):            # direct_flp.go ExportFlows: items (raw records, now_ns, mono_ns) until CLOSE
+        while True:
+            item = inp.get()
+            if item is CLOSE:
+                return
+            raw, now_ns, mono_ns = item
+            self.ExportEvicted(raw, now_ns, mono_ns)
+
+
+def StartDirectFLPJSON(table, stream, names=None, agent_ip=None, **kw) -> DirectFLPJSON:
+    """StartDirectFLP (direct_flp.go) with the `write: stdout, format: json` pipeline of direct_flp_test.go:17-33."""
+    return DirectFLPJSON(table, stream, names=names, agent_ip=agent_ip, **kw)

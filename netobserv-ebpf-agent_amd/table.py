@@ -442,6 +442,45 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, need.value
 
+    # -- export encode (record -> direct-FLP JSON lines), nfagg_encode_flp_json
+    def encode_flp_json(self, records: np.ndarray, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip=None,
+                        time_received: int = 0, unknown: bytes = b"unknown"):
+        """The direct-FLP stdout lines (`format: json`, keys sorted) for evicted records, encoded on the GPU. agent_ip: 16 (or
+        4) bytes, None = a nil AgentIP ("<nil>"). Returns (buf, line_offsets, deferred): line i is
+        buf[line_offsets[i]:line_offsets[i + 1]], its newline included; deferred[i] == 1 marks a record that carries TLS
+        version / cipher suite / key share, whose line is empty and which the caller formats itself."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        deferred = np.zeros(n, dtype=np.uint8)
+        need, n_def = C.c_size_t(0), C.c_size_t(0)
+        cap = max(448 * n, 64)
+        while True:
+            buf = np.zeros(cap, dtype=np.uint8)
+            rc = L.lib.nfagg_encode_flp_json(self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(o), buf.ctypes.data_as(C.c_void_p), cap,
+                                             off.ctypes.data_as(C.c_void_p), deferred.ctypes.data_as(C.c_void_p), C.byref(n_def),
+                                             C.byref(need))
+            if rc == L.TRUNCATED:
+                cap = need.value
+                continue
+            self._check(rc)
+            break
+        assert int(deferred.sum()) == n_def.value
+        return buf[: need.value], off, deferred
+
+    def encode_flp_json_device(self, d_records: int, n: int, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip,
+                               time_received: int, d_out: int, out_cap: int, d_line_offsets: int, d_deferred: int = 0,
+                               unknown: bytes = b"unknown"):
+        """Device-resident variant (raw device pointers; d_out = 0 asks for the size, d_deferred = 0: no flags wanted).
+        Returns (rc, bytes needed/written, deferred records)."""
+        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
+        need, n_def = C.c_size_t(0), C.c_size_t(0)
+        rc = L.lib.nfagg_encode_flp_json_device(self._h, C.c_void_p(d_records), n, C.byref(o), C.c_void_p(d_out or None), out_cap,
+                                                C.c_void_p(d_line_offsets), C.c_void_p(d_deferred or None), C.byref(n_def), C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value, n_def.value
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -616,6 +655,28 @@ def ipfix_options(now_unix_ns=0, mono_now_ns=0, names=None, export_time_s=0, seq
     o.unknown_name, o.unknown_len = unknown, len(unknown)
     o.export_time_s, o.seq0, o.obs_domain_id = export_time_s & 0xFFFFFFFF, seq0 & 0xFFFFFFFF, obs_domain_id
     o.template_id_v4, o.template_id_v6 = template_ids
+    return o, names
+
+
+def flp_options(now_unix_ns=0, mono_now_ns=0, names=None, agent_ip=None, time_received=0, unknown=b"unknown"):
+    """nfagg_flp_options; returns (options, the names array the options point into: keep it alive for the call).
+    agent_ip: 16 bytes, 4 bytes (stored v4-mapped, as net.IP prints both alike) or None (nil)."""
+    o = L.FlpOptions()
+    o.struct_size = C.sizeof(L.FlpOptions)
+    o.now_unix_ns, o.mono_now_ns = now_unix_ns, mono_now_ns
+    names = np.ascontiguousarray(names if names is not None else np.zeros(0, dtype=INTF_NAME))
+    o.names, o.n_names = (names.ctypes.data if len(names) else None), len(names)
+    o.unknown_name, o.unknown_len = unknown, len(unknown)
+    if agent_ip is None:
+        o.agent_ip_nil = 1
+    else:
+        ip = bytes(agent_ip)
+        if len(ip) == 4:
+            ip = bytes(10) + b"\xff\xff" + ip
+        if len(ip) != 16:
+            raise ValueError("agent_ip: 4 or 16 bytes")
+        o.agent_ip = (C.c_uint8 * 16)(*ip)
+    o.time_received_s = time_received
     return o, names
 
 
