@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <set>
@@ -72,7 +73,6 @@ struct nfagg_handle {
     void* d_roll[3] = {nullptr, nullptr, nullptr};
     size_t d_roll_cap[3] = {0, 0, 0};
     uint32_t* d_hist = nullptr;
-    // protobuf encode scratch: local offsets, block sums, block bases, namer table, (host variant) records/out/offsets/lens/keys
     // map merge scratch: [0] slots [1] slot_of [2] local_off [3] block_sum [4] block_base [5] dup counter,
     // (host variant) [6..12] ids, [13..19] values, [20..27] outputs
     void* d_mm[28] = {};
@@ -83,17 +83,25 @@ struct nfagg_handle {
     size_t d_sort_cap[2] = {};
     int sort_bits = 0;
     bool epoch_unclustered = false; // a batch of this epoch claimed slots in arrival order (single-pass / direct / dedup kernels)
-    std::vector<nfagg_intf_name> pb_names;   // host copy of the namer table, sorted (kept until the stream has consumed it)
-    void* d_pb[15] = {};
-    size_t d_pb_cap[15] = {};
-    // IPFIX encode scratch: name rows, local offsets, block sums, block bases, namer table, (host variant) records/out/offsets
-    void* d_ipfix[8] = {};
-    size_t d_ipfix_cap[8] = {};
-    // direct-FLP JSON encode scratch: interface rows + lengths, local offsets, block sums, block bases, namer table, escaped table,
-    // deferred counter, (host variant) records/out/offsets/deferred flags
-    void* d_flp[11] = {};
-    size_t d_flp_cap[11] = {};
-    std::vector<uint8_t> flp_esc;            // host copy of the escaped namer table (kept until the stream has consumed it)
+    // export encoders (protobuf, IPFIX, direct-FLP JSON): one scratch, they serialise on the stream and synchronise before returning
+    struct DevBuf { void* p = nullptr; size_t cap = 0; };
+    struct EncodeScratch {
+        DevBuf local_off, block_sum, block_base;     // the two scans: u32[n], u32[blocks], u64[blocks + 1] (the total last)
+        DevBuf names;                                // the namer table, stably sorted by if_index
+        DevBuf ipfix_name_rows;                      // size pass -> write pass: u32[n]
+        DevBuf flp_rows;                             // size pass -> write pass: 8 x u32 per record (seven rows, the line's length)
+        DevBuf flp_esc, flp_n_deferred;              // the escaped table; the deferred counter
+        DevBuf in_records, out, out_offsets;         // host-memory entry points: staged records, output bytes, offsets
+        DevBuf out_extra[2];                         //   protobuf: body lengths, kafka keys; FLP: deferred flags
+        DevBuf pb_feat[6];                           //   protobuf: present bits and the five feature parts
+        std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
+        std::vector<uint8_t> h_flp_esc;
+        template <typename F> void each(F f) {
+            for (DevBuf* b : {&local_off, &block_sum, &block_base, &names, &ipfix_name_rows, &flp_rows, &flp_esc, &flp_n_deferred,
+                              &in_records, &out, &out_offsets, &out_extra[0], &out_extra[1]}) f(*b);
+            for (DevBuf& b : pb_feat) f(b);
+        }
+    } enc;
     // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
     void* d_opt[4] = {};
     size_t d_opt_cap[4] = {};
@@ -867,9 +875,7 @@ void nfagg_destroy(nfagg_handle* h) {
     if (h->d_spill) hipFree(h->d_spill);
     if (h->tv.spill.xp) hipFree(h->tv.spill.xp);
     for (int k = 0; k < 4; k++) if (h->d_opt[k]) hipFree(h->d_opt[k]);
-    for (int k = 0; k < 15; k++) if (h->d_pb[k]) hipFree(h->d_pb[k]);
-    for (int k = 0; k < 8; k++) if (h->d_ipfix[k]) hipFree(h->d_ipfix[k]);
-    for (int k = 0; k < 11; k++) if (h->d_flp[k]) hipFree(h->d_flp[k]);
+    h->enc.each([](nfagg_handle::DevBuf& b) { if (b.p) hipFree(b.p); });
     for (int k = 0; k < 2; k++) if (h->d_sort[k]) hipFree(h->d_sort[k]);
     for (int k = 0; k < 7; k++) if (h->d_hh[k]) hipFree(h->d_hh[k]);
     for (int k = 0; k < 28; k++) if (h->d_mm[k]) hipFree(h->d_mm[k]);
@@ -2183,6 +2189,106 @@ int nfagg_stats_get(nfagg_handle* h, nfagg_stats* out) {
     return NFAGG_OK;
 }
 
+}  // extern "C"
+
+// ---- the export encoders' host side: what protobuf, IPFIX and direct-FLP JSON do alike
+namespace {
+
+int ensure_buf(nfagg_handle* h, nfagg_handle::DevBuf& b, size_t need) { return ensure_bytes(h, &b.p, &b.cap, need); }
+
+int check_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names, uint32_t unknown_len, bool check_udn) {
+    if (unknown_len > 16 || (n_names && !names)) return fail(h, NFAGG_EINVAL, "bad namer table");
+    for (uint32_t k = 0; k < n_names; k++) {
+        if (names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
+        if (check_udn && names[k].udn_len > 63) return fail(h, NFAGG_EINVAL, "namer row %u: udn too long", k);
+    }
+    return NFAGG_OK;
+}
+
+// The kernels binary-search the table: a stable sort by if_index keeps the scan-in-table-order answer.
+int stage_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names) {
+    auto& S = h->enc;
+    int rc = ensure_buf(h, S.names, (size_t)(n_names + 1) * sizeof(nfagg_intf_name));
+    if (rc != NFAGG_OK) return rc;
+    S.h_names.assign(names, names + n_names);
+    std::stable_sort(S.h_names.begin(), S.h_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
+    if (n_names) HIP_TRY(h, hipMemcpyAsync(S.names.p, S.h_names.data(), n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
+    return NFAGG_OK;
+}
+
+void split_now(int64_t now_unix_ns, int64_t& sec, int64_t& nsec) {   // time.Time's (sec, nsec), 0 <= nsec < 1e9
+    sec = now_unix_ns / 1000000000ll; nsec = now_unix_ns % 1000000000ll;
+    if (nsec < 0) { nsec += 1000000000ll; sec -= 1; }
+}
+
+// What follows the argument checks of a device entry point: the device, the zeroed results, the answer for n == 0 (*done), the
+// scratch of the two scans, the namer table.
+int encode_begin(nfagg_handle* h, size_t n, uint64_t* d_offsets, size_t* out_bytes, const nfagg_intf_name* names, uint32_t n_names, bool* done) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    *out_bytes = 0;
+    *done = n == 0;
+    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
+    const size_t blocks = (n + 1023) / 1024;
+    int rc;
+    if ((rc = ensure_buf(h, h->enc.local_off, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, h->enc.block_sum, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, h->enc.block_base, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    return stage_namer(h, names, n_names);
+}
+
+// The two passes: size(local_off, block_sum, block_base) launches the size kernel and the scan of the block sums; the total (and
+// the FLP encoder's deferred counter) is read back; a buffer that is too small or absent ends it there, with the total in
+// *out_bytes; write(local_off, block_base, total) launches the write kernel.
+template <typename SizeLaunch, typename WriteLaunch>
+int encode_two_pass(nfagg_handle* h, size_t n, const char* what, const char* write_verb, void* d_out, size_t out_cap, size_t* out_bytes,
+                           size_t* n_deferred, SizeLaunch size, WriteLaunch write) {
+    auto& S = h->enc;
+    const size_t blocks = (n + 1023) / 1024;
+    hipError_t e = size((uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s size launch failed: %s", what, hipGetErrorString(e));
+    uint64_t total = 0;
+    uint32_t deferred = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)S.block_base.p + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    if (n_deferred) HIP_TRY(h, hipMemcpyAsync(&deferred, S.flp_n_deferred.p, sizeof deferred, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *out_bytes = (size_t)total;
+    if (n_deferred) *n_deferred = deferred;
+    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
+    e = write((const uint32_t*)S.local_off.p, (const uint64_t*)S.block_base.p, total);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s %s launch failed: %s", what, write_verb, hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+// The host-memory entry points: records in, device(d_records, d_out or null, d_offsets) = the device entry point, bytes and offsets
+// out, and the format's per-record extras (out_extra[k] -> host, `bytes` per record; skipped when the caller passed no host array).
+struct EncodeExtra { void* host; size_t bytes; };
+template <typename DeviceEntry>
+int encode_staged(nfagg_handle* h, const void* records, size_t n, void* out, size_t out_cap, uint64_t* offsets, size_t* out_bytes,
+                         std::initializer_list<EncodeExtra> extras, DeviceEntry device) {
+    auto& S = h->enc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.out, out_cap + 32)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.out_offsets, (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    size_t k = 0;
+    for (const EncodeExtra& x : extras) { if (x.host && (rc = ensure_buf(h, S.out_extra[k], n * x.bytes + 32)) != NFAGG_OK) return rc; k++; }
+    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+    rc = device(S.in_records.p, out ? S.out.p : nullptr, (uint64_t*)S.out_offsets.p);
+    if (rc != NFAGG_OK) return rc;
+    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, S.out.p, *out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(offsets, S.out_offsets.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    k = 0;
+    for (const EncodeExtra& x : extras) { if (n && x.host) HIP_TRY(h, hipMemcpyAsync(x.host, S.out_extra[k].p, n * x.bytes, hipMemcpyDeviceToHost, h->stream)); k++; }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 // ---- record -> protobuf (nfagg_pb.hip)
 // feat (optional): DEVICE pointers
 static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const nfagg_pb_options* opt,
@@ -2190,10 +2296,10 @@ static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t 
                                  void* d_kafka_keys, size_t* out_bytes) {
     if (!h || !opt || !out_bytes || !d_frame_offsets || (n && (!d_records || !d_body_len))) return fail(h, NFAGG_EINVAL, "null argument");
     if (opt->struct_size != sizeof(nfagg_pb_options)) return fail(h, NFAGG_EINVAL, "nfagg_pb_options.struct_size mismatch");
-    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");
+    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");   // ahead of the alignment, the rows behind it
     if ((((uintptr_t)d_records | (uintptr_t)d_out | (uintptr_t)d_kafka_keys) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
-    for (uint32_t k = 0; k < opt->n_names; k++)
-        if (opt->names[k].name_len > 16 || opt->names[k].udn_len > 63) return fail(h, NFAGG_EINVAL, "namer row %u: name/udn too long", k);
+    int rc = check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
+    if (rc != NFAGG_OK) return rc;
     PbFeat F{};
     if (feat) {
         if (feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
@@ -2203,39 +2309,40 @@ static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t 
         F.additional = (const uint8_t*)feat->additional; F.dns = (const uint8_t*)feat->dns; F.drops = (const uint8_t*)feat->drops;
         F.xlat = (const uint8_t*)feat->xlat; F.quic = (const uint8_t*)feat->quic;
     }
-    HIP_TRY(h, hipSetDevice(h->device));
-    *out_bytes = 0;
-    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_frame_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
-    const size_t blocks = (n + 1023) / 1024;
-    int rc;
-    if ((rc = ensure_bytes(h, &h->d_pb[0], &h->d_pb_cap[0], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_pb[1], &h->d_pb_cap[1], blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_pb[2], &h->d_pb_cap[2], (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_pb[3], &h->d_pb_cap[3], (size_t)(opt->n_names + 1) * sizeof(nfagg_intf_name))) != NFAGG_OK) return rc;
-    if (opt->n_names) {   // the kernels binary-search the table: stable sort by if_index keeps the scan-in-table-order answer
-        h->pb_names.assign(opt->names, opt->names + opt->n_names);
-        std::stable_sort(h->pb_names.begin(), h->pb_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
-        HIP_TRY(h, hipMemcpyAsync(h->d_pb[3], h->pb_names.data(), opt->n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
-    }
+    bool done;
+    if ((rc = encode_begin(h, n, d_frame_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
     PbParams P{};
-    P.now_sec = opt->now_unix_ns / 1000000000ll; P.now_nsec = opt->now_unix_ns % 1000000000ll;
-    if (P.now_nsec < 0) { P.now_nsec += 1000000000ll; P.now_sec -= 1; }
+    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
     P.mono_now = opt->mono_now_ns;
     memcpy(P.agent_ip_w, opt->agent_ip, 16);
     static const uint8_t v4pre[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xff, 0xff};
     P.agent_is_v4 = memcmp(opt->agent_ip, v4pre, 12) == 0;     // net.IP.To4() != nil (proto.go:255-261)
-    P.names = (const nfagg_intf_name*)h->d_pb[3]; P.n_names = opt->n_names;
+    P.names = (const nfagg_intf_name*)h->enc.names.p; P.n_names = opt->n_names;
     P.unknown_len = opt->unknown_len; memcpy(P.unknown, opt->unknown_name, 16);
-    hipError_t e = launch_pb_size(d_records, n, P, F, d_body_len, (uint32_t*)h->d_pb[0], (uint32_t*)h->d_pb[1], (uint64_t*)h->d_pb[2], h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "protobuf size launch failed: %s", hipGetErrorString(e));
-    uint64_t total = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)h->d_pb[2] + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *out_bytes = (size_t)total;
-    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
-    e = launch_pb_write(d_records, n, P, F, d_body_len, (const uint32_t*)h->d_pb[0], (const uint64_t*)h->d_pb[2], d_out, d_frame_offsets, d_kafka_keys, total, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "protobuf encode launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return encode_two_pass(h, n, "protobuf", "encode", d_out, out_cap, out_bytes, nullptr,
+        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+            return launch_pb_size(d_records, n, P, F, d_body_len, local_off, block_sum, block_base, h->stream); },
+        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t total) {
+            return launch_pb_write(d_records, n, P, F, d_body_len, local_off, block_base, d_out, d_frame_offsets, d_kafka_keys, total, h->stream); });
+}
+
+// The feature parts of a host-memory call, uploaded: *dfeat gets the device pointers.
+static int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, nfagg_pb_features* dfeat) {
+    dfeat->struct_size = sizeof *dfeat;
+    const void* src[6] = {feat->present, feat->additional, feat->dns, feat->drops, feat->xlat, feat->quic};
+    const size_t elem[6] = {1, sizeof(nfagg_additional_metrics), sizeof(nfagg_dns_metrics), sizeof(nfagg_pkt_drop_metrics),
+                            sizeof(nfagg_xlat_metrics), sizeof(nfagg_quic_metrics)};
+    void* dst[6] = {};
+    for (int k = 0; k < 6; k++) {
+        if (!src[k]) continue;
+        int rc = ensure_buf(h, h->enc.pb_feat[k], n * elem[k] + 16);
+        if (rc != NFAGG_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->enc.pb_feat[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
+        dst[k] = h->enc.pb_feat[k].p;
+    }
+    dfeat->present = (const uint8_t*)dst[0]; dfeat->additional = (const nfagg_additional_metrics*)dst[1];
+    dfeat->dns = (const nfagg_dns_metrics*)dst[2]; dfeat->drops = (const nfagg_pkt_drop_metrics*)dst[3];
+    dfeat->xlat = (const nfagg_xlat_metrics*)dst[4]; dfeat->quic = (const nfagg_quic_metrics*)dst[5];
     return NFAGG_OK;
 }
 
@@ -2245,40 +2352,12 @@ static int encode_pb_host_core(nfagg_handle* h, const void* records, size_t n, c
                                void* kafka_keys, size_t* out_bytes) {
     if (!h || !opt || !out_bytes || !frame_offsets || (n && (!records || !body_len))) return fail(h, NFAGG_EINVAL, "null argument");
     if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure_bytes(h, &h->d_pb[4], &h->d_pb_cap[4], n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_pb[5], &h->d_pb_cap[5], out_cap + 32)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_pb[6], &h->d_pb_cap[6], (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_pb[7], &h->d_pb_cap[7], (n + 1) * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if (kafka_keys && (rc = ensure_bytes(h, &h->d_pb[8], &h->d_pb_cap[8], n * 32 + 32)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_pb[4], records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    nfagg_pb_features dfeat{};
-    if (feat && n) {
-        dfeat.struct_size = sizeof dfeat;
-        const void* src[6] = {feat->present, feat->additional, feat->dns, feat->drops, feat->xlat, feat->quic};
-        const size_t elem[6] = {1, sizeof(nfagg_additional_metrics), sizeof(nfagg_dns_metrics), sizeof(nfagg_pkt_drop_metrics),
-                                sizeof(nfagg_xlat_metrics), sizeof(nfagg_quic_metrics)};
-        void* dst[6] = {};
-        for (int k = 0; k < 6; k++) {
-            if (!src[k]) continue;
-            if ((rc = ensure_bytes(h, &h->d_pb[9 + k], &h->d_pb_cap[9 + k], n * elem[k] + 16)) != NFAGG_OK) return rc;
-            HIP_TRY(h, hipMemcpyAsync(h->d_pb[9 + k], src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
-            dst[k] = h->d_pb[9 + k];
-        }
-        dfeat.present = (const uint8_t*)dst[0]; dfeat.additional = (const nfagg_additional_metrics*)dst[1];
-        dfeat.dns = (const nfagg_dns_metrics*)dst[2]; dfeat.drops = (const nfagg_pkt_drop_metrics*)dst[3];
-        dfeat.xlat = (const nfagg_xlat_metrics*)dst[4]; dfeat.quic = (const nfagg_quic_metrics*)dst[5];
-    }
-    rc = encode_pb_device_core(h, h->d_pb[4], n, (feat && n) ? &dfeat : nullptr, opt, out ? h->d_pb[5] : nullptr, out_cap,
-                               (uint64_t*)h->d_pb[6], (uint32_t*)h->d_pb[7], kafka_keys ? h->d_pb[8] : nullptr, out_bytes);
-    if (rc != NFAGG_OK) return rc;
-    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, h->d_pb[5], *out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(frame_offsets, h->d_pb[6], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    if (n) HIP_TRY(h, hipMemcpyAsync(body_len, h->d_pb[7], n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (n && kafka_keys) HIP_TRY(h, hipMemcpyAsync(kafka_keys, h->d_pb[8], n * 32, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
+    return encode_staged(h, records, n, out, out_cap, frame_offsets, out_bytes, {{body_len, sizeof(uint32_t)}, {kafka_keys, 32}},
+        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
+            nfagg_pb_features dfeat{};
+            if (feat && n) { int rc = stage_pb_features(h, feat, n, &dfeat); if (rc != NFAGG_OK) return rc; }
+            return encode_pb_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, opt, d_out, out_cap, d_offsets,
+                                         (uint32_t*)h->enc.out_extra[0].p, kafka_keys ? h->enc.out_extra[1].p : nullptr, out_bytes); });
 }
 
 int nfagg_encode_pb_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_options* opt,
@@ -2338,10 +2417,7 @@ int nfagg_ipfix_template(const nfagg_ipfix_options* opt, int v6, void* out, size
 static int encode_ipfix_check(nfagg_handle* h, const nfagg_ipfix_options* opt) {
     if (!opt) return fail(h, NFAGG_EINVAL, "null options");
     if (opt->struct_size != sizeof(nfagg_ipfix_options)) return fail(h, NFAGG_EINVAL, "nfagg_ipfix_options.struct_size mismatch");
-    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");
-    for (uint32_t k = 0; k < opt->n_names; k++)
-        if (opt->names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
-    return NFAGG_OK;
+    return check_namer(h, opt->names, opt->n_names, opt->unknown_len, false);
 }
 
 int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_ipfix_options* opt,
@@ -2350,41 +2426,22 @@ int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, 
     if (rc != NFAGG_OK) return rc;
     if (!h || !out_bytes || !d_msg_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    *out_bytes = 0;
-    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_msg_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
-    const size_t blocks = (n + 1023) / 1024;
-    if ((rc = ensure_bytes(h, &h->d_ipfix[0], &h->d_ipfix_cap[0], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_ipfix[1], &h->d_ipfix_cap[1], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_ipfix[2], &h->d_ipfix_cap[2], blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_ipfix[3], &h->d_ipfix_cap[3], (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_ipfix[4], &h->d_ipfix_cap[4], (size_t)(opt->n_names + 1) * sizeof(nfagg_intf_name))) != NFAGG_OK) return rc;
-    if (opt->n_names) {   // the kernels binary-search the table: stable sort by if_index keeps the scan-in-table-order answer
-        h->pb_names.assign(opt->names, opt->names + opt->n_names);
-        std::stable_sort(h->pb_names.begin(), h->pb_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
-        HIP_TRY(h, hipMemcpyAsync(h->d_ipfix[4], h->pb_names.data(), opt->n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
-    }
+    bool done;
+    if ((rc = encode_begin(h, n, d_msg_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
+    if ((rc = ensure_buf(h, h->enc.ipfix_name_rows, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    uint32_t* name_rows = (uint32_t*)h->enc.ipfix_name_rows.p;
     IpfixParams P{};
-    P.now_sec = opt->now_unix_ns / 1000000000ll; P.now_nsec = opt->now_unix_ns % 1000000000ll;
-    if (P.now_nsec < 0) { P.now_nsec += 1000000000ll; P.now_sec -= 1; }
+    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
     P.mono_now = opt->mono_now_ns;
-    P.names = (const nfagg_intf_name*)h->d_ipfix[4]; P.n_names = opt->n_names;
+    P.names = (const nfagg_intf_name*)h->enc.names.p; P.n_names = opt->n_names;
     P.unknown_len = opt->unknown_len; memcpy(P.unknown_w, opt->unknown_name, 16);
     P.export_time = opt->export_time_s; P.seq0 = opt->seq0; P.obs_domain = opt->obs_domain_id;
     P.tid_v4 = opt->template_id_v4; P.tid_v6 = opt->template_id_v6;
-    hipError_t e = launch_ipfix_size(d_records, n, P, (uint32_t*)h->d_ipfix[0], (uint32_t*)h->d_ipfix[1], (uint32_t*)h->d_ipfix[2],
-                                     (uint64_t*)h->d_ipfix[3], h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "IPFIX size launch failed: %s", hipGetErrorString(e));
-    uint64_t total = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)h->d_ipfix[3] + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *out_bytes = (size_t)total;
-    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
-    e = launch_ipfix_write(d_records, n, P, (const uint32_t*)h->d_ipfix[0], (const uint32_t*)h->d_ipfix[1], (const uint64_t*)h->d_ipfix[3],
-                           d_out, d_msg_offsets, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "IPFIX write launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
+    return encode_two_pass(h, n, "IPFIX", "write", d_out, out_cap, out_bytes, nullptr,
+        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+            return launch_ipfix_size(d_records, n, P, name_rows, local_off, block_sum, block_base, h->stream); },
+        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+            return launch_ipfix_write(d_records, n, P, name_rows, local_off, block_base, d_out, d_msg_offsets, h->stream); });
 }
 
 int nfagg_encode_ipfix(nfagg_handle* h, const void* records, size_t n, const nfagg_ipfix_options* opt,
@@ -2392,17 +2449,9 @@ int nfagg_encode_ipfix(nfagg_handle* h, const void* records, size_t n, const nfa
     int rc = encode_ipfix_check(h, opt);
     if (rc != NFAGG_OK) return rc;
     if (!h || !out_bytes || !msg_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = ensure_bytes(h, &h->d_ipfix[5], &h->d_ipfix_cap[5], n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_ipfix[6], &h->d_ipfix_cap[6], out_cap + 32)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_ipfix[7], &h->d_ipfix_cap[7], (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_ipfix[5], records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    rc = nfagg_encode_ipfix_device(h, h->d_ipfix[5], n, opt, out ? h->d_ipfix[6] : nullptr, out_cap, (uint64_t*)h->d_ipfix[7], out_bytes);
-    if (rc != NFAGG_OK) return rc;
-    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, h->d_ipfix[6], *out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(msg_offsets, h->d_ipfix[7], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
+    return encode_staged(h, records, n, out, out_cap, msg_offsets, out_bytes, {},
+        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
+            return nfagg_encode_ipfix_device(h, d_records, n, opt, d_out, out_cap, d_offsets, out_bytes); });
 }
 
 // ---- record -> direct-FLP JSON lines (nfagg_flp.hip)
@@ -2434,12 +2483,7 @@ static void flp_escape_row(uint8_t* row, const char* name, uint32_t name_len, co
 static int encode_flp_check(nfagg_handle* h, const nfagg_flp_options* opt) {
     if (!opt) return fail(h, NFAGG_EINVAL, "null options");
     if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
-    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");
-    for (uint32_t k = 0; k < opt->n_names; k++) {
-        if (opt->names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
-        if (opt->names[k].udn_len > 63) return fail(h, NFAGG_EINVAL, "namer row %u: udn too long", k);
-    }
-    return NFAGG_OK;
+    return check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
 }
 
 int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
@@ -2449,56 +2493,37 @@ int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t 
     if (rc != NFAGG_OK) return rc;
     if (!h || !out_bytes || !d_line_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    *out_bytes = 0;
-    if (n_deferred) *n_deferred = 0;
-    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_line_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
-    const size_t blocks = (n + 1023) / 1024;
+    size_t deferred_unused;
+    if (!n_deferred) n_deferred = &deferred_unused;
+    *n_deferred = 0;
+    bool done;
+    if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
+    auto& S = h->enc;
     const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
-    if ((rc = ensure_bytes(h, &h->d_flp[0], &h->d_flp_cap[0], n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[1], &h->d_flp_cap[1], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[2], &h->d_flp_cap[2], blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[3], &h->d_flp_cap[3], (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[4], &h->d_flp_cap[4], (size_t)(opt->n_names + 1) * sizeof(nfagg_intf_name))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[5], &h->d_flp_cap[5], esc_bytes)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[6], &h->d_flp_cap[6], 16)) != NFAGG_OK) return rc;
-    // the kernels binary-search the table: stable sort by if_index keeps the scan-in-table-order answer. Names and UDNs
-    // are escaped here, once per row: neither kernel escapes per flow.
-    h->pb_names.assign(opt->names, opt->names + opt->n_names);
-    std::stable_sort(h->pb_names.begin(), h->pb_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
-    h->flp_esc.assign(esc_bytes, 0);
-    flp_escape_row(h->flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
+    if ((rc = ensure_buf(h, S.flp_rows, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.flp_esc, esc_bytes)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.flp_n_deferred, 16)) != NFAGG_OK) return rc;
+    // names and UDNs are escaped here, once per row of the sorted table: neither kernel escapes per flow
+    S.h_flp_esc.assign(esc_bytes, 0);
+    flp_escape_row(S.h_flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
     for (uint32_t k = 0; k < opt->n_names; k++) {
-        const nfagg_intf_name& e = h->pb_names[k];
-        flp_escape_row(h->flp_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
+        const nfagg_intf_name& e = S.h_names[k];
+        flp_escape_row(S.h_flp_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
     }
-    if (opt->n_names)
-        HIP_TRY(h, hipMemcpyAsync(h->d_flp[4], h->pb_names.data(), opt->n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_flp[5], h->flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_flp[6], 0, 16, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(S.flp_esc.p, S.h_flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
+    uint32_t* rows = (uint32_t*)S.flp_rows.p;
     FlpParams P{};
-    P.now_sec = opt->now_unix_ns / 1000000000ll; P.now_nsec = opt->now_unix_ns % 1000000000ll;
-    if (P.now_nsec < 0) { P.now_nsec += 1000000000ll; P.now_sec -= 1; }
+    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
     P.mono_now = opt->mono_now_ns;
     P.time_received = opt->time_received_s;
-    P.names = (const nfagg_intf_name*)h->d_flp[4]; P.esc = (const uint8_t*)h->d_flp[5]; P.n_names = opt->n_names;
+    P.names = (const nfagg_intf_name*)S.names.p; P.esc = (const uint8_t*)S.flp_esc.p; P.n_names = opt->n_names;
     P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
-    hipError_t e = launch_flp_size(d_records, n, P, (uint32_t*)h->d_flp[0], (uint32_t*)h->d_flp[1], (uint32_t*)h->d_flp[2],
-                                   (uint64_t*)h->d_flp[3], (uint32_t*)h->d_flp[6], h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "FLP JSON size launch failed: %s", hipGetErrorString(e));
-    uint64_t total = 0;
-    uint32_t deferred = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)h->d_flp[3] + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&deferred, h->d_flp[6], sizeof deferred, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *out_bytes = (size_t)total;
-    if (n_deferred) *n_deferred = deferred;
-    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
-    e = launch_flp_write(d_records, n, P, (const uint32_t*)h->d_flp[0], (const uint32_t*)h->d_flp[1], (const uint64_t*)h->d_flp[3],
-                         d_out, d_line_offsets, d_deferred, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "FLP JSON write launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
+    return encode_two_pass(h, n, "FLP JSON", "write", d_out, out_cap, out_bytes, n_deferred,
+        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+            return launch_flp_size(d_records, n, P, rows, local_off, block_sum, block_base, (uint32_t*)S.flp_n_deferred.p, h->stream); },
+        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+            return launch_flp_write(d_records, n, P, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
 }
 
 int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
@@ -2507,20 +2532,10 @@ int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const 
     int rc = encode_flp_check(h, opt);
     if (rc != NFAGG_OK) return rc;
     if (!h || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = ensure_bytes(h, &h->d_flp[7], &h->d_flp_cap[7], n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[8], &h->d_flp_cap[8], out_cap + 32)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[9], &h->d_flp_cap[9], (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_flp[10], &h->d_flp_cap[10], n + 16)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_flp[7], records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    rc = nfagg_encode_flp_json_device(h, h->d_flp[7], n, opt, out ? h->d_flp[8] : nullptr, out_cap, (uint64_t*)h->d_flp[9],
-                                      deferred ? (uint8_t*)h->d_flp[10] : nullptr, n_deferred, out_bytes);
-    if (rc != NFAGG_OK) return rc;
-    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, h->d_flp[8], *out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(line_offsets, h->d_flp[9], (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    if (deferred && n) HIP_TRY(h, hipMemcpyAsync(deferred, h->d_flp[10], n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
+    return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
+        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
+            return nfagg_encode_flp_json_device(h, d_records, n, opt, d_out, out_cap, d_offsets,
+                                                deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
 }
 
 #ifdef NFAGG_DIAG

@@ -1,5 +1,7 @@
-// nfagg_encode.h — device pieces the export encoders share (nfagg_pb.hip: protobuf, nfagg_ipfix.hip: IPFIX):
-// byte sinks, the flow's wall-clock time, the interface-namer lookup and its LDS staging, address words.
+// nfagg_encode.h — device pieces the export encoders share (nfagg_pb.hip: protobuf, nfagg_ipfix.hip: IPFIX,
+// nfagg_flp.hip: direct-FLP JSON): byte sinks, the flow's wall-clock time, the interface-namer lookup and its LDS
+// staging, address words, and the two-pass skeleton around the per-format code: the size kernels'
+// block scan, the write kernels' wave image and its copy-out.
 #pragma once
 #include "nfagg_device.h"
 
@@ -81,8 +83,61 @@ NF_DEV uint64_t mac_be(uint64_t mac_le48) {   // Rec::smac() holds byte 0 in the
     return v;
 }
 
-// Both encoders' size kernels run kScanBlock records per workgroup and scan the message lengths inside it; the
-// block sums go through launch_scan_block_sums (nfagg_internal.h).
+// ---- the two-pass skeleton. Every size kernel runs kScanBlock records per workgroup and scans their lengths inside it
+// (block_scan); the block sums go through launch_scan_block_sums (nfagg_internal.h, nfagg_encode.hip). Every write kernel
+// runs one wave per 64 records: it builds the wave's bytes in LDS (WaveImage) and copies them out (copy_image_out).
 constexpr int kScanBlock = 1024;
+
+// Block-local exclusive scan of one length per thread: inclusive scan inside the wave, then across the 16 waves
+// (wave_tot: kScanBlock / 64 words of LDS). Record i < n gets local_off[i]; the block's total goes to block_sum.
+NF_DEV void block_scan(uint32_t len, uint64_t i, uint64_t n, uint32_t* wave_tot, uint32_t* local_off, uint32_t* block_sum) {
+    uint32_t v = len;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= d) v += o; }
+    if (lane == 63) wave_tot[wave] = v;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int w = 0; w < wave; w++) base += wave_tot[w];
+    if (i < n) local_off[i] = base + v - len;
+    if (threadIdx.x == kScanBlock - 1) block_sum[blockIdx.x] = base + v;
+}
+
+// Where record i starts in the output, from the two scans.
+NF_DEV uint64_t record_off(const uint64_t* block_base, const uint32_t* local_off, uint64_t i) {
+    return block_base[i / kScanBlock] + local_off[i];
+}
+
+// The LDS image of the 64 consecutive records from i0 on: their bytes are contiguous in the output, from wave_base.
+// The image has the destination's 16-byte alignment: output byte wave_base is image byte `shift`, and image byte c goes
+// to dst[c]. close() takes where each lane's record ends (0 beyond n) and finds where the wave's bytes end.
+struct WaveImage {
+    uint64_t wave_base, end;
+    uint32_t shift, span;          // the wave's bytes: image bytes [shift, span)
+    uint8_t* dst;                  // 16-byte aligned
+    NF_DEV WaveImage(const uint64_t* block_base, const uint32_t* local_off, uint64_t i0)
+        : wave_base(record_off(block_base, local_off, i0)), shift((uint32_t)(wave_base & 15)) {}
+    NF_DEV uint32_t pos(uint64_t off) const { return shift + (uint32_t)(off - wave_base); }   // image byte of output byte off
+    NF_DEV void close(uint64_t my_end, uint8_t* out) {
+        end = my_end;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(end, d, 64); end = o > end ? o : end; }
+        span = pos(end);
+        dst = out + (wave_base - shift);
+    }
+};
+
+// Image bytes [lo, hi) -> dst, by a wave; lds[0] is image byte `base` (a multiple of 16). Aligned 16-byte stores for
+// the chunks wholly inside [lo, hi); the partial chunk at either end goes out bytewise, the neighbouring window or wave
+// writes the rest of it.
+NF_DEV void copy_image_out(uint8_t* dst, const uint8_t* lds, uint32_t base, uint32_t lo, uint32_t hi) {
+    for (uint32_t c = base + threadIdx.x * 16; c < hi; c += 64 * 16) {
+        if (c >= lo && c + 16 <= hi) {
+            *reinterpret_cast<uint4*>(dst + c) = *reinterpret_cast<const uint4*>(lds + (c - base));
+        } else {
+            for (uint32_t b = c < lo ? lo : c; b < c + 16 && b < hi; b++) dst[b] = lds[b - base];
+        }
+    }
+}
 
 }  // namespace nfagg

@@ -11,7 +11,7 @@
 //   AgentIP [Bytes] [Dscp] [DstAddr] DstMac [DstPort] Etype [Flags] [IcmpCode] [IcmpType] IfDirections Interfaces
 //   [Packets] [Proto] [Sampling] [SrcAddr] SrcMac [SrcPort] [TLSTypes] TimeFlowEndMs TimeFlowStartMs TimeReceived Udns
 //
-// Three kernels: sizes + block-local scan, scan of the block sums (shared with nfagg_pb.hip), write. One encoder
+// The two-pass skeleton of nfagg_encode.h. One encoder
 // (encode_line) serves both passes: over a counting sink it adds digit counts (compares against powers of ten) and the
 // escaped names' lengths, it never forms a digit or touches a name's bytes. Names and UDNs come escaped and quoted
 // from the table the host escaped once per call. A wave writes its 64 lines into an LDS window of kFlpWindow bytes at
@@ -29,17 +29,13 @@ constexpr uint32_t kFlpWindow = 28672;                       // line starts a wi
 constexpr uint32_t kFlpLds = kFlpWindow + (kFlpMaxLine + 15) / 16 * 16;
 static_assert(kFlpLds <= 32768, "four waves per compute unit");
 
-// ---- sinks: FlpCount only measures, FlpLds writes through a pointer
-struct FlpCount {
-    uint32_t n = 0;
-    NF_DEV void put(uint8_t) { n++; }
-};
+// ---- sinks: CountSink (nfagg_encode.h) only measures, FlpLds writes through a pointer
 struct FlpLds {
     uint8_t* p;
     NF_DEV void put(uint8_t b) { *p++ = b; }
 };
 template <typename S> struct is_count { static constexpr bool value = false; };
-template <> struct is_count<FlpCount> { static constexpr bool value = true; };
+template <> struct is_count<CountSink> { static constexpr bool value = true; };
 
 template <typename S, size_t N> NF_DEV void lit(S& s, const char (&a)[N]) {
     if constexpr (is_count<S>::value) s.n += (uint32_t)(N - 1);
@@ -180,7 +176,7 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
     return k == 0 ? r.d[24] & 0xffu : k <= 4 ? (r.d[25] >> (8 * (k - 1))) & 0xffu : (r.d[26] >> (8 * (k - 5))) & 0xffu;
 }
 
-// One line. Same code measures (FlpCount) and writes (FlpLds).
+// One line. Same code measures (CountSink) and writes (FlpLds).
 template <typename S> NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (&row)[7]) {
     const uint32_t eth = r.eth(), proto = r.d[9] & 0xffu;
     const bool ip = eth == 0x0800u || eth == 0x86DDu;
@@ -271,23 +267,15 @@ __global__ __launch_bounds__(kScanBlock) void k_flp_size(const void* __restrict_
         uint32_t row[7];
         flp_rows(tab, P.n_names, r, row);
         deferred = flp_deferred(r);
-        if (!deferred) { FlpCount c; encode_line(c, r, P, row); len = c.n; }
+        if (!deferred) { CountSink c; encode_line(c, r, P, row); len = c.n; }
         uint4* o = reinterpret_cast<uint4*>(rows + i * 8);
         o[0] = make_uint4(row[0], row[1], row[2], row[3]);
         o[1] = make_uint4(row[4], row[5], row[6], len);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const uint64_t dm = __ballot(deferred);
     if (lane == 0 && dm) atomicAdd(n_deferred, (uint32_t)__popcll(dm));
-    uint32_t v = len;
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) { const uint32_t o = __shfl_up(v, k, 64); if (lane >= k) v += o; }
-    if (lane == 63) wave_tot[wave] = v;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; w++) base += wave_tot[w];
-    if (i < n) local_off[i] = base + v - len;
-    if (threadIdx.x == kScanBlock - 1) block_sum[blockIdx.x] = base + v;
+    block_scan(len, i, n, wave_tot, local_off, block_sum);
 }
 
 // ---- kernel 3: write. One wave per 64 consecutive records; their lines are contiguous in the output. The wave moves a
@@ -300,8 +288,7 @@ __global__ __launch_bounds__(64) void k_flp_write(const void* __restrict__ recs,
                                                   uint64_t* __restrict__ line_offsets, uint8_t* __restrict__ deferred) {
     __shared__ __align__(16) uint8_t lds[kFlpLds];
     const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
-    const uint64_t wave_base = block_base[i0 / kScanBlock] + local_off[i0];
-    const uint32_t shift = (uint32_t)(wave_base & 15);       // the LDS image has the alignment of the destination
+    WaveImage w(block_base, local_off, i0);
     uint64_t my_off = 0; uint32_t my_len = 0;
     uint32_t row[7] = {};
     Rec r;
@@ -311,33 +298,23 @@ __global__ __launch_bounds__(64) void k_flp_write(const void* __restrict__ recs,
         const uint4 a = q[0], b = q[1];
         row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w; row[4] = b.x; row[5] = b.y; row[6] = b.z;
         my_len = b.w;
-        my_off = block_base[i / kScanBlock] + local_off[i];
+        my_off = record_off(block_base, local_off, i);
         line_offsets[i] = my_off;
         if (i == n - 1) line_offsets[n] = my_off + my_len;
         if (deferred) deferred[i] = my_len == 0 ? 1 : 0;     // every line that is written has at least its braces
     }
-    uint64_t end = my_off + my_len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(end, d, 64); end = o > end ? o : end; }
-    const uint32_t span = shift + (uint32_t)(end - wave_base);   // image bytes [shift, span)
-    const uint32_t p0 = shift + (uint32_t)(my_off - wave_base);  // my line = image bytes [p0, p0 + my_len)
-    uint8_t* dst = out + (wave_base - shift);                     // 16-byte aligned
-    uint32_t lo = shift;
-    while (lo < span) {
+    w.close(my_off + my_len, out);
+    const uint32_t p0 = w.pos(my_off);                            // my line = image bytes [p0, p0 + my_len)
+    uint32_t lo = w.shift;
+    while (lo < w.span) {
         const uint32_t base = lo & ~15u;
         const bool mine = my_len && p0 >= lo && p0 - base < kFlpWindow;
         if (mine) { FlpLds s{lds + (p0 - base)}; encode_line(s, r, P, row); }
-        uint32_t hi = mine ? p0 + my_len : lo;                    // the window's end: at most base + kFlpWindow + kFlpMaxLine
+        uint32_t hi = mine ? p0 + my_len : lo;                  // the window's end: at most base + kFlpWindow + kFlpMaxLine
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(hi, d, 64); hi = o > hi ? o : hi; }
         __syncthreads();
-        for (uint32_t c = base + threadIdx.x * 16; c < hi; c += 64 * 16) {
-            if (c >= lo && c + 16 <= hi) {
-                *reinterpret_cast<uint4*>(dst + c) = *reinterpret_cast<const uint4*>(lds + (c - base));
-            } else {     // the partial first / last 16 bytes: the neighbouring window or wave writes the rest of them
-                for (uint32_t b = c < lo ? lo : c; b < c + 16 && b < hi; b++) dst[b] = lds[b - base];
-            }
-        }
+        copy_image_out(w.dst, lds, base, lo, hi);
         __syncthreads();
         lo = hi;
     }

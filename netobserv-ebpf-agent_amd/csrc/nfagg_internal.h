@@ -290,7 +290,7 @@ hipError_t launch_merge_build(const MergeIn& in, void* d_slots, uint32_t n_slots
                               uint32_t* d_local_off, uint32_t* d_block_sum, hipStream_t s);
 hipError_t launch_merge_fold(const MergeIn& in, const MergeOut& out, const void* d_slots, const uint32_t* d_slot_of,
                              const uint32_t* d_local_off, const uint64_t* d_block_base, hipStream_t s);
-// exclusive scan of n_blocks block sums into d_block_base[0..n_blocks], total at [n_blocks] (nfagg_pb.hip)
+// exclusive scan of n_blocks block sums into d_block_base[0..n_blocks], total at [n_blocks] (nfagg_encode.hip)
 hipError_t launch_scan_block_sums(const uint32_t* d_block_sum, uint32_t n_blocks, uint64_t* d_block_base, hipStream_t s);
 
 }  // namespace nfagg

@@ -13,9 +13,8 @@
 // shifts everything after them by 24: 117 + L bytes.
 //
 // Fixed layout, no varints: the size pass only has to resolve the interface name (kept as a row index for the write
-// pass). Three kernels: sizes + block-local scan, scan of the block sums (shared with nfagg_pb.hip), write. A wave
-// writes its 64 messages (at most 64 x 133 B) into one LDS image at their final relative byte positions and copies
-// it out with aligned 16-byte stores.
+// pass). The two-pass skeleton of nfagg_encode.h; its own: a wave's 64 messages (at most 64 x 133 B) fit one LDS
+// image, written once through plain pointers.
 #include "nfagg_encode.h"
 #include "nfagg_ipfix.h"
 
@@ -57,16 +56,7 @@ __global__ __launch_bounds__(kScanBlock) void k_ipfix_size(const void* __restric
         name_row[i] = ipfix_name_row(tab, P.n_names, d, nl, P.unknown_len);
         len = ipfix_len(d[1] & 0xffffu, nl);
     }
-    uint32_t v = len;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) { const uint32_t o = __shfl_up(v, k, 64); if (lane >= k) v += o; }
-    if (lane == 63) wave_tot[wave] = v;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; w++) base += wave_tot[w];
-    if (i < n) local_off[i] = base + v - len;
-    if (threadIdx.x == kScanBlock - 1) block_sum[blockIdx.x] = base + v;
+    block_scan(len, i, n, wave_tot, local_off, block_sum);
 }
 
 // big-endian N-byte value at p (LDS)
@@ -127,8 +117,7 @@ __global__ __launch_bounds__(64) void k_ipfix_write(const void* __restrict__ rec
                                                     uint64_t* __restrict__ msg_offsets) {
     __shared__ __align__(16) uint8_t img[kIpfixImage];
     const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
-    const uint64_t wave_base = block_base[i0 / kScanBlock] + local_off[i0];
-    const uint32_t shift = (uint32_t)(wave_base & 15);       // the LDS image has the alignment of the destination
+    WaveImage w(block_base, local_off, i0);
     uint64_t end = 0;
     if (i < n) {
         Rec r;
@@ -141,24 +130,15 @@ __global__ __launch_bounds__(64) void k_ipfix_write(const void* __restrict__ rec
             nw[0] = e[3]; nw[1] = e[4]; nw[2] = e[5]; nw[3] = e[6];
         }
         const uint32_t len = ipfix_len(r.eth(), nlen);
-        const uint64_t off = block_base[i / kScanBlock] + local_off[i];
+        const uint64_t off = record_off(block_base, local_off, i);
         msg_offsets[i] = off;
         if (i == n - 1) msg_offsets[n] = off + len;
         end = off + len;
-        write_message(img + shift + (uint32_t)(off - wave_base), r, P, P.seq0 + (uint32_t)i, len, nw, nlen);
+        write_message(img + w.pos(off), r, P, P.seq0 + (uint32_t)i, len, nw, nlen);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(end, d, 64); end = o > end ? o : end; }
-    const uint32_t span = shift + (uint32_t)(end - wave_base);   // image bytes [shift, span)
-    uint8_t* dst = out + (wave_base - shift);                     // 16-byte aligned
+    w.close(end, out);
     __syncthreads();
-    for (uint32_t c = threadIdx.x * 16; c < span; c += 64 * 16) {
-        if (c >= shift && c + 16 <= span) {
-            *reinterpret_cast<uint4*>(dst + c) = *reinterpret_cast<const uint4*>(img + c);
-        } else {     // the partial first / last 16 bytes: the neighbouring waves write the rest of them
-            for (uint32_t b = c < shift ? shift : c; b < c + 16 && b < span; b++) dst[b] = img[b];
-        }
-    }
+    copy_image_out(w.dst, img, 0, w.shift, w.span);
 }
 
 hipError_t launch_ipfix_size(const void* d_recs, uint64_t n, const IpfixParams& P, uint32_t* d_name_row, uint32_t* d_local_off,

@@ -17,10 +17,8 @@
 // record.go:116-125) — with a nil SampleDecoder (record.go:126): network events are not decoded.
 //
 // Byte-granular, HBM-bound streaming work: 144 B read + ~110 B written per record (more with
-// features). Three kernels: sizes + block-local scan, scan of the block sums, encode. A wave
-// encodes its 64 records into LDS at their final relative byte positions (consecutive records are
-// contiguous in the output), one 16 KiB window of the output at a time, and copies each window out
-// with aligned 16-byte stores.
+// features). The two-pass skeleton of nfagg_encode.h; its own: a wave's image is encoded one fixed
+// window at a time (8, 16 or 24 KiB), the whole encoder running once per window the wave's frames span.
 #include "nfagg_encode.h"
 #include "nfagg_pb.h"
 
@@ -242,40 +240,14 @@ __global__ __launch_bounds__(kScanBlock) void k_pb_size(const void* __restrict__
         body_len[i] = c.n;
         frame = 1 + varint_len(c.n) + c.n;
     }
-    // inclusive scan inside the wave, then across the 16 waves
-    uint32_t v = frame;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d, 64); if (lane >= d) v += o; }
-    if (lane == 63) wave_tot[wave] = v;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; w++) base += wave_tot[w];
-    if (i < n) local_off[i] = base + v - frame;
-    if (threadIdx.x == kScanBlock - 1) block_sum[blockIdx.x] = base + v;
-}
-
-// ---- kernel 2: exclusive scan of the block sums (one workgroup), total in block_base[n_blocks]
-__global__ __launch_bounds__(1024) void k_pb_scan_blocks(const uint32_t* __restrict__ block_sum, uint32_t n_blocks,
-                                                         uint64_t* __restrict__ block_base) {
-    __shared__ uint64_t part[1024];
-    const uint32_t per = (n_blocks + 1023) / 1024;
-    const uint32_t lo = threadIdx.x * per, hi = (lo + per < n_blocks) ? lo + per : n_blocks;
-    uint64_t s = 0;
-    for (uint32_t k = lo; k < hi; k++) s += block_sum[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { uint64_t acc = 0; for (int k = 0; k < 1024; k++) { const uint64_t x = part[k]; part[k] = acc; acc += x; } block_base[n_blocks] = acc; }
-    __syncthreads();
-    uint64_t acc = part[threadIdx.x];
-    for (uint32_t k = lo; k < hi; k++) { block_base[k] = acc; acc += block_sum[k]; }
+    block_scan(frame, i, n, wave_tot, local_off, block_sum);
 }
 
 // ---- kernel 3: encode. One wave per 64 consecutive records, one kPbWindow-byte window of its output at a time.
 // The window (LDS per wave, beside 2 KiB of DNS-name slots and the 8.6 KiB namer table) is chosen by the host from the
 // average frame length the size pass found: the whole encoder runs once per window a wave's 64 frames span, so the
 // window should hold them all (64 x ~110 B for Accounter records, 64 x ~270 B with every feature part).
-// (a frame is at most 1033 bytes, DESIGN.md §4.7: any window of at least that size makes progress)
+// (a frame is at most 1033 bytes, DESIGN.md §4.7a: any window of at least that size makes progress)
 
 template <uint32_t kPbWindow>
 __global__ __launch_bounds__(64) void k_pb_write(const void* __restrict__ recs, uint64_t n, PbParams P, PbFeat F,
@@ -287,14 +259,13 @@ __global__ __launch_bounds__(64) void k_pb_write(const void* __restrict__ recs, 
     __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
     const uint8_t* tab = stage_names<64>(P.names, P.n_names, tab_lds);
     const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
-    const uint64_t wave_base = block_base[i0 / kScanBlock] + local_off[i0];
-    const uint32_t shift = (uint32_t)(wave_base & 15);       // the LDS image has the alignment of the destination
+    WaveImage w(block_base, local_off, i0);
     uint64_t my_off = 0; uint32_t my_len = 0, bl = 0;
     Rec r;
     if (i < n) {
         load_record(recs, i, r);
         r.canonicalize();
-        my_off = block_base[i / kScanBlock] + local_off[i];
+        my_off = record_off(block_base, local_off, i);
         bl = body_len[i];
         my_len = 1 + varint_len(bl) + bl;
         frame_offsets[i] = my_off;
@@ -311,15 +282,10 @@ __global__ __launch_bounds__(64) void k_pb_write(const void* __restrict__ recs, 
         }
         if (i == n - 1) frame_offsets[n] = my_off + my_len;
     }
-    // total bytes of this wave = end of its last valid record
-    uint64_t end = my_off + my_len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(end, d, 64); end = o > end ? o : end; }
-    const uint32_t span = shift + (uint32_t)(end - wave_base);   // image bytes [shift, span)
-    const uint32_t p0 = shift + (uint32_t)(my_off - wave_base);  // my frame = image bytes [p0, p0 + my_len)
-    uint8_t* dst = out + (wave_base - shift);                     // 16-byte aligned
-    for (uint32_t lo = 0; lo < span; lo += kPbWindow) {
-        const uint32_t hi = lo + kPbWindow < span ? lo + kPbWindow : span;
+    w.close(my_off + my_len, out);
+    const uint32_t p0 = w.pos(my_off);                            // my frame = image bytes [p0, p0 + my_len)
+    for (uint32_t lo = 0; lo < w.span; lo += kPbWindow) {
+        const uint32_t hi = lo + kPbWindow < w.span ? lo + kPbWindow : w.span;
         if (my_len && p0 < hi && p0 + my_len > lo) {
             WindowSink s{lds, p0, lo, hi - lo};
             s.put(0x0A);                                          // Records.entries = 1, length-delimited
@@ -327,13 +293,7 @@ __global__ __launch_bounds__(64) void k_pb_write(const void* __restrict__ recs, 
             encode_record(s, r, P, F, i, name_lds[threadIdx.x], tab);
         }
         __syncthreads();
-        for (uint32_t c = lo + threadIdx.x * 16; c < hi; c += 64 * 16) {
-            if (c >= shift && c + 16 <= hi) {
-                *reinterpret_cast<uint4*>(dst + c) = *reinterpret_cast<const uint4*>(lds + (c - lo));
-            } else {
-                for (uint32_t b = c < shift ? shift : c; b < c + 16 && b < hi; b++) dst[b] = lds[b - lo];
-            }
-        }
+        copy_image_out(w.dst, lds, lo, w.shift, hi);              // from max(lo, shift): lo is 0 or beyond any shift
         __syncthreads();
     }
 }
@@ -345,14 +305,7 @@ hipError_t launch_pb_size(const void* d_recs, uint64_t n, const PbParams& P, con
     hipLaunchKernelGGL(k_pb_size, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_body_len, d_local_off, d_block_sum);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pb_scan_blocks, dim3(1), dim3(1024), 0, s, d_block_sum, blocks, d_block_base);
-    return hipGetLastError();
-}
-
-hipError_t launch_scan_block_sums(const uint32_t* d_block_sum, uint32_t n_blocks, uint64_t* d_block_base, hipStream_t s) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_pb_scan_blocks, dim3(1), dim3(1024), 0, s, d_block_sum, n_blocks, d_block_base);
-    return hipGetLastError();
+    return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
 }
 
 hipError_t launch_pb_write(const void* d_recs, uint64_t n, const PbParams& P, const PbFeat& F, const uint32_t* d_body_len, const uint32_t* d_local_off,

@@ -328,14 +328,22 @@ class FlowTable:
     # -- misc
     # -- export encode (record -> protobuf), nfagg_encode_pb
     def _pb_options(self, now_unix_ns, mono_now_ns, agent_ip16, names, unknown):
-        o = L.PbOptions()
-        o.struct_size = C.sizeof(L.PbOptions)
-        o.now_unix_ns, o.mono_now_ns = now_unix_ns, mono_now_ns
+        o, names = _encode_options(L.PbOptions, now_unix_ns, mono_now_ns, names, unknown)
         o.agent_ip[:] = list(bytes(agent_ip16))
-        names = np.ascontiguousarray(names)
-        o.names, o.n_names = (names.ctypes.data if len(names) else None), len(names)
-        o.unknown_name, o.unknown_len = unknown, len(unknown)
         return o, names
+
+    def _encode_grown(self, n, per_flow, call):
+        """The host-memory encoders' output buffer: per_flow bytes per flow as a first guess; on TRUNCATED, the size the
+        library reported. call(buf pointer, cap, need) -> rc. Returns the bytes written."""
+        need = C.c_size_t(0)
+        cap = max(per_flow * n, 64)
+        while True:
+            buf = np.zeros(cap, dtype=np.uint8)
+            rc = call(buf.ctypes.data_as(C.c_void_p), cap, C.byref(need))
+            if rc != L.TRUNCATED:
+                self._check(rc)
+                return buf[: need.value]
+            cap = need.value
 
     @staticmethod
     def _pb_features(n, present, parts, device=False):
@@ -375,22 +383,12 @@ class FlowTable:
         off = np.zeros(n + 1, dtype=np.uint64)
         blen = np.zeros(max(n, 1), dtype=np.uint32)
         keys = np.zeros((max(n, 1), 32), dtype=np.uint8) if kafka_keys else None
-        need = C.c_size_t(0)
-        cap = max(256 * n, 64)
-        while True:
-            buf = np.zeros(cap, dtype=np.uint8)
-            tail = (C.byref(o), buf.ctypes.data_as(C.c_void_p), cap, off.ctypes.data_as(C.c_void_p), blen.ctypes.data_as(C.c_void_p),
-                    keys.ctypes.data_as(C.c_void_p) if kafka_keys else None, C.byref(need))
-            if feat is None:
-                rc = L.lib.nfagg_encode_pb(self._h, r.ctypes.data_as(C.c_void_p), n, *tail)
-            else:
-                rc = L.lib.nfagg_encode_pb_content(self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat), *tail)
-            if rc == L.TRUNCATED:
-                cap = need.value
-                continue
-            self._check(rc)
-            break
-        out = (buf[: need.value], off, blen[:n])
+        head = (self._h, r.ctypes.data_as(C.c_void_p), n) + ((C.byref(feat),) if feat is not None else ())
+        fn = L.lib.nfagg_encode_pb if feat is None else L.lib.nfagg_encode_pb_content
+        buf = self._encode_grown(n, 256, lambda p, cap, need: fn(
+            *head, C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p), blen.ctypes.data_as(C.c_void_p),
+            keys.ctypes.data_as(C.c_void_p) if kafka_keys else None, need))
+        out = (buf, off, blen[:n])
         return out + (keys[:n],) if kafka_keys else out
 
     def encode_pb_device(self, d_records: int, n: int, now_unix_ns: int, mono_now_ns: int, agent_ip16: bytes, names: np.ndarray,
@@ -419,18 +417,9 @@ class FlowTable:
         n = r.nbytes // 144
         o, keep = ipfix_options(now_unix_ns, mono_now_ns, names, export_time_s, seq0, unknown, obs_domain_id)
         off = np.zeros(n + 1, dtype=np.uint64)
-        need = C.c_size_t(0)
-        cap = max(120 * n, 64)
-        while True:
-            buf = np.zeros(cap, dtype=np.uint8)
-            rc = L.lib.nfagg_encode_ipfix(self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(o), buf.ctypes.data_as(C.c_void_p), cap,
-                                          off.ctypes.data_as(C.c_void_p), C.byref(need))
-            if rc == L.TRUNCATED:
-                cap = need.value
-                continue
-            self._check(rc)
-            break
-        return buf[: need.value], off
+        buf = self._encode_grown(n, 120, lambda p, cap, need: L.lib.nfagg_encode_ipfix(
+            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p), need))
+        return buf, off
 
     def encode_ipfix_device(self, d_records: int, n: int, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, export_time_s: int,
                             seq0: int, d_out: int, out_cap: int, d_msg_offsets: int, unknown: bytes = b"unknown", obs_domain_id: int = 1):
@@ -454,20 +443,12 @@ class FlowTable:
         o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
         off = np.zeros(n + 1, dtype=np.uint64)
         deferred = np.zeros(n, dtype=np.uint8)
-        need, n_def = C.c_size_t(0), C.c_size_t(0)
-        cap = max(448 * n, 64)
-        while True:
-            buf = np.zeros(cap, dtype=np.uint8)
-            rc = L.lib.nfagg_encode_flp_json(self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(o), buf.ctypes.data_as(C.c_void_p), cap,
-                                             off.ctypes.data_as(C.c_void_p), deferred.ctypes.data_as(C.c_void_p), C.byref(n_def),
-                                             C.byref(need))
-            if rc == L.TRUNCATED:
-                cap = need.value
-                continue
-            self._check(rc)
-            break
+        n_def = C.c_size_t(0)
+        buf = self._encode_grown(n, 448, lambda p, cap, need: L.lib.nfagg_encode_flp_json(
+            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p),
+            deferred.ctypes.data_as(C.c_void_p), C.byref(n_def), need))
         assert int(deferred.sum()) == n_def.value
-        return buf[: need.value], off, deferred
+        return buf, off, deferred
 
     def encode_flp_json_device(self, d_records: int, n: int, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip,
                                time_received: int, d_out: int, out_cap: int, d_line_offsets: int, d_deferred: int = 0,
@@ -644,15 +625,22 @@ class FlowGroup:
 IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6 = 256, 257      # go-ipfix NewTemplateID() from 255: v4 is created first
 
 
-def ipfix_options(now_unix_ns=0, mono_now_ns=0, names=None, export_time_s=0, seq0=0, unknown=b"unknown", obs_domain_id=1,
-                  template_ids=(IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6)):
-    """nfagg_ipfix_options; returns (options, the names array the options point into: keep it alive for the call)."""
-    o = L.IpfixOptions()
-    o.struct_size = C.sizeof(L.IpfixOptions)
+def _encode_options(cls, now_unix_ns, mono_now_ns, names, unknown):
+    """What the three encoders' option structs share: the clocks, the namer table, the unknown name. Returns (options, the
+    names array the options point into: keep it alive for the call)."""
+    o = cls()
+    o.struct_size = C.sizeof(cls)
     o.now_unix_ns, o.mono_now_ns = now_unix_ns, mono_now_ns
     names = np.ascontiguousarray(names if names is not None else np.zeros(0, dtype=INTF_NAME))
     o.names, o.n_names = (names.ctypes.data if len(names) else None), len(names)
     o.unknown_name, o.unknown_len = unknown, len(unknown)
+    return o, names
+
+
+def ipfix_options(now_unix_ns=0, mono_now_ns=0, names=None, export_time_s=0, seq0=0, unknown=b"unknown", obs_domain_id=1,
+                  template_ids=(IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6)):
+    """nfagg_ipfix_options; returns (options, the names array the options point into: keep it alive for the call)."""
+    o, names = _encode_options(L.IpfixOptions, now_unix_ns, mono_now_ns, names, unknown)
     o.export_time_s, o.seq0, o.obs_domain_id = export_time_s & 0xFFFFFFFF, seq0 & 0xFFFFFFFF, obs_domain_id
     o.template_id_v4, o.template_id_v6 = template_ids
     return o, names
@@ -661,12 +649,7 @@ def ipfix_options(now_unix_ns=0, mono_now_ns=0, names=None, export_time_s=0, seq
 def flp_options(now_unix_ns=0, mono_now_ns=0, names=None, agent_ip=None, time_received=0, unknown=b"unknown"):
     """nfagg_flp_options; returns (options, the names array the options point into: keep it alive for the call).
     agent_ip: 16 bytes, 4 bytes (stored v4-mapped, as net.IP prints both alike) or None (nil)."""
-    o = L.FlpOptions()
-    o.struct_size = C.sizeof(L.FlpOptions)
-    o.now_unix_ns, o.mono_now_ns = now_unix_ns, mono_now_ns
-    names = np.ascontiguousarray(names if names is not None else np.zeros(0, dtype=INTF_NAME))
-    o.names, o.n_names = (names.ctypes.data if len(names) else None), len(names)
-    o.unknown_name, o.unknown_len = unknown, len(unknown)
+    o, names = _encode_options(L.FlpOptions, now_unix_ns, mono_now_ns, names, unknown)
     if agent_ip is None:
         o.agent_ip_nil = 1
     else:
