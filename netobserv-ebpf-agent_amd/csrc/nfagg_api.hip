@@ -254,7 +254,7 @@ int launch_ingest_profiled(nfagg_handle* h, const void* d, uint64_t n, uint64_t 
             // the partition pass sorts its items by sub-partition first when a partition's flows will not fit one cache (1024
             // sub-flow entries x 2048 partitions): the last epoch's flow count is the guess, the table's size before there is one
             const uint64_t guess = h->last_epoch_flows ? h->last_epoch_flows * (h->tv.subflow ? 1 : 2) : (h->cfg.max_entries > (1ull << 22) ? ~0ull : 0ull);
-            h->tv.spill.sort_first = h->cfg.ingest_variant == 16 ? 2u : (guess > 2500000ull ? 1u : 0u);    // 2: whatever the partition's size (tests)      // ~1200 sub-flows per partition: one cache (and its retry round) still holds them
+            h->tv.spill.sort_first = h->cfg.ingest_variant == kVariantDedupSortFirst ? 2u : (guess > 2500000ull ? 1u : 0u);    // 2: whatever the partition's size (tests)      // ~1200 sub-flows per partition: one cache (and its retry round) still holds them
         }
         if (h->cfg.mode == NFAGG_MODE_KERNEL_DEDUP && !h->tv.spill.xp) {     // exported cache entries of the streaming pass (38 MB)
             size_t cap = 0;
@@ -742,7 +742,7 @@ int nfagg_create(const nfagg_config* cfg_in, nfagg_handle** out) {
     if (cfg.max_entries == 0) cfg.max_entries = 5000;   // CACHE_MAX_FLOWS default (pkg/config/config.go:146)
     if (cfg.mode != NFAGG_MODE_ACCOUNTER && cfg.mode != NFAGG_MODE_KERNEL_DEDUP)
         return fail(nullptr, NFAGG_EINVAL, "unknown mode %u", cfg.mode);
-    if (!ingest_variant_supported((int)cfg.ingest_variant))
+    if (!ingest_variant_supported((int)cfg.ingest_variant, kDiagBuild))
         return fail(nullptr, NFAGG_EINVAL, "ingest_variant %u is not part of this build (phase-timing builds live in libnfagg_diag.so)", cfg.ingest_variant);
     if (cfg.cm_depth == 0) cfg.cm_depth = 4;
     if (cfg.cm_log2_width == 0) cfg.cm_log2_width = 20;
@@ -1443,8 +1443,6 @@ int nfagg_window_restart_device(nfagg_handle* h, uint32_t n_shards, uint32_t sha
 
 // ---------------------------------------------------------------- nfagg_account*: the record arm WITH its evictions on "full"
 constexpr uint64_t kAccountFastMaxEntries = 32768;   // beyond that an epoch is long enough for the optimistic fold of nfagg_ingest
-
-constexpr uint32_t kVariantAccountChain = 30;        // ingest_variant (tests): nfagg_account always takes the kernel chain
 
 // May the device-resident epoch loop (the kernel chain, nfagg_epoch_chain.hip) take this batch?
 static bool account_fast_ok(const nfagg_handle* h, size_t n, size_t out_cap) {

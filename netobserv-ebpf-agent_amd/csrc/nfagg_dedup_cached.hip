@@ -868,7 +868,7 @@ __global__ __launch_bounds__(256) void k_dedup_overflow(TableView t, SketchView 
 
 // Four launches: stream, overflow claims, partitions, overflow folds (+ the reset of the overflow tail). The sketches of sk (flags = 0:
 // none) are fed by the partition pass's flushes and the overflow folds.
-// variant 12 (A/B, tests): no retry rounds in the partition pass.
+// kVariantDedupOneRound (A/B, tests): no retry rounds in the partition pass.
 hipError_t launch_ingest_dedup_cached(const TableView& t, const SketchView& sk, const void* d_records, uint64_t n, uint64_t seq_base, int variant, hipStream_t s) {
     using namespace dcache;
     if (n == 0) return hipSuccess;
@@ -900,12 +900,12 @@ hipError_t launch_ingest_dedup_cached(const TableView& t, const SketchView& sk, 
     NF_LAUNCH(k_dedup_stream, dim3(grid), dim3(kBlock), lds1, s, t, q, d_records, n, seq_base);
     NF_LAUNCH((k_dedup_overflow<false>), dim3(32), dim3(256), 0, s, t, sk, q, d_records, n, seq_base);
 #ifdef NFAGG_DIAG
-    if (variant == 13) NF_LAUNCH(k_dedup_parts<1>, dim3(kSpillParts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base, 1);
-    else if (variant == 14) NF_LAUNCH(k_dedup_parts<3>, dim3(kSpillParts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base, 1);
-    else if (variant == 15) NF_LAUNCH(k_dedup_parts<7>, dim3(kSpillParts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base, 1);
+    if (variant == kVariantDedupNoFlush) NF_LAUNCH(k_dedup_parts<1>, dim3(kSpillParts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base, 1);
+    else if (variant == kVariantDedupNoFold) NF_LAUNCH(k_dedup_parts<3>, dim3(kSpillParts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base, 1);
+    else if (variant == kVariantDedupNoClaim) NF_LAUNCH(k_dedup_parts<7>, dim3(kSpillParts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base, 1);
     else
 #endif
-    NF_LAUNCH(k_dedup_parts<0>, dim3(kSpillParts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base, variant == 12 ? 1 : kMaxRounds);
+    NF_LAUNCH(k_dedup_parts<0>, dim3(kSpillParts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base, variant == kVariantDedupOneRound ? 1 : kMaxRounds);
     NF_LAUNCH((k_dedup_overflow<true>), dim3(32), dim3(256), 0, s, t, sk, q, d_records, n, seq_base);
 #undef NF_LAUNCH
     return hipMemsetAsync(q.ovf_tail, 0, sizeof(uint32_t), s);

@@ -235,16 +235,16 @@ hipError_t launch_ingest_cached(const TableView& t, const SketchView& sk, const 
                                 int variant, hipStream_t s) {
     const bool f = sk.flags != 0;
     switch (variant) {
-        case 3: return f ? run_cached<512, 512, true>(t, sk, d_records, n, seq_base, 2, s)       // 2 WG/CU x 64 KB
+        case kVariantCached512x2: return f ? run_cached<512, 512, true>(t, sk, d_records, n, seq_base, 2, s)       // 2 WG/CU x 64 KB
                          : run_cached<512, 512, false>(t, sk, d_records, n, seq_base, 2, s);
-        case 4: return f ? run_cached<256, 256, true>(t, sk, d_records, n, seq_base, 4, s)       // 4 WG/CU x 32 KB
+        case kVariantCached256x4: return f ? run_cached<256, 256, true>(t, sk, d_records, n, seq_base, 4, s)       // 4 WG/CU x 32 KB
                          : run_cached<256, 256, false>(t, sk, d_records, n, seq_base, 4, s);
-        case 5: return f ? run_cached<1024, 512, true>(t, sk, d_records, n, seq_base, 2, s)
+        case kVariantCached1024h: return f ? run_cached<1024, 512, true>(t, sk, d_records, n, seq_base, 2, s)
                          : run_cached<1024, 512, false>(t, sk, d_records, n, seq_base, 2, s);
 #ifdef NFAGG_DIAG
-        case 6: return run_cached<1024, 1024, false, true>(t, sk, d_records, n, seq_base, 1, s);    // diagnostics: phase timing
+        case kVariantCachedTiming: return run_cached<1024, 1024, false, true>(t, sk, d_records, n, seq_base, 1, s);    // diagnostics: phase timing
 #endif
-        default: return f ? run_cached<1024, 1024, true>(t, sk, d_records, n, seq_base, 1, s)    // 7 (and 0 for small batches): 1 WG/CU x 120 KB
+        default: return f ? run_cached<1024, 1024, true>(t, sk, d_records, n, seq_base, 1, s)    // kVariantCached (and the default for small batches): 1 WG/CU x 120 KB
                           : run_cached<1024, 1024, false>(t, sk, d_records, n, seq_base, 1, s);
     }
 }

@@ -1,4 +1,4 @@
-// nfagg_ingest_part.hip — two-pass partitioned ingest (the default from 384 Ki records per call; ingest_variant 10 forces it).
+// nfagg_ingest_part.hip — two-pass partitioned ingest (the default from 384 Ki records per call; kVariantTwoPass forces it).
 //
 // The single-pass cached kernel (nfagg_ingest_cached.hip) folds the hot head of a
 // Zipf stream in LDS, but every record of the cold tail (40 % of configs[1]) goes to
@@ -134,99 +134,6 @@ NF_DEV int cache_fold(Cache& L, int ent, const Rec& r, const uint64_t w[5], uint
     if (r.dmac() && qq.w > seq32) atomicMin(qw + 3, seq32);
     return ent;
 }
-
-#ifdef NFAGG_DIAG
-// ---- experiment (libnfagg_diag.so, ingest_variant 24; results RIGHT): a wave's duplicates combined BEFORE the LDS atomics ----------
-// The round-2/3/4 reviews asked for this to be built and measured instead of estimated (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE
-// is 56 % in pass 1: 64 lanes hit a hash-indexed cache, and ~5 lanes of every wave fold into the hottest flow). One group per
-// wave and tile: the entries of lanes 0, 16, 32 and 48 are candidates, the one most lanes share wins; its lanes' contributions
-// are reduced across the wave with DPP (row shifts + row broadcasts, identities elsewhere), ONE lane performs the entry's
-// atomics with the totals, the others of the group skip theirs. Everything else takes cache_fold as before.
-// Result: profiles/r05x_wave_combining.txt.
-template <int CTRL, int ROW_MASK>
-NF_DEV uint32_t comb_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, true); }
-template <int CTRL, int ROW_MASK>
-NF_DEV uint64_t comb_dpp64(uint64_t v) { return (uint64_t)comb_dpp<CTRL, ROW_MASK>((uint32_t)v) | ((uint64_t)comb_dpp<CTRL, ROW_MASK>((uint32_t)(v >> 32)) << 32); }
-#define NF_COMB_STEPS(OP, T, F)                                                                              \
-    v = OP(v, F<0x111, 0xf>(v)); v = OP(v, F<0x112, 0xf>(v)); v = OP(v, F<0x114, 0xf>(v)); v = OP(v, F<0x118, 0xf>(v)); \
-    v = OP(v, F<0x142, 0xa>(v)); v = OP(v, F<0x143, 0xc>(v));
-NF_DEV uint32_t comb_add32(uint32_t a, uint32_t b) { return a + b; }
-NF_DEV uint32_t comb_or32(uint32_t a, uint32_t b) { return a | b; }
-NF_DEV uint32_t comb_max32(uint32_t a, uint32_t b) { return a > b ? a : b; }
-NF_DEV uint64_t comb_add64(uint64_t a, uint64_t b) { return a + b; }
-NF_DEV uint64_t comb_max64(uint64_t a, uint64_t b) { return a > b ? a : b; }
-// the wave's total (lane 63 holds it after the steps; every lane must be active)
-NF_DEV uint32_t wave_add32(uint32_t v) { NF_COMB_STEPS(comb_add32, uint32_t, comb_dpp) return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
-NF_DEV uint32_t wave_or32(uint32_t v) { NF_COMB_STEPS(comb_or32, uint32_t, comb_dpp) return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
-NF_DEV uint32_t wave_max32(uint32_t v) { NF_COMB_STEPS(comb_max32, uint32_t, comb_dpp) return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
-NF_DEV uint64_t wave_add64(uint64_t v) {
-    NF_COMB_STEPS(comb_add64, uint64_t, comb_dpp64)
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32);
-}
-NF_DEV uint64_t wave_max64(uint64_t v) {
-    NF_COMB_STEPS(comb_max64, uint64_t, comb_dpp64)
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32);
-}
-#undef NF_COMB_STEPS
-
-// phase B for a whole wave (every lane calls it: `valid` lanes with ent >= 0 take part). Returns the lane's entry, -1 for a
-// key mismatch (as cache_fold).
-NF_DEV int cache_fold_combined(Cache& L, bool valid, int ent, const Rec& r, const uint64_t w[5], uint32_t seq32) {
-    const int lane = threadIdx.x & 63;
-    bool active = valid && ent >= 0;
-    if (active) {
-        const uint4 a = L.k0[ent], b = L.k1[ent], c = L.k2[ent];
-        active = ((u64hi(a) ^ w[0]) | (u64lo(b) ^ w[1]) | (u64hi(b) ^ w[2]) | (u64lo(c) ^ w[3]) | (u64hi(c) ^ w[4])) == 0;
-        if (!active) ent = -1;
-    }
-    const int mine = active ? ent : -1;
-    // the group: of the entries of four sample lanes the one most lanes share
-    int best_e = -1;
-    unsigned long long best_g = 0;
-#pragma unroll
-    for (int s = 0; s < 64; s += 16) {
-        const int e = __builtin_amdgcn_readlane(mine, s);
-        if (e >= 0) {
-            const unsigned long long g = __ballot(mine == e);
-            if (__popcll(g) > __popcll(best_g)) { best_g = g; best_e = e; }
-        }
-    }
-    const bool grouped = __popcll(best_g) >= 2;                       // (wave-uniform)
-    const bool member = grouped && mine == best_e;
-    if (grouped) {
-        const uint64_t s1 = (uint64_t)seq32 + 1;
-        const uint64_t bytes = wave_add64(member ? r.bytes() : 0ull);
-        const uint32_t packets = wave_add32(member ? r.packets() : 0u);
-        const uint32_t flags = wave_or32(member ? r.flags() : 0u);
-        const uint64_t end = wave_max64(member ? r.end() : 0ull);
-        const uint64_t start_inv = wave_max64(member && r.start() ? ~r.start() : 0ull);
-        const uint64_t eth_tag = wave_max64(member && r.eth() ? (s1 << 16) | r.eth() : 0ull);
-        const uint64_t dscp_tag = wave_max64(member && r.dscp() ? (s1 << 8) | r.dscp() : 0ull);
-        const uint64_t samp_tag = wave_max64(member && r.sampling() ? (s1 << 32) | r.sampling() : 0ull);
-        const uint32_t first_inv = wave_max32(member ? ~seq32 : 0u);      // (~seq32 > 0: sequence numbers stop short of 2^32 - 16)
-        const uint32_t smac_inv = wave_max32(member && r.smac() ? ~seq32 : 0u);
-        const uint32_t dmac_inv = wave_max32(member && r.dmac() ? ~seq32 : 0u);
-        if (lane == (int)__builtin_ctzll(best_g)) {                   // the group's first lane: the entry's atomics, once
-            const int e = best_e;
-            const uint4 tt = L.t[e], qq = L.q[e];
-            if (bytes) atomicAdd(lo64(&L.v[e]), (unsigned long long)bytes);
-            if (packets) atomicAdd(&L.packets[e], packets);
-            if (flags & ~qq.x) atomicOr(reinterpret_cast<uint32_t*>(&L.q[e]), flags);
-            if (end > u64lo(tt)) atomicMax(lo64(&L.t[e]), (unsigned long long)end);
-            if (start_inv > u64hi(tt)) atomicMax(hi64(&L.t[e]), (unsigned long long)start_inv);
-            if (eth_tag) atomicMax(lo64(&L.w[e]), (unsigned long long)eth_tag);
-            if (dscp_tag) atomicMax(hi64(&L.w[e]), (unsigned long long)dscp_tag);
-            if (samp_tag) atomicMax(hi64(&L.v[e]), (unsigned long long)samp_tag);
-            uint32_t* qw = reinterpret_cast<uint32_t*>(&L.q[e]);
-            if (qq.y > ~first_inv) atomicMin(qw + 1, ~first_inv);
-            if (smac_inv && qq.z > ~smac_inv) atomicMin(qw + 2, ~smac_inv);
-            if (dmac_inv && qq.w > ~dmac_inv) atomicMin(qw + 3, ~dmac_inv);
-        }
-    }
-    if (active && !member) ent = cache_fold(L, ent, r, w, seq32);      // everybody else: as before (the key was checked twice: harmless)
-    return ent;
-}
-#endif
 
 // Overflow list: spills that found their partition queue (or staging group) full.
 // Sized by the API for the worst case; pass 3 merges its records one by one.
@@ -366,26 +273,44 @@ NF_DEV uint32_t queue_entry(uint64_t i, uint64_t h, uint32_t sub_shift, uint32_t
     return e;
 }
 
+// A drained staging group goes to the position reserved in its partition's queue, or — queue full (adversarial skew) — to the
+// overflow list.
+NF_DEV void queue_store_group(const SpillView& q, uint32_t p, uint32_t at, uint4 v) {
+    if (at + kStage <= q.qcap) *reinterpret_cast<uint4*>(q.queue + (uint64_t)p * q.qcap + at) = v;
+    else overflow_push(q, v);
+}
+
+// ---- shared by the two pass-1 kernels (k_pass1, k_pass1_free) ------------------------------------------------------
+// The workgroup's dynamic LDS, carved and cleared (ends with a barrier). door: with DOOR only.
+struct Pass1Lds { Cache& L; Stage& S; uint32_t* door; };
+template <bool DOOR>
+NF_DEV Pass1Lds pass1_lds_setup(unsigned char* lds_raw, int tid) {
+    const Pass1Lds m = {*reinterpret_cast<Cache*>(lds_raw), *reinterpret_cast<Stage*>(lds_raw + sizeof(Cache)),
+                        reinterpret_cast<Door*>(lds_raw + sizeof(Cache) + sizeof(Stage))->bits};
+    cache_init(m.L, tid);
+    for (int p = tid; p < kSpillParts; p += kBlock) m.S.cnt[p] = 0;
+    if (DOOR) for (int p = tid; p < kDoorBits / 32; p += kBlock) m.door[p] = 0;
+    __syncthreads();
+    return m;
+}
+
 // ---- pass 1 ------------------------------------------------------------------------------------------------------
 // 256 workgroups stream records[0..n), tiles of 1024 consecutive records, one per lane. Hot flows fold in the workgroup's
 // persistent LDS cache; a record whose flow has no entry is spilled: its index goes to the queue of its flow's partition,
 // staged four at a time in LDS so that a spill costs one 16-byte store and a quarter of an atomic.
-// ABL (libnfagg_diag.so only, ingest_variant 20..27: timing experiments, results are WRONG): bit 0 = spills are counted but not
-// queued, bit 1 = no fold into the cache entry, bit 2 = no cache claim (every record counts as a miss). Bit 3 (variant 24, results
-// RIGHT): a wave's duplicates are combined before the LDS atomics (cache_fold_combined).
-template <bool SKETCH, bool TIMING, bool DOOR, int ABL = 0, bool DEEP = false>
+// TIMING (libnfagg_diag.so only): per-phase wave-cycle sums. ABL (libnfagg_diag.so only: timing experiments, results are WRONG):
+// bit 0 = spills are counted but not queued, bit 1 = no fold into the cache entry, bit 2 = no cache claim (every record counts
+// as a miss). nfagg_variants.h says which ingest_variant selects which.
+template <bool SKETCH, bool TIMING, bool DOOR, int ABL = 0>
 __global__ __launch_bounds__(kBlock) void k_pass1(TableView t, SketchView sk, SpillView q, const void* __restrict__ recs,
                                                   uint64_t n, uint64_t seq_base) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    Cache& L = *reinterpret_cast<Cache*>(lds_raw);
-    Stage& S = *reinterpret_cast<Stage*>(lds_raw + sizeof(Cache));
-    uint32_t* door = reinterpret_cast<Door*>(lds_raw + sizeof(Cache) + sizeof(Stage))->bits;   // with DOOR only
     const int tid = threadIdx.x;
     const uint32_t seq_base32 = (uint32_t)seq_base;
-    cache_init(L, tid);
-    for (int p = tid; p < kSpillParts; p += kBlock) S.cnt[p] = 0;
-    if (DOOR) for (int p = tid; p < kDoorBits / 32; p += kBlock) door[p] = 0;
-    __syncthreads();
+    const Pass1Lds lds = pass1_lds_setup<DOOR>(lds_raw, tid);
+    Cache& L = lds.L;
+    Stage& S = lds.S;
+    uint32_t* const door = lds.door;
 
     unsigned long long ph[7] = {0, 0, 0, 0, 0, 0, 0}, tp = 0;          // TIMING: load+hash, A, barrier, B, barrier, C, flush
 #define NF_TICK(k) do { if (TIMING) { const unsigned long long tn_ = __builtin_readcyclecounter(); ph[k] += tn_ - tp; tp = tn_; } } while (0)
@@ -394,9 +319,7 @@ __global__ __launch_bounds__(kBlock) void k_pass1(TableView t, SketchView sk, Sp
     // Tiles go round the workgroups: every workgroup's cache sees the whole stream's hot flows.
     const uint64_t tile_first = (uint64_t)blockIdx.x, tile_end = n_tiles, tile_step = (uint64_t)gridDim.x;
     unsigned long long skipped = 0, spilled = 0;
-    const bool tag_on = n <= (uint64_t)kIdxMask;                       // the index leaves room for the sub-partition bits
-    const uint32_t e_mask = entry_idx_mask(n);                         // ... and for the "units needed" bits
-    (void)tag_on;                                                      // (the diag build's queue-store experiment reads it)
+    const uint32_t e_mask = entry_idx_mask(n);                         // what of a queue entry is the record's index
     const uint32_t sub_shift = sub_shift_of(q);
     // Drain state. The lane whose append FILLS a staging group (position kStage - 1) drains it one tile later — no lane polls the
     // 2048 group counters (round 2: two LDS reads per lane and tile) — and stores the drained group another tile later, when the
@@ -410,20 +333,8 @@ __global__ __launch_bounds__(kBlock) void k_pass1(TableView t, SketchView sk, Sp
 #pragma unroll
     for (int k = 0; k < 2; k++) { pend[k] = false; pend_at[k] = 0; pend_p[k] = 0; fill_p[k] = kNoPart; pend_v[k] = make_uint4(0, 0, 0, 0); }
     uint32_t carry = 0xffffffffu, carry_p = 0;                         // a spill that found its group full: retried next tile
-#ifdef NFAGG_DIAG
-    // ABL bit 4 (variant 26; results WRONG — pass 2 does not know about it — a timing experiment for PASS 1 only): a quarter of the
-    // partitions, staging groups of SIXTEEN entries, every queue write one whole 64-byte sector (four 16-byte stores to
-    // consecutive addresses) instead of a 16-byte piece of one. What the round-4 review's item 2(a) could give pass 1 at best.
-    uint4 pw_v[2][4];
-    uint32_t pw_at[2] = {0, 0}, pw_p[2] = {0, 0}, fw_p[2] = {kNoPart, kNoPart};
-    bool pw[2] = {false, false};
-    uint32_t* const SW = &S.buf[0][0];                                 // [512][16]
-#endif
     // Software pipeline: the records of tile k+1 are requested before tile k is folded, so no HBM latency is exposed inside
     // a tile. Loads are unconditional on a clamped index; `valid` only gates the fold.
-    // DEEP (experiment, round 5: libnfagg_diag.so ingest_variant 28): the records of tile k+2 are requested before tile k is folded —
-    // three record buffers in fixed roles, the loop unrolled by three so that no register copy waits for the youngest load; the
-    // seventh 16-byte unit shrinks to the one dword of it the fold reads (dscp) to stay inside 128 registers.
     auto fold_tile = [&](Rec& r, bool valid, const uint64_t i) __attribute__((always_inline)) {
         uint64_t w[5];
         uint64_t h = 0;
@@ -439,55 +350,11 @@ __global__ __launch_bounds__(kBlock) void k_pass1(TableView t, SketchView sk, Sp
         NF_TICK(1);
         __syncthreads();
         NF_TICK(2);
-#ifdef NFAGG_DIAG
-        if (ABL & 8) ent = cache_fold_combined(L, valid, ent, r, w, seq32);   // experiment: a wave's duplicates combined first (variant 24)
-        else
-#endif
         if (valid && ent >= 0 && !(ABL & 2)) ent = cache_fold(L, ent, r, w, seq32);
-#ifdef NFAGG_DIAG
-        if (ABL & 16) {
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                if (pw[k]) {
-                    if (pw_at[k] + 16u <= 4u * q.qcap) {
-                        uint4* dst = reinterpret_cast<uint4*>(q.queue + (uint64_t)pw_p[k] * 4u * q.qcap + pw_at[k]);
-#pragma unroll
-                        for (int j = 0; j < 4; j++) dst[j] = pw_v[k][j];
-                    }
-                    pw[k] = false;
-                }
-                if (fw_p[k] != kNoPart) {
-                    const uint32_t p = fw_p[k];
-                    const uint4* src = reinterpret_cast<const uint4*>(SW + p * 16u);
-#pragma unroll
-                    for (int j = 0; j < 4; j++) pw_v[k][j] = src[j];
-                    S.cnt[p] = 0;
-                    pw_at[k] = aadd(&q.qtail[p * 4u], 16u);
-                    pw_p[k] = p; pw[k] = true; fw_p[k] = kNoPart;
-                }
-            }
-            __syncthreads();
-            if (carry != 0xffffffffu) {
-                const uint32_t at = atomicAdd(&S.cnt[carry_p], 1u);
-                if (at < 16u) { SW[carry_p * 16u + at] = carry; if (at == 15u) fw_p[0] = carry_p; }
-                carry = 0xffffffffu;
-            }
-            if (valid && ent < 0) {
-                spilled++;
-                const uint32_t p = part_of(h, q) >> 2;
-                const uint32_t at = atomicAdd(&S.cnt[p], 1u);
-                const uint32_t qi = (uint32_t)i | (tag_on ? ((uint32_t)(h >> sub_shift) & (uint32_t)(kSubs - 1)) << kIdxBits : 0u);
-                if (at < 16u) { SW[p * 16u + at] = qi; if (at == 15u) fw_p[1] = p; }
-                else { carry = qi; carry_p = p; }
-            }
-            return;
-        }
-#endif
 #pragma unroll
         for (int k = 0; k < 2; k++) {
             if (pend[k]) {
-                if (pend_at[k] + kStage <= q.qcap) *reinterpret_cast<uint4*>(q.queue + (uint64_t)pend_p[k] * q.qcap + pend_at[k]) = pend_v[k];
-                else overflow_push(q, pend_v[k]);                     // partition queue full (adversarial skew)
+                queue_store_group(q, pend_p[k], pend_at[k], pend_v[k]);
                 pend[k] = false;
             }
             if (fill_p[k] != kNoPart) {                               // filled by this lane in the previous tile: every append is in LDS (barriers since)
@@ -521,46 +388,23 @@ __global__ __launch_bounds__(kBlock) void k_pass1(TableView t, SketchView sk, Sp
         // next tile: phase A touches only h64/key of NEW entries, the barrier after it orders phase B/C as before;
         // staging appends of this tile are drained after the next tile's first barrier
     };
-    if (!DEEP) {
-        bool valid; uint64_t i; Rec r;
+    bool valid; uint64_t i; Rec r;
+    {
+        const uint64_t pos = tile_first * kBlock + tid;
+        valid = pos < n; i = valid ? pos : 0;
+        load_record_head(recs, i, r);
+    }
+    for (uint64_t tile = tile_first; tile < tile_end; tile += tile_step) {
+        bool valid_n; uint64_t i_n; Rec r_n;
         {
-            const uint64_t pos = tile_first * kBlock + tid;
-            valid = pos < n; i = valid ? pos : 0;
-            load_record_head(recs, i, r);
+            const uint64_t pos = (tile + tile_step) * kBlock + tid;
+            valid_n = pos < n; i_n = valid_n ? pos : 0;
+            load_record_head(recs, i_n, r_n);
         }
-        for (uint64_t tile = tile_first; tile < tile_end; tile += tile_step) {
-            bool valid_n; uint64_t i_n; Rec r_n;
-            {
-                const uint64_t pos = (tile + tile_step) * kBlock + tid;
-                valid_n = pos < n; i_n = valid_n ? pos : 0;
-                load_record_head(recs, i_n, r_n);
-            }
-            fold_tile(r, valid, i);
-            valid = valid_n; i = i_n;
+        fold_tile(r, valid, i);
+        valid = valid_n; i = i_n;
 #pragma unroll
-            for (int k = 0; k < 28; k++) r.d[k] = r_n.d[k];
-        }
-    } else {
-        Rec ra, rb, rc; bool va, vb, vc; uint64_t ia, ib, ic;
-        auto request = [&](uint64_t tile_idx, Rec& rr, bool& vv, uint64_t& ii) __attribute__((always_inline)) {
-            const uint64_t pos = tile_idx * kBlock + tid;
-            vv = pos < n; ii = vv ? pos : 0;
-            const uint4* p = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(recs) + ii * kRecordBytes);
-#pragma unroll
-            for (int k = 0; k < 6; k++) { const uint4 v = p[k]; rr.d[4 * k] = v.x; rr.d[4 * k + 1] = v.y; rr.d[4 * k + 2] = v.z; rr.d[4 * k + 3] = v.w; }
-            rr.d[24] = reinterpret_cast<const uint32_t*>(p)[24];      // dscp; dwords 25..27 are not read by the fold
-        };
-        request(tile_first, ra, va, ia);
-        request(tile_first + tile_step, rb, vb, ib);
-        uint64_t tile = tile_first;
-        for (;;) {
-            if (tile >= tile_end) break;
-            request(tile + 2 * tile_step, rc, vc, ic); fold_tile(ra, va, ia); tile += tile_step;
-            if (tile >= tile_end) break;
-            request(tile + 2 * tile_step, ra, va, ia); fold_tile(rb, vb, ib); tile += tile_step;
-            if (tile >= tile_end) break;
-            request(tile + 2 * tile_step, rb, vb, ib); fold_tile(rc, vc, ic); tile += tile_step;
-        }
+        for (int k = 0; k < 28; k++) r.d[k] = r_n.d[k];
     }
     __syncthreads();
     if (carry != 0xffffffffu) {
@@ -574,8 +418,7 @@ __global__ __launch_bounds__(kBlock) void k_pass1(TableView t, SketchView sk, Sp
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         if (pend[k]) {
-            if (pend_at[k] + kStage <= q.qcap) *reinterpret_cast<uint4*>(q.queue + (uint64_t)pend_p[k] * q.qcap + pend_at[k]) = pend_v[k];
-            else overflow_push(q, pend_v[k]);
+            queue_store_group(q, pend_p[k], pend_at[k], pend_v[k]);
         }
     }
 #pragma unroll
@@ -589,8 +432,7 @@ __global__ __launch_bounds__(kBlock) void k_pass1(TableView t, SketchView sk, Sp
             if (c < 2) v.y = 0xffffffffu;
             if (c < 3) v.z = 0xffffffffu;
             if (c < 4) v.w = 0xffffffffu;
-            if (at + kStage <= q.qcap) *reinterpret_cast<uint4*>(q.queue + (uint64_t)p * q.qcap + at) = v;
-            else overflow_push(q, v);
+            queue_store_group(q, (uint32_t)p, at, v);
         }
     }
     for (int e = tid; e < kEntries; e += kBlock) cache_flush_entry<SKETCH, false>(t, sk, L, e, recs, seq_base32, nullptr, nullptr, false);
@@ -604,7 +446,7 @@ __global__ __launch_bounds__(kBlock) void k_pass1(TableView t, SketchView sk, Sp
     if (spilled) aadd(&t.ctr->n_bypassed, spilled);
 }
 
-// ---- pass 1 WITHOUT its barriers (round 6; ingest_variant 17) -------------------------------------------------------------------
+// ---- pass 1 WITHOUT its barriers (round 6; kVariantPass1Free) ---------------------------------------------------------------------
 // k_pass1 above takes its 16 waves through two workgroup barriers per tile: one so that the creator of a cache entry may write the
 // entry's key with plain stores before anybody compares it, one for the spill staging (a group is drained a tile after it was
 // filled). Its phase timing says what that costs: 29 % of the wave-cycles at the barriers, waves that hold their loads already
@@ -654,15 +496,12 @@ template <bool SKETCH, bool DOOR>
 __global__ __launch_bounds__(kBlock) void k_pass1_free(TableView t, SketchView sk, SpillView q, const void* __restrict__ recs,
                                                        uint64_t n, uint64_t seq_base) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    Cache& L = *reinterpret_cast<Cache*>(lds_raw);
-    Stage& S = *reinterpret_cast<Stage*>(lds_raw + sizeof(Cache));
-    uint32_t* door = reinterpret_cast<Door*>(lds_raw + sizeof(Cache) + sizeof(Stage))->bits;   // with DOOR only
     const int tid = threadIdx.x;
     const uint32_t seq_base32 = (uint32_t)seq_base;
-    cache_init(L, tid);
-    for (int p = tid; p < kSpillParts; p += kBlock) S.cnt[p] = 0;
-    if (DOOR) for (int p = tid; p < kDoorBits / 32; p += kBlock) door[p] = 0;
-    __syncthreads();
+    const Pass1Lds lds = pass1_lds_setup<DOOR>(lds_raw, tid);
+    Cache& L = lds.L;
+    Stage& S = lds.S;
+    uint32_t* const door = lds.door;
     const uint64_t n_tiles = (n + kBlock - 1) / kBlock;
     const uint64_t tile_first = (uint64_t)blockIdx.x, tile_step = (uint64_t)gridDim.x;
     unsigned long long skipped = 0, spilled = 0;
@@ -697,8 +536,7 @@ __global__ __launch_bounds__(kBlock) void k_pass1_free(TableView t, SketchView s
 #pragma unroll
         for (int k = 0; k < 2; k++) {
             if (pend[k]) {
-                if (pend_at[k] + kStage <= q.qcap) *reinterpret_cast<uint4*>(q.queue + (uint64_t)pend_p[k] * q.qcap + pend_at[k]) = pend_v[k];
-                else overflow_push(q, pend_v[k]);
+                queue_store_group(q, pend_p[k], pend_at[k], pend_v[k]);
                 pend[k] = false;
             }
         }
@@ -763,8 +601,7 @@ __global__ __launch_bounds__(kBlock) void k_pass1_free(TableView t, SketchView s
             if (c < 2) vq.y = 0xffffffffu;
             if (c < 3) vq.z = 0xffffffffu;
             if (c < 4) vq.w = 0xffffffffu;
-            if (at + kStage <= q.qcap) *reinterpret_cast<uint4*>(q.queue + (uint64_t)p * q.qcap + at) = vq;
-            else overflow_push(q, vq);
+            queue_store_group(q, (uint32_t)p, at, vq);
         }
     }
     for (int e = tid; e < kEntries; e += kBlock) cache_flush_entry<SKETCH, false>(t, sk, L, e, recs, seq_base32, nullptr, nullptr, false);
@@ -1041,9 +878,11 @@ __global__ __launch_bounds__(256) void k_merge_overflow(TableView t, SketchView 
     if (direct) aadd(&t.ctr->n_direct, direct);
 }
 
-template <bool SKETCH, bool T1 = false, bool T2 = false, bool DOOR = true, int ABL = 0, bool DEEP = false, bool FREE = false>
+// FREE: pass 1 is k_pass1_free (no TIMING or ABL build of it exists)
+template <bool SKETCH, bool T1 = false, bool T2 = false, bool DOOR = true, int ABL = 0, bool FREE = false>
 static hipError_t run(const TableView& t, const SketchView& sk, const SpillView& q, const void* d_records, uint64_t n,
                       uint64_t seq_base, hipStream_t s) {
+    const auto pass1 = FREE ? &k_pass1_free<SKETCH, DOOR> : &k_pass1<SKETCH, T1, DOOR, ABL>;
     const size_t lds1 = sizeof(Cache) + sizeof(Stage) + (DOOR ? sizeof(Door) : 0), lds2 = sizeof(Cache) + sizeof(Pass2Lds);
     static_assert(sizeof(Cache) + sizeof(Stage) + sizeof(Door) <= 160 * 1024, "pass 1 needs the whole LDS of a CU");
     static std::atomic<bool> attr_set_dev[64];   // per device: a process may drive several GPUs, from several host threads
@@ -1051,9 +890,7 @@ static hipError_t run(const TableView& t, const SketchView& sk, const SpillView&
     (void)hipGetDevice(&dev_);
     std::atomic<bool>& attr_set = attr_set_dev[dev_ & 63];
     if (!attr_set.load(std::memory_order_acquire)) {
-        hipError_t e = FREE ? hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pass1_free<SKETCH, DOOR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1)
-                            : hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pass1<SKETCH, T1, DOOR, ABL, DEEP>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pass1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pass2<SKETCH, T2>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
@@ -1068,8 +905,7 @@ static hipError_t run(const TableView& t, const SketchView& sk, const SpillView&
     if (grid > 256) grid = 256;
     if (grid > tiles) grid = tiles;
     (void)hipGetLastError();
-    if (FREE) hipLaunchKernelGGL((k_pass1_free<SKETCH, DOOR>), dim3((unsigned)grid), dim3(kBlock), lds1, s, t, sk, q, d_records, n, seq_base);
-    else hipLaunchKernelGGL((k_pass1<SKETCH, T1, DOOR, ABL, DEEP>), dim3((unsigned)grid), dim3(kBlock), lds1, s, t, sk, q, d_records, n, seq_base);
+    hipLaunchKernelGGL(pass1, dim3((unsigned)grid), dim3(kBlock), lds1, s, t, sk, q, d_records, n, seq_base);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_pass2<SKETCH, T2>), dim3(q.n_parts), dim3(kBlock), lds2, s, t, sk, q, d_records, n, seq_base);
@@ -1100,28 +936,25 @@ hipError_t launch_ingest_part(const TableView& t, const SketchView& sk, const Sp
     q.qcap = (uint32_t)((((uint64_t)q_in.qcap * kSpillParts) / parts) & ~3ull);
     TableView tq = t;
     tq.spill = q;
-#ifdef NFAGG_DIAG
-    if (variant == 8) return part::run<false, true, false>(tq, sk, q, d_records, n, seq_base, s);   // diagnostics: pass-1 phase timing
-    if (variant == 9) return part::run<false, false, true>(tq, sk, q, d_records, n, seq_base, s);   // diagnostics: pass-2 phase timing
-    switch (variant) {                                                                              // diagnostics: pass-1 ablations (wrong results)
-        case 21: return part::run<false, false, false, true, 1>(tq, sk, q, d_records, n, seq_base, s);
-        case 22: return part::run<false, false, false, true, 2>(tq, sk, q, d_records, n, seq_base, s);
-        case 23: return part::run<false, false, false, true, 3>(tq, sk, q, d_records, n, seq_base, s);
-        case 25: return part::run<false, false, false, true, 5>(tq, sk, q, d_records, n, seq_base, s);
-        case 27: return part::run<false, false, false, true, 7>(tq, sk, q, d_records, n, seq_base, s);
-        case 26: return part::run<false, false, false, true, 16>(tq, sk, q, d_records, n, seq_base, s);        // experiment, pass 1's time only (results WRONG): 64-byte queue stores, a quarter of the partitions
-        case 24: return part::run<false, false, false, true, 8>(tq, sk, q, d_records, n, seq_base, s);         // experiment: wave-level duplicate combining before the LDS atomics (results RIGHT)
-        case 28: return part::run<false, false, false, true, 0, true>(tq, sk, q, d_records, n, seq_base, s);   // experiment: records requested two tiles ahead (results RIGHT)
-        default: break;
-    }
+    const bool f = sk.flags != 0;
+    switch (variant) {
+#ifdef NFAGG_DIAG                         // phase timing; pass-1 ablations (wrong results)
+        case kVariantPass1Timing: return part::run<false, true, false>(tq, sk, q, d_records, n, seq_base, s);
+        case kVariantPass2Timing: return part::run<false, false, true>(tq, sk, q, d_records, n, seq_base, s);
+        case kVariantAblNoQueue: return part::run<false, false, false, true, 1>(tq, sk, q, d_records, n, seq_base, s);
+        case kVariantAblNoFold: return part::run<false, false, false, true, 2>(tq, sk, q, d_records, n, seq_base, s);
+        case kVariantAblNoQueueNoFold: return part::run<false, false, false, true, 3>(tq, sk, q, d_records, n, seq_base, s);
+        case kVariantAblNoClaimNoQueue: return part::run<false, false, false, true, 5>(tq, sk, q, d_records, n, seq_base, s);
+        case kVariantAblLoadsOnly: return part::run<false, false, false, true, 7>(tq, sk, q, d_records, n, seq_base, s);
 #endif
-    if (variant == 17)   // round 6: pass 1 without its barriers (published cache entries, staging groups drained by their last writer)
-        return sk.flags ? part::run<true, false, false, true, 0, false, true>(tq, sk, q, d_records, n, seq_base, s)
-                        : part::run<false, false, false, true, 0, false, true>(tq, sk, q, d_records, n, seq_base, s);
-    if (variant == 11)   // A/B: pass 1 without the admission filter (first come, first served)
-        return sk.flags ? part::run<true, false, false, false>(tq, sk, q, d_records, n, seq_base, s)
-                        : part::run<false, false, false, false>(tq, sk, q, d_records, n, seq_base, s);
-    return sk.flags ? part::run<true>(tq, sk, q, d_records, n, seq_base, s) : part::run<false>(tq, sk, q, d_records, n, seq_base, s);
+        case kVariantPass1Free:           // round 6: pass 1 without its barriers (published cache entries, staging groups drained by their last writer)
+            return f ? part::run<true, false, false, true, 0, true>(tq, sk, q, d_records, n, seq_base, s)
+                     : part::run<false, false, false, true, 0, true>(tq, sk, q, d_records, n, seq_base, s);
+        case kVariantTwoPassNoDoor:       // A/B: pass 1 without the admission filter (first come, first served)
+            return f ? part::run<true, false, false, false>(tq, sk, q, d_records, n, seq_base, s)
+                     : part::run<false, false, false, false>(tq, sk, q, d_records, n, seq_base, s);
+        default: return f ? part::run<true>(tq, sk, q, d_records, n, seq_base, s) : part::run<false>(tq, sk, q, d_records, n, seq_base, s);
+    }
 }
 
 }  // namespace nfagg

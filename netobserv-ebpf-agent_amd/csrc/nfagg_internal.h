@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "nfagg_hash.h"
+#include "nfagg_variants.h"
 #include "../../include/nfagg.h"
 
 namespace nfagg {
@@ -147,14 +148,16 @@ struct SketchView {
 
 // ---- launch wrappers (defined in nfagg_kernels.hip) ----
 // Fold records[0..n) into the table; record i carries sequence seq_base + i.
-// variant: 0 = default, see DESIGN.md.
+// variant: 0 = default; nfagg_variants.h lists them and decides the path (ingest_path).
 // When ingest_fuses_sketches(variant), the kernel also applies the sketch updates of sk
 // (pass sk.flags = 0 to disable); otherwise the caller launches launch_sketch_update itself.
 hipError_t launch_ingest(const TableView& t, const SketchView& sk, const void* d_records, uint64_t n, uint64_t seq_base,
                          int mode, int variant, hipStream_t s);
-bool ingest_fuses_sketches(int mode, int variant, uint64_t n, uint32_t sketch_flags);
-bool ingest_variant_supported(int variant);
-bool ingest_needs_spill(int mode, int variant, uint64_t n);
+#ifdef NFAGG_DIAG
+constexpr bool kDiagBuild = true;         // libnfagg_diag.so: the phase-timing and ablation variants exist
+#else
+constexpr bool kDiagBuild = false;
+#endif
 hipError_t launch_ingest_part(const TableView& t, const SketchView& sk, const SpillView& q, const void* d_records, uint64_t n,
                               uint64_t seq_base, int variant, hipStream_t s);
 // nfagg_epoch_par.hip / nfagg_account_par.inc: the evict-on-full loop of nfagg_account with its epochs found first — sort keys

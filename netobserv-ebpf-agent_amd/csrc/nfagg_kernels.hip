@@ -302,51 +302,17 @@ static inline int grid_for(uint64_t n, int block, int max_blocks) {
 hipError_t launch_ingest_cached(const TableView& t, const SketchView& sk, const void* d_records, uint64_t n, uint64_t seq_base,
                                 int variant, hipStream_t s);  // nfagg_ingest_cached.hip
 
-// Default kernel by batch size, measured on configs[1]'s stream, per call (round 3: profiles/r03_batch_size_sweep.txt; round 2:
-// profiles/r02_batch_size_sweep.txt; round 1: profiles/r01e_batch_size_crossover.txt):
-//   below 6 144 records the direct kernel (one record per lane, HBM atomics; no LDS cache to set up and flush);
-//   below 384 Ki records (768 Ki in round 2) the single-pass LDS-cached kernel: 0.049 ms per 65 536 records against 0.063 ms for the launches
-//     of the two-pass fold, 0.130 against 0.120 ms at 256 Ki;
-//   from there the two-pass partitioned fold: 0.17 against 0.24 ms at 512 Ki, 0.26 against 0.41 ms at 1 Mi, 0.70 against 1.29 ms at
-//     4 Mi (partitions scaled to the batch and a cheaper flush moved the crossover from 768 Ki to ~300 Ki this round).
-constexpr uint64_t kDirectMaxBatch = 6144;
-constexpr uint64_t kPartMinBatch = 3u << 17;   // 384 Ki (round 3: 0.114 against 0.128 ms at 256 Ki, 0.18 against 0.23 at 512 Ki)
-constexpr uint64_t kDedupCachedMinBatch = 1u << 16;
-static bool takes_two_pass(int variant, uint64_t n) { return (variant >= 8 && variant <= 11) || variant == 17 || (variant >= 20 && variant <= 28) || ((variant == 0 || variant == 30) && n >= kPartMinBatch); }
-// Shipping variants: 0 (by batch size), 1 direct, 3/4/5/7 geometries of the single-pass cached kernel, 10/11 two-pass
-// (with / without the admission filter). 6/8/9 are the phase-timing builds and exist only in libnfagg_diag.so (-DNFAGG_DIAG).
-bool ingest_variant_supported(int variant) {
-#ifdef NFAGG_DIAG
-    if (variant == 6 || variant == 8 || variant == 9 || (variant >= 13 && variant <= 15) || (variant >= 20 && variant <= 28)) return true;
-#endif
-    return variant == 0 || variant == 1 || variant == 3 || variant == 4 || variant == 5 || variant == 7 || variant == 10 || variant == 11 || variant == 12 ||
-           variant == 17 ||   // 17: the two-pass fold always, pass 1 without its barriers (nfagg_ingest_part.hip k_pass1_free)
-           variant == 16 ||   // 16 (kernel-dedup mode, tests): the cached passes always, the partition pass always sorts its items first
-           variant == 30;     // 30 (tests): everything as 0, but nfagg_account always takes its kernel chain — the fallback of the epochs-found-first path
-}
-static bool takes_direct(int variant, uint64_t n, uint32_t sketch_flags) {
-    return variant == 1 || ((variant == 0 || variant == 30) && n < kDirectMaxBatch && sketch_flags == 0);   // with sketches on, the cached kernel fuses them: one launch
-}
-static bool dedup_takes_cached(int variant, uint64_t n) { return !(variant == 1 || (variant != 10 && (variant < 12 || variant > 16) && n < kDedupCachedMinBatch)); }
-bool ingest_needs_spill(int mode, int variant, uint64_t n) { return mode == 0 ? takes_two_pass(variant, n) : dedup_takes_cached(variant, n); }
-bool ingest_fuses_sketches(int mode, int variant, uint64_t n, uint32_t sketch_flags) {
-    if (mode == 1) return dedup_takes_cached(variant, n) && !(variant >= 13 && variant <= 15);   // the partition pass's flushes feed them (nfagg_dedup_cached.hip); 13-15: its timing ablations
-    return mode == 0 && !takes_direct(variant, n, sketch_flags) && variant != 6 && variant != 8 && variant != 9 && (variant < 20 || variant == 30);
-}
-
+// Which kernels fold the batch: ingest_path (nfagg_variants.h) — by batch size for the default variant.
 hipError_t launch_ingest(const TableView& t, const SketchView& sk, const void* d_records, uint64_t n, uint64_t seq_base,
                          int mode, int variant, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    if (mode == 1) {   // NFAGG_MODE_KERNEL_DEDUP: LDS-cached passes; direct per-record passes for small batches (variant 1: always, 10: never)
-        if (!dedup_takes_cached(variant, n)) return launch_ingest_dedup(t, d_records, n, seq_base, s);
-        return launch_ingest_dedup_cached(t, sk, d_records, n, seq_base, variant, s);
+    switch (ingest_path(mode, variant, n, sk.flags)) {
+        case IngestPath::DedupDirect: return launch_ingest_dedup(t, d_records, n, seq_base, s);
+        case IngestPath::DedupCached: return launch_ingest_dedup_cached(t, sk, d_records, n, seq_base, variant, s);
+        case IngestPath::TwoPass: return launch_ingest_part(t, sk, t.spill, d_records, n, seq_base, variant, s);
+        case IngestPath::Cached: return launch_ingest_cached(t, sk, d_records, n, seq_base, variant, s);
+        case IngestPath::Direct: break;
     }
-    // 0 (default): by batch size (see kDirectMaxBatch / kPartMinBatch above) — direct kernel, single-pass cached kernel
-    // (what variant 7 always runs), two-pass partitioned fold (nfagg_ingest_part.hip; 8/9 = its phase-timing builds).
-    // 3..5: other geometries of the cached kernel, 6: its phase-timing build (diag library only); 1: direct always.
-    if (takes_two_pass(variant, n))   // 10: two-pass whatever the size; 11: same without the admission filter
-        return launch_ingest_part(t, sk, t.spill, d_records, n, seq_base, variant, s);
-    if (!takes_direct(variant, n, sk.flags)) return launch_ingest_cached(t, sk, d_records, n, seq_base, variant, s);
     (void)hipGetLastError(); hipLaunchKernelGGL(k_ingest_direct, dim3(grid_for(n, 256, 256 * 8)), dim3(256), 0, s, t, d_records, n, seq_base);
     return hipGetLastError();
 }
