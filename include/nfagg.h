@@ -822,6 +822,48 @@ int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t 
                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
                                  size_t* n_deferred, size_t* out_bytes);
 
+/* The MapTracer branch (pkg/flow/tracer_map.go:103-146) through direct-FLP:
+ * nfagg_encode_flp_json over (records[i].id, BpfFlowContent{records[i].metrics,
+ * features[i]}), `features` as for nfagg_encode_pb_content (what
+ * nfagg_map_merge writes: part k is present for flow i when its array is
+ * non-NULL and present[i] has its NFAGG_FEAT_* bit). The line gains, at their
+ * places in byte order, the keys of decode_protobuf.go:130-192 with
+ * NewRecord's DNSLatency / TimeFlowRtt (record.go:116-125):
+ *   dns:        DnsErrno when non-zero; when id != 0 DnsFlags,
+ *               DnsFlagsResponseCode (DNSRcodeToStr(flags & 0xF),
+ *               decode_protobuf.go:426-464), DnsId, DnsLatencyMs
+ *               (int64(latency) / 1e6, truncating), and DnsName when
+ *               utils.DNSRawNameToDotted (pkg/utils/utils.go:18-60) is not
+ *               empty, escaped as every other string of the line;
+ *   drops:      when latest_drop_cause != 0 PktDropBytes, PktDropPackets,
+ *               PktDropLatestFlags, PktDropLatestState (TCPStateToStr,
+ *               decode_protobuf.go:199-225), PktDropLatestDropCause
+ *               (PktDropCauseToStr, decode_protobuf.go:230-422, with the
+ *               "NetworkEvent_" causes of network_events.go:17-28,133-138);
+ *   xlat:       unless model.AllZeroIP (record.go:233-238: all zero, or
+ *               ::ffff:0.0.0.0) holds for saddr or daddr: ZoneId, XlatSrcAddr,
+ *               XlatDstAddr (net.IP.String() of the 16 bytes, whatever the
+ *               flow's eth_protocol), XlatSrcPort / XlatDstPort when non-zero;
+ *   additional: IPSecRetCode and IPSecStatus ("error" when
+ *               ipsec_encrypted_ret != 0, else "success" with code 0 when
+ *               ipsec_encrypted), TimeFlowRttNs when flow_rtt != 0;
+ *   quic:       QuicVersion (record.go:259-270), QuicSeenLongHdr,
+ *               QuicSeenShortHdr.
+ * Network events (NFAGG_FEAT_NETWORK_EVENTS) need the OVN sample decoder: the
+ * line is the one NewRecord gives with a nil decoder (record.go:126) — no
+ * NetworkEvents key, no drop injected — the choice nfagg_encode_pb_content makes.
+ * Outputs, deferred records and return codes as nfagg_encode_flp_json;
+ * features == NULL is nfagg_encode_flp_json. All pointers HOST memory: */
+int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                  const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
+                                  uint8_t* deferred, size_t* n_deferred, size_t* out_bytes);
+/* Same with every data pointer (also those inside d_features) in DEVICE memory,
+ * e.g. the d_out of nfagg_map_merge_device; the nfagg_pb_features struct
+ * itself is in host memory. */
+int nfagg_encode_flp_json_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                         const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
+                                         uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes);
+
 /* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */
 /* ------------------------------------------------------------------ */

@@ -165,6 +165,8 @@ SIGNATURES = {
     "nfagg_encode_ipfix_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(IpfixOptions), _vp, _sz, _vp, _psz]),
     "nfagg_encode_flp_json": (C.c_int, [_vp, _vp, _sz, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_encode_flp_json_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
+    "nfagg_encode_flp_json_content": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
+    "nfagg_encode_flp_json_content_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

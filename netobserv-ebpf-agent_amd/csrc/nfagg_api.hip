@@ -2287,6 +2287,17 @@ int encode_staged(nfagg_handle* h, const void* records, size_t n, void* out, siz
 
 extern "C" {
 
+// nfagg_pb_features with DEVICE pointers, checked, as the kernels take it (protobuf and direct-FLP content encoders)
+static int device_features(nfagg_handle* h, const nfagg_pb_features* feat, PbFeat* F) {
+    if (feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
+    if ((((uintptr_t)feat->additional | (uintptr_t)feat->dns | (uintptr_t)feat->drops | (uintptr_t)feat->xlat | (uintptr_t)feat->quic) & 7u) != 0)
+        return fail(h, NFAGG_EINVAL, "feature arrays must be 8-byte aligned");
+    F->present = feat->present;
+    F->additional = (const uint8_t*)feat->additional; F->dns = (const uint8_t*)feat->dns; F->drops = (const uint8_t*)feat->drops;
+    F->xlat = (const uint8_t*)feat->xlat; F->quic = (const uint8_t*)feat->quic;
+    return NFAGG_OK;
+}
+
 // ---- record -> protobuf (nfagg_pb.hip)
 // feat (optional): DEVICE pointers
 static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const nfagg_pb_options* opt,
@@ -2299,14 +2310,7 @@ static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t 
     int rc = check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
     if (rc != NFAGG_OK) return rc;
     PbFeat F{};
-    if (feat) {
-        if (feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
-        if ((((uintptr_t)feat->additional | (uintptr_t)feat->dns | (uintptr_t)feat->drops | (uintptr_t)feat->xlat | (uintptr_t)feat->quic) & 7u) != 0)
-            return fail(h, NFAGG_EINVAL, "feature arrays must be 8-byte aligned");
-        F.present = feat->present;
-        F.additional = (const uint8_t*)feat->additional; F.dns = (const uint8_t*)feat->dns; F.drops = (const uint8_t*)feat->drops;
-        F.xlat = (const uint8_t*)feat->xlat; F.quic = (const uint8_t*)feat->quic;
-    }
+    if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
     bool done;
     if ((rc = encode_begin(h, n, d_frame_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
     PbParams P{};
@@ -2484,13 +2488,16 @@ static int encode_flp_check(nfagg_handle* h, const nfagg_flp_options* opt) {
     return check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
 }
 
-int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
-                                 void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
-                                 size_t* n_deferred, size_t* out_bytes) {
+// feat (optional): DEVICE pointers. Without it the kernels of nfagg_flp.hip run, with it those of nfagg_flp_content.hip.
+static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const nfagg_flp_options* opt,
+                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
+                                  size_t* n_deferred, size_t* out_bytes) {
     int rc = encode_flp_check(h, opt);
     if (rc != NFAGG_OK) return rc;
     if (!h || !out_bytes || !d_line_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
+    PbFeat F{};
+    if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
     size_t deferred_unused;
     if (!n_deferred) n_deferred = &deferred_unused;
     *n_deferred = 0;
@@ -2517,23 +2524,59 @@ int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t 
     P.time_received = opt->time_received_s;
     P.names = (const nfagg_intf_name*)S.names.p; P.esc = (const uint8_t*)S.flp_esc.p; P.n_names = opt->n_names;
     P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
-    return encode_two_pass(h, n, "FLP JSON", "write", d_out, out_cap, out_bytes, n_deferred,
+    uint32_t* counter = (uint32_t*)S.flp_n_deferred.p;
+    if (!feat)
+        return encode_two_pass(h, n, "FLP JSON", "write", d_out, out_cap, out_bytes, n_deferred,
+            [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+                return launch_flp_size(d_records, n, P, rows, local_off, block_sum, block_base, counter, h->stream); },
+            [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+                return launch_flp_write(d_records, n, P, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
+    return encode_two_pass(h, n, "FLP JSON content", "write", d_out, out_cap, out_bytes, n_deferred,
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-            return launch_flp_size(d_records, n, P, rows, local_off, block_sum, block_base, (uint32_t*)S.flp_n_deferred.p, h->stream); },
+            return launch_flpc_size(d_records, n, P, F, rows, local_off, block_sum, block_base, counter, h->stream); },
         [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-            return launch_flp_write(d_records, n, P, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
+            return launch_flpc_write(d_records, n, P, F, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
+}
+
+// feat (optional): HOST pointers, uploaded beside the records
+static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const nfagg_flp_options* opt,
+                                void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
+                                size_t* n_deferred, size_t* out_bytes) {
+    int rc = encode_flp_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
+    return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
+        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
+            nfagg_pb_features dfeat{};
+            if (feat && n) { int rc2 = stage_pb_features(h, feat, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
+            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, opt, d_out, out_cap, d_offsets,
+                                          deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
+}
+
+int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
+                                 void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
+                                 size_t* n_deferred, size_t* out_bytes) {
+    return encode_flp_device_core(h, d_records, n, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
                           void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
                           size_t* n_deferred, size_t* out_bytes) {
-    int rc = encode_flp_check(h, opt);
-    if (rc != NFAGG_OK) return rc;
-    if (!h || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
-    return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
-        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
-            return nfagg_encode_flp_json_device(h, d_records, n, opt, d_out, out_cap, d_offsets,
-                                                deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
+    return encode_flp_host_core(h, records, n, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+}
+
+// features == NULL: the flows carry no parts, the call is nfagg_encode_flp_json[_device]
+int nfagg_encode_flp_json_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                         const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
+                                         uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
+    return encode_flp_device_core(h, d_records, n, d_features, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+}
+
+int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                  const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
+                                  uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
+    return encode_flp_host_core(h, records, n, features, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
 
 #ifdef NFAGG_DIAG

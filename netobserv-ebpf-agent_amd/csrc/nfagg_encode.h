@@ -83,6 +83,37 @@ NF_DEV uint64_t mac_be(uint64_t mac_le48) {   // Rec::smac() holds byte 0 in the
     return v;
 }
 
+// ---- feature parts of a MapTracer flow (protobuf and FLP-JSON content encoders)
+// utils.DNSRawNameToDotted (pkg/utils/utils.go:18-58) over the 32-byte kernel copy at `raw` (the lane's LDS slot):
+// bytes up to the first NUL, label by label; stops at a zero length, a compression pointer, or a label that
+// runs past the end. EMIT = false only measures.
+template <bool EMIT, typename S> NF_DEV uint32_t dns_dotted(S& s, const uint8_t* __restrict__ raw) {
+    uint32_t nb = 0;
+    while (nb < 32 && raw[nb] != 0) nb++;
+    uint32_t i = 0, out = 0;
+    while (i < nb) {
+        const uint32_t l = raw[i];
+        if (l == 0 || (l & 0xC0u) == 0xC0u) break;
+        i++;
+        if (i + l > nb) break;
+        if (out) { if (EMIT) s.put('.'); out++; }
+        if (EMIT) for (uint32_t k = 0; k < l; k++) s.put(raw[i + k]);
+        out += l; i += l;
+    }
+    return out;
+}
+
+template <int N> NF_DEV void load_dwords16(const uint8_t* p, uint32_t (&w)[N]) {   // N/4 16-byte loads
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+    for (int k = 0; k < N / 4; k++) { const uint4 v = q[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
+}
+template <int N> NF_DEV void load_dwords8(const uint8_t* p, uint32_t (&w)[N]) {    // N/2 8-byte loads
+    const uint2* q = reinterpret_cast<const uint2*>(p);
+#pragma unroll
+    for (int k = 0; k < N / 2; k++) { const uint2 v = q[k]; w[2 * k] = v.x; w[2 * k + 1] = v.y; }
+}
+
 // ---- the two-pass skeleton. Every size kernel runs kScanBlock records per workgroup and scans their lengths inside it
 // (block_scan); the block sums go through launch_scan_block_sums (nfagg_internal.h, nfagg_encode.hip). Every write kernel
 // runs one wave per 64 records: it builds the wave's bytes in LDS (WaveImage) and copies them out (copy_image_out).

@@ -1,8 +1,9 @@
-// nfagg_flp.h — launch interface of the record -> direct-FLP JSON line kernels (nfagg_flp.hip).
+// nfagg_flp.h — launch interface of the record -> direct-FLP JSON line kernels (nfagg_flp.hip, nfagg_flp_content.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/nfagg.h"
+#include "nfagg_pb.h"
 
 namespace nfagg {
 
@@ -32,5 +33,13 @@ hipError_t launch_flp_size(const void* d_recs, uint64_t n, const FlpParams& P, u
                            uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s);
 hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, const uint32_t* d_rows, const uint32_t* d_local_off,
                             const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, uint8_t* d_deferred, hipStream_t s);
+
+// The same two passes over full BpfFlowContents (nfagg_flp_content.hip): F names the flows' feature parts as it does for the
+// protobuf encoder. Same scratch, same outputs.
+hipError_t launch_flpc_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, uint32_t* d_rows, uint32_t* d_local_off,
+                            uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s);
+hipError_t launch_flpc_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const uint32_t* d_rows,
+                             const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
+                             uint8_t* d_deferred, hipStream_t s);
 
 }  // namespace nfagg

@@ -1,0 +1,361 @@
+// nfagg_flp_content.hip — MapTracer flows (pkg/flow/tracer_map.go:103-146: a flow_record_t plus the feature parts of a
+// full model.BpfFlowContent) -> direct-FLP JSON lines. The line of nfagg_flp.hip with the keys that
+//   pkg/decode/decode_protobuf.go:130-192   RecordToMap, the feature parts
+//   pkg/model/record.go:116-125             NewRecord: DNSLatency, TimeFlowRtt
+// add, at their places in byte order ([] = only when RecordToMap's rule says so):
+//   after Bytes:         [DnsErrno] [DnsFlags DnsFlagsResponseCode DnsId DnsLatencyMs [DnsName]]
+//   after Flags:         [IPSecRetCode IPSecStatus]
+//   after Packets:       [PktDropBytes PktDropLatestDropCause PktDropLatestFlags PktDropLatestState PktDropPackets]
+//   after Proto:         [QuicSeenLongHdr QuicSeenShortHdr QuicVersion]
+//   after TimeFlowEndMs: [TimeFlowRttNs]
+//   after Udns:          [XlatDstAddr [XlatDstPort] XlatSrcAddr [XlatSrcPort]] [ZoneId]
+// Network events are encoded as NewRecord does with a nil decoder (record.go:126): no key, no drop injected.
+//
+// Same two passes, same window scheme and the same encode_line as nfagg_flp.hip, with FlpContent as its feature policy;
+// the kernels are separate so that the Accounter path keeps its code and its registers. A lane reads the parts its
+// present byte names with 16- and 8-byte loads before anything is emitted, keeps the fields the line needs in registers
+// and the DNS name in a 32-byte LDS slot of its own. The names of response codes, TCP states and drop causes sit in one
+// constant blob with an offset and a length per name; the counting pass reads only the lengths.
+#include "nfagg_flp_line.h"
+
+namespace nfagg {
+
+// ---- the name tables: DNSRcodeToStr, TCPStateToStr, PktDropCauseToStr (decode_protobuf.go:199-464) and the causes of
+// networkevents.DropReasonCodeToString (network_events.go:17-28,133-138) behind their "NetworkEvent_" prefix
+constexpr const char* const kFlpNames[] = {
+    // DNSRcodeToStr of a 4-bit value: 0..10, everything else "UnDefined" (its cases 16..21 cannot match)
+    "NoError", "FormErr", "ServFail", "NXDomain", "NotImp", "Refused", "YXDomain", "YXRRSet", "NXRRSet", "NotAuth", "NotZone",
+    "UnDefined",
+    // TCPStateToStr: the fallback, then states 1..11
+    "TCP_INVALID_STATE", "TCP_ESTABLISHED", "TCP_SYN_SENT", "TCP_SYN_RECV", "TCP_FIN_WAIT1", "TCP_FIN_WAIT2", "TCP_CLOSE",
+    "TCP_CLOSE_WAIT", "TCP_LAST_ACK", "TCP_LISTEN", "TCP_CLOSING", "TCP_NEW_SYN_RECV",
+    // PktDropCauseToStr: the core subsystem's causes 2..80
+    "SKB_DROP_REASON_NOT_SPECIFIED", "SKB_DROP_REASON_NO_SOCKET", "SKB_DROP_REASON_PKT_TOO_SMALL", "SKB_DROP_REASON_TCP_CSUM",
+    "SKB_DROP_REASON_SOCKET_FILTER", "SKB_DROP_REASON_UDP_CSUM", "SKB_DROP_REASON_NETFILTER_DROP", "SKB_DROP_REASON_OTHERHOST",
+    "SKB_DROP_REASON_IP_CSUM", "SKB_DROP_REASON_IP_INHDR", "SKB_DROP_REASON_IP_RPFILTER",
+    "SKB_DROP_REASON_UNICAST_IN_L2_MULTICAST", "SKB_DROP_REASON_XFRM_POLICY", "SKB_DROP_REASON_IP_NOPROTO",
+    "SKB_DROP_REASON_SOCKET_RCVBUFF", "SKB_DROP_REASON_PROTO_MEM", "SKB_DROP_REASON_TCP_MD5NOTFOUND",
+    "SKB_DROP_REASON_TCP_MD5UNEXPECTED", "SKB_DROP_REASON_TCP_MD5FAILURE", "SKB_DROP_REASON_SOCKET_BACKLOG",
+    "SKB_DROP_REASON_TCP_FLAGS", "SKB_DROP_REASON_TCP_ZEROWINDOW", "SKB_DROP_REASON_TCP_OLD_DATA",
+    "SKB_DROP_REASON_TCP_OVERWINDOW", "SKB_DROP_REASON_TCP_OFOMERGE", "SKB_DROP_REASON_TCP_RFC7323_PAWS",
+    "SKB_DROP_REASON_TCP_INVALID_SEQUENCE", "SKB_DROP_REASON_TCP_RESET", "SKB_DROP_REASON_TCP_INVALID_SYN",
+    "SKB_DROP_REASON_TCP_CLOSE", "SKB_DROP_REASON_TCP_FASTOPEN", "SKB_DROP_REASON_TCP_OLD_ACK",
+    "SKB_DROP_REASON_TCP_TOO_OLD_ACK", "SKB_DROP_REASON_TCP_ACK_UNSENT_DATA", "SKB_DROP_REASON_TCP_OFO_QUEUE_PRUNE",
+    "SKB_DROP_REASON_TCP_OFO_DROP", "SKB_DROP_REASON_IP_OUTNOROUTES", "SKB_DROP_REASON_BPF_CGROUP_EGRESS",
+    "SKB_DROP_REASON_IPV6DISABLED", "SKB_DROP_REASON_NEIGH_CREATEFAIL", "SKB_DROP_REASON_NEIGH_FAILED",
+    "SKB_DROP_REASON_NEIGH_QUEUEFULL", "SKB_DROP_REASON_NEIGH_DEAD", "SKB_DROP_REASON_TC_EGRESS", "SKB_DROP_REASON_QDISC_DROP",
+    "SKB_DROP_REASON_CPU_BACKLOG", "SKB_DROP_REASON_XDP", "SKB_DROP_REASON_TC_INGRESS", "SKB_DROP_REASON_UNHANDLED_PROTO",
+    "SKB_DROP_REASON_SKB_CSUM", "SKB_DROP_REASON_SKB_GSO_SEG", "SKB_DROP_REASON_SKB_UCOPY_FAULT", "SKB_DROP_REASON_DEV_HDR",
+    "SKB_DROP_REASON_DEV_READY", "SKB_DROP_REASON_FULL_RING", "SKB_DROP_REASON_NOMEM", "SKB_DROP_REASON_HDR_TRUNC",
+    "SKB_DROP_REASON_TAP_FILTER", "SKB_DROP_REASON_TAP_TXFILTER", "SKB_DROP_REASON_ICMP_CSUM", "SKB_DROP_REASON_INVALID_PROTO",
+    "SKB_DROP_REASON_IP_INADDRERRORS", "SKB_DROP_REASON_IP_INNOROUTES", "SKB_DROP_REASON_PKT_TOO_BIG", "SKB_DROP_REASON_DUP_FRAG",
+    "SKB_DROP_REASON_FRAG_REASM_TIMEOUT", "SKB_DROP_REASON_FRAG_TOO_FAR", "SKB_DROP_REASON_TCP_MINTTL",
+    "SKB_DROP_REASON_IPV6_BAD_EXTHDR", "SKB_DROP_REASON_IPV6_NDISC_FRAG", "SKB_DROP_REASON_IPV6_NDISC_HOP_LIMIT",
+    "SKB_DROP_REASON_IPV6_NDISC_BAD_CODE", "SKB_DROP_REASON_IPV6_NDISC_BAD_OPTIONS", "SKB_DROP_REASON_IPV6_NDISC_NS_OTHERHOST",
+    "SKB_DROP_REASON_QUEUE_PURGE", "SKB_DROP_REASON_TC_COOKIE_ERROR", "SKB_DROP_REASON_PACKET_SOCK_ERROR",
+    "SKB_DROP_REASON_TC_CHAIN_NOTFOUND", "SKB_DROP_REASON_TC_RECLASSIFY_LOOP",
+    // the Open vSwitch subsystem's causes (3 << 16) + 1..11
+    "OVS_DROP_LAST_ACTION", "OVS_DROP_ACTION_ERROR", "OVS_DROP_EXPLICIT", "OVS_DROP_EXPLICIT_WITH_ERROR", "OVS_DROP_METER",
+    "OVS_DROP_RECURSION_LIMIT", "OVS_DROP_DEFERRED_LIMIT", "OVS_DROP_FRAG_L2_TOO_LONG", "OVS_DROP_FRAG_INVALID_PROTO",
+    "OVS_DROP_CONNTRACK", "OVS_DROP_IP_TTL",
+    // network-event causes (1 << 24) + 0..9
+    "NetworkEvent_Unknown", "NetworkEvent_EgressFirewall", "NetworkEvent_AdminNetworkPolicy",
+    "NetworkEvent_BaselineAdminNetworkPolicy", "NetworkEvent_NetworkPolicy", "NetworkEvent_MulticastNS",
+    "NetworkEvent_MulticastCluster", "NetworkEvent_NetpolNode", "NetworkEvent_NetpolNamespace", "NetworkEvent_UDNIsolation",
+    "SKB_DROP_UNKNOWN_CAUSE"};
+constexpr uint32_t kFlpNameCount = sizeof(kFlpNames) / sizeof(kFlpNames[0]);
+constexpr uint32_t kNameRcode = 0, kNameRcodeUndefined = 11, kNameTcpInvalid = 12;
+constexpr uint32_t kNameCore = 24, kCoreFirst = 2, kCoreLast = 80;
+constexpr uint32_t kNameOvs = kNameCore + (kCoreLast - kCoreFirst + 1), kOvsBase = (3u << 16) + 1, kOvsCount = 11;
+constexpr uint32_t kNameNetEvent = kNameOvs + kOvsCount, kNetEventBase = 1u << 24, kNetEventCount = 10;
+constexpr uint32_t kNameUnknownCause = kNameNetEvent + kNetEventCount;
+static_assert(kNameUnknownCause + 1 == kFlpNameCount, "name table layout");
+
+constexpr uint32_t cstr_len(const char* p) { uint32_t n = 0; while (p[n]) n++; return n; }
+constexpr uint32_t flp_names_dwords() {
+    uint32_t d = 0;
+    for (uint32_t k = 0; k < kFlpNameCount; k++) d += (cstr_len(kFlpNames[k]) + 3) / 4;
+    return d;
+}
+constexpr uint32_t flp_names_longest() {
+    uint32_t m = 0;
+    for (uint32_t k = 0; k < kFlpNameCount; k++) m = cstr_len(kFlpNames[k]) > m ? cstr_len(kFlpNames[k]) : m;
+    return m;
+}
+// Each name starts at a dword of the blob: a name is read four bytes at a time.
+struct FlpNameTab {
+    uint8_t len[kFlpNameCount];
+    uint16_t off[kFlpNameCount];                 // in dwords
+    uint32_t blob[flp_names_dwords()];
+};
+constexpr FlpNameTab make_flp_names() {
+    FlpNameTab t{};
+    uint32_t o = 0;
+    for (uint32_t k = 0; k < kFlpNameCount; k++) {
+        const uint32_t n = cstr_len(kFlpNames[k]);
+        for (uint32_t b = 0; b < n; b++) t.blob[o + b / 4] |= (uint32_t)(uint8_t)kFlpNames[k][b] << (8 * (b & 3));
+        t.len[k] = (uint8_t)n; t.off[k] = (uint16_t)o;
+        o += (n + 3) / 4;
+    }
+    return t;
+}
+__constant__ FlpNameTab d_flp_names = make_flp_names();
+
+NF_DEV uint32_t drop_cause_name(uint32_t cause) {
+    if (cause - kCoreFirst <= kCoreLast - kCoreFirst) return kNameCore + (cause - kCoreFirst);
+    if (cause - kOvsBase < kOvsCount) return kNameOvs + (cause - kOvsBase);
+    if (cause - kNetEventBase < kNetEventCount) return kNameNetEvent + (cause - kNetEventBase);
+    return kNameUnknownCause;
+}
+
+// "name" of the table, quotes included. No name needs escaping.
+template <typename S> NF_DEV void table_str(S& s, uint32_t idx) {
+    const uint32_t len = d_flp_names.len[idx];
+    if constexpr (is_count<S>::value) s.n += len + 2;
+    else {
+        const uint32_t* p = d_flp_names.blob + d_flp_names.off[idx];
+        s.put('"');
+        for (uint32_t c = 0; c < len; c += 4) {
+            const uint32_t w = p[c >> 2];
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (c + k < len) s.put((uint8_t)(w >> (8 * k)));
+        }
+        s.put('"');
+    }
+}
+
+// jsoniter's WriteString escaping (stream_str.go:311-372, as flp_escape of nfagg_api.hip does for the namer table), one
+// byte at a time in front of another sink: the DNS name is the one string of a line that the host has not seen.
+template <typename S> struct EscSink {
+    S& s;
+    NF_DEV void put(uint8_t b) {
+        if (b > 31 && b != '"' && b != '\\') { s.put(b); return; }
+        s.put('\\');
+        if (b == '"' || b == '\\') s.put(b);
+        else if (b == '\n') s.put('n');
+        else if (b == '\r') s.put('r');
+        else if (b == '\t') s.put('t');
+        else { s.put('u'); s.put('0'); s.put('0'); s.put(hexc(b >> 4)); s.put(hexc(b & 15)); }
+    }
+};
+
+// model.AllZeroIP (record.go:233-238): net.IPv6zero, or net.IPv4zero in its 16-byte form ::ffff:0.0.0.0
+NF_DEV bool all_zero_ip(const Ip4w& a) { return (a.w[0] | a.w[1] | a.w[3]) == 0 && (a.w[2] == 0 || a.w[2] == 0xffff0000u); }
+
+// The longest line: every key of nfagg_flp.hip's worst case plus, in the order of the list above, 15 + 17 + 35 + 14 + 30
+// + 11 + (2 + 6 x 31: a dotted name has at most 31 bytes) for DNS, 27 + 24 for IPsec, 21 + (28 + the longest name) + 27
+// + 41 + 23 for drops, 22 + 23 + 42 for QUIC, 37 for the RTT, 2 x 56 + 2 x 20 + 15 for xlat and the zone.
+constexpr uint32_t kFlpcKeysMax = (15 + 17 + 35 + 14 + 30 + 11 + 2 + 6 * 31) + (27 + 24) + (21 + 28 + flp_names_longest() + 27 + 41 + 23) +
+                                  (22 + 23 + 42) + 37 + (2 * 56 + 2 * 20 + 15);
+constexpr uint32_t kFlpcMaxLine = kFlpMaxLine + kFlpcKeysMax;
+constexpr uint32_t kFlpcNameLds = 64 * 32;                    // the wave's DNS name slots
+constexpr uint32_t kFlpcWindow = 25600;                       // line starts a window takes, from its aligned base
+constexpr uint32_t kFlpcLds = kFlpcWindow + (kFlpcMaxLine + 15) / 16 * 16;
+static_assert(kFlpcLds + kFlpcNameLds <= 32768, "four waves per compute unit");
+
+// The feature parts of one flow, as encode_line's feature policy. load() reads the parts that are present (array given
+// and the flow's present byte has the bit) and nothing of the others.
+struct FlpContent {
+    uint32_t have = 0;          // NFAGG_FEAT_* bits of the parts that were loaded
+    uint32_t add[4] = {};       // additional_metrics @16: flow_rtt (2), ipsec_encrypted_ret, eth | ipsec_encrypted << 16
+    uint32_t dnsw[4] = {};      // dns_metrics @16: latency (2), id | flags << 16, eth | errno << 16 | name[0] << 24
+    uint32_t drp[4] = {};       // pkt_drop_metrics @16: bytes | packets << 16, cause, flags | eth << 16, state
+    uint32_t xlt[10] = {};      // xlat_metrics @16: saddr (4), daddr (4), sport | dport << 16, zone | eth << 16
+    uint32_t quc[2] = {};       // quic_metrics @16: version, eth | long << 16 | short << 24
+    const uint8_t* name = nullptr;   // dns_metrics.name, 32 bytes in this lane's LDS slot (16-byte aligned)
+
+    NF_DEV void load(const PbFeat& F, uint64_t i, uint8_t* name_lds) {
+        const uint32_t p = F.present ? F.present[i] : 0u;
+        have = (F.additional ? p & NFAGG_FEAT_ADDITIONAL : 0u) | (F.dns ? p & NFAGG_FEAT_DNS : 0u) | (F.drops ? p & NFAGG_FEAT_DROPS : 0u) |
+               (F.xlat ? p & NFAGG_FEAT_XLAT : 0u) | (F.quic ? p & NFAGG_FEAT_QUIC : 0u);
+        name = name_lds;
+        if (have & NFAGG_FEAT_ADDITIONAL) {
+            uint32_t w[8]; load_dwords16(F.additional + i * 32, w);
+#pragma unroll
+            for (int k = 0; k < 4; k++) add[k] = w[4 + k];
+        }
+        if (have & NFAGG_FEAT_DNS) {     // name @31..62 is unaligned: whole struct in, the name out of the registers
+            uint32_t w[16]; load_dwords16(F.dns + i * 64, w);
+#pragma unroll
+            for (int k = 0; k < 4; k++) dnsw[k] = w[4 + k];
+            uint32_t nm[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) nm[k] = (w[7 + k] >> 24) | (w[8 + k] << 8);
+            uint4* slot = reinterpret_cast<uint4*>(name_lds);
+            slot[0] = make_uint4(nm[0], nm[1], nm[2], nm[3]); slot[1] = make_uint4(nm[4], nm[5], nm[6], nm[7]);
+        }
+        if (have & NFAGG_FEAT_DROPS) {
+            uint32_t w[8]; load_dwords16(F.drops + i * 32, w);
+#pragma unroll
+            for (int k = 0; k < 4; k++) drp[k] = w[4 + k];
+        }
+        if (have & NFAGG_FEAT_XLAT) {
+            uint32_t w[14]; load_dwords8(F.xlat + i * 56, w);
+#pragma unroll
+            for (int k = 0; k < 10; k++) xlt[k] = w[4 + k];
+        }
+        if (have & NFAGG_FEAT_QUIC) {
+            uint32_t w[6]; load_dwords8(F.quic + i * 24, w);
+            quc[0] = w[4]; quc[1] = w[5];
+        }
+    }
+
+    template <typename S> NF_DEV void dns(S& s) const {                 // decode_protobuf.go:130-143
+        if (!(have & NFAGG_FEAT_DNS)) return;
+        const uint32_t err = (dnsw[3] >> 16) & 0xffu, id = dnsw[2] & 0xffffu, flags = dnsw[2] >> 16;
+        if (err) { lit(s, ",\"DnsErrno\":"); dec<3>(s, err); }
+        if (!id) return;
+        lit(s, ",\"DnsFlags\":"); dec<5>(s, flags);
+        const uint32_t rc = flags & 15u;
+        lit(s, ",\"DnsFlagsResponseCode\":"); table_str(s, rc <= 10 ? kNameRcode + rc : kNameRcodeUndefined);
+        lit(s, ",\"DnsId\":"); dec<5>(s, id);
+        // record.go:116-120 + Duration.Milliseconds(): int64(latency) / 1e6, truncating towards zero
+        lit(s, ",\"DnsLatencyMs\":"); dec_i64(s, (int64_t)((uint64_t)dnsw[0] | ((uint64_t)dnsw[1] << 32)) / 1000000ll);
+        CountSink c;
+        if (dns_dotted<false>(c, name)) {
+            lit(s, ",\"DnsName\":\"");
+            EscSink<S> e{s};
+            dns_dotted<true>(e, name);
+            s.put('"');
+        }
+    }
+    template <typename S> NF_DEV void ipsec(S& s) const {               // decode_protobuf.go:170-178
+        if (!(have & NFAGG_FEAT_ADDITIONAL)) return;
+        const int32_t ret = (int32_t)add[2];
+        if (ret != 0) { lit(s, ",\"IPSecRetCode\":"); dec_i64(s, ret); lit(s, ",\"IPSecStatus\":\"error\""); }
+        else if ((add[3] >> 16) & 0xffu) lit(s, ",\"IPSecRetCode\":0,\"IPSecStatus\":\"success\"");
+    }
+    template <typename S> NF_DEV void drops(S& s) const {               // decode_protobuf.go:145-153
+        if (!(have & NFAGG_FEAT_DROPS) || drp[1] == 0) return;
+        lit(s, ",\"PktDropBytes\":"); dec<5>(s, drp[0] & 0xffffu);
+        lit(s, ",\"PktDropLatestDropCause\":"); table_str(s, drop_cause_name(drp[1]));
+        lit(s, ",\"PktDropLatestFlags\":"); dec<5>(s, drp[2] & 0xffffu);
+        const uint32_t st = drp[3] & 0xffu;
+        lit(s, ",\"PktDropLatestState\":"); table_str(s, kNameTcpInvalid + (st <= 11 ? st : 0u));
+        lit(s, ",\"PktDropPackets\":"); dec<5>(s, drp[0] >> 16);
+    }
+    template <typename S> NF_DEV void quic(S& s) const {                // decode_protobuf.go:188-192, record.go:259-270
+        if (!(have & NFAGG_FEAT_QUIC)) return;
+        lit(s, ",\"QuicSeenLongHdr\":"); dec<3>(s, (quc[1] >> 16) & 0xffu);
+        lit(s, ",\"QuicSeenShortHdr\":"); dec<3>(s, quc[1] >> 24);
+        lit(s, ",\"QuicVersion\":\"QUIC ");
+        if (quc[0] <= 1) { s.put('v'); s.put((uint8_t)('1' + quc[0])); }
+        else { lit(s, "Unknown ("); dec<10>(s, quc[0]); s.put(')'); }
+        s.put('"');
+    }
+    template <typename S> NF_DEV void rtt(S& s) const {                 // record.go:121-125, decode_protobuf.go:180-182
+        const uint64_t v = (uint64_t)add[0] | ((uint64_t)add[1] << 32);
+        if ((have & NFAGG_FEAT_ADDITIONAL) && v) { lit(s, ",\"TimeFlowRttNs\":"); dec_i64(s, (int64_t)v); }
+    }
+    NF_DEV bool xlated() const {                                        // decode_protobuf.go:155-157
+        return (have & NFAGG_FEAT_XLAT) && !all_zero_ip(Ip4w{{xlt[0], xlt[1], xlt[2], xlt[3]}}) && !all_zero_ip(Ip4w{{xlt[4], xlt[5], xlt[6], xlt[7]}});
+    }
+    template <typename S> NF_DEV void xlat(S& s) const {                // decode_protobuf.go:158-167
+        if (!xlated()) return;
+        lit(s, ",\"XlatDstAddr\":\""); ip_text(s, Ip4w{{xlt[4], xlt[5], xlt[6], xlt[7]}}); s.put('"');
+        if (xlt[8] >> 16) { lit(s, ",\"XlatDstPort\":"); dec<5>(s, xlt[8] >> 16); }
+        lit(s, ",\"XlatSrcAddr\":\""); ip_text(s, Ip4w{{xlt[0], xlt[1], xlt[2], xlt[3]}}); s.put('"');
+        if (xlt[8] & 0xffffu) { lit(s, ",\"XlatSrcPort\":"); dec<5>(s, xlt[8] & 0xffffu); }
+    }
+    template <typename S> NF_DEV void zone(S& s) const {
+        if (xlated()) { lit(s, ",\"ZoneId\":"); dec<5>(s, xlt[9] & 0xffffu); }
+    }
+};
+
+// ---- kernel 1: as k_flp_size, the line measured with the flow's feature parts
+__global__ __launch_bounds__(kScanBlock) void k_flpc_size(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F,
+                                                          uint32_t* __restrict__ rows, uint32_t* __restrict__ local_off,
+                                                          uint32_t* __restrict__ block_sum, uint32_t* __restrict__ n_deferred) {
+    __shared__ uint32_t wave_tot[kScanBlock / 64];
+    __shared__ __align__(16) uint8_t name_lds[kScanBlock][32];
+    __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
+    const uint8_t* tab = stage_names<kScanBlock>(P.names, P.n_names, tab_lds);
+    const uint64_t i = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x;
+    uint32_t len = 0;
+    bool deferred = false;
+    if (i < n) {
+        Rec r;
+        load_record(recs, i, r);
+        uint32_t row[7];
+        flp_rows(tab, P.n_names, r, row);
+        deferred = flp_deferred(r);
+        if (!deferred) {
+            FlpContent f;
+            f.load(F, i, name_lds[threadIdx.x]);
+            CountSink c;
+            encode_line(c, r, P, row, f);
+            len = c.n;
+        }
+        uint4* o = reinterpret_cast<uint4*>(rows + i * 8);
+        o[0] = make_uint4(row[0], row[1], row[2], row[3]);
+        o[1] = make_uint4(row[4], row[5], row[6], len);
+    }
+    const int lane = threadIdx.x & 63;
+    const uint64_t dm = __ballot(deferred);
+    if (lane == 0 && dm) atomicAdd(n_deferred, (uint32_t)__popcll(dm));
+    block_scan(len, i, n, wave_tot, local_off, block_sum);
+}
+
+// ---- kernel 3: as k_flp_write, windows of kFlpcWindow bytes (the DNS name slots take 2 KiB of the 32 KiB)
+__global__ __launch_bounds__(64) void k_flpc_write(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F,
+                                                   const uint32_t* __restrict__ rows, const uint32_t* __restrict__ local_off,
+                                                   const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
+                                                   uint64_t* __restrict__ line_offsets, uint8_t* __restrict__ deferred) {
+    __shared__ __align__(16) uint8_t lds[kFlpcLds];
+    __shared__ __align__(16) uint8_t name_lds[64][32];
+    const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
+    WaveImage w(block_base, local_off, i0);
+    uint64_t my_off = 0; uint32_t my_len = 0;
+    uint32_t row[7] = {};
+    Rec r;
+    FlpContent f;
+    if (i < n) {
+        load_record(recs, i, r);
+        const uint4* q = reinterpret_cast<const uint4*>(rows + i * 8);
+        const uint4 a = q[0], b = q[1];
+        row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w; row[4] = b.x; row[5] = b.y; row[6] = b.z;
+        my_len = b.w;
+        if (my_len) f.load(F, i, name_lds[threadIdx.x]);              // a deferred record's parts are not read
+        my_off = record_off(block_base, local_off, i);
+        line_offsets[i] = my_off;
+        if (i == n - 1) line_offsets[n] = my_off + my_len;
+        if (deferred) deferred[i] = my_len == 0 ? 1 : 0;     // every line that is written has at least its braces
+    }
+    w.close(my_off + my_len, out);
+    const uint32_t p0 = w.pos(my_off);                            // my line = image bytes [p0, p0 + my_len)
+    uint32_t lo = w.shift;
+    while (lo < w.span) {
+        const uint32_t base = lo & ~15u;
+        const bool mine = my_len && p0 >= lo && p0 - base < kFlpcWindow;
+        if (mine) { FlpLds s{lds + (p0 - base)}; encode_line(s, r, P, row, f); }
+        uint32_t hi = mine ? p0 + my_len : lo;                  // the window's end: at most base + kFlpcWindow + kFlpcMaxLine
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(hi, d, 64); hi = o > hi ? o : hi; }
+        __syncthreads();
+        copy_image_out(w.dst, lds, base, lo, hi);
+        __syncthreads();
+        lo = hi;
+    }
+}
+
+hipError_t launch_flpc_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, uint32_t* d_rows, uint32_t* d_local_off,
+                            uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_flpc_size, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_sum, d_n_deferred);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
+}
+
+hipError_t launch_flpc_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const uint32_t* d_rows,
+                             const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
+                             uint8_t* d_deferred, hipStream_t s) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_flpc_write, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_base,
+                       (uint8_t*)d_out, d_line_offsets, d_deferred);
+    return hipGetLastError();
+}
+
+}  // namespace nfagg

@@ -88,36 +88,6 @@ template <typename S> NF_DEV void put_duration(S& s, uint32_t field, uint64_t d_
     put_uint(s, 2, nanos);
 }
 
-// utils.DNSRawNameToDotted (pkg/utils/utils.go:18-58) over the 32-byte kernel copy at `raw` (the lane's LDS slot):
-// bytes up to the first NUL, label by label; stops at a zero length, a compression pointer, or a label that
-// runs past the end. EMIT = false only measures.
-template <bool EMIT, typename S> NF_DEV uint32_t dns_dotted(S& s, const uint8_t* __restrict__ raw) {
-    uint32_t nb = 0;
-    while (nb < 32 && raw[nb] != 0) nb++;
-    uint32_t i = 0, out = 0;
-    while (i < nb) {
-        const uint32_t l = raw[i];
-        if (l == 0 || (l & 0xC0u) == 0xC0u) break;
-        i++;
-        if (i + l > nb) break;
-        if (out) { if (EMIT) s.put('.'); out++; }
-        if (EMIT) for (uint32_t k = 0; k < l; k++) s.put(raw[i + k]);
-        out += l; i += l;
-    }
-    return out;
-}
-
-template <int N> NF_DEV void load_dwords16(const uint8_t* p, uint32_t (&w)[N]) {   // N/4 16-byte loads
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-#pragma unroll
-    for (int k = 0; k < N / 4; k++) { const uint4 v = q[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
-}
-template <int N> NF_DEV void load_dwords8(const uint8_t* p, uint32_t (&w)[N]) {    // N/2 8-byte loads
-    const uint2* q = reinterpret_cast<const uint2*>(p);
-#pragma unroll
-    for (int k = 0; k < N / 2; k++) { const uint2 v = q[k]; w[2 * k] = v.x; w[2 * k + 1] = v.y; }
-}
-
 // The body of pbflow.Record for one flow: evicted record `r`, plus the feature parts of flow `i` when F carries
 // them — each part is read whole with vector loads before anything is emitted. `name_lds`: 32 bytes of LDS owned by
 // this lane (the DNS name is walked byte by byte). Same code sizes (CountSink) and writes (WindowSink).

@@ -462,6 +462,43 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, need.value, n_def.value
 
+    # -- export encode (MapTracer flow -> direct-FLP JSON line), nfagg_encode_flp_json_content
+    def encode_flp_json_content(self, records: np.ndarray, present, parts, now_unix_ns: int, mono_now_ns: int, names: np.ndarray,
+                                agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown"):
+        """encode_flp_json over full BpfFlowContents: `records`, `present` (FEAT_* bits per flow) and `parts` ({"additional" |
+        "dns" | "drops" | "xlat" | "quic": array of n structs}; other kinds are ignored) as map_merge returns them.
+        present=None: no flow carries a part. Returns (buf, line_offsets, deferred) as encode_flp_json does."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
+        feat = None
+        if present is not None:
+            feat, keep_f = self._pb_features(n, present, {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS})
+        off = np.zeros(n + 1, dtype=np.uint64)
+        deferred = np.zeros(n, dtype=np.uint8)
+        n_def = C.c_size_t(0)
+        buf = self._encode_grown(n, 640, lambda p, cap, need: L.lib.nfagg_encode_flp_json_content(
+            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat) if feat is not None else None, C.byref(o), p, cap,
+            off.ctypes.data_as(C.c_void_p), deferred.ctypes.data_as(C.c_void_p), C.byref(n_def), need))
+        assert int(deferred.sum()) == n_def.value
+        return buf, off, deferred
+
+    def encode_flp_json_content_device(self, d_records: int, n: int, d_present: int, d_parts, now_unix_ns: int, mono_now_ns: int,
+                                       names: np.ndarray, agent_ip, time_received: int, d_out: int, out_cap: int, d_line_offsets: int,
+                                       d_deferred: int = 0, unknown: bytes = b"unknown"):
+        """Device-resident variant (raw device pointers, e.g. the d_out of map_merge_device; d_present = 0: no parts; d_out = 0
+        asks for the size). Returns (rc, bytes needed/written, deferred records)."""
+        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
+        feat = None
+        if d_present:
+            feat, _ = self._pb_features(n, d_present, {k: v for k, v in (d_parts or {}).items() if k in _CONTENT_PARTS}, device=True)
+        need, n_def = C.c_size_t(0), C.c_size_t(0)
+        rc = L.lib.nfagg_encode_flp_json_content_device(
+            self._h, C.c_void_p(d_records), n, C.byref(feat) if feat is not None else None, C.byref(o), C.c_void_p(d_out or None), out_cap,
+            C.c_void_p(d_line_offsets), C.c_void_p(d_deferred or None), C.byref(n_def), C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value, n_def.value
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -623,6 +660,9 @@ class FlowGroup:
 
 
 IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6 = 256, 257      # go-ipfix NewTemplateID() from 255: v4 is created first
+
+
+_CONTENT_PARTS = ("additional", "dns", "drops", "xlat", "quic")     # the parts nfagg_pb_features carries
 
 
 def _encode_options(cls, now_unix_ns, mono_now_ns, names, unknown):

@@ -7,7 +7,11 @@ Per size: a Zipf(1.1) stream over F keys (4 F records) is folded and evicted on 
 evicted records. Reported per encoder: the median wall time of a whole call (size pass, its read-back of the total,
 write pass), flows/s, bytes moved (144 B per flow read, the output bytes written, 8 B per flow of offsets; the JSON
 encoder also writes and reads 32 B per flow of interface rows and writes 1 B per flow of deferred flags) and that rate
-as a fraction of 8 TB/s. Kernel-level device time: run under rocprofv3 --kernel-trace --stats."""
+as a fraction of 8 TB/s. Kernel-level device time: run under rocprofv3 --kernel-trace --stats.
+
+--content: the MapTracer leg instead. The flows evicted at the larger size are encoded as full BpfFlowContents
+(nfagg_encode_flp_json_content_device) with every feature part present on about half of them, and as plain records
+(nfagg_encode_flp_json_device) in the same process as the yardstick; both report their time per output byte."""
 import io
 import os
 import queue
@@ -28,6 +32,39 @@ NAMES = {2: "eth0", 3: "eth1", 4: "br-ex", 5: "ovn-k8s-mp0"}
 names = nf.intf_table([(2, None, "eth0", ""), (3, None, "eth1", "default"), (4, None, "br-ex", ""), (5, None, "ovn-k8s-mp0", "blue")])
 agent = bytes(10) + b"\xff\xff" + bytes([10, 0, 0, 1])
 NOW, MONO = 10**18, 10**12
+CONTENT = "--content" in sys.argv[1:]
+PART_BYTES = {"additional": 32, "dns": 64, "drops": 32, "xlat": 56, "quic": 24}
+
+
+def device_parts(m, seed=5):
+    """present and the five part arrays for m flows, made on the device: all five parts on a random half of the flows, none on
+    the others; random bytes, then the fields that gate keys set so that every key appears (a DNS id and a three-label name, a
+    core drop cause, v4-mapped xlat addresses, an IPsec return code of zero)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    parts = {k: torch.randint(0, 256, (m, b), dtype=torch.uint8, device="cuda", generator=g) for k, b in PART_BYTES.items()}
+    name = np.zeros(32, dtype=np.uint8)
+    raw = b"\x03www\x07example\x03com"
+    name[: len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+    parts["dns"][:, 31:63] = torch.from_numpy(name).cuda()
+    parts["dns"][:, 24] |= 1                                          # id != 0
+    parts["dns"][:, 21:24] = 0                                        # latency below 2^40 ns
+    parts["drops"][:, 20:24] = 0
+    parts["drops"][:, 20] = 2 + torch.randint(0, 79, (m,), dtype=torch.uint8, device="cuda", generator=g)
+    v4 = torch.from_numpy(np.frombuffer(bytes(10) + b"\xff\xff", dtype=np.uint8).copy()).cuda()
+    parts["xlat"][:, 16:28] = v4
+    parts["xlat"][:, 32:44] = v4
+    parts["xlat"][:, 28] |= 1
+    parts["xlat"][:, 44] |= 1
+    parts["additional"][:, 21:28] = 0                                 # rtt below 2^40 ns, ipsec_encrypted_ret = 0
+    parts["quic"][:, 17:20] = 0
+    present = torch.randint(0, 2, (m,), dtype=torch.uint8, device="cuda", generator=g) * 0x37
+    torch.cuda.synchronize()
+    return present, parts
+
+
+def per_byte(what, m, dt, wrote):
+    print(f"  {what:8s} {m} flows -> {wrote} bytes ({wrote / m:.1f} B/line) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s, "
+          f"{dt / wrote * 1e12:.3f} ps per output byte")
 
 
 def timed(fn):
@@ -48,7 +85,7 @@ def line(what, m, dt, wrote, extra_per_flow):
     return dt
 
 
-for flows in (1_000_000, 10_000_000):
+for flows in ((10_000_000,) if CONTENT else (1_000_000, 10_000_000)):
     n = 4 * flows
     d_th = torch.from_numpy(synth.zipf_thresholds(flows, 1.1).view(np.int64)).cuda()
     d = torch.empty(n * 144, dtype=torch.uint8, device="cuda")
@@ -69,6 +106,20 @@ for flows in (1_000_000, 10_000_000):
         (rc, wrote, n_def), dt = timed(lambda: tab.encode_flp_json_device(d_ev.data_ptr(), m, NOW, MONO, names, agent, 1_700_000_000,
                                                                           d_out.data_ptr(), need, d_off.data_ptr(), d_def.data_ptr()))
         assert rc == nf.OK and wrote == need and n_def == 0
+        if CONTENT:
+            per_byte("plain", m, dt, wrote)
+            del d_out
+            d_present, d_parts = device_parts(m)
+            feat = (d_present.data_ptr(), {k: v.data_ptr() for k, v in d_parts.items()})
+            rc, need, n_def = tab.encode_flp_json_content_device(d_ev.data_ptr(), m, *feat, NOW, MONO, names, agent, 1_700_000_000, 0, 0,
+                                                                 d_off.data_ptr())
+            d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+            (rc, wrote, n_def), dt = timed(lambda: tab.encode_flp_json_content_device(
+                d_ev.data_ptr(), m, *feat, NOW, MONO, names, agent, 1_700_000_000, d_out.data_ptr(), need, d_off.data_ptr(), d_def.data_ptr()))
+            assert rc == nf.OK and wrote == need and n_def == 0
+            per_byte("content", m, dt, wrote)
+            print(f"  parts on {int((d_present != 0).sum())} of {m} flows")
+            continue
         dt_json = line("json", m, dt, wrote, 64 + 1)
         del d_out, d_def
         # IPFIX on the same records (A/B)
