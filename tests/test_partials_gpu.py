@@ -74,10 +74,9 @@ class Ranks:
         return nf.sort_by_key(np.concatenate(out)), counts
 
 
-@pytest.mark.parametrize("n_ranks,hot", [(1, 0), (2, 0), (4, 900), (8, 0), (8, 999)])
-def test_ranks_with_contiguous_slices_equal_one_accounter(nf, O, n_ranks, hot):
-    """bench.py's layout: rank r holds arrival positions [r n, (r+1) n) of the one stream."""
-    recs = _stream(O, 480_000, 50_000, seed=21, hot=hot)
+def ranks_with_contiguous_slices(nf, O, recs, n_ranks):
+    """The rank driver of the test below for any stream (tests/test_crafted_hashes_gpu.py feeds it crafted key hashes): two epochs,
+    rank r folds arrival positions [r n, (r+1) n), the union of the ranks' evictions equals ONE Accounter."""
     per = len(recs) // n_ranks
     R = Ranks(nf, n_ranks)
     try:
@@ -91,6 +90,12 @@ def test_ranks_with_contiguous_slices_equal_one_accounter(nf, O, n_ranks, hot):
                 assert sum(map(sum, counts)) > 0
     finally:
         R.close()
+
+
+@pytest.mark.parametrize("n_ranks,hot", [(1, 0), (2, 0), (4, 900), (8, 0), (8, 999)])
+def test_ranks_with_contiguous_slices_equal_one_accounter(nf, O, n_ranks, hot):
+    """bench.py's layout: rank r holds arrival positions [r n, (r+1) n) of the one stream."""
+    ranks_with_contiguous_slices(nf, O, _stream(O, 480_000, 50_000, seed=21, hot=hot), n_ranks)
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
