@@ -156,7 +156,7 @@ def _distinct(rng, n, bits=64):
 def family_targets(name, rng, mask, consts):
     """The target hashes of a family (see each branch) for a table of mask + 1 slots."""
     bits = int(mask).bit_length()
-    assert mask == (1 << bits) - 1 and 16 <= bits <= 21
+    assert mask == (1 << bits) - 1 and 10 <= bits <= 21       # the fold's tables have 2^16..2^21 slots, the map merge's join 2^10 and up
     win, ent = consts["window"], consts["kEntries"]
     if name == "same64":                      # groups of flows with ONE hash: every full-key compare behind a hash match
         return np.repeat(_distinct(rng, len(SAME64_GROUPS)), SAME64_GROUPS)

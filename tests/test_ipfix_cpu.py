@@ -317,3 +317,20 @@ def test_c_driver_builds_against_the_header_alone(nf, tmp_path):
                            os.path.join(root, "tools", "c", "nfagg_ipfix_cdriver.c"), "-o", exe, "-L", libdir, "-lnfagg", "-Wl,-rpath," + libdir])
     needed = subprocess.check_output(["readelf", "-d", exe], text=True)
     assert "libnfagg.so" in needed and "torch" not in needed and "python" not in needed
+
+
+def test_flow_times_on_the_edges_against_python_integers():
+    """ipfix_ref.flow_times on the edges of tests/test_export_edges_gpu.py: time stamps ahead of the clock by a wrap, 2^63 away
+    from it, zero; clocks before 1970. Expected: now.Add(-Duration(mono - ts)) with the subtraction and the negation wrapping
+    in int64 (record.go:90-97), then uint32(t.Unix()) and uint64(t.UnixMilli()) (ipfix.go:286-300), both flooring."""
+    mono = 2_500_000
+    ts = [0, 1, mono - 1, mono, mono + 1, 2**64 - 5, 2**64 - 1, 2**63 + 12345, 2**63, 2**63 - 1, (mono + 2**63) % 2**64, (mono + 2**63 + 1) % 2**64,
+          (mono - 2**63 + 1) % 2**64, mono - 999_999, mono - 1_000_000, 123_456_789_012_345_678]
+    for now in (1_700_000_000_123_456_789, 5, 0, -1, -999_999, -10**9, -10**15, -10**17, 2**32 * 10**9 - 1, 2**32 * 10**9):
+        sec, ms = R.flow_times(np.array(ts, dtype=np.uint64), now, mono)
+        for k, v in enumerate(ts):
+            delta = (mono - v) % 2**64
+            d = -(delta - 2**64 if delta >= 2**63 else delta)
+            t = now + (d if d < 2**63 else d - 2**64)
+            assert int(sec[k]) == (t // 10**9) & 0xFFFFFFFF, (now, v)
+            assert int(ms[k]) == (t // 10**6) % 2**64, (now, v)

@@ -146,45 +146,56 @@ def _namer(names):
 
 
 def test_decoded_fields_equal_the_host_mirror_record(nf, O):
-    """What ipfix.go:272-322 takes from accounter.NewRecord(...), field by field, read back through the collector's decoder."""
-    recs = stream(nf, O, 2000, seed=5)
-    with nf.FlowTable(max_entries=64) as tab:
-        buf, off = tab.encode_ipfix(recs, NOW, MONO, nf.intf_table(NAMES), EXPORT, 1000)
+    """What ipfix.go:272-322 takes from accounter.NewRecord(...), field by field, read back through the collector's decoder;
+    then the same over the edge stream of tests/test_flp_json_gpu.py (times ahead of the clock by a wrap, start = 2^63 + ...,
+    Bytes = 2^64 - 1) under clocks before 1970, where the seconds and milliseconds are those of a negative time."""
+    import test_flp_json_gpu as G
     nf.SetInterfaceNamer(_namer(NAMES))
     try:
-        col = R.Collector()
-        col.decode(R.template_message(False, EXPORT, 1000))
-        col.decode(R.template_message(True, EXPORT, 1000))
-        raw = buf.tobytes()
-        for i, r in enumerate(recs):
-            rec = nf.NewRecord(r["id"], r["metrics"], NOW, MONO)
-            d = col.decode(raw[int(off[i]):int(off[i + 1])])
-            v6 = int(rec.Metrics["eth_protocol"]) == 0x86DD
-            assert (d["seq"], d["export_time"], d["domain"], d["set_id"]) == (1000 + i, EXPORT, 1, 257 if v6 else 256)
-            f = d["records"][0]
-            sip, dip = bytes(rec.ID["src_ip"]), bytes(rec.ID["dst_ip"])
-            if v6:
-                assert (f["sourceIPv6Address"], f["destinationIPv6Address"]) == (sip, dip)
-                assert (f["nextHeaderIPv6"], f["icmpTypeIPv6"], f["icmpCodeIPv6"]) == (
-                    int(rec.ID["transport_protocol"]), int(rec.ID["icmp_type"]), int(rec.ID["icmp_code"]))
-            else:
-                to4 = lambda a: a[12:] if a[:12] == bytes(10) + b"\xff\xff" else bytes(4)   # noqa: E731
-                assert (f["sourceIPv4Address"], f["destinationIPv4Address"]) == (to4(sip), to4(dip))
-                assert (f["protocolIdentifier"], f["icmpTypeIPv4"], f["icmpCodeIPv4"]) == (
-                    int(rec.ID["transport_protocol"]), int(rec.ID["icmp_type"]), int(rec.ID["icmp_code"]))
-            assert f["ethernetType"] == int(rec.Metrics["eth_protocol"])
-            assert f["flowDirection"] == rec.Interfaces[0].Direction
-            assert f["interfaceName"] == rec.Interfaces[0].Interface
-            assert (f["sourceMacAddress"], f["destinationMacAddress"]) == (bytes(rec.Metrics["src_mac"]), bytes(rec.Metrics["dst_mac"]))
-            assert (f["sourceTransportPort"], f["destinationTransportPort"]) == (int(rec.ID["src_port"]), int(rec.ID["dst_port"]))
-            assert f["octetDeltaCount"] == int(rec.Metrics["bytes"]) and f["packetDeltaCount"] == int(rec.Metrics["packets"])
-            assert f["tcpControlBits"] == int(rec.Metrics["flags"])
-            assert f["flowStartSeconds"] == (rec.TimeFlowStart // 10**9) & 0xFFFFFFFF
-            assert f["flowStartMilliseconds"] == (rec.TimeFlowStart // 10**6) % 2**64
-            assert f["flowEndSeconds"] == (rec.TimeFlowEnd // 10**9) & 0xFFFFFFFF
-            assert f["flowEndMilliseconds"] == (rec.TimeFlowEnd // 10**6) % 2**64
+        for recs, now in ((stream(nf, O, 2000, seed=5), NOW), (G.stream(nf, O, 700, seed=6, keep_tls=True), -10**15),
+                          (G.stream(nf, O, 700, seed=7, keep_tls=True), -10**17)):
+            _decoded_fields_equal_the_host_mirror_record(nf, recs, now)
     finally:
         nf.SetInterfaceNamer(nf.accounter._default_namer)
+
+
+def _decoded_fields_equal_the_host_mirror_record(nf, recs, now):
+    with nf.FlowTable(max_entries=64) as tab:
+        buf, off = tab.encode_ipfix(recs, now, MONO, nf.intf_table(NAMES), EXPORT, 1000)
+    negative = 0
+    col = R.Collector()
+    col.decode(R.template_message(False, EXPORT, 1000))
+    col.decode(R.template_message(True, EXPORT, 1000))
+    raw = buf.tobytes()
+    for i, r in enumerate(recs):
+        rec = nf.NewRecord(r["id"], r["metrics"], now, MONO)
+        d = col.decode(raw[int(off[i]):int(off[i + 1])])
+        v6 = int(rec.Metrics["eth_protocol"]) == 0x86DD
+        assert (d["seq"], d["export_time"], d["domain"], d["set_id"]) == (1000 + i, EXPORT, 1, 257 if v6 else 256)
+        f = d["records"][0]
+        sip, dip = bytes(rec.ID["src_ip"]), bytes(rec.ID["dst_ip"])
+        if v6:
+            assert (f["sourceIPv6Address"], f["destinationIPv6Address"]) == (sip, dip)
+            assert (f["nextHeaderIPv6"], f["icmpTypeIPv6"], f["icmpCodeIPv6"]) == (
+                int(rec.ID["transport_protocol"]), int(rec.ID["icmp_type"]), int(rec.ID["icmp_code"]))
+        else:
+            to4 = lambda a: a[12:] if a[:12] == bytes(10) + b"\xff\xff" else bytes(4)   # noqa: E731
+            assert (f["sourceIPv4Address"], f["destinationIPv4Address"]) == (to4(sip), to4(dip))
+            assert (f["protocolIdentifier"], f["icmpTypeIPv4"], f["icmpCodeIPv4"]) == (
+                int(rec.ID["transport_protocol"]), int(rec.ID["icmp_type"]), int(rec.ID["icmp_code"]))
+        assert f["ethernetType"] == int(rec.Metrics["eth_protocol"])
+        assert f["flowDirection"] == rec.Interfaces[0].Direction
+        assert f["interfaceName"] == rec.Interfaces[0].Interface
+        assert (f["sourceMacAddress"], f["destinationMacAddress"]) == (bytes(rec.Metrics["src_mac"]), bytes(rec.Metrics["dst_mac"]))
+        assert (f["sourceTransportPort"], f["destinationTransportPort"]) == (int(rec.ID["src_port"]), int(rec.ID["dst_port"]))
+        assert f["octetDeltaCount"] == int(rec.Metrics["bytes"]) and f["packetDeltaCount"] == int(rec.Metrics["packets"])
+        assert f["tcpControlBits"] == int(rec.Metrics["flags"])
+        assert f["flowStartSeconds"] == (rec.TimeFlowStart // 10**9) & 0xFFFFFFFF
+        assert f["flowStartMilliseconds"] == (rec.TimeFlowStart // 10**6) % 2**64
+        assert f["flowEndSeconds"] == (rec.TimeFlowEnd // 10**9) & 0xFFFFFFFF
+        assert f["flowEndMilliseconds"] == (rec.TimeFlowEnd // 10**6) % 2**64
+        negative += rec.TimeFlowEnd < 0
+    assert now >= 0 or negative > len(recs) / 2
 
 
 def test_exporter_over_a_datagram_socket_pair(nf, O):
@@ -249,6 +260,32 @@ def test_one_million_flows_evicted_and_encoded_on_the_device(nf, O):
     want, want_off = R.encode(ev, NOW, MONO, rows(NAMES), EXPORT, 0xFFFF0000)
     assert got_off.tolist() == want_off.tolist()
     assert got.tobytes() == want
+
+
+def test_more_than_1024_scan_blocks_in_one_call(nf, O):
+    """k_scan_block_sums (csrc/nfagg_encode.hip, the middle kernel of every two-pass job) gives each of its 1024 threads
+    ceil(n_blocks / 1024) block sums: more than one only beyond 1024 blocks of 1024 records. One call of
+    nfagg_encode_ipfix_device over 1024 * 1024 + 1025 records (1026 blocks, the last one ragged) against the restatement, the
+    size query first: a wrong total is seen before anything is written."""
+    import torch
+    n = 1024 * 1024 + 1025
+    assert (n + 1023) // 1024 > 1024 and n % 1024
+    recs = stream(nf, O, n, seed=3)
+    names = nf.intf_table(NAMES)
+    want, want_off = R.encode(recs, NOW, MONO, rows(NAMES), EXPORT, 0xFFFF0000)
+    with nf.FlowTable(max_entries=64) as tab:
+        d_recs = torch.from_numpy(recs.view(np.uint8).reshape(-1)).cuda()
+        d_off = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+        rc, need = tab.encode_ipfix_device(d_recs.data_ptr(), n, NOW, MONO, names, EXPORT, 0xFFFF0000, 0, 0, d_off.data_ptr())
+        assert rc == nf.TRUNCATED and need == len(want)
+        d_out = torch.full((need + 64,), 0xAB, dtype=torch.uint8, device="cuda")
+        rc, wrote = tab.encode_ipfix_device(d_recs.data_ptr(), n, NOW, MONO, names, EXPORT, 0xFFFF0000, d_out.data_ptr(), need, d_off.data_ptr())
+        torch.cuda.synchronize()
+        assert rc == nf.OK and wrote == need
+        got, got_off = d_out.cpu().numpy(), d_off.cpu().numpy().astype(np.uint64)
+    assert np.array_equal(got_off, want_off)
+    assert (got[need:] == 0xAB).all()
+    assert got[:need].tobytes() == want
 
 
 def test_c_driver_matches_restatement(nf, O, tmp_path):

@@ -2,7 +2,9 @@
 
 CPU leg: the oracle's join (oracle/nfagg_oracle_maps.c) against an independent composition in Python — a dict
 keyed by the id, the per-kind orc_rollup chained in Go's walk order. GPU leg: nfagg_map_merge[_device] through
-the C ABI, bit-exact against the oracle; chained into nfagg_encode_pb_content_device.
+the C ABI, bit-exact against the oracle; chained into nfagg_encode_pb_content_device. Both legs again on maps whose ids
+have CHOSEN key hashes (tests/keycraft.py): several ids with one hash, 300 with one home slot and a probe chain that wraps,
+hashes on the edges of the index field, single-bit neighbours — what ids drawn at random never give the join.
 The reference has no unit test for this function (it needs live eBPF maps): parity of the join is unpinned,
 the Accumulate* it applies are pinned by tests/test_oracle_kat.py."""
 import numpy as np
@@ -208,3 +210,196 @@ def test_map_merge_device_then_encode(nf, O):
     want_sorted = O.pb_encode_contents(ids, contents, O.pb_options(now, mono, AGENT4, O.intf_table(NAMES)))
     for pos, j in enumerate(order):
         assert got[j] == want_sorted[pos]
+
+
+# ------------------------------------------------------------------ ids with chosen key hashes (tests/keycraft.py)
+import keycraft as kc  # noqa: E402
+
+CRAFTED = ("same64", "one_home_ones", "one_home_m5", "one_home_ones_min", "one_home_m5_min", "edge", "one_bit")
+
+
+def merge_mask(total_rows):
+    """The join's table (csrc/nfagg_api.hip, map_merge_device_core: `n_slots = 1024; while (n_slots < 2 * total) n_slots <<= 1`):
+    the smallest power of two that is at least max(1024, 2 * total rows), minus one. k_merge_build's home slot is
+    (uint32_t)key_hash & mask."""
+    n_slots = 1024
+    while n_slots < 2 * total_rows:
+        n_slots <<= 1
+    return n_slots - 1
+
+
+def _key40(ids):
+    raw = np.ascontiguousarray(ids).view(np.uint8).reshape(-1, 40).copy()
+    raw[:, 39] = 0
+    return raw
+
+
+def crafted_maps(O, family, n_cpu, seed=1):
+    """Main map and six feature maps over crafted ids (all value bytes random, as make_maps). Every crafted id stands in one to
+    four maps drawn at random — so the members of a group of equal hashes are spread over the main map and different feature
+    maps, some ids stand in several maps and some in feature maps only — among `fill` ids with random hashes; a few rows are
+    listed twice in their map, some of them with another byte 39. The memberships are drawn first: they fix the number of rows,
+    that the mask, and the mask the hashes. Returns (main ids, main values, feats, crafted keys, their target hashes, mask)."""
+    rng = np.random.default_rng(seed * 1000 + CRAFTED.index(family))
+    small = family.endswith("_min")
+    n_keys = {"same64": sum(kc.SAME64_GROUPS), "edge": 14, "one_bit": 313 + 8}.get(family, kc.ONE_HOME_K)
+    fill = 0 if small else 1500
+    n_all = n_keys + fill
+    member = np.zeros((n_all, 7), dtype=bool)                       # column 0: the main map, 1..6: WALK
+    member[np.arange(n_all), rng.integers(0, 7, n_all)] = True
+    more = rng.integers(0, 7, (n_all, 3))
+    for c in range(3):
+        pick = rng.random(n_all) < (0.12 if small else 0.4)
+        member[np.nonzero(pick)[0], more[pick, c]] = True
+    dup = np.zeros(n_all, dtype=bool)                               # ids listed twice in the first map that holds them
+    dup[rng.permutation(n_keys)[:10]] = True
+    total = int(member.sum() + dup.sum())
+    mask = merge_mask(total)
+    assert not small or (total <= 512 and mask == 1023)
+    targets = None
+    if family == "one_bit":
+        # a base id and its 312 single-bit neighbours (no crafting), then 8 ids that differ from the base in word 4 alone AND
+        # share its home slot (searched: a compare that skipped word 4 would fold them into the base)
+        keys = kc.one_bit_keys(rng)
+        w = np.tile(kc.as_words(keys[:1]), (1 << 16, 1))
+        w[:, 4] = rng.integers(0, 1 << 56, len(w), dtype=np.uint64)
+        same_home = (kc.key_hash(w) & np.uint64(mask)) == (kc.key_hash(kc.as_words(keys[:1])) & np.uint64(mask))
+        sib = np.ascontiguousarray(w[same_home][:8]).view(np.uint8).reshape(-1, 40)
+        assert len(sib) == 8 and (sib[:, :32] == keys[0, :32]).all()
+        keys = np.concatenate([keys, sib])
+    else:
+        if family == "edge":                  # keycraft's edge hashes (0, 1, 2, 3, 2^63, 2^64 - 2, 2^64 - 1), and low halves 0, 1, 2^32 - 1 under random high halves
+            hi = rng.integers(1, 1 << 32, 3, dtype=np.uint64) << np.uint64(32)
+            targets = np.concatenate([kc.family_targets("edge", rng, mask, kc.fold_constants()), hi | np.array([0, 1, 0xFFFFFFFF], dtype=np.uint64)])
+        else:
+            targets = kc.family_targets(family[:-4] if small else family, rng, mask, kc.fold_constants())
+        keys = kc.craft(targets, rng)
+    assert len(keys) == n_keys
+    filler = rng.integers(0, 256, (fill, 40), dtype=np.uint8)
+    filler[:, 39] = 0
+    ids_all = np.concatenate([keys, filler])
+    maps = []
+    for q in range(7):
+        rows = np.nonzero(member[:, q])[0]
+        rows = rows[rng.permutation(len(rows))]
+        first = np.array([r for r in rows if dup[r] and member[r].argmax() == q], dtype=np.int64)
+        rows = np.concatenate([rows, first])                       # the second listing comes last: its values must be ignored
+        ids = ids_all[rows].copy()
+        ids[len(rows) - len(first):, 39] = rng.integers(0, 256, len(first))       # byte 39 is no part of the key
+        ids[::7, 39] = 0x5A
+        maps.append(np.ascontiguousarray(ids).view(O.FLOW_ID).reshape(-1))
+    assert sum(len(m) for m in maps) == total
+    mv = np.zeros(len(maps[0]), dtype=O.FLOW_METRICS)
+    mv.view(np.uint8).reshape(len(mv), 104)[:] = rng.integers(0, 256, (len(mv), 104), dtype=np.uint8)
+    feats = {}
+    for q, kind in enumerate(WALK, start=1):
+        dt = O.KIND_DTYPES[O.KIND_INDEX[kind]]
+        n = len(maps[q])
+        fv = np.zeros((n, n_cpu), dtype=dt)
+        fv.view(np.uint8).reshape(n, n_cpu * dt.itemsize)[:] = rng.integers(0, 256, (n, n_cpu * dt.itemsize), dtype=np.uint8)
+        fv.view(np.uint8).reshape(n, n_cpu, dt.itemsize)[rng.integers(0, 3, (n, n_cpu)) == 0] = 0
+        feats[kind] = (maps[q], fv)
+    return maps[0], mv, feats, keys, targets, mask
+
+
+def check_crafted(family, mi, feats, keys, targets, mask):
+    """What the family promises, from keycraft's restatement of the hash; returns (distinct ids, rows listed twice)."""
+    h = kc.key_hash(kc.as_words(keys))
+    home = (h & np.uint64(0xFFFFFFFF)) & np.uint64(mask)
+    if targets is not None:
+        assert np.array_equal(h, targets)
+    if family == "same64":
+        assert sorted(np.unique(h, return_counts=True)[1].tolist()) == sorted(kc.SAME64_GROUPS)
+    elif family.startswith("one_home"):
+        want = mask if "ones" in family else mask - 5
+        assert (home == want).all() and len(keys) == 300 and want + 300 > mask + 1       # the chain runs over the last slot to slot 0
+        assert not family.endswith("_min") or mask == 1023                                # ... and is nearly a third of the table
+    elif family == "edge":
+        low = {int(x) & 0xFFFFFFFF for x in h}
+        assert {0, 1, 0xFFFFFFFF} <= low and {0, (1 << 64) - 1} <= {int(x) for x in h}
+        assert sum(int(x) & 0xFFFFFFFF == 0 for x in h) >= 3 and {0, 1, mask} <= {int(x) for x in home}
+    elif family == "one_bit":
+        assert len(np.unique(home[[0] + list(range(313, 321))])) == 1 and (keys[313:, :32] == keys[0, :32]).all()
+    every = [mi] + [feats[k][0] for k in WALK]
+    where = {}
+    for q, ids in enumerate(every):
+        for k in _key40(ids):
+            where.setdefault(k.tobytes(), set()).add(q)
+    mine = [where[k.tobytes()] for k in _key40(keys)]
+    assert any(len(s) > 1 for s in mine) and any(0 not in s for s in mine) and any(0 in s for s in mine)
+    if family == "same64":                                            # a group's members stand in different maps
+        for t in np.unique(h):
+            assert len(set().union(*[mine[j] for j in np.nonzero(h == t)[0]])) > 1
+    n_dup = sum(len(ids) - len({k.tobytes() for k in _key40(ids)}) for ids in every)
+    assert n_dup == 10 and any(ids["pad"].any() for ids in every)
+    return len(where), n_dup
+
+
+def _first_appearance(mi, feats):
+    seen, order = set(), []
+    for ids in [mi] + [feats[k][0] for k in WALK]:
+        for k in _key40(ids):
+            if k.tobytes() not in seen:
+                seen.add(k.tobytes())
+                order.append(k.tobytes())
+    return b"".join(order)
+
+
+@pytest.mark.parametrize("n_cpu", [1, 8])
+@pytest.mark.parametrize("family", CRAFTED)
+def test_oracle_join_on_crafted_hashes_matches_python_composition(O, family, n_cpu):
+    """The oracle must keep colliding ids apart too (it has its own table and its own restatement of the hash)."""
+    mi, mv, feats, keys, targets, mask = crafted_maps(O, family, n_cpu)
+    n_flows, _ = check_crafted(family, mi, feats, keys, targets, mask)
+    ids, contents = O.map_merge(mi, mv, feats, n_cpu)
+    want_ids, want = python_join(O, mi, mv, feats, n_cpu)
+    assert len(ids) == n_flows
+    assert ids.tobytes() == want_ids.tobytes()
+    for name in ("has_dns", "has_drops", "has_netev", "has_xlat", "has_additional", "has_quic"):
+        assert np.array_equal(contents[name] != 0, want[name] != 0), name
+    for name in ("base", "dns", "drops", "netev", "xlat", "additional", "quic"):
+        assert contents[name].tobytes() == want[name].tobytes(), name
+
+
+def _product_maps(nf, mi, mv, feats):
+    return (mi.view(nf.FLOW_ID), mv.view(nf.FLOW_METRICS),
+            {k: (a.view(nf.FLOW_ID), b.view(np.uint8).reshape(-1).view(nf.ROLLUP_KINDS[k])) for k, (a, b) in feats.items()})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_cpu", [1, 8])
+@pytest.mark.parametrize("family", CRAFTED)
+def test_map_merge_on_crafted_hashes_matches_oracle(nf, O, family, n_cpu):
+    mi, mv, feats, keys, targets, mask = crafted_maps(O, family, n_cpu)
+    n_flows, n_dup = check_crafted(family, mi, feats, keys, targets, mask)
+    with nf.FlowTable(max_entries=64) as tab:
+        got = tab.map_merge(*_product_maps(nf, mi, mv, feats), n_cpu)
+    assert len(got[0]) == n_flows and got[3] == n_dup
+    _assert_matches_oracle(nf, O, got, mi, mv, feats, n_cpu)
+    assert got[0]["id"].tobytes() == _first_appearance(mi, feats)       # main map rows first, then the ids new to each map in walk order
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_cpu", [1, 8])
+@pytest.mark.parametrize("family", ["same64", "one_home_ones", "one_home_m5_min"])
+def test_map_merge_device_on_crafted_hashes_matches_oracle(nf, O, family, n_cpu):
+    import torch
+    mi, mv, feats, keys, targets, mask = crafted_maps(O, family, n_cpu, seed=2)
+    n_flows, n_dup = check_crafted(family, mi, feats, keys, targets, mask)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
+    d_mi, d_mv = dev(mi), dev(mv)
+    d_f = {k: (dev(a), dev(b), len(a)) for k, (a, b) in feats.items()}
+    total = len(mi) + sum(len(a) for a, _ in feats.values())
+    sizes = {"records": 144, "present": 1, "additional": 32, "dns": 64, "drops": 32, "network_events": 72, "xlat": 56, "quic": 24}
+    d_out = {k: torch.full((total * s + 16,), 0xAB, dtype=torch.uint8, device="cuda") for k, s in sizes.items()}
+    with nf.FlowTable(max_entries=64) as tab:
+        rc, n, dups = tab.map_merge_device((d_mi.data_ptr(), d_mv.data_ptr(), len(mi)), {k: (i.data_ptr(), v.data_ptr(), m) for k, (i, v, m) in d_f.items()},
+                                           n_cpu, {k: t.data_ptr() for k, t in d_out.items()}, total)
+    assert rc == nf.OK and n == n_flows and dups == n_dup
+    recs = d_out["records"][: n * 144].cpu().numpy().view(nf.FLOW_RECORD)
+    present = d_out["present"][:n].cpu().numpy()
+    parts = {k: d_out[k][: n * sizes[k]].cpu().numpy().view(nf.ROLLUP_KINDS[k]) for k in sizes if k not in ("records", "present")}
+    _assert_matches_oracle(nf, O, (recs, present, parts, dups), mi, mv, feats, n_cpu)
+    assert recs["id"].tobytes() == _first_appearance(mi, feats)
+    for k, s in sizes.items():
+        assert (d_out[k][n * s:].cpu().numpy() == 0xAB).all(), k          # nothing behind the merged flows is touched

@@ -170,3 +170,40 @@ def test_reference_identical_keys(O):
     r["id"]["src_port"], r["id"]["dst_port"], r["id"]["icmp_type"], r["id"]["proto"] = 4321, 1234, 8, 210
     keys = O.kafka_keys(r)
     assert keys[0].tobytes() == keys[1].tobytes() == b.tobytes() + a.tobytes()
+
+
+def test_oracle_matches_protobuf_runtime_on_the_edge_stream(nf, O):
+    """The records, clocks and agents of tests/test_export_edges_gpu.py (first 300 records): times ahead of the clock by a wrap,
+    start = 2^63 + ..., Bytes = 2^64 - 1, a clock before 1970 (negative seconds: ten-byte varints) — the C oracle against the
+    protobuf runtime, before the GPU is compared with the oracle. record.go:90-97 and proto.go:61-68 decide: time.Time.Add on
+    (sec, nsec), then timestamppb.New = (t.Unix(), t.Nanosecond())."""
+    import gen_pb_golden as G
+    import test_export_edges_gpu as E
+    Record, _ = G.build_classes()
+    n = 300
+    recs = E.G.stream(nf, O, n, seed=5000 + 11, keep_tls=True)
+    E.assert_stream_has_the_edges(recs)
+    present, parts = E.content_parts(nf, n, seed=5000 + 12)
+    # a string field takes valid UTF-8 only (the runtime refuses anything else): such DNS names give way to a well-formed one
+    for k in range(n):
+        try:
+            G.dns_raw_name_to_dotted(parts["dns"]["name"][k]).decode("utf-8")
+        except UnicodeDecodeError:
+            parts["dns"]["name"][k] = np.frombuffer((b"\x03www\x07example\x03com" + bytes(32))[:32], dtype=np.uint8)
+    contents = E.oracle_contents(nf, O, recs, present, parts)
+    orecs = recs.view(O.FLOW_RECORD)
+    namer = G.namer_from(E.NAMES)
+    negative = 0
+    for now, agent in E.clocks_and_agents():
+        opts = O.pb_options(now, E.MONO, agent, O.intf_table(E.NAMES))
+        got_r = O.pb_encode(orecs, opts)
+        got_c = O.pb_encode_contents(orecs["id"], contents, opts)
+        for k in range(n):
+            pb = G.flow_to_pb(Record, orecs[k], now, E.MONO, agent, namer)
+            t = E.flow_time(now, E.MONO, int(orecs[k]["metrics"]["end"]))
+            assert (pb.time_flow_end.seconds, pb.time_flow_end.nanos) == (t // 10**9, t % 10**9)      # the restatement on plain integers
+            negative += t < 0
+            assert got_r[k] == pb.SerializeToString(deterministic=True), f"record {k} now {now}"
+            want_c = G.flow_to_pb(Record, orecs[k], now, E.MONO, agent, namer, content=contents[k]).SerializeToString(deterministic=True)
+            assert got_c[k] == want_c, f"content {k} now {now}"
+    assert negative > n
