@@ -695,9 +695,10 @@ int nfagg_encode_pb_device(nfagg_handle* h, const void* d_records, size_t n, con
  * TimeFlowRtt) and FlowToPB (proto.go:79-118,129-138: dns_id/flags/errno/name
  * via utils.DNSRawNameToDotted, dns_latency only when non-zero, pkt_drop_*, xlat
  * with the address family of the FLOW's eth_protocol, ipsec_encrypted[_ret],
- * quic). Network events (NFAGG_FEAT_NETWORK_EVENTS) need the OVN sample decoder:
- * they are encoded as NewRecord does with a nil decoder (record.go:126) — field 27
- * empty, no drop injected; a caller with a decoder routes those flows through Go.
+ * quic). Network events (NFAGG_FEAT_NETWORK_EVENTS) need the OVN sample decoder's
+ * answers: here they are encoded as NewRecord does with a nil decoder
+ * (record.go:126) — field 27 empty, no drop injected; a caller with a decoder
+ * uses nfagg_netev_resolve and nfagg_encode_pb_content_netev (below).
  * dns.name bytes are copied as they are (Go's Marshal rejects a non-UTF-8 string). */
 typedef struct nfagg_pb_features {
     uint32_t struct_size;        /* sizeof(nfagg_pb_features) */
@@ -849,9 +850,10 @@ int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t 
  *               ipsec_encrypted), TimeFlowRttNs when flow_rtt != 0;
  *   quic:       QuicVersion (record.go:259-270), QuicSeenLongHdr,
  *               QuicSeenShortHdr.
- * Network events (NFAGG_FEAT_NETWORK_EVENTS) need the OVN sample decoder: the
- * line is the one NewRecord gives with a nil decoder (record.go:126) — no
- * NetworkEvents key, no drop injected — the choice nfagg_encode_pb_content makes.
+ * Network events (NFAGG_FEAT_NETWORK_EVENTS) need the OVN sample decoder's
+ * answers: here the line is the one NewRecord gives with a nil decoder
+ * (record.go:126) — no NetworkEvents key, no drop injected; a caller with a
+ * decoder uses nfagg_netev_resolve and nfagg_encode_flp_json_content_netev.
  * Outputs, deferred records and return codes as nfagg_encode_flp_json;
  * features == NULL is nfagg_encode_flp_json. All pointers HOST memory: */
 int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
@@ -863,6 +865,125 @@ int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n
 int nfagg_encode_flp_json_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                          const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
                                          uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes);
+
+/* ------------------------------------------------------------------ */
+/* Network events — the part of model.NewRecord that takes the OVN      */
+/* sample decoder (record.go:126-157), with the decoder's ANSWERS handed */
+/* over as a table: the host asks its decoder once per distinct cookie,  */
+/* the GPU does the per-flow work (look-up, `seen` de-duplication, drop   */
+/* injection, the bytes of both wire formats) and names the cookies the   */
+/* table does not know yet.                                              */
+/* ------------------------------------------------------------------ */
+
+enum { NFAGG_NETEV_ACL = 0,          /* *ovnmodel.ACLEvent                                       */
+       NFAGG_NETEV_OTHER = 1,        /* any other ovnmodel.NetworkEvent                          */
+       NFAGG_NETEV_UNDECODABLE = 2   /* DecodeCookie8Bytes returned an error (record.go:131)     */ };
+enum { NFAGG_NETEV_JSON = 0, NFAGG_NETEV_PB = 1 };      /* nfagg_netev_render formats */
+/* A rendered event (either format) has at most this many bytes; a longer one fails the table. The bound is what lets a
+ * JSON line with four events still fit the write kernel's LDS window. The reference's own test event renders to 115 bytes,
+ * two 63-byte Kubernetes names give about 330. */
+#define NFAGG_NETEV_MAX_RENDERED 512
+#define NFAGG_NETEV_MAX_ROWS     65535
+#define NFAGG_NETEV_NO_ROW       0xFFFFu
+
+/* What the decoder said about one cookie. Strings are arbitrary bytes, pointer and length each (NULL with length 0 is
+ * the empty string); they are read during the call only. `string` is the event's String() — the library does not restate
+ * ACLEvent.String(): rows whose String() bytes are equal share one de-duplication class (record.go:132-137). */
+typedef struct nfagg_netev_entry {
+    uint8_t  cookie[8];          /* NetworkEvents[i] as the kernel wrote it */
+    uint32_t kind;               /* NFAGG_NETEV_* */
+    uint32_t reserved_;
+    const char* action;          /* ACL only: ACLEvent.Action, .Actor, .Name, .Namespace, .Direction */
+    const char* actor;
+    const char* name;
+    const char* namespace_;
+    const char* direction;
+    const char* string;          /* ACL and OTHER: String() */
+    uint32_t action_len, actor_len, name_len, namespace_len, direction_len, string_len;
+} nfagg_netev_entry;
+
+typedef struct nfagg_netev_table nfagg_netev_table;
+
+/* Render one entry as the encoders will emit it (host only: no handle, no device; the CPU suite pins the bytes with it).
+ *   NFAGG_NETEV_JSON: the JSON object of networkevents.ToMap (network_events.go:38-52), keys in byte order, values
+ *     escaped as jsoniter's WriteString: ACL {"Action","Direction","Feature":"acl","Name","Namespace","Type"} with
+ *     Type = Actor and empty strings still present; OTHER {"Message": String()}.
+ *   NFAGG_NETEV_PB: the serialized pbflow.NetworkEvent (proto/flow.proto:27-29, proto.go:140-147): one
+ *     0x0A len {0x0A klen key 0x12 vlen value} per map entry, keys in byte order, key and value written even when
+ *     empty — Go's deterministic marshal.
+ * NFAGG_EINVAL for an UNDECODABLE entry (it renders to nothing) and for a rendering of more than
+ * NFAGG_NETEV_MAX_RENDERED bytes; NFAGG_TRUNCATED with *n_out = bytes needed when cap is smaller. */
+int nfagg_netev_render(const nfagg_netev_entry* entry, int format, void* out, size_t cap, size_t* n_out);
+
+/* Build the table from n entries, one per cookie the caller has asked its decoder about (n <= NFAGG_NETEV_MAX_ROWS).
+ * Every row is rendered once, in both formats. Rows are kept sorted by the cookie's little-endian 64-bit value: ROW r of
+ * the table, as nfagg_netev_resolve reports it, is the r-th cookie in that order. Per row the table also holds the
+ * de-duplication class and the drop cause networkevents.ToDropReasonCode gives (network_events.go:121-131: an ACL with
+ * Action "drop" -> (1 << 24) + the index of Actor in network_events.go:17-28, + 0 for an unknown actor).
+ * Errors (NFAGG_EINVAL, nfagg_last_error names the entry): a duplicate cookie, an unknown kind, a rendering over the cap.
+ * With a handle the table is uploaded to that handle's device and serves its calls until destroyed. h == NULL builds
+ * and checks the table on the host alone (errors through nfagg_last_error(NULL)); such a table is refused by the device calls. */
+int nfagg_netev_table_create(nfagg_handle* h, const nfagg_netev_entry* entries, size_t n, nfagg_netev_table** table);
+void nfagg_netev_table_destroy(nfagg_netev_table* table);
+
+/* record.go:126-157 for n flows, one GPU lane per flow. Inputs as nfagg_map_merge writes them: present (NFAGG_FEAT_*
+ * bits), network_events (NULL: no flow has the part) and drops (NULL: no flow has the part, whatever present says).
+ * For a flow with the network-events part, slots i = 0..3 in order, packets[i] == 0 skipped:
+ *   - the cookie is looked up; a row of kind UNDECODABLE is skipped whole;
+ *   - the row joins the flow's list unless an earlier row of this flow had the same class (the FIRST cookie's map stays);
+ *   - a row with a drop cause injects a packet drop, also when its class was seen: drops part absent -> created with
+ *     start/end of the network-events part, the cause, bytes[i], packets[i], everything else zero, and NFAGG_FEAT_DROPS
+ *     set; present -> cause overwritten, bytes and packets added saturating at 65535 (flow_content.go:209-215), flags
+ *     and state kept.
+ * Outputs (present_out / drops_out may be the input arrays): present_out[n]; drops_out[n] (all zero for a flow without
+ * the part; without a drops input NFAGG_FEAT_DROPS is set only where a drop was injected); rows_out[4n]: the table
+ * rows of the flow's events in order, NFAGG_NETEV_NO_ROW for none. Every other flow is copied through.
+ * A cookie the table has no row for adds nothing to its flow in this call; the distinct ones are returned in `missing`
+ * (missing_cap cookies of 8 bytes, order unspecified; *n_missing = how many were stored; *overflow = 1 when there were
+ * more than fit, what is stored is then a subset without duplicates). The protocol: resolve, ask the decoder about
+ * the missing cookies, rebuild the table, resolve again until *n_missing == 0.
+ * All pointers HOST memory: */
+int nfagg_netev_resolve(nfagg_handle* h, const nfagg_netev_table* table, const uint8_t* present,
+                        const nfagg_network_events_metrics* network_events, const nfagg_pkt_drop_metrics* drops, size_t n,
+                        uint8_t* present_out, nfagg_pkt_drop_metrics* drops_out, uint16_t* rows_out,
+                        uint8_t (*missing)[8], size_t missing_cap, size_t* n_missing, int* overflow);
+/* Same with the arrays in DEVICE memory (8-byte aligned), e.g. the outputs of nfagg_map_merge_device. The missing cookies
+ * come as an open-addressed set of missing_cap 64-bit slots (d_missing_set, zeroed by the call; a slot holds the
+ * cookie's little-endian value, 0 = empty). The all-zero cookie, which a slot cannot hold, is reported by
+ * *zero_missing = 1. *n_missing counts the distinct cookies recorded (the all-zero one included); *overflow as above. */
+int nfagg_netev_resolve_device(nfagg_handle* h, const nfagg_netev_table* table, const uint8_t* d_present,
+                               const nfagg_network_events_metrics* d_network_events, const nfagg_pkt_drop_metrics* d_drops, size_t n,
+                               uint8_t* d_present_out, nfagg_pkt_drop_metrics* d_drops_out, uint16_t* d_rows_out,
+                               uint64_t* d_missing_set, size_t missing_cap, size_t* n_missing, int* zero_missing, int* overflow);
+
+/* nfagg_encode_pb_content with the flows' network events: `features` carries the present_out / drops_out of
+ * nfagg_netev_resolve (so an injected drop is encoded as any other), `rows` its rows_out, `table` the table those rows
+ * index. Field 27 (network_events_metadata, proto.go:140-147) gets one length-delimited NetworkEvent per row, between
+ * dup_list and xlat; no row, no field. A row index beyond the table counts as none. Everything else as
+ * nfagg_encode_pb_content. All pointers HOST memory: */
+int nfagg_encode_pb_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                  const uint16_t* rows, const nfagg_netev_table* table,
+                                  const nfagg_pb_options* opt, void* out, size_t out_cap, uint64_t* frame_offsets,
+                                  uint32_t* body_len, void* kafka_keys, size_t* out_bytes);
+/* Same with every data pointer (d_rows and those inside d_features too) in DEVICE memory. */
+int nfagg_encode_pb_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                         const uint16_t* d_rows, const nfagg_netev_table* table,
+                                         const nfagg_pb_options* opt, void* d_out, size_t out_cap, uint64_t* d_frame_offsets,
+                                         uint32_t* d_body_len, void* d_kafka_keys, size_t* out_bytes);
+
+/* nfagg_encode_flp_json_content with the flows' network events, inputs as for nfagg_encode_pb_content_netev. A flow
+ * with at least one row gains "NetworkEvents":[obj,obj,...] (decode_protobuf.go:184-186) between Interfaces and
+ * Packets; an injected drop prints its "NetworkEvent_" cause. Deferred records stay deferred, their rows are not read.
+ * features may be NULL (no flow carries another part). All pointers HOST memory: */
+int nfagg_encode_flp_json_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                        const uint16_t* rows, const nfagg_netev_table* table,
+                                        const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
+                                        uint8_t* deferred, size_t* n_deferred, size_t* out_bytes);
+/* Same with every data pointer in DEVICE memory. */
+int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                               const uint16_t* d_rows, const nfagg_netev_table* table,
+                                               const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
+                                               uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes);
 
 /* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */

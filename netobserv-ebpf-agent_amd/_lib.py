@@ -98,6 +98,19 @@ class PbFeatures(C.Structure):
                 ("dns", C.c_void_p), ("drops", C.c_void_p), ("xlat", C.c_void_p), ("quic", C.c_void_p)]
 
 
+class NetevEntry(C.Structure):
+    """nfagg_netev_entry (include/nfagg.h)."""
+    _fields_ = [("cookie", C.c_uint8 * 8), ("kind", C.c_uint32), ("reserved_", C.c_uint32),
+                ("action", C.c_char_p), ("actor", C.c_char_p), ("name", C.c_char_p), ("namespace_", C.c_char_p),
+                ("direction", C.c_char_p), ("string", C.c_char_p),
+                ("action_len", C.c_uint32), ("actor_len", C.c_uint32), ("name_len", C.c_uint32), ("namespace_len", C.c_uint32),
+                ("direction_len", C.c_uint32), ("string_len", C.c_uint32)]
+
+
+NETEV_ACL, NETEV_OTHER, NETEV_UNDECODABLE = 0, 1, 2
+NETEV_JSON, NETEV_PB = 0, 1
+NETEV_MAX_RENDERED, NETEV_MAX_ROWS, NETEV_NO_ROW = 512, 65535, 0xFFFF
+
 FEAT_ADDITIONAL, FEAT_DNS, FEAT_DROPS, FEAT_NETWORK_EVENTS, FEAT_XLAT, FEAT_QUIC = 1, 2, 4, 8, 16, 32
 
 
@@ -167,6 +180,15 @@ SIGNATURES = {
     "nfagg_encode_flp_json_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_encode_flp_json_content": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_encode_flp_json_content_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
+    "nfagg_netev_render": (C.c_int, [C.POINTER(NetevEntry), C.c_int, _vp, _sz, _psz]),
+    "nfagg_netev_table_create": (C.c_int, [_vp, C.POINTER(NetevEntry), _sz, C.POINTER(_vp)]),
+    "nfagg_netev_table_destroy": (None, [_vp]),
+    "nfagg_netev_resolve": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _psz, C.POINTER(C.c_int)]),
+    "nfagg_netev_resolve_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _psz, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nfagg_encode_pb_content_netev": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(PbOptions), _vp, _sz, _vp, _vp, _vp, _psz]),
+    "nfagg_encode_pb_content_netev_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(PbOptions), _vp, _sz, _vp, _vp, _vp, _psz]),
+    "nfagg_encode_flp_json_content_netev": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
+    "nfagg_encode_flp_json_content_netev_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

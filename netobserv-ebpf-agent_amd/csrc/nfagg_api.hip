@@ -22,6 +22,7 @@
 #include "nfagg_pb.h"
 #include "nfagg_ipfix.h"
 #include "nfagg_flp.h"
+#include "nfagg_netev.h"
 
 using namespace nfagg;
 
@@ -94,12 +95,15 @@ struct nfagg_handle {
         DevBuf in_records, out, out_offsets;         // host-memory entry points: staged records, output bytes, offsets
         DevBuf out_extra[2];                         //   protobuf: body lengths, kafka keys; FLP: deferred flags
         DevBuf pb_feat[6];                           //   protobuf: present bits and the five feature parts
+        DevBuf ne_rows;                              //   *_netev: the flows' table rows
+        DevBuf ne_in[3], ne_out[3], ne_missing, ne_info;   // nfagg_netev_resolve: staged inputs and outputs, the missing set, its counters
         std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
         std::vector<uint8_t> h_flp_esc;
         template <typename F> void each(F f) {
             for (DevBuf* b : {&local_off, &block_sum, &block_base, &names, &ipfix_name_rows, &flp_rows, &flp_esc, &flp_n_deferred,
                               &in_records, &out, &out_offsets, &out_extra[0], &out_extra[1]}) f(*b);
             for (DevBuf& b : pb_feat) f(b);
+            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info}) f(*b);
         }
     } enc;
     // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
@@ -2189,6 +2193,15 @@ int nfagg_stats_get(nfagg_handle* h, nfagg_stats* out) {
 
 }  // extern "C"
 
+// The cookie table of nfagg_netev_table_create: the sorted rows and the rendered blob, on the host and (with a handle) on its device.
+struct nfagg_netev_table {
+    nfagg_handle* h = nullptr;
+    std::vector<NetevRow> rows;
+    std::vector<uint8_t> blob;
+    void* d_rows = nullptr;
+    void* d_blob = nullptr;
+};
+
 // ---- the export encoders' host side: what protobuf, IPFIX and direct-FLP JSON do alike
 namespace {
 
@@ -2298,9 +2311,31 @@ static int device_features(nfagg_handle* h, const nfagg_pb_features* feat, PbFea
     return NFAGG_OK;
 }
 
+// The *_netev entry points' extra inputs: the flows' rows (DEVICE memory) and the table they index, into F.
+struct NetevArgs { const uint16_t* rows; const nfagg_netev_table* table; };
+static int device_netev(nfagg_handle* h, const NetevArgs* ne, size_t n, PbFeat* F) {
+    if (!ne->table || (n && !ne->rows)) return fail(h, NFAGG_EINVAL, "null network-events rows or table");
+    if (ne->table->h != h || !ne->table->d_rows) return fail(h, NFAGG_EINVAL, "the network-events table was not created for this handle");
+    if (((uintptr_t)ne->rows & 7u) != 0) return fail(h, NFAGG_EINVAL, "network-events rows must be 8-byte aligned");
+    F->ne_rows = ne->rows; F->ne_tab = (const uint8_t*)ne->table->d_rows; F->ne_blob = (const uint8_t*)ne->table->d_blob;
+    F->ne_n = (uint32_t)ne->table->rows.size();
+    return NFAGG_OK;
+}
+// The rows of a host-memory call, uploaded.
+static int stage_netev_rows(nfagg_handle* h, const NetevArgs* ne, size_t n, NetevArgs* dne) {
+    *dne = *ne;
+    if (!n || !ne->rows) return NFAGG_OK;
+    int rc = ensure_buf(h, h->enc.ne_rows, n * 8 + 16);
+    if (rc != NFAGG_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->enc.ne_rows.p, ne->rows, n * 8, hipMemcpyHostToDevice, h->stream));
+    dne->rows = (const uint16_t*)h->enc.ne_rows.p;
+    return NFAGG_OK;
+}
+
 // ---- record -> protobuf (nfagg_pb.hip)
-// feat (optional): DEVICE pointers
-static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const nfagg_pb_options* opt,
+// feat (optional): DEVICE pointers. ne (optional): the network events of the *_netev entry points.
+static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                                 const nfagg_pb_options* opt,
                                  void* d_out, size_t out_cap, uint64_t* d_frame_offsets, uint32_t* d_body_len,
                                  void* d_kafka_keys, size_t* out_bytes) {
     if (!h || !opt || !out_bytes || !d_frame_offsets || (n && (!d_records || !d_body_len))) return fail(h, NFAGG_EINVAL, "null argument");
@@ -2311,6 +2346,7 @@ static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t 
     if (rc != NFAGG_OK) return rc;
     PbFeat F{};
     if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
+    if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
     bool done;
     if ((rc = encode_begin(h, n, d_frame_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
     PbParams P{};
@@ -2349,7 +2385,8 @@ static int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, siz
 }
 
 // feat (optional): HOST pointers
-static int encode_pb_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const nfagg_pb_options* opt,
+static int encode_pb_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                               const nfagg_pb_options* opt,
                                void* out, size_t out_cap, uint64_t* frame_offsets, uint32_t* body_len,
                                void* kafka_keys, size_t* out_bytes) {
     if (!h || !opt || !out_bytes || !frame_offsets || (n && (!records || !body_len))) return fail(h, NFAGG_EINVAL, "null argument");
@@ -2358,34 +2395,52 @@ static int encode_pb_host_core(nfagg_handle* h, const void* records, size_t n, c
         [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
             nfagg_pb_features dfeat{};
             if (feat && n) { int rc = stage_pb_features(h, feat, n, &dfeat); if (rc != NFAGG_OK) return rc; }
-            return encode_pb_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, opt, d_out, out_cap, d_offsets,
+            NetevArgs dne{};
+            if (ne) { int rc = stage_netev_rows(h, ne, n, &dne); if (rc != NFAGG_OK) return rc; }
+            return encode_pb_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, opt, d_out, out_cap, d_offsets,
                                          (uint32_t*)h->enc.out_extra[0].p, kafka_keys ? h->enc.out_extra[1].p : nullptr, out_bytes); });
 }
 
 int nfagg_encode_pb_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_options* opt,
                            void* d_out, size_t out_cap, uint64_t* d_frame_offsets, uint32_t* d_body_len,
                            void* d_kafka_keys, size_t* out_bytes) {
-    return encode_pb_device_core(h, d_records, n, nullptr, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
+    return encode_pb_device_core(h, d_records, n, nullptr, nullptr, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
 }
 
 int nfagg_encode_pb(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_options* opt,
                     void* out, size_t out_cap, uint64_t* frame_offsets, uint32_t* body_len,
                     void* kafka_keys, size_t* out_bytes) {
-    return encode_pb_host_core(h, records, n, nullptr, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
+    return encode_pb_host_core(h, records, n, nullptr, nullptr, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
 }
 
 int nfagg_encode_pb_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                    const nfagg_pb_options* opt, void* d_out, size_t out_cap, uint64_t* d_frame_offsets,
                                    uint32_t* d_body_len, void* d_kafka_keys, size_t* out_bytes) {
     if (!d_features) return fail(h, NFAGG_EINVAL, "null features (use nfagg_encode_pb_device)");
-    return encode_pb_device_core(h, d_records, n, d_features, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
+    return encode_pb_device_core(h, d_records, n, d_features, nullptr, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
 }
 
 int nfagg_encode_pb_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
                             const nfagg_pb_options* opt, void* out, size_t out_cap, uint64_t* frame_offsets,
                             uint32_t* body_len, void* kafka_keys, size_t* out_bytes) {
     if (!features) return fail(h, NFAGG_EINVAL, "null features (use nfagg_encode_pb)");
-    return encode_pb_host_core(h, records, n, features, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
+    return encode_pb_host_core(h, records, n, features, nullptr, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
+}
+
+int nfagg_encode_pb_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                         const uint16_t* d_rows, const nfagg_netev_table* table,
+                                         const nfagg_pb_options* opt, void* d_out, size_t out_cap, uint64_t* d_frame_offsets,
+                                         uint32_t* d_body_len, void* d_kafka_keys, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, table};
+    return encode_pb_device_core(h, d_records, n, d_features, &ne, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
+}
+
+int nfagg_encode_pb_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                  const uint16_t* rows, const nfagg_netev_table* table,
+                                  const nfagg_pb_options* opt, void* out, size_t out_cap, uint64_t* frame_offsets,
+                                  uint32_t* body_len, void* kafka_keys, size_t* out_bytes) {
+    const NetevArgs ne{rows, table};
+    return encode_pb_host_core(h, records, n, features, &ne, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
 }
 
 // ---- record -> IPFIX (nfagg_ipfix.hip)
@@ -2488,8 +2543,10 @@ static int encode_flp_check(nfagg_handle* h, const nfagg_flp_options* opt) {
     return check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
 }
 
-// feat (optional): DEVICE pointers. Without it the kernels of nfagg_flp.hip run, with it those of nfagg_flp_content.hip.
-static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const nfagg_flp_options* opt,
+// feat (optional): DEVICE pointers. Without it the kernels of nfagg_flp.hip run, with it those of nfagg_flp_content.hip;
+// with ne (the *_netev entry points) the latter's instantiations that carry the NetworkEvents hook.
+static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                                  const nfagg_flp_options* opt,
                                   void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
                                   size_t* n_deferred, size_t* out_bytes) {
     int rc = encode_flp_check(h, opt);
@@ -2498,6 +2555,7 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
     PbFeat F{};
     if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
+    if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
     size_t deferred_unused;
     if (!n_deferred) n_deferred = &deferred_unused;
     *n_deferred = 0;
@@ -2525,7 +2583,7 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     P.names = (const nfagg_intf_name*)S.names.p; P.esc = (const uint8_t*)S.flp_esc.p; P.n_names = opt->n_names;
     P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
     uint32_t* counter = (uint32_t*)S.flp_n_deferred.p;
-    if (!feat)
+    if (!feat && !ne)
         return encode_two_pass(h, n, "FLP JSON", "write", d_out, out_cap, out_bytes, n_deferred,
             [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
                 return launch_flp_size(d_records, n, P, rows, local_off, block_sum, block_base, counter, h->stream); },
@@ -2539,7 +2597,8 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
 }
 
 // feat (optional): HOST pointers, uploaded beside the records
-static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const nfagg_flp_options* opt,
+static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                                const nfagg_flp_options* opt,
                                 void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
                                 size_t* n_deferred, size_t* out_bytes) {
     int rc = encode_flp_check(h, opt);
@@ -2550,34 +2609,293 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
         [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
             nfagg_pb_features dfeat{};
             if (feat && n) { int rc2 = stage_pb_features(h, feat, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
-            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, opt, d_out, out_cap, d_offsets,
+            NetevArgs dne{};
+            if (ne) { int rc2 = stage_netev_rows(h, ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
+            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, opt, d_out, out_cap, d_offsets,
                                           deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
 }
 
 int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
                                  size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_device_core(h, d_records, n, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+    return encode_flp_device_core(h, d_records, n, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
                           void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
                           size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_host_core(h, records, n, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+    return encode_flp_host_core(h, records, n, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
 
 // features == NULL: the flows carry no parts, the call is nfagg_encode_flp_json[_device]
 int nfagg_encode_flp_json_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                          const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
                                          uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_device_core(h, d_records, n, d_features, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+    return encode_flp_device_core(h, d_records, n, d_features, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
                                   const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
                                   uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_host_core(h, records, n, features, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+    return encode_flp_host_core(h, records, n, features, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
+
+int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                               const uint16_t* d_rows, const nfagg_netev_table* table,
+                                               const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
+                                               uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, table};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+}
+
+int nfagg_encode_flp_json_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                        const uint16_t* rows, const nfagg_netev_table* table,
+                                        const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
+                                        uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
+    const NetevArgs ne{rows, table};
+    return encode_flp_host_core(h, records, n, features, &ne, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+}
+
+}  // extern "C"
+
+// ---- network events: the cookie table and the resolve kernel (nfagg_netev.hip)
+namespace {
+
+struct NetevStr { const char* p; uint32_t len; };
+// networkevents.ToMap (network_events.go:38-52), keys in byte order. Returns the number of pairs, 0 for an undecodable entry.
+int netev_pairs(const nfagg_netev_entry& e, const char* (&keys)[6], NetevStr (&vals)[6]) {
+    if (e.kind == NFAGG_NETEV_ACL) {
+        static const char* const k[6] = {"Action", "Direction", "Feature", "Name", "Namespace", "Type"};
+        const NetevStr v[6] = {{e.action, e.action_len}, {e.direction, e.direction_len}, {"acl", 3}, {e.name, e.name_len},
+                               {e.namespace_, e.namespace_len}, {e.actor, e.actor_len}};
+        for (int q = 0; q < 6; q++) { keys[q] = k[q]; vals[q] = v[q]; }
+        return 6;
+    }
+    if (e.kind == NFAGG_NETEV_OTHER) { keys[0] = "Message"; vals[0] = {e.string, e.string_len}; return 1; }
+    return 0;
+}
+
+bool netev_strings_ok(const nfagg_netev_entry& e) {
+    const NetevStr v[6] = {{e.action, e.action_len}, {e.actor, e.actor_len}, {e.name, e.name_len}, {e.namespace_, e.namespace_len},
+                           {e.direction, e.direction_len}, {e.string, e.string_len}};
+    for (int q = e.kind == NFAGG_NETEV_ACL ? 0 : 5; q < 6; q++)
+        if (v[q].len && !v[q].p) return false;
+    return true;
+}
+
+void put_varint_host(std::vector<uint8_t>& o, uint64_t v) {
+    while (v >= 0x80) { o.push_back((uint8_t)(v | 0x80)); v >>= 7; }
+    o.push_back((uint8_t)v);
+}
+
+// The rendered bytes of one entry. false: an undecodable entry, or a string so long that the rendering cannot fit the cap
+// (checked before anything of that size is built).
+bool netev_render(const nfagg_netev_entry& e, int format, std::vector<uint8_t>& o) {
+    const char* keys[6]; NetevStr vals[6];
+    const int np = netev_pairs(e, keys, vals);
+    o.clear();
+    if (!np) return false;
+    for (int q = 0; q < np; q++) if (vals[q].len > kNetevMaxRendered) return false;
+    if (format == NFAGG_NETEV_JSON) {
+        uint8_t buf[2 + 6 * kNetevMaxRendered];
+        o.push_back('{');
+        for (int q = 0; q < np; q++) {
+            if (q) o.push_back(',');
+            o.push_back('"'); o.insert(o.end(), keys[q], keys[q] + strlen(keys[q])); o.push_back('"'); o.push_back(':');
+            const uint32_t n = flp_escape(vals[q].p, vals[q].len, buf);
+            o.insert(o.end(), buf, buf + n);
+        }
+        o.push_back('}');
+    } else {
+        for (int q = 0; q < np; q++) {                       // map entry: key = 1, value = 2, both written even when empty
+            const size_t kl = strlen(keys[q]);
+            std::vector<uint8_t> ent;
+            ent.push_back(0x0A); put_varint_host(ent, kl); ent.insert(ent.end(), keys[q], keys[q] + kl);
+            ent.push_back(0x12); put_varint_host(ent, vals[q].len); ent.insert(ent.end(), vals[q].p, vals[q].p + vals[q].len);
+            o.push_back(0x0A); put_varint_host(o, ent.size()); o.insert(o.end(), ent.begin(), ent.end());
+        }
+    }
+    return true;
+}
+
+uint32_t netev_cause(const nfagg_netev_entry& e) {          // networkevents.ToDropReasonCode (network_events.go:121-131)
+    static const char* const causes[10] = {"Unknown", "EgressFirewall", "AdminNetworkPolicy", "BaselineAdminNetworkPolicy", "NetworkPolicy",
+                                           "MulticastNS", "MulticastCluster", "NetpolNode", "NetpolNamespace", "UDNIsolation"};
+    if (e.kind != NFAGG_NETEV_ACL || e.action_len != 4 || memcmp(e.action, "drop", 4) != 0) return 0;
+    for (uint32_t q = 0; q < 10; q++)
+        if (strlen(causes[q]) == e.actor_len && memcmp(causes[q], e.actor, e.actor_len) == 0) return (1u << 24) + q;
+    return 1u << 24;
+}
+
+uint64_t netev_cookie(const uint8_t* c) { uint64_t v; memcpy(&v, c, 8); return v; }
+
+}  // namespace
+
+extern "C" {
+
+int nfagg_netev_render(const nfagg_netev_entry* entry, int format, void* out, size_t cap, size_t* n_out) {
+    if (!entry || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
+    if (format != NFAGG_NETEV_JSON && format != NFAGG_NETEV_PB) return fail(nullptr, NFAGG_EINVAL, "unknown format %d", format);
+    if (entry->kind > NFAGG_NETEV_UNDECODABLE || !netev_strings_ok(*entry)) return fail(nullptr, NFAGG_EINVAL, "bad network-events entry");
+    std::vector<uint8_t> o;
+    if (!netev_render(*entry, format, o)) {
+        if (entry->kind == NFAGG_NETEV_UNDECODABLE) return fail(nullptr, NFAGG_EINVAL, "an undecodable entry renders to nothing");
+        return fail(nullptr, NFAGG_EINVAL, "rendered event exceeds %u bytes", kNetevMaxRendered);
+    }
+    if (o.size() > kNetevMaxRendered) return fail(nullptr, NFAGG_EINVAL, "rendered event has %zu bytes, more than %u", o.size(), kNetevMaxRendered);
+    *n_out = o.size();
+    if (!out || cap < o.size()) return NFAGG_TRUNCATED;
+    memcpy(out, o.data(), o.size());
+    return NFAGG_OK;
+}
+
+int nfagg_netev_table_create(nfagg_handle* h, const nfagg_netev_entry* entries, size_t n, nfagg_netev_table** table) {
+    if (!table || (n && !entries)) return fail(h, NFAGG_EINVAL, "null argument");
+    *table = nullptr;
+    if (n > NFAGG_NETEV_MAX_ROWS) return fail(h, NFAGG_EINVAL, "%zu network-events entries, more than %d", n, NFAGG_NETEV_MAX_ROWS);
+    std::vector<uint32_t> order(n);
+    for (size_t k = 0; k < n; k++) {
+        order[k] = (uint32_t)k;
+        if (entries[k].kind > NFAGG_NETEV_UNDECODABLE) return fail(h, NFAGG_EINVAL, "network-events entry %zu: unknown kind %u", k, entries[k].kind);
+        if (!netev_strings_ok(entries[k])) return fail(h, NFAGG_EINVAL, "network-events entry %zu: null string with a length", k);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return netev_cookie(entries[a].cookie) < netev_cookie(entries[b].cookie); });
+    for (size_t r = 1; r < n; r++)
+        if (netev_cookie(entries[order[r]].cookie) == netev_cookie(entries[order[r - 1]].cookie))
+            return fail(h, NFAGG_EINVAL, "network-events entries %u and %u carry the same cookie", std::min(order[r - 1], order[r]), std::max(order[r - 1], order[r]));
+    nfagg_netev_table* t = new (std::nothrow) nfagg_netev_table;
+    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
+    t->h = h;
+    t->rows.resize(n);
+    std::vector<uint8_t> piece;
+    for (size_t r = 0; r < n; r++) {
+        const nfagg_netev_entry& e = entries[order[r]];
+        NetevRow& row = t->rows[r];
+        row = NetevRow{};
+        row.cookie = netev_cookie(e.cookie);
+        row.kind = (uint16_t)e.kind;
+        row.cls = (uint16_t)kNetevNoRow;
+        if (e.kind == NFAGG_NETEV_UNDECODABLE) continue;
+        row.cause = netev_cause(e);
+        row.cls = (uint16_t)r;                                      // the first row with the same String() bytes
+        for (size_t q = 0; q < r; q++) {
+            const nfagg_netev_entry& f = entries[order[q]];
+            if (f.kind != NFAGG_NETEV_UNDECODABLE && f.string_len == e.string_len && (e.string_len == 0 || memcmp(f.string, e.string, e.string_len) == 0)) {
+                row.cls = (uint16_t)q;
+                break;
+            }
+        }
+        for (int format : {NFAGG_NETEV_JSON, NFAGG_NETEV_PB}) {
+            if (!netev_render(e, format, piece) || piece.size() > kNetevMaxRendered) {
+                const size_t got = piece.size();
+                delete t;
+                return fail(h, NFAGG_EINVAL, "network-events entry %u: its %s rendering has %s%zu bytes, the cap is %u", order[r],
+                            format == NFAGG_NETEV_JSON ? "JSON" : "protobuf", got ? "" : "more than ", got ? got : (size_t)kNetevMaxRendered, kNetevMaxRendered);
+            }
+            const uint32_t off = (uint32_t)t->blob.size();
+            t->blob.insert(t->blob.end(), piece.begin(), piece.end());
+            t->blob.resize((t->blob.size() + 15) / 16 * 16, 0);      // the kernels read a piece 16 bytes at a time
+            if (format == NFAGG_NETEV_JSON) { row.json_off = off; row.json_len = (uint16_t)piece.size(); }
+            else { row.pb_off = off; row.pb_len = (uint16_t)piece.size(); }
+        }
+    }
+    if (h) {
+        auto up = [&]() -> int {
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMalloc(&t->d_rows, std::max<size_t>(n, 1) * sizeof(NetevRow)));
+            HIP_TRY(h, hipMalloc(&t->d_blob, std::max<size_t>(t->blob.size(), 16)));
+            if (n) HIP_TRY(h, hipMemcpy(t->d_rows, t->rows.data(), n * sizeof(NetevRow), hipMemcpyHostToDevice));
+            if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
+            return NFAGG_OK;
+        };
+        const int rc = up();
+        if (rc != NFAGG_OK) { nfagg_netev_table_destroy(t); return rc; }
+    }
+    *table = t;
+    return NFAGG_OK;
+}
+
+void nfagg_netev_table_destroy(nfagg_netev_table* t) {
+    if (!t) return;
+    if (t->h && (t->d_rows || t->d_blob)) {
+        (void)hipSetDevice(t->h->device);
+        (void)hipStreamSynchronize(t->h->stream);
+        if (t->d_rows) (void)hipFree(t->d_rows);
+        if (t->d_blob) (void)hipFree(t->d_blob);
+    }
+    delete t;
+}
+
+int nfagg_netev_resolve_device(nfagg_handle* h, const nfagg_netev_table* table, const uint8_t* d_present,
+                               const nfagg_network_events_metrics* d_network_events, const nfagg_pkt_drop_metrics* d_drops, size_t n,
+                               uint8_t* d_present_out, nfagg_pkt_drop_metrics* d_drops_out, uint16_t* d_rows_out,
+                               uint64_t* d_missing_set, size_t missing_cap, size_t* n_missing, int* zero_missing, int* overflow) {
+    if (!h || !table || !n_missing || !zero_missing || !overflow || (missing_cap && !d_missing_set) ||
+        (n && (!d_present || !d_present_out || !d_drops_out || !d_rows_out)))
+        return fail(h, NFAGG_EINVAL, "null argument");
+    if (table->h != h || !table->d_rows) return fail(h, NFAGG_EINVAL, "the network-events table was not created for this handle");
+    if ((((uintptr_t)d_network_events | (uintptr_t)d_drops | (uintptr_t)d_drops_out | (uintptr_t)d_rows_out | (uintptr_t)d_missing_set) & 7u) != 0)
+        return fail(h, NFAGG_EINVAL, "device arrays must be 8-byte aligned");
+    if (missing_cap > 0xffffffffull) return fail(h, NFAGG_EINVAL, "missing_cap too large");
+    *n_missing = 0; *zero_missing = 0; *overflow = 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = ensure_buf(h, h->enc.ne_info, 16);
+    if (rc != NFAGG_OK) return rc;
+    HIP_TRY(h, hipMemsetAsync(h->enc.ne_info.p, 0, 16, h->stream));
+    if (missing_cap) HIP_TRY(h, hipMemsetAsync(d_missing_set, 0, missing_cap * sizeof(uint64_t), h->stream));
+    if (n) {
+        hipError_t e = launch_netev_resolve(d_present, (const uint8_t*)d_network_events, (const uint8_t*)d_drops, n, (const NetevRow*)table->d_rows,
+                                            (uint32_t)table->rows.size(), d_present_out, (uint8_t*)d_drops_out, d_rows_out, d_missing_set,
+                                            (uint32_t)missing_cap, (uint32_t*)h->enc.ne_info.p, h->stream);
+        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "network-events resolve launch failed: %s", hipGetErrorString(e));
+    }
+    uint32_t info[4] = {};
+    HIP_TRY(h, hipMemcpyAsync(info, h->enc.ne_info.p, sizeof info, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *n_missing = info[0]; *overflow = info[1] ? 1 : 0; *zero_missing = info[2] ? 1 : 0;
+    return NFAGG_OK;
+}
+
+int nfagg_netev_resolve(nfagg_handle* h, const nfagg_netev_table* table, const uint8_t* present,
+                        const nfagg_network_events_metrics* network_events, const nfagg_pkt_drop_metrics* drops, size_t n,
+                        uint8_t* present_out, nfagg_pkt_drop_metrics* drops_out, uint16_t* rows_out,
+                        uint8_t (*missing)[8], size_t missing_cap, size_t* n_missing, int* overflow) {
+    if (!h || !table || !n_missing || !overflow || (missing_cap && !missing) || (n && (!present || !present_out || !drops_out || !rows_out)))
+        return fail(h, NFAGG_EINVAL, "null argument");
+    auto& S = h->enc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const void* src[3] = {present, network_events, drops};
+    const size_t elem[3] = {1, sizeof(nfagg_network_events_metrics), sizeof(nfagg_pkt_drop_metrics)}, out_elem[3] = {1, sizeof(nfagg_pkt_drop_metrics), 8};
+    int rc;
+    for (int k = 0; k < 3; k++) {
+        if ((rc = ensure_buf(h, S.ne_out[k], n * out_elem[k] + 16)) != NFAGG_OK) return rc;
+        if (!src[k] || !n) continue;
+        if ((rc = ensure_buf(h, S.ne_in[k], n * elem[k] + 16)) != NFAGG_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(S.ne_in[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
+    }
+    if ((rc = ensure_buf(h, S.ne_missing, missing_cap * sizeof(uint64_t) + 16)) != NFAGG_OK) return rc;
+    size_t stored = 0; int zero = 0;
+    rc = nfagg_netev_resolve_device(h, table, (const uint8_t*)S.ne_in[0].p, network_events ? (const nfagg_network_events_metrics*)S.ne_in[1].p : nullptr,
+                                    drops ? (const nfagg_pkt_drop_metrics*)S.ne_in[2].p : nullptr, n, (uint8_t*)S.ne_out[0].p,
+                                    (nfagg_pkt_drop_metrics*)S.ne_out[1].p, (uint16_t*)S.ne_out[2].p, missing_cap ? (uint64_t*)S.ne_missing.p : nullptr,
+                                    missing_cap, &stored, &zero, overflow);
+    if (rc != NFAGG_OK) return rc;
+    void* dst[3] = {present_out, drops_out, rows_out};
+    for (int k = 0; k < 3; k++)
+        if (n) HIP_TRY(h, hipMemcpyAsync(dst[k], S.ne_out[k].p, n * out_elem[k], hipMemcpyDeviceToHost, h->stream));
+    std::vector<uint64_t> set(missing_cap);
+    if (missing_cap) HIP_TRY(h, hipMemcpyAsync(set.data(), S.ne_missing.p, missing_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    size_t m = 0;
+    for (uint64_t v : set) if (v) memcpy(missing[m++], &v, 8);
+    if (zero) { if (m < missing_cap) memset(missing[m++], 0, 8); else *overflow = 1; }    // the all-zero cookie takes a place of the list like any other
+    *n_missing = m;
+    return NFAGG_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 #ifdef NFAGG_DIAG
 // libnfagg_diag.so only: what the last epochs-found-first launch of nfagg_account saw — its control words and its cuts (host copies)

@@ -114,6 +114,26 @@ template <int N> NF_DEV void load_dwords8(const uint8_t* p, uint32_t (&w)[N]) { 
     for (int k = 0; k < N / 2; k++) { const uint2 v = q[k]; w[2 * k] = v.x; w[2 * k + 1] = v.y; }
 }
 
+// ---- network events (nfagg_netev.h): the rendered object / message of table row r, copied through a sink. The blob's
+// pieces start at 16-byte aligned offsets; a counting sink reads nothing.
+NF_DEV void put_blob(CountSink& s, const uint8_t*, uint32_t len) { s.n += len; }
+template <typename S> NF_DEV void put_blob(S& s, const uint8_t* p, uint32_t len) {
+    for (uint32_t c = 0; c < len; c += 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p + c);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            if (c + k < len) s.put((uint8_t)(w[k >> 2] >> (8 * (k & 3))));
+    }
+}
+// The four rows of flow i (0xFFFF: none; a row beyond the table counts as none) and the second half of a table row:
+// x = json_off, y = pb_off, z = json_len | pb_len << 16.
+NF_DEV void netev_rows(const uint16_t* ne_rows, uint64_t i, uint32_t (&ev)[4]) {
+    const uint2 v = reinterpret_cast<const uint2*>(ne_rows)[i];
+    ev[0] = v.x & 0xffffu; ev[1] = v.x >> 16; ev[2] = v.y & 0xffffu; ev[3] = v.y >> 16;
+}
+NF_DEV uint4 netev_row_blobs(const uint8_t* ne_tab, uint32_t r) { return reinterpret_cast<const uint4*>(ne_tab)[2 * r + 1]; }
+
 // ---- the two-pass skeleton. Every size kernel runs kScanBlock records per workgroup and scans their lengths inside it
 // (block_scan); the block sums go through launch_scan_block_sums (nfagg_internal.h, nfagg_encode.hip). Every write kernel
 // runs one wave per 64 records: it builds the wave's bytes in LDS (WaveImage) and copies them out (copy_image_out).

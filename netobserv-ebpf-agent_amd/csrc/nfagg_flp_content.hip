@@ -9,7 +9,10 @@
 //   after Proto:         [QuicSeenLongHdr QuicSeenShortHdr QuicVersion]
 //   after TimeFlowEndMs: [TimeFlowRttNs]
 //   after Udns:          [XlatDstAddr [XlatDstPort] XlatSrcAddr [XlatSrcPort]] [ZoneId]
-// Network events are encoded as NewRecord does with a nil decoder (record.go:126): no key, no drop injected.
+//   after Interfaces:    [NetworkEvents]      (decode_protobuf.go:184-186; the *_netev entry points only)
+// Without a cookie table network events are encoded as NewRecord does with a nil decoder (record.go:126): no key, no drop
+// injected. With one (FlpContentNetev) the line carries the rendered objects of the rows nfagg_netev_resolve found; the
+// drop it injected arrives in the drops part like any other.
 //
 // Same two passes, same window scheme and the same encode_line as nfagg_flp.hip, with FlpContent as its feature policy;
 // the kernels are separate so that the Accounter path keeps its code and its registers. A lane reads the parts its
@@ -17,6 +20,7 @@
 // and the DNS name in a 32-byte LDS slot of its own. The names of response codes, TCP states and drop causes sit in one
 // constant blob with an offset and a length per name; the counting pass reads only the lengths.
 #include "nfagg_flp_line.h"
+#include "nfagg_netev.h"
 
 namespace nfagg {
 
@@ -154,9 +158,17 @@ constexpr uint32_t kFlpcWindow = 25600;                       // line starts a w
 constexpr uint32_t kFlpcLds = kFlpcWindow + (kFlpcMaxLine + 15) / 16 * 16;
 static_assert(kFlpcLds + kFlpcNameLds <= 32768, "four waves per compute unit");
 
+// With network events the longest line grows by the key, four rendered objects at their cap, the commas between them
+// and the closing bracket; the window shrinks by as much, so that the wave's LDS stays at 32 KiB.
+constexpr uint32_t kFlpnMaxLine = kFlpcMaxLine + (sizeof(",\"NetworkEvents\":[") - 1) + 4 * kNetevMaxRendered + 3 + 1;
+constexpr uint32_t kFlpnWindow = (32768 - kFlpcNameLds - (kFlpnMaxLine + 15) / 16 * 16) / 16 * 16;
+constexpr uint32_t kFlpnLds = kFlpnWindow + (kFlpnMaxLine + 15) / 16 * 16;
+static_assert(kFlpnLds + kFlpcNameLds <= 32768 && kFlpnWindow >= 16384, "four waves per compute unit, and a window worth its copy-out");
+
 // The feature parts of one flow, as encode_line's feature policy. load() reads the parts that are present (array given
 // and the flow's present byte has the bit) and nothing of the others.
 struct FlpContent {
+    static constexpr uint32_t kWindow = kFlpcWindow, kLds = kFlpcLds;
     uint32_t have = 0;          // NFAGG_FEAT_* bits of the parts that were loaded
     uint32_t add[4] = {};       // additional_metrics @16: flow_rtt (2), ipsec_encrypted_ret, eth | ipsec_encrypted << 16
     uint32_t dnsw[4] = {};      // dns_metrics @16: latency (2), id | flags << 16, eth | errno << 16 | name[0] << 24
@@ -226,6 +238,7 @@ struct FlpContent {
         if (ret != 0) { lit(s, ",\"IPSecRetCode\":"); dec_i64(s, ret); lit(s, ",\"IPSecStatus\":\"error\""); }
         else if ((add[3] >> 16) & 0xffu) lit(s, ",\"IPSecRetCode\":0,\"IPSecStatus\":\"success\"");
     }
+    template <typename S> NF_DEV void netev(S&) const {}                // record.go:126 with a nil decoder; FlpContentNetev has the key
     template <typename S> NF_DEV void drops(S& s) const {               // decode_protobuf.go:145-153
         if (!(have & NFAGG_FEAT_DROPS) || drp[1] == 0) return;
         lit(s, ",\"PktDropBytes\":"); dec<5>(s, drp[0] & 0xffffu);
@@ -263,7 +276,36 @@ struct FlpContent {
     }
 };
 
-// ---- kernel 1: as k_flp_size, the line measured with the flow's feature parts
+// FlpContent plus the flow's network events: the table rows nfagg_netev_resolve wrote (PbFeat::ne_rows), each row's JSON
+// object rendered once on the host (nfagg_netev.h). The counting pass reads only the lengths.
+struct FlpContentNetev : FlpContent {
+    static constexpr uint32_t kWindow = kFlpnWindow, kLds = kFlpnLds;
+    uint32_t ev[4] = {kNetevNoRow, kNetevNoRow, kNetevNoRow, kNetevNoRow};
+    const uint8_t* ne_tab = nullptr;
+    const uint8_t* ne_blob = nullptr;
+    uint32_t ne_n = 0;
+
+    NF_DEV void load(const PbFeat& F, uint64_t i, uint8_t* name_lds) {
+        FlpContent::load(F, i, name_lds);
+        netev_rows(F.ne_rows, i, ev);
+        ne_tab = F.ne_tab; ne_blob = F.ne_blob; ne_n = F.ne_n;
+    }
+    template <typename S> NF_DEV void netev(S& s) const {               // decode_protobuf.go:184-186: no event, no key
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (ev[k] < ne_n) {
+                if (any) s.put(','); else lit(s, ",\"NetworkEvents\":[");
+                any = true;
+                const uint4 m = netev_row_blobs(ne_tab, ev[k]);
+                put_blob(s, ne_blob + m.x, m.z & 0xffffu);
+            }
+        if (any) s.put(']');
+    }
+};
+
+// ---- kernel 1: as k_flp_size, the line measured with the flow's feature parts (Feat: FlpContent or FlpContentNetev)
+template <typename Feat>
 __global__ __launch_bounds__(kScanBlock) void k_flpc_size(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F,
                                                           uint32_t* __restrict__ rows, uint32_t* __restrict__ local_off,
                                                           uint32_t* __restrict__ block_sum, uint32_t* __restrict__ n_deferred) {
@@ -281,7 +323,7 @@ __global__ __launch_bounds__(kScanBlock) void k_flpc_size(const void* __restrict
         flp_rows(tab, P.n_names, r, row);
         deferred = flp_deferred(r);
         if (!deferred) {
-            FlpContent f;
+            Feat f;
             f.load(F, i, name_lds[threadIdx.x]);
             CountSink c;
             encode_line(c, r, P, row, f);
@@ -297,19 +339,20 @@ __global__ __launch_bounds__(kScanBlock) void k_flpc_size(const void* __restrict
     block_scan(len, i, n, wave_tot, local_off, block_sum);
 }
 
-// ---- kernel 3: as k_flp_write, windows of kFlpcWindow bytes (the DNS name slots take 2 KiB of the 32 KiB)
+// ---- kernel 3: as k_flp_write, windows of Feat::kWindow bytes (the DNS name slots take 2 KiB of the 32 KiB)
+template <typename Feat>
 __global__ __launch_bounds__(64) void k_flpc_write(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F,
                                                    const uint32_t* __restrict__ rows, const uint32_t* __restrict__ local_off,
                                                    const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
                                                    uint64_t* __restrict__ line_offsets, uint8_t* __restrict__ deferred) {
-    __shared__ __align__(16) uint8_t lds[kFlpcLds];
+    __shared__ __align__(16) uint8_t lds[Feat::kLds];
     __shared__ __align__(16) uint8_t name_lds[64][32];
     const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
     WaveImage w(block_base, local_off, i0);
     uint64_t my_off = 0; uint32_t my_len = 0;
     uint32_t row[7] = {};
     Rec r;
-    FlpContent f;
+    Feat f;
     if (i < n) {
         load_record(recs, i, r);
         const uint4* q = reinterpret_cast<const uint4*>(rows + i * 8);
@@ -327,9 +370,9 @@ __global__ __launch_bounds__(64) void k_flpc_write(const void* __restrict__ recs
     uint32_t lo = w.shift;
     while (lo < w.span) {
         const uint32_t base = lo & ~15u;
-        const bool mine = my_len && p0 >= lo && p0 - base < kFlpcWindow;
+        const bool mine = my_len && p0 >= lo && p0 - base < Feat::kWindow;
         if (mine) { FlpLds s{lds + (p0 - base)}; encode_line(s, r, P, row, f); }
-        uint32_t hi = mine ? p0 + my_len : lo;                  // the window's end: at most base + kFlpcWindow + kFlpcMaxLine
+        uint32_t hi = mine ? p0 + my_len : lo;                  // the window's end: at most base + the window + the longest line
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(hi, d, 64); hi = o > hi ? o : hi; }
         __syncthreads();
@@ -343,7 +386,8 @@ hipError_t launch_flpc_size(const void* d_recs, uint64_t n, const FlpParams& P, 
                             uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s) {
     const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_flpc_size, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_sum, d_n_deferred);
+    if (F.ne_rows) hipLaunchKernelGGL(k_flpc_size<FlpContentNetev>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_sum, d_n_deferred);
+    else hipLaunchKernelGGL(k_flpc_size<FlpContent>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_sum, d_n_deferred);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
@@ -353,8 +397,11 @@ hipError_t launch_flpc_write(const void* d_recs, uint64_t n, const FlpParams& P,
                              const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
                              uint8_t* d_deferred, hipStream_t s) {
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_flpc_write, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_base,
-                       (uint8_t*)d_out, d_line_offsets, d_deferred);
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (F.ne_rows) hipLaunchKernelGGL(k_flpc_write<FlpContentNetev>, grid, dim3(64), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_base,
+                                      (uint8_t*)d_out, d_line_offsets, d_deferred);
+    else hipLaunchKernelGGL(k_flpc_write<FlpContent>, grid, dim3(64), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_base,
+                            (uint8_t*)d_out, d_line_offsets, d_deferred);
     return hipGetLastError();
 }
 

@@ -157,13 +157,14 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
     return k == 0 ? r.d[24] & 0xffu : k <= 4 ? (r.d[25] >> (8 * (k - 1))) & 0xffu : (r.d[26] >> (8 * (k - 5))) & 0xffu;
 }
 
-// The keys of a flow's feature parts (DNS, drops, xlat, RTT / IPsec, QUIC) fall in seven contiguous groups of the sorted
-// line; encode_line calls one hook of its feature policy at each. NoFeat: a record that carries only BpfFlowMetrics,
+// The keys of a flow's feature parts (DNS, drops, xlat, RTT / IPsec, QUIC, network events) fall in eight contiguous groups of
+// the sorted line; encode_line calls one hook of its feature policy at each. NoFeat: a record that carries only BpfFlowMetrics,
 // every hook is empty and the line is the one of decode_protobuf.go:57-127. FlpContent (nfagg_flp_content.hip) holds
-// the parts of a full BpfFlowContent.
+// the parts of a full BpfFlowContent, FlpContentNetev adds the flow's resolved network events.
 struct NoFeat {
     template <typename S> NF_DEV void dns(S&) const {}        // Dns*          after Bytes
     template <typename S> NF_DEV void ipsec(S&) const {}      // IPSec*        after Flags
+    template <typename S> NF_DEV void netev(S&) const {}      // NetworkEvents after Interfaces
     template <typename S> NF_DEV void drops(S&) const {}      // PktDrop*      after Packets
     template <typename S> NF_DEV void quic(S&) const {}       // Quic*         after Proto
     template <typename S> NF_DEV void rtt(S&) const {}        // TimeFlowRttNs after TimeFlowEndMs
@@ -213,6 +214,7 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
             esc_str(s, e + kFlpEscNameOff, lens[k] & 0xffffu);
         }
     s.put(']');
+    f.netev(s);
     if (r.packets()) { lit(s, ",\"Packets\":"); dec<10>(s, r.packets()); }
     f.drops(s);
     if (ip) { lit(s, ",\"Proto\":"); dec<3>(s, proto); }

@@ -27,6 +27,12 @@ struct PbFeat {
     const uint8_t* drops = nullptr;        // nfagg_pkt_drop_metrics[n]     32 B
     const uint8_t* xlat = nullptr;         // nfagg_xlat_metrics[n]         56 B
     const uint8_t* quic = nullptr;         // nfagg_quic_metrics[n]         24 B
+    // network events (the *_netev entry points only; ne_rows == nullptr: the kernels without the hook run): four table rows
+    // per flow as nfagg_netev_resolve writes them, and the table (nfagg_netev.h: 32-byte rows, the rendered blob)
+    const uint16_t* ne_rows = nullptr;
+    const uint8_t* ne_tab = nullptr;
+    const uint8_t* ne_blob = nullptr;
+    uint32_t ne_n = 0;
 };
 
 hipError_t launch_pb_size(const void* d_recs, uint64_t n, const PbParams& P, const PbFeat& F, uint32_t* d_body_len, uint32_t* d_local_off,

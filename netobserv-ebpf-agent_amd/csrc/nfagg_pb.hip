@@ -15,6 +15,9 @@
 // With a PbFeat the same kernels encode the MapTracer branch (pkg/flow/tracer_map.go:103-146): the
 // full model.BpfFlowContent — DNS, packet drops, xlat, RTT/IPsec, QUIC (proto.go:79-118,129-138;
 // record.go:116-125) — with a nil SampleDecoder (record.go:126): network events are not decoded.
+// The NE instantiations (PbFeat::ne_rows given, the *_netev entry points) add field 27, network_events_metadata
+// (proto.go:140-147): the rendered NetworkEvent of each table row nfagg_netev_resolve found for the flow. The
+// kernels without the hook are separate instantiations and keep their code and their registers.
 //
 // Byte-granular, HBM-bound streaming work: 144 B read + ~110 B written per record (more with
 // features). The two-pass skeleton of nfagg_encode.h; its own: a wave's image is encoded one fixed
@@ -91,7 +94,7 @@ template <typename S> NF_DEV void put_duration(S& s, uint32_t field, uint64_t d_
 // The body of pbflow.Record for one flow: evicted record `r`, plus the feature parts of flow `i` when F carries
 // them — each part is read whole with vector loads before anything is emitted. `name_lds`: 32 bytes of LDS owned by
 // this lane (the DNS name is walked byte by byte). Same code sizes (CountSink) and writes (WindowSink).
-template <typename S> NF_DEV void encode_record(S& s, const Rec& r, const PbParams& P, const PbFeat& F, uint64_t i, uint8_t* name_lds, const uint8_t* tab) {
+template <bool NE, typename S> NF_DEV void encode_record(S& s, const Rec& r, const PbParams& P, const PbFeat& F, uint64_t i, uint8_t* name_lds, const uint8_t* tab) {
     const uint32_t have = F.present ? F.present[i] : 0u;
     const bool add = F.additional && (have & 1u), dns = F.dns && (have & 2u), drp = F.drops && (have & 4u);
     const bool xlt = F.xlat && (have & 16u), quc = F.quic && (have & 32u);
@@ -159,6 +162,17 @@ template <typename S> NF_DEV void encode_record(S& s, const Rec& r, const PbPara
             put_dup(s, P, tab, oi, lmac, od);
         }
     }
+    if constexpr (NE) {                          // network_events_metadata = 27 (proto.go:140-147), tag bytes 0xDA 0x01
+        uint32_t ev[4];
+        netev_rows(F.ne_rows, i, ev);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (ev[k] < F.ne_n) {
+                const uint4 m = netev_row_blobs(F.ne_tab, ev[k]);
+                put_tag(s, 27, 2); put_varint(s, m.z >> 16);
+                put_blob(s, F.ne_blob + m.y, m.z >> 16);
+            }
+    }
     if (xlt) {                                   // proto.go:99-105,129-138: address family by the FLOW's eth_protocol
         const bool v6 = eth == 0x86DDu;
         const uint32_t sd = xltw[12], ze = xltw[13];
@@ -192,6 +206,7 @@ template <typename S> NF_DEV void encode_record(S& s, const Rec& r, const PbPara
 }
 
 // ---- kernel 1: body length per record, frame length, block-local exclusive scan of the frame lengths
+template <bool NE>
 __global__ __launch_bounds__(kScanBlock) void k_pb_size(const void* __restrict__ recs, uint64_t n, PbParams P, PbFeat F,
                                                         uint32_t* __restrict__ body_len, uint32_t* __restrict__ local_off,
                                                         uint32_t* __restrict__ block_sum) {
@@ -206,7 +221,7 @@ __global__ __launch_bounds__(kScanBlock) void k_pb_size(const void* __restrict__
         load_record(recs, i, r);
         r.canonicalize();
         CountSink c;
-        encode_record(c, r, P, F, i, name_lds[threadIdx.x], tab);
+        encode_record<NE>(c, r, P, F, i, name_lds[threadIdx.x], tab);
         body_len[i] = c.n;
         frame = 1 + varint_len(c.n) + c.n;
     }
@@ -217,9 +232,10 @@ __global__ __launch_bounds__(kScanBlock) void k_pb_size(const void* __restrict__
 // The window (LDS per wave, beside 2 KiB of DNS-name slots and the 8.6 KiB namer table) is chosen by the host from the
 // average frame length the size pass found: the whole encoder runs once per window a wave's 64 frames span, so the
 // window should hold them all (64 x ~110 B for Accounter records, 64 x ~270 B with every feature part).
-// (a frame is at most 1033 bytes, DESIGN.md §4.7a: any window of at least that size makes progress)
+// (a frame is at most 1033 bytes, DESIGN.md §4.7a, 3097 with four network events at their cap; the window sink takes a
+// frame of any length: a frame that straddles windows is encoded once per window)
 
-template <uint32_t kPbWindow>
+template <uint32_t kPbWindow, bool NE = false>
 __global__ __launch_bounds__(64) void k_pb_write(const void* __restrict__ recs, uint64_t n, PbParams P, PbFeat F,
                                                  const uint32_t* __restrict__ body_len, const uint32_t* __restrict__ local_off,
                                                  const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
@@ -260,7 +276,7 @@ __global__ __launch_bounds__(64) void k_pb_write(const void* __restrict__ recs, 
             WindowSink s{lds, p0, lo, hi - lo};
             s.put(0x0A);                                          // Records.entries = 1, length-delimited
             put_varint(s, bl);
-            encode_record(s, r, P, F, i, name_lds[threadIdx.x], tab);
+            encode_record<NE>(s, r, P, F, i, name_lds[threadIdx.x], tab);
         }
         __syncthreads();
         copy_image_out(w.dst, lds, lo, w.shift, hi);              // from max(lo, shift): lo is 0 or beyond any shift
@@ -272,23 +288,25 @@ hipError_t launch_pb_size(const void* d_recs, uint64_t n, const PbParams& P, con
                           uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s) {
     const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_pb_size, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_body_len, d_local_off, d_block_sum);
+    if (F.ne_rows) hipLaunchKernelGGL(k_pb_size<true>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_body_len, d_local_off, d_block_sum);
+    else hipLaunchKernelGGL(k_pb_size<false>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_body_len, d_local_off, d_block_sum);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
 }
 
+// One window rule for both sets of instantiations; F.ne_rows picks the set that carries the network-events hook.
 hipError_t launch_pb_write(const void* d_recs, uint64_t n, const PbParams& P, const PbFeat& F, const uint32_t* d_body_len, const uint32_t* d_local_off,
                            const uint64_t* d_block_base, void* d_out, uint64_t* d_frame_offsets, void* d_kafka_keys, uint64_t total_bytes, hipStream_t s) {
     const uint64_t avg = n ? total_bytes / n : 0;
     const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    const bool ne = F.ne_rows != nullptr;
+    void (*kernel)(const void*, uint64_t, PbParams, PbFeat, const uint32_t*, const uint32_t*, const uint64_t*, uint8_t*, uint64_t*, uint8_t*);
+    if (avg <= 120) kernel = ne ? k_pb_write<8192, true> : k_pb_write<8192>;
+    else if (avg <= 248) kernel = ne ? k_pb_write<16384, true> : k_pb_write<16384>;
+    else kernel = ne ? k_pb_write<24576, true> : k_pb_write<24576>;
     (void)hipGetLastError();
-    if (avg <= 120)
-        hipLaunchKernelGGL(k_pb_write<8192>, grid, block, 0, s, d_recs, n, P, F, d_body_len, d_local_off, d_block_base, (uint8_t*)d_out, d_frame_offsets, (uint8_t*)d_kafka_keys);
-    else if (avg <= 248)
-        hipLaunchKernelGGL(k_pb_write<16384>, grid, block, 0, s, d_recs, n, P, F, d_body_len, d_local_off, d_block_base, (uint8_t*)d_out, d_frame_offsets, (uint8_t*)d_kafka_keys);
-    else
-        hipLaunchKernelGGL(k_pb_write<24576>, grid, block, 0, s, d_recs, n, P, F, d_body_len, d_local_off, d_block_base, (uint8_t*)d_out, d_frame_offsets, (uint8_t*)d_kafka_keys);
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, d_recs, n, P, F, d_body_len, d_local_off, d_block_base, (uint8_t*)d_out, d_frame_offsets, (uint8_t*)d_kafka_keys);
     return hipGetLastError();
 }
 

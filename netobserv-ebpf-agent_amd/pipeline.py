@@ -185,11 +185,53 @@ class MapTracer:
     invoke evictFlows directly (what Flush() ends up doing)."""
 
     def __init__(self, fetcher, eviction_timeout, stale_entries_evict_timeout, metrics=None, s=None, udn_enabled=False,
-                 clock=None, mono_clock=None):
+                 clock=None, mono_clock=None, sample_decoder: Callable = None):
         self.mapFetcher, self.evictionTimeout, self.staleEntriesEvictTimeout = fetcher, eviction_timeout, stale_entries_evict_timeout
         self.metrics, self.s, self.udnEnabled = metrics, s, udn_enabled
         self.clock = clock or (lambda: time.time_ns())
         self.monoClock = mono_clock or (lambda: time.monotonic_ns())
+        # model.SampleDecoder as a callable: cookie (8 bytes) -> an ACL as (action, actor, name, namespace, direction, String()),
+        # any other event as its String(), or None / a raised exception when DecodeCookie8Bytes fails. Its answers are kept
+        # for the tracer's lifetime, and with them the device table they were rendered into: the decoder is asked once per cookie.
+        self.sampleDecoder = sample_decoder
+        self.decoderCalls = 0
+        self._netevAnswers, self._netevTable = {}, None
+
+    def resolveNetworkEvents(self, present, parts, missing_cap: int = 4096):
+        """record.go:126-157 for merged flows (map_merge's present / parts) on the GPU: resolve, ask the decoder about the
+        cookies the table does not know, rebuild the table, resolve again until nothing is missing. Returns (present_out,
+        parts with the decorated drops, rows, table) for encode_flp_json_netev / encode_pb_netev."""
+        table = self.mapFetcher.table
+        while True:
+            if self._netevTable is None:
+                self._netevTable = table.netev_table(self._netevAnswers.items())
+            p_out, d_out, rows, missing, _ = table.netev_resolve(self._netevTable, present, parts.get("network_events"),
+                                                                 parts.get("drops"), missing_cap)
+            if not missing:
+                return p_out, {**parts, "drops": d_out}, rows, self._netevTable
+            for cookie in missing:
+                self.decoderCalls += 1
+                try:
+                    self._netevAnswers[cookie] = self.sampleDecoder(cookie)
+                except Exception as e:                                  # err != nil: the cookie's events are skipped
+                    self._netevAnswers[cookie] = e
+            self._netevTable.close()
+            self._netevTable = None
+
+    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown"):
+        """evictFlows for a direct-FLP `write: stdout, format: json` stage, without a Record per flow: the drained maps are merged,
+        decorated with the sample decoder's network events and encoded on the GPU. Returns (buf, line_offsets, deferred) as
+        FlowTable.encode_flp_json_content does."""
+        monotonic_now, current = self.monoClock(), self.clock()
+        table = self.mapFetcher.table
+        main_ids, main_vals, feats, n_cpu = self.mapFetcher.drain()
+        recs, present, parts, _dups = table.map_merge(main_ids, main_vals, feats, n_cpu)
+        names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
+        mono = monotonic_now & ((1 << 64) - 1)
+        if self.sampleDecoder is None:                                  # s == nil: no events, no injected drops (record.go:126)
+            return table.encode_flp_json_content(recs, present, parts, current, mono, names, agent_ip, time_received, unknown)
+        p_out, parts, rows, tab = self.resolveNetworkEvents(present, parts)
+        return table.encode_flp_json_netev(recs, p_out, parts, rows, tab, current, mono, names, agent_ip, time_received, unknown)
 
     def evictFlows(self, forwardFlows: "queue.Queue"):                  # :103-146
         monotonic_now, current = self.monoClock(), self.clock()

@@ -499,6 +499,101 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, need.value, n_def.value
 
+    # -- network events (nfagg_netev_*): the decoder's answers as a table, the per-flow work on the GPU
+    def netev_table(self, entries) -> "NetevTable":
+        """A cookie table on this handle's device; entries: [(cookie8, event)], see NetevTable."""
+        return NetevTable(entries, self)
+
+    def netev_resolve(self, table: "NetevTable", present, network_events, drops=None, missing_cap: int = 1024):
+        """record.go:126-157 for every flow (nfagg_netev_resolve): present / network_events / drops as map_merge returns them
+        (drops=None: no flow has a drops part). Returns (present_out, drops_out, rows uint16[n, 4], missing cookies (list of
+        8-byte strings, distinct, order unspecified), overflow)."""
+        p = np.ascontiguousarray(present, dtype=np.uint8)
+        n = p.size
+        ne = np.ascontiguousarray(network_events, dtype=ROLLUP_KINDS["network_events"]) if network_events is not None else None
+        dr = np.ascontiguousarray(drops, dtype=ROLLUP_KINDS["drops"]) if drops is not None else None
+        assert (ne is None or len(ne) == n) and (dr is None or len(dr) == n)
+        p_out = np.zeros(n, dtype=np.uint8)
+        d_out = np.zeros(n, dtype=ROLLUP_KINDS["drops"])
+        rows = np.zeros((n, 4), dtype=np.uint16)
+        miss = np.zeros((max(missing_cap, 1), 8), dtype=np.uint8)
+        n_miss, over = C.c_size_t(0), C.c_int(0)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        self._check(L.lib.nfagg_netev_resolve(self._h, table._t, ptr(p), ptr(ne), ptr(dr), n, ptr(p_out), ptr(d_out), ptr(rows),
+                                              miss.ctypes.data_as(C.c_void_p), missing_cap, C.byref(n_miss), C.byref(over)))
+        return p_out, d_out, rows, [miss[k].tobytes() for k in range(n_miss.value)], bool(over.value)
+
+    def netev_resolve_device(self, table: "NetevTable", d_present: int, d_network_events: int, d_drops: int, n: int, d_present_out: int,
+                             d_drops_out: int, d_rows_out: int, d_missing_set: int = 0, missing_cap: int = 0):
+        """Device-resident variant (raw device pointers; outputs may alias the inputs). Returns (distinct missing cookies
+        recorded, the all-zero cookie was missing, overflow); d_missing_set holds the non-zero ones, 0 = empty slot."""
+        n_miss, zero, over = C.c_size_t(0), C.c_int(0), C.c_int(0)
+        self._check(L.lib.nfagg_netev_resolve_device(
+            self._h, table._t, C.c_void_p(d_present or None), C.c_void_p(d_network_events or None), C.c_void_p(d_drops or None), n,
+            C.c_void_p(d_present_out or None), C.c_void_p(d_drops_out or None), C.c_void_p(d_rows_out or None),
+            C.c_void_p(d_missing_set or None), missing_cap, C.byref(n_miss), C.byref(zero), C.byref(over)))
+        return n_miss.value, bool(zero.value), bool(over.value)
+
+    def encode_pb_netev(self, records: np.ndarray, present, parts, rows, table: "NetevTable", now_unix_ns: int, mono_now_ns: int,
+                        agent_ip16: bytes, names: np.ndarray, unknown: bytes = b"unknown"):
+        """encode_pb with present/parts plus the flows' network events (nfagg_encode_pb_content_netev): present and
+        parts["drops"] are netev_resolve's outputs, rows its rows. Returns (buf, frame_offsets, body_len)."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        o, keep = self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown)
+        feat, keep_f = self._pb_features(n, present, {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS})
+        rw = np.ascontiguousarray(rows, dtype=np.uint16).reshape(n, 4)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        blen = np.zeros(max(n, 1), dtype=np.uint32)
+        buf = self._encode_grown(n, 256, lambda p, cap, need: L.lib.nfagg_encode_pb_content_netev(
+            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat), rw.ctypes.data_as(C.c_void_p), table._t, C.byref(o), p, cap,
+            off.ctypes.data_as(C.c_void_p), blen.ctypes.data_as(C.c_void_p), None, need))
+        return buf, off, blen[:n]
+
+    def encode_pb_netev_device(self, d_records: int, n: int, d_present: int, d_parts, d_rows: int, table: "NetevTable", now_unix_ns: int,
+                               mono_now_ns: int, agent_ip16: bytes, names: np.ndarray, d_out: int, out_cap: int, d_frame_offsets: int,
+                               d_body_len: int, unknown: bytes = b"unknown"):
+        """Device-resident variant (raw device pointers). Returns (rc, bytes needed/written)."""
+        o, keep = self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown)
+        feat, _ = self._pb_features(n, d_present, {k: v for k, v in (d_parts or {}).items() if k in _CONTENT_PARTS}, device=True)
+        need = C.c_size_t(0)
+        rc = L.lib.nfagg_encode_pb_content_netev_device(
+            self._h, C.c_void_p(d_records), n, C.byref(feat), C.c_void_p(d_rows or None), table._t, C.byref(o), C.c_void_p(d_out or None),
+            out_cap, C.c_void_p(d_frame_offsets), C.c_void_p(d_body_len), None, C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value
+
+    def encode_flp_json_netev(self, records: np.ndarray, present, parts, rows, table: "NetevTable", now_unix_ns: int, mono_now_ns: int,
+                              names: np.ndarray, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown"):
+        """encode_flp_json_content plus the flows' network events (nfagg_encode_flp_json_content_netev); inputs as
+        encode_pb_netev. Returns (buf, line_offsets, deferred)."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
+        feat, keep_f = self._pb_features(n, present, {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS})
+        rw = np.ascontiguousarray(rows, dtype=np.uint16).reshape(n, 4)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        deferred = np.zeros(n, dtype=np.uint8)
+        n_def = C.c_size_t(0)
+        buf = self._encode_grown(n, 640, lambda p, cap, need: L.lib.nfagg_encode_flp_json_content_netev(
+            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat), rw.ctypes.data_as(C.c_void_p), table._t, C.byref(o), p, cap,
+            off.ctypes.data_as(C.c_void_p), deferred.ctypes.data_as(C.c_void_p), C.byref(n_def), need))
+        assert int(deferred.sum()) == n_def.value
+        return buf, off, deferred
+
+    def encode_flp_json_netev_device(self, d_records: int, n: int, d_present: int, d_parts, d_rows: int, table: "NetevTable",
+                                     now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip, time_received: int, d_out: int,
+                                     out_cap: int, d_line_offsets: int, d_deferred: int = 0, unknown: bytes = b"unknown"):
+        """Device-resident variant (raw device pointers). Returns (rc, bytes needed/written, deferred records)."""
+        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
+        feat, _ = self._pb_features(n, d_present, {k: v for k, v in (d_parts or {}).items() if k in _CONTENT_PARTS}, device=True)
+        need, n_def = C.c_size_t(0), C.c_size_t(0)
+        rc = L.lib.nfagg_encode_flp_json_content_netev_device(
+            self._h, C.c_void_p(d_records), n, C.byref(feat), C.c_void_p(d_rows or None), table._t, C.byref(o), C.c_void_p(d_out or None),
+            out_cap, C.c_void_p(d_line_offsets), C.c_void_p(d_deferred or None), C.byref(n_def), C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value, n_def.value
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -663,6 +758,79 @@ IPFIX_TEMPLATE_ID_V4, IPFIX_TEMPLATE_ID_V6 = 256, 257      # go-ipfix NewTemplat
 
 
 _CONTENT_PARTS = ("additional", "dns", "drops", "xlat", "quic")     # the parts nfagg_pb_features carries
+
+
+def _netev_entry(cookie: bytes, event):
+    """nfagg_netev_entry of one decoder answer. event: an ACL as (action, actor, name, namespace, direction, string) with
+    string = the event's String(); any other event as its String() (bytes or str); None or an exception: the decoder failed."""
+    e = L.NetevEntry()
+    cookie = bytes(cookie)
+    assert len(cookie) == 8
+    e.cookie[:] = list(cookie)
+    enc = lambda v: v.encode() if isinstance(v, str) else bytes(v)
+    if event is None or isinstance(event, BaseException):
+        e.kind = L.NETEV_UNDECODABLE
+    elif isinstance(event, (bytes, str)):
+        e.kind = L.NETEV_OTHER
+        e.string, e.string_len = enc(event), len(enc(event))      # not len(e.string): reading a c_char_p back stops at a NUL
+    else:
+        e.kind = L.NETEV_ACL
+        for f, v in zip(("action", "actor", "name", "namespace_", "direction", "string"), event):
+            setattr(e, f, enc(v))
+        e.action_len, e.actor_len, e.name_len, e.namespace_len, e.direction_len, e.string_len = (len(enc(v)) for v in event)
+    return e
+
+
+def netev_render(event, fmt: int) -> bytes:
+    """nfagg_netev_render: the JSON object (L.NETEV_JSON) or the serialized pbflow.NetworkEvent (L.NETEV_PB) of one decoder
+    answer (see _netev_entry), as the encoders emit it. Host only."""
+    e = _netev_entry(bytes(8), event)
+    buf = np.zeros(L.NETEV_MAX_RENDERED, dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = L.lib.nfagg_netev_render(C.byref(e), fmt, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n))
+    if rc != L.OK:
+        raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
+    return buf[: n.value].tobytes()
+
+
+class NetevTable:
+    """The OVN sample decoder's answers as a table (nfagg_netev_table_create): entries = [(cookie8, event)], event as
+    _netev_entry takes it. With a FlowTable the table lives on its device and serves netev_resolve and the *_netev encoders;
+    with table=None it is built and checked on the host only. Row r, as netev_resolve reports it, is cookies[r]: the cookies
+    in ascending order of their little-endian 64-bit value."""
+
+    def __init__(self, entries, table: "FlowTable" = None):
+        entries = list(entries)
+        arr = (L.NetevEntry * max(len(entries), 1))(*[_netev_entry(c, ev) for c, ev in entries])
+        self._t = C.c_void_p()
+        h = table._h if table is not None else None
+        rc = L.lib.nfagg_netev_table_create(h, arr, len(entries), C.byref(self._t))
+        if rc != L.OK:
+            self._t = None
+            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
+        self._owner = table                       # the handle must outlive the table
+        self.cookies = sorted((bytes(c) for c, _ in entries), key=lambda c: int.from_bytes(c, "little"))
+
+    def __len__(self):
+        return len(self.cookies)
+
+    def close(self):
+        if getattr(self, "_t", None):
+            if self._owner is None or self._owner._h:
+                L.lib.nfagg_netev_table_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def _encode_options(cls, now_unix_ns, mono_now_ns, names, unknown):
