@@ -807,7 +807,8 @@ typedef struct nfagg_flp_options {
  * ssl_version, tls_cipher_suite or tls_key_share is non-zero gets an EMPTY
  * line (line_offsets[i+1] == line_offsets[i]); deferred[i] (optional, n bytes)
  * is 1 for it and 0 otherwise, *n_deferred (optional) is their count. The
- * caller formats those records itself.
+ * caller formats those records itself, or hands the names over as a table and
+ * calls nfagg_encode_flp_json_tls (below), which defers nothing.
  * One difference from the reference, by design: the reference reads the clock
  * for every flow's TimeReceived, here one time_received_s covers the call.
  * Returns NFAGG_TRUNCATED with *out_bytes = bytes needed (and *n_deferred)
@@ -984,6 +985,66 @@ int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_re
                                                const uint16_t* d_rows, const nfagg_netev_table* table,
                                                const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
                                                uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes);
+
+/* ------------------------------------------------------------------ */
+/* TLS names — TLSVersion, TLSCipherSuite and TLSGroup of the direct-FLP */
+/* line (decode_protobuf.go:99-110, record.go:240-257) take their text    */
+/* from Go's crypto/tls. The library does not restate it: the caller      */
+/* hands the names over as a table, built once at start from its own      */
+/* crypto/tls, and the GPU does the look-up, the      */
+/* fall-back formats and the bytes.                                       */
+/* ------------------------------------------------------------------ */
+
+enum { NFAGG_TLS_VERSION = 0,        /* ssl_version:      tls.VersionName(id),       unknown: 0x%04X        */
+       NFAGG_TLS_CIPHER_SUITE = 1,   /* tls_cipher_suite: tls.CipherSuiteName(id),   unknown: 0x%04X        */
+       NFAGG_TLS_GROUP = 2           /* tls_key_share:    tls.CurveID(id).String(),  unknown: CurveID(%d)   */ };
+#define NFAGG_TLS_NAME_MAX 63        /* bytes of a name */
+#define NFAGG_TLS_MAX_ROWS 256       /* rows of one kind */
+
+typedef struct nfagg_tls_name_entry {
+    uint16_t kind;               /* NFAGG_TLS_* */
+    uint16_t id;
+    uint32_t name_len;
+    const char* name;            /* read during the call only */
+} nfagg_tls_name_entry;
+
+typedef struct nfagg_tls_names nfagg_tls_names;
+
+/* Build the table from n entries (n == 0 is valid: every value then takes its kind's fall-back format, as does an id
+ * its kind has no row for). Errors (NFAGG_EINVAL, nfagg_last_error names the entry): an unknown kind, a duplicate
+ * (kind, id), an empty name, a name of more than NFAGG_TLS_NAME_MAX bytes, more than NFAGG_TLS_MAX_ROWS rows of a kind,
+ * a name with a byte jsoniter's WriteString would escape (below 0x20, '"' or '\\'): every name of Go's tables is plain
+ * ASCII, and refusing the others keeps the device side a plain copy and bounds how much a line can grow.
+ * With a handle the table is uploaded to that handle's device and serves its calls until destroyed. h == NULL builds
+ * and checks the table on the host alone (errors through nfagg_last_error(NULL)); such a table is refused by the device calls. */
+int nfagg_tls_names_create(nfagg_handle* h, const nfagg_tls_name_entry* entries, size_t n, nfagg_tls_names** table);
+void nfagg_tls_names_destroy(nfagg_tls_names* table);
+
+/* The unquoted string the encoder emits for one value (host only: no handle, no device; the CPU suite pins the bytes
+ * with it): the name or the kind's fall-back format, with "~ " in front for NFAGG_TLS_VERSION when mismatch != 0
+ * (MiscFlagsSSLMismatch, record.go:240-257). NFAGG_TRUNCATED with *n_out = bytes needed when cap is smaller. */
+int nfagg_tls_names_render(const nfagg_tls_names* table, int kind, uint16_t id, int mismatch, void* out, size_t cap, size_t* n_out);
+
+/* The three pairs of direct-FLP entry points in one, with the TLS keys written instead of their records deferred:
+ *   features == NULL                      the line of nfagg_encode_flp_json,
+ *   features, rows == table == NULL       that of nfagg_encode_flp_json_content,
+ *   features, rows and netev_table        that of nfagg_encode_flp_json_content_netev
+ * (rows and netev_table both NULL or both set, else NFAGG_EINVAL), plus, between SrcPort and TimeFlowEndMs and in byte
+ * order with TLSTypes: "TLSCipherSuite" when tls_cipher_suite != 0, "TLSGroup" when tls_key_share != 0, "TLSVersion"
+ * when ssl_version != 0, each a JSON string as nfagg_tls_names_render gives it. tls_names is required and must have been
+ * created for this handle. No record is deferred: every line has at least its braces, and there is neither a deferred
+ * array nor a count. A record without a TLS field gets the bytes the other entry points give it. Size query (out == NULL),
+ * NFAGG_TRUNCATED, alignment and n == 0 as there. All pointers HOST memory: */
+int nfagg_encode_flp_json_tls(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes);
+/* Same with every data pointer (d_rows and those inside d_features too) in DEVICE memory. */
+int nfagg_encode_flp_json_tls_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes);
+/* The longest line nfagg_encode_flp_json_tls can write, in bytes with its newline (policy 0: features == NULL, 1: features,
+ * 2: features with network events; 0 for any other value). The write kernels size their LDS windows by it. */
+uint32_t nfagg_flp_json_tls_max_line(int policy);
 
 /* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */

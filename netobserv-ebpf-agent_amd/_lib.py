@@ -107,6 +107,14 @@ class NetevEntry(C.Structure):
                 ("direction_len", C.c_uint32), ("string_len", C.c_uint32)]
 
 
+class TlsNameEntry(C.Structure):
+    """nfagg_tls_name_entry (include/nfagg.h)."""
+    _fields_ = [("kind", C.c_uint16), ("id", C.c_uint16), ("name_len", C.c_uint32), ("name", C.c_char_p)]
+
+
+TLS_VERSION, TLS_CIPHER_SUITE, TLS_GROUP = 0, 1, 2
+TLS_NAME_MAX, TLS_MAX_ROWS = 63, 256
+
 NETEV_ACL, NETEV_OTHER, NETEV_UNDECODABLE = 0, 1, 2
 NETEV_JSON, NETEV_PB = 0, 1
 NETEV_MAX_RENDERED, NETEV_MAX_ROWS, NETEV_NO_ROW = 512, 65535, 0xFFFF
@@ -189,6 +197,12 @@ SIGNATURES = {
     "nfagg_encode_pb_content_netev_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(PbOptions), _vp, _sz, _vp, _vp, _vp, _psz]),
     "nfagg_encode_flp_json_content_netev": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_encode_flp_json_content_netev_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
+    "nfagg_tls_names_create": (C.c_int, [_vp, C.POINTER(TlsNameEntry), _sz, C.POINTER(_vp)]),
+    "nfagg_tls_names_destroy": (None, [_vp]),
+    "nfagg_tls_names_render": (C.c_int, [_vp, C.c_int, C.c_uint16, C.c_int, _vp, _sz, _psz]),
+    "nfagg_encode_flp_json_tls": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_encode_flp_json_tls_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_flp_json_tls_max_line": (C.c_uint32, [C.c_int]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

@@ -2543,6 +2543,35 @@ static int encode_flp_check(nfagg_handle* h, const nfagg_flp_options* opt) {
     return check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
 }
 
+// What the FLP device entry points stage after encode_begin: the size pass's rows, the escaped namer table, the deferred counter
+// (zeroed), the kernels' parameters.
+static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, FlpParams* Pout, uint32_t** rows_out) {
+    int rc;
+    auto& S = h->enc;
+    const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
+    if ((rc = ensure_buf(h, S.flp_rows, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.flp_esc, esc_bytes)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.flp_n_deferred, 16)) != NFAGG_OK) return rc;
+    // names and UDNs are escaped here, once per row of the sorted table: neither kernel escapes per flow
+    S.h_flp_esc.assign(esc_bytes, 0);
+    flp_escape_row(S.h_flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
+    for (uint32_t k = 0; k < opt->n_names; k++) {
+        const nfagg_intf_name& e = S.h_names[k];
+        flp_escape_row(S.h_flp_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
+    }
+    HIP_TRY(h, hipMemcpyAsync(S.flp_esc.p, S.h_flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
+    *rows_out = (uint32_t*)S.flp_rows.p;
+    FlpParams& P = *Pout;
+    P = FlpParams{};
+    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
+    P.mono_now = opt->mono_now_ns;
+    P.time_received = opt->time_received_s;
+    P.names = (const nfagg_intf_name*)S.names.p; P.esc = (const uint8_t*)S.flp_esc.p; P.n_names = opt->n_names;
+    P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
+    return NFAGG_OK;
+}
+
 // feat (optional): DEVICE pointers. Without it the kernels of nfagg_flp.hip run, with it those of nfagg_flp_content.hip;
 // with ne (the *_netev entry points) the latter's instantiations that carry the NetworkEvents hook.
 static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
@@ -2562,26 +2591,9 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     bool done;
     if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
     auto& S = h->enc;
-    const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
-    if ((rc = ensure_buf(h, S.flp_rows, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.flp_esc, esc_bytes)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.flp_n_deferred, 16)) != NFAGG_OK) return rc;
-    // names and UDNs are escaped here, once per row of the sorted table: neither kernel escapes per flow
-    S.h_flp_esc.assign(esc_bytes, 0);
-    flp_escape_row(S.h_flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
-    for (uint32_t k = 0; k < opt->n_names; k++) {
-        const nfagg_intf_name& e = S.h_names[k];
-        flp_escape_row(S.h_flp_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
-    }
-    HIP_TRY(h, hipMemcpyAsync(S.flp_esc.p, S.h_flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
-    uint32_t* rows = (uint32_t*)S.flp_rows.p;
     FlpParams P{};
-    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
-    P.mono_now = opt->mono_now_ns;
-    P.time_received = opt->time_received_s;
-    P.names = (const nfagg_intf_name*)S.names.p; P.esc = (const uint8_t*)S.flp_esc.p; P.n_names = opt->n_names;
-    P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
+    uint32_t* rows;
+    if ((rc = stage_flp(h, n, opt, &P, &rows)) != NFAGG_OK) return rc;
     uint32_t* counter = (uint32_t*)S.flp_n_deferred.p;
     if (!feat && !ne)
         return encode_two_pass(h, n, "FLP JSON", "write", d_out, out_cap, out_bytes, n_deferred,
@@ -2891,6 +2903,160 @@ int nfagg_netev_resolve(nfagg_handle* h, const nfagg_netev_table* table, const u
     if (zero) { if (m < missing_cap) memset(missing[m++], 0, 8); else *overflow = 1; }    // the all-zero cookie takes a place of the list like any other
     *n_missing = m;
     return NFAGG_OK;
+}
+
+}  // extern "C"
+
+// ---- TLS names: the caller's table (nfagg_tls.h) and the direct-FLP entry points that write the three keys
+// Per kind the ids ascending and a 64-byte row per id (length byte, name), on the host and (with a handle) on its device.
+struct nfagg_tls_names {
+    nfagg_handle* h = nullptr;
+    uint32_t n[kTlsKinds] = {};
+    std::vector<uint16_t> ids = std::vector<uint16_t>(kTlsKinds * kTlsMaxRows, 0);
+    std::vector<uint8_t> rows = std::vector<uint8_t>((size_t)kTlsKinds * kTlsMaxRows * kTlsRowBytes, 0);
+    void* d_mem = nullptr;        // the ids, then the rows
+};
+
+extern "C" {
+
+int nfagg_tls_names_create(nfagg_handle* h, const nfagg_tls_name_entry* entries, size_t n, nfagg_tls_names** table) {
+    if (!table || (n && !entries)) return fail(h, NFAGG_EINVAL, "null argument");
+    *table = nullptr;
+    size_t count[kTlsKinds] = {};
+    std::vector<uint32_t> order(n);
+    for (size_t k = 0; k < n; k++) {
+        const nfagg_tls_name_entry& e = entries[k];
+        order[k] = (uint32_t)k;
+        if (e.kind >= kTlsKinds) return fail(h, NFAGG_EINVAL, "TLS name entry %zu: unknown kind %u", k, (unsigned)e.kind);
+        if (e.name_len == 0 || !e.name) return fail(h, NFAGG_EINVAL, "TLS name entry %zu: empty name", k);
+        if (e.name_len > NFAGG_TLS_NAME_MAX) return fail(h, NFAGG_EINVAL, "TLS name entry %zu: a name of %u bytes, the cap is %d", k, e.name_len, NFAGG_TLS_NAME_MAX);
+        for (uint32_t b = 0; b < e.name_len; b++) {
+            const uint8_t c = (uint8_t)e.name[b];
+            if (c < 0x20 || c == '"' || c == '\\') return fail(h, NFAGG_EINVAL, "TLS name entry %zu: byte 0x%02x at %u would need escaping", k, c, b);
+        }
+        if (++count[e.kind] > kTlsMaxRows) return fail(h, NFAGG_EINVAL, "TLS name entry %zu: more than %u rows of kind %u", k, kTlsMaxRows, (unsigned)e.kind);
+    }
+    auto key = [&](uint32_t k) { return ((uint32_t)entries[k].kind << 16) | entries[k].id; };
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) != key(b) ? key(a) < key(b) : a < b; });
+    for (size_t r = 1; r < n; r++)
+        if (key(order[r]) == key(order[r - 1]))
+            return fail(h, NFAGG_EINVAL, "TLS name entries %u and %u carry the same kind %u and id 0x%04x", order[r - 1], order[r],
+                        (unsigned)entries[order[r]].kind, (unsigned)entries[order[r]].id);
+    nfagg_tls_names* t = new (std::nothrow) nfagg_tls_names;
+    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
+    t->h = h;
+    for (size_t r = 0; r < n; r++) {
+        const nfagg_tls_name_entry& e = entries[order[r]];
+        const size_t slot = (size_t)e.kind * kTlsMaxRows + t->n[e.kind]++;
+        t->ids[slot] = e.id;
+        uint8_t* row = t->rows.data() + slot * kTlsRowBytes;
+        row[0] = (uint8_t)e.name_len;
+        memcpy(row + 1, e.name, e.name_len);
+    }
+    if (h) {
+        const size_t id_bytes = t->ids.size() * sizeof(uint16_t);
+        static_assert(kTlsKinds * kTlsMaxRows * sizeof(uint16_t) % 16 == 0, "the rows start 16-byte aligned");
+        auto up = [&]() -> int {
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMalloc(&t->d_mem, id_bytes + t->rows.size()));
+            HIP_TRY(h, hipMemcpy(t->d_mem, t->ids.data(), id_bytes, hipMemcpyHostToDevice));
+            HIP_TRY(h, hipMemcpy((uint8_t*)t->d_mem + id_bytes, t->rows.data(), t->rows.size(), hipMemcpyHostToDevice));
+            return NFAGG_OK;
+        };
+        const int rc = up();
+        if (rc != NFAGG_OK) { nfagg_tls_names_destroy(t); return rc; }
+    }
+    *table = t;
+    return NFAGG_OK;
+}
+
+void nfagg_tls_names_destroy(nfagg_tls_names* t) {
+    if (!t) return;
+    if (t->h && t->d_mem) {
+        (void)hipSetDevice(t->h->device);
+        (void)hipStreamSynchronize(t->h->stream);
+        (void)hipFree(t->d_mem);
+    }
+    delete t;
+}
+
+int nfagg_tls_names_render(const nfagg_tls_names* t, int kind, uint16_t id, int mismatch, void* out, size_t cap, size_t* n_out) {
+    if (!t || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
+    if (kind < 0 || kind >= (int)kTlsKinds) return fail(nullptr, NFAGG_EINVAL, "unknown kind %d", kind);
+    char buf[2 + NFAGG_TLS_NAME_MAX + 1];
+    size_t len = 0;
+    if (kind == NFAGG_TLS_VERSION && mismatch) { buf[0] = '~'; buf[1] = ' '; len = 2; }
+    const uint16_t* ids = t->ids.data() + (size_t)kind * kTlsMaxRows;
+    const uint16_t* hit = std::lower_bound(ids, ids + t->n[kind], id);
+    if (hit != ids + t->n[kind] && *hit == id) {
+        const uint8_t* row = t->rows.data() + ((size_t)kind * kTlsMaxRows + (size_t)(hit - ids)) * kTlsRowBytes;
+        memcpy(buf + len, row + 1, row[0]);
+        len += row[0];
+    } else {
+        len += (size_t)snprintf(buf + len, sizeof buf - len, kind == NFAGG_TLS_GROUP ? "CurveID(%u)" : "0x%04X", (unsigned)id);
+    }
+    *n_out = len;
+    if (!out || cap < len) return NFAGG_TRUNCATED;
+    memcpy(out, buf, len);
+    return NFAGG_OK;
+}
+
+uint32_t nfagg_flp_json_tls_max_line(int policy) { return flp_tls_max_line(policy); }
+
+static int encode_flp_tls_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                                      const nfagg_tls_names* tls, const nfagg_flp_options* opt, void* d_out, size_t out_cap,
+                                      uint64_t* d_line_offsets, size_t* out_bytes) {
+    int rc = encode_flp_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !tls || !out_bytes || !d_line_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (tls->h != h || !tls->d_mem) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
+    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
+    PbFeat F{};
+    if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
+    if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
+    bool done;
+    if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
+    FlpParams P{};
+    uint32_t* rows;
+    if ((rc = stage_flp(h, n, opt, &P, &rows)) != NFAGG_OK) return rc;
+    TlsDev T{};
+    T.ids = (const uint16_t*)tls->d_mem;
+    T.rows = (const uint8_t*)tls->d_mem + tls->ids.size() * sizeof(uint16_t);
+    for (uint32_t k = 0; k < kTlsKinds; k++) T.n[k] = tls->n[k];
+    const PbFeat* Fp = (feat || ne) ? &F : nullptr;                   // neither: the plain line
+    return encode_two_pass(h, n, "FLP JSON with TLS names", "write", d_out, out_cap, out_bytes, nullptr,
+        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+            return launch_flpt_size(d_records, n, P, Fp, T, rows, local_off, block_sum, block_base, h->stream); },
+        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+            return launch_flpt_write(d_records, n, P, Fp, T, rows, local_off, block_base, d_out, d_line_offsets, h->stream); });
+}
+
+int nfagg_encode_flp_json_tls_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
+    if ((d_rows != nullptr) != (netev_table != nullptr) && (n || d_rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
+    const NetevArgs ne{d_rows, netev_table};
+    return encode_flp_tls_device_core(h, d_records, n, d_features, netev_table ? &ne : nullptr, tls_names, opt, d_out, out_cap, d_line_offsets, out_bytes);
+}
+
+int nfagg_encode_flp_json_tls(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
+    int rc = encode_flp_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !tls_names || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if ((rows != nullptr) != (netev_table != nullptr) && (n || rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
+    if (features && features->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
+    const NetevArgs ne{rows, netev_table};
+    return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {},
+        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
+            nfagg_pb_features dfeat{};
+            dfeat.struct_size = sizeof dfeat;
+            if (features && n) { int rc2 = stage_pb_features(h, features, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
+            NetevArgs dne{};
+            if (netev_table) { int rc2 = stage_netev_rows(h, &ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
+            return encode_flp_tls_device_core(h, d_records, n, features ? &dfeat : nullptr, netev_table ? &dne : nullptr, tls_names, opt, d_out,
+                                              out_cap, d_offsets, out_bytes); });
 }
 
 }  // extern "C"

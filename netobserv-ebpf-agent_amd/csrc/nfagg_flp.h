@@ -26,6 +26,16 @@ struct FlpParams {
     uint32_t agent_ip_w[4];       // Record.AgentIP as a 16-byte net.IP, four little-endian dwords
 };
 
+// The TLS name table of nfagg_tls_names_create on the device (nfagg_tls.h): per kind kTlsMaxRows ids, ascending, the first
+// n[kind] of them in use, and as many 64-byte rows (a length byte, then up to 63 name bytes).
+constexpr uint32_t kTlsKinds = 3, kTlsMaxRows = NFAGG_TLS_MAX_ROWS, kTlsRowBytes = 64;
+static_assert(NFAGG_TLS_NAME_MAX + 1 == kTlsRowBytes && (kTlsMaxRows & (kTlsMaxRows - 1)) == 0, "TLS name row layout, search steps");
+struct TlsDev {
+    const uint16_t* ids;          // [kTlsKinds][kTlsMaxRows]
+    const uint8_t* rows;          // [kTlsKinds][kTlsMaxRows][kTlsRowBytes], 16-byte aligned
+    uint32_t n[kTlsKinds];
+};
+
 // Line lengths (0 = deferred) and the seven resolved interface rows per record (d_rows: 8 dwords per record, rows 0..6
 // and the length), block-local scan, scan of the block sums: d_block_base[ceil(n / 1024)] = total bytes afterwards.
 // *d_n_deferred (zeroed by the caller) counts the deferred records.
@@ -41,5 +51,14 @@ hipError_t launch_flpc_size(const void* d_recs, uint64_t n, const FlpParams& P, 
 hipError_t launch_flpc_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const uint32_t* d_rows,
                              const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
                              uint8_t* d_deferred, hipStream_t s);
+
+// The same two passes with the TLS names on (nfagg_encode_flp_json_tls): TLSVersion, TLSCipherSuite and TLSGroup are looked up
+// in T and written, no record is deferred. Policy: F == nullptr the line of launch_flp_*, else that of launch_flpc_*.
+hipError_t launch_flpt_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, uint32_t* d_rows,
+                            uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s);
+hipError_t launch_flpt_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const uint32_t* d_rows,
+                             const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s);
+// The longest line each of those policies can write (0: plain, 1: content, 2: content with network events).
+uint32_t flp_tls_max_line(int policy);
 
 }  // namespace nfagg

@@ -21,6 +21,7 @@
 // constant blob with an offset and a length per name; the counting pass reads only the lengths.
 #include "nfagg_flp_line.h"
 #include "nfagg_netev.h"
+#include "nfagg_tls.h"
 
 namespace nfagg {
 
@@ -274,6 +275,8 @@ struct FlpContent {
     template <typename S> NF_DEV void zone(S& s) const {
         if (xlated()) { lit(s, ",\"ZoneId\":"); dec<5>(s, xlt[9] & 0xffffu); }
     }
+    template <typename S> NF_DEV void tls_names(S&, const Rec&) const {}     // a record with these keys is deferred; FlpTls has them
+    template <typename S> NF_DEV void tls_version(S&, const Rec&) const {}
 };
 
 // FlpContent plus the flow's network events: the table rows nfagg_netev_resolve wrote (PbFeat::ne_rows), each row's JSON
@@ -403,6 +406,117 @@ hipError_t launch_flpc_write(const void* d_recs, uint64_t n, const FlpParams& P,
     else hipLaunchKernelGGL(k_flpc_write<FlpContent>, grid, dim3(64), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_base,
                             (uint8_t*)d_out, d_line_offsets, d_deferred);
     return hipGetLastError();
+}
+
+// ---- the three policies with the TLS names on (nfagg_encode_flp_json_tls): FlpTls over the plain line, over FlpContent and
+// over FlpContentNetev. Kernels of their own, so that the six above keep their code and their registers; no record is
+// deferred, so there is neither a flag nor a counter. Their longest lines are the ones that are reached (nfagg_tls.h).
+struct FlpPlainT : NoFeat {
+    static constexpr uint32_t kMaxLine = kFlpMaxLine - kFlpLineUnreached, kSideLds = 16;      // no DNS name slots: one unused chunk
+    NF_DEV void load(const PbFeat&, uint64_t, uint8_t*) {}
+};
+struct FlpContentT : FlpContent { static constexpr uint32_t kMaxLine = kFlpcMaxLine - kFlpcLineUnreached, kSideLds = kFlpcNameLds; };
+struct FlpContentNetevT : FlpContentNetev { static constexpr uint32_t kMaxLine = kFlpnMaxLine - kFlpcLineUnreached, kSideLds = kFlpcNameLds; };
+
+template <typename Feat>
+__global__ __launch_bounds__(kScanBlock) void k_flpt_size(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T,
+                                                          uint32_t* __restrict__ rows, uint32_t* __restrict__ local_off,
+                                                          uint32_t* __restrict__ block_sum) {
+    constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;       // a DNS name slot per lane where the policy reads one
+    __shared__ uint32_t wave_tot[kScanBlock / 64];
+    __shared__ __align__(16) uint8_t name_lds[kSlot ? kScanBlock * kSlot : 16];
+    __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
+    const uint8_t* tab = stage_names<kScanBlock>(P.names, P.n_names, tab_lds);
+    const uint64_t i = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x;
+    uint32_t len = 0;
+    if (i < n) {
+        Rec r;
+        load_record(recs, i, r);
+        uint32_t row[7];
+        flp_rows(tab, P.n_names, r, row);
+        Feat f;
+        f.load(F, i, name_lds + threadIdx.x * kSlot);
+        f.tls = T;
+        CountSink c;
+        encode_line(c, r, P, row, f);
+        len = c.n;
+        uint4* o = reinterpret_cast<uint4*>(rows + i * 8);
+        o[0] = make_uint4(row[0], row[1], row[2], row[3]);
+        o[1] = make_uint4(row[4], row[5], row[6], len);
+    }
+    block_scan(len, i, n, wave_tot, local_off, block_sum);
+}
+
+template <typename Feat>
+__global__ __launch_bounds__(64) void k_flpt_write(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T,
+                                                   const uint32_t* __restrict__ rows, const uint32_t* __restrict__ local_off,
+                                                   const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
+                                                   uint64_t* __restrict__ line_offsets) {
+    constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;
+    static_assert(Feat::kLds + Feat::kSideLds <= 32768, "four waves per compute unit");
+    __shared__ __align__(16) uint8_t lds[Feat::kLds];
+    __shared__ __align__(16) uint8_t name_lds[Feat::kSideLds];
+    const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
+    WaveImage w(block_base, local_off, i0);
+    uint64_t my_off = 0; uint32_t my_len = 0;
+    uint32_t row[7] = {};
+    Rec r;
+    Feat f;
+    f.tls = T;
+    if (i < n) {
+        load_record(recs, i, r);
+        const uint4* q = reinterpret_cast<const uint4*>(rows + i * 8);
+        const uint4 a = q[0], b = q[1];
+        row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w; row[4] = b.x; row[5] = b.y; row[6] = b.z;
+        my_len = b.w;                                                 // every line has at least its braces
+        f.load(F, i, name_lds + threadIdx.x * kSlot);
+        my_off = record_off(block_base, local_off, i);
+        line_offsets[i] = my_off;
+        if (i == n - 1) line_offsets[n] = my_off + my_len;
+    }
+    w.close(my_off + my_len, out);
+    const uint32_t p0 = w.pos(my_off);                            // my line = image bytes [p0, p0 + my_len)
+    uint32_t lo = w.shift;
+    while (lo < w.span) {
+        const uint32_t base = lo & ~15u;
+        const bool mine = my_len && p0 >= lo && p0 - base < Feat::kWindow;
+        if (mine) { FlpLds s{lds + (p0 - base)}; encode_line(s, r, P, row, f); }
+        uint32_t hi = mine ? p0 + my_len : lo;                  // the window's end: at most base + Feat::kWindow + Feat::kMaxLine
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(hi, d, 64); hi = o > hi ? o : hi; }
+        __syncthreads();
+        copy_image_out(w.dst, lds, base, lo, hi);
+        __syncthreads();
+        lo = hi;
+    }
+}
+
+hipError_t launch_flpt_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, uint32_t* d_rows,
+                            uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
+    const dim3 grid(blocks), block(kScanBlock);
+    (void)hipGetLastError();
+    if (!F) hipLaunchKernelGGL(k_flpt_size<FlpTls<FlpPlainT>>, grid, block, 0, s, d_recs, n, P, PbFeat{}, T, d_rows, d_local_off, d_block_sum);
+    else if (F->ne_rows) hipLaunchKernelGGL(k_flpt_size<FlpTls<FlpContentNetevT>>, grid, block, 0, s, d_recs, n, P, *F, T, d_rows, d_local_off, d_block_sum);
+    else hipLaunchKernelGGL(k_flpt_size<FlpTls<FlpContentT>>, grid, block, 0, s, d_recs, n, P, *F, T, d_rows, d_local_off, d_block_sum);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
+}
+
+hipError_t launch_flpt_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const uint32_t* d_rows,
+                             const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s) {
+    (void)hipGetLastError();
+    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    uint8_t* out = (uint8_t*)d_out;
+    if (!F) hipLaunchKernelGGL(k_flpt_write<FlpTls<FlpPlainT>>, grid, block, 0, s, d_recs, n, P, PbFeat{}, T, d_rows, d_local_off, d_block_base, out, d_line_offsets);
+    else if (F->ne_rows) hipLaunchKernelGGL(k_flpt_write<FlpTls<FlpContentNetevT>>, grid, block, 0, s, d_recs, n, P, *F, T, d_rows, d_local_off, d_block_base, out, d_line_offsets);
+    else hipLaunchKernelGGL(k_flpt_write<FlpTls<FlpContentT>>, grid, block, 0, s, d_recs, n, P, *F, T, d_rows, d_local_off, d_block_base, out, d_line_offsets);
+    return hipGetLastError();
+}
+
+uint32_t flp_tls_max_line(int policy) {
+    return policy == 0 ? FlpTls<FlpPlainT>::kMaxLine : policy == 1 ? FlpTls<FlpContentT>::kMaxLine : policy == 2 ? FlpTls<FlpContentNetevT>::kMaxLine : 0u;
 }
 
 }  // namespace nfagg

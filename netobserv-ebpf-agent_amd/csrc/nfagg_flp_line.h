@@ -157,10 +157,11 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
     return k == 0 ? r.d[24] & 0xffu : k <= 4 ? (r.d[25] >> (8 * (k - 1))) & 0xffu : (r.d[26] >> (8 * (k - 5))) & 0xffu;
 }
 
-// The keys of a flow's feature parts (DNS, drops, xlat, RTT / IPsec, QUIC, network events) fall in eight contiguous groups of
+// The keys of a flow's feature parts (DNS, drops, xlat, RTT / IPsec, QUIC, network events) fall in ten contiguous groups of
 // the sorted line; encode_line calls one hook of its feature policy at each. NoFeat: a record that carries only BpfFlowMetrics,
 // every hook is empty and the line is the one of decode_protobuf.go:57-127. FlpContent (nfagg_flp_content.hip) holds
-// the parts of a full BpfFlowContent, FlpContentNetev adds the flow's resolved network events.
+// the parts of a full BpfFlowContent, FlpContentNetev adds the flow's resolved network events. The two TLS hooks take the
+// record: they are empty in all three, and a record that would need them is deferred; FlpTls (nfagg_tls.h) fills them.
 struct NoFeat {
     template <typename S> NF_DEV void dns(S&) const {}        // Dns*          after Bytes
     template <typename S> NF_DEV void ipsec(S&) const {}      // IPSec*        after Flags
@@ -170,6 +171,8 @@ struct NoFeat {
     template <typename S> NF_DEV void rtt(S&) const {}        // TimeFlowRttNs after TimeFlowEndMs
     template <typename S> NF_DEV void xlat(S&) const {}       // Xlat*         after Udns
     template <typename S> NF_DEV void zone(S&) const {}       // ZoneId        last
+    template <typename S> NF_DEV void tls_names(S&, const Rec&) const {}     // TLSCipherSuite TLSGroup  after SrcPort
+    template <typename S> NF_DEV void tls_version(S&, const Rec&) const {}   // TLSVersion               after TLSTypes
 };
 
 // One line. Same code measures (CountSink) and writes (FlpLds). The policy travels by value: a reference to an empty NoFeat
@@ -223,6 +226,7 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
     if (ip) { lit(s, ",\"SrcAddr\":\""); ip_text(s, Ip4w{{r.d[0], r.d[1], r.d[2], r.d[3]}}); s.put('"'); }
     lit(s, ",\"SrcMac\":\""); mac_text(s, r.smac()); s.put('"');
     if (ports) { lit(s, ",\"SrcPort\":"); dec<5>(s, r.d[8] & 0xffffu); }
+    f.tls_names(s, r);
     const uint32_t tls = (r.d[34] >> 16) & 0xffu;                      // tls_types @138
     if (tls) {   // tlsTypesToStrings (pkg/model/tls_types.go) in its order; no known bit: a nil slice, "null"
         lit(s, ",\"TLSTypes\":");
@@ -239,6 +243,7 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
             s.put(']');
         }
     }
+    f.tls_version(s, r);
     const TimeParts ts = flow_time(P.now_sec, P.now_nsec, P.mono_now, r.start());
     const TimeParts te = flow_time(P.now_sec, P.now_nsec, P.mono_now, r.end());
     lit(s, ",\"TimeFlowEndMs\":"); dec_i64(s, te.sec * 1000 + te.nsec / 1000000);      // t.UnixMilli()

@@ -11,7 +11,8 @@ BASELINE configs[0] ("10k flow_record_t, 1k 5-tuples, Accounter via direct-flp s
 
 Plumbing only — no flow state is touched here; the records come from libnfagg (accounter.py). The
 string tables of the feature branch (TCP states, drop causes, DNS rcodes, TLS names) stay with the Go
-decoder: RecordToMap refuses records that would need them instead of guessing."""
+decoder: RecordToMap refuses records that would need them instead of guessing. (The GPU encoders take the TLS
+names as a caller-built table, TlsNames: DirectFLPJSON and MapTracer.evictFlowsJSON with tls_names.)"""
 import ipaddress
 import json
 import queue
@@ -218,10 +219,11 @@ class MapTracer:
             self._netevTable.close()
             self._netevTable = None
 
-    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown"):
+    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None):
         """evictFlows for a direct-FLP `write: stdout, format: json` stage, without a Record per flow: the drained maps are merged,
         decorated with the sample decoder's network events and encoded on the GPU. Returns (buf, line_offsets, deferred) as
-        FlowTable.encode_flp_json_content does."""
+        FlowTable.encode_flp_json_content does; with tls_names (a TlsNames of the fetcher's table) the TLS keys are written too,
+        nothing is deferred and the result is (buf, line_offsets) as FlowTable.encode_flp_json_tls gives it."""
         monotonic_now, current = self.monoClock(), self.clock()
         table = self.mapFetcher.table
         main_ids, main_vals, feats, n_cpu = self.mapFetcher.drain()
@@ -229,8 +231,12 @@ class MapTracer:
         names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         mono = monotonic_now & ((1 << 64) - 1)
         if self.sampleDecoder is None:                                  # s == nil: no events, no injected drops (record.go:126)
+            if tls_names is not None:
+                return table.encode_flp_json_tls(recs, tls_names, current, mono, names, agent_ip, time_received, unknown, present, parts)
             return table.encode_flp_json_content(recs, present, parts, current, mono, names, agent_ip, time_received, unknown)
         p_out, parts, rows, tab = self.resolveNetworkEvents(present, parts)
+        if tls_names is not None:
+            return table.encode_flp_json_tls(recs, tls_names, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         return table.encode_flp_json_netev(recs, p_out, parts, rows, tab, current, mono, names, agent_ip, time_received, unknown)
 
     def evictFlows(self, forwardFlows: "queue.Queue"):                  # :103-146
@@ -342,11 +348,13 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
     per flow. Lines are written to `stream` (binary: anything with write(bytes)) in record order. A record the encoder
     defers (TLS version / cipher suite / key share set) is formatted by `fallback(record, now_ns, mono_ns) -> bytes`, the
     whole line with its newline, and written at its place; the default raises, as RecordToMap does for such a record.
+    With `tls_names` (a TlsNames of `table`) the encoder writes those records' TLS keys itself (FlowTable.encode_flp_json_tls):
+    nothing is deferred, `fallback` is never called and an eviction is one write.
 
     One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
 
     def __init__(self, table, stream, names=None, agent_ip=None, unknown: bytes = b"unknown", time_received: Callable[[], int] = None,
-                 fallback: Callable = None, encode=None):
+                 fallback: Callable = None, encode=None, tls_names=None):
         self.table, self.stream = table, stream
         self.names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         self.agent_ip, self.unknown = agent_ip, unknown
@@ -355,6 +363,7 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         self.lines = self.deferred = 0
         # encode(raw, now_ns, mono_ns, names, agent_ip, time_received, unknown) -> (buf, line_offsets, deferred)
         self._encode = encode or table.encode_flp_json
+        self.tls_names = tls_names
 
     def ExportEvicted(self, raw, now_ns: int, mono_ns: int) -> int:
         """One eviction's lines. now_ns / mono_ns: the eviction's currentTime / monotonicCurrentTime (account.go:103-104).
@@ -362,6 +371,12 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         n = len(raw)
         if n == 0:
             return 0
+        if self.tls_names is not None:
+            buf, off = self.table.encode_flp_json_tls(raw, self.tls_names, now_ns, mono_ns & ((1 << 64) - 1), self.names, self.agent_ip,
+                                                      self.time_received(), self.unknown)
+            self.stream.write(memoryview(np.ascontiguousarray(buf))[:int(off[n])])
+            self.lines += n
+            return n
         buf, off, deferred = self._encode(raw, now_ns, mono_ns & ((1 << 64) - 1), self.names, self.agent_ip, self.time_received(),
                                           self.unknown)
         raw_buf = memoryview(np.ascontiguousarray(buf))

@@ -594,6 +594,49 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, need.value, n_def.value
 
+    # -- TLS names (nfagg_tls_names_*) and the direct-FLP encoder that writes them, nfagg_encode_flp_json_tls
+    def tls_names(self, entries=None) -> "TlsNames":
+        """A TLS name table on this handle's device; entries: [(kind, id, name)], default GO_TLS_NAMES. See TlsNames."""
+        return TlsNames(GO_TLS_NAMES if entries is None else entries, self)
+
+    def encode_flp_json_tls(self, records: np.ndarray, tls_names: "TlsNames", now_unix_ns: int, mono_now_ns: int, names: np.ndarray,
+                            agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", present=None, parts=None, rows=None,
+                            netev_table: "NetevTable" = None):
+        """encode_flp_json (present=None), encode_flp_json_content (present / parts) or encode_flp_json_netev (rows and
+        netev_table as well) with TLSVersion, TLSCipherSuite and TLSGroup written from `tls_names` (nfagg_encode_flp_json_tls):
+        no record is deferred. Returns (buf, line_offsets)."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
+        feat = None
+        if present is not None:
+            feat, keep_f = self._pb_features(n, present, {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS})
+        rw = np.ascontiguousarray(rows, dtype=np.uint16).reshape(n, 4) if rows is not None else None
+        off = np.zeros(n + 1, dtype=np.uint64)
+        buf = self._encode_grown(n, 640, lambda p, cap, need: L.lib.nfagg_encode_flp_json_tls(
+            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat) if feat is not None else None,
+            rw.ctypes.data_as(C.c_void_p) if rw is not None else None, netev_table._t if netev_table is not None else None, tls_names._t,
+            C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p), need))
+        return buf, off
+
+    def encode_flp_json_tls_device(self, d_records: int, n: int, tls_names: "TlsNames", now_unix_ns: int, mono_now_ns: int,
+                                   names: np.ndarray, agent_ip, time_received: int, d_out: int, out_cap: int, d_line_offsets: int,
+                                   unknown: bytes = b"unknown", d_present: int = 0, d_parts=None, d_rows: int = 0,
+                                   netev_table: "NetevTable" = None):
+        """Device-resident variant (raw device pointers; d_present = 0: no parts; d_out = 0 asks for the size). Returns (rc,
+        bytes needed/written)."""
+        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
+        feat = None
+        if d_present:
+            feat, _ = self._pb_features(n, d_present, {k: v for k, v in (d_parts or {}).items() if k in _CONTENT_PARTS}, device=True)
+        need = C.c_size_t(0)
+        rc = L.lib.nfagg_encode_flp_json_tls_device(
+            self._h, C.c_void_p(d_records or None), n, C.byref(feat) if feat is not None else None, C.c_void_p(d_rows or None),
+            netev_table._t if netev_table is not None else None, tls_names._t, C.byref(o), C.c_void_p(d_out or None), out_cap,
+            C.c_void_p(d_line_offsets or None), C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -818,6 +861,87 @@ class NetevTable:
         if getattr(self, "_t", None):
             if self._owner is None or self._owner._h:
                 L.lib.nfagg_netev_table_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+# Go's crypto/tls names as product data: tls.VersionName of 0x0300..0x0304, tls.CipherSuiteName of CipherSuites() and
+# InsecureCipherSuites(), tls.CurveID.String() of the curve constants.
+GO_TLS_NAMES = (
+    [(L.TLS_VERSION, i, n) for i, n in ((0x0300, "SSLv3"), (0x0301, "TLS 1.0"), (0x0302, "TLS 1.1"), (0x0303, "TLS 1.2"), (0x0304, "TLS 1.3"))] +
+    [(L.TLS_CIPHER_SUITE, i, n) for i, n in (
+        (0x0005, "TLS_RSA_WITH_RC4_128_SHA"), (0x000a, "TLS_RSA_WITH_3DES_EDE_CBC_SHA"), (0x002f, "TLS_RSA_WITH_AES_128_CBC_SHA"),
+        (0x0035, "TLS_RSA_WITH_AES_256_CBC_SHA"), (0x003c, "TLS_RSA_WITH_AES_128_CBC_SHA256"), (0x009c, "TLS_RSA_WITH_AES_128_GCM_SHA256"),
+        (0x009d, "TLS_RSA_WITH_AES_256_GCM_SHA384"), (0x1301, "TLS_AES_128_GCM_SHA256"), (0x1302, "TLS_AES_256_GCM_SHA384"),
+        (0x1303, "TLS_CHACHA20_POLY1305_SHA256"), (0xc007, "TLS_ECDHE_ECDSA_WITH_RC4_128_SHA"),
+        (0xc009, "TLS_ECDHE_ECDSA_WITH_AES_128_CBC_SHA"), (0xc00a, "TLS_ECDHE_ECDSA_WITH_AES_256_CBC_SHA"),
+        (0xc011, "TLS_ECDHE_RSA_WITH_RC4_128_SHA"), (0xc012, "TLS_ECDHE_RSA_WITH_3DES_EDE_CBC_SHA"),
+        (0xc013, "TLS_ECDHE_RSA_WITH_AES_128_CBC_SHA"), (0xc014, "TLS_ECDHE_RSA_WITH_AES_256_CBC_SHA"),
+        (0xc023, "TLS_ECDHE_ECDSA_WITH_AES_128_CBC_SHA256"), (0xc027, "TLS_ECDHE_RSA_WITH_AES_128_CBC_SHA256"),
+        (0xc02b, "TLS_ECDHE_ECDSA_WITH_AES_128_GCM_SHA256"), (0xc02c, "TLS_ECDHE_ECDSA_WITH_AES_256_GCM_SHA384"),
+        (0xc02f, "TLS_ECDHE_RSA_WITH_AES_128_GCM_SHA256"), (0xc030, "TLS_ECDHE_RSA_WITH_AES_256_GCM_SHA384"),
+        (0xcca8, "TLS_ECDHE_RSA_WITH_CHACHA20_POLY1305_SHA256"), (0xcca9, "TLS_ECDHE_ECDSA_WITH_CHACHA20_POLY1305_SHA256"))] +
+    [(L.TLS_GROUP, i, n) for i, n in ((23, "CurveP256"), (24, "CurveP384"), (25, "CurveP521"), (29, "X25519"), (4588, "X25519MLKEM768"))])
+
+
+class TlsNames:
+    """The names of TLS versions, cipher suites and groups as a table (nfagg_tls_names_create): entries = [(kind, id, name)],
+    kind one of L.TLS_VERSION / L.TLS_CIPHER_SUITE / L.TLS_GROUP, name str or bytes (plain: nothing a JSON string escapes).
+    With a FlowTable the table lives on its device and serves encode_flp_json_tls; with table=None it is built and
+    checked on the host only, which is enough for render(). An id without a row prints as 0x%04X (version, cipher suite)
+    or CurveID(%d) (group).
+
+    GO_TLS_NAMES, the default of FlowTable.tls_names(), is a restatement of Go's crypto/tls tables kept as product data.
+    The reference's own test vectors pin only "TLS 1.2", "TLS 1.3", "TLS_AES_256_GCM_SHA384", "X25519" and the 0x0200
+    fall-back; the Go shim should not use the list but build its table from its own crypto/tls, so
+    that the names follow the Go release it is built with."""
+
+    def __init__(self, entries=GO_TLS_NAMES, table: "FlowTable" = None):
+        entries = [(int(k), int(i), n.encode() if isinstance(n, str) else bytes(n)) for k, i, n in entries]
+        for k, i, _ in entries:
+            if not (0 <= k <= 0xFFFF and 0 <= i <= 0xFFFF):
+                raise ValueError("TLS name entry (%d, %d): kind and id are 16-bit values" % (k, i))
+        arr = (L.TlsNameEntry * max(len(entries), 1))()
+        for e, (k, i, n) in zip(arr, entries):
+            e.kind, e.id, e.name, e.name_len = k, i, n, len(n)        # not len(e.name): reading a c_char_p back stops at a NUL
+        self._t = C.c_void_p()
+        h = table._h if table is not None else None
+        rc = L.lib.nfagg_tls_names_create(h, arr, len(entries), C.byref(self._t))
+        if rc != L.OK:
+            self._t = None
+            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
+        self._owner = table                       # the handle must outlive the table
+        self.n = len(entries)
+
+    def __len__(self):
+        return self.n
+
+    def render(self, kind: int, id: int, mismatch: bool = False) -> bytes:
+        """nfagg_tls_names_render: the unquoted string the encoder emits for this value. Host only."""
+        if not 0 <= int(id) <= 0xFFFF:
+            raise ValueError("id %d does not fit the record's 16-bit field" % id)
+        buf = np.zeros(L.TLS_NAME_MAX + 2, dtype=np.uint8)
+        n = C.c_size_t(0)
+        rc = L.lib.nfagg_tls_names_render(self._t, kind, int(id), 1 if mismatch else 0, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n))
+        if rc != L.OK:
+            raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
+        return buf[: n.value].tobytes()
+
+    def close(self):
+        if getattr(self, "_t", None):
+            if self._owner is None or self._owner._h:
+                L.lib.nfagg_tls_names_destroy(self._t)
             self._t = None
 
     def __del__(self):

@@ -11,7 +11,12 @@ as a fraction of 8 TB/s. Kernel-level device time: run under rocprofv3 --kernel-
 
 --content: the MapTracer leg instead. The flows evicted at the larger size are encoded as full BpfFlowContents
 (nfagg_encode_flp_json_content_device) with every feature part present on about half of them, and as plain records
-(nfagg_encode_flp_json_device) in the same process as the yardstick; both report their time per output byte."""
+(nfagg_encode_flp_json_device) in the same process as the yardstick; both report their time per output byte.
+
+--tls: the TLS-name leg. The flows evicted at the larger size are encoded twice in one process: with their TLS fields clear
+through nfagg_encode_flp_json_device, the yardstick, then with ssl_version / tls_cipher_suite / tls_key_share set on a seeded
+half of them (known and unknown ids, the mismatch flag on some) through nfagg_encode_flp_json_tls_device with the default
+name table. Both report their time per flow and per output byte."""
 import io
 import os
 import queue
@@ -33,6 +38,7 @@ names = nf.intf_table([(2, None, "eth0", ""), (3, None, "eth1", "default"), (4, 
 agent = bytes(10) + b"\xff\xff" + bytes([10, 0, 0, 1])
 NOW, MONO = 10**18, 10**12
 CONTENT = "--content" in sys.argv[1:]
+TLS = "--tls" in sys.argv[1:]
 PART_BYTES = {"additional": 32, "dns": 64, "drops": 32, "xlat": 56, "quic": 24}
 
 
@@ -62,6 +68,22 @@ def device_parts(m, seed=5):
     return present, parts
 
 
+def set_tls_fields(d_ev, m, seed=7):
+    """ssl_version @132, tls_cipher_suite @134, tls_key_share @136, misc_flags @139 of the evicted records in HBM, on a seeded
+    half of the flows: ids the default table knows and ids it does not, the mismatch flag on a quarter of that half."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    pick = lambda values: torch.tensor(values, dtype=torch.int64, device="cuda")[torch.randint(0, len(values), (m,), device="cuda", generator=g)]  # noqa: E731
+    on = torch.randint(0, 2, (m,), device="cuda", generator=g) == 1
+    v = d_ev[: m * 144].view(m, 144)
+    for col, values in ((132, [0x0303, 0x0304, 0x0304, 0x0200]), (134, [0x1301, 0x1302, 0xc02f, 0xcca8, 0x00ff]), (136, [29, 23, 4588, 0, 30])):
+        w = torch.where(on, pick(values), torch.zeros(m, dtype=torch.int64, device="cuda"))
+        v[:, col] = (w & 0xff).to(torch.uint8)
+        v[:, col + 1] = (w >> 8).to(torch.uint8)
+    v[:, 139] |= (on & (torch.randint(0, 4, (m,), device="cuda", generator=g) == 0)).to(torch.uint8)
+    torch.cuda.synchronize()
+    return int(on.sum())
+
+
 def per_byte(what, m, dt, wrote):
     print(f"  {what:8s} {m} flows -> {wrote} bytes ({wrote / m:.1f} B/line) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s, "
           f"{dt / wrote * 1e12:.3f} ps per output byte")
@@ -85,7 +107,7 @@ def line(what, m, dt, wrote, extra_per_flow):
     return dt
 
 
-for flows in ((10_000_000,) if CONTENT else (1_000_000, 10_000_000)):
+for flows in ((10_000_000,) if CONTENT or TLS else (1_000_000, 10_000_000)):
     n = 4 * flows
     d_th = torch.from_numpy(synth.zipf_thresholds(flows, 1.1).view(np.int64)).cuda()
     d = torch.empty(n * 144, dtype=torch.uint8, device="cuda")
@@ -106,6 +128,20 @@ for flows in ((10_000_000,) if CONTENT else (1_000_000, 10_000_000)):
         (rc, wrote, n_def), dt = timed(lambda: tab.encode_flp_json_device(d_ev.data_ptr(), m, NOW, MONO, names, agent, 1_700_000_000,
                                                                           d_out.data_ptr(), need, d_off.data_ptr(), d_def.data_ptr()))
         assert rc == nf.OK and wrote == need and n_def == 0
+        if TLS:
+            per_byte("no TLS", m, dt, wrote)
+            print(f"           {dt / m * 1e9:.3f} ns per flow")
+            del d_out
+            n_on = set_tls_fields(d_ev, m)
+            with tab.tls_names() as tls:
+                rc, need = tab.encode_flp_json_tls_device(d_ev.data_ptr(), m, tls, NOW, MONO, names, agent, 1_700_000_000, 0, 0, d_off.data_ptr())
+                d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+                (rc, wrote), dt = timed(lambda: tab.encode_flp_json_tls_device(d_ev.data_ptr(), m, tls, NOW, MONO, names, agent, 1_700_000_000,
+                                                                              d_out.data_ptr(), need, d_off.data_ptr()))
+            assert rc == nf.OK and wrote == need
+            per_byte("TLS", m, dt, wrote)
+            print(f"           {dt / m * 1e9:.3f} ns per flow; TLS fields on {n_on} of {m} flows")
+            continue
         if CONTENT:
             per_byte("plain", m, dt, wrote)
             del d_out
