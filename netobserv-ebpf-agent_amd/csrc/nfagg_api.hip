@@ -2202,6 +2202,16 @@ struct nfagg_netev_table {
     void* d_blob = nullptr;
 };
 
+// The TLS name table of nfagg_tls_names_create (nfagg_tls.h):
+// per kind the ids ascending and a 64-byte row per id (length byte, name), on the host and (with a handle) on its device.
+struct nfagg_tls_names {
+    nfagg_handle* h = nullptr;
+    uint32_t n[kTlsKinds] = {};
+    std::vector<uint16_t> ids = std::vector<uint16_t>(kTlsKinds * kTlsMaxRows, 0);
+    std::vector<uint8_t> rows = std::vector<uint8_t>((size_t)kTlsKinds * kTlsMaxRows * kTlsRowBytes, 0);
+    void* d_mem = nullptr;        // the ids, then the rows
+};
+
 // ---- the export encoders' host side: what protobuf, IPFIX and direct-FLP JSON do alike
 namespace {
 
@@ -2572,50 +2582,65 @@ static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, Fl
     return NFAGG_OK;
 }
 
-// feat (optional): DEVICE pointers. Without it the kernels of nfagg_flp.hip run, with it those of nfagg_flp_content.hip;
-// with ne (the *_netev entry points) the latter's instantiations that carry the NetworkEvents hook.
+// The TLS entry points' extra input. With it the three TLS keys are written from the table, no record is deferred (flags and
+// counter are not used), and the network events are an option: rows and table both, or neither (*ne = nullptr).
+struct FlpTlsArgs { const nfagg_tls_names* names; };
+static int netev_optional(nfagg_handle* h, const NetevArgs** ne, size_t n) {
+    if (!*ne) return NFAGG_OK;
+    const NetevArgs& a = **ne;
+    if ((a.rows != nullptr) != (a.table != nullptr) && (n || a.rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
+    if (!a.table) *ne = nullptr;
+    return NFAGG_OK;
+}
+
+// feat (optional): DEVICE pointers. The launchers pick the kernels' feature policy: neither feat nor ne the plain line, ne (the
+// *_netev and *_tls entry points) the one with the NetworkEvents hook, tls the TLS names on top of either.
 static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                                  const nfagg_flp_options* opt,
+                                  const FlpTlsArgs* tls, const nfagg_flp_options* opt,
                                   void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
                                   size_t* n_deferred, size_t* out_bytes) {
-    int rc = encode_flp_check(h, opt);
-    if (rc != NFAGG_OK) return rc;
-    if (!h || !out_bytes || !d_line_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
+    int rc;
+    if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
+    if ((rc = encode_flp_check(h, opt)) != NFAGG_OK) return rc;
+    if (!h || (tls && !tls->names) || !out_bytes || !d_line_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (tls && (tls->names->h != h || !tls->names->d_mem)) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
     PbFeat F{};
     if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
     if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
-    size_t deferred_unused;
-    if (!n_deferred) n_deferred = &deferred_unused;
-    *n_deferred = 0;
+    if (n_deferred) *n_deferred = 0;
     bool done;
     if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
-    auto& S = h->enc;
     FlpParams P{};
     uint32_t* rows;
     if ((rc = stage_flp(h, n, opt, &P, &rows)) != NFAGG_OK) return rc;
-    uint32_t* counter = (uint32_t*)S.flp_n_deferred.p;
-    if (!feat && !ne)
-        return encode_two_pass(h, n, "FLP JSON", "write", d_out, out_cap, out_bytes, n_deferred,
-            [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-                return launch_flp_size(d_records, n, P, rows, local_off, block_sum, block_base, counter, h->stream); },
-            [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-                return launch_flp_write(d_records, n, P, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
-    return encode_two_pass(h, n, "FLP JSON content", "write", d_out, out_cap, out_bytes, n_deferred,
+    uint32_t* counter = (uint32_t*)h->enc.flp_n_deferred.p;
+    TlsDev T{};
+    if (tls) {
+        T.ids = (const uint16_t*)tls->names->d_mem;
+        T.rows = (const uint8_t*)tls->names->d_mem + tls->names->ids.size() * sizeof(uint16_t);
+        for (uint32_t k = 0; k < kTlsKinds; k++) T.n[k] = tls->names->n[k];
+    }
+    const PbFeat* Fp = (feat || ne) ? &F : nullptr;                   // neither: the plain line
+    const TlsDev* Tp = tls ? &T : nullptr;
+    size_t deferred_unused;
+    return encode_two_pass(h, n, tls ? "FLP JSON with TLS names" : Fp ? "FLP JSON content" : "FLP JSON", "write", d_out, out_cap, out_bytes,
+        tls ? nullptr : n_deferred ? n_deferred : &deferred_unused,
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-            return launch_flpc_size(d_records, n, P, F, rows, local_off, block_sum, block_base, counter, h->stream); },
+            return launch_flp_size(d_records, n, P, Fp, Tp, rows, local_off, block_sum, block_base, counter, h->stream); },
         [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-            return launch_flpc_write(d_records, n, P, F, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
+            return launch_flp_write(d_records, n, P, Fp, Tp, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
 }
 
-// feat (optional): HOST pointers, uploaded beside the records
+// feat (optional): HOST pointers, uploaded beside the records, as are the rows of ne
 static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                                const nfagg_flp_options* opt,
+                                const FlpTlsArgs* tls, const nfagg_flp_options* opt,
                                 void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
                                 size_t* n_deferred, size_t* out_bytes) {
     int rc = encode_flp_check(h, opt);
     if (rc != NFAGG_OK) return rc;
-    if (!h || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (!h || (tls && !tls->names) || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
     if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
     return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
         [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
@@ -2623,33 +2648,33 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
             if (feat && n) { int rc2 = stage_pb_features(h, feat, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
             NetevArgs dne{};
             if (ne) { int rc2 = stage_netev_rows(h, ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
-            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, opt, d_out, out_cap, d_offsets,
+            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, tls, opt, d_out, out_cap, d_offsets,
                                           deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
 }
 
 int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
                                  size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_device_core(h, d_records, n, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+    return encode_flp_device_core(h, d_records, n, nullptr, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
                           void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
                           size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_host_core(h, records, n, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+    return encode_flp_host_core(h, records, n, nullptr, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
 
 // features == NULL: the flows carry no parts, the call is nfagg_encode_flp_json[_device]
 int nfagg_encode_flp_json_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                          const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
                                          uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_device_core(h, d_records, n, d_features, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+    return encode_flp_device_core(h, d_records, n, d_features, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
                                   const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
                                   uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_host_core(h, records, n, features, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+    return encode_flp_host_core(h, records, n, features, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
@@ -2657,7 +2682,7 @@ int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_re
                                                const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
                                                uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
     const NetevArgs ne{d_rows, table};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
@@ -2665,7 +2690,7 @@ int nfagg_encode_flp_json_content_netev(nfagg_handle* h, const void* records, si
                                         const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
                                         uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
     const NetevArgs ne{rows, table};
-    return encode_flp_host_core(h, records, n, features, &ne, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+    return encode_flp_host_core(h, records, n, features, &ne, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
 
 }  // extern "C"
@@ -2908,15 +2933,6 @@ int nfagg_netev_resolve(nfagg_handle* h, const nfagg_netev_table* table, const u
 }  // extern "C"
 
 // ---- TLS names: the caller's table (nfagg_tls.h) and the direct-FLP entry points that write the three keys
-// Per kind the ids ascending and a 64-byte row per id (length byte, name), on the host and (with a handle) on its device.
-struct nfagg_tls_names {
-    nfagg_handle* h = nullptr;
-    uint32_t n[kTlsKinds] = {};
-    std::vector<uint16_t> ids = std::vector<uint16_t>(kTlsKinds * kTlsMaxRows, 0);
-    std::vector<uint8_t> rows = std::vector<uint8_t>((size_t)kTlsKinds * kTlsMaxRows * kTlsRowBytes, 0);
-    void* d_mem = nullptr;        // the ids, then the rows
-};
-
 extern "C" {
 
 int nfagg_tls_names_create(nfagg_handle* h, const nfagg_tls_name_entry* entries, size_t n, nfagg_tls_names** table) {
@@ -3003,60 +3019,20 @@ int nfagg_tls_names_render(const nfagg_tls_names* t, int kind, uint16_t id, int 
 
 uint32_t nfagg_flp_json_tls_max_line(int policy) { return flp_tls_max_line(policy); }
 
-static int encode_flp_tls_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                                      const nfagg_tls_names* tls, const nfagg_flp_options* opt, void* d_out, size_t out_cap,
-                                      uint64_t* d_line_offsets, size_t* out_bytes) {
-    int rc = encode_flp_check(h, opt);
-    if (rc != NFAGG_OK) return rc;
-    if (!h || !tls || !out_bytes || !d_line_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
-    if (tls->h != h || !tls->d_mem) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
-    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
-    PbFeat F{};
-    if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
-    if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
-    bool done;
-    if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
-    FlpParams P{};
-    uint32_t* rows;
-    if ((rc = stage_flp(h, n, opt, &P, &rows)) != NFAGG_OK) return rc;
-    TlsDev T{};
-    T.ids = (const uint16_t*)tls->d_mem;
-    T.rows = (const uint8_t*)tls->d_mem + tls->ids.size() * sizeof(uint16_t);
-    for (uint32_t k = 0; k < kTlsKinds; k++) T.n[k] = tls->n[k];
-    const PbFeat* Fp = (feat || ne) ? &F : nullptr;                   // neither: the plain line
-    return encode_two_pass(h, n, "FLP JSON with TLS names", "write", d_out, out_cap, out_bytes, nullptr,
-        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-            return launch_flpt_size(d_records, n, P, Fp, T, rows, local_off, block_sum, block_base, h->stream); },
-        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-            return launch_flpt_write(d_records, n, P, Fp, T, rows, local_off, block_base, d_out, d_line_offsets, h->stream); });
-}
-
 int nfagg_encode_flp_json_tls_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                      const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
                                      const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
-    if ((d_rows != nullptr) != (netev_table != nullptr) && (n || d_rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
     const NetevArgs ne{d_rows, netev_table};
-    return encode_flp_tls_device_core(h, d_records, n, d_features, netev_table ? &ne : nullptr, tls_names, opt, d_out, out_cap, d_line_offsets, out_bytes);
+    const FlpTlsArgs tls{tls_names};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
 }
 
 int nfagg_encode_flp_json_tls(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
                               const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
                               const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
-    int rc = encode_flp_check(h, opt);
-    if (rc != NFAGG_OK) return rc;
-    if (!h || !tls_names || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
-    if ((rows != nullptr) != (netev_table != nullptr) && (n || rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
-    if (features && features->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
     const NetevArgs ne{rows, netev_table};
-    return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {},
-        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
-            nfagg_pb_features dfeat{};
-            dfeat.struct_size = sizeof dfeat;
-            if (features && n) { int rc2 = stage_pb_features(h, features, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
-            NetevArgs dne{};
-            if (netev_table) { int rc2 = stage_netev_rows(h, &ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
-            return encode_flp_tls_device_core(h, d_records, n, features ? &dfeat : nullptr, netev_table ? &dne : nullptr, tls_names, opt, d_out,
-                                              out_cap, d_offsets, out_bytes); });
+    const FlpTlsArgs tls{tls_names};
+    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// nfagg_flp.h — launch interface of the record -> direct-FLP JSON line kernels (nfagg_flp.hip, nfagg_flp_content.hip).
+// nfagg_flp.h — launch interface of the record -> direct-FLP JSON line kernels (nfagg_flp_line.h; nfagg_flp.hip, nfagg_flp_content.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,28 +37,17 @@ struct TlsDev {
 };
 
 // Line lengths (0 = deferred) and the seven resolved interface rows per record (d_rows: 8 dwords per record, rows 0..6
-// and the length), block-local scan, scan of the block sums: d_block_base[ceil(n / 1024)] = total bytes afterwards.
-// *d_n_deferred (zeroed by the caller) counts the deferred records.
-hipError_t launch_flp_size(const void* d_recs, uint64_t n, const FlpParams& P, uint32_t* d_rows, uint32_t* d_local_off,
-                           uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s);
-hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, const uint32_t* d_rows, const uint32_t* d_local_off,
-                            const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, uint8_t* d_deferred, hipStream_t s);
-
-// The same two passes over full BpfFlowContents (nfagg_flp_content.hip): F names the flows' feature parts as it does for the
-// protobuf encoder. Same scratch, same outputs.
-hipError_t launch_flpc_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, uint32_t* d_rows, uint32_t* d_local_off,
-                            uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s);
-hipError_t launch_flpc_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const uint32_t* d_rows,
-                             const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
-                             uint8_t* d_deferred, hipStream_t s);
-
-// The same two passes with the TLS names on (nfagg_encode_flp_json_tls): TLSVersion, TLSCipherSuite and TLSGroup are looked up
-// in T and written, no record is deferred. Policy: F == nullptr the line of launch_flp_*, else that of launch_flpc_*.
-hipError_t launch_flpt_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, uint32_t* d_rows,
-                            uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s);
-hipError_t launch_flpt_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const uint32_t* d_rows,
-                             const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s);
-// The longest line each of those policies can write (0: plain, 1: content, 2: content with network events).
+// and the length), block-local scan, scan of the block sums: d_block_base[ceil(n / 1024)] = total bytes afterwards. Then the
+// write pass. F (optional) names the feature parts of full BpfFlowContents as it does for the protobuf encoder; with
+// F->ne_rows the line carries the flows' network events. T (optional): TLSVersion, TLSCipherSuite and TLSGroup are looked up in
+// it and written. Without T a record that has them is deferred: no line, d_deferred[i] = 1 (where given), counted in
+// *d_n_deferred (zeroed by the caller); with T neither is touched.
+hipError_t launch_flp_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev* T, uint32_t* d_rows,
+                           uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s);
+hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev* T, const uint32_t* d_rows,
+                            const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
+                            uint8_t* d_deferred, hipStream_t s);
+// The longest line each policy can write with T (0: plain, 1: content, 2: content with network events).
 uint32_t flp_tls_max_line(int policy);
 
 }  // namespace nfagg

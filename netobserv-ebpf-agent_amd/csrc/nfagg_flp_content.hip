@@ -14,8 +14,9 @@
 // injected. With one (FlpContentNetev) the line carries the rendered objects of the rows nfagg_netev_resolve found; the
 // drop it injected arrives in the drops part like any other.
 //
-// Same two passes, same window scheme and the same encode_line as nfagg_flp.hip, with FlpContent as its feature policy;
-// the kernels are separate so that the Accounter path keeps its code and its registers. A lane reads the parts its
+// Same two passes, same window scheme, same encode_line and the same two kernels as nfagg_flp.hip (k_flp_size<Feat>,
+// k_flp_write<Feat> of nfagg_flp_line.h), with FlpContent as the feature policy: this file compiles them for FlpContent,
+// FlpContentNetev and FlpTls (nfagg_tls.h) over those two and over FlpPlain, and selects. A lane reads the parts its
 // present byte names with 16- and 8-byte loads before anything is emitted, keeps the fields the line needs in registers
 // and the DNS name in a 32-byte LDS slot of its own. The names of response codes, TCP states and drop causes sit in one
 // constant blob with an offset and a length per name; the counting pass reads only the lengths.
@@ -169,7 +170,8 @@ static_assert(kFlpnLds + kFlpcNameLds <= 32768 && kFlpnWindow >= 16384, "four wa
 // The feature parts of one flow, as encode_line's feature policy. load() reads the parts that are present (array given
 // and the flow's present byte has the bit) and nothing of the others.
 struct FlpContent {
-    static constexpr uint32_t kWindow = kFlpcWindow, kLds = kFlpcLds;
+    static constexpr uint32_t kWindow = kFlpcWindow, kLds = kFlpcLds, kSideLds = kFlpcNameLds, kMaxLine = kFlpcMaxLine - kFlpcLineUnreached;
+    static constexpr bool kDefers = true;
     uint32_t have = 0;          // NFAGG_FEAT_* bits of the parts that were loaded
     uint32_t add[4] = {};       // additional_metrics @16: flow_rtt (2), ipsec_encrypted_ret, eth | ipsec_encrypted << 16
     uint32_t dnsw[4] = {};      // dns_metrics @16: latency (2), id | flags << 16, eth | errno << 16 | name[0] << 24
@@ -282,7 +284,7 @@ struct FlpContent {
 // FlpContent plus the flow's network events: the table rows nfagg_netev_resolve wrote (PbFeat::ne_rows), each row's JSON
 // object rendered once on the host (nfagg_netev.h). The counting pass reads only the lengths.
 struct FlpContentNetev : FlpContent {
-    static constexpr uint32_t kWindow = kFlpnWindow, kLds = kFlpnLds;
+    static constexpr uint32_t kWindow = kFlpnWindow, kLds = kFlpnLds, kMaxLine = kFlpnMaxLine - kFlpcLineUnreached;
     uint32_t ev[4] = {kNetevNoRow, kNetevNoRow, kNetevNoRow, kNetevNoRow};
     const uint8_t* ne_tab = nullptr;
     const uint8_t* ne_blob = nullptr;
@@ -307,216 +309,30 @@ struct FlpContentNetev : FlpContent {
     }
 };
 
-// ---- kernel 1: as k_flp_size, the line measured with the flow's feature parts (Feat: FlpContent or FlpContentNetev)
-template <typename Feat>
-__global__ __launch_bounds__(kScanBlock) void k_flpc_size(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F,
-                                                          uint32_t* __restrict__ rows, uint32_t* __restrict__ local_off,
-                                                          uint32_t* __restrict__ block_sum, uint32_t* __restrict__ n_deferred) {
-    __shared__ uint32_t wave_tot[kScanBlock / 64];
-    __shared__ __align__(16) uint8_t name_lds[kScanBlock][32];
-    __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
-    const uint8_t* tab = stage_names<kScanBlock>(P.names, P.n_names, tab_lds);
-    const uint64_t i = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    uint32_t len = 0;
-    bool deferred = false;
-    if (i < n) {
-        Rec r;
-        load_record(recs, i, r);
-        uint32_t row[7];
-        flp_rows(tab, P.n_names, r, row);
-        deferred = flp_deferred(r);
-        if (!deferred) {
-            Feat f;
-            f.load(F, i, name_lds[threadIdx.x]);
-            CountSink c;
-            encode_line(c, r, P, row, f);
-            len = c.n;
-        }
-        uint4* o = reinterpret_cast<uint4*>(rows + i * 8);
-        o[0] = make_uint4(row[0], row[1], row[2], row[3]);
-        o[1] = make_uint4(row[4], row[5], row[6], len);
-    }
-    const int lane = threadIdx.x & 63;
-    const uint64_t dm = __ballot(deferred);
-    if (lane == 0 && dm) atomicAdd(n_deferred, (uint32_t)__popcll(dm));
-    block_scan(len, i, n, wave_tot, local_off, block_sum);
+// ---- the launchers. The policy a call selects: F == nullptr the plain line, F->ne_rows network events, T the TLS names.
+template <typename Feat> struct FlpPolicy { using type = Feat; };
+template <typename Fn> static hipError_t flp_select(const PbFeat* F, const TlsDev* T, Fn fn) {
+    if (T) return !F ? fn(FlpPolicy<FlpTls<FlpPlain>>{}) : F->ne_rows ? fn(FlpPolicy<FlpTls<FlpContentNetev>>{}) : fn(FlpPolicy<FlpTls<FlpContent>>{});
+    return !F ? fn(FlpPolicy<FlpPlain>{}) : F->ne_rows ? fn(FlpPolicy<FlpContentNetev>{}) : fn(FlpPolicy<FlpContent>{});
 }
 
-// ---- kernel 3: as k_flp_write, windows of Feat::kWindow bytes (the DNS name slots take 2 KiB of the 32 KiB)
-template <typename Feat>
-__global__ __launch_bounds__(64) void k_flpc_write(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F,
-                                                   const uint32_t* __restrict__ rows, const uint32_t* __restrict__ local_off,
-                                                   const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
-                                                   uint64_t* __restrict__ line_offsets, uint8_t* __restrict__ deferred) {
-    __shared__ __align__(16) uint8_t lds[Feat::kLds];
-    __shared__ __align__(16) uint8_t name_lds[64][32];
-    const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
-    WaveImage w(block_base, local_off, i0);
-    uint64_t my_off = 0; uint32_t my_len = 0;
-    uint32_t row[7] = {};
-    Rec r;
-    Feat f;
-    if (i < n) {
-        load_record(recs, i, r);
-        const uint4* q = reinterpret_cast<const uint4*>(rows + i * 8);
-        const uint4 a = q[0], b = q[1];
-        row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w; row[4] = b.x; row[5] = b.y; row[6] = b.z;
-        my_len = b.w;
-        if (my_len) f.load(F, i, name_lds[threadIdx.x]);              // a deferred record's parts are not read
-        my_off = record_off(block_base, local_off, i);
-        line_offsets[i] = my_off;
-        if (i == n - 1) line_offsets[n] = my_off + my_len;
-        if (deferred) deferred[i] = my_len == 0 ? 1 : 0;     // every line that is written has at least its braces
-    }
-    w.close(my_off + my_len, out);
-    const uint32_t p0 = w.pos(my_off);                            // my line = image bytes [p0, p0 + my_len)
-    uint32_t lo = w.shift;
-    while (lo < w.span) {
-        const uint32_t base = lo & ~15u;
-        const bool mine = my_len && p0 >= lo && p0 - base < Feat::kWindow;
-        if (mine) { FlpLds s{lds + (p0 - base)}; encode_line(s, r, P, row, f); }
-        uint32_t hi = mine ? p0 + my_len : lo;                  // the window's end: at most base + the window + the longest line
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(hi, d, 64); hi = o > hi ? o : hi; }
-        __syncthreads();
-        copy_image_out(w.dst, lds, base, lo, hi);
-        __syncthreads();
-        lo = hi;
-    }
+hipError_t launch_flp_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev* T, uint32_t* d_rows,
+                           uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s) {
+    return flp_select(F, T, [&](auto policy) {
+        return flp_size_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T ? *T : TlsDev{}, d_rows, d_local_off, d_block_sum,
+                                                            d_block_base, d_n_deferred, s); });
 }
 
-hipError_t launch_flpc_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, uint32_t* d_rows, uint32_t* d_local_off,
-                            uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s) {
-    const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
-    (void)hipGetLastError();
-    if (F.ne_rows) hipLaunchKernelGGL(k_flpc_size<FlpContentNetev>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_sum, d_n_deferred);
-    else hipLaunchKernelGGL(k_flpc_size<FlpContent>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_sum, d_n_deferred);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
-}
-
-hipError_t launch_flpc_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const uint32_t* d_rows,
-                             const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
-                             uint8_t* d_deferred, hipStream_t s) {
-    (void)hipGetLastError();
-    const dim3 grid((unsigned)((n + 63) / 64));
-    if (F.ne_rows) hipLaunchKernelGGL(k_flpc_write<FlpContentNetev>, grid, dim3(64), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_base,
-                                      (uint8_t*)d_out, d_line_offsets, d_deferred);
-    else hipLaunchKernelGGL(k_flpc_write<FlpContent>, grid, dim3(64), 0, s, d_recs, n, P, F, d_rows, d_local_off, d_block_base,
-                            (uint8_t*)d_out, d_line_offsets, d_deferred);
-    return hipGetLastError();
-}
-
-// ---- the three policies with the TLS names on (nfagg_encode_flp_json_tls): FlpTls over the plain line, over FlpContent and
-// over FlpContentNetev. Kernels of their own, so that the six above keep their code and their registers; no record is
-// deferred, so there is neither a flag nor a counter. Their longest lines are the ones that are reached (nfagg_tls.h).
-struct FlpPlainT : NoFeat {
-    static constexpr uint32_t kMaxLine = kFlpMaxLine - kFlpLineUnreached, kSideLds = 16;      // no DNS name slots: one unused chunk
-    NF_DEV void load(const PbFeat&, uint64_t, uint8_t*) {}
-};
-struct FlpContentT : FlpContent { static constexpr uint32_t kMaxLine = kFlpcMaxLine - kFlpcLineUnreached, kSideLds = kFlpcNameLds; };
-struct FlpContentNetevT : FlpContentNetev { static constexpr uint32_t kMaxLine = kFlpnMaxLine - kFlpcLineUnreached, kSideLds = kFlpcNameLds; };
-
-template <typename Feat>
-__global__ __launch_bounds__(kScanBlock) void k_flpt_size(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T,
-                                                          uint32_t* __restrict__ rows, uint32_t* __restrict__ local_off,
-                                                          uint32_t* __restrict__ block_sum) {
-    constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;       // a DNS name slot per lane where the policy reads one
-    __shared__ uint32_t wave_tot[kScanBlock / 64];
-    __shared__ __align__(16) uint8_t name_lds[kSlot ? kScanBlock * kSlot : 16];
-    __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
-    const uint8_t* tab = stage_names<kScanBlock>(P.names, P.n_names, tab_lds);
-    const uint64_t i = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    uint32_t len = 0;
-    if (i < n) {
-        Rec r;
-        load_record(recs, i, r);
-        uint32_t row[7];
-        flp_rows(tab, P.n_names, r, row);
-        Feat f;
-        f.load(F, i, name_lds + threadIdx.x * kSlot);
-        f.tls = T;
-        CountSink c;
-        encode_line(c, r, P, row, f);
-        len = c.n;
-        uint4* o = reinterpret_cast<uint4*>(rows + i * 8);
-        o[0] = make_uint4(row[0], row[1], row[2], row[3]);
-        o[1] = make_uint4(row[4], row[5], row[6], len);
-    }
-    block_scan(len, i, n, wave_tot, local_off, block_sum);
-}
-
-template <typename Feat>
-__global__ __launch_bounds__(64) void k_flpt_write(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T,
-                                                   const uint32_t* __restrict__ rows, const uint32_t* __restrict__ local_off,
-                                                   const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
-                                                   uint64_t* __restrict__ line_offsets) {
-    constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;
-    static_assert(Feat::kLds + Feat::kSideLds <= 32768, "four waves per compute unit");
-    __shared__ __align__(16) uint8_t lds[Feat::kLds];
-    __shared__ __align__(16) uint8_t name_lds[Feat::kSideLds];
-    const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
-    WaveImage w(block_base, local_off, i0);
-    uint64_t my_off = 0; uint32_t my_len = 0;
-    uint32_t row[7] = {};
-    Rec r;
-    Feat f;
-    f.tls = T;
-    if (i < n) {
-        load_record(recs, i, r);
-        const uint4* q = reinterpret_cast<const uint4*>(rows + i * 8);
-        const uint4 a = q[0], b = q[1];
-        row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w; row[4] = b.x; row[5] = b.y; row[6] = b.z;
-        my_len = b.w;                                                 // every line has at least its braces
-        f.load(F, i, name_lds + threadIdx.x * kSlot);
-        my_off = record_off(block_base, local_off, i);
-        line_offsets[i] = my_off;
-        if (i == n - 1) line_offsets[n] = my_off + my_len;
-    }
-    w.close(my_off + my_len, out);
-    const uint32_t p0 = w.pos(my_off);                            // my line = image bytes [p0, p0 + my_len)
-    uint32_t lo = w.shift;
-    while (lo < w.span) {
-        const uint32_t base = lo & ~15u;
-        const bool mine = my_len && p0 >= lo && p0 - base < Feat::kWindow;
-        if (mine) { FlpLds s{lds + (p0 - base)}; encode_line(s, r, P, row, f); }
-        uint32_t hi = mine ? p0 + my_len : lo;                  // the window's end: at most base + Feat::kWindow + Feat::kMaxLine
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(hi, d, 64); hi = o > hi ? o : hi; }
-        __syncthreads();
-        copy_image_out(w.dst, lds, base, lo, hi);
-        __syncthreads();
-        lo = hi;
-    }
-}
-
-hipError_t launch_flpt_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, uint32_t* d_rows,
-                            uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s) {
-    const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
-    const dim3 grid(blocks), block(kScanBlock);
-    (void)hipGetLastError();
-    if (!F) hipLaunchKernelGGL(k_flpt_size<FlpTls<FlpPlainT>>, grid, block, 0, s, d_recs, n, P, PbFeat{}, T, d_rows, d_local_off, d_block_sum);
-    else if (F->ne_rows) hipLaunchKernelGGL(k_flpt_size<FlpTls<FlpContentNetevT>>, grid, block, 0, s, d_recs, n, P, *F, T, d_rows, d_local_off, d_block_sum);
-    else hipLaunchKernelGGL(k_flpt_size<FlpTls<FlpContentT>>, grid, block, 0, s, d_recs, n, P, *F, T, d_rows, d_local_off, d_block_sum);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
-}
-
-hipError_t launch_flpt_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const uint32_t* d_rows,
-                             const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s) {
-    (void)hipGetLastError();
-    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
-    uint8_t* out = (uint8_t*)d_out;
-    if (!F) hipLaunchKernelGGL(k_flpt_write<FlpTls<FlpPlainT>>, grid, block, 0, s, d_recs, n, P, PbFeat{}, T, d_rows, d_local_off, d_block_base, out, d_line_offsets);
-    else if (F->ne_rows) hipLaunchKernelGGL(k_flpt_write<FlpTls<FlpContentNetevT>>, grid, block, 0, s, d_recs, n, P, *F, T, d_rows, d_local_off, d_block_base, out, d_line_offsets);
-    else hipLaunchKernelGGL(k_flpt_write<FlpTls<FlpContentT>>, grid, block, 0, s, d_recs, n, P, *F, T, d_rows, d_local_off, d_block_base, out, d_line_offsets);
-    return hipGetLastError();
+hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev* T, const uint32_t* d_rows,
+                            const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
+                            uint8_t* d_deferred, hipStream_t s) {
+    return flp_select(F, T, [&](auto policy) {
+        return flp_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T ? *T : TlsDev{}, d_rows, d_local_off, d_block_base,
+                                                             d_out, d_line_offsets, d_deferred, s); });
 }
 
 uint32_t flp_tls_max_line(int policy) {
-    return policy == 0 ? FlpTls<FlpPlainT>::kMaxLine : policy == 1 ? FlpTls<FlpContentT>::kMaxLine : policy == 2 ? FlpTls<FlpContentNetevT>::kMaxLine : 0u;
+    return policy == 0 ? FlpTls<FlpPlain>::kMaxLine : policy == 1 ? FlpTls<FlpContent>::kMaxLine : policy == 2 ? FlpTls<FlpContentNetev>::kMaxLine : 0u;
 }
 
 }  // namespace nfagg

@@ -1,7 +1,9 @@
-// nfagg_flp_line.h — the direct-FLP JSON line encoder the two pairs of kernels share (nfagg_flp.hip: records that carry
-// only BpfFlowMetrics; nfagg_flp_content.hip: full BpfFlowContents): sinks, numbers, addresses, MACs, the escaped names,
-// and encode_line itself. Device code only.
+// nfagg_flp_line.h — the direct-FLP JSON line encoder and the one pair of kernels that runs it: sinks, numbers, addresses,
+// MACs, the escaped names, encode_line, the feature-policy contract, k_flp_size<Feat> and k_flp_write<Feat>. nfagg_flp.hip
+// instantiates the pair for records that carry only BpfFlowMetrics, nfagg_flp_content.hip for full BpfFlowContents and for
+// the lines with TLS names. Device code only.
 #pragma once
+#include <type_traits>
 #include "nfagg_encode.h"
 #include "nfagg_flp.h"
 
@@ -9,6 +11,16 @@ namespace nfagg {
 
 // keys, punctuation and numbers of a line with every optional key: 618 bytes; seven directions, names and UDNs on top
 constexpr uint32_t kFlpMaxLine = 700 + 7 * (4 + kFlpEscNameMax + 1 + kFlpEscUdnMax + 1);
+constexpr uint32_t kFlpWindow = 28672;                       // line starts a window takes, from its aligned base
+constexpr uint32_t kFlpLds = kFlpWindow + (kFlpMaxLine + 15) / 16 * 16;
+static_assert(kFlpLds <= 32768, "four waves per compute unit");
+
+// kFlpMaxLine counts bytes that no line has: its 700 stands for 618; each of the three lists has one comma fewer than
+// entries; TimeFlowEndMs and TimeFlowStartMs have at most 15 characters, not 20 (the seconds of time.Time.Add over two
+// int64 nanosecond counts stay within +-1.85e10); Flags is written for protocol 6 alone, whose Proto has one digit, not
+// three. kFlpcKeysMax (nfagg_flp_content.hip) counts IPSecRetCode at its longest (27) together with
+// "success" (24): the longest pair is the error one, 27 + 22. Without them the maximum is reached.
+constexpr uint32_t kFlpLineUnreached = (700 - 618) + 3 + 2 * (20 - 15) + 2, kFlpcLineUnreached = kFlpLineUnreached + 2;
 
 // ---- sinks: CountSink (nfagg_encode.h) only measures, FlpLds writes through a pointer
 struct FlpLds {
@@ -162,6 +174,18 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
 // every hook is empty and the line is the one of decode_protobuf.go:57-127. FlpContent (nfagg_flp_content.hip) holds
 // the parts of a full BpfFlowContent, FlpContentNetev adds the flow's resolved network events. The two TLS hooks take the
 // record: they are empty in all three, and a record that would need them is deferred; FlpTls (nfagg_tls.h) fills them.
+//
+// What k_flp_size<Feat> and k_flp_write<Feat> ask of a policy beside the hooks, all of it known when they are compiled:
+//   kWindow   line starts a window of the write kernel takes, from its 16-byte aligned base
+//   kLds      the window's LDS: kWindow plus the longest line, rounded up to 16
+//   kSideLds  the LDS a wave holds beside the window: 64 x 32 for a DNS name slot per lane; 0 or 16 for none
+//   kDefers   a record with TLS names (flp_deferred) gets no line, is flagged and counted; false: the policy has a member
+//             `tls` that takes the kernel's TLS name table, and the record is written
+//   kMaxLine  the longest line the policy reaches; FlpTls sizes its window from it
+//   load(F, i, slot)   reads record i's feature parts, only for a line that is measured or written
+// A policy without data members (FlpPlain) is not asked to load: handing the kernel's F to an empty function by reference is
+// enough to change the register allocation of k_flp_write<FlpPlain> (530 instructions more). The table is
+// assigned, not handed to a setter, for the same reason.
 struct NoFeat {
     template <typename S> NF_DEV void dns(S&) const {}        // Dns*          after Bytes
     template <typename S> NF_DEV void ipsec(S&) const {}      // IPSec*        after Flags
@@ -174,11 +198,17 @@ struct NoFeat {
     template <typename S> NF_DEV void tls_names(S&, const Rec&) const {}     // TLSCipherSuite TLSGroup  after SrcPort
     template <typename S> NF_DEV void tls_version(S&, const Rec&) const {}   // TLSVersion               after TLSTypes
 };
+// The plain policy: the line of the records Accounter.evict produces.
+struct FlpPlain : NoFeat {
+    static constexpr uint32_t kWindow = kFlpWindow, kLds = kFlpLds, kSideLds = 0, kMaxLine = kFlpMaxLine - kFlpLineUnreached;
+    static constexpr bool kDefers = true;
+    NF_DEV void load(const PbFeat&, uint64_t, uint8_t*) {}       // for FlpTls<FlpPlain>, which is not empty
+};
 
-// One line. Same code measures (CountSink) and writes (FlpLds). The policy travels by value: a reference to an empty NoFeat
-// is enough to change the register allocation of k_flp_write.
-template <typename S, typename F = NoFeat>
-NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (&row)[7], F f = F{}) {
+// One line. Same code measures (CountSink) and writes (FlpLds). The policy travels by value: a reference to an empty policy
+// is enough to change the register allocation of k_flp_write<FlpPlain>.
+template <typename S, typename F>
+NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (&row)[7], F f) {
     const uint32_t eth = r.eth(), proto = r.d[9] & 0xffu;
     const bool ip = eth == 0x0800u || eth == 0x86DDu;
     const bool icmp = ip && (proto == 1 || proto == 58), ports = ip && (proto == 6 || proto == 17 || proto == 132);
@@ -262,5 +292,123 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
     f.zone(s);
     lit(s, "}\n");
 }
+
+// ---- kernel 1: line length per record (the seven interface rows resolved once), block-local exclusive scan. rows: 8 dwords
+// per record, rows 0..6 and the length (0 = deferred).
+template <typename Feat>
+__global__ __launch_bounds__(kScanBlock) void k_flp_size(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T,
+                                                         uint32_t* __restrict__ rows, uint32_t* __restrict__ local_off,
+                                                         uint32_t* __restrict__ block_sum, uint32_t* __restrict__ n_deferred) {
+    constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;       // a DNS name slot per lane where the policy reads one
+    constexpr bool kHolds = !std::is_empty_v<Feat>;                      // the policy has members to fill
+    __shared__ uint32_t wave_tot[kScanBlock / 64];
+    __shared__ __align__(16) uint8_t name_lds[kSlot ? kScanBlock * kSlot : 16];
+    __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
+    const uint8_t* tab = stage_names<kScanBlock>(P.names, P.n_names, tab_lds);
+    const uint64_t i = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x;
+    uint32_t len = 0;
+    bool deferred = false;
+    if (i < n) {
+        Rec r;
+        load_record(recs, i, r);
+        uint32_t row[7];
+        flp_rows(tab, P.n_names, r, row);
+        if constexpr (Feat::kDefers) deferred = flp_deferred(r);
+        if (!deferred) {
+            Feat f;
+            if constexpr (kHolds) f.load(F, i, name_lds + threadIdx.x * kSlot);
+            if constexpr (!Feat::kDefers) f.tls = T;
+            CountSink c;
+            encode_line(c, r, P, row, f);
+            len = c.n;
+        }
+        uint4* o = reinterpret_cast<uint4*>(rows + i * 8);
+        o[0] = make_uint4(row[0], row[1], row[2], row[3]);
+        o[1] = make_uint4(row[4], row[5], row[6], len);
+    }
+    if constexpr (Feat::kDefers) {
+        const int lane = threadIdx.x & 63;
+        const uint64_t dm = __ballot(deferred);
+        if (lane == 0 && dm) atomicAdd(n_deferred, (uint32_t)__popcll(dm));
+    }
+    block_scan(len, i, n, wave_tot, local_off, block_sum);
+}
+
+// ---- kernel 3: write. One wave per 64 consecutive records; their lines are contiguous in the output. The wave moves a
+// window along its byte range [shift, span) of the image: a window starts at a line start `lo`, takes every line that
+// starts less than Feat::kWindow bytes behind its 16-byte aligned base, and ends where the last of them ends, so a line is
+// always written whole (the buffer has the longest line's bytes of slack) and exactly once.
+template <typename Feat>
+__global__ __launch_bounds__(64) void k_flp_write(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T,
+                                                  const uint32_t* __restrict__ rows, const uint32_t* __restrict__ local_off,
+                                                  const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
+                                                  uint64_t* __restrict__ line_offsets, uint8_t* __restrict__ deferred) {
+    constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;
+    constexpr bool kHolds = !std::is_empty_v<Feat>;
+    static_assert(Feat::kLds + Feat::kSideLds <= 32768, "four waves per compute unit");
+    __shared__ __align__(16) uint8_t lds[Feat::kLds];
+    __shared__ __align__(16) uint8_t name_lds[kSlot ? 64 * kSlot : 16];
+    const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
+    WaveImage w(block_base, local_off, i0);
+    uint64_t my_off = 0; uint32_t my_len = 0;
+    uint32_t row[7] = {};
+    Rec r;
+    Feat f;
+    if constexpr (!Feat::kDefers) f.tls = T;
+    if (i < n) {
+        load_record(recs, i, r);
+        const uint4* q = reinterpret_cast<const uint4*>(rows + i * 8);
+        const uint4 a = q[0], b = q[1];
+        row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w; row[4] = b.x; row[5] = b.y; row[6] = b.z;
+        my_len = b.w;                                                 // every line that is written has at least its braces
+        if constexpr (kHolds) { if (!Feat::kDefers || my_len) f.load(F, i, name_lds + threadIdx.x * kSlot); }     // a deferred record's parts are not read
+        my_off = record_off(block_base, local_off, i);
+        line_offsets[i] = my_off;
+        if (i == n - 1) line_offsets[n] = my_off + my_len;
+        if constexpr (Feat::kDefers) { if (deferred) deferred[i] = my_len == 0 ? 1 : 0; }
+    }
+    w.close(my_off + my_len, out);
+    const uint32_t p0 = w.pos(my_off);                            // my line = image bytes [p0, p0 + my_len)
+    uint32_t lo = w.shift;
+    while (lo < w.span) {
+        const uint32_t base = lo & ~15u;
+        const bool mine = my_len && p0 >= lo && p0 - base < Feat::kWindow;
+        if (mine) { FlpLds s{lds + (p0 - base)}; encode_line(s, r, P, row, f); }
+        uint32_t hi = mine ? p0 + my_len : lo;                  // the window's end: at most base + the window + the longest line
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(hi, d, 64); hi = o > hi ? o : hi; }
+        __syncthreads();
+        copy_image_out(w.dst, lds, base, lo, hi);
+        __syncthreads();
+        lo = hi;
+    }
+}
+
+// The two launches for one policy. Each instantiation lives in one translation unit: the plain one in nfagg_flp.hip (declared
+// below, so that no other file compiles it), the others in nfagg_flp_content.hip, where launch_flp_size / launch_flp_write select.
+template <typename Feat>
+__attribute__((noinline)) hipError_t flp_size_as(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const TlsDev& T,
+                                                 uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base,
+                                                 uint32_t* d_n_deferred, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_flp_size<Feat>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, T, d_rows, d_local_off, d_block_sum, d_n_deferred);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
+}
+template <typename Feat>
+__attribute__((noinline)) hipError_t flp_write_as(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const TlsDev& T,
+                                                  const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base,
+                                                  void* d_out, uint64_t* d_line_offsets, uint8_t* d_deferred, hipStream_t s) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_flp_write<Feat>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_recs, n, P, F, T, d_rows, d_local_off,
+                       d_block_base, (uint8_t*)d_out, d_line_offsets, d_deferred);
+    return hipGetLastError();
+}
+extern template hipError_t flp_size_as<FlpPlain>(const void*, uint64_t, const FlpParams&, const PbFeat&, const TlsDev&, uint32_t*, uint32_t*,
+                                                 uint32_t*, uint64_t*, uint32_t*, hipStream_t);
+extern template hipError_t flp_write_as<FlpPlain>(const void*, uint64_t, const FlpParams&, const PbFeat&, const TlsDev&, const uint32_t*,
+                                                  const uint32_t*, const uint64_t*, void*, uint64_t*, uint8_t*, hipStream_t);
 
 }  // namespace nfagg

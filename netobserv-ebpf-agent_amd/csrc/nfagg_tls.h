@@ -15,13 +15,6 @@ constexpr uint32_t kTlsLineMax = (sizeof(",\"TLSCipherSuite\":\"\"") - 1) + (siz
                                  3 * NFAGG_TLS_NAME_MAX;
 static_assert(kTlsLineMax == (20 + 14 + 16 + 2) + 3 * 63 && NFAGG_TLS_NAME_MAX >= sizeof("CurveID(65535)") - 1, "TLS keys");
 
-// kFlpMaxLine counts bytes that no line has: its 700 stands for 618; each of the three lists has one comma fewer than
-// entries; TimeFlowEndMs and TimeFlowStartMs have at most 15 characters, not 20 (the seconds of time.Time.Add over two
-// int64 nanosecond counts stay within +-1.85e10); Flags is written for protocol 6 alone, whose Proto has one digit, not
-// three. kFlpcKeysMax counts IPSecRetCode at its longest (27) together with
-// "success" (24): the longest pair is the error one, 27 + 22. Without them the maximum is reached.
-constexpr uint32_t kFlpLineUnreached = (700 - 618) + 3 + 2 * (20 - 15) + 2, kFlpcLineUnreached = kFlpLineUnreached + 2;
-
 // Row of (kind, id) in the table, -1 when the kind has no row for the id: the last id <= the one looked for, in
 // log2(kTlsMaxRows) = 8 steps.
 NF_DEV int tls_find(const TlsDev& t, uint32_t kind, uint32_t id) {
@@ -64,14 +57,16 @@ template <uint32_t KIND, typename S> NF_DEV void tls_value(S& s, const TlsDev& t
     }
 }
 
-// Base with the TLS keys: no record is deferred. Base::kMaxLine is the longest line Base writes, Base::kSideLds the LDS a
-// wave of its write kernel holds beside the window; the window takes what the longest line leaves of 32 KiB.
+// Base with the TLS keys: no record is deferred. The window takes what the longest line leaves of 32 KiB beside the wave's
+// side LDS; a base without name slots leaves one 16-byte chunk unused.
 template <typename Base> struct FlpTls : Base {
+    static constexpr bool kDefers = false;
     static constexpr uint32_t kMaxLine = Base::kMaxLine + kTlsLineMax;
-    static constexpr uint32_t kWindow = (32768 - Base::kSideLds - (kMaxLine + 15) / 16 * 16) / 16 * 16;
+    static constexpr uint32_t kSideLds = Base::kSideLds ? Base::kSideLds : 16;
+    static constexpr uint32_t kWindow = (32768 - kSideLds - (kMaxLine + 15) / 16 * 16) / 16 * 16;
     static constexpr uint32_t kLds = kWindow + (kMaxLine + 15) / 16 * 16;
-    static_assert(kLds + Base::kSideLds <= 32768 && kWindow >= 16384, "four waves per compute unit, and a window worth its copy-out");
-    TlsDev tls;
+    static_assert(kLds + kSideLds <= 32768 && kWindow >= 16384, "four waves per compute unit, and a window worth its copy-out");
+    TlsDev tls;                   // the kernels assign it (kDefers == false)
 
     template <typename S> NF_DEV void tls_names(S& s, const Rec& r) const {
         const uint32_t cipher = r.d[33] >> 16, group = r.d[34] & 0xffffu;   // tls_cipher_suite @134, tls_key_share @136

@@ -368,44 +368,68 @@ class FlowTable:
             setattr(f, k, a.ctypes.data)
         return f, keep
 
-    def encode_pb(self, records: np.ndarray, now_unix_ns: int, mono_now_ns: int, agent_ip16: bytes, names: np.ndarray,
-                  unknown: bytes = b"unknown", kafka_keys=False, present=None, parts=None):
-        """FlowsToPB + proto.Marshal of evicted records on the GPU. Returns (buf, frame_offsets, body_len[, keys]):
-        buf[frame_offsets[a]:frame_offsets[b]] is a serialized pbflow.Records of entries a..b-1; the last body_len[i]
-        bytes of frame i are the serialized pbflow.Record. With present/parts (see _pb_features) the flows are full
-        BpfFlowContents of the MapTracer branch (nfagg_encode_pb_content)."""
+    @staticmethod
+    def _content_parts(parts):
+        return {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS}
+
+    def _pb(self, records, options, kafka_keys=False, features=None, rows=None, netev_table=None):
+        """The host-memory entry points. options: _pb_options(...). features: (present, parts), present None: nfagg_encode_pb,
+        else nfagg_encode_pb_content; with rows and netev_table nfagg_encode_pb_content_netev. Returns (buf, frame_offsets,
+        body_len[, keys])."""
         r = np.ascontiguousarray(records)
         n = r.nbytes // 144
-        o, keep = self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown)
-        feat = None
-        if present is not None:
-            feat, keep_f = self._pb_features(n, present, parts or {})
+        o, keep = options
+        head = (self._h, r.ctypes.data_as(C.c_void_p), n)
+        fn, feat = L.lib.nfagg_encode_pb, None
+        if features is not None and features[0] is not None:
+            feat, keep_f = self._pb_features(n, features[0], self._content_parts(features[1]))
+            fn, head = L.lib.nfagg_encode_pb_content, head + (C.byref(feat),)
+        if netev_table is not None:
+            assert feat is not None
+            rw = np.ascontiguousarray(rows, dtype=np.uint16).reshape(n, 4)
+            fn, head = L.lib.nfagg_encode_pb_content_netev, head + (rw.ctypes.data_as(C.c_void_p), netev_table._t)
         off = np.zeros(n + 1, dtype=np.uint64)
         blen = np.zeros(max(n, 1), dtype=np.uint32)
         keys = np.zeros((max(n, 1), 32), dtype=np.uint8) if kafka_keys else None
-        head = (self._h, r.ctypes.data_as(C.c_void_p), n) + ((C.byref(feat),) if feat is not None else ())
-        fn = L.lib.nfagg_encode_pb if feat is None else L.lib.nfagg_encode_pb_content
         buf = self._encode_grown(n, 256, lambda p, cap, need: fn(
             *head, C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p), blen.ctypes.data_as(C.c_void_p),
             keys.ctypes.data_as(C.c_void_p) if kafka_keys else None, need))
         out = (buf, off, blen[:n])
         return out + (keys[:n],) if kafka_keys else out
 
+    def _pb_device(self, d_records, n, options, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys=0, features=None, d_rows=0,
+                   netev_table=None):
+        """The device entry points (raw device pointers); the optionals select as in _pb, features = (d_present, d_parts).
+        Returns (rc, bytes needed/written)."""
+        o, keep = options
+        need = C.c_size_t(0)
+        head = (self._h, C.c_void_p(d_records), n)
+        fn, feat = L.lib.nfagg_encode_pb_device, None
+        if features is not None:
+            feat, _ = self._pb_features(n, features[0], self._content_parts(features[1]), device=True)
+            fn, head = L.lib.nfagg_encode_pb_content_device, head + (C.byref(feat),)
+        if netev_table is not None:
+            assert feat is not None
+            fn, head = L.lib.nfagg_encode_pb_content_netev_device, head + (C.c_void_p(d_rows or None), netev_table._t)
+        rc = fn(*head, C.byref(o), C.c_void_p(d_out or None), out_cap, C.c_void_p(d_frame_offsets), C.c_void_p(d_body_len),
+                C.c_void_p(d_kafka_keys or None), C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value
+
+    def encode_pb(self, records: np.ndarray, now_unix_ns: int, mono_now_ns: int, agent_ip16: bytes, names: np.ndarray,
+                  unknown: bytes = b"unknown", kafka_keys=False, present=None, parts=None):
+        """FlowsToPB + proto.Marshal of evicted records on the GPU. Returns (buf, frame_offsets, body_len[, keys]):
+        buf[frame_offsets[a]:frame_offsets[b]] is a serialized pbflow.Records of entries a..b-1; the last body_len[i]
+        bytes of frame i are the serialized pbflow.Record. With present/parts (see _pb_features) the flows are full
+        BpfFlowContents of the MapTracer branch (nfagg_encode_pb_content)."""
+        return self._pb(records, self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown), kafka_keys, (present, parts))
+
     def encode_pb_device(self, d_records: int, n: int, now_unix_ns: int, mono_now_ns: int, agent_ip16: bytes, names: np.ndarray,
                          d_out: int, out_cap: int, d_frame_offsets: int, d_body_len: int, d_kafka_keys: int = 0,
                          unknown: bytes = b"unknown", d_present: int = 0, d_parts=None):
         """Device-resident variant (raw device pointers). Returns (rc, bytes needed/written)."""
-        o, keep = self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown)
-        need = C.c_size_t(0)
-        tail = (C.byref(o), C.c_void_p(d_out or None), out_cap, C.c_void_p(d_frame_offsets), C.c_void_p(d_body_len),
-                C.c_void_p(d_kafka_keys or None), C.byref(need))
-        if d_present:
-            feat, _ = self._pb_features(n, d_present, d_parts or {}, device=True)
-            rc = L.lib.nfagg_encode_pb_content_device(self._h, C.c_void_p(d_records), n, C.byref(feat), *tail)
-        else:
-            rc = L.lib.nfagg_encode_pb_device(self._h, C.c_void_p(d_records), n, *tail)
-        self._check(rc, ok=(L.OK, L.TRUNCATED))
-        return rc, need.value
+        return self._pb_device(d_records, n, self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown), d_out, out_cap,
+                               d_frame_offsets, d_body_len, d_kafka_keys, (d_present, d_parts) if d_present else None)
 
     # -- export encode (record -> IPFIX messages), nfagg_encode_ipfix
     def encode_ipfix(self, records: np.ndarray, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, export_time_s: int,
@@ -431,36 +455,79 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, need.value
 
-    # -- export encode (record -> direct-FLP JSON lines), nfagg_encode_flp_json
+    # -- export encode (record -> direct-FLP JSON lines), nfagg_encode_flp_json*
+    def _flp_json(self, records, options, features=None, rows=None, netev_table=None, tls_names=None):
+        """The host-memory entry points. options: flp_options(...). features: None (nfagg_encode_flp_json) or (present, parts)
+        (the *_content ones; present None: no flow carries a part). rows and netev_table: the *_netev one. tls_names:
+        nfagg_encode_flp_json_tls, which takes the others as options and defers nothing. Returns (buf, line_offsets, deferred)."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        o, keep = options
+        feat = None
+        if features is not None and features[0] is not None:
+            feat, keep_f = self._pb_features(n, features[0], self._content_parts(features[1]))
+        rw = np.ascontiguousarray(rows, dtype=np.uint16).reshape(n, 4) if rows is not None else None
+        off = np.zeros(n + 1, dtype=np.uint64)
+        deferred = np.zeros(n, dtype=np.uint8)
+        n_def = C.c_size_t(0)
+        head = (self._h, r.ctypes.data_as(C.c_void_p), n)
+        f_arg = (C.byref(feat) if feat is not None else None,)
+        ne_args = (rw.ctypes.data_as(C.c_void_p) if rw is not None else None, netev_table._t if netev_table is not None else None)
+        if tls_names is not None:
+            fn, head, flags = L.lib.nfagg_encode_flp_json_tls, head + f_arg + ne_args + (tls_names._t,), ()
+        else:
+            flags = (deferred.ctypes.data_as(C.c_void_p), C.byref(n_def))
+            if netev_table is not None:
+                fn, head = L.lib.nfagg_encode_flp_json_content_netev, head + f_arg + ne_args
+            elif features is not None:
+                fn, head = L.lib.nfagg_encode_flp_json_content, head + f_arg
+            else:
+                fn = L.lib.nfagg_encode_flp_json
+        per_flow = 448 if fn is L.lib.nfagg_encode_flp_json else 640
+        buf = self._encode_grown(n, per_flow, lambda p, cap, need: fn(*head, C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p), *flags, need))
+        assert int(deferred.sum()) == n_def.value
+        return buf, off, deferred
+
+    def _flp_json_device(self, d_records, n, options, d_out, out_cap, d_line_offsets, d_deferred=0, features=None, d_rows=0,
+                         netev_table=None, tls_names=None):
+        """The device entry points (raw device pointers); the optionals select as in _flp_json, features = (d_present, d_parts).
+        Returns (rc, bytes needed/written, deferred records)."""
+        o, keep = options
+        feat = None
+        if features is not None:
+            feat, _ = self._pb_features(n, features[0], self._content_parts(features[1]), device=True)
+        need, n_def = C.c_size_t(0), C.c_size_t(0)
+        head = (self._h, C.c_void_p(d_records or None), n)
+        f_arg = (C.byref(feat) if feat is not None else None,)
+        ne_args = (C.c_void_p(d_rows or None), netev_table._t if netev_table is not None else None)
+        flags = (C.c_void_p(d_deferred or None), C.byref(n_def))
+        if tls_names is not None:
+            fn, head, flags = L.lib.nfagg_encode_flp_json_tls_device, head + f_arg + ne_args + (tls_names._t,), ()
+        elif netev_table is not None:
+            fn, head = L.lib.nfagg_encode_flp_json_content_netev_device, head + f_arg + ne_args
+        elif features is not None:
+            fn, head = L.lib.nfagg_encode_flp_json_content_device, head + f_arg
+        else:
+            fn = L.lib.nfagg_encode_flp_json_device
+        rc = fn(*head, C.byref(o), C.c_void_p(d_out or None), out_cap, C.c_void_p(d_line_offsets or None), *flags, C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value, n_def.value
+
     def encode_flp_json(self, records: np.ndarray, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip=None,
                         time_received: int = 0, unknown: bytes = b"unknown"):
         """The direct-FLP stdout lines (`format: json`, keys sorted) for evicted records, encoded on the GPU. agent_ip: 16 (or
         4) bytes, None = a nil AgentIP ("<nil>"). Returns (buf, line_offsets, deferred): line i is
         buf[line_offsets[i]:line_offsets[i + 1]], its newline included; deferred[i] == 1 marks a record that carries TLS
         version / cipher suite / key share, whose line is empty and which the caller formats itself."""
-        r = np.ascontiguousarray(records)
-        n = r.nbytes // 144
-        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        deferred = np.zeros(n, dtype=np.uint8)
-        n_def = C.c_size_t(0)
-        buf = self._encode_grown(n, 448, lambda p, cap, need: L.lib.nfagg_encode_flp_json(
-            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p),
-            deferred.ctypes.data_as(C.c_void_p), C.byref(n_def), need))
-        assert int(deferred.sum()) == n_def.value
-        return buf, off, deferred
+        return self._flp_json(records, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown))
 
     def encode_flp_json_device(self, d_records: int, n: int, now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip,
                                time_received: int, d_out: int, out_cap: int, d_line_offsets: int, d_deferred: int = 0,
                                unknown: bytes = b"unknown"):
         """Device-resident variant (raw device pointers; d_out = 0 asks for the size, d_deferred = 0: no flags wanted).
         Returns (rc, bytes needed/written, deferred records)."""
-        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
-        need, n_def = C.c_size_t(0), C.c_size_t(0)
-        rc = L.lib.nfagg_encode_flp_json_device(self._h, C.c_void_p(d_records), n, C.byref(o), C.c_void_p(d_out or None), out_cap,
-                                                C.c_void_p(d_line_offsets), C.c_void_p(d_deferred or None), C.byref(n_def), C.byref(need))
-        self._check(rc, ok=(L.OK, L.TRUNCATED))
-        return rc, need.value, n_def.value
+        return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
+                                     d_out, out_cap, d_line_offsets, d_deferred)
 
     # -- export encode (MapTracer flow -> direct-FLP JSON line), nfagg_encode_flp_json_content
     def encode_flp_json_content(self, records: np.ndarray, present, parts, now_unix_ns: int, mono_now_ns: int, names: np.ndarray,
@@ -468,36 +535,15 @@ class FlowTable:
         """encode_flp_json over full BpfFlowContents: `records`, `present` (FEAT_* bits per flow) and `parts` ({"additional" |
         "dns" | "drops" | "xlat" | "quic": array of n structs}; other kinds are ignored) as map_merge returns them.
         present=None: no flow carries a part. Returns (buf, line_offsets, deferred) as encode_flp_json does."""
-        r = np.ascontiguousarray(records)
-        n = r.nbytes // 144
-        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
-        feat = None
-        if present is not None:
-            feat, keep_f = self._pb_features(n, present, {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS})
-        off = np.zeros(n + 1, dtype=np.uint64)
-        deferred = np.zeros(n, dtype=np.uint8)
-        n_def = C.c_size_t(0)
-        buf = self._encode_grown(n, 640, lambda p, cap, need: L.lib.nfagg_encode_flp_json_content(
-            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat) if feat is not None else None, C.byref(o), p, cap,
-            off.ctypes.data_as(C.c_void_p), deferred.ctypes.data_as(C.c_void_p), C.byref(n_def), need))
-        assert int(deferred.sum()) == n_def.value
-        return buf, off, deferred
+        return self._flp_json(records, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown), (present, parts))
 
     def encode_flp_json_content_device(self, d_records: int, n: int, d_present: int, d_parts, now_unix_ns: int, mono_now_ns: int,
                                        names: np.ndarray, agent_ip, time_received: int, d_out: int, out_cap: int, d_line_offsets: int,
                                        d_deferred: int = 0, unknown: bytes = b"unknown"):
         """Device-resident variant (raw device pointers, e.g. the d_out of map_merge_device; d_present = 0: no parts; d_out = 0
         asks for the size). Returns (rc, bytes needed/written, deferred records)."""
-        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
-        feat = None
-        if d_present:
-            feat, _ = self._pb_features(n, d_present, {k: v for k, v in (d_parts or {}).items() if k in _CONTENT_PARTS}, device=True)
-        need, n_def = C.c_size_t(0), C.c_size_t(0)
-        rc = L.lib.nfagg_encode_flp_json_content_device(
-            self._h, C.c_void_p(d_records), n, C.byref(feat) if feat is not None else None, C.byref(o), C.c_void_p(d_out or None), out_cap,
-            C.c_void_p(d_line_offsets), C.c_void_p(d_deferred or None), C.byref(n_def), C.byref(need))
-        self._check(rc, ok=(L.OK, L.TRUNCATED))
-        return rc, need.value, n_def.value
+        return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
+                                     d_out, out_cap, d_line_offsets, d_deferred, (d_present, d_parts) if d_present else None)
 
     # -- network events (nfagg_netev_*): the decoder's answers as a table, the per-flow work on the GPU
     def netev_table(self, entries) -> "NetevTable":
@@ -538,61 +584,28 @@ class FlowTable:
                         agent_ip16: bytes, names: np.ndarray, unknown: bytes = b"unknown"):
         """encode_pb with present/parts plus the flows' network events (nfagg_encode_pb_content_netev): present and
         parts["drops"] are netev_resolve's outputs, rows its rows. Returns (buf, frame_offsets, body_len)."""
-        r = np.ascontiguousarray(records)
-        n = r.nbytes // 144
-        o, keep = self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown)
-        feat, keep_f = self._pb_features(n, present, {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS})
-        rw = np.ascontiguousarray(rows, dtype=np.uint16).reshape(n, 4)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        blen = np.zeros(max(n, 1), dtype=np.uint32)
-        buf = self._encode_grown(n, 256, lambda p, cap, need: L.lib.nfagg_encode_pb_content_netev(
-            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat), rw.ctypes.data_as(C.c_void_p), table._t, C.byref(o), p, cap,
-            off.ctypes.data_as(C.c_void_p), blen.ctypes.data_as(C.c_void_p), None, need))
-        return buf, off, blen[:n]
+        return self._pb(records, self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown), False, (present, parts), rows, table)
 
     def encode_pb_netev_device(self, d_records: int, n: int, d_present: int, d_parts, d_rows: int, table: "NetevTable", now_unix_ns: int,
                                mono_now_ns: int, agent_ip16: bytes, names: np.ndarray, d_out: int, out_cap: int, d_frame_offsets: int,
                                d_body_len: int, unknown: bytes = b"unknown"):
         """Device-resident variant (raw device pointers). Returns (rc, bytes needed/written)."""
-        o, keep = self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown)
-        feat, _ = self._pb_features(n, d_present, {k: v for k, v in (d_parts or {}).items() if k in _CONTENT_PARTS}, device=True)
-        need = C.c_size_t(0)
-        rc = L.lib.nfagg_encode_pb_content_netev_device(
-            self._h, C.c_void_p(d_records), n, C.byref(feat), C.c_void_p(d_rows or None), table._t, C.byref(o), C.c_void_p(d_out or None),
-            out_cap, C.c_void_p(d_frame_offsets), C.c_void_p(d_body_len), None, C.byref(need))
-        self._check(rc, ok=(L.OK, L.TRUNCATED))
-        return rc, need.value
+        return self._pb_device(d_records, n, self._pb_options(now_unix_ns, mono_now_ns, agent_ip16, names, unknown), d_out, out_cap,
+                               d_frame_offsets, d_body_len, 0, (d_present, d_parts), d_rows, table)
 
     def encode_flp_json_netev(self, records: np.ndarray, present, parts, rows, table: "NetevTable", now_unix_ns: int, mono_now_ns: int,
                               names: np.ndarray, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown"):
         """encode_flp_json_content plus the flows' network events (nfagg_encode_flp_json_content_netev); inputs as
         encode_pb_netev. Returns (buf, line_offsets, deferred)."""
-        r = np.ascontiguousarray(records)
-        n = r.nbytes // 144
-        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
-        feat, keep_f = self._pb_features(n, present, {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS})
-        rw = np.ascontiguousarray(rows, dtype=np.uint16).reshape(n, 4)
-        off = np.zeros(n + 1, dtype=np.uint64)
-        deferred = np.zeros(n, dtype=np.uint8)
-        n_def = C.c_size_t(0)
-        buf = self._encode_grown(n, 640, lambda p, cap, need: L.lib.nfagg_encode_flp_json_content_netev(
-            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat), rw.ctypes.data_as(C.c_void_p), table._t, C.byref(o), p, cap,
-            off.ctypes.data_as(C.c_void_p), deferred.ctypes.data_as(C.c_void_p), C.byref(n_def), need))
-        assert int(deferred.sum()) == n_def.value
-        return buf, off, deferred
+        return self._flp_json(records, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown), (present, parts),
+                              rows, table)
 
     def encode_flp_json_netev_device(self, d_records: int, n: int, d_present: int, d_parts, d_rows: int, table: "NetevTable",
                                      now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip, time_received: int, d_out: int,
                                      out_cap: int, d_line_offsets: int, d_deferred: int = 0, unknown: bytes = b"unknown"):
         """Device-resident variant (raw device pointers). Returns (rc, bytes needed/written, deferred records)."""
-        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
-        feat, _ = self._pb_features(n, d_present, {k: v for k, v in (d_parts or {}).items() if k in _CONTENT_PARTS}, device=True)
-        need, n_def = C.c_size_t(0), C.c_size_t(0)
-        rc = L.lib.nfagg_encode_flp_json_content_netev_device(
-            self._h, C.c_void_p(d_records), n, C.byref(feat), C.c_void_p(d_rows or None), table._t, C.byref(o), C.c_void_p(d_out or None),
-            out_cap, C.c_void_p(d_line_offsets), C.c_void_p(d_deferred or None), C.byref(n_def), C.byref(need))
-        self._check(rc, ok=(L.OK, L.TRUNCATED))
-        return rc, need.value, n_def.value
+        return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
+                                     d_out, out_cap, d_line_offsets, d_deferred, (d_present, d_parts), d_rows, table)
 
     # -- TLS names (nfagg_tls_names_*) and the direct-FLP encoder that writes them, nfagg_encode_flp_json_tls
     def tls_names(self, entries=None) -> "TlsNames":
@@ -605,19 +618,8 @@ class FlowTable:
         """encode_flp_json (present=None), encode_flp_json_content (present / parts) or encode_flp_json_netev (rows and
         netev_table as well) with TLSVersion, TLSCipherSuite and TLSGroup written from `tls_names` (nfagg_encode_flp_json_tls):
         no record is deferred. Returns (buf, line_offsets)."""
-        r = np.ascontiguousarray(records)
-        n = r.nbytes // 144
-        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
-        feat = None
-        if present is not None:
-            feat, keep_f = self._pb_features(n, present, {k: v for k, v in (parts or {}).items() if k in _CONTENT_PARTS})
-        rw = np.ascontiguousarray(rows, dtype=np.uint16).reshape(n, 4) if rows is not None else None
-        off = np.zeros(n + 1, dtype=np.uint64)
-        buf = self._encode_grown(n, 640, lambda p, cap, need: L.lib.nfagg_encode_flp_json_tls(
-            self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(feat) if feat is not None else None,
-            rw.ctypes.data_as(C.c_void_p) if rw is not None else None, netev_table._t if netev_table is not None else None, tls_names._t,
-            C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p), need))
-        return buf, off
+        return self._flp_json(records, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown), (present, parts),
+                              rows, netev_table, tls_names)[:2]
 
     def encode_flp_json_tls_device(self, d_records: int, n: int, tls_names: "TlsNames", now_unix_ns: int, mono_now_ns: int,
                                    names: np.ndarray, agent_ip, time_received: int, d_out: int, out_cap: int, d_line_offsets: int,
@@ -625,17 +627,9 @@ class FlowTable:
                                    netev_table: "NetevTable" = None):
         """Device-resident variant (raw device pointers; d_present = 0: no parts; d_out = 0 asks for the size). Returns (rc,
         bytes needed/written)."""
-        o, keep = flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown)
-        feat = None
-        if d_present:
-            feat, _ = self._pb_features(n, d_present, {k: v for k, v in (d_parts or {}).items() if k in _CONTENT_PARTS}, device=True)
-        need = C.c_size_t(0)
-        rc = L.lib.nfagg_encode_flp_json_tls_device(
-            self._h, C.c_void_p(d_records or None), n, C.byref(feat) if feat is not None else None, C.c_void_p(d_rows or None),
-            netev_table._t if netev_table is not None else None, tls_names._t, C.byref(o), C.c_void_p(d_out or None), out_cap,
-            C.c_void_p(d_line_offsets or None), C.byref(need))
-        self._check(rc, ok=(L.OK, L.TRUNCATED))
-        return rc, need.value
+        return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
+                                     d_out, out_cap, d_line_offsets, 0, (d_present, d_parts) if d_present else None, d_rows, netev_table,
+                                     tls_names)[:2]
 
     def stats(self) -> L.Stats:
         s = L.Stats()

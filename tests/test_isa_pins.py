@@ -112,3 +112,27 @@ def test_the_cut_walk_keeps_twelve_loads_in_flight(disassembly):
     assert waits.get(12, 0) == 4, "k_par_cuts waits on its loads as %r (wanted: vmcnt(12) x 4)" % waits
     last12 = max(i for i, n in enumerate(order) if n == 12)
     assert 0 not in order[:last12], "k_par_cuts drains its loads inside the walk: %r" % order
+
+
+def test_the_flp_write_kernels_keep_their_registers_and_their_four_waves(tmp_path):
+    """The direct-FLP JSON kernels are one template pair (csrc/nfagg_flp_line.h: k_flp_size<Feat>, k_flp_write<Feat>), compiled
+    once per feature policy. The policy of the Accounter path (FlpPlain) sits just under the register limit; what keeps it there is
+    that each instantiation is a kernel of its own, and a policy that leaks into the shared body (a hook taken by reference, a
+    member that is not dead) shows first as scratch in that kernel. Every write kernel holds a window of LDS per wave sized for four
+    waves per compute unit: 32 KiB at the most. Read from the code objects' metadata notes."""
+    readelf = os.path.join(os.path.dirname(OBJDUMP), "llvm-readelf")
+    if not (os.path.exists(OBJDUMP) and os.path.exists(readelf)):
+        pytest.skip("no llvm-objdump / llvm-readelf in this image")
+    shutil.copy(LIB, tmp_path / "libnfagg.so")
+    subprocess.check_call([OBJDUMP, "--offloading", "libnfagg.so"], cwd=tmp_path, stdout=subprocess.DEVNULL)
+    write = {}
+    for co in sorted(glob.glob(str(tmp_path / "libnfagg.so.*gfx950*"))):
+        notes = subprocess.check_output([readelf, "--notes", co], text=True)
+        for entry in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:       # one kernel's map each: .agpr_count is its first key
+            field = lambda key: re.search(r"\.%s:\s+(\S+)" % key, entry).group(1)      # noqa: E731
+            if re.match(r"_ZN5nfagg11k_flp_writeI", field("name")):
+                write[field("name")] = (int(field("private_segment_fixed_size")), int(field("group_segment_fixed_size")))
+    assert len(write) == 6, "one k_flp_write per policy (plain, content, network events; each with and without TLS names): %r" % sorted(write)
+    plain = [k for k in write if "FlpPlain" in k and "FlpTls" not in k]
+    assert len(plain) == 1 and write[plain[0]][0] == 0, "k_flp_write<FlpPlain> spills: %r" % write
+    assert all(lds <= 32768 for _, lds in write.values()), write
