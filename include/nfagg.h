@@ -1047,6 +1047,110 @@ int nfagg_encode_flp_json_tls_device(nfagg_handle* h, const void* d_records, siz
 uint32_t nfagg_flp_json_tls_max_line(int policy);
 
 /* ------------------------------------------------------------------ */
+/* Kubernetes enrichment — what flowlogs-pipeline's `transform network` */
+/* stage adds in front of the writer NetObserv ships: add_kubernetes    */
+/* for SrcAddr and for DstAddr, then add_kubernetes_infra               */
+/* (pkg/pipeline/transform/kubernetes/enrich.go:37-104: Enrich with the */
+/* default assignee, no label or annotation prefixes, zone on;          */
+/* enrich.go:140-165: EnrichLayer and objectIsApp;                      */
+/* pkg/api/transform_network.go:153-162: the key names). The informers  */
+/* are not restated: the caller asks its own and hands over, per IP     */
+/* address, what IndexLookup(nil, ip) returns (pod, then node, then     */
+/* service; checkParent and NetworkName = "primary" applied) and the    */
+/* zone fillInK8sZone would pick (a node's own label, a pod's node's).  */
+/* The GPU does the per-flow work: a hash join of both addresses        */
+/* against the table and a copy of the row's pre-rendered keys.         */
+/*                                                                      */
+/* The rule shape is fixed as NetObserv configures it: outputs SrcK8S   */
+/* for SrcAddr, DstK8S for DstAddr and K8S_FlowLayer, the layer rule's  */
+/* NamespaceNameFields = [(SrcK8S_Name, SrcK8S_Namespace),              */
+/* (DstK8S_Name, DstK8S_Namespace)], rule order src, dst, infra.        */
+/*                                                                      */
+/* Differences from the reference, by design:                           */
+/*  - addresses match by value, not by text: an informer string that is */
+/*    not in Go's canonical form misses in Go and hits here;            */
+/*  - one table serves a whole call, where the reference can see an     */
+/*    informer update between two flows of a batch;                     */
+/*  - a side's block of more than NFAGG_K8S_MAX_RENDERED bytes fails    */
+/*    the table (Kubernetes' own bounds on names, namespaces, kinds and */
+/*    label values keep a block near 1.5 KB before escapes);            */
+/*  - out of scope: secondary-network keys (MAC, interface, UDN         */
+/*    indexes), label and annotation copies, the otel assignee, other   */
+/*    output names, the remaining transform network rules.              */
+/* ------------------------------------------------------------------ */
+
+typedef struct nfagg_k8s_entry {      /* strings: pointer + length, arbitrary bytes, read during the call only */
+    uint8_t ip[16];                   /* net.IP.To16(): an IPv4 address as ::ffff:a.b.c.d, as the flow id holds it */
+    const char *namespace_, *name, *kind, *owner_name, *owner_kind, *network_name, *host_ip, *host_name, *zone;
+    uint32_t namespace_len, name_len, kind_len, owner_name_len, owner_kind_len, network_name_len, host_ip_len, host_name_len, zone_len;
+    uint8_t has_zone;                 /* the zone label exists (it may be empty: the key is then written with "") */
+} nfagg_k8s_entry;
+
+/* K8sInfraRule: a namespace that starts with one of infra_prefixes, or a (namespace, name) pair among infra_refs, is
+ * infrastructure. NUL-terminated strings; infra_refs holds 2 * n_refs of them, namespace then name. */
+typedef struct nfagg_k8s_layer {
+    uint32_t struct_size;
+    uint32_t n_prefixes;
+    const char* const* infra_prefixes;
+    const char* const* infra_refs;
+    uint32_t n_refs;
+    uint32_t pad_;
+} nfagg_k8s_layer;
+
+#define NFAGG_K8S_MAX_RENDERED 2048   /* one side's block: 181 bytes of key text, the escaped values */
+#define NFAGG_K8S_MAX_ROWS (1u << 22)
+#define NFAGG_K8S_NO_ROW 0xFFFFFFFFu
+
+typedef struct nfagg_k8s_table nfagg_k8s_table;
+
+/* One side's block as the encoder emits it behind SrcAddr (side 0: "SrcK8S_" keys) or DstAddr (side 1: "DstK8S_"), with
+ * its leading comma (host only: no handle, no device). Keys in byte order: HostIP, HostName, Name, Namespace,
+ * NetworkName, OwnerName, OwnerType, Type (= kind), Zone. Name, Type, OwnerName, OwnerType and NetworkName are always
+ * there, even when empty; Namespace only when non-empty; HostIP only when non-empty, HostName only when HostIP and
+ * HostName are both non-empty (enrich.go:81-86); Zone only when has_zone. Values are escaped as jsoniter's WriteString
+ * does without HTML escaping; bytes from 0x80 up are copied. NFAGG_EINVAL for a block of more than
+ * NFAGG_K8S_MAX_RENDERED bytes, NFAGG_TRUNCATED with *n_out = bytes needed when cap is smaller. */
+int nfagg_k8s_render(const nfagg_k8s_entry* entry, int side, void* out, size_t cap, size_t* n_out);
+
+/* Build the table from n entries (n == 0 is valid: no address has a row): both blocks of every row rendered once, the
+ * row's app flag (its namespace is not empty and objectIsApp(namespace, name) holds for `layer`), an open-addressed table
+ * keyed by the 16 address bytes (a power of two of slots, at most half in use, home slot = the low bits of
+ * nfagg_ip_hash(ip, 3), linear probe). Row r, as nfagg_k8s_resolve reports it, is entries[r]. layer == NULL: the lines get
+ * no K8S_FlowLayer key. Errors (NFAGG_EINVAL, nfagg_last_error names the entry): a duplicate address, a null string with
+ * a length, a block over the cap, more than NFAGG_K8S_MAX_ROWS entries. With a handle the table is uploaded to that
+ * handle's device and serves its calls until destroyed; rebuild it when the informer caches changed. h == NULL builds and
+ * checks the table on the host alone (errors through nfagg_last_error(NULL)); such a table is refused by the device calls. */
+int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size_t n, const nfagg_k8s_layer* layer, nfagg_k8s_table** table);
+void nfagg_k8s_table_destroy(nfagg_k8s_table* table);
+
+/* The hash join alone, one GPU lane per flow: rows[2i] = the row of record i's src_ip, rows[2i + 1] that of its dst_ip,
+ * NFAGG_K8S_NO_ROW for an address without a row. A record whose eth_protocol is neither 0x0800 nor 0x86DD has no SrcAddr /
+ * DstAddr key for Enrich to look up and gets NFAGG_K8S_NO_ROW twice, whatever its id bytes hold. All pointers HOST memory: */
+int nfagg_k8s_resolve(nfagg_handle* h, const nfagg_k8s_table* table, const void* records, size_t n, uint32_t* rows);
+/* Same with records and rows in DEVICE memory (records 16-byte, rows 8-byte aligned). */
+int nfagg_k8s_resolve_device(nfagg_handle* h, const nfagg_k8s_table* table, const void* d_records, size_t n, uint32_t* d_rows);
+
+/* nfagg_encode_flp_json_tls (same three policies chosen by features / rows, tls_names required, nothing deferred) plus
+ * the enrichment: the dst row's block behind DstAddr, the src row's behind SrcAddr, and, for a table with a layer,
+ * "K8S_FlowLayer":"app"|"infra" on every line between Interfaces and NetworkEvents / Packets: "app" when at least one side
+ * resolved to a row whose app flag is set, else "infra". A record that is not IP has no address keys and so no block; it
+ * still gets K8S_FlowLayer ("infra"), which EnrichLayer sets unconditionally. k8s_table is required and must have been
+ * created for this handle; with an empty table and no layer the output is byte for byte that of nfagg_encode_flp_json_tls.
+ * All pointers HOST memory: */
+int nfagg_encode_flp_json_k8s(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* out, size_t out_cap,
+                              uint64_t* line_offsets, size_t* out_bytes);
+/* Same with every data pointer (d_rows and those inside d_features too) in DEVICE memory. */
+int nfagg_encode_flp_json_k8s_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* d_out, size_t out_cap,
+                                     uint64_t* d_line_offsets, size_t* out_bytes);
+/* The longest line nfagg_encode_flp_json_k8s can write: nfagg_flp_json_tls_max_line(policy) plus two blocks at the cap
+ * and ,"K8S_FlowLayer":"infra"; 0 for an unknown policy. The write kernels size their LDS windows by it. */
+uint32_t nfagg_flp_json_k8s_max_line(int policy);
+
+/* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */
 /* ------------------------------------------------------------------ */
 
@@ -1058,8 +1162,8 @@ uint32_t nfagg_shard_of(const nfagg_flow_id* id, uint32_t n_shards);
 void nfagg_shard_ids(const void* records, size_t n, uint32_t n_shards, uint32_t* out_shard);
 /* The 64-bit key hash itself (table index / fingerprint / shard all derive from it). */
 uint64_t nfagg_key_hash(const nfagg_flow_id* id);
-/* The 64-bit hash of a 16-byte IP with the given seed index (0..3), as used by
- * the sketches. */
+/* The 64-bit hash of a 16-byte IP with the given seed index (0..3): 0..2 as used
+ * by the sketches, 3 by the Kubernetes table. */
 uint64_t nfagg_ip_hash(const uint8_t ip[16], uint32_t seed_index);
 
 int nfagg_stats_get(nfagg_handle* h, nfagg_stats* out);

@@ -112,6 +112,21 @@ class TlsNameEntry(C.Structure):
     _fields_ = [("kind", C.c_uint16), ("id", C.c_uint16), ("name_len", C.c_uint32), ("name", C.c_char_p)]
 
 
+class K8sEntry(C.Structure):
+    """nfagg_k8s_entry (include/nfagg.h)."""
+    _STRINGS = ("namespace_", "name", "kind", "owner_name", "owner_kind", "network_name", "host_ip", "host_name", "zone")
+    _fields_ = ([("ip", C.c_uint8 * 16)] + [(f, C.c_char_p) for f in _STRINGS] +
+                [(f.rstrip("_") + "_len", C.c_uint32) for f in _STRINGS] + [("has_zone", C.c_uint8)])
+
+
+class K8sLayer(C.Structure):
+    """nfagg_k8s_layer (include/nfagg.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_prefixes", C.c_uint32), ("infra_prefixes", C.POINTER(C.c_char_p)),
+                ("infra_refs", C.POINTER(C.c_char_p)), ("n_refs", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+K8S_MAX_RENDERED, K8S_MAX_ROWS, K8S_NO_ROW = 2048, 1 << 22, 0xFFFFFFFF
+
 TLS_VERSION, TLS_CIPHER_SUITE, TLS_GROUP = 0, 1, 2
 TLS_NAME_MAX, TLS_MAX_ROWS = 63, 256
 
@@ -203,6 +218,14 @@ SIGNATURES = {
     "nfagg_encode_flp_json_tls": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
     "nfagg_encode_flp_json_tls_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
     "nfagg_flp_json_tls_max_line": (C.c_uint32, [C.c_int]),
+    "nfagg_k8s_render": (C.c_int, [C.POINTER(K8sEntry), C.c_int, _vp, _sz, _psz]),
+    "nfagg_k8s_table_create": (C.c_int, [_vp, C.POINTER(K8sEntry), _sz, C.POINTER(K8sLayer), C.POINTER(_vp)]),
+    "nfagg_k8s_table_destroy": (None, [_vp]),
+    "nfagg_k8s_resolve": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "nfagg_k8s_resolve_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "nfagg_encode_flp_json_k8s": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_encode_flp_json_k8s_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_flp_json_k8s_max_line": (C.c_uint32, [C.c_int]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

@@ -97,13 +97,14 @@ struct nfagg_handle {
         DevBuf pb_feat[6];                           //   protobuf: present bits and the five feature parts
         DevBuf ne_rows;                              //   *_netev: the flows' table rows
         DevBuf ne_in[3], ne_out[3], ne_missing, ne_info;   // nfagg_netev_resolve: staged inputs and outputs, the missing set, its counters
+        DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record
         std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
         std::vector<uint8_t> h_flp_esc;
         template <typename F> void each(F f) {
             for (DevBuf* b : {&local_off, &block_sum, &block_base, &names, &ipfix_name_rows, &flp_rows, &flp_esc, &flp_n_deferred,
                               &in_records, &out, &out_offsets, &out_extra[0], &out_extra[1]}) f(*b);
             for (DevBuf& b : pb_feat) f(b);
-            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info}) f(*b);
+            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows}) f(*b);
         }
     } enc;
     // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
@@ -2212,6 +2213,19 @@ struct nfagg_tls_names {
     void* d_mem = nullptr;        // the ids, then the rows
 };
 
+// The Kubernetes table of nfagg_k8s_table_create (nfagg_flp.h, nfagg_k8s.h): the slots, the rows and the rendered blocks, on the
+// host and (with a handle) on its device.
+struct nfagg_k8s_table {
+    nfagg_handle* h = nullptr;
+    std::vector<K8sSlot> slots;
+    std::vector<K8sRow> rows;
+    std::vector<uint8_t> blob;
+    bool has_layer = false;
+    void* d_slots = nullptr;
+    void* d_rows = nullptr;
+    void* d_blob = nullptr;
+};
+
 // ---- the export encoders' host side: what protobuf, IPFIX and direct-FLP JSON do alike
 namespace {
 
@@ -2584,7 +2598,12 @@ static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, Fl
 
 // The TLS entry points' extra input. With it the three TLS keys are written from the table, no record is deferred (flags and
 // counter are not used), and the network events are an option: rows and table both, or neither (*ne = nullptr).
-struct FlpTlsArgs { const nfagg_tls_names* names; };
+// with_k8s: the *_k8s entry points, whose table is required as well and whose lines carry the Kubernetes keys.
+struct FlpTlsArgs { const nfagg_tls_names* names; bool with_k8s = false; const nfagg_k8s_table* k8s = nullptr; };
+static K8sDev k8s_dev(const nfagg_k8s_table* t) {
+    return K8sDev{(const K8sSlot*)t->d_slots, (const K8sRow*)t->d_rows, (const uint8_t*)t->d_blob, (uint32_t)t->slots.size() - 1,
+                  (uint32_t)t->rows.size(), t->has_layer ? 1u : 0u};
+}
 static int netev_optional(nfagg_handle* h, const NetevArgs** ne, size_t n) {
     if (!*ne) return NFAGG_OK;
     const NetevArgs& a = **ne;
@@ -2602,8 +2621,11 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     int rc;
     if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
     if ((rc = encode_flp_check(h, opt)) != NFAGG_OK) return rc;
-    if (!h || (tls && !tls->names) || !out_bytes || !d_line_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || !out_bytes || !d_line_offsets || (n && !d_records))
+        return fail(h, NFAGG_EINVAL, "null argument");
     if (tls && (tls->names->h != h || !tls->names->d_mem)) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
+    const nfagg_k8s_table* k8s = tls && tls->with_k8s ? tls->k8s : nullptr;
+    if (k8s && (k8s->h != h || !k8s->d_slots)) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
     PbFeat F{};
     if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
@@ -2623,6 +2645,18 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     }
     const PbFeat* Fp = (feat || ne) ? &F : nullptr;                   // neither: the plain line
     const TlsDev* Tp = tls ? &T : nullptr;
+    if (k8s) {
+        if ((rc = ensure_buf(h, h->enc.k8s_rows, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+        uint32_t* k8s_rows = (uint32_t*)h->enc.k8s_rows.p;
+        const K8sDev K = k8s_dev(k8s);
+        hipError_t e = launch_k8s_resolve(d_records, n, K, k8s_rows, h->stream);
+        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
+        return encode_two_pass(h, n, "FLP JSON with Kubernetes keys", "write", d_out, out_cap, out_bytes, nullptr,
+            [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+                return launch_flp_k8s_size(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_sum, block_base, h->stream); },
+            [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+                return launch_flp_k8s_write(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_base, d_out, d_line_offsets, h->stream); });
+    }
     size_t deferred_unused;
     return encode_two_pass(h, n, tls ? "FLP JSON with TLS names" : Fp ? "FLP JSON content" : "FLP JSON", "write", d_out, out_cap, out_bytes,
         tls ? nullptr : n_deferred ? n_deferred : &deferred_unused,
@@ -2639,7 +2673,8 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
                                 size_t* n_deferred, size_t* out_bytes) {
     int rc = encode_flp_check(h, opt);
     if (rc != NFAGG_OK) return rc;
-    if (!h || (tls && !tls->names) || !out_bytes || !line_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || !out_bytes || !line_offsets || (n && !records))
+        return fail(h, NFAGG_EINVAL, "null argument");
     if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
     if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
     return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
@@ -3032,6 +3067,209 @@ int nfagg_encode_flp_json_tls(nfagg_handle* h, const void* records, size_t n, co
                               const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
     const NetevArgs ne{rows, netev_table};
     const FlpTlsArgs tls{tls_names};
+    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+}
+
+}  // extern "C"
+
+// ---- Kubernetes enrichment: the caller's table (nfagg_k8s.h), the hash join alone, and the direct-FLP entry points with the keys
+namespace {
+
+struct K8sStr { const char* p; uint32_t len; };
+
+// One side's block. false: a null string with a length (*bad_string), or a value so long that the block cannot fit the cap
+// (checked before anything of that size is built).
+bool k8s_render(const nfagg_k8s_entry& e, int side, std::vector<uint8_t>& o, bool* bad_string) {
+    // enrich.go:51-87 in the byte order of the keys (transform_network.go:153-162)
+    const bool host_ip = e.host_ip_len != 0;
+    const struct { const char* key; K8sStr v; bool on; } kv[9] = {
+        {"HostIP", {e.host_ip, e.host_ip_len}, host_ip}, {"HostName", {e.host_name, e.host_name_len}, host_ip && e.host_name_len != 0},
+        {"Name", {e.name, e.name_len}, true}, {"Namespace", {e.namespace_, e.namespace_len}, e.namespace_len != 0},
+        {"NetworkName", {e.network_name, e.network_name_len}, true}, {"OwnerName", {e.owner_name, e.owner_name_len}, true},
+        {"OwnerType", {e.owner_kind, e.owner_kind_len}, true}, {"Type", {e.kind, e.kind_len}, true},
+        {"Zone", {e.zone, e.has_zone ? e.zone_len : 0u}, e.has_zone != 0}};
+    o.clear();
+    *bad_string = false;
+    for (const auto& q : kv) if (q.v.len && !q.v.p) { *bad_string = true; return false; }
+    for (const auto& q : kv) if (q.on && q.v.len > kK8sMaxRendered) return false;
+    uint8_t buf[2 + 6 * kK8sMaxRendered];
+    for (const auto& q : kv) {
+        if (!q.on) continue;
+        const char* head = side ? ",\"DstK8S_" : ",\"SrcK8S_";
+        o.insert(o.end(), head, head + 9);
+        o.insert(o.end(), q.key, q.key + strlen(q.key));
+        o.push_back('"'); o.push_back(':');
+        const uint32_t n = flp_escape(q.v.p, q.v.len, buf);
+        o.insert(o.end(), buf, buf + n);
+    }
+    return true;
+}
+
+// enrich.go:143-165 for one row: EnrichLayer asks only about a side whose namespace is not empty
+bool k8s_is_app(const nfagg_k8s_entry& e, const nfagg_k8s_layer& l) {
+    if (!e.namespace_len) return false;
+    for (uint32_t k = 0; k < l.n_prefixes; k++) {
+        const size_t pl = strlen(l.infra_prefixes[k]);
+        if (pl <= e.namespace_len && memcmp(e.namespace_, l.infra_prefixes[k], pl) == 0) return false;
+    }
+    for (uint32_t k = 0; k < l.n_refs; k++) {
+        const char *ns = l.infra_refs[2 * k], *nm = l.infra_refs[2 * k + 1];
+        if (strlen(ns) == e.namespace_len && memcmp(ns, e.namespace_, e.namespace_len) == 0 && strlen(nm) == e.name_len &&
+            (e.name_len == 0 || memcmp(nm, e.name, e.name_len) == 0))
+            return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nfagg_k8s_render(const nfagg_k8s_entry* entry, int side, void* out, size_t cap, size_t* n_out) {
+    if (!entry || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
+    if (side != 0 && side != 1) return fail(nullptr, NFAGG_EINVAL, "unknown side %d", side);
+    std::vector<uint8_t> o;
+    bool bad_string;
+    if (!k8s_render(*entry, side, o, &bad_string))
+        return bad_string ? fail(nullptr, NFAGG_EINVAL, "null string with a length") : fail(nullptr, NFAGG_EINVAL, "rendered block exceeds %u bytes", kK8sMaxRendered);
+    if (o.size() > kK8sMaxRendered) return fail(nullptr, NFAGG_EINVAL, "rendered block has %zu bytes, more than %u", o.size(), kK8sMaxRendered);
+    *n_out = o.size();
+    if (!out || cap < o.size()) return NFAGG_TRUNCATED;
+    memcpy(out, o.data(), o.size());
+    return NFAGG_OK;
+}
+
+int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size_t n, const nfagg_k8s_layer* layer, nfagg_k8s_table** table) {
+    if (!table || (n && !entries)) return fail(h, NFAGG_EINVAL, "null argument");
+    *table = nullptr;
+    if (layer) {
+        if (layer->struct_size != sizeof(nfagg_k8s_layer)) return fail(h, NFAGG_EINVAL, "nfagg_k8s_layer.struct_size mismatch");
+        if ((layer->n_prefixes && !layer->infra_prefixes) || (layer->n_refs && !layer->infra_refs)) return fail(h, NFAGG_EINVAL, "null layer list with a count");
+        for (uint32_t k = 0; k < layer->n_prefixes; k++) if (!layer->infra_prefixes[k]) return fail(h, NFAGG_EINVAL, "layer prefix %u is null", k);
+        for (uint32_t k = 0; k < 2 * layer->n_refs; k++) if (!layer->infra_refs[k]) return fail(h, NFAGG_EINVAL, "layer ref %u is null", k / 2);
+    }
+    if (n > NFAGG_K8S_MAX_ROWS) return fail(h, NFAGG_EINVAL, "%zu Kubernetes entries, more than %u", n, NFAGG_K8S_MAX_ROWS);
+    nfagg_k8s_table* t = new (std::nothrow) nfagg_k8s_table;
+    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
+    t->h = h;
+    t->has_layer = layer != nullptr;
+    size_t cap = 1;
+    while (cap < 2 * n) cap <<= 1;                                       // at most half full: a probe always meets a free slot
+    K8sSlot free_slot{};
+    free_slot.row = kK8sNoRow;
+    t->slots.assign(cap, free_slot);
+    t->rows.resize(n);
+    std::vector<uint8_t> piece;
+    for (size_t r = 0; r < n; r++) {
+        const nfagg_k8s_entry& e = entries[r];
+        K8sSlot key{};
+        memcpy(key.ip, e.ip, 16);
+        uint64_t lo, hi;
+        memcpy(&lo, e.ip, 8); memcpy(&hi, e.ip + 8, 8);
+        size_t s = (size_t)((uint32_t)k8s_hash(lo, hi) & (uint32_t)(cap - 1));
+        while (t->slots[s].row != kK8sNoRow) {
+            if (memcmp(t->slots[s].ip, key.ip, 16) == 0) {
+                const uint32_t first = t->slots[s].row;
+                delete t;
+                return fail(h, NFAGG_EINVAL, "Kubernetes entries %u and %zu carry the same address", first, r);
+            }
+            s = (s + 1) & (cap - 1);
+        }
+        key.row = (uint32_t)r;
+        t->slots[s] = key;
+        K8sRow& row = t->rows[r];
+        row = K8sRow{};
+        for (int side = 0; side < 2; side++) {
+            bool bad_string;
+            if (!k8s_render(e, side, piece, &bad_string) || piece.size() > kK8sMaxRendered) {
+                const size_t got = piece.size();
+                delete t;
+                if (bad_string) return fail(h, NFAGG_EINVAL, "Kubernetes entry %zu: null string with a length", r);
+                return fail(h, NFAGG_EINVAL, "Kubernetes entry %zu: its %s block has %s%zu bytes, the cap is %u", r, side ? "DstK8S" : "SrcK8S",
+                            got ? "" : "more than ", got ? got : (size_t)kK8sMaxRendered, kK8sMaxRendered);
+            }
+            const uint32_t off = (uint32_t)(t->blob.size() / 16);
+            t->blob.insert(t->blob.end(), piece.begin(), piece.end());
+            t->blob.resize((t->blob.size() + 15) / 16 * 16, 0);          // the kernels read a block 16 bytes at a time
+            if (side == 0) { row.src_off = off; row.src_len = (uint16_t)piece.size(); }
+            else { row.dst_off = off; row.dst_len = (uint16_t)piece.size(); }
+        }
+        row.flags = layer && k8s_is_app(e, *layer) ? kK8sRowApp : 0u;
+    }
+    if (h) {
+        auto up = [&]() -> int {
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMalloc(&t->d_slots, cap * sizeof(K8sSlot)));
+            HIP_TRY(h, hipMalloc(&t->d_rows, std::max<size_t>(n, 1) * sizeof(K8sRow)));
+            HIP_TRY(h, hipMalloc(&t->d_blob, std::max<size_t>(t->blob.size(), 16)));
+            HIP_TRY(h, hipMemcpy(t->d_slots, t->slots.data(), cap * sizeof(K8sSlot), hipMemcpyHostToDevice));
+            if (n) HIP_TRY(h, hipMemcpy(t->d_rows, t->rows.data(), n * sizeof(K8sRow), hipMemcpyHostToDevice));
+            if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
+            return NFAGG_OK;
+        };
+        const int rc = up();
+        if (rc != NFAGG_OK) { nfagg_k8s_table_destroy(t); return rc; }
+    }
+    *table = t;
+    return NFAGG_OK;
+}
+
+void nfagg_k8s_table_destroy(nfagg_k8s_table* t) {
+    if (!t) return;
+    if (t->h && (t->d_slots || t->d_rows || t->d_blob)) {
+        (void)hipSetDevice(t->h->device);
+        (void)hipStreamSynchronize(t->h->stream);
+        if (t->d_slots) (void)hipFree(t->d_slots);
+        if (t->d_rows) (void)hipFree(t->d_rows);
+        if (t->d_blob) (void)hipFree(t->d_blob);
+    }
+    delete t;
+}
+
+int nfagg_k8s_resolve_device(nfagg_handle* h, const nfagg_k8s_table* table, const void* d_records, size_t n, uint32_t* d_rows) {
+    if (!h || !table || (n && (!d_records || !d_rows))) return fail(h, NFAGG_EINVAL, "null argument");
+    if (table->h != h || !table->d_slots) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
+    if (((uintptr_t)d_records & 15u) != 0 || ((uintptr_t)d_rows & 7u) != 0) return fail(h, NFAGG_EINVAL, "device records must be 16-byte, rows 8-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (n) {
+        hipError_t e = launch_k8s_resolve(d_records, n, k8s_dev(table), d_rows, h->stream);
+        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+int nfagg_k8s_resolve(nfagg_handle* h, const nfagg_k8s_table* table, const void* records, size_t n, uint32_t* rows) {
+    if (!h || !table || (n && (!records || !rows))) return fail(h, NFAGG_EINVAL, "null argument");
+    auto& S = h->enc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+    if ((rc = nfagg_k8s_resolve_device(h, table, S.in_records.p, n, (uint32_t*)S.k8s_rows.p)) != NFAGG_OK) return rc;
+    if (n) HIP_TRY(h, hipMemcpyAsync(rows, S.k8s_rows.p, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+uint32_t nfagg_flp_json_k8s_max_line(int policy) { return flp_k8s_max_line(policy); }
+
+int nfagg_encode_flp_json_k8s_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* d_out, size_t out_cap,
+                                     uint64_t* d_line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+}
+
+int nfagg_encode_flp_json_k8s(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* out, size_t out_cap,
+                              uint64_t* line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table};
     return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/nfagg.h"
+#include "nfagg_hash.h"
 #include "nfagg_pb.h"
 
 namespace nfagg {
@@ -36,6 +37,24 @@ struct TlsDev {
     uint32_t n[kTlsKinds];
 };
 
+// The Kubernetes table of nfagg_k8s_table_create on the device (nfagg_k8s.h). Slots: open addressing over the 16 address
+// bytes, a power of two of them, at most half in use, home slot = the low bits of k8s_hash, linear probe; a slot is 32
+// bytes so that one aligned read holds the key and the row (row == kK8sNoRow: free). Rows: where the row's two rendered
+// blocks (",\"SrcK8S_..\":..", ",\"DstK8S_..\":..", each at most kK8sMaxRendered bytes) start in the blob, in 16-byte units,
+// and their lengths; kK8sRowApp: the namespace is not empty and objectIsApp holds (enrich.go:143-165).
+constexpr uint32_t kK8sNoRow = NFAGG_K8S_NO_ROW, kK8sMaxRendered = NFAGG_K8S_MAX_RENDERED, kK8sSeedIndex = 3, kK8sRowApp = 1;
+NF_HD uint64_t k8s_hash(uint64_t lo, uint64_t hi) { return ip_hash(lo, hi, kK8sSeedIndex); }
+struct K8sSlot { uint32_t ip[4]; uint32_t row; uint32_t pad_[3]; };
+struct K8sRow { uint32_t src_off, dst_off; uint16_t src_len, dst_len; uint32_t flags; };
+static_assert(sizeof(K8sSlot) == 32 && sizeof(K8sRow) == 16, "Kubernetes table layout");
+struct K8sDev {
+    const K8sSlot* slots;         // mask + 1 of them, 32-byte aligned
+    const K8sRow* rows;
+    const uint8_t* blob;          // 16-byte aligned
+    uint32_t mask, n_rows;
+    uint32_t has_layer;           // the table was created with a layer: every line carries K8S_FlowLayer
+};
+
 // Line lengths (0 = deferred) and the seven resolved interface rows per record (d_rows: 8 dwords per record, rows 0..6
 // and the length), block-local scan, scan of the block sums: d_block_base[ceil(n / 1024)] = total bytes afterwards. Then the
 // write pass. F (optional) names the feature parts of full BpfFlowContents as it does for the protobuf encoder; with
@@ -49,5 +68,16 @@ hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, 
                             uint8_t* d_deferred, hipStream_t s);
 // The longest line each policy can write with T (0: plain, 1: content, 2: content with network events).
 uint32_t flp_tls_max_line(int policy);
+
+// The same two passes with the Kubernetes enrichment on top of T (required): d_k8s_rows holds two rows per record, as
+// launch_k8s_resolve (nfagg_k8s.hip: one lane per flow, two probes of K) wrote them. Nothing is deferred.
+hipError_t launch_k8s_resolve(const void* d_recs, uint64_t n, const K8sDev& K, uint32_t* d_rows_out, hipStream_t s);
+hipError_t launch_flp_k8s_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                               const uint32_t* d_k8s_rows, uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base,
+                               hipStream_t s);
+hipError_t launch_flp_k8s_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                                const uint32_t* d_k8s_rows, const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base,
+                                void* d_out, uint64_t* d_line_offsets, hipStream_t s);
+uint32_t flp_k8s_max_line(int policy);
 
 }  // namespace nfagg

@@ -16,13 +16,15 @@
 //
 // Same two passes, same window scheme, same encode_line and the same two kernels as nfagg_flp.hip (k_flp_size<Feat>,
 // k_flp_write<Feat> of nfagg_flp_line.h), with FlpContent as the feature policy: this file compiles them for FlpContent,
-// FlpContentNetev and FlpTls (nfagg_tls.h) over those two and over FlpPlain, and selects. A lane reads the parts its
+// FlpContentNetev and FlpTls (nfagg_tls.h) over those two and over FlpPlain, and selects; it also compiles the kernel pair of
+// nfagg_k8s.h for FlpK8s over the three TLS policies. A lane reads the parts its
 // present byte names with 16- and 8-byte loads before anything is emitted, keeps the fields the line needs in registers
 // and the DNS name in a 32-byte LDS slot of its own. The names of response codes, TCP states and drop causes sit in one
 // constant blob with an offset and a length per name; the counting pass reads only the lengths.
 #include "nfagg_flp_line.h"
 #include "nfagg_netev.h"
 #include "nfagg_tls.h"
+#include "nfagg_k8s.h"
 
 namespace nfagg {
 
@@ -279,6 +281,9 @@ struct FlpContent {
     }
     template <typename S> NF_DEV void tls_names(S&, const Rec&) const {}     // a record with these keys is deferred; FlpTls has them
     template <typename S> NF_DEV void tls_version(S&, const Rec&) const {}
+    template <typename S> NF_DEV void k8s_dst(S&) const {}                   // FlpK8s (nfagg_k8s.h) has the Kubernetes keys
+    template <typename S> NF_DEV void k8s_layer(S&) const {}
+    template <typename S> NF_DEV void k8s_src(S&) const {}
 };
 
 // FlpContent plus the flow's network events: the table rows nfagg_netev_resolve wrote (PbFeat::ne_rows), each row's JSON
@@ -330,6 +335,29 @@ hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, 
         return flp_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T ? *T : TlsDev{}, d_rows, d_local_off, d_block_base,
                                                              d_out, d_line_offsets, d_deferred, s); });
 }
+
+// The Kubernetes enrichment: FlpK8s over the three TLS policies, in the kernel pair of nfagg_k8s.h.
+template <typename Fn> static hipError_t flp_k8s_select(const PbFeat* F, Fn fn) {
+    return !F ? fn(FlpPolicy<FlpK8s<FlpTls<FlpPlain>>>{}) : F->ne_rows ? fn(FlpPolicy<FlpK8s<FlpTls<FlpContentNetev>>>{}) : fn(FlpPolicy<FlpK8s<FlpTls<FlpContent>>>{});
+}
+
+hipError_t launch_flp_k8s_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                               const uint32_t* d_k8s_rows, uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base,
+                               hipStream_t s) {
+    return flp_k8s_select(F, [&](auto policy) {
+        return k8s_size_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, d_k8s_rows, d_rows, d_local_off, d_block_sum,
+                                                            d_block_base, s); });
+}
+
+hipError_t launch_flp_k8s_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                                const uint32_t* d_k8s_rows, const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base,
+                                void* d_out, uint64_t* d_line_offsets, hipStream_t s) {
+    return flp_k8s_select(F, [&](auto policy) {
+        return k8s_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, d_k8s_rows, d_rows, d_local_off, d_block_base,
+                                                             d_out, d_line_offsets, s); });
+}
+
+uint32_t flp_k8s_max_line(int policy) { return flp_tls_max_line(policy) ? flp_tls_max_line(policy) + kK8sLineMax : 0u; }
 
 uint32_t flp_tls_max_line(int policy) {
     return policy == 0 ? FlpTls<FlpPlain>::kMaxLine : policy == 1 ? FlpTls<FlpContent>::kMaxLine : policy == 2 ? FlpTls<FlpContentNetev>::kMaxLine : 0u;

@@ -169,11 +169,12 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
     return k == 0 ? r.d[24] & 0xffu : k <= 4 ? (r.d[25] >> (8 * (k - 1))) & 0xffu : (r.d[26] >> (8 * (k - 5))) & 0xffu;
 }
 
-// The keys of a flow's feature parts (DNS, drops, xlat, RTT / IPsec, QUIC, network events) fall in ten contiguous groups of
+// The keys of a flow's feature parts (DNS, drops, xlat, RTT / IPsec, QUIC, network events) fall in contiguous groups of
 // the sorted line; encode_line calls one hook of its feature policy at each. NoFeat: a record that carries only BpfFlowMetrics,
 // every hook is empty and the line is the one of decode_protobuf.go:57-127. FlpContent (nfagg_flp_content.hip) holds
 // the parts of a full BpfFlowContent, FlpContentNetev adds the flow's resolved network events. The two TLS hooks take the
 // record: they are empty in all three, and a record that would need them is deferred; FlpTls (nfagg_tls.h) fills them.
+// The three Kubernetes hooks are empty in all of these; FlpK8s (nfagg_k8s.h) fills them, in kernels of its own.
 //
 // What k_flp_size<Feat> and k_flp_write<Feat> ask of a policy beside the hooks, all of it known when they are compiled:
 //   kWindow   line starts a window of the write kernel takes, from its 16-byte aligned base
@@ -197,6 +198,9 @@ struct NoFeat {
     template <typename S> NF_DEV void zone(S&) const {}       // ZoneId        last
     template <typename S> NF_DEV void tls_names(S&, const Rec&) const {}     // TLSCipherSuite TLSGroup  after SrcPort
     template <typename S> NF_DEV void tls_version(S&, const Rec&) const {}   // TLSVersion               after TLSTypes
+    template <typename S> NF_DEV void k8s_dst(S&) const {}    // DstK8S_*      after DstAddr
+    template <typename S> NF_DEV void k8s_layer(S&) const {}  // K8S_FlowLayer after Interfaces, before NetworkEvents
+    template <typename S> NF_DEV void k8s_src(S&) const {}    // SrcK8S_*      after SrcAddr
 };
 // The plain policy: the line of the records Accounter.evict produces.
 struct FlpPlain : NoFeat {
@@ -222,6 +226,7 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
     if (ip) {
         lit(s, ",\"Dscp\":"); dec<3>(s, r.dscp());
         lit(s, ",\"DstAddr\":\""); ip_text(s, Ip4w{{r.d[4], r.d[5], r.d[6], r.d[7]}}); s.put('"');
+        f.k8s_dst(s);
     }
     lit(s, ",\"DstMac\":\""); mac_text(s, r.dmac()); s.put('"');
     if (ports) { lit(s, ",\"DstPort\":"); dec<5>(s, r.d[8] >> 16); }
@@ -247,13 +252,14 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
             esc_str(s, e + kFlpEscNameOff, lens[k] & 0xffffu);
         }
     s.put(']');
+    f.k8s_layer(s);
     f.netev(s);
     if (r.packets()) { lit(s, ",\"Packets\":"); dec<10>(s, r.packets()); }
     f.drops(s);
     if (ip) { lit(s, ",\"Proto\":"); dec<3>(s, proto); }
     f.quic(s);
     if (r.sampling()) { lit(s, ",\"Sampling\":"); dec<10>(s, r.sampling()); }
-    if (ip) { lit(s, ",\"SrcAddr\":\""); ip_text(s, Ip4w{{r.d[0], r.d[1], r.d[2], r.d[3]}}); s.put('"'); }
+    if (ip) { lit(s, ",\"SrcAddr\":\""); ip_text(s, Ip4w{{r.d[0], r.d[1], r.d[2], r.d[3]}}); s.put('"'); f.k8s_src(s); }
     lit(s, ",\"SrcMac\":\""); mac_text(s, r.smac()); s.put('"');
     if (ports) { lit(s, ",\"SrcPort\":"); dec<5>(s, r.d[8] & 0xffffu); }
     f.tls_names(s, r);

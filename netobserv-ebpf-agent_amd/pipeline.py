@@ -219,11 +219,15 @@ class MapTracer:
             self._netevTable.close()
             self._netevTable = None
 
-    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None):
+    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None, k8s=None):
         """evictFlows for a direct-FLP `write: stdout, format: json` stage, without a Record per flow: the drained maps are merged,
         decorated with the sample decoder's network events and encoded on the GPU. Returns (buf, line_offsets, deferred) as
         FlowTable.encode_flp_json_content does; with tls_names (a TlsNames of the fetcher's table) the TLS keys are written too,
-        nothing is deferred and the result is (buf, line_offsets) as FlowTable.encode_flp_json_tls gives it."""
+        nothing is deferred and the result is (buf, line_offsets) as FlowTable.encode_flp_json_tls gives it. With k8s (a K8sTable of the
+        fetcher's table; needs tls_names) the lines carry what the `transform network` stage's Kubernetes rules add as well
+        (FlowTable.encode_flp_json_k8s)."""
+        if k8s is not None and tls_names is None:
+            raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         monotonic_now, current = self.monoClock(), self.clock()
         table = self.mapFetcher.table
         main_ids, main_vals, feats, n_cpu = self.mapFetcher.drain()
@@ -231,10 +235,14 @@ class MapTracer:
         names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         mono = monotonic_now & ((1 << 64) - 1)
         if self.sampleDecoder is None:                                  # s == nil: no events, no injected drops (record.go:126)
+            if k8s is not None:
+                return table.encode_flp_json_k8s(recs, tls_names, k8s, current, mono, names, agent_ip, time_received, unknown, present, parts)
             if tls_names is not None:
                 return table.encode_flp_json_tls(recs, tls_names, current, mono, names, agent_ip, time_received, unknown, present, parts)
             return table.encode_flp_json_content(recs, present, parts, current, mono, names, agent_ip, time_received, unknown)
         p_out, parts, rows, tab = self.resolveNetworkEvents(present, parts)
+        if k8s is not None:
+            return table.encode_flp_json_k8s(recs, tls_names, k8s, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         if tls_names is not None:
             return table.encode_flp_json_tls(recs, tls_names, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         return table.encode_flp_json_netev(recs, p_out, parts, rows, tab, current, mono, names, agent_ip, time_received, unknown)
@@ -349,12 +357,16 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
     defers (TLS version / cipher suite / key share set) is formatted by `fallback(record, now_ns, mono_ns) -> bytes`, the
     whole line with its newline, and written at its place; the default raises, as RecordToMap does for such a record.
     With `tls_names` (a TlsNames of `table`) the encoder writes those records' TLS keys itself (FlowTable.encode_flp_json_tls):
-    nothing is deferred, `fallback` is never called and an eviction is one write.
+    nothing is deferred, `fallback` is never called and an eviction is one write. With `k8s` as well (a K8sTable of `table`; needs
+    `tls_names`) the lines are those of the pipeline NetObserv ships, with the Kubernetes rules of its `transform network` stage in
+    front of the writer (FlowTable.encode_flp_json_k8s).
 
     One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
 
     def __init__(self, table, stream, names=None, agent_ip=None, unknown: bytes = b"unknown", time_received: Callable[[], int] = None,
-                 fallback: Callable = None, encode=None, tls_names=None):
+                 fallback: Callable = None, encode=None, tls_names=None, k8s=None):
+        if k8s is not None and tls_names is None:
+            raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         self.table, self.stream = table, stream
         self.names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         self.agent_ip, self.unknown = agent_ip, unknown
@@ -363,7 +375,7 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         self.lines = self.deferred = 0
         # encode(raw, now_ns, mono_ns, names, agent_ip, time_received, unknown) -> (buf, line_offsets, deferred)
         self._encode = encode or table.encode_flp_json
-        self.tls_names = tls_names
+        self.tls_names, self.k8s = tls_names, k8s
 
     def ExportEvicted(self, raw, now_ns: int, mono_ns: int) -> int:
         """One eviction's lines. now_ns / mono_ns: the eviction's currentTime / monotonicCurrentTime (account.go:103-104).
@@ -372,8 +384,12 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         if n == 0:
             return 0
         if self.tls_names is not None:
-            buf, off = self.table.encode_flp_json_tls(raw, self.tls_names, now_ns, mono_ns & ((1 << 64) - 1), self.names, self.agent_ip,
-                                                      self.time_received(), self.unknown)
+            if self.k8s is not None:
+                buf, off = self.table.encode_flp_json_k8s(raw, self.tls_names, self.k8s, now_ns, mono_ns & ((1 << 64) - 1), self.names,
+                                                          self.agent_ip, self.time_received(), self.unknown)
+            else:
+                buf, off = self.table.encode_flp_json_tls(raw, self.tls_names, now_ns, mono_ns & ((1 << 64) - 1), self.names, self.agent_ip,
+                                                          self.time_received(), self.unknown)
             self.stream.write(memoryview(np.ascontiguousarray(buf))[:int(off[n])])
             self.lines += n
             return n

@@ -456,10 +456,11 @@ class FlowTable:
         return rc, need.value
 
     # -- export encode (record -> direct-FLP JSON lines), nfagg_encode_flp_json*
-    def _flp_json(self, records, options, features=None, rows=None, netev_table=None, tls_names=None):
+    def _flp_json(self, records, options, features=None, rows=None, netev_table=None, tls_names=None, k8s=None):
         """The host-memory entry points. options: flp_options(...). features: None (nfagg_encode_flp_json) or (present, parts)
         (the *_content ones; present None: no flow carries a part). rows and netev_table: the *_netev one. tls_names:
-        nfagg_encode_flp_json_tls, which takes the others as options and defers nothing. Returns (buf, line_offsets, deferred)."""
+        nfagg_encode_flp_json_tls, which takes the others as options and defers nothing; k8s (with tls_names): nfagg_encode_flp_json_k8s.
+        Returns (buf, line_offsets, deferred)."""
         r = np.ascontiguousarray(records)
         n = r.nbytes // 144
         o, keep = options
@@ -475,6 +476,8 @@ class FlowTable:
         ne_args = (rw.ctypes.data_as(C.c_void_p) if rw is not None else None, netev_table._t if netev_table is not None else None)
         if tls_names is not None:
             fn, head, flags = L.lib.nfagg_encode_flp_json_tls, head + f_arg + ne_args + (tls_names._t,), ()
+            if k8s is not None:
+                fn, head = L.lib.nfagg_encode_flp_json_k8s, head + (k8s._t,)
         else:
             flags = (deferred.ctypes.data_as(C.c_void_p), C.byref(n_def))
             if netev_table is not None:
@@ -483,13 +486,13 @@ class FlowTable:
                 fn, head = L.lib.nfagg_encode_flp_json_content, head + f_arg
             else:
                 fn = L.lib.nfagg_encode_flp_json
-        per_flow = 448 if fn is L.lib.nfagg_encode_flp_json else 640
+        per_flow = 448 if fn is L.lib.nfagg_encode_flp_json else 1024 if k8s is not None else 640
         buf = self._encode_grown(n, per_flow, lambda p, cap, need: fn(*head, C.byref(o), p, cap, off.ctypes.data_as(C.c_void_p), *flags, need))
         assert int(deferred.sum()) == n_def.value
         return buf, off, deferred
 
     def _flp_json_device(self, d_records, n, options, d_out, out_cap, d_line_offsets, d_deferred=0, features=None, d_rows=0,
-                         netev_table=None, tls_names=None):
+                         netev_table=None, tls_names=None, k8s=None):
         """The device entry points (raw device pointers); the optionals select as in _flp_json, features = (d_present, d_parts).
         Returns (rc, bytes needed/written, deferred records)."""
         o, keep = options
@@ -503,6 +506,8 @@ class FlowTable:
         flags = (C.c_void_p(d_deferred or None), C.byref(n_def))
         if tls_names is not None:
             fn, head, flags = L.lib.nfagg_encode_flp_json_tls_device, head + f_arg + ne_args + (tls_names._t,), ()
+            if k8s is not None:
+                fn, head = L.lib.nfagg_encode_flp_json_k8s_device, head + (k8s._t,)
         elif netev_table is not None:
             fn, head = L.lib.nfagg_encode_flp_json_content_netev_device, head + f_arg + ne_args
         elif features is not None:
@@ -630,6 +635,43 @@ class FlowTable:
         return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
                                      d_out, out_cap, d_line_offsets, 0, (d_present, d_parts) if d_present else None, d_rows, netev_table,
                                      tls_names)[:2]
+
+    # -- Kubernetes enrichment (nfagg_k8s_*): the informers' answers as a table, the hash join and the keys on the GPU
+    def k8s_table(self, entries, layer=None) -> "K8sTable":
+        """A Kubernetes table on this handle's device; entries and layer as K8sTable takes them."""
+        return K8sTable(entries, layer, self)
+
+    def k8s_resolve(self, table: "K8sTable", records: np.ndarray) -> np.ndarray:
+        """nfagg_k8s_resolve: uint32[n, 2], the table rows of each record's src_ip and dst_ip (L.K8S_NO_ROW: none; both for
+        a record that is not IP)."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        rows = np.zeros((n, 2), dtype=np.uint32)
+        self._check(L.lib.nfagg_k8s_resolve(self._h, table._t, r.ctypes.data_as(C.c_void_p) if n else None, n,
+                                            rows.ctypes.data_as(C.c_void_p) if n else None))
+        return rows
+
+    def k8s_resolve_device(self, table: "K8sTable", d_records: int, n: int, d_rows: int) -> None:
+        """Device-resident variant (raw device pointers; d_rows: 2n uint32)."""
+        self._check(L.lib.nfagg_k8s_resolve_device(self._h, table._t, C.c_void_p(d_records or None), n, C.c_void_p(d_rows or None)))
+
+    def encode_flp_json_k8s(self, records: np.ndarray, tls_names: "TlsNames", k8s: "K8sTable", now_unix_ns: int, mono_now_ns: int,
+                            names: np.ndarray, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", present=None, parts=None,
+                            rows=None, netev_table: "NetevTable" = None):
+        """encode_flp_json_tls plus the Kubernetes keys of both endpoints and, for a table with a layer, K8S_FlowLayer
+        (nfagg_encode_flp_json_k8s). Returns (buf, line_offsets)."""
+        return self._flp_json(records, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown), (present, parts),
+                              rows, netev_table, tls_names, k8s)[:2]
+
+    def encode_flp_json_k8s_device(self, d_records: int, n: int, tls_names: "TlsNames", k8s: "K8sTable", now_unix_ns: int, mono_now_ns: int,
+                                   names: np.ndarray, agent_ip, time_received: int, d_out: int, out_cap: int, d_line_offsets: int,
+                                   unknown: bytes = b"unknown", d_present: int = 0, d_parts=None, d_rows: int = 0,
+                                   netev_table: "NetevTable" = None):
+        """Device-resident variant (raw device pointers; d_present = 0: no parts; d_out = 0 asks for the size). Returns (rc,
+        bytes needed/written)."""
+        return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
+                                     d_out, out_cap, d_line_offsets, 0, (d_present, d_parts) if d_present else None, d_rows, netev_table,
+                                     tls_names, k8s)[:2]
 
     def stats(self) -> L.Stats:
         s = L.Stats()
@@ -1010,6 +1052,108 @@ def key_hash(flow_id_bytes: bytes) -> int:
 def shard_of(flow_id_bytes: bytes, n_shards: int) -> int:
     buf = (C.c_uint8 * 40).from_buffer_copy(bytes(flow_id_bytes)[:40])
     return L.lib.nfagg_shard_of(buf, n_shards)
+
+
+K8S_FIELDS = ("namespace", "name", "kind", "owner_name", "owner_kind", "network_name", "host_ip", "host_name", "zone")
+
+
+def _k8s_ip16(ip) -> bytes:
+    """net.IP.To16() of an address given as 16 bytes, 4 bytes or text."""
+    if isinstance(ip, str):
+        import ipaddress
+        ip = ipaddress.ip_address(ip).packed
+    ip = bytes(ip)
+    if len(ip) == 4:
+        ip = bytes(10) + b"\xff\xff" + ip
+    if len(ip) != 16:
+        raise ValueError("an address has 4 or 16 bytes")
+    return ip
+
+
+def _k8s_entry(ip, info: dict):
+    """nfagg_k8s_entry of what IndexLookup(nil, ip) returned: info maps K8S_FIELDS to str or bytes (absent: empty); zone None or
+    absent: the label does not exist. Returns (entry, the objects it points into)."""
+    e = L.K8sEntry()
+    e.ip[:] = _k8s_ip16(ip)
+    unknown = set(info) - set(K8S_FIELDS)
+    if unknown:
+        raise ValueError("unknown Kubernetes fields %r" % sorted(unknown))
+    keep = []
+    for f in K8S_FIELDS:
+        v = info.get(f)
+        v = b"" if v is None else v.encode() if isinstance(v, str) else bytes(v)
+        keep.append(v)
+        setattr(e, "namespace_" if f == "namespace" else f, v)
+        setattr(e, f + "_len", len(v))
+    e.has_zone = 1 if info.get("zone") is not None else 0
+    return e, keep
+
+
+def _k8s_layer(layer):
+    """nfagg_k8s_layer of (infra_prefixes, infra_refs): prefixes [str], refs [(namespace, name)]. Returns (struct, keep)."""
+    prefixes, refs = layer
+    pre = [p.encode() if isinstance(p, str) else bytes(p) for p in prefixes]
+    flat = [x.encode() if isinstance(x, str) else bytes(x) for ref in refs for x in ref]
+    if any(b"\0" in x for x in pre + flat):
+        raise ValueError("layer strings are NUL-terminated")
+    a, b = (C.c_char_p * max(len(pre), 1))(*pre), (C.c_char_p * max(len(flat), 1))(*flat)
+    s = L.K8sLayer(C.sizeof(L.K8sLayer), len(pre), a, b, len(flat) // 2, 0)
+    return s, (a, b, pre, flat)
+
+
+def k8s_render(ip, info: dict, side: int) -> bytes:
+    """nfagg_k8s_render: the block of keys the encoder writes behind SrcAddr (side 0) or DstAddr (side 1) for this answer,
+    with its leading comma. Host only."""
+    e, keep = _k8s_entry(ip, info)
+    buf = np.zeros(L.K8S_MAX_RENDERED, dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = L.lib.nfagg_k8s_render(C.byref(e), side, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n))
+    if rc != L.OK:
+        raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
+    return buf[:n.value].tobytes()
+
+
+class K8sTable:
+    """The Kubernetes informers' answers as a table (nfagg_k8s_table_create): entries = [(ip, info)], ip as 16 bytes, 4 bytes
+    or text, info as _k8s_entry takes it (what IndexLookup(nil, ip) returned, plus the zone fillInK8sZone would pick).
+    layer: None (no K8S_FlowLayer key) or (infra_prefixes, infra_refs) of the add_kubernetes_infra rule. With a FlowTable
+    the table lives on its device and serves k8s_resolve and encode_flp_json_k8s; with table=None it is built and checked on
+    the host only. Row r, as k8s_resolve reports it, is entries[r]. Rebuild the table when the informer caches changed."""
+
+    def __init__(self, entries, layer=None, table: "FlowTable" = None):
+        entries = list(entries)
+        made = [_k8s_entry(ip, info) for ip, info in entries]
+        arr = (L.K8sEntry * max(len(made), 1))(*[e for e, _ in made])
+        lay, keep = _k8s_layer(layer) if layer is not None else (None, None)
+        self._t = C.c_void_p()
+        h = table._h if table is not None else None
+        rc = L.lib.nfagg_k8s_table_create(h, arr, len(made), C.byref(lay) if lay is not None else None, C.byref(self._t))
+        if rc != L.OK:
+            self._t = None
+            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
+        self._owner = table                       # the handle must outlive the table
+        self.n, self.has_layer = len(made), layer is not None
+
+    def __len__(self):
+        return self.n
+
+    def close(self):
+        if getattr(self, "_t", None):
+            if self._owner is None or self._owner._h:
+                L.lib.nfagg_k8s_table_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def ip_hash(ip16: bytes, seed_index: int) -> int:

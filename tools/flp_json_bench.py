@@ -16,7 +16,13 @@ as a fraction of 8 TB/s. Kernel-level device time: run under rocprofv3 --kernel-
 --tls: the TLS-name leg. The flows evicted at the larger size are encoded twice in one process: with their TLS fields clear
 through nfagg_encode_flp_json_device, the yardstick, then with ssl_version / tls_cipher_suite / tls_key_share set on a seeded
 half of them (known and unknown ids, the mismatch flag on some) through nfagg_encode_flp_json_tls_device with the default
-name table. Both report their time per flow and per output byte."""
+name table. Both report their time per flow and per output byte.
+
+--k8s: the Kubernetes leg, at both sizes. The evicted flows are encoded through nfagg_encode_flp_json_tls_device, the yardstick,
+and through nfagg_encode_flp_json_k8s_device with a table of 100 000 rows and a layer: every other distinct address of the
+evicted flows (as many as fit), filled up with addresses no flow has. The hash join alone (nfagg_k8s_resolve_device) is timed
+too. Kernel-level device time: run the same leg under rocprofv3 --kernel-trace --output-format csv -d DIR, then
+--k8s-trace DIR prints the median device time of every encoder kernel per launch size from that trace."""
 import io
 import os
 import queue
@@ -39,6 +45,8 @@ agent = bytes(10) + b"\xff\xff" + bytes([10, 0, 0, 1])
 NOW, MONO = 10**18, 10**12
 CONTENT = "--content" in sys.argv[1:]
 TLS = "--tls" in sys.argv[1:]
+K8S = "--k8s" in sys.argv[1:]
+K8S_ROWS = 100_000
 PART_BYTES = {"additional": 32, "dns": 64, "drops": 32, "xlat": 56, "quic": 24}
 
 
@@ -84,6 +92,45 @@ def set_tls_fields(d_ev, m, seed=7):
     return int(on.sum())
 
 
+def k8s_entries(d_ev, m):
+    """K8S_ROWS informer answers: every other distinct address of the m evicted flows' IP records, as many as fit, then
+    addresses no flow has. Returns (entries, distinct addresses, flows that are IP)."""
+    recs = d_ev[: m * 144].cpu().numpy().view(nf.FLOW_RECORD)
+    ip = np.isin(recs["metrics"]["eth_protocol"], (0x0800, 0x86DD))
+    both = np.concatenate([recs["id"]["src_ip"][ip], recs["id"]["dst_ip"][ip]])
+    distinct = np.unique(np.ascontiguousarray(both).view("V16").reshape(-1))
+    take = [a.tobytes() for a in distinct[::2][:K8S_ROWS]]
+    fill = [b"\xfd\x00" + bytes(10) + k.to_bytes(4, "big") for k in range(K8S_ROWS - len(take))]
+    info = lambda k: dict(namespace="openshift-dns" if k % 10 == 0 else "ns-%d" % (k % 50), name="pod-%d" % k, kind="Pod",  # noqa: E731
+                          owner_name="deploy-%d" % (k % 5000), owner_kind="Deployment", network_name="primary", host_ip="10.0.0.%d" % (k % 200),
+                          host_name="node-%d" % (k % 200), zone="zone-%s" % "abc"[k % 3])
+    return [(a, info(k)) for k, a in enumerate(take + fill)], len(distinct), int(ip.sum())
+
+
+def k8s_trace(root):
+    """Median device time per (kernel, launch size) of the encoder kernels in a rocprofv3 kernel trace below `root`."""
+    import csv
+    import glob
+    import re
+    spans = {}
+    for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
+        for row in csv.DictReader(open(f)):
+            name = row["Kernel_Name"]
+            if not re.search(r"k_flp_|k_k8s_|scan", name):
+                continue
+            short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
+            grid = int(row.get("Grid_Size_X") or row.get("Grid_Size") or 0)
+            spans.setdefault((short, grid), []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+    print("device time per launch from the kernel trace, median over the launches of one size, us:")
+    for (short, grid), v in sorted(spans.items(), key=lambda kv: (kv[0][1] > 4_000_000, kv[0][0], kv[0][1])):
+        print(f"  {short:48s} grid {grid:9d}: {float(np.median(v)):9.1f}  min {min(v):9.1f}  max {max(v):9.1f}  ({len(v)} launches)")
+
+
+if "--k8s-trace" in sys.argv[1:]:
+    k8s_trace(sys.argv[sys.argv.index("--k8s-trace") + 1])
+    sys.exit(0)
+
+
 def per_byte(what, m, dt, wrote):
     print(f"  {what:8s} {m} flows -> {wrote} bytes ({wrote / m:.1f} B/line) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s, "
           f"{dt / wrote * 1e12:.3f} ps per output byte")
@@ -108,6 +155,8 @@ def line(what, m, dt, wrote, extra_per_flow):
 
 
 for flows in ((10_000_000,) if CONTENT or TLS else (1_000_000, 10_000_000)):
+    if K8S:
+        torch.cuda.empty_cache()
     n = 4 * flows
     d_th = torch.from_numpy(synth.zipf_thresholds(flows, 1.1).view(np.int64)).cuda()
     d = torch.empty(n * 144, dtype=torch.uint8, device="cuda")
@@ -120,6 +169,31 @@ for flows in ((10_000_000,) if CONTENT or TLS else (1_000_000, 10_000_000)):
         d_ev = torch.empty(flows * 144 + 16, dtype=torch.uint8, device="cuda")
         m = tab.evict_device(d_ev.data_ptr(), flows)
         print(f"{flows} keys, {n} records -> {m} evicted flows")
+        if K8S:
+            entries, n_distinct, n_ip = k8s_entries(d_ev, m)
+            d_off = torch.empty(m + 1, dtype=torch.int64, device="cuda")
+            d_rows = torch.empty((m, 2), dtype=torch.int32, device="cuda")
+            with tab.tls_names() as tls, tab.k8s_table(entries, (["openshift", "kube-"], [("ns-1", "pod-1")])) as k8s:
+                rc, need = tab.encode_flp_json_tls_device(d_ev.data_ptr(), m, tls, NOW, MONO, names, agent, 1_700_000_000, 0, 0, d_off.data_ptr())
+                d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+                (rc, wrote), dt = timed(lambda: tab.encode_flp_json_tls_device(d_ev.data_ptr(), m, tls, NOW, MONO, names, agent, 1_700_000_000,
+                                                                              d_out.data_ptr(), need, d_off.data_ptr()))
+                assert rc == nf.OK and wrote == need
+                per_byte("_tls", m, dt, wrote)
+                del d_out
+                _, dt_res = timed(lambda: tab.k8s_resolve_device(k8s, d_ev.data_ptr(), m, d_rows.data_ptr()))
+                hits = int((d_rows != -1).sum())
+                rc, need = tab.encode_flp_json_k8s_device(d_ev.data_ptr(), m, tls, k8s, NOW, MONO, names, agent, 1_700_000_000, 0, 0, d_off.data_ptr())
+                d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+                (rc, wrote), dt = timed(lambda: tab.encode_flp_json_k8s_device(d_ev.data_ptr(), m, tls, k8s, NOW, MONO, names, agent, 1_700_000_000,
+                                                                              d_out.data_ptr(), need, d_off.data_ptr()))
+                assert rc == nf.OK and wrote == need
+                per_byte("_k8s", m, dt, wrote)
+                print(f"           table: {len(entries)} rows, {min(K8S_ROWS, (n_distinct + 1) // 2)} of them among the {n_distinct} distinct addresses of {n_ip} IP flows; "
+                      f"{hits} of {2 * m} endpoints resolved; the hash join alone: {dt_res * 1e3:.3f} ms per call")
+                del d_out
+            del d_ev, d_off, d_rows
+            continue
         # direct-FLP JSON
         d_off = torch.empty(m + 1, dtype=torch.int64, device="cuda")
         d_def = torch.empty(m, dtype=torch.uint8, device="cuda")
