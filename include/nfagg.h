@@ -1076,7 +1076,8 @@ uint32_t nfagg_flp_json_tls_max_line(int policy);
 /*    label values keep a block near 1.5 KB before escapes);            */
 /*  - out of scope: secondary-network keys (MAC, interface, UDN         */
 /*    indexes), label and annotation copies, the otel assignee, other   */
-/*    output names, the remaining transform network rules.              */
+/*    output names. Three more transform network rules are further     */
+/*    down (nfagg_encode_flp_json_net); the others are out of scope.    */
 /* ------------------------------------------------------------------ */
 
 typedef struct nfagg_k8s_entry {      /* strings: pointer + length, arbitrary bytes, read during the call only */
@@ -1117,7 +1118,8 @@ int nfagg_k8s_render(const nfagg_k8s_entry* entry, int side, void* out, size_t c
  * keyed by the 16 address bytes (a power of two of slots, at most half in use, home slot = the low bits of
  * nfagg_ip_hash(ip, 3), linear probe). Row r, as nfagg_k8s_resolve reports it, is entries[r]. layer == NULL: the lines get
  * no K8S_FlowLayer key. Errors (NFAGG_EINVAL, nfagg_last_error names the entry): a duplicate address, a null string with
- * a length, a block over the cap, more than NFAGG_K8S_MAX_ROWS entries. With a handle the table is uploaded to that
+ * a length, a block over the cap, more than NFAGG_K8S_MAX_ROWS entries. Every row's host_ip TEXT is interned as well (one id per
+ * row, 0 for the empty string, in an array of its own): nfagg_encode_flp_json_net's reinterpret_direction compares ids. With a handle the table is uploaded to that
  * handle's device and serves its calls until destroyed; rebuild it when the informer caches changed. h == NULL builds and
  * checks the table on the host alone (errors through nfagg_last_error(NULL)); such a table is refused by the device calls. */
 int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size_t n, const nfagg_k8s_layer* layer, nfagg_k8s_table** table);
@@ -1149,6 +1151,150 @@ int nfagg_encode_flp_json_k8s_device(nfagg_handle* h, const void* d_records, siz
 /* The longest line nfagg_encode_flp_json_k8s can write: nfagg_flp_json_tls_max_line(policy) plus two blocks at the cap
  * and ,"K8S_FlowLayer":"infra"; 0 for an unknown policy. The write kernels size their LDS windows by it. */
 uint32_t nfagg_flp_json_k8s_max_line(int policy);
+
+/* ------------------------------------------------------------------ */
+/* Direction, subnet labels, TCP flag names — three more rules of the   */
+/* `transform network` stage that are pure per-flow work, on top of the */
+/* Kubernetes enrichment (paths under flowlogs-pipeline's pkg/):         */
+/*  - reinterpret_direction                                             */
+/*    (pipeline/transform/transform_network_direction.go:32-64) with    */
+/*    FlowDirectionField = FlowDirection, ReporterIPField = AgentIP,    */
+/*    SrcHostField = SrcK8S_HostIP, DstHostField = DstK8S_HostIP.       */
+/*    decode.RecordToMap writes no FlowDirection key                    */
+/*    (decode/decode_protobuf.go:57-128 has only IfDirections), so the  */
+/*    IfDirectionField copy of lines 33-35 never fires: no such key.    */
+/*    With s, d the two host-IP keys ("" when absent: no row, a row     */
+/*    with an empty host IP, a record that is not IP) and reporter the  */
+/*    text of AgentIP ("<nil>" for a nil address):                      */
+/*      s != d, s == reporter                  "FlowDirection":1        */
+/*      s != d, s != reporter, d == reporter   "FlowDirection":0        */
+/*      s == d, s != ""                        "FlowDirection":2        */
+/*      otherwise                              no key                   */
+/*  - add_subnet_label for SrcAddr -> SrcSubnetLabel and DstAddr ->     */
+/*    DstSubnetLabel (pipeline/transform/transform_network.go:129-146,  */
+/*    166-196): the categories in configuration order, each one's CIDRs */
+/*    in order, the FIRST net.IPNet.Contains hit names the label (not   */
+/*    the longest prefix). An empty name still ends the search and      */
+/*    writes no key. Contains compares within one family: an address is */
+/*    IPv4 iff its 16 bytes are v4-mapped, a network iff its masked     */
+/*    address is (for a CIDR given in IPv6 text the mask is then its    */
+/*    last 32 bits): ::/0 holds no IPv4 address, 0.0.0.0/0 no IPv6 one. */
+/*    A record that is not IP has no address key and gets no label. The */
+/*    two-minute ipLabelCache cannot be seen between two configuration  */
+/*    updates and is not restated.                                      */
+/*  - decode_tcp_flags in place on Flags (transform_network.go:147-156, */
+/*    utils/tcp_flags.go:8-48): the value becomes the array of the      */
+/*    names whose bit is set, in table order FIN 1, SYN 2, RST 4,       */
+/*    PSH 8, ACK 16, URG 32, ECE 64, CWR 128, SYN_ACK 256, FIN_ACK 512, */
+/*    RST_ACK 1024; higher bits are ignored; with no known bit the      */
+/*    value is a nil slice, which jsoniter writes as null               */
+/*    (json-iterator/go/reflect_slice.go:28-29). Input equals output,   */
+/*    so the key is always written where Flags is (IP, protocol 6).     */
+/* Rule order: add_kubernetes src, dst, reinterpret_direction,          */
+/* add_kubernetes_infra, the two add_subnet_label, decode_tcp_flags;    */
+/* only "direction after Kubernetes" matters.                           */
+/*                                                                      */
+/* Differences from the reference, by design:                           */
+/*  - one table serves a whole call (an Update between two flows of a   */
+/*    batch cannot be seen);                                            */
+/*  - the rule shape and the key names are fixed as above;              */
+/*  - a label whose escaped value has more than NFAGG_NET_LABEL_MAX     */
+/*    bytes, or more than NFAGG_NET_MAX_CIDRS CIDRs, fail the table;    */
+/*  - none for the host-IP comparison: it is textual, as the            */
+/*    reference's is. nfagg_k8s_table_create interns every row's        */
+/*    host_ip text (id 0: the empty string), the call renders AgentIP   */
+/*    as the line prints it and looks that text up once, and the device */
+/*    compares ids. "<nil>", an agent address no row has and a host IP  */
+/*    in non-canonical text behave as in the reference.                 */
+/*  - out of scope: add_location, add_service (they need files the      */
+/*    agent does not ship), add_subnet (unused by NetObserv).           */
+/* ------------------------------------------------------------------ */
+
+#define NFAGG_NET_REINTERPRET_DIRECTION 1u
+#define NFAGG_NET_SUBNET_LABELS 2u
+#define NFAGG_NET_DECODE_TCP_FLAGS 4u
+
+#define NFAGG_NET_MAX_CIDRS 1024      /* CIDRs, and labels, of one table */
+#define NFAGG_NET_LABEL_MAX 256       /* one label's escaped value, without its quotes */
+#define NFAGG_NET_NO_LABEL 0xFFFFu
+#define NFAGG_NET_NO_DIRECTION 0xFFu
+
+/* One CIDR as net.ParseCIDR returns it (transform_network.go:166-183), flattened in walk order: the categories in
+ * configuration order (one without CIDRs left out), each one's CIDRs in order. */
+typedef struct nfagg_net_cidr {
+    uint8_t ip[16];                   /* the parsed address, net.IP.To16() */
+    uint32_t ones;                    /* prefix length, 0..bits */
+    uint32_t bits;                    /* 32: IPv4 text, 128: IPv6 text */
+    uint32_t label;                   /* index of the category's name in labels */
+} nfagg_net_cidr;
+
+typedef struct nfagg_net_label {      /* arbitrary bytes, read during the call only; len 0: the search ends, no key */
+    const char* text;
+    uint32_t len;
+    uint32_t pad_;
+} nfagg_net_label;
+
+typedef struct nfagg_net_rules {
+    uint32_t struct_size;
+    uint32_t flags;                   /* NFAGG_NET_*: each rule on its own */
+    const nfagg_net_cidr* cidrs;
+    const nfagg_net_label* labels;
+    uint32_t n_cidrs;
+    uint32_t n_labels;
+} nfagg_net_rules;
+
+/* What nfagg_net_resolve writes per flow. */
+typedef struct nfagg_net_row {
+    uint16_t src_label, dst_label;    /* index of the first matching CIDR's label (an empty one included); NFAGG_NET_NO_LABEL: none */
+    uint8_t direction;                /* 0 ingress, 1 egress, 2 inner; NFAGG_NET_NO_DIRECTION: no key */
+    uint8_t pad_[3];                  /* 0 */
+} nfagg_net_row;
+
+typedef struct nfagg_net_table nfagg_net_table;
+
+/* Build the table: every CIDR normalised to its family as Contains does (transform_network.go:170-176 and net.IPNet), every
+ * label's two fragments rendered once (nfagg_net_render). rules->n_cidrs == 0 is valid: no address has a label; flags == 0 is
+ * valid: the lines are those of nfagg_encode_flp_json_k8s. Errors (NFAGG_EINVAL, nfagg_last_error names the entry): ones >
+ * bits, bits neither 32 nor 128, bits 32 with an address that is not v4-mapped, a label index out of range, a null label
+ * with a length, a label over NFAGG_NET_LABEL_MAX, more than NFAGG_NET_MAX_CIDRS CIDRs or labels, unknown flag bits.
+ * With a handle the table is uploaded to that handle's device and serves its calls until destroyed; rebuild it when the
+ * stage's configuration is updated. h == NULL builds and checks the table on the host alone (errors through
+ * nfagg_last_error(NULL)); such a table is refused by the device calls. */
+int nfagg_net_table_create(nfagg_handle* h, const nfagg_net_rules* rules, nfagg_net_table** table);
+void nfagg_net_table_destroy(nfagg_net_table* table);
+
+/* One label's fragment as the encoder emits it behind SrcPort (side 0: ,"SrcSubnetLabel":"..") or DstPort (side 1:
+ * ,"DstSubnetLabel":".."), with its leading comma; nothing (*n_out = 0) for an empty label. The value is escaped as interface
+ * names are. Host only. NFAGG_TRUNCATED with *n_out = bytes needed when cap is smaller. */
+int nfagg_net_render(const nfagg_net_table* table, int side, uint32_t label, void* out, size_t cap, size_t* n_out);
+
+/* The join alone, one GPU lane per flow: a first-match walk of the CIDR list for both addresses and the direction from the
+ * host-IP ids of the flow's two Kubernetes rows. k8s_rows: what nfagg_k8s_resolve wrote for these records with k8s_table
+ * (both required when the table has NFAGG_NET_REINTERPRET_DIRECTION, else ignored). opt: its agent_ip / agent_ip_nil name the
+ * reporter; nothing else of it is read. A rule that is off leaves its fields at "none". All pointers HOST memory: */
+int nfagg_net_resolve(nfagg_handle* h, const nfagg_net_table* net_table, const nfagg_k8s_table* k8s_table, const void* records, size_t n,
+                      const uint32_t* k8s_rows, const nfagg_flp_options* opt, nfagg_net_row* out);
+/* Same with records, k8s_rows and out in DEVICE memory (records 16-byte, the others 8-byte aligned). */
+int nfagg_net_resolve_device(nfagg_handle* h, const nfagg_net_table* net_table, const nfagg_k8s_table* k8s_table, const void* d_records,
+                             size_t n, const uint32_t* d_k8s_rows, const nfagg_flp_options* opt, nfagg_net_row* d_out);
+
+/* nfagg_encode_flp_json_k8s (same three policies, same outputs and return codes, nothing deferred) plus the rules that are
+ * switched on in net_table: "FlowDirection":0|1|2 behind Flags, ,"SrcSubnetLabel":".." behind SrcPort, ,"DstSubnetLabel":".."
+ * behind DstPort, and the array of names (or null) as the value of Flags. net_table is required and must have been created
+ * for this handle; with no rule on the output is byte for byte that of nfagg_encode_flp_json_k8s. All pointers HOST memory: */
+int nfagg_encode_flp_json_net(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
+                              void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes);
+/* Same with every data pointer (d_rows and those inside d_features too) in DEVICE memory. */
+int nfagg_encode_flp_json_net_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
+                                     void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes);
+/* The longest line nfagg_encode_flp_json_net can write: nfagg_flp_json_k8s_max_line(policy) plus two label fragments at the
+ * cap (18 bytes of key text, the quotes, NFAGG_NET_LABEL_MAX), ,"FlowDirection":2 and the eleven flag names in place of five
+ * digits; 0 for an unknown policy. The write kernels size their LDS windows by it. */
+uint32_t nfagg_flp_json_net_max_line(int policy);
 
 /* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */

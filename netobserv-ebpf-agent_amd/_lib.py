@@ -127,6 +127,31 @@ class K8sLayer(C.Structure):
 
 K8S_MAX_RENDERED, K8S_MAX_ROWS, K8S_NO_ROW = 2048, 1 << 22, 0xFFFFFFFF
 
+
+class NetCidr(C.Structure):
+    """nfagg_net_cidr (include/nfagg.h)."""
+    _fields_ = [("ip", C.c_uint8 * 16), ("ones", C.c_uint32), ("bits", C.c_uint32), ("label", C.c_uint32)]
+
+
+class NetLabel(C.Structure):
+    """nfagg_net_label (include/nfagg.h)."""
+    _fields_ = [("text", C.c_char_p), ("len", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class NetRules(C.Structure):
+    """nfagg_net_rules (include/nfagg.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("cidrs", C.POINTER(NetCidr)), ("labels", C.POINTER(NetLabel)),
+                ("n_cidrs", C.c_uint32), ("n_labels", C.c_uint32)]
+
+
+class NetRow(C.Structure):
+    """nfagg_net_row (include/nfagg.h)."""
+    _fields_ = [("src_label", C.c_uint16), ("dst_label", C.c_uint16), ("direction", C.c_uint8), ("pad_", C.c_uint8 * 3)]
+
+
+NET_REINTERPRET_DIRECTION, NET_SUBNET_LABELS, NET_DECODE_TCP_FLAGS = 1, 2, 4
+NET_MAX_CIDRS, NET_LABEL_MAX, NET_NO_LABEL, NET_NO_DIRECTION = 1024, 256, 0xFFFF, 0xFF
+
 TLS_VERSION, TLS_CIPHER_SUITE, TLS_GROUP = 0, 1, 2
 TLS_NAME_MAX, TLS_MAX_ROWS = 63, 256
 
@@ -226,6 +251,14 @@ SIGNATURES = {
     "nfagg_encode_flp_json_k8s": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
     "nfagg_encode_flp_json_k8s_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
     "nfagg_flp_json_k8s_max_line": (C.c_uint32, [C.c_int]),
+    "nfagg_net_table_create": (C.c_int, [_vp, C.POINTER(NetRules), C.POINTER(_vp)]),
+    "nfagg_net_table_destroy": (None, [_vp]),
+    "nfagg_net_render": (C.c_int, [_vp, C.c_int, C.c_uint32, _vp, _sz, _psz]),
+    "nfagg_net_resolve": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(FlpOptions), _vp]),
+    "nfagg_net_resolve_device": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(FlpOptions), _vp]),
+    "nfagg_encode_flp_json_net": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_encode_flp_json_net_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_flp_json_net_max_line": (C.c_uint32, [C.c_int]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

@@ -14,6 +14,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/nfagg.h"
@@ -98,13 +99,14 @@ struct nfagg_handle {
         DevBuf ne_rows;                              //   *_netev: the flows' table rows
         DevBuf ne_in[3], ne_out[3], ne_missing, ne_info;   // nfagg_netev_resolve: staged inputs and outputs, the missing set, its counters
         DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record
+        DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record
         std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
         std::vector<uint8_t> h_flp_esc;
         template <typename F> void each(F f) {
             for (DevBuf* b : {&local_off, &block_sum, &block_base, &names, &ipfix_name_rows, &flp_rows, &flp_esc, &flp_n_deferred,
                               &in_records, &out, &out_offsets, &out_extra[0], &out_extra[1]}) f(*b);
             for (DevBuf& b : pb_feat) f(b);
-            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows}) f(*b);
+            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows, &net_rows}) f(*b);
         }
     } enc;
     // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
@@ -2221,9 +2223,27 @@ struct nfagg_k8s_table {
     std::vector<K8sRow> rows;
     std::vector<uint8_t> blob;
     bool has_layer = false;
+    // reinterpret_direction compares host-IP TEXT: every row's host_ip interned, 0 for the empty string, in an array of its
+    // own beside the rows (the kernels that read K8sRow do not see it); host_text finds a call's reporter
+    std::vector<uint32_t> host_ids;
+    std::unordered_map<std::string, uint32_t> host_text;
     void* d_slots = nullptr;
     void* d_rows = nullptr;
     void* d_blob = nullptr;
+    void* d_host_ids = nullptr;
+};
+
+// The table of nfagg_net_table_create (nfagg_flp.h, nfagg_net.h): the normalised CIDR list, the labels' fragments, on the host
+// and (with a handle) in one allocation on its device: cidrs, meta, frags, blob, each 32-byte aligned.
+struct nfagg_net_table {
+    nfagg_handle* h = nullptr;
+    uint32_t flags = 0;
+    std::vector<NetCidr> cidrs;
+    std::vector<uint32_t> meta;
+    std::vector<NetFrag> frags;
+    std::vector<uint8_t> blob;
+    size_t off_meta = 0, off_frags = 0, off_blob = 0;
+    void* d_mem = nullptr;
 };
 
 // ---- the export encoders' host side: what protobuf, IPFIX and direct-FLP JSON do alike
@@ -2599,7 +2619,47 @@ static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, Fl
 // The TLS entry points' extra input. With it the three TLS keys are written from the table, no record is deferred (flags and
 // counter are not used), and the network events are an option: rows and table both, or neither (*ne = nullptr).
 // with_k8s: the *_k8s entry points, whose table is required as well and whose lines carry the Kubernetes keys.
-struct FlpTlsArgs { const nfagg_tls_names* names; bool with_k8s = false; const nfagg_k8s_table* k8s = nullptr; };
+// with_net: the *_net entry points, which take the table of the transform network rules on top of that.
+struct FlpTlsArgs {
+    const nfagg_tls_names* names; bool with_k8s = false; const nfagg_k8s_table* k8s = nullptr;
+    bool with_net = false; const nfagg_net_table* net = nullptr;
+};
+static NetDev net_dev(const nfagg_net_table* t) {
+    const uint8_t* m = (const uint8_t*)t->d_mem;
+    return NetDev{(const NetCidr*)m, (const uint32_t*)(m + t->off_meta), (const NetFrag*)(m + t->off_frags), m + t->off_blob,
+                  (uint32_t)t->cidrs.size(), (uint32_t)t->frags.size(), t->flags};
+}
+// net.IP.String() of a 16-byte address, as ip_text (nfagg_flp_line.h) prints AgentIP on the device: the dotted quad for a
+// v4-mapped one, else netip's appendTo6.
+static std::string go_ip_text(const uint8_t ip[16]) {
+    static const uint8_t v4[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xff, 0xff};
+    char buf[48];
+    if (memcmp(ip, v4, 12) == 0) { snprintf(buf, sizeof buf, "%u.%u.%u.%u", ip[12], ip[13], ip[14], ip[15]); return buf; }
+    uint32_t g[8];
+    for (int k = 0; k < 8; k++) g[k] = ((uint32_t)ip[2 * k] << 8) | ip[2 * k + 1];
+    int z0 = -1, zlen = 1, cur = 0, curlen = 0;                          // only runs of two or more zero groups count; the first longest wins
+    for (int k = 0; k < 8; k++) {
+        if (g[k] == 0) { if (curlen == 0) cur = k; curlen++; if (curlen > zlen) { z0 = cur; zlen = curlen; } }
+        else curlen = 0;
+    }
+    const int z1 = z0 < 0 ? -1 : z0 + zlen;
+    std::string o;
+    for (int k = 0; k < 8; k++) {
+        if (k == z0) o += "::";
+        else if (k < z0 || k >= z1) {
+            if (k > 0 && k != z1) o += ':';
+            snprintf(buf, sizeof buf, "%x", g[k]);
+            o += buf;
+        }
+    }
+    return o;
+}
+// The reporter of a call: the id of AgentIP's text among the table's host IPs, kNetNoHost when no row carries that text
+// (transform_network_direction.go:37-44; "<nil>" is not empty, so the rule goes on).
+static uint32_t net_reporter(const nfagg_k8s_table* k8s, const nfagg_flp_options* opt) {
+    const auto it = k8s->host_text.find(opt->agent_ip_nil ? std::string("<nil>") : go_ip_text(opt->agent_ip));
+    return it == k8s->host_text.end() ? kNetNoHost : it->second;
+}
 static K8sDev k8s_dev(const nfagg_k8s_table* t) {
     return K8sDev{(const K8sSlot*)t->d_slots, (const K8sRow*)t->d_rows, (const uint8_t*)t->d_blob, (uint32_t)t->slots.size() - 1,
                   (uint32_t)t->rows.size(), t->has_layer ? 1u : 0u};
@@ -2621,11 +2681,14 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     int rc;
     if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
     if ((rc = encode_flp_check(h, opt)) != NFAGG_OK) return rc;
-    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || !out_bytes || !d_line_offsets || (n && !d_records))
+    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !d_line_offsets ||
+        (n && !d_records))
         return fail(h, NFAGG_EINVAL, "null argument");
     if (tls && (tls->names->h != h || !tls->names->d_mem)) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
     const nfagg_k8s_table* k8s = tls && tls->with_k8s ? tls->k8s : nullptr;
     if (k8s && (k8s->h != h || !k8s->d_slots)) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
+    const nfagg_net_table* net = k8s && tls->with_net ? tls->net : nullptr;
+    if (net && (net->h != h || !net->d_mem)) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
     PbFeat F{};
     if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
@@ -2651,6 +2714,20 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
         const K8sDev K = k8s_dev(k8s);
         hipError_t e = launch_k8s_resolve(d_records, n, K, k8s_rows, h->stream);
         if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
+        if (net) {
+            if ((rc = ensure_buf(h, h->enc.net_rows, n * sizeof(uint2))) != NFAGG_OK) return rc;
+            const uint2* net_rows = (const uint2*)h->enc.net_rows.p;
+            const NetDev N = net_dev(net);
+            e = launch_net_resolve(d_records, n, N, k8s_rows, (const uint32_t*)k8s->d_host_ids, K.n_rows, net_reporter(k8s, opt), (uint2*)h->enc.net_rows.p,
+                                   h->stream);
+            if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
+            return encode_two_pass(h, n, "FLP JSON with transform network keys", "write", d_out, out_cap, out_bytes, nullptr,
+                [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+                    return launch_flp_net_size(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_sum, block_base, h->stream); },
+                [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+                    return launch_flp_net_write(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_base, d_out, d_line_offsets,
+                                                h->stream); });
+        }
         return encode_two_pass(h, n, "FLP JSON with Kubernetes keys", "write", d_out, out_cap, out_bytes, nullptr,
             [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
                 return launch_flp_k8s_size(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_sum, block_base, h->stream); },
@@ -2673,7 +2750,8 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
                                 size_t* n_deferred, size_t* out_bytes) {
     int rc = encode_flp_check(h, opt);
     if (rc != NFAGG_OK) return rc;
-    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || !out_bytes || !line_offsets || (n && !records))
+    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !line_offsets ||
+        (n && !records))
         return fail(h, NFAGG_EINVAL, "null argument");
     if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
     if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
@@ -3159,6 +3237,7 @@ int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size
     free_slot.row = kK8sNoRow;
     t->slots.assign(cap, free_slot);
     t->rows.resize(n);
+    t->host_ids.assign(n, 0u);
     std::vector<uint8_t> piece;
     for (size_t r = 0; r < n; r++) {
         const nfagg_k8s_entry& e = entries[r];
@@ -3195,6 +3274,8 @@ int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size
             else { row.dst_off = off; row.dst_len = (uint16_t)piece.size(); }
         }
         row.flags = layer && k8s_is_app(e, *layer) ? kK8sRowApp : 0u;
+        // the text of the row's SrcK8S_HostIP / DstK8S_HostIP key, as reinterpret_direction compares it; the key is absent for ""
+        t->host_ids[r] = e.host_ip_len ? t->host_text.emplace(std::string(e.host_ip, e.host_ip_len), (uint32_t)t->host_text.size() + 1).first->second : 0u;
     }
     if (h) {
         auto up = [&]() -> int {
@@ -3202,6 +3283,8 @@ int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size
             HIP_TRY(h, hipMalloc(&t->d_slots, cap * sizeof(K8sSlot)));
             HIP_TRY(h, hipMalloc(&t->d_rows, std::max<size_t>(n, 1) * sizeof(K8sRow)));
             HIP_TRY(h, hipMalloc(&t->d_blob, std::max<size_t>(t->blob.size(), 16)));
+            HIP_TRY(h, hipMalloc(&t->d_host_ids, std::max<size_t>(n, 1) * sizeof(uint32_t)));
+            if (n) HIP_TRY(h, hipMemcpy(t->d_host_ids, t->host_ids.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
             HIP_TRY(h, hipMemcpy(t->d_slots, t->slots.data(), cap * sizeof(K8sSlot), hipMemcpyHostToDevice));
             if (n) HIP_TRY(h, hipMemcpy(t->d_rows, t->rows.data(), n * sizeof(K8sRow), hipMemcpyHostToDevice));
             if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
@@ -3216,12 +3299,13 @@ int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size
 
 void nfagg_k8s_table_destroy(nfagg_k8s_table* t) {
     if (!t) return;
-    if (t->h && (t->d_slots || t->d_rows || t->d_blob)) {
+    if (t->h && (t->d_slots || t->d_rows || t->d_blob || t->d_host_ids)) {
         (void)hipSetDevice(t->h->device);
         (void)hipStreamSynchronize(t->h->stream);
         if (t->d_slots) (void)hipFree(t->d_slots);
         if (t->d_rows) (void)hipFree(t->d_rows);
         if (t->d_blob) (void)hipFree(t->d_blob);
+        if (t->d_host_ids) (void)hipFree(t->d_host_ids);
     }
     delete t;
 }
@@ -3270,6 +3354,192 @@ int nfagg_encode_flp_json_k8s(nfagg_handle* h, const void* records, size_t n, co
                               uint64_t* line_offsets, size_t* out_bytes) {
     const NetevArgs ne{rows, netev_table};
     const FlpTlsArgs tls{tls_names, true, k8s_table};
+    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+}
+
+}  // extern "C"
+
+// ---- direction, subnet labels, TCP flag names (nfagg_net.h): the caller's rules as a table, the join alone, the entry points
+namespace {
+
+// One label's fragment, ,"SrcSubnetLabel":"<escaped>" or ,"DstSubnetLabel":"<escaped>"; empty for an empty label.
+void net_render(const char* text, uint32_t len, int side, std::vector<uint8_t>& o) {
+    o.clear();
+    if (!len) return;
+    const char* head = side ? ",\"DstSubnetLabel\":" : ",\"SrcSubnetLabel\":";
+    o.insert(o.end(), head, head + 18);
+    std::vector<uint8_t> buf(2 + 6 * (size_t)len);
+    const uint32_t n = flp_escape(text, len, buf.data());
+    o.insert(o.end(), buf.begin(), buf.begin() + n);
+}
+
+// net.CIDRMask(ones, 128) as four little-endian dwords of the 16 bytes
+void net_mask128(uint32_t ones, uint8_t m[16]) {
+    for (uint32_t k = 0; k < 16; k++) m[k] = ones >= 8 * (k + 1) ? 0xffu : ones > 8 * k ? (uint8_t)(0xff00u >> (ones - 8 * k)) : 0u;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nfagg_net_table_create(nfagg_handle* h, const nfagg_net_rules* rules, nfagg_net_table** table) {
+    if (!table || !rules) return fail(h, NFAGG_EINVAL, "null argument");
+    *table = nullptr;
+    if (rules->struct_size != sizeof(nfagg_net_rules)) return fail(h, NFAGG_EINVAL, "nfagg_net_rules.struct_size mismatch");
+    const uint32_t known = NFAGG_NET_REINTERPRET_DIRECTION | NFAGG_NET_SUBNET_LABELS | NFAGG_NET_DECODE_TCP_FLAGS;
+    if (rules->flags & ~known) return fail(h, NFAGG_EINVAL, "unknown net rule flags 0x%x", rules->flags & ~known);
+    if ((rules->n_cidrs && !rules->cidrs) || (rules->n_labels && !rules->labels)) return fail(h, NFAGG_EINVAL, "null list with a count");
+    if (rules->n_cidrs > NFAGG_NET_MAX_CIDRS) return fail(h, NFAGG_EINVAL, "%u CIDRs, more than %u", rules->n_cidrs, (unsigned)NFAGG_NET_MAX_CIDRS);
+    if (rules->n_labels > NFAGG_NET_MAX_CIDRS) return fail(h, NFAGG_EINVAL, "%u labels, more than %u", rules->n_labels, (unsigned)NFAGG_NET_MAX_CIDRS);
+    nfagg_net_table* t = new (std::nothrow) nfagg_net_table;
+    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
+    t->h = h;
+    t->flags = rules->flags;
+    std::vector<uint8_t> piece;
+    for (uint32_t k = 0; k < rules->n_labels; k++) {
+        const nfagg_net_label& l = rules->labels[k];
+        if (l.len && !l.text) { delete t; return fail(h, NFAGG_EINVAL, "net label %u: null string with a length", k); }
+        if (l.len > kNetLabelMax) { delete t; return fail(h, NFAGG_EINVAL, "net label %u: its escaped value has more than %u bytes", k, kNetLabelMax); }
+        NetFrag f{};
+        for (int side = 0; side < 2; side++) {
+            net_render(l.text, l.len, side, piece);
+            if (piece.size() > kNetFragMax) {
+                const size_t got = piece.size() - (kNetFragMax - kNetLabelMax);
+                delete t;
+                return fail(h, NFAGG_EINVAL, "net label %u: its escaped value has %zu bytes, the cap is %u", k, got, kNetLabelMax);
+            }
+            const uint32_t off = (uint32_t)(t->blob.size() / 16);
+            t->blob.insert(t->blob.end(), piece.begin(), piece.end());
+            t->blob.resize((t->blob.size() + 15) / 16 * 16, 0);          // the kernels read a fragment 16 bytes at a time
+            if (side == 0) { f.src_off = off; f.src_len = (uint32_t)piece.size(); }
+            else { f.dst_off = off; f.dst_len = (uint32_t)piece.size(); }
+        }
+        t->frags.push_back(f);
+    }
+    static const uint8_t v4_prefix[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xff, 0xff};
+    for (uint32_t k = 0; k < rules->n_cidrs; k++) {
+        const nfagg_net_cidr& c = rules->cidrs[k];
+        if (c.bits != 32 && c.bits != 128) { delete t; return fail(h, NFAGG_EINVAL, "CIDR %u: %u bits, neither 32 nor 128", k, c.bits); }
+        if (c.ones > c.bits) { delete t; return fail(h, NFAGG_EINVAL, "CIDR %u: a prefix of %u in %u bits", k, c.ones, c.bits); }
+        if (c.label >= rules->n_labels) { delete t; return fail(h, NFAGG_EINVAL, "CIDR %u: label %u of %u", k, c.label, rules->n_labels); }
+        if (c.bits == 32 && memcmp(c.ip, v4_prefix, 12) != 0) { delete t; return fail(h, NFAGG_EINVAL, "CIDR %u: 32 bits and an address that is not v4-mapped", k); }
+        // net.IPNet.Contains -> networkNumberAndMask: the network is IPv4 iff its masked address is v4-mapped, and then only
+        // the mask's last 32 bits count; the twelve 0xff in front make the compare refuse every address that is not v4-mapped
+        uint8_t mask[16], netw[16];
+        net_mask128(c.bits == 32 ? 96 + c.ones : c.ones, mask);
+        for (int b = 0; b < 16; b++) netw[b] = c.ip[b] & mask[b];
+        const bool v4 = memcmp(netw, v4_prefix, 12) == 0;
+        if (v4) memset(mask, 0xff, 12);
+        NetCidr d;
+        memcpy(d.net, netw, 16); memcpy(d.mask, mask, 16);
+        t->cidrs.push_back(d);
+        t->meta.push_back(c.label | (v4 ? 0u : kNetCidrV6));
+    }
+    auto up32 = [](size_t x) { return (x + 31) / 32 * 32; };
+    t->off_meta = up32(std::max<size_t>(t->cidrs.size(), 1) * sizeof(NetCidr));
+    t->off_frags = t->off_meta + up32(std::max<size_t>(t->meta.size(), 1) * sizeof(uint32_t));
+    t->off_blob = t->off_frags + up32(std::max<size_t>(t->frags.size(), 1) * sizeof(NetFrag));
+    if (h) {
+        auto up = [&]() -> int {
+            std::vector<uint8_t> img(t->off_blob + std::max<size_t>(t->blob.size(), 16), 0);
+            if (!t->cidrs.empty()) memcpy(img.data(), t->cidrs.data(), t->cidrs.size() * sizeof(NetCidr));
+            if (!t->meta.empty()) memcpy(img.data() + t->off_meta, t->meta.data(), t->meta.size() * sizeof(uint32_t));
+            if (!t->frags.empty()) memcpy(img.data() + t->off_frags, t->frags.data(), t->frags.size() * sizeof(NetFrag));
+            if (!t->blob.empty()) memcpy(img.data() + t->off_blob, t->blob.data(), t->blob.size());
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMalloc(&t->d_mem, img.size()));
+            HIP_TRY(h, hipMemcpy(t->d_mem, img.data(), img.size(), hipMemcpyHostToDevice));
+            return NFAGG_OK;
+        };
+        const int rc = up();
+        if (rc != NFAGG_OK) { nfagg_net_table_destroy(t); return rc; }
+    }
+    *table = t;
+    return NFAGG_OK;
+}
+
+void nfagg_net_table_destroy(nfagg_net_table* t) {
+    if (!t) return;
+    if (t->h && t->d_mem) {
+        (void)hipSetDevice(t->h->device);
+        (void)hipStreamSynchronize(t->h->stream);
+        (void)hipFree(t->d_mem);
+    }
+    delete t;
+}
+
+int nfagg_net_render(const nfagg_net_table* table, int side, uint32_t label, void* out, size_t cap, size_t* n_out) {
+    if (!table || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
+    if (side != 0 && side != 1) return fail(nullptr, NFAGG_EINVAL, "unknown side %d", side);
+    if (label >= table->frags.size()) return fail(nullptr, NFAGG_EINVAL, "label %u of %zu", label, table->frags.size());
+    const NetFrag& f = table->frags[label];
+    const size_t off = (size_t)(side ? f.dst_off : f.src_off) * 16, len = side ? f.dst_len : f.src_len;
+    *n_out = len;
+    if (len && (!out || cap < len)) return NFAGG_TRUNCATED;
+    if (len) memcpy(out, table->blob.data() + off, len);
+    return NFAGG_OK;
+}
+
+int nfagg_net_resolve_device(nfagg_handle* h, const nfagg_net_table* net_table, const nfagg_k8s_table* k8s_table, const void* d_records,
+                             size_t n, const uint32_t* d_k8s_rows, const nfagg_flp_options* opt, nfagg_net_row* d_out) {
+    if (!h || !net_table || (n && (!d_records || !d_out))) return fail(h, NFAGG_EINVAL, "null argument");
+    if (net_table->h != h || !net_table->d_mem) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
+    const bool dir = (net_table->flags & NFAGG_NET_REINTERPRET_DIRECTION) != 0;
+    if (dir) {
+        if (!k8s_table || !opt || (n && !d_k8s_rows)) return fail(h, NFAGG_EINVAL, "reinterpret_direction needs the Kubernetes table, the flows' rows and the options");
+        if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
+        if (k8s_table->h != h || !k8s_table->d_slots) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
+    }
+    if (((uintptr_t)d_records & 15u) != 0 || ((uintptr_t)d_out & 7u) != 0 || (dir && ((uintptr_t)d_k8s_rows & 7u) != 0))
+        return fail(h, NFAGG_EINVAL, "device records must be 16-byte, rows 8-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (n) {
+        hipError_t e = launch_net_resolve(d_records, n, net_dev(net_table), dir ? d_k8s_rows : nullptr, dir ? (const uint32_t*)k8s_table->d_host_ids : nullptr,
+                                          dir ? (uint32_t)k8s_table->rows.size() : 0u, dir ? net_reporter(k8s_table, opt) : kNetNoHost, (uint2*)d_out,
+                                          h->stream);
+        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+int nfagg_net_resolve(nfagg_handle* h, const nfagg_net_table* net_table, const nfagg_k8s_table* k8s_table, const void* records, size_t n,
+                      const uint32_t* k8s_rows, const nfagg_flp_options* opt, nfagg_net_row* out) {
+    if (!h || !net_table || (n && (!records || !out))) return fail(h, NFAGG_EINVAL, "null argument");
+    const bool dir = (net_table->flags & NFAGG_NET_REINTERPRET_DIRECTION) != 0;
+    if (dir && n && !k8s_rows) return fail(h, NFAGG_EINVAL, "reinterpret_direction needs the Kubernetes table, the flows' rows and the options");
+    auto& S = h->enc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
+    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+    if (n && dir) HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if ((rc = nfagg_net_resolve_device(h, net_table, k8s_table, S.in_records.p, n, (const uint32_t*)S.k8s_rows.p, opt, (nfagg_net_row*)S.net_rows.p)) != NFAGG_OK)
+        return rc;
+    if (n) HIP_TRY(h, hipMemcpyAsync(out, S.net_rows.p, n * sizeof(nfagg_net_row), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+uint32_t nfagg_flp_json_net_max_line(int policy) { return flp_net_max_line(policy); }
+
+int nfagg_encode_flp_json_net_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
+                                     void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+}
+
+int nfagg_encode_flp_json_net(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
+                              void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
     return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
 }
 

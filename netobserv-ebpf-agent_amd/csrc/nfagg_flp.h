@@ -80,4 +80,35 @@ hipError_t launch_flp_k8s_write(const void* d_recs, uint64_t n, const FlpParams&
                                 void* d_out, uint64_t* d_line_offsets, hipStream_t s);
 uint32_t flp_k8s_max_line(int policy);
 
+// The table of nfagg_net_table_create on the device (nfagg_net.h): the CIDR list in walk order, every entry normalised so
+// that one masked compare of the 16 address bytes decides Contains within the family (an IPv4 network carries the
+// v4-mapped prefix in `net` and twelve 0xff bytes in front of its mask; an IPv6 one is flagged, and a v4-mapped address
+// never matches it); per label the two rendered fragments in a blob, 16-byte aligned.
+constexpr uint32_t kNetMaxCidrs = NFAGG_NET_MAX_CIDRS, kNetLabelMax = NFAGG_NET_LABEL_MAX, kNetNoLabel = NFAGG_NET_NO_LABEL,
+                   kNetNoDirection = NFAGG_NET_NO_DIRECTION, kNetCidrV6 = 1u << 16, kNetNoHost = 0xFFFFFFFFu;
+constexpr uint32_t kNetFragMax = (sizeof(",\"SrcSubnetLabel\":\"\"") - 1) + kNetLabelMax;      // one fragment: key text, quotes, the escaped label
+struct NetCidr { uint32_t net[4]; uint32_t mask[4]; };
+struct NetFrag { uint32_t src_off, src_len, dst_off, dst_len; };      // offsets in 16-byte units; len 0: an empty label, no key
+static_assert(sizeof(NetCidr) == 32 && sizeof(NetFrag) == 16, "net table layout");
+struct NetDev {
+    const NetCidr* cidrs;         // n_cidrs of them, 32-byte aligned
+    const uint32_t* meta;         // per CIDR: its label | kNetCidrV6
+    const NetFrag* frags;         // n_labels of them
+    const uint8_t* blob;          // 16-byte aligned
+    uint32_t n_cidrs, n_labels, flags;
+};
+
+// The join of nfagg_net_resolve (nfagg_net.hip: one lane per flow): 8 bytes per record, nfagg_net_row. d_k8s_rows / d_host_ids
+// / reporter: the flows' Kubernetes rows, the rows' interned host-IP ids and the reporter's id (kNetNoHost: no row has its
+// text); read only with NFAGG_NET_REINTERPRET_DIRECTION.
+hipError_t launch_net_resolve(const void* d_recs, uint64_t n, const NetDev& N, const uint32_t* d_k8s_rows, const uint32_t* d_host_ids,
+                              uint32_t n_k8s_rows, uint32_t reporter, uint2* d_out, hipStream_t s);
+hipError_t launch_flp_net_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                               const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, uint32_t* d_rows, uint32_t* d_local_off,
+                               uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s);
+hipError_t launch_flp_net_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                                const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint32_t* d_rows,
+                                const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s);
+uint32_t flp_net_max_line(int policy);
+
 }  // namespace nfagg

@@ -17,7 +17,7 @@
 // Same two passes, same window scheme, same encode_line and the same two kernels as nfagg_flp.hip (k_flp_size<Feat>,
 // k_flp_write<Feat> of nfagg_flp_line.h), with FlpContent as the feature policy: this file compiles them for FlpContent,
 // FlpContentNetev and FlpTls (nfagg_tls.h) over those two and over FlpPlain, and selects; it also compiles the kernel pair of
-// nfagg_k8s.h for FlpK8s over the three TLS policies. A lane reads the parts its
+// nfagg_k8s.h for FlpK8s over the three TLS policies, and that of nfagg_net.h for FlpNet over those. A lane reads the parts its
 // present byte names with 16- and 8-byte loads before anything is emitted, keeps the fields the line needs in registers
 // and the DNS name in a 32-byte LDS slot of its own. The names of response codes, TCP states and drop causes sit in one
 // constant blob with an offset and a length per name; the counting pass reads only the lengths.
@@ -25,6 +25,7 @@
 #include "nfagg_netev.h"
 #include "nfagg_tls.h"
 #include "nfagg_k8s.h"
+#include "nfagg_net.h"
 
 namespace nfagg {
 
@@ -284,6 +285,10 @@ struct FlpContent {
     template <typename S> NF_DEV void k8s_dst(S&) const {}                   // FlpK8s (nfagg_k8s.h) has the Kubernetes keys
     template <typename S> NF_DEV void k8s_layer(S&) const {}
     template <typename S> NF_DEV void k8s_src(S&) const {}
+    static constexpr bool kFlagNames = false;                                // FlpNet (nfagg_net.h) has the transform network rules
+    template <typename S> NF_DEV void dst_subnet(S&) const {}
+    template <typename S> NF_DEV void flow_direction(S&) const {}
+    template <typename S> NF_DEV void src_subnet(S&) const {}
 };
 
 // FlpContent plus the flow's network events: the table rows nfagg_netev_resolve wrote (PbFeat::ne_rows), each row's JSON
@@ -356,6 +361,30 @@ hipError_t launch_flp_k8s_write(const void* d_recs, uint64_t n, const FlpParams&
         return k8s_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, d_k8s_rows, d_rows, d_local_off, d_block_base,
                                                              d_out, d_line_offsets, s); });
 }
+
+// The transform network rules: FlpNet over the three Kubernetes policies, in the kernel pair of nfagg_net.h.
+template <typename Fn> static hipError_t flp_net_select(const PbFeat* F, Fn fn) {
+    return !F ? fn(FlpPolicy<FlpNet<FlpK8s<FlpTls<FlpPlain>>>>{}) : F->ne_rows ? fn(FlpPolicy<FlpNet<FlpK8s<FlpTls<FlpContentNetev>>>>{})
+                                                                               : fn(FlpPolicy<FlpNet<FlpK8s<FlpTls<FlpContent>>>>{});
+}
+
+hipError_t launch_flp_net_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                               const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, uint32_t* d_rows, uint32_t* d_local_off,
+                               uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s) {
+    return flp_net_select(F, [&](auto policy) {
+        return net_size_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_rows, d_local_off,
+                                                            d_block_sum, d_block_base, s); });
+}
+
+hipError_t launch_flp_net_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                                const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint32_t* d_rows,
+                                const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s) {
+    return flp_net_select(F, [&](auto policy) {
+        return net_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_rows, d_local_off,
+                                                             d_block_base, d_out, d_line_offsets, s); });
+}
+
+uint32_t flp_net_max_line(int policy) { return flp_k8s_max_line(policy) ? flp_k8s_max_line(policy) + kNetLineMax : 0u; }
 
 uint32_t flp_k8s_max_line(int policy) { return flp_tls_max_line(policy) ? flp_tls_max_line(policy) + kK8sLineMax : 0u; }
 

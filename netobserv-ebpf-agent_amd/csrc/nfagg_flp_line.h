@@ -174,7 +174,9 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
 // every hook is empty and the line is the one of decode_protobuf.go:57-127. FlpContent (nfagg_flp_content.hip) holds
 // the parts of a full BpfFlowContent, FlpContentNetev adds the flow's resolved network events. The two TLS hooks take the
 // record: they are empty in all three, and a record that would need them is deferred; FlpTls (nfagg_tls.h) fills them.
-// The three Kubernetes hooks are empty in all of these; FlpK8s (nfagg_k8s.h) fills them, in kernels of its own.
+// The three Kubernetes hooks are empty in all of these; FlpK8s (nfagg_k8s.h) fills them, in kernels of its own. So are the
+// three hooks of the transform network rules (FlowDirection, the two subnet labels); kFlagNames = false keeps dec<5> as the
+// value of Flags, and no call stands in its place. FlpNet (nfagg_net.h) fills the hooks and names the flags, in kernels of its own.
 //
 // What k_flp_size<Feat> and k_flp_write<Feat> ask of a policy beside the hooks, all of it known when they are compiled:
 //   kWindow   line starts a window of the write kernel takes, from its 16-byte aligned base
@@ -201,6 +203,10 @@ struct NoFeat {
     template <typename S> NF_DEV void k8s_dst(S&) const {}    // DstK8S_*      after DstAddr
     template <typename S> NF_DEV void k8s_layer(S&) const {}  // K8S_FlowLayer after Interfaces, before NetworkEvents
     template <typename S> NF_DEV void k8s_src(S&) const {}    // SrcK8S_*      after SrcAddr
+    static constexpr bool kFlagNames = false;                 // true: flags_value(s, flags) writes the value of Flags
+    template <typename S> NF_DEV void dst_subnet(S&) const {}      // DstSubnetLabel after DstPort
+    template <typename S> NF_DEV void flow_direction(S&) const {}  // FlowDirection  after Flags
+    template <typename S> NF_DEV void src_subnet(S&) const {}      // SrcSubnetLabel after SrcPort
 };
 // The plain policy: the line of the records Accounter.evict produces.
 struct FlpPlain : NoFeat {
@@ -230,8 +236,13 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
     }
     lit(s, ",\"DstMac\":\""); mac_text(s, r.dmac()); s.put('"');
     if (ports) { lit(s, ",\"DstPort\":"); dec<5>(s, r.d[8] >> 16); }
+    f.dst_subnet(s);
     lit(s, ",\"Etype\":"); dec<5>(s, eth);
-    if (ip && proto == 6) { lit(s, ",\"Flags\":"); dec<5>(s, r.flags()); }
+    if (ip && proto == 6) {
+        lit(s, ",\"Flags\":");
+        if constexpr (F::kFlagNames) f.flags_value(s, r.flags()); else dec<5>(s, r.flags());
+    }
+    f.flow_direction(s);
     f.ipsec(s);
     if (icmp) {
         lit(s, ",\"IcmpCode\":"); dec<3>(s, (r.d[9] >> 16) & 0xffu);
@@ -262,6 +273,7 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
     if (ip) { lit(s, ",\"SrcAddr\":\""); ip_text(s, Ip4w{{r.d[0], r.d[1], r.d[2], r.d[3]}}); s.put('"'); f.k8s_src(s); }
     lit(s, ",\"SrcMac\":\""); mac_text(s, r.smac()); s.put('"');
     if (ports) { lit(s, ",\"SrcPort\":"); dec<5>(s, r.d[8] & 0xffffu); }
+    f.src_subnet(s);
     f.tls_names(s, r);
     const uint32_t tls = (r.d[34] >> 16) & 0xffu;                      // tls_types @138
     if (tls) {   // tlsTypesToStrings (pkg/model/tls_types.go) in its order; no known bit: a nil slice, "null"

@@ -219,15 +219,18 @@ class MapTracer:
             self._netevTable.close()
             self._netevTable = None
 
-    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None, k8s=None):
+    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None, k8s=None, net=None):
         """evictFlows for a direct-FLP `write: stdout, format: json` stage, without a Record per flow: the drained maps are merged,
         decorated with the sample decoder's network events and encoded on the GPU. Returns (buf, line_offsets, deferred) as
         FlowTable.encode_flp_json_content does; with tls_names (a TlsNames of the fetcher's table) the TLS keys are written too,
         nothing is deferred and the result is (buf, line_offsets) as FlowTable.encode_flp_json_tls gives it. With k8s (a K8sTable of the
         fetcher's table; needs tls_names) the lines carry what the `transform network` stage's Kubernetes rules add as well
-        (FlowTable.encode_flp_json_k8s)."""
+        (FlowTable.encode_flp_json_k8s). With net (a NetTable; needs k8s) also what its reinterpret_direction, add_subnet_label and
+        decode_tcp_flags rules add (FlowTable.encode_flp_json_net)."""
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
+        if net is not None and k8s is None:
+            raise ValueError("net needs k8s: reinterpret_direction reads the Kubernetes keys")
         monotonic_now, current = self.monoClock(), self.clock()
         table = self.mapFetcher.table
         main_ids, main_vals, feats, n_cpu = self.mapFetcher.drain()
@@ -235,12 +238,16 @@ class MapTracer:
         names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         mono = monotonic_now & ((1 << 64) - 1)
         if self.sampleDecoder is None:                                  # s == nil: no events, no injected drops (record.go:126)
+            if net is not None:
+                return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, present, parts)
             if k8s is not None:
                 return table.encode_flp_json_k8s(recs, tls_names, k8s, current, mono, names, agent_ip, time_received, unknown, present, parts)
             if tls_names is not None:
                 return table.encode_flp_json_tls(recs, tls_names, current, mono, names, agent_ip, time_received, unknown, present, parts)
             return table.encode_flp_json_content(recs, present, parts, current, mono, names, agent_ip, time_received, unknown)
         p_out, parts, rows, tab = self.resolveNetworkEvents(present, parts)
+        if net is not None:
+            return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         if k8s is not None:
             return table.encode_flp_json_k8s(recs, tls_names, k8s, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         if tls_names is not None:
@@ -359,14 +366,18 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
     With `tls_names` (a TlsNames of `table`) the encoder writes those records' TLS keys itself (FlowTable.encode_flp_json_tls):
     nothing is deferred, `fallback` is never called and an eviction is one write. With `k8s` as well (a K8sTable of `table`; needs
     `tls_names`) the lines are those of the pipeline NetObserv ships, with the Kubernetes rules of its `transform network` stage in
-    front of the writer (FlowTable.encode_flp_json_k8s).
+    front of the writer (FlowTable.encode_flp_json_k8s). With `net` on top (a NetTable of `table`; needs `k8s`) the stage's
+    reinterpret_direction, add_subnet_label and decode_tcp_flags rules are applied too (FlowTable.encode_flp_json_net), and no host pass
+    over the lines is left.
 
     One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
 
     def __init__(self, table, stream, names=None, agent_ip=None, unknown: bytes = b"unknown", time_received: Callable[[], int] = None,
-                 fallback: Callable = None, encode=None, tls_names=None, k8s=None):
+                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None):
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
+        if net is not None and k8s is None:
+            raise ValueError("net needs k8s: reinterpret_direction reads the Kubernetes keys")
         self.table, self.stream = table, stream
         self.names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         self.agent_ip, self.unknown = agent_ip, unknown
@@ -375,7 +386,7 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         self.lines = self.deferred = 0
         # encode(raw, now_ns, mono_ns, names, agent_ip, time_received, unknown) -> (buf, line_offsets, deferred)
         self._encode = encode or table.encode_flp_json
-        self.tls_names, self.k8s = tls_names, k8s
+        self.tls_names, self.k8s, self.net = tls_names, k8s, net
 
     def ExportEvicted(self, raw, now_ns: int, mono_ns: int) -> int:
         """One eviction's lines. now_ns / mono_ns: the eviction's currentTime / monotonicCurrentTime (account.go:103-104).
@@ -384,7 +395,10 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         if n == 0:
             return 0
         if self.tls_names is not None:
-            if self.k8s is not None:
+            if self.net is not None:
+                buf, off = self.table.encode_flp_json_net(raw, self.tls_names, self.k8s, self.net, now_ns, mono_ns & ((1 << 64) - 1), self.names,
+                                                          self.agent_ip, self.time_received(), self.unknown)
+            elif self.k8s is not None:
                 buf, off = self.table.encode_flp_json_k8s(raw, self.tls_names, self.k8s, now_ns, mono_ns & ((1 << 64) - 1), self.names,
                                                           self.agent_ip, self.time_received(), self.unknown)
             else:

@@ -456,11 +456,11 @@ class FlowTable:
         return rc, need.value
 
     # -- export encode (record -> direct-FLP JSON lines), nfagg_encode_flp_json*
-    def _flp_json(self, records, options, features=None, rows=None, netev_table=None, tls_names=None, k8s=None):
+    def _flp_json(self, records, options, features=None, rows=None, netev_table=None, tls_names=None, k8s=None, net=None):
         """The host-memory entry points. options: flp_options(...). features: None (nfagg_encode_flp_json) or (present, parts)
         (the *_content ones; present None: no flow carries a part). rows and netev_table: the *_netev one. tls_names:
-        nfagg_encode_flp_json_tls, which takes the others as options and defers nothing; k8s (with tls_names): nfagg_encode_flp_json_k8s.
-        Returns (buf, line_offsets, deferred)."""
+        nfagg_encode_flp_json_tls, which takes the others as options and defers nothing; k8s (with tls_names): nfagg_encode_flp_json_k8s;
+        net (with k8s): nfagg_encode_flp_json_net. Returns (buf, line_offsets, deferred)."""
         r = np.ascontiguousarray(records)
         n = r.nbytes // 144
         o, keep = options
@@ -478,6 +478,8 @@ class FlowTable:
             fn, head, flags = L.lib.nfagg_encode_flp_json_tls, head + f_arg + ne_args + (tls_names._t,), ()
             if k8s is not None:
                 fn, head = L.lib.nfagg_encode_flp_json_k8s, head + (k8s._t,)
+                if net is not None:
+                    fn, head = L.lib.nfagg_encode_flp_json_net, head + (net._t,)
         else:
             flags = (deferred.ctypes.data_as(C.c_void_p), C.byref(n_def))
             if netev_table is not None:
@@ -492,7 +494,7 @@ class FlowTable:
         return buf, off, deferred
 
     def _flp_json_device(self, d_records, n, options, d_out, out_cap, d_line_offsets, d_deferred=0, features=None, d_rows=0,
-                         netev_table=None, tls_names=None, k8s=None):
+                         netev_table=None, tls_names=None, k8s=None, net=None):
         """The device entry points (raw device pointers); the optionals select as in _flp_json, features = (d_present, d_parts).
         Returns (rc, bytes needed/written, deferred records)."""
         o, keep = options
@@ -508,6 +510,8 @@ class FlowTable:
             fn, head, flags = L.lib.nfagg_encode_flp_json_tls_device, head + f_arg + ne_args + (tls_names._t,), ()
             if k8s is not None:
                 fn, head = L.lib.nfagg_encode_flp_json_k8s_device, head + (k8s._t,)
+                if net is not None:
+                    fn, head = L.lib.nfagg_encode_flp_json_net_device, head + (net._t,)
         elif netev_table is not None:
             fn, head = L.lib.nfagg_encode_flp_json_content_netev_device, head + f_arg + ne_args
         elif features is not None:
@@ -672,6 +676,48 @@ class FlowTable:
         return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
                                      d_out, out_cap, d_line_offsets, 0, (d_present, d_parts) if d_present else None, d_rows, netev_table,
                                      tls_names, k8s)[:2]
+
+    # -- direction, subnet labels, TCP flag names (nfagg_net_*): three more rules of the transform network stage
+    def net_table(self, flags: int = 0, categories=()) -> "NetTable":
+        """A net table on this handle's device; flags and categories as NetTable takes them."""
+        return NetTable(flags, categories, self)
+
+    def net_resolve(self, net: "NetTable", records: np.ndarray, k8s: "K8sTable" = None, k8s_rows: np.ndarray = None, agent_ip=None) -> np.ndarray:
+        """nfagg_net_resolve: NET_ROW[n] (src_label, dst_label: L.NET_NO_LABEL for none; direction: L.NET_NO_DIRECTION for no
+        key). k8s, k8s_rows (what k8s_resolve returned) and agent_ip (None: nil) are read for reinterpret_direction only."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        out = np.zeros(n, dtype=NET_ROW)
+        kr = np.ascontiguousarray(k8s_rows, dtype=np.uint32) if k8s_rows is not None else None
+        o, keep = flp_options(agent_ip=agent_ip)
+        self._check(L.lib.nfagg_net_resolve(self._h, net._t, k8s._t if k8s is not None else None, r.ctypes.data_as(C.c_void_p) if n else None, n,
+                                            kr.ctypes.data_as(C.c_void_p) if kr is not None and n else None, C.byref(o),
+                                            out.ctypes.data_as(C.c_void_p) if n else None))
+        return out
+
+    def net_resolve_device(self, net: "NetTable", d_records: int, n: int, d_out: int, k8s: "K8sTable" = None, d_k8s_rows: int = 0, agent_ip=None) -> None:
+        """Device-resident variant (raw device pointers; d_out: n NET_ROW of 8 bytes)."""
+        o, keep = flp_options(agent_ip=agent_ip)
+        self._check(L.lib.nfagg_net_resolve_device(self._h, net._t, k8s._t if k8s is not None else None, C.c_void_p(d_records or None), n,
+                                                   C.c_void_p(d_k8s_rows or None), C.byref(o), C.c_void_p(d_out or None)))
+
+    def encode_flp_json_net(self, records: np.ndarray, tls_names: "TlsNames", k8s: "K8sTable", net: "NetTable", now_unix_ns: int, mono_now_ns: int,
+                            names: np.ndarray, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", present=None, parts=None,
+                            rows=None, netev_table: "NetevTable" = None):
+        """encode_flp_json_k8s plus the rules switched on in `net`: FlowDirection, SrcSubnetLabel / DstSubnetLabel, the names
+        of the TCP flags as the value of Flags (nfagg_encode_flp_json_net). Returns (buf, line_offsets)."""
+        return self._flp_json(records, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown), (present, parts),
+                              rows, netev_table, tls_names, k8s, net)[:2]
+
+    def encode_flp_json_net_device(self, d_records: int, n: int, tls_names: "TlsNames", k8s: "K8sTable", net: "NetTable", now_unix_ns: int,
+                                   mono_now_ns: int, names: np.ndarray, agent_ip, time_received: int, d_out: int, out_cap: int,
+                                   d_line_offsets: int, unknown: bytes = b"unknown", d_present: int = 0, d_parts=None, d_rows: int = 0,
+                                   netev_table: "NetevTable" = None):
+        """Device-resident variant (raw device pointers; d_present = 0: no parts; d_out = 0 asks for the size). Returns (rc,
+        bytes needed/written)."""
+        return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
+                                     d_out, out_cap, d_line_offsets, 0, (d_present, d_parts) if d_present else None, d_rows, netev_table,
+                                     tls_names, k8s, net)[:2]
 
     def stats(self) -> L.Stats:
         s = L.Stats()
@@ -1154,6 +1200,92 @@ class K8sTable:
 
     def __exit__(self, *a):
         self.close()
+
+
+NET_ROW = np.dtype([("src_label", "<u2"), ("dst_label", "<u2"), ("direction", "u1"), ("pad_", "u1", (3,))])      # nfagg_net_row
+
+
+def net_cidrs(categories):
+    """The FLP stage's subnetLabels as the flat lists nfagg_net_rules takes: categories = [(name, [CIDR text])] in configuration
+    order. Returns ([(ip16, ones, bits, label)], [name bytes]) in walk order, each CIDR as net.ParseCIDR returns it (the
+    address as typed, To16; bits 32 for IPv4 text, 128 for IPv6 text). A category without CIDRs is dropped, as parseSubnets
+    drops it. Text the stdlib `ipaddress` module refuses raises ValueError."""
+    import ipaddress
+    cidrs, labels = [], []
+    for name, texts in categories:
+        texts = list(texts)
+        if not texts:
+            continue
+        labels.append(name.encode() if isinstance(name, str) else bytes(name))
+        for text in texts:
+            addr, slash, ones = text.partition("/")
+            ip = ipaddress.ip_address(addr)
+            if not slash or not ones.isdigit() or int(ones) > ip.max_prefixlen:
+                raise ValueError("not a CIDR: %r" % text)
+            cidrs.append((_k8s_ip16(ip.packed), int(ones), ip.max_prefixlen, len(labels) - 1))
+    return cidrs, labels
+
+
+def _net_rules(flags, cidrs, labels):
+    """nfagg_net_rules of flat lists as net_cidrs returns them. Returns (struct, keep)."""
+    ca = (L.NetCidr * max(len(cidrs), 1))()
+    for k, (ip, ones, bits, label) in enumerate(cidrs):
+        ca[k].ip[:] = _k8s_ip16(ip)
+        ca[k].ones, ca[k].bits, ca[k].label = ones, bits, label
+    texts = [x.encode() if isinstance(x, str) else bytes(x) for x in labels]
+    la = (L.NetLabel * max(len(texts), 1))()
+    for k, t in enumerate(texts):
+        la[k].text, la[k].len = t, len(t)
+    return L.NetRules(C.sizeof(L.NetRules), flags, ca, la, len(cidrs), len(texts)), (ca, la, texts)
+
+
+class NetTable:
+    """Three rules of the FLP `transform network` stage as a table (nfagg_net_table_create). flags: L.NET_REINTERPRET_DIRECTION |
+    L.NET_SUBNET_LABELS | L.NET_DECODE_TCP_FLAGS, each rule on its own. categories: the stage's subnetLabels, [(name, [CIDR
+    text])] in configuration order (net_cidrs), or with raw=True the flat (cidrs, labels) lists themselves. With a FlowTable
+    the table lives on its device and serves net_resolve and encode_flp_json_net; with table=None it is built and checked on
+    the host only. Rebuild it when the stage's configuration is updated."""
+
+    def __init__(self, flags: int = 0, categories=(), table: "FlowTable" = None, raw: bool = False):
+        cidrs, labels = categories if raw else net_cidrs(categories)
+        rules, keep = _net_rules(flags, list(cidrs), list(labels))
+        self._t = C.c_void_p()
+        h = table._h if table is not None else None
+        rc = L.lib.nfagg_net_table_create(h, C.byref(rules), C.byref(self._t))
+        if rc != L.OK:
+            self._t = None
+            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
+        self._owner = table                       # the handle must outlive the table
+        self.flags, self.n_cidrs, self.n_labels = flags, rules.n_cidrs, rules.n_labels
+
+    def close(self):
+        if getattr(self, "_t", None):
+            if self._owner is None or self._owner._h:
+                L.lib.nfagg_net_table_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def net_render(net: "NetTable", side: int, label: int) -> bytes:
+    """nfagg_net_render: the fragment the encoder writes behind SrcPort (side 0) or DstPort (side 1) for label `label` of the
+    table, with its leading comma; b"" for an empty label. Host only."""
+    buf = np.zeros(L.NET_LABEL_MAX + 32, dtype=np.uint8)
+    n = C.c_size_t(0)
+    rc = L.lib.nfagg_net_render(net._t, side, label, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n))
+    if rc != L.OK:
+        raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
+    return buf[:n.value].tobytes()
 
 
 def ip_hash(ip16: bytes, seed_index: int) -> int:

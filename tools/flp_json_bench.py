@@ -22,7 +22,12 @@ name table. Both report their time per flow and per output byte.
 and through nfagg_encode_flp_json_k8s_device with a table of 100 000 rows and a layer: every other distinct address of the
 evicted flows (as many as fit), filled up with addresses no flow has. The hash join alone (nfagg_k8s_resolve_device) is timed
 too. Kernel-level device time: run the same leg under rocprofv3 --kernel-trace --output-format csv -d DIR, then
---k8s-trace DIR prints the median device time of every encoder kernel per launch size from that trace."""
+--k8s-trace DIR prints the median device time of every encoder kernel per launch size from that trace.
+
+--net (with --k8s): the transform network leg on top, on the same records and the same Kubernetes table in the same run:
+nfagg_encode_flp_json_net_device with reinterpret_direction, add_subnet_label and decode_tcp_flags on and 48 CIDRs in seven categories
+(46 narrow ones no address need match, then 0.0.0.0/0 and ::/0, so that every address walks the whole list). The join alone
+(nfagg_net_resolve_device) is timed too; --k8s-trace covers the k_net_* kernels."""
 import io
 import os
 import queue
@@ -46,6 +51,9 @@ NOW, MONO = 10**18, 10**12
 CONTENT = "--content" in sys.argv[1:]
 TLS = "--tls" in sys.argv[1:]
 K8S = "--k8s" in sys.argv[1:]
+NET = "--net" in sys.argv[1:]
+NET_CATEGORIES = [("cat-%d" % c, ["172.%d.%d.0/24" % (16 + c, k) for k in range(8)] + ["2001:db8:%x::/48" % (16 * c + k) for k in range(1)]) for c in range(5)] + \
+                 [("pods", ["100.64.0.0/10"]), ("everything", ["0.0.0.0/0", "::/0"])]
 K8S_ROWS = 100_000
 PART_BYTES = {"additional": 32, "dns": 64, "drops": 32, "xlat": 56, "quic": 24}
 
@@ -116,7 +124,7 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|scan", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|scan", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
             grid = int(row.get("Grid_Size_X") or row.get("Grid_Size") or 0)
@@ -192,6 +200,25 @@ for flows in ((10_000_000,) if CONTENT or TLS else (1_000_000, 10_000_000)):
                 print(f"           table: {len(entries)} rows, {min(K8S_ROWS, (n_distinct + 1) // 2)} of them among the {n_distinct} distinct addresses of {n_ip} IP flows; "
                       f"{hits} of {2 * m} endpoints resolved; the hash join alone: {dt_res * 1e3:.3f} ms per call")
                 del d_out
+                if NET:
+                    flags = nf._lib.NET_REINTERPRET_DIRECTION | nf._lib.NET_SUBNET_LABELS | nf._lib.NET_DECODE_TCP_FLAGS
+                    d_net = torch.empty((m, 2), dtype=torch.int32, device="cuda")
+                    with tab.net_table(flags, NET_CATEGORIES) as net:
+                        tab.k8s_resolve_device(k8s, d_ev.data_ptr(), m, d_rows.data_ptr())
+                        _, dt_net = timed(lambda: tab.net_resolve_device(net, d_ev.data_ptr(), m, d_net.data_ptr(), k8s, d_rows.data_ptr(), agent))
+                        got = d_net.cpu().numpy().view(nf.NET_ROW).reshape(-1)
+                        rc, need = tab.encode_flp_json_net_device(d_ev.data_ptr(), m, tls, k8s, net, NOW, MONO, names, agent, 1_700_000_000, 0, 0,
+                                                                  d_off.data_ptr())
+                        d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+                        (rc, wrote), dt = timed(lambda: tab.encode_flp_json_net_device(d_ev.data_ptr(), m, tls, k8s, net, NOW, MONO, names, agent,
+                                                                                      1_700_000_000, d_out.data_ptr(), need, d_off.data_ptr()))
+                        assert rc == nf.OK and wrote == need
+                        per_byte("_net", m, dt, wrote)
+                        print(f"           rules: all three, {net.n_cidrs} CIDRs in {net.n_labels} categories; "
+                              f"{int((got['src_label'] != nf._lib.NET_NO_LABEL).sum() + (got['dst_label'] != nf._lib.NET_NO_LABEL).sum())} of {2 * m} endpoints labelled, "
+                              f"{int((got['direction'] != nf._lib.NET_NO_DIRECTION).sum())} of {m} flows with a direction; the join alone: {dt_net * 1e3:.3f} ms per call")
+                        del d_out
+                    del d_net
             del d_ev, d_off, d_rows
             continue
         # direct-FLP JSON
