@@ -1297,6 +1297,99 @@ int nfagg_encode_flp_json_net_device(nfagg_handle* h, const void* d_records, siz
 uint32_t nfagg_flp_json_net_max_line(int policy);
 
 /* ------------------------------------------------------------------ */
+/* Flow metrics — the GROUP BY under flowlogs-pipeline's `encode prom`  */
+/* counters (pkg/pipeline/encode/metrics_common.go:107-125 ProcessCounter, */
+/* 179-211 prepareMetric, 265-295 extractLabels; pkg/api/encode_prom.go). */
+/* The reference walks every flow for every metric: filters, value,     */
+/* label map, a timed-cache lookup, Add. Here the device groups the     */
+/* flows by a tuple of small dimension ids and sums; the host then      */
+/* visits the GROUPS (thousands, not millions) and does there what      */
+/* prepareMetric does per flow: filters with a real regex engine, the   */
+/* value key, the label texts, Add. A metric's grouping is the set of   */
+/* keys its labels AND its filters name; that is exact, because every   */
+/* predicate of utils/filters/filters.go and every label value is a     */
+/* function of those keys alone. Everything a counter needs per flow is */
+/* on the device as small integers already: the two Kubernetes rows     */
+/* (nfagg_k8s_resolve), the two label indexes and the direction         */
+/* (nfagg_net_resolve), the row's app flag, and bytes, packets, the     */
+/* ethertype and the protocol of the record. The sums are integers, so  */
+/* the result does not depend on the order of the flows.                */
+/*                                                                      */
+/* Differences from the reference, by design:                           */
+/*  - one table serves a whole call;                                    */
+/*  - MaxMetrics and the expiry cache are the host's business: they     */
+/*    depend on the order of the flows and are not restated;            */
+/*  - sums are exact integers: a valueScale is applied by the host to   */
+/*    the sum, not per flow;                                            */
+/*  - counters only: gauges, histograms, `flatten`, and keys outside    */
+/*    the dimension list (Interfaces, the DNS, drop and RTT keys, Dscp, */
+/*    ...) stay on the host path.                                       */
+/* ------------------------------------------------------------------ */
+
+/* One grouping is a mask of dimensions. Bit f (0..8): field f of the src row in nfagg_k8s_entry's order (namespace, name,
+ * kind, owner_name, owner_kind, network_name, host_ip, host_name, zone); bit 9 + f: the same field of the dst row. */
+#define NFAGG_DIM_SRC_K8S(f) (1u << (f))
+#define NFAGG_DIM_DST_K8S(f) (1u << (9 + (f)))
+#define NFAGG_DIM_SRC_SUBNET_LABEL (1u << 18)
+#define NFAGG_DIM_DST_SUBNET_LABEL (1u << 19)
+#define NFAGG_DIM_FLOW_DIRECTION (1u << 20)
+#define NFAGG_DIM_FLOW_LAYER (1u << 21)
+#define NFAGG_DIM_PROTO (1u << 22)
+#define NFAGG_DIM_ALL ((1u << 23) - 1u)
+
+#define NFAGG_MET_MAX_GROUPINGS 8
+#define NFAGG_MET_MAX_GROUPS (1u << 20)
+
+/* One group of one grouping. A dimension that the grouping does not select carries its "none" value in every group. */
+typedef struct nfagg_metric_group {
+    uint32_t src_class, dst_class;    /* nfagg_metrics_class_row turns a class back into a table row; 0: no row, or no field selected */
+    uint16_t src_label, dst_label;    /* the net row's values; NFAGG_NET_NO_LABEL: none */
+    uint8_t direction;                /* NFAGG_NET_NO_DIRECTION: none */
+    uint8_t layer;                    /* 0: no key, 1: infra, 2: app */
+    uint8_t proto;                    /* 0 unless is_ip */
+    uint8_t is_ip;                    /* eth_protocol 0x0800 or 0x86DD: only then does RecordToMap write Proto (decode_protobuf.go:112-116) */
+    uint64_t flows, bytes, packets;   /* sums over the group's flows (modulo 2^64) */
+    /* RecordToMap omits Bytes / Packets when zero (decode_protobuf.go:87-93) and extractGenericValue then skips the flow
+     * before its labels are registered (metrics_common.go:249-253): a series exists for a value key only if its count is not 0 */
+    uint64_t flows_with_bytes, flows_with_packets;
+    uint64_t pad_;                    /* 0 */
+} nfagg_metric_group;
+
+typedef struct nfagg_metrics_table nfagg_metrics_table;
+
+/* Build the table of n_groupings (1..NFAGG_MET_MAX_GROUPINGS) masks over the rows of k8s_table, which must outlive it. For
+ * every grouping and side each Kubernetes row gets a CLASS: the dense id, from 1 in order of first appearance, of the tuple of
+ * its selected fields, each taken as (text, presence) with nfagg_k8s_render's presence: namespace and host_ip only when not
+ * empty, host_name only when host_ip and host_name are both not empty, zone only with has_zone, the other five always. Two
+ * rows with equal selected tuples share a class; class 0: the side has no row, or the grouping selects no field of it.
+ * Unknown bits, n_groupings out of range, a null argument: NFAGG_EINVAL. With a handle (k8s_table must be of the same
+ * handle) the classes are uploaded, one uint32 per row, grouping and selected side; h == NULL builds and checks the table on
+ * the host alone (k8s_table built with h == NULL as well; errors through nfagg_last_error(NULL)), and the fold refuses it. */
+int nfagg_metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const uint32_t* dims, uint32_t n_groupings,
+                               nfagg_metrics_table** table);
+void nfagg_metrics_table_destroy(nfagg_metrics_table* table);
+/* Classes of grouping g, side 0 (src) or 1 (dst), class 0 not counted; 0 for arguments out of range. */
+uint32_t nfagg_metrics_n_classes(const nfagg_metrics_table* table, uint32_t g, int side);
+/* *row = the first entry index of class cls (NFAGG_K8S_NO_ROW for class 0): the caller turns a class back into strings from
+ * its own entries. NFAGG_EINVAL for arguments out of range. */
+int nfagg_metrics_class_row(const nfagg_metrics_table* table, uint32_t g, int side, uint32_t cls, uint32_t* row);
+
+/* The fold. k8s_rows (2 x uint32 per record) and net_rows are what nfagg_k8s_resolve and nfagg_net_resolve wrote for these
+ * records; net_rows may be NULL only if no grouping selects a label or direction dimension (else NFAGG_EINVAL). group_cap,
+ * out and n_groups are arrays of n_groupings: out[g] has room for group_cap[g] (<= NFAGG_MET_MAX_GROUPS, else NFAGG_ERANGE)
+ * groups and receives grouping g's groups in unspecified order, n_groups[g] their number. If any grouping has more distinct
+ * groups than its cap: NFAGG_TRUNCATED, nothing is written to any out[g], n_groups[g] is exact for the groupings that fit
+ * and some value greater than group_cap[g] (a lower bound) for those that did not. n == 0 is valid: no groups. All pointers
+ * HOST memory: */
+int nfagg_metrics_fold(nfagg_handle* h, const nfagg_metrics_table* table, const void* records, size_t n, const uint32_t* k8s_rows,
+                       const nfagg_net_row* net_rows, const uint32_t* group_cap, nfagg_metric_group* const* out, uint32_t* n_groups);
+/* Same with records, k8s_rows, net_rows and every out[g] in DEVICE memory (records and every out[g] 16-byte, the rows 8-byte
+ * aligned); the three arrays of n_groupings themselves stay in host memory. */
+int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table, const void* d_records, size_t n,
+                              const uint32_t* d_k8s_rows, const nfagg_net_row* d_net_rows, const uint32_t* group_cap,
+                              nfagg_metric_group* const* d_out, uint32_t* n_groups);
+
+/* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */
 /* ------------------------------------------------------------------ */
 

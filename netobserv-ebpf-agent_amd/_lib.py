@@ -152,6 +152,12 @@ class NetRow(C.Structure):
 NET_REINTERPRET_DIRECTION, NET_SUBNET_LABELS, NET_DECODE_TCP_FLAGS = 1, 2, 4
 NET_MAX_CIDRS, NET_LABEL_MAX, NET_NO_LABEL, NET_NO_DIRECTION = 1024, 256, 0xFFFF, 0xFF
 
+# flow metrics (nfagg_metrics_*): one grouping is a mask of dimensions
+DIM_SRC_K8S, DIM_DST_K8S = (lambda f: 1 << f), (lambda f: 1 << (9 + f))      # f: index into table.K8S_FIELDS
+DIM_SRC_SUBNET_LABEL, DIM_DST_SUBNET_LABEL, DIM_FLOW_DIRECTION, DIM_FLOW_LAYER, DIM_PROTO = 1 << 18, 1 << 19, 1 << 20, 1 << 21, 1 << 22
+DIM_ALL = (1 << 23) - 1
+MET_MAX_GROUPINGS, MET_MAX_GROUPS = 8, 1 << 20
+
 TLS_VERSION, TLS_CIPHER_SUITE, TLS_GROUP = 0, 1, 2
 TLS_NAME_MAX, TLS_MAX_ROWS = 63, 256
 
@@ -259,6 +265,12 @@ SIGNATURES = {
     "nfagg_encode_flp_json_net": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
     "nfagg_encode_flp_json_net_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
     "nfagg_flp_json_net_max_line": (C.c_uint32, [C.c_int]),
+    "nfagg_metrics_table_create": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_vp)]),
+    "nfagg_metrics_table_destroy": (None, [_vp]),
+    "nfagg_metrics_n_classes": (C.c_uint32, [_vp, C.c_uint32, C.c_int]),
+    "nfagg_metrics_class_row": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "nfagg_metrics_fold": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    "nfagg_metrics_fold_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(C.c_uint32)]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

@@ -9,6 +9,7 @@
 #include <string.h>
 #include <algorithm>
 #include <initializer_list>
+#include <map>
 #include <mutex>
 #include <new>
 #include <set>
@@ -24,6 +25,7 @@
 #include "nfagg_ipfix.h"
 #include "nfagg_flp.h"
 #include "nfagg_netev.h"
+#include "nfagg_metrics.h"
 
 using namespace nfagg;
 
@@ -100,13 +102,14 @@ struct nfagg_handle {
         DevBuf ne_in[3], ne_out[3], ne_missing, ne_info;   // nfagg_netev_resolve: staged inputs and outputs, the missing set, its counters
         DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record
         DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record
+        DevBuf met_slots, met_out;                   // nfagg_metrics_fold: control words and the groupings' tables; the host entry point's groups
         std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
         std::vector<uint8_t> h_flp_esc;
         template <typename F> void each(F f) {
             for (DevBuf* b : {&local_off, &block_sum, &block_base, &names, &ipfix_name_rows, &flp_rows, &flp_esc, &flp_n_deferred,
                               &in_records, &out, &out_offsets, &out_extra[0], &out_extra[1]}) f(*b);
             for (DevBuf& b : pb_feat) f(b);
-            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows, &net_rows}) f(*b);
+            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows, &net_rows, &met_slots, &met_out}) f(*b);
         }
     } enc;
     // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
@@ -2227,6 +2230,11 @@ struct nfagg_k8s_table {
     // own beside the rows (the kernels that read K8sRow do not see it); host_text finds a call's reporter
     std::vector<uint32_t> host_ids;
     std::unordered_map<std::string, uint32_t> host_text;
+    // nfagg_metrics_table_create groups rows by the TEXT of their fields: nine ids per row in nfagg_k8s_entry's order, 0: the
+    // field is absent as nfagg_k8s_render has it, else 1 + the interned text (the empty string has an id like any other).
+    // Host side only.
+    std::vector<uint32_t> field_ids;
+    std::unordered_map<std::string, uint32_t> field_text;
     void* d_slots = nullptr;
     void* d_rows = nullptr;
     void* d_blob = nullptr;
@@ -3276,6 +3284,14 @@ int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size
         row.flags = layer && k8s_is_app(e, *layer) ? kK8sRowApp : 0u;
         // the text of the row's SrcK8S_HostIP / DstK8S_HostIP key, as reinterpret_direction compares it; the key is absent for ""
         t->host_ids[r] = e.host_ip_len ? t->host_text.emplace(std::string(e.host_ip, e.host_ip_len), (uint32_t)t->host_text.size() + 1).first->second : 0u;
+        const K8sStr field[9] = {{e.namespace_, e.namespace_len}, {e.name, e.name_len}, {e.kind, e.kind_len}, {e.owner_name, e.owner_name_len},
+                                 {e.owner_kind, e.owner_kind_len}, {e.network_name, e.network_name_len}, {e.host_ip, e.host_ip_len},
+                                 {e.host_name, e.host_name_len}, {e.zone, e.zone_len}};
+        const bool present[9] = {e.namespace_len != 0, true, true, true, true, true, e.host_ip_len != 0, e.host_ip_len != 0 && e.host_name_len != 0,
+                                 e.has_zone != 0};
+        for (int f = 0; f < 9; f++)                                      // k8s_render has refused a null string with a length
+            t->field_ids.push_back(present[f] ? 1u + t->field_text.emplace(std::string(field[f].p ? field[f].p : "", field[f].len),
+                                                                           (uint32_t)t->field_text.size()).first->second : 0u);
     }
     if (h) {
         auto up = [&]() -> int {
@@ -3541,6 +3557,190 @@ int nfagg_encode_flp_json_net(nfagg_handle* h, const void* records, size_t n, co
     const NetevArgs ne{rows, netev_table};
     const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
     return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+}
+
+}  // extern "C"
+
+// ---- flow metrics (nfagg_metrics.h): the groupings' classes over a Kubernetes table, and the fold's host side
+struct nfagg_metrics_table {
+    nfagg_handle* h = nullptr;
+    const nfagg_k8s_table* k8s = nullptr;              // not owned: the caller keeps it alive
+    uint32_t n_groupings = 0;
+    uint32_t dims[kMetMaxGroupings] = {};
+    std::vector<uint32_t> cls[kMetMaxGroupings][2];    // per row; empty: the grouping selects no field of that side
+    std::vector<uint32_t> first_row[kMetMaxGroupings][2];   // [class - 1] = the first row of that class
+    void* d_cls = nullptr;                             // the non-empty cls arrays one behind the other
+    size_t d_off[kMetMaxGroupings][2] = {};            // in words
+};
+
+extern "C" {
+
+int nfagg_metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const uint32_t* dims, uint32_t n_groupings,
+                               nfagg_metrics_table** table) {
+    if (!table || !k8s_table || !dims) return fail(h, NFAGG_EINVAL, "null argument");
+    *table = nullptr;
+    if (n_groupings < 1 || n_groupings > kMetMaxGroupings) return fail(h, NFAGG_EINVAL, "%u groupings, not 1..%u", n_groupings, kMetMaxGroupings);
+    for (uint32_t g = 0; g < n_groupings; g++)
+        if (dims[g] & ~NFAGG_DIM_ALL) return fail(h, NFAGG_EINVAL, "grouping %u: unknown dimension bits 0x%x", g, dims[g] & ~NFAGG_DIM_ALL);
+    if (k8s_table->h != h) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
+    nfagg_metrics_table* t = new (std::nothrow) nfagg_metrics_table;
+    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
+    t->h = h;
+    t->k8s = k8s_table;
+    t->n_groupings = n_groupings;
+    const size_t n = k8s_table->rows.size();
+    size_t words = 0;
+    for (uint32_t g = 0; g < n_groupings; g++) {
+        t->dims[g] = dims[g];
+        for (int side = 0; side < 2; side++) {
+            const uint32_t sel = (dims[g] >> (9 * side)) & kMetSrcFields;
+            if (!sel) continue;
+            std::map<std::vector<uint32_t>, uint32_t> seen;
+            std::vector<uint32_t> key;
+            t->cls[g][side].resize(n);
+            for (size_t r = 0; r < n; r++) {
+                key.clear();
+                for (int f = 0; f < 9; f++) if (sel & (1u << f)) key.push_back(k8s_table->field_ids[r * 9 + f]);
+                const auto it = seen.emplace(key, (uint32_t)seen.size() + 1);
+                if (it.second) t->first_row[g][side].push_back((uint32_t)r);
+                t->cls[g][side][r] = it.first->second;
+            }
+            t->d_off[g][side] = words;
+            words += (n + 3) / 4 * 4;
+        }
+    }
+    if (h) {
+        auto up = [&]() -> int {
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMalloc(&t->d_cls, std::max<size_t>(words, 4) * sizeof(uint32_t)));
+            for (uint32_t g = 0; g < n_groupings; g++)
+                for (int side = 0; side < 2; side++)
+                    if (n && !t->cls[g][side].empty())
+                        HIP_TRY(h, hipMemcpy((uint32_t*)t->d_cls + t->d_off[g][side], t->cls[g][side].data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            return NFAGG_OK;
+        };
+        const int rc = up();
+        if (rc != NFAGG_OK) { nfagg_metrics_table_destroy(t); return rc; }
+    }
+    *table = t;
+    return NFAGG_OK;
+}
+
+void nfagg_metrics_table_destroy(nfagg_metrics_table* t) {
+    if (!t) return;
+    if (t->h && t->d_cls) {
+        (void)hipSetDevice(t->h->device);
+        (void)hipStreamSynchronize(t->h->stream);
+        (void)hipFree(t->d_cls);
+    }
+    delete t;
+}
+
+uint32_t nfagg_metrics_n_classes(const nfagg_metrics_table* table, uint32_t g, int side) {
+    if (!table || g >= table->n_groupings || (side != 0 && side != 1)) return 0;
+    return (uint32_t)table->first_row[g][side].size();
+}
+
+int nfagg_metrics_class_row(const nfagg_metrics_table* table, uint32_t g, int side, uint32_t cls, uint32_t* row) {
+    nfagg_handle* h = table ? table->h : nullptr;
+    if (!table || !row) return fail(h, NFAGG_EINVAL, "null argument");
+    if (g >= table->n_groupings || (side != 0 && side != 1)) return fail(h, NFAGG_EINVAL, "grouping %u, side %d: out of range", g, side);
+    if (cls > table->first_row[g][side].size()) return fail(h, NFAGG_EINVAL, "class %u of %zu", cls, table->first_row[g][side].size());
+    *row = cls ? table->first_row[g][side][cls - 1] : NFAGG_K8S_NO_ROW;
+    return NFAGG_OK;
+}
+
+int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table, const void* d_records, size_t n, const uint32_t* d_k8s_rows,
+                              const nfagg_net_row* d_net_rows, const uint32_t* group_cap, nfagg_metric_group* const* d_out, uint32_t* n_groups) {
+    if (!h || !table || !group_cap || !d_out || !n_groups || (n && (!d_records || !d_k8s_rows))) return fail(h, NFAGG_EINVAL, "null argument");
+    if (table->h != h || !table->d_cls) return fail(h, NFAGG_EINVAL, "the metrics table was not created for this handle");
+    const uint32_t G = table->n_groupings;
+    const uint32_t net_dims = NFAGG_DIM_SRC_SUBNET_LABEL | NFAGG_DIM_DST_SUBNET_LABEL | NFAGG_DIM_FLOW_DIRECTION;
+    MetDev M{};
+    M.n_groupings = G;
+    uint64_t blocks = 0;
+    for (uint32_t g = 0; g < G; g++) {
+        if (group_cap[g] > kMetMaxGroups) return fail(h, NFAGG_ERANGE, "grouping %u: a cap of %u groups, more than %u", g, group_cap[g], kMetMaxGroups);
+        if (group_cap[g] && !d_out[g]) return fail(h, NFAGG_EINVAL, "grouping %u: a cap without an output array", g);
+        if (((uintptr_t)d_out[g] & 15u) != 0) return fail(h, NFAGG_EINVAL, "device records and group arrays must be 16-byte, rows 8-byte aligned");
+        if (n && (table->dims[g] & net_dims) && !d_net_rows) return fail(h, NFAGG_EINVAL, "grouping %u selects a label or the direction: it needs the flows' net rows", g);
+        M.dims[g] = table->dims[g];
+        M.cap[g] = group_cap[g];
+        M.mask[g] = (uint32_t)std::max<uint64_t>(next_pow2(2ull * group_cap[g]), kMetMinSlots) - 1;
+        M.first_block[g] = (uint32_t)blocks;
+        blocks += ((uint64_t)M.mask[g] + 1) / kMetMinSlots;
+        M.out[g] = d_out[g];
+        if (M.dims[g] & NFAGG_DIM_FLOW_LAYER) M.any_layer = 1;
+        for (int side = 0; side < 2; side++)
+            M.cls[g][side] = table->cls[g][side].empty() ? nullptr : (const uint32_t*)table->d_cls + table->d_off[g][side];
+    }
+    M.first_block[G] = (uint32_t)blocks;
+    if (((uintptr_t)d_records & 15u) != 0 || ((uintptr_t)d_k8s_rows & 7u) != 0 || ((uintptr_t)d_net_rows & 7u) != 0)
+        return fail(h, NFAGG_EINVAL, "device records and group arrays must be 16-byte, rows 8-byte aligned");
+    for (uint32_t g = 0; g < G; g++) n_groups[g] = 0;
+    if (!n) return NFAGG_OK;
+    const K8sDev K = k8s_dev(table->k8s);
+    M.rows = K.rows; M.n_rows = K.n_rows; M.has_layer = K.has_layer;
+    auto& S = h->enc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    const size_t slot_bytes = (size_t)blocks * kMetMinSlots * kMetSlotWords * sizeof(uint64_t);
+    if ((rc = ensure_buf(h, S.met_slots, 256 + slot_bytes)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.local_off, (size_t)blocks * kMetMinSlots * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.block_sum, (size_t)blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.block_base, ((size_t)blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    M.ctl = (MetCtl*)S.met_slots.p;
+    uint64_t* slots = (uint64_t*)((uint8_t*)S.met_slots.p + 256);
+    for (uint32_t g = 0; g < G; g++) M.slots[g] = slots + (size_t)M.first_block[g] * kMetMinSlots * kMetSlotWords;
+    HIP_TRY(h, hipMemsetAsync(S.met_slots.p, 0, 256 + slot_bytes, h->stream));
+    hipError_t e = launch_metrics_fold(d_records, n, M, d_k8s_rows, (const uint2*)d_net_rows, h->stream);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "metrics fold launch failed: %s", hipGetErrorString(e));
+    e = launch_metrics_emit(M, (uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p, h->stream);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "metrics emit launch failed: %s", hipGetErrorString(e));
+    MetCtl ctl;
+    HIP_TRY(h, hipMemcpyAsync(&ctl, M.ctl, sizeof ctl, hipMemcpyDeviceToHost, h->stream));      // the one read-back: counts and flags
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    bool over = false;
+    for (uint32_t g = 0; g < G; g++) {
+        // an overflowed grouping stopped claiming behind its cap: its count is a lower bound, and above the cap
+        n_groups[g] = ctl.over[g] ? std::max(ctl.count[g], group_cap[g] + 1) : ctl.count[g];
+        over = over || ctl.over[g];
+    }
+    return over ? NFAGG_TRUNCATED : NFAGG_OK;
+}
+
+int nfagg_metrics_fold(nfagg_handle* h, const nfagg_metrics_table* table, const void* records, size_t n, const uint32_t* k8s_rows,
+                       const nfagg_net_row* net_rows, const uint32_t* group_cap, nfagg_metric_group* const* out, uint32_t* n_groups) {
+    if (!h || !table || !group_cap || !out || !n_groups || (n && (!records || !k8s_rows))) return fail(h, NFAGG_EINVAL, "null argument");
+    const uint32_t G = table->n_groupings;
+    size_t total = 0;
+    for (uint32_t g = 0; g < G; g++) {
+        if (group_cap[g] > kMetMaxGroups) return fail(h, NFAGG_ERANGE, "grouping %u: a cap of %u groups, more than %u", g, group_cap[g], kMetMaxGroups);
+        if (group_cap[g] && !out[g]) return fail(h, NFAGG_EINVAL, "grouping %u: a cap without an output array", g);
+        total += group_cap[g];
+    }
+    auto& S = h->enc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.met_out, total * sizeof(nfagg_metric_group) + 16)) != NFAGG_OK) return rc;
+    if (n) {
+        HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        if (net_rows) HIP_TRY(h, hipMemcpyAsync(S.net_rows.p, net_rows, n * sizeof(nfagg_net_row), hipMemcpyHostToDevice, h->stream));
+    }
+    nfagg_metric_group* d_out[kMetMaxGroupings] = {};
+    size_t at = 0;
+    for (uint32_t g = 0; g < G; g++) { d_out[g] = (nfagg_metric_group*)S.met_out.p + at; at += group_cap[g]; }
+    rc = nfagg_metrics_fold_device(h, table, S.in_records.p, n, (const uint32_t*)S.k8s_rows.p, net_rows ? (const nfagg_net_row*)S.net_rows.p : nullptr, group_cap,
+                                   d_out, n_groups);
+    if (rc != NFAGG_OK) return rc;
+    for (uint32_t g = 0; g < G; g++)
+        if (n_groups[g]) HIP_TRY(h, hipMemcpyAsync(out[g], d_out[g], (size_t)n_groups[g] * sizeof(nfagg_metric_group), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,202 @@
+"""The counters of flowlogs-pipeline's `encode prom` stage over the GPU's grouped sums (nfagg_metrics_fold): the host mirror of
+pkg/pipeline/encode/metrics_common.go:107-125,179-211,265-295 that visits the GROUPS, not the flows.
+
+The reference runs prepareMetric for every flow and every metric: filters, value key, label map, cache lookup, Add. Here the
+device groups the flows by the keys a metric's labels and filters name and sums flows, bytes and packets; per group this module
+rebuilds those keys, applies the filters (ApplyFilters, encode/metrics/filtering.go:5-23, over the six predicates of
+utils/filters/filters.go), takes the value and the labels and adds once. That is exact: every predicate and every label value
+is a function of the grouping's keys alone.
+
+Strings are bytes throughout, as Go's are: keys and label targets are str, values (label values, filter values after UTF-8
+encoding) are bytes. Python's `re` stands in for Go's RE2 (regexp.MatchString is an unanchored search: re.search); the two
+engines agree on the common syntax, but not on everything (RE2 has no backreferences or lookaround; a few escapes differ), so a
+pattern that only one of them accepts, or that they read differently, is the caller's to avoid.
+
+Not restated, by design: MaxMetrics and the expiry cache (order-dependent, the caller's business), gauges, histograms, `flatten`,
+and keys outside the dimension list (Interfaces, the DNS, drop and RTT keys, Dscp, ...): PromCounters raises ValueError for such
+an item, which stays on the host path."""
+import re
+
+
+from . import _lib as L
+from .table import K8S_FIELDS
+
+K8S_SUFFIXES = ("Namespace", "Name", "Type", "OwnerName", "OwnerType", "NetworkName", "HostIP", "HostName", "Zone")   # transform_network.go:153-162
+KEY_DIMS = {}
+for _f, _s in enumerate(K8S_SUFFIXES):
+    KEY_DIMS["SrcK8S_" + _s] = L.DIM_SRC_K8S(_f)
+    KEY_DIMS["DstK8S_" + _s] = L.DIM_DST_K8S(_f)
+KEY_DIMS.update(SrcSubnetLabel=L.DIM_SRC_SUBNET_LABEL, DstSubnetLabel=L.DIM_DST_SUBNET_LABEL, FlowDirection=L.DIM_FLOW_DIRECTION,
+                K8S_FlowLayer=L.DIM_FLOW_LAYER, Proto=L.DIM_PROTO)
+NET_DIMS = L.DIM_SRC_SUBNET_LABEL | L.DIM_DST_SUBNET_LABEL | L.DIM_FLOW_DIRECTION
+VALUE_FIELDS = {"": ("flows", "flows"), "Bytes": ("bytes", "flows_with_bytes"), "Packets": ("packets", "flows_with_packets")}
+VARIABLE = re.compile(rb"\$\(([^\)]+)\)")                 # filters.go:13
+FILTER_TYPES = ("equal", "not_equal", "presence", "absence", "match_regex", "not_match_regex")      # api/encode_prom.go:65-73
+
+
+def _b(v) -> bytes:
+    return v.encode() if isinstance(v, str) else bytes(v)
+
+
+def convert_to_string(v) -> bytes:
+    """utils.ConvertToString (utils/convert.go:255-278) of the values a group's keys take: strings and small integers."""
+    return b"%d" % v if isinstance(v, int) else bytes(v)
+
+
+def _field_present(info: dict, f: int) -> bool:
+    """nfagg_k8s_render's presence of K8S_FIELDS[f] (enrich.go:51-87)."""
+    name = K8S_FIELDS[f]
+    if name in ("namespace", "host_ip"):
+        return len(_b(info.get(name) or b"")) != 0
+    if name == "host_name":
+        return len(_b(info.get("host_ip") or b"")) != 0 and len(_b(info.get("host_name") or b"")) != 0
+    if name == "zone":
+        return info.get("zone") is not None
+    return True
+
+
+def group_keys(dims: int, group, entries, labels, class_row, g: int) -> dict:
+    """The grouping's keys of one group as the enriched map holds them: {key: bytes or int}, an absent key left out. entries:
+    the Kubernetes table's [(ip, info)]; labels: the net table's label texts; class_row(g, side, cls) -> entry index."""
+    m = {}
+    for side, prefix, cls in ((0, "SrcK8S_", int(group["src_class"])), (1, "DstK8S_", int(group["dst_class"]))):
+        sel = (dims >> (9 * side)) & 0x1FF
+        if not sel or not cls:
+            continue
+        info = entries[class_row(g, side, cls)][1]
+        for f in range(9):
+            if sel >> f & 1 and _field_present(info, f):
+                m[prefix + K8S_SUFFIXES[f]] = _b(info.get(K8S_FIELDS[f]) or b"")
+    for key, field, dim in (("SrcSubnetLabel", "src_label", L.DIM_SRC_SUBNET_LABEL), ("DstSubnetLabel", "dst_label", L.DIM_DST_SUBNET_LABEL)):
+        k = int(group[field]) if dims & dim else L.NET_NO_LABEL
+        if k != L.NET_NO_LABEL and labels[k]:                            # an empty name ends the search and writes no key
+            m[key] = _b(labels[k])
+    if dims & L.DIM_FLOW_DIRECTION and int(group["direction"]) != L.NET_NO_DIRECTION:
+        m["FlowDirection"] = int(group["direction"])
+    if dims & L.DIM_FLOW_LAYER and int(group["layer"]):
+        m["K8S_FlowLayer"] = b"app" if int(group["layer"]) == 2 else b"infra"
+    if dims & L.DIM_PROTO and int(group["is_ip"]):
+        m["Proto"] = int(group["proto"])
+    return m
+
+
+class _Filter:
+    """One MetricsFilter as filterToPredicate builds it (encode/metrics/preprocess.go:39-58)."""
+
+    def __init__(self, f: dict):
+        self.key, self.type = f["key"], f.get("type") or "equal"
+        self.value = _b(f.get("value", ""))
+        if self.type not in FILTER_TYPES:
+            self.type = "equal"                                          # "Default = Exact"
+        self.vars = [(m.group(0), m.group(1).decode()) for m in VARIABLE.finditer(self.value)] if self.type in ("equal", "not_equal") else []
+        self.regex = re.compile(self.value) if self.type in ("match_regex", "not_match_regex") else None
+
+    def keys(self):
+        return [self.key] + [name for _, name in self.vars]
+
+    def __call__(self, m: dict) -> bool:
+        found = self.key in m
+        if self.type == "presence":
+            return found
+        if self.type == "absence":
+            return not found
+        if self.type in ("equal", "not_equal"):
+            want = self.value
+            for text, name in self.vars:                                 # injectVars: a missing key injects ""
+                want = want.replace(text, convert_to_string(m[name]) if name in m else b"")
+            hit = found and convert_to_string(m[self.key]) == want
+            return hit if self.type == "equal" else not hit
+        hit = found and self.regex.search(convert_to_string(m[self.key])) is not None
+        return hit if self.type == "match_regex" else not hit
+
+
+class PromCounters:
+    """`encode prom` counters fed by the GPU fold. items: FLP MetricsItem dicts (api/encode_prom.go:49-60: name, type, filters,
+    valueKey, labels, remap, flatten, valueScale). Each item's grouping is the set of keys its labels and filters (and the
+    $(Key) variables of its equal filters) name; equal groupings are shared. ValueError for an item this path cannot serve: a
+    type other than counter, `flatten`, a value key other than "" / Bytes / Packets, a label or filter key outside the
+    dimension list, more than L.MET_MAX_GROUPINGS distinct groupings.
+
+    values: {(prefix + name, ((target, value bytes), ...) in the item's label order): float}, what CounterVec.With(labels).Add
+    has summed. Regular expressions run on Python's `re`, which stands in for Go's RE2 (see the module's docstring)."""
+
+    def __init__(self, items, prefix: str = ""):
+        self.prefix, self.items, self.values = prefix, [], {}
+        self.groupings = []
+        for it in items:
+            name = it.get("name", "")
+            if it.get("type") != "counter":
+                raise ValueError("metric %r: type %r is not counter" % (name, it.get("type")))
+            if it.get("flatten"):
+                raise ValueError("metric %r: flatten stays on the host path" % name)
+            value_key = it.get("valueKey") or ""
+            if value_key not in VALUE_FIELDS:
+                raise ValueError("metric %r: value key %r is none of '', Bytes, Packets" % (name, value_key))
+            remap = it.get("remap") or {}
+            labels = [(l, remap.get(l) or l) for l in it.get("labels") or []]             # Preprocess: Remap[l] != "" renames
+            filters = {}
+            for f in it.get("filters") or []:
+                filters.setdefault(f["key"], []).append(_Filter(f))
+            dims = 0
+            for key in [l for l, _ in labels] + [k for fs in filters.values() for f in fs for k in f.keys()]:
+                if key not in KEY_DIMS:
+                    raise ValueError("metric %r: key %r is outside the dimension list" % (name, key))
+                dims |= KEY_DIMS[key]
+            if dims not in self.groupings:
+                self.groupings.append(dims)
+            self.items.append(dict(name=prefix + name, grouping=self.groupings.index(dims), labels=labels, filters=filters, value_key=value_key,
+                                   scale=float(it.get("valueScale") or 0)))
+        if len(self.groupings) > L.MET_MAX_GROUPINGS:
+            raise ValueError("%d distinct groupings, more than %d" % (len(self.groupings), L.MET_MAX_GROUPINGS))
+        self.caps = [4096] * len(self.groupings)
+        self._met = None
+
+    def add_groups(self, groups, entries, labels, class_row) -> None:
+        """prepareMetric + ProcessCounter per group: groups[g] is grouping g's METRIC_GROUP array. Two groups can land in one
+        series (their keys differ, their label texts do not: a missing key and an empty value both print ""), so a series'
+        integer sums are added up first and each series gets one Add of float(sum) / valueScale per call."""
+        totals = {}
+        for g, dims in enumerate(self.groupings):
+            mine = [(k, it) for k, it in enumerate(self.items) if it["grouping"] == g]
+            for group in groups[g]:
+                m = group_keys(dims, group, entries, labels, class_row, g)
+                for k, it in mine:
+                    # ApplyFilters: the filters of one key are ORed, the keys ANDed
+                    if not all(any(f(m) for f in fs) for fs in it["filters"].values()):
+                        continue
+                    total, series = VALUE_FIELDS[it["value_key"]]
+                    if int(group[series]) == 0:                          # extractGenericValue: no flow of the group carries the key
+                        continue
+                    key = (k, tuple((target, convert_to_string(m[src]) if src in m else b"") for src, target in it["labels"]))
+                    totals[key] = totals.get(key, 0) + int(group[total])
+        for (k, series_labels), total in totals.items():
+            it = self.items[k]
+            value = float(total)
+            if it["scale"] != 0:
+                value /= it["scale"]
+            key = (it["name"], series_labels)
+            self.values[key] = self.values.get(key, 0.0) + value
+
+    def observe(self, table, records, k8s, net=None, agent_ip=None) -> None:
+        """The two resolves and the fold for these records on `table`'s device, then add_groups. k8s: the K8sTable (of `table`),
+        net: the NetTable, required when a grouping selects a label or the direction. A cap that proves too small is grown and
+        the fold repeated once."""
+        if not self.items:
+            return
+        if net is None and any(d & NET_DIMS for d in self.groupings):
+            raise ValueError("a grouping selects a subnet label or the direction: observe needs the net table")
+        if self._met is None or self._met.k8s is not k8s or self._met._t is None:
+            self._met = table.metrics_table(k8s, self.groupings)
+        met = self._met
+        k8s_rows = table.k8s_resolve(k8s, records)
+        net_rows = table.net_resolve(net, records, k8s, k8s_rows, agent_ip) if net is not None else None
+        rc, groups, counts = table.metrics_fold(met, records, k8s_rows, net_rows, self.caps)
+        if rc == L.TRUNCATED:
+            # a grouping that did not fit reports a lower bound only: the one retry takes the largest cap, and the next call a
+            # cap sized by what the retry found
+            over = [c > cap for c, cap in zip(counts, self.caps)]
+            rc, groups, counts = table.metrics_fold(met, records, k8s_rows, net_rows, [L.MET_MAX_GROUPS if o else cap for o, cap in zip(over, self.caps)])
+            if rc != L.OK:
+                raise RuntimeError("more than %d groups in one grouping: %r" % (L.MET_MAX_GROUPS, counts))
+            self.caps = [min(L.MET_MAX_GROUPS, max(cap, 1 << (2 * c).bit_length())) if o else cap for o, c, cap in zip(over, counts, self.caps)]
+        self.add_groups(groups, k8s.entries, net.labels if net is not None else [], met.class_row)

@@ -219,24 +219,30 @@ class MapTracer:
             self._netevTable.close()
             self._netevTable = None
 
-    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None, k8s=None, net=None):
+    def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None, k8s=None, net=None,
+                       metrics=None):
         """evictFlows for a direct-FLP `write: stdout, format: json` stage, without a Record per flow: the drained maps are merged,
         decorated with the sample decoder's network events and encoded on the GPU. Returns (buf, line_offsets, deferred) as
         FlowTable.encode_flp_json_content does; with tls_names (a TlsNames of the fetcher's table) the TLS keys are written too,
         nothing is deferred and the result is (buf, line_offsets) as FlowTable.encode_flp_json_tls gives it. With k8s (a K8sTable of the
         fetcher's table; needs tls_names) the lines carry what the `transform network` stage's Kubernetes rules add as well
         (FlowTable.encode_flp_json_k8s). With net (a NetTable; needs k8s) also what its reinterpret_direction, add_subnet_label and
-        decode_tcp_flags rules add (FlowTable.encode_flp_json_net)."""
+        decode_tcp_flags rules add (FlowTable.encode_flp_json_net). With metrics (a PromCounters; needs k8s) the `encode prom` counters
+        observe the same flows (PromCounters.observe)."""
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         if net is not None and k8s is None:
             raise ValueError("net needs k8s: reinterpret_direction reads the Kubernetes keys")
+        if metrics is not None and k8s is None:
+            raise ValueError("metrics needs k8s: the counters group by the Kubernetes keys")
         monotonic_now, current = self.monoClock(), self.clock()
         table = self.mapFetcher.table
         main_ids, main_vals, feats, n_cpu = self.mapFetcher.drain()
         recs, present, parts, _dups = table.map_merge(main_ids, main_vals, feats, n_cpu)
         names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         mono = monotonic_now & ((1 << 64) - 1)
+        if metrics is not None:
+            metrics.observe(table, recs, k8s, net, agent_ip)
         if self.sampleDecoder is None:                                  # s == nil: no events, no injected drops (record.go:126)
             if net is not None:
                 return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, present, parts)
@@ -368,17 +374,20 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
     `tls_names`) the lines are those of the pipeline NetObserv ships, with the Kubernetes rules of its `transform network` stage in
     front of the writer (FlowTable.encode_flp_json_k8s). With `net` on top (a NetTable of `table`; needs `k8s`) the stage's
     reinterpret_direction, add_subnet_label and decode_tcp_flags rules are applied too (FlowTable.encode_flp_json_net), and no host pass
-    over the lines is left.
+    over the lines is left. With `metrics` (a PromCounters; needs `k8s`) the `encode prom` counters observe every eviction too
+    (PromCounters.observe): the pipeline's other output, from the same records.
 
     One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
 
     def __init__(self, table, stream, names=None, agent_ip=None, unknown: bytes = b"unknown", time_received: Callable[[], int] = None,
-                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None):
+                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None, metrics=None):
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         if net is not None and k8s is None:
             raise ValueError("net needs k8s: reinterpret_direction reads the Kubernetes keys")
-        self.table, self.stream = table, stream
+        if metrics is not None and k8s is None:
+            raise ValueError("metrics needs k8s: the counters group by the Kubernetes keys")
+        self.table, self.stream, self.metrics = table, stream, metrics
         self.names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         self.agent_ip, self.unknown = agent_ip, unknown
         self.time_received = time_received or (lambda: int(time.time()))   # time.Now().Unix()
@@ -394,6 +403,8 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         n = len(raw)
         if n == 0:
             return 0
+        if self.metrics is not None:
+            self.metrics.observe(self.table, raw, self.k8s, self.net, self.agent_ip)
         if self.tls_names is not None:
             if self.net is not None:
                 buf, off = self.table.encode_flp_json_net(raw, self.tls_names, self.k8s, self.net, now_ns, mono_ns & ((1 << 64) - 1), self.names,

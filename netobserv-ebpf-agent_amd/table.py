@@ -719,6 +719,42 @@ class FlowTable:
                                      d_out, out_cap, d_line_offsets, 0, (d_present, d_parts) if d_present else None, d_rows, netev_table,
                                      tls_names, k8s, net)[:2]
 
+    # -- flow metrics (nfagg_metrics_*): the GROUP BY under the `encode prom` counters
+    def metrics_table(self, k8s: "K8sTable", groupings) -> "MetricsTable":
+        """A metrics table on this handle's device; groupings: the dimension masks (L.DIM_*), at most L.MET_MAX_GROUPINGS."""
+        return MetricsTable(k8s, groupings, self)
+
+    def metrics_fold(self, met: "MetricsTable", records: np.ndarray, k8s_rows: np.ndarray, net_rows: np.ndarray = None, caps=4096):
+        """nfagg_metrics_fold: k8s_rows / net_rows are what k8s_resolve / net_resolve returned for these records (net_rows may be
+        None when no grouping selects a label or the direction). caps: one cap, or one per grouping. Returns (rc, groups,
+        n_groups): groups[g] is a METRIC_GROUP array in unspecified order; with rc == L.TRUNCATED every groups[g] is empty and
+        n_groups[g] is exact for the groupings that fit and a lower bound above the cap for the others."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        G = len(met.groupings)
+        caps = [int(caps)] * G if np.isscalar(caps) else [int(c) for c in caps]
+        kr = np.ascontiguousarray(k8s_rows, dtype=np.uint32)
+        nr = np.ascontiguousarray(net_rows, dtype=NET_ROW) if net_rows is not None else None
+        outs = [np.zeros(min(c, L.MET_MAX_GROUPS), dtype=METRIC_GROUP) for c in caps]
+        ptrs = (C.c_void_p * G)(*[o.ctypes.data if o.size else None for o in outs])
+        cap_a, n_a = (C.c_uint32 * G)(*caps), (C.c_uint32 * G)()
+        rc = L.lib.nfagg_metrics_fold(self._h, met._t, r.ctypes.data_as(C.c_void_p) if n else None, n, kr.ctypes.data_as(C.c_void_p) if n else None,
+                                      nr.ctypes.data_as(C.c_void_p) if nr is not None and n else None, cap_a, ptrs, n_a)
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        counts = [int(x) for x in n_a]
+        return rc, [o[:c if rc == L.OK else 0] for o, c in zip(outs, counts)], counts
+
+    def metrics_fold_device(self, met: "MetricsTable", d_records: int, n: int, d_k8s_rows: int, d_net_rows: int, caps, d_outs):
+        """Device-resident variant (raw device pointers; d_net_rows = 0: none; d_outs[g]: room for caps[g] groups of 64 bytes,
+        16-byte aligned). Returns (rc, n_groups)."""
+        G = len(met.groupings)
+        ptrs = (C.c_void_p * G)(*[p or None for p in d_outs])
+        cap_a, n_a = (C.c_uint32 * G)(*[int(c) for c in caps]), (C.c_uint32 * G)()
+        rc = L.lib.nfagg_metrics_fold_device(self._h, met._t, C.c_void_p(d_records or None), n, C.c_void_p(d_k8s_rows or None),
+                                             C.c_void_p(d_net_rows or None), cap_a, ptrs, n_a)
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, [int(x) for x in n_a]
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -1179,6 +1215,7 @@ class K8sTable:
             raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
         self._owner = table                       # the handle must outlive the table
         self.n, self.has_layer = len(made), layer is not None
+        self.entries = entries                    # row r is entries[r]: PromCounters turns a class back into texts
 
     def __len__(self):
         return self.n
@@ -1257,6 +1294,7 @@ class NetTable:
             raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
         self._owner = table                       # the handle must outlive the table
         self.flags, self.n_cidrs, self.n_labels = flags, rules.n_cidrs, rules.n_labels
+        self.labels = list(keep[2])               # label k's text, as nfagg_net_row's indexes name it
 
     def close(self):
         if getattr(self, "_t", None):
@@ -1286,6 +1324,61 @@ def net_render(net: "NetTable", side: int, label: int) -> bytes:
     if rc != L.OK:
         raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
     return buf[:n.value].tobytes()
+
+
+METRIC_GROUP = np.dtype([("src_class", "<u4"), ("dst_class", "<u4"), ("src_label", "<u2"), ("dst_label", "<u2"), ("direction", "u1"), ("layer", "u1"),
+                         ("proto", "u1"), ("is_ip", "u1"), ("flows", "<u8"), ("bytes", "<u8"), ("packets", "<u8"), ("flows_with_bytes", "<u8"),
+                         ("flows_with_packets", "<u8"), ("pad_", "<u8")])                                           # nfagg_metric_group
+assert METRIC_GROUP.itemsize == 64
+
+
+class MetricsTable:
+    """The groupings of the `encode prom` counters over a Kubernetes table (nfagg_metrics_table_create). groupings: up to
+    L.MET_MAX_GROUPINGS masks of L.DIM_SRC_K8S(f) / L.DIM_DST_K8S(f) (f: index into K8S_FIELDS), L.DIM_SRC_SUBNET_LABEL,
+    L.DIM_DST_SUBNET_LABEL, L.DIM_FLOW_DIRECTION, L.DIM_FLOW_LAYER, L.DIM_PROTO. Every row of `k8s` gets a class per grouping
+    and side: the dense id, from 1, of the tuple of its selected fields; class_row turns a class back into a row of the
+    caller's entries. With a FlowTable (the one `k8s` lives on) the table serves metrics_fold; with table=None (and a host-only
+    `k8s`) it is built and checked on the host alone. Rebuild it when the Kubernetes table is rebuilt."""
+
+    def __init__(self, k8s: "K8sTable", groupings, table: "FlowTable" = None):
+        self.groupings = [int(g) for g in groupings]
+        arr = (C.c_uint32 * max(len(self.groupings), 1))(*[g & 0xFFFFFFFF for g in self.groupings])
+        self._t = C.c_void_p()
+        h = table._h if table is not None else None
+        rc = L.lib.nfagg_metrics_table_create(h, k8s._t, arr, len(self.groupings), C.byref(self._t))
+        if rc != L.OK:
+            self._t = None
+            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
+        self._owner, self.k8s = table, k8s        # the handle and the Kubernetes table must outlive this one
+
+    def n_classes(self, g: int, side: int) -> int:
+        return L.lib.nfagg_metrics_n_classes(self._t, g, side)
+
+    def class_row(self, g: int, side: int, cls: int) -> int:
+        """The first entry index of class `cls` (L.K8S_NO_ROW for class 0)."""
+        row = C.c_uint32(0)
+        rc = L.lib.nfagg_metrics_class_row(self._t, g, side, cls, C.byref(row))
+        if rc != L.OK:
+            raise NfaggError(rc, (L.lib.nfagg_last_error(self._owner._h if self._owner is not None else None) or b"").decode())
+        return row.value
+
+    def close(self):
+        if getattr(self, "_t", None):
+            if self._owner is None or self._owner._h:
+                L.lib.nfagg_metrics_table_destroy(self._t)
+            self._t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def ip_hash(ip16: bytes, seed_index: int) -> int:

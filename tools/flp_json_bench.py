@@ -27,7 +27,13 @@ too. Kernel-level device time: run the same leg under rocprofv3 --kernel-trace -
 --net (with --k8s): the transform network leg on top, on the same records and the same Kubernetes table in the same run:
 nfagg_encode_flp_json_net_device with reinterpret_direction, add_subnet_label and decode_tcp_flags on and 48 CIDRs in seven categories
 (46 narrow ones no address need match, then 0.0.0.0/0 and ::/0, so that every address walks the whole list). The join alone
-(nfagg_net_resolve_device) is timed too; --k8s-trace covers the k_net_* kernels."""
+(nfagg_net_resolve_device) is timed too; --k8s-trace covers the k_net_* kernels.
+
+--metrics (with --k8s --net): the flow metrics leg on top, on the same records, rows and net rows in the same run:
+nfagg_metrics_fold_device with two groupings, the namespace pair + layer + both subnet labels, and owner / type / namespace of both sides
++ direction. Reported: the median wall time of a whole call (the memset of the tables, fold, count, scan, emit, the read-back), the
+group counts, the bytes a flow's lane reads by this tool's own count, and that read rate as a fraction of a read-stream rate measured in
+the same run (a sum over 1 GiB). --k8s-trace covers the k_metrics_* kernels and the memset's fill kernel."""
 import io
 import os
 import queue
@@ -52,6 +58,7 @@ CONTENT = "--content" in sys.argv[1:]
 TLS = "--tls" in sys.argv[1:]
 K8S = "--k8s" in sys.argv[1:]
 NET = "--net" in sys.argv[1:]
+METRICS = "--metrics" in sys.argv[1:]
 NET_CATEGORIES = [("cat-%d" % c, ["172.%d.%d.0/24" % (16 + c, k) for k in range(8)] + ["2001:db8:%x::/48" % (16 * c + k) for k in range(1)]) for c in range(5)] + \
                  [("pods", ["100.64.0.0/10"]), ("everything", ["0.0.0.0/0", "::/0"])]
 K8S_ROWS = 100_000
@@ -124,19 +131,60 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|k_net_|scan", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|fillBuffer|scan", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
             grid = int(row.get("Grid_Size_X") or row.get("Grid_Size") or 0)
-            spans.setdefault((short, grid), []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+            spans.setdefault((short, grid), []).append((int(row["Start_Timestamp"]), (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3))
     print("device time per launch from the kernel trace, median over the launches of one size, us:")
-    for (short, grid), v in sorted(spans.items(), key=lambda kv: (kv[0][1] > 4_000_000, kv[0][0], kv[0][1])):
+    for (short, grid), tv in sorted(spans.items(), key=lambda kv: (kv[0][1] > 4_000_000, kv[0][0], kv[0][1])):
+        v = [us for _, us in tv]
         print(f"  {short:48s} grid {grid:9d}: {float(np.median(v)):9.1f}  min {min(v):9.1f}  max {max(v):9.1f}  ({len(v)} launches)")
+    # the metrics fold's grid is capped, so both sizes of the leg launch the same one: its launches in start order, the smaller size first
+    for (short, grid), tv in sorted(spans.items()):
+        if short.startswith("k_metrics_fold"):
+            print(f"  {short} grid {grid}, launches in start order: " + " ".join("%.1f" % us for _, us in sorted(tv)))
 
 
 if "--k8s-trace" in sys.argv[1:]:
     k8s_trace(sys.argv[sys.argv.index("--k8s-trace") + 1])
     sys.exit(0)
+
+
+def read_stream_rate():
+    """Bytes per second of a plain read of 1 GiB (four times the Infinity Cache), the yardstick of the metrics leg."""
+    x = torch.zeros(1 << 27, dtype=torch.int64, device="cuda")
+    _, dt = timed(lambda: x.sum())
+    return x.numel() * 8 / dt
+
+
+def metrics_leg(tab, k8s, d_ev, m, d_rows, d_net):
+    L = nf._lib
+    ns = L.DIM_SRC_K8S(0) | L.DIM_DST_K8S(0) | L.DIM_FLOW_LAYER | L.DIM_SRC_SUBNET_LABEL | L.DIM_DST_SUBNET_LABEL
+    workload = 0
+    for f in (3, 2, 0):                                               # owner name, type, namespace
+        workload |= L.DIM_SRC_K8S(f) | L.DIM_DST_K8S(f)
+    workload |= L.DIM_FLOW_DIRECTION
+    caps = [1 << 16, 1 << 16]
+    with tab.metrics_table(k8s, [ns, workload]) as met:
+        while True:
+            d_groups = [torch.empty(c * 64, dtype=torch.uint8, device="cuda") for c in caps]
+            fold = lambda: tab.metrics_fold_device(met, d_ev.data_ptr(), m, d_rows.data_ptr(), d_net.data_ptr(), caps, [g.data_ptr() for g in d_groups])  # noqa: E731
+            rc, counts = fold()
+            if rc == nf.OK:
+                break
+            caps = [min(4 * c, L.MET_MAX_GROUPS) for c in caps]
+        (rc, counts), dt = timed(fold)
+        assert rc == nf.OK
+        groups = [g[: c * 64].cpu().numpy().view(nf.METRIC_GROUP) for g, c in zip(d_groups, counts)]
+        assert all(int(g["flows"].sum()) == m for g in groups)
+    # a lane reads three 16-byte units of its record (protocol; bytes; packets and ethertype), its 8 bytes of Kubernetes rows, its 8
+    # bytes of net row, two class words per grouping, and the two rows' flag words because a grouping selects the layer
+    per_flow = 48 + 8 + 8 + 2 * 8 + 8
+    rate = read_stream_rate()
+    print(f"  metrics  {m} flows -> {counts[0]} + {counts[1]} groups (caps {caps[0]}, {caps[1]}) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s; "
+          f"{per_flow} B read per flow = {per_flow * m / dt / 1e9:.1f} GB/s per call, {per_flow * m / dt / rate:.3f} of the read-stream rate "
+          f"measured here ({rate / 1e9:.0f} GB/s over 1 GiB)")
 
 
 def per_byte(what, m, dt, wrote):
@@ -218,6 +266,8 @@ for flows in ((10_000_000,) if CONTENT or TLS else (1_000_000, 10_000_000)):
                               f"{int((got['src_label'] != nf._lib.NET_NO_LABEL).sum() + (got['dst_label'] != nf._lib.NET_NO_LABEL).sum())} of {2 * m} endpoints labelled, "
                               f"{int((got['direction'] != nf._lib.NET_NO_DIRECTION).sum())} of {m} flows with a direction; the join alone: {dt_net * 1e3:.3f} ms per call")
                         del d_out
+                        if METRICS:
+                            metrics_leg(tab, k8s, d_ev, m, d_rows, d_net)
                     del d_net
             del d_ev, d_off, d_rows
             continue
