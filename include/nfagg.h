@@ -1404,6 +1404,13 @@ uint64_t nfagg_key_hash(const nfagg_flow_id* id);
 /* The 64-bit hash of a 16-byte IP with the given seed index (0..3): 0..2 as used
  * by the sketches, 3 by the Kubernetes table. */
 uint64_t nfagg_ip_hash(const uint8_t ip[16], uint32_t seed_index);
+/* The 64-bit hash that places a group of grouping index `grouping` (0..NFAGG_MET_MAX_GROUPINGS - 1) in the tables of
+ * nfagg_metrics_fold; only the eight key fields of *key are read. Pure CPU. The key is packed into two 64-bit halves
+ *   A = 1<<63 | grouping<<58 | dst_class<<29 | src_class
+ *   B = 1<<63 | grouping<<56 | is_ip<<50 | proto<<42 | layer<<40 | direction<<32 | dst_label<<16 | src_label
+ * and the hash is fmix64((rotl64(A * K, 27) ^ B) * K) with K = 0x9E3779B97F4A7C15 and MurmurHash3's 64-bit finalizer
+ * fmix64. A table of 2^k slots is probed linearly from the hash's low k bits. key == NULL or a grouping out of range: 0. */
+uint64_t nfagg_metrics_group_hash(uint32_t grouping, const nfagg_metric_group* key);
 
 int nfagg_stats_get(nfagg_handle* h, nfagg_stats* out);
 int nfagg_stats_reset_profile(nfagg_handle* h);

@@ -275,6 +275,7 @@ SIGNATURES = {
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),
     "nfagg_ip_hash": (C.c_uint64, [_vp, C.c_uint32]),
+    "nfagg_metrics_group_hash": (C.c_uint64, [C.c_uint32, _vp]),
     "nfagg_stats_get": (C.c_int, [_vp, C.POINTER(Stats)]),
     "nfagg_stats_reset_profile": (C.c_int, [_vp]),
     "nfagg_sync": (C.c_int, [_vp]),

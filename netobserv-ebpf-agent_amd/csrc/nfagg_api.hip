@@ -2025,13 +2025,18 @@ int nfagg_sketch_reset(nfagg_handle* h) {
 }
 
 // HyperLogLog estimate (Flajolet et al. 2007, 64-bit hash so no large-range
-// correction) from the histogram of register values: sum_k hist[k] * 2^-k in
-// ascending k. Our own spec; the scalar oracle loops over the registers instead.
+// correction) from the histogram of register values: sum_k hist[k] * 2^-k. The sum is accumulated exactly, as the
+// integer sum_k hist[k] << (64 - k) (below 2^103 for any 65 uint32 counts: it fits 128 bits), converted to double once and
+// scaled by 2^-64: one rounding whatever the registers hold. (A sum of doubles term by term rounds at every term whose
+// exponent lies 53 bits below the running sum's: half of the registers at 1 and half at 47 with p = 18 already does it.)
+// alpha * m * m is exact (m is a power of two), the division rounds once. Our own spec; the scalar oracle loops over
+// the registers instead and does the same arithmetic.
 double nfagg_hll_estimate_from_histogram(const uint32_t* hist, uint32_t p) {
     const double m = (double)(1ull << p);
     const double alpha = (p == 4) ? 0.673 : (p == 5) ? 0.697 : (p == 6) ? 0.709 : 0.7213 / (1.0 + 1.079 / m);
-    double sum = 0.0;
-    for (int k = 0; k <= 64; k++) sum += (double)hist[k] * __builtin_ldexp(1.0, -k);
+    unsigned __int128 acc = 0;
+    for (int k = 0; k <= 64; k++) acc += (unsigned __int128)hist[k] << (64 - k);
+    const double sum = __builtin_ldexp((double)acc, -64);
     double e = alpha * m * m / sum;
     if (e <= 2.5 * m && hist[0] != 0) e = m * __builtin_log(m / (double)hist[0]);
     return e;
@@ -2168,6 +2173,12 @@ uint64_t nfagg_ip_hash(const uint8_t ip[16], uint32_t seed_index) {
     uint64_t lo, hi;
     memcpy(&lo, ip, 8); memcpy(&hi, ip + 8, 8);
     return ip_hash(lo, hi, seed_index);
+}
+
+uint64_t nfagg_metrics_group_hash(uint32_t grouping, const nfagg_metric_group* key) {
+    if (!key || grouping >= kMetMaxGroupings) return 0;
+    return met_hash(met_key_a(grouping, key->src_class, key->dst_class),
+                    met_key_b(grouping, key->src_label, key->dst_label, key->direction, key->layer, key->proto, key->is_ip));
 }
 
 int nfagg_sync(nfagg_handle* h) {

@@ -1386,6 +1386,14 @@ def ip_hash(ip16: bytes, seed_index: int) -> int:
     return L.lib.nfagg_ip_hash(buf, seed_index)
 
 
+def metrics_group_hash(grouping: int, groups) -> np.ndarray:
+    """nfagg_metrics_group_hash of every METRIC_GROUP in `groups` (only the key fields are read) for grouping index `grouping`:
+    the hash whose low bits are the group's home slot in the fold's tables. Pure CPU."""
+    g = np.ascontiguousarray(np.atleast_1d(groups), dtype=METRIC_GROUP)
+    base = g.ctypes.data
+    return np.fromiter((L.lib.nfagg_metrics_group_hash(grouping, base + METRIC_GROUP.itemsize * i) for i in range(len(g))), dtype=np.uint64, count=len(g))
+
+
 def hll_estimate_from_histogram(hist, p: int) -> float:
     h = np.ascontiguousarray(hist, dtype=np.uint32)
     assert h.size == 65

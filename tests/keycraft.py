@@ -79,6 +79,38 @@ def craft(targets, rng, fixed=None):
     return keys
 
 
+# ---------------------------------------------------------------- addresses with chosen ip_hash values
+IP_SEEDS = (0x243F6A8885A308D3, 0x13198A2E03707344, 0xA4093822299F31D0, 0x082EFA98EC4E6C89)
+
+
+def ip_hash(lo, hi, seed_index):
+    """csrc/nfagg_hash.h ip_hash restated, vectorised: lo / hi = the address's little-endian 64-bit words. Returns uint64."""
+    lo, hi = np.asarray(lo, dtype=np.uint64), np.asarray(hi, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        h = (_rot(_u(IP_SEEDS[seed_index & 3]), 27) ^ lo) * _u(K_MUL)
+        return _fmix((_rot(h, 27) ^ hi) * _u(K_MUL))
+
+
+def ip_words(addrs):
+    """(n, 16) uint8 addresses -> (lo, hi) little-endian uint64 words."""
+    w = np.ascontiguousarray(addrs, dtype=np.uint8).reshape(-1, 16).view("<u8")
+    return w[:, 0].copy(), w[:, 1].copy()
+
+
+def craft_ip(targets, seed_index, rng):
+    """One 16-byte address per 64-bit target: (n, 16) uint8 with ip_hash(address, seed_index) == target, all addresses distinct.
+    For any lower word the hash is a bijection of the upper word: the lower word is drawn from rng, the upper one solved (the
+    hash run forwards over the lower word, backwards from the target over fmix64 and the last multiplication). Equal targets get
+    different addresses, because their lower words differ."""
+    t = np.ascontiguousarray(np.asarray(targets, dtype=np.uint64).reshape(-1))
+    lo = _distinct(rng, len(t))
+    with np.errstate(over="ignore"):
+        h1 = (_rot(_u(IP_SEEDS[seed_index & 3]), 27) ^ lo) * _u(K_MUL)
+        hi = (_fmix_inv(t) * _u(K_MUL_INV)) ^ _rot(h1, 27)
+    assert np.array_equal(ip_hash(lo, hi, seed_index), t)
+    return np.ascontiguousarray(np.stack([lo, hi], axis=1).astype("<u8")).view(np.uint8).reshape(len(t), 16)
+
+
 def _key_column(recs):
     """The 40 key bytes of every record with byte 39 zeroed, as one opaque 40-byte column (sorts much faster than 39 columns)."""
     raw = np.ascontiguousarray(np.ascontiguousarray(recs).view(np.uint8).reshape(len(recs), 144)[:, :40])
@@ -136,6 +168,46 @@ def fold_constants():
         "kSpillParts": grab("nfagg_internal.h", r"^constexpr int kSpillParts = (\d+);"),
     }
     c["window"] = max(c["kProbe"], c["kCacheProbe"], c["kDedupProbe"])
+    return c
+
+
+# ---------------------------------------------------------------- the group hash of the metrics fold (csrc/nfagg_metrics.h)
+def metrics_group_hash(grouping, src_class, dst_class, src_label=0xFFFF, dst_label=0xFFFF, direction=0xFF, layer=0, proto=0, is_ip=0):
+    """met_hash(met_key_a, met_key_b) restated, vectorised over any of the key fields (the defaults are every dimension's "none").
+    A = 1<<63 | g<<58 | dst_class<<29 | src_class; B = 1<<63 | g<<56 | is_ip<<50 | proto<<42 | layer<<40 | direction<<32 |
+    dst_label<<16 | src_label; hash = fmix64((rotl(A * kMul, 27) ^ B) * kMul)."""
+    f = [np.asarray(x, dtype=np.uint64) for x in (src_class, dst_class, src_label, dst_label, direction, layer, proto, is_ip)]
+    g, mark = _u(grouping), _u(1 << 63)
+    a = mark | (g << _u(58)) | (f[1] << _u(29)) | f[0]
+    b = mark | (g << _u(56)) | (f[7] << _u(50)) | (f[6] << _u(42)) | (f[5] << _u(40)) | (f[4] << _u(32)) | (f[3] << _u(16)) | f[2]
+    with np.errstate(over="ignore"):
+        return _fmix((_rot(a * _u(K_MUL), 27) ^ b) * _u(K_MUL))
+
+
+def _grab(fname, pattern):
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "netobserv-ebpf-agent_amd", "csrc")
+    with open(os.path.join(csrc, fname)) as f:
+        m = re.search(pattern, f.read(), re.M)
+    assert m, (fname, pattern)
+    return int(m.group(1))
+
+
+def metrics_constants():
+    """The sizes the metrics fold's families are built around, parsed from csrc/ like fold_constants()."""
+    return {"kMetLdsSlots": _grab("nfagg_metrics.hip", r"\bkMetLdsSlots = (\d+)"), "kMetLdsProbe": _grab("nfagg_metrics.hip", r"\bkMetLdsProbe = (\d+)"),
+            "kMetFlowsPerBlock": _grab("nfagg_metrics.hip", r"^constexpr uint64_t kMetFlowsPerBlock = (\d+);"),
+            "kMetMinSlots": _grab("nfagg_metrics.h", r"\bkMetMinSlots = (\d+)")}
+
+
+def partition_constants():
+    """Tile size, the scan's chunk of tiles and the grid cap of the stable partition, parsed from csrc/nfagg_partition.hip."""
+    f = "nfagg_partition.hip"
+    c = {"kPartBlock": _grab(f, r"^constexpr int kPartBlock = (\d+);"), "kPartRounds": _grab(f, r"^constexpr int kPartRounds = (\d+);"),
+         "kMaxShards": _grab(f, r"^constexpr int kMaxShards = (\d+);"),
+         "scan_chunk": _grab(f, r"for \(uint32_t t0 = 0; t0 < n_tiles; t0 \+= (\d+)\)"), "grid_cap": _grab(f, r"const unsigned grid = n_tiles < (\d+)u")}
+    c["tile"] = c["kPartBlock"] * c["kPartRounds"]
     return c
 
 

@@ -70,13 +70,8 @@ def test_new_record_mirrors_reference(nf):
 
 def test_hll_estimator_from_histogram_within_1ulp_of_scalar(nf, O):
     """north_star: HLL estimate agrees with a scalar HLL on the same registers to ±1 ULP."""
-    rng = np.random.default_rng(11)
-    for p, n in ((14, 50), (14, 20000), (14, 400000), (10, 3000), (4, 3), (16, 5_000_000)):
-        regs = np.zeros(1 << p, dtype=np.uint8)
-        # geometric register values as a real HLL would produce for ~n items
-        idx = rng.integers(0, 1 << p, size=min(n, 2_000_000))
-        rho = np.minimum(rng.geometric(0.5, size=idx.size), 64 - p + 1).astype(np.uint8)
-        np.maximum.at(regs, idx, rho)
+    from sketchcraft import seeded_registers
+    for p, n, regs in seeded_registers():                   # geometric register values as a real HLL would produce for ~n items
         hist = np.bincount(regs, minlength=65).astype(np.uint32)
         got = nf.hll_estimate_from_histogram(hist, p)
         want = O.hll_estimate(regs, p)
