@@ -1,31 +1,25 @@
-// nfagg_api.hip — the C ABI of libnfagg (include/nfagg.h): handle, pinned
+// nfagg_api.hip — the flow table behind the C ABI of libnfagg (include/nfagg.h): handle, pinned
 // staging ring, batch control flow of Accounter.Account
 // (pkg/flow/account.go:58-100) around the kernels. No CPU fallback: without a
-// gfx950 device nfagg_create fails.
+// gfx950 device nfagg_create fails. The rest of the ABI's host side: nfagg_api_export.hip (the encoders),
+// nfagg_api_tables.hip (the caller tables), nfagg_api_aux.hip (rollups, map merge, sketches).
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <initializer_list>
-#include <map>
 #include <mutex>
 #include <new>
 #include <set>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/nfagg.h"
 #include "nfagg_internal.h"
+#include "nfagg_handle.h"
 #include "nfagg_hostpool.h"
-#include "nfagg_pb.h"
-#include "nfagg_ipfix.h"
-#include "nfagg_flp.h"
-#include "nfagg_netev.h"
-#include "nfagg_metrics.h"
 
 using namespace nfagg;
 
@@ -43,144 +37,10 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct EventPair { hipEvent_t a, b; int kind; };
-
 }  // namespace
 
-struct nfagg_handle {
-    nfagg_config cfg{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    uint64_t slots = 0;
-    TableView tv{};
-    SketchView sk{};
-    bool own_sketch[4] = {false, false, false, false};
-    DevCounters* h_ctr = nullptr;       // pinned mirror
-    // staging ring (host ingest path)
-    void* pinned[2] = {nullptr, nullptr};
-    void* d_stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_free[2] = {nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;   // H2D copies of the staging ring: chunk k+1 goes up while chunk k is folded on `stream`
-    hipEvent_t stage_up[2] = {nullptr, nullptr};
-    int stage_next = 0;
-    bool stage_acquired = false;
-    // careful-path scratch
-    uint64_t careful_chunk = 0;
-    uint32_t* d_slot_idx = nullptr;
-    uint8_t* d_flags = nullptr;
-    uint32_t* d_block_counts = nullptr;
-    std::vector<uint32_t> h_block_counts;
-    // eviction buffer (device)
-    void* d_evict = nullptr;
-    uint64_t d_evict_cap = 0;
-    // rollup scratch
-    void* d_roll[3] = {nullptr, nullptr, nullptr};
-    size_t d_roll_cap[3] = {0, 0, 0};
-    uint32_t* d_hist = nullptr;
-    // map merge scratch: [0] slots [1] slot_of [2] local_off [3] block_sum [4] block_base [5] dup counter,
-    // (host variant) [6..12] ids, [13..19] values, [20..27] outputs
-    void* d_mm[28] = {};
-    size_t d_mm_cap[28] = {};
-    void* d_hh[7] = {};            // heavy hitters: est, est sorted, idx, idx sorted, sort scratch, gathered rows, (host variant) records
-    size_t d_hh_cap[7] = {};
-    void* d_sort[2] = {};          // eviction: live list in slot order, radix-sort scratch
-    size_t d_sort_cap[2] = {};
-    int sort_bits = 0;
-    bool epoch_unclustered = false; // a batch of this epoch claimed slots in arrival order (single-pass / direct / dedup kernels)
-    // export encoders (protobuf, IPFIX, direct-FLP JSON): one scratch, they serialise on the stream and synchronise before returning
-    struct DevBuf { void* p = nullptr; size_t cap = 0; };
-    struct EncodeScratch {
-        DevBuf local_off, block_sum, block_base;     // the two scans: u32[n], u32[blocks], u64[blocks + 1] (the total last)
-        DevBuf names;                                // the namer table, stably sorted by if_index
-        DevBuf ipfix_name_rows;                      // size pass -> write pass: u32[n]
-        DevBuf flp_rows;                             // size pass -> write pass: 8 x u32 per record (seven rows, the line's length)
-        DevBuf flp_esc, flp_n_deferred;              // the escaped table; the deferred counter
-        DevBuf in_records, out, out_offsets;         // host-memory entry points: staged records, output bytes, offsets
-        DevBuf out_extra[2];                         //   protobuf: body lengths, kafka keys; FLP: deferred flags
-        DevBuf pb_feat[6];                           //   protobuf: present bits and the five feature parts
-        DevBuf ne_rows;                              //   *_netev: the flows' table rows
-        DevBuf ne_in[3], ne_out[3], ne_missing, ne_info;   // nfagg_netev_resolve: staged inputs and outputs, the missing set, its counters
-        DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record
-        DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record
-        DevBuf met_slots, met_out;                   // nfagg_metrics_fold: control words and the groupings' tables; the host entry point's groups
-        std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
-        std::vector<uint8_t> h_flp_esc;
-        template <typename F> void each(F f) {
-            for (DevBuf* b : {&local_off, &block_sum, &block_base, &names, &ipfix_name_rows, &flp_rows, &flp_esc, &flp_n_deferred,
-                              &in_records, &out, &out_offsets, &out_extra[0], &out_extra[1]}) f(*b);
-            for (DevBuf& b : pb_feat) f(b);
-            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows, &net_rows, &met_slots, &met_out}) f(*b);
-        }
-    } enc;
-    // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
-    void* d_opt[4] = {};
-    size_t d_opt_cap[4] = {};
-    uint64_t epoch_len_hint = 0;   // records the last epoch that ended on "full" took (0 = this stream has not stopped on full)
-    uint64_t last_epoch_flows = 0; // slots the last epoch had claimed when it ended (flows; sub-flows on a sub-flow table): what the next one is sized by
-    uint64_t abort_cap = 0;        // largest chunk worth trying after the kernels refused claims (0 = no limit known)
-    // spill queues of the two-pass ingest
-    void* d_spill = nullptr;
-    size_t d_spill_cap = 0;
-    // accounting
-    uint64_t epoch_seq = 0;         // sequence number of the next record, counted from the start of the epoch (64 bits: never runs out)
-    uint64_t seq_origin = 0;        // the device sees epoch_seq - seq_origin: a 32-bit window, moved by a rebase (nfagg_rebase.hip)
-    bool ext_sequenced = false;     // sequence numbers are handed in (nfagg_set_sequence, group local fold): other tables hold tags of the
-                                    // same numbering, so this handle must not move its window on its own
-    uint64_t live = 0;       // len(entries): exact after refresh_counters and on the paths that keep counters_exact
-    uint64_t live_ub = 0;    // upper bound on the device's n_live (the claimed slots); equal to it while counters_exact
-    // The host knows the device's n_live and len(entries) without asking (after an eviction; after a claim + flag chunk,
-    // whose counts it has just read): the next "might this batch fill the table" / eviction needs no round trip. Every
-    // asynchronous fold clears it. mirror_fresh: *h_ctr equals the device counters (what the optimistic fold's rollback restores).
-    bool counters_exact = false;
-    bool mirror_fresh = false;
-    uint8_t* h_careful = nullptr;   // pinned: block counts + flags of a claim + flag chunk of up to kCarefulMaxBatch records
-    bool must_evict = false; // a "full" split is pending (account.go:85-94)
-    uint64_t split_seq = 0;
-    // local fold across GPUs (nfagg_partials_*): the flows of other shards have been exported to their owners; nothing may be
-    // folded on top of them before the eviction (they would be exported twice)
-    bool exported = false;
-    void* d_exp = nullptr;          // 64 owner counts + 64 segment cursors + the owned-flows count
-    size_t d_exp_cap = 0;
-    unsigned long long* h_exp = nullptr;   // pinned mirror of the counts
-    // nfagg_account*: control block of the epoch kernel chain (device + pinned mirror), epoch ends, slot scratch
-    void* d_ep[3] = {};             // [0] control block, [1] epoch ends, [2] live-list scratch
-    size_t d_ep_cap[3] = {};
-    void* d_ep_out = nullptr;       // second device buffer for evictions (nfagg_account alternates with d_evict)
-    size_t d_ep_out_cap = 0;
-    void* h_ep = nullptr;           // pinned: control block, then the epoch ends
-    size_t h_ep_cap = 0;
-    // device -> pageable host memory through two pinned bounce buffers (d2h_copy): a plain hipMemcpy to pageable memory runs at
-    // ~13 GB/s here, this at the PCIe rate
-    void* h_bounce[2] = {nullptr, nullptr};
-    hipStream_t d2h_stream = nullptr;
-    hipStream_t d2h_small = nullptr;     // small / one-off downloads (d2h_copy): not the stream the pipelined page-locked downloads use
-    hipEvent_t bounce_ev[2] = {nullptr, nullptr};
-    hipGraphExec_t ep_graph[3] = {nullptr, nullptr, nullptr};   // kChainWindows[k] windows of the epoch kernel chain, captured once (their arguments never change)
-    bool ep_graph_off = false;           // the capture or the instantiation failed once: this handle launches its windows eagerly
-    void* ep_graph_key[3] = {};          // the buffers the captured launches point at: re-capture when one was re-allocated
-    // sub-flow table (kernel-dedup mode of a local-fold rank, nfagg_dedup.h): the flow-keyed table its epochs are joined into
-    // (nfagg_dedup_join.hip), allocated at the first eviction; scratch; the join that has been made and not yet evicted
-    TableView jv{};
-    DevCounters* h_jctr = nullptr;  // pinned mirror of jv.ctr
-    void* d_join = nullptr;         // slot_of[]: the J slot of every live sub-flow
-    size_t d_join_cap = 0;
-    struct { bool valid = false, dirty = false; uint32_t n_shards = 0, shard_id = 0; uint64_t flows = 0, claimed = 0; } join;   // dirty: J may hold claims
-    // the evict-on-full loop with its epochs found first (nfagg_account_par.inc): analysis arrays, pinned mirror, the stream the
-    // middle epochs are folded on while the table takes the first and the last
-    uint32_t* h_par = nullptr;      // pinned: control words, then the cuts
-    void* d_par[8] = {};            // sort keys, sorted keys, prev, pos, long segments, sort scratch, control + cuts, rank tile counts
-    size_t d_par_cap[8] = {};
-    hipStream_t par_stream = nullptr;
-    hipEvent_t par_done = nullptr;
-    hipEvent_t par_part[16] = {};   // one behind every part of the cut walk (kParWalkPartsMax)
-    nfagg_stats stats{};
-    std::vector<EventPair> ev_pending;
-    std::vector<EventPair> ev_free;
-    std::mutex err_mu;              // nfagg_account's helper threads report through fail() too
-    std::string err;
-};
-
-namespace {
+// Declared in nfagg_handle.h: the other host files of the ABI report errors and grow scratch through these.
+namespace nfagg {
 
 int fail(nfagg_handle* h, int code, const char* fmt, ...) {
     char buf[512];
@@ -192,24 +52,19 @@ int fail(nfagg_handle* h, int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(h, expr)                                                                      \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail((h), NFAGG_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
+int ensure_bytes(nfagg_handle* h, void** p, size_t* cap, size_t need) {
+    if (*cap >= need) return NFAGG_OK;
+    if (*p) { hipFree(*p); *p = nullptr; *cap = 0; }
+    size_t want = need + need / 4 + 4096;
+    hipError_t e = hipMalloc(p, want);
+    if (e != hipSuccess) return fail(h, NFAGG_ENOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    *cap = want;
+    return NFAGG_OK;
+}
 
-// ... with something to do before the error is reported (a second stream to join)
-#define HIP_TRY_DO(h, expr, cleanup)                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            cleanup;                                                                          \
-            return fail((h), NFAGG_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-        }                                                                                     \
-    } while (0)
+}  // namespace nfagg
 
-uint64_t next_pow2(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
+namespace {
 
 // --- profiling: HIP events on the handle's stream around the dominant kernels
 void prof_begin(nfagg_handle* h, EventPair& ep, int kind) {
@@ -235,8 +90,6 @@ void prof_resolve(nfagg_handle* h) {
     }
     h->ev_pending.clear();
 }
-
-int ensure_bytes(nfagg_handle* h, void** p, size_t* cap, size_t need);
 
 int launch_ingest_profiled(nfagg_handle* h, const void* d, uint64_t n, uint64_t seq_base) {
     EventPair ep{};
@@ -625,16 +478,6 @@ int ingest_device_core(nfagg_handle* h, const void* d_records, size_t n, size_t*
     }
     if (consumed_out) *consumed_out = consumed;
     return rc;
-}
-
-int ensure_bytes(nfagg_handle* h, void** p, size_t* cap, size_t need) {
-    if (*cap >= need) return NFAGG_OK;
-    if (*p) { hipFree(*p); *p = nullptr; *cap = 0; }
-    size_t want = need + need / 4 + 4096;
-    hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) return fail(h, NFAGG_ENOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-    *cap = want;
-    return NFAGG_OK;
 }
 
 // ---- sub-flow tables (kernel-dedup mode of a local-fold rank): the join that ends an epoch (nfagg_dedup_join.hip) ----------------
@@ -1828,331 +1671,6 @@ void nfagg_record_times(int64_t now_unix_ns, uint64_t mono_now_ns, const nfagg_f
     if (time_flow_end_unix_ns) *time_flow_end_unix_ns = (int64_t)((uint64_t)now_unix_ns - (uint64_t)end_delta);
 }
 
-// ---------------------------------------------------------------- rollups
-static int rollup_core(nfagg_handle* h, int kind, const void* partials, size_t n_flows, size_t n_cpu,
-                       nfagg_flow_metrics* base, void* folded) {
-    if (!h || !partials || !base || !folded) return fail(h, NFAGG_EINVAL, "null argument");
-    if (n_flows == 0) return NFAGG_OK;
-    if (n_cpu == 0) return fail(h, NFAGG_EINVAL, "n_cpu must be >= 1");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t ssz = rollup_struct_size(kind);
-    const size_t pb = n_flows * n_cpu * ssz, bb = n_flows * sizeof(nfagg_flow_metrics), fb = n_flows * ssz;
-    int rc;
-    if ((rc = ensure_bytes(h, &h->d_roll[0], &h->d_roll_cap[0], pb)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_roll[1], &h->d_roll_cap[1], bb)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_roll[2], &h->d_roll_cap[2], fb)) != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_roll[0], partials, pb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_roll[1], base, bb, hipMemcpyHostToDevice, h->stream));
-    hipError_t e = launch_rollup(kind, h->d_roll[0], n_flows, n_cpu, h->d_roll[1], h->d_roll[2], h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "rollup launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(base, h->d_roll[1], bb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(folded, h->d_roll[2], fb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-int nfagg_rollup_additional(nfagg_handle* h, const nfagg_additional_metrics* p, size_t nf, size_t nc,
-                            nfagg_flow_metrics* base, nfagg_additional_metrics* folded) { return rollup_core(h, 0, p, nf, nc, base, folded); }
-int nfagg_rollup_dns(nfagg_handle* h, const nfagg_dns_metrics* p, size_t nf, size_t nc,
-                     nfagg_flow_metrics* base, nfagg_dns_metrics* folded) { return rollup_core(h, 1, p, nf, nc, base, folded); }
-int nfagg_rollup_drops(nfagg_handle* h, const nfagg_pkt_drop_metrics* p, size_t nf, size_t nc,
-                       nfagg_flow_metrics* base, nfagg_pkt_drop_metrics* folded) { return rollup_core(h, 2, p, nf, nc, base, folded); }
-int nfagg_rollup_network_events(nfagg_handle* h, const nfagg_network_events_metrics* p, size_t nf, size_t nc,
-                                nfagg_flow_metrics* base, nfagg_network_events_metrics* folded) { return rollup_core(h, 3, p, nf, nc, base, folded); }
-int nfagg_rollup_xlat(nfagg_handle* h, const nfagg_xlat_metrics* p, size_t nf, size_t nc,
-                      nfagg_flow_metrics* base, nfagg_xlat_metrics* folded) { return rollup_core(h, 4, p, nf, nc, base, folded); }
-int nfagg_rollup_quic(nfagg_handle* h, const nfagg_quic_metrics* p, size_t nf, size_t nc,
-                      nfagg_flow_metrics* base, nfagg_quic_metrics* folded) { return rollup_core(h, 5, p, nf, nc, base, folded); }
-
-// ---------------------------------------------------------------- map merge (LookupAndDeleteMap's join)
-static const int kWalk[7] = {-1, NFAGG_ROLLUP_DNS, NFAGG_ROLLUP_DROPS, NFAGG_ROLLUP_NETWORK_EVENTS, NFAGG_ROLLUP_XLAT,
-                             NFAGG_ROLLUP_ADDITIONAL, NFAGG_ROLLUP_QUIC};   // tracer.go:1057-1110; position 0 = main map
-
-static int map_merge_device_core(nfagg_handle* h, const nfagg_map_view* mm, const nfagg_map_view fm[6], size_t n_cpu,
-                                 const nfagg_merged_flows* out, size_t cap, size_t* n_out, size_t* n_dup) {
-    if (!h || !mm || !fm || !out || !n_out) return fail(h, NFAGG_EINVAL, "null argument");
-    if (n_cpu == 0 || n_cpu > 0xFFFFu) return fail(h, NFAGG_EINVAL, "n_cpu must be in [1, 65535]");
-    MergeIn in{};
-    in.n_cpu = (uint32_t)n_cpu;
-    uint64_t total = 0;
-    uintptr_t align = 0;
-    for (int q = 0; q < 7; q++) {
-        const nfagg_map_view& v = q == 0 ? *mm : fm[kWalk[q]];
-        if (v.n && (!v.ids || !v.values)) return fail(h, NFAGG_EINVAL, "map %d: null ids/values", q);
-        in.ids[q] = (const uint8_t*)v.ids; in.vals[q] = (const uint8_t*)v.values;
-        in.off[q] = (uint32_t)total;
-        total += v.n;
-        if (v.n) align |= (uintptr_t)v.ids | (uintptr_t)v.values;
-    }
-    if (total > (1ull << 30)) return fail(h, NFAGG_ERANGE, "map merge: more than 2^30 rows");
-    in.off[7] = (uint32_t)total;
-    *n_out = 0;
-    if (n_dup) *n_dup = 0;
-    if (total == 0) return NFAGG_OK;
-    if (cap && (!out->records || !out->present)) return fail(h, NFAGG_EINVAL, "null records/present output");
-    align |= (uintptr_t)out->records | (uintptr_t)out->additional | (uintptr_t)out->dns | (uintptr_t)out->drops |
-             (uintptr_t)out->network_events | (uintptr_t)out->xlat | (uintptr_t)out->quic;
-    if (align & 7u) return fail(h, NFAGG_EINVAL, "map merge: device arrays must be 8-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    uint32_t n_slots = 1024;
-    while ((uint64_t)n_slots < 2 * total) n_slots <<= 1;
-    const size_t blocks = (total + 1023) / 1024;
-    int rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[0], &h->d_mm_cap[0], (size_t)n_slots * merge_slot_bytes())) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[1], &h->d_mm_cap[1], total * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[2], &h->d_mm_cap[2], total * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[3], &h->d_mm_cap[3], blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[4], &h->d_mm_cap[4], (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[5], &h->d_mm_cap[5], 16)) != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->d_mm[0], 0xFF, (size_t)n_slots * merge_slot_bytes(), h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_mm[5], 0, 16, h->stream));
-    hipError_t e = launch_merge_build(in, h->d_mm[0], n_slots, (uint32_t*)h->d_mm[1], (unsigned int*)h->d_mm[5],
-                                      (uint32_t*)h->d_mm[2], (uint32_t*)h->d_mm[3], h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "map merge build launch failed: %s", hipGetErrorString(e));
-    e = launch_scan_block_sums((const uint32_t*)h->d_mm[3], (uint32_t)blocks, (uint64_t*)h->d_mm[4], h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "map merge scan launch failed: %s", hipGetErrorString(e));
-    uint64_t flows = 0; unsigned int dups = 0;
-    HIP_TRY(h, hipMemcpyAsync(&flows, (uint64_t*)h->d_mm[4] + blocks, sizeof flows, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&dups, h->d_mm[5], sizeof dups, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *n_out = (size_t)flows;
-    if (n_dup) *n_dup = dups;
-    if (flows > cap) return NFAGG_TRUNCATED;
-    MergeOut o{out->records, out->present, out->additional, out->dns, out->drops, out->network_events, out->xlat, out->quic};
-    e = launch_merge_fold(in, o, h->d_mm[0], (const uint32_t*)h->d_mm[1], (const uint32_t*)h->d_mm[2], (const uint64_t*)h->d_mm[4], h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "map merge fold launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-int nfagg_map_merge_device(nfagg_handle* h, const nfagg_map_view* d_main_map, const nfagg_map_view d_feature_maps[6],
-                           size_t n_cpu, const nfagg_merged_flows* d_out, size_t cap, size_t* n_out, size_t* n_duplicate_keys) {
-    return map_merge_device_core(h, d_main_map, d_feature_maps, n_cpu, d_out, cap, n_out, n_duplicate_keys);
-}
-
-int nfagg_map_merge(nfagg_handle* h, const nfagg_map_view* main_map, const nfagg_map_view feature_maps[6],
-                    size_t n_cpu, const nfagg_merged_flows* out, size_t cap, size_t* n_out, size_t* n_duplicate_keys) {
-    if (!h || !main_map || !feature_maps || !out || !n_out) return fail(h, NFAGG_EINVAL, "null argument");
-    if (n_cpu == 0) return fail(h, NFAGG_EINVAL, "n_cpu must be >= 1");
-    HIP_TRY(h, hipSetDevice(h->device));
-    nfagg_map_view dm{}, df[6] = {};
-    int rc;
-    for (int q = 0; q < 7; q++) {
-        const nfagg_map_view& v = q == 0 ? *main_map : feature_maps[q - 1];
-        nfagg_map_view& d = q == 0 ? dm : df[q - 1];
-        d.n = v.n;
-        if (!v.n) continue;
-        if (!v.ids || !v.values) return fail(h, NFAGG_EINVAL, "map %d: null ids/values", q);
-        const size_t vb = q == 0 ? v.n * sizeof(nfagg_flow_metrics) : v.n * n_cpu * rollup_struct_size(q - 1);
-        if ((rc = ensure_bytes(h, &h->d_mm[6 + q], &h->d_mm_cap[6 + q], v.n * sizeof(nfagg_flow_id))) != NFAGG_OK) return rc;
-        if ((rc = ensure_bytes(h, &h->d_mm[13 + q], &h->d_mm_cap[13 + q], vb)) != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_mm[6 + q], v.ids, v.n * sizeof(nfagg_flow_id), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->d_mm[13 + q], v.values, vb, hipMemcpyHostToDevice, h->stream));
-        d.ids = (const nfagg_flow_id*)h->d_mm[6 + q]; d.values = h->d_mm[13 + q];
-    }
-    void* host_out[8] = {out->records, out->present, out->additional, out->dns, out->drops, out->network_events, out->xlat, out->quic};
-    const size_t elem[8] = {sizeof(nfagg_flow_record), 1, sizeof(nfagg_additional_metrics), sizeof(nfagg_dns_metrics), sizeof(nfagg_pkt_drop_metrics),
-                            sizeof(nfagg_network_events_metrics), sizeof(nfagg_xlat_metrics), sizeof(nfagg_quic_metrics)};
-    void* dev_out[8] = {};
-    for (int k = 0; k < 8; k++) {
-        if (!host_out[k] || !cap) continue;
-        if ((rc = ensure_bytes(h, &h->d_mm[20 + k], &h->d_mm_cap[20 + k], cap * elem[k] + 16)) != NFAGG_OK) return rc;
-        dev_out[k] = h->d_mm[20 + k];
-    }
-    nfagg_merged_flows dout{(nfagg_flow_record*)dev_out[0], (uint8_t*)dev_out[1], (nfagg_additional_metrics*)dev_out[2], (nfagg_dns_metrics*)dev_out[3],
-                            (nfagg_pkt_drop_metrics*)dev_out[4], (nfagg_network_events_metrics*)dev_out[5], (nfagg_xlat_metrics*)dev_out[6],
-                            (nfagg_quic_metrics*)dev_out[7]};
-    rc = map_merge_device_core(h, &dm, df, n_cpu, &dout, cap, n_out, n_duplicate_keys);
-    if (rc != NFAGG_OK) return rc;
-    for (int k = 0; k < 8; k++)
-        if (dev_out[k] && *n_out) HIP_TRY(h, hipMemcpyAsync(host_out[k], dev_out[k], *n_out * elem[k], hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-// ---------------------------------------------------------------- sketches
-static int sketch_info(nfagg_handle* h, int which, void** p, size_t* bytes) {
-    if (which == NFAGG_CM_SRC || which == NFAGG_CM_DST) {
-        if (!(h->sk.flags & NFAGG_SKETCH_CM)) return fail(h, NFAGG_ESTATE, "Count-Min sketch not enabled");
-        *p = h->sk.cm[which - NFAGG_CM_SRC];
-        *bytes = ((size_t)h->sk.cm_depth << h->sk.cm_log2w) * sizeof(uint64_t);
-        return NFAGG_OK;
-    }
-    if (which == NFAGG_HLL_SRC || which == NFAGG_HLL_DST) {
-        if (!(h->sk.flags & NFAGG_SKETCH_HLL)) return fail(h, NFAGG_ESTATE, "HyperLogLog sketch not enabled");
-        *p = h->sk.hll[which - NFAGG_HLL_SRC];
-        *bytes = ((size_t)1 << h->sk.hll_p);                     // uint8_t registers
-        return NFAGG_OK;
-    }
-    return fail(h, NFAGG_EINVAL, "unknown sketch id %d", which);
-}
-
-int nfagg_sketch_device_ptr(nfagg_handle* h, int which, void** d_ptr, size_t* bytes) {
-    if (!h || !d_ptr || !bytes) return fail(h, NFAGG_EINVAL, "null argument");
-    return sketch_info(h, which, d_ptr, bytes);
-}
-
-int nfagg_sketch_snapshot(nfagg_handle* h, int which, void* out, size_t out_bytes) {
-    if (!h || !out) return fail(h, NFAGG_EINVAL, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    void* p; size_t bytes;
-    int rc = sketch_info(h, which, &p, &bytes);
-    if (rc != NFAGG_OK) return rc;
-    if (which == NFAGG_CM_SRC || which == NFAGG_CM_DST) {
-        if (out_bytes < bytes) return NFAGG_TRUNCATED;
-        HIP_TRY(h, hipMemcpyAsync(out, p, bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return NFAGG_OK;
-    }
-    if (out_bytes < bytes) return NFAGG_TRUNCATED;                   // the device registers ARE the snapshot layout: one byte each
-    HIP_TRY(h, hipMemcpyAsync(out, p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-int nfagg_sketch_reset(nfagg_handle* h) {
-    if (!h) return NFAGG_EINVAL;
-    HIP_TRY(h, hipSetDevice(h->device));
-    for (int which = 0; which < 4; which++) {
-        const bool on = which < 2 ? (h->sk.flags & NFAGG_SKETCH_CM) : (h->sk.flags & NFAGG_SKETCH_HLL);
-        if (!on) continue;
-        void* p; size_t bytes;
-        int rc = sketch_info(h, which, &p, &bytes);
-        if (rc != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemsetAsync(p, 0, bytes, h->stream));
-    }
-    return NFAGG_OK;
-}
-
-// HyperLogLog estimate (Flajolet et al. 2007, 64-bit hash so no large-range
-// correction) from the histogram of register values: sum_k hist[k] * 2^-k. The sum is accumulated exactly, as the
-// integer sum_k hist[k] << (64 - k) (below 2^103 for any 65 uint32 counts: it fits 128 bits), converted to double once and
-// scaled by 2^-64: one rounding whatever the registers hold. (A sum of doubles term by term rounds at every term whose
-// exponent lies 53 bits below the running sum's: half of the registers at 1 and half at 47 with p = 18 already does it.)
-// alpha * m * m is exact (m is a power of two), the division rounds once. Our own spec; the scalar oracle loops over
-// the registers instead and does the same arithmetic.
-double nfagg_hll_estimate_from_histogram(const uint32_t* hist, uint32_t p) {
-    const double m = (double)(1ull << p);
-    const double alpha = (p == 4) ? 0.673 : (p == 5) ? 0.697 : (p == 6) ? 0.709 : 0.7213 / (1.0 + 1.079 / m);
-    unsigned __int128 acc = 0;
-    for (int k = 0; k <= 64; k++) acc += (unsigned __int128)hist[k] << (64 - k);
-    const double sum = __builtin_ldexp((double)acc, -64);
-    double e = alpha * m * m / sum;
-    if (e <= 2.5 * m && hist[0] != 0) e = m * __builtin_log(m / (double)hist[0]);
-    return e;
-}
-
-int nfagg_hll_estimate(nfagg_handle* h, int which, double* estimate) {
-    if (!h || !estimate) return fail(h, NFAGG_EINVAL, "null argument");
-    if (which != NFAGG_HLL_SRC && which != NFAGG_HLL_DST) return fail(h, NFAGG_EINVAL, "which must be an HLL sketch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    void* p; size_t bytes;
-    int rc = sketch_info(h, which, &p, &bytes);
-    if (rc != NFAGG_OK) return rc;
-    hipError_t e = launch_hll_histogram((const uint8_t*)p, h->sk.hll_p, h->d_hist, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "hll histogram launch failed: %s", hipGetErrorString(e));
-    uint32_t hist[65];
-    HIP_TRY(h, hipMemcpyAsync(hist, h->d_hist, sizeof hist, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *estimate = nfagg_hll_estimate_from_histogram(hist, h->sk.hll_p);
-    return NFAGG_OK;
-}
-
-int nfagg_cm_query(nfagg_handle* h, int which, const uint8_t ip[16], uint64_t* estimate) {
-    if (!h || !ip || !estimate) return fail(h, NFAGG_EINVAL, "null argument");
-    if (which != NFAGG_CM_SRC && which != NFAGG_CM_DST) return fail(h, NFAGG_EINVAL, "which must be a CM sketch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    void* p; size_t bytes;
-    int rc = sketch_info(h, which, &p, &bytes);
-    if (rc != NFAGG_OK) return rc;
-    uint64_t lo, hi;
-    memcpy(&lo, ip, 8); memcpy(&hi, ip + 8, 8);
-    const uint64_t ha = ip_hash(lo, hi, 0), hb = ip_hash(lo, hi, 1) | 1ull;
-    uint64_t best = ~0ull;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (uint32_t r = 0; r < h->sk.cm_depth; r++) {
-        uint64_t v;
-        const uint64_t at = ((uint64_t)r << h->sk.cm_log2w) + cm_index(ha, hb, r, h->sk.cm_log2w);
-        HIP_TRY(h, hipMemcpy(&v, (const uint64_t*)p + at, sizeof v, hipMemcpyDeviceToHost));
-        if (v < best) best = v;
-    }
-    *estimate = best;
-    return NFAGG_OK;
-}
-
-// Heavy hitters. Device: estimate per record, radix sort by estimate (descending). Host: walk the sorted order, keep the
-// first occurrence of every address, stop once k distinct addresses are known AND the estimate has dropped below the
-// k-th one (ties at the boundary are resolved by address bytes, so every candidate with the boundary estimate must be seen).
-static int cm_topk_core(nfagg_handle* h, int which, const void* d_records, size_t n, size_t k, nfagg_heavy_hitter* out, size_t* n_out) {
-    if (!h || !n_out || (k && !out) || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
-    if (which != NFAGG_CM_SRC && which != NFAGG_CM_DST) return fail(h, NFAGG_EINVAL, "which must be a CM sketch");
-    if (n >= (1ull << 31)) return fail(h, NFAGG_ERANGE, "heavy hitters: more than 2^31 candidate records");
-    *n_out = 0;
-    void* cm; size_t cm_bytes;
-    int rc = sketch_info(h, which, &cm, &cm_bytes);
-    if (rc != NFAGG_OK) return rc;
-    if (n == 0 || k == 0) return NFAGG_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int side = which - NFAGG_CM_SRC;
-    size_t temp_bytes = 0;
-    hipError_t e = launch_cm_sort_desc(nullptr, nullptr, nullptr, nullptr, n, nullptr, &temp_bytes, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "sort size query failed: %s", hipGetErrorString(e));
-    if ((rc = ensure_bytes(h, &h->d_hh[0], &h->d_hh_cap[0], n * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_hh[1], &h->d_hh_cap[1], n * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_hh[2], &h->d_hh_cap[2], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_hh[3], &h->d_hh_cap[3], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_hh[4], &h->d_hh_cap[4], temp_bytes + 16)) != NFAGG_OK) return rc;
-    e = launch_cm_estimate((const uint64_t*)cm, h->sk.cm_depth, h->sk.cm_log2w, side, d_records, n, (uint64_t*)h->d_hh[0], (uint32_t*)h->d_hh[2], h->stream);
-    if (e == hipSuccess) e = launch_cm_sort_desc((const uint64_t*)h->d_hh[0], (uint64_t*)h->d_hh[1], (const uint32_t*)h->d_hh[2], (uint32_t*)h->d_hh[3], n,
-                                                 h->d_hh[4], &temp_bytes, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "heavy-hitter launch failed: %s", hipGetErrorString(e));
-    struct Row { uint64_t lo, hi, est; };
-    std::vector<Row> rows, best;                         // best: distinct addresses in order of appearance (estimate descending)
-    std::set<std::pair<uint64_t, uint64_t>> group;       // addresses already taken at the current estimate
-    uint64_t group_est = ~0ull;
-    size_t seen = 0, m = k * 16 < 4096 ? 4096 : k * 16;
-    for (;;) {
-        if (m > n) m = n;
-        if ((rc = ensure_bytes(h, &h->d_hh[5], &h->d_hh_cap[5], m * sizeof(Row))) != NFAGG_OK) return rc;
-        e = launch_cm_gather(d_records, side, (const uint64_t*)h->d_hh[1], (const uint32_t*)h->d_hh[3], m, (uint64_t*)h->d_hh[5], h->stream);
-        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "heavy-hitter gather failed: %s", hipGetErrorString(e));
-        rows.resize(m);
-        HIP_TRY(h, hipMemcpyAsync(rows.data(), h->d_hh[5], m * sizeof(Row), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        bool done = false;
-        for (; seen < m; seen++) {
-            const Row& r = rows[seen];
-            if (best.size() >= k && r.est < best[k - 1].est) { done = true; break; }   // below the boundary: nothing further can enter
-            // an address always carries the same estimate, so a duplicate can only sit among the entries with THIS estimate
-            if (r.est != group_est) { group.clear(); group_est = r.est; }
-            if (group.insert(std::make_pair(r.lo, r.hi)).second) best.push_back(r);
-        }
-        if (done || m == n) break;
-        m *= 4;
-    }
-    std::sort(best.begin(), best.end(), [](const Row& a, const Row& b) {
-        if (a.est != b.est) return a.est > b.est;
-        return memcmp(&a.lo, &b.lo, 16) < 0;             // lo,hi are adjacent: the 16 address bytes in order
-    });
-    const size_t cnt = best.size() < k ? best.size() : k;
-    for (size_t q = 0; q < cnt; q++) { memcpy(out[q].ip, &best[q].lo, 16); out[q].estimate = best[q].est; }
-    *n_out = cnt;
-    return NFAGG_OK;
-}
-
-int nfagg_cm_topk_device(nfagg_handle* h, int which, const void* d_records, size_t n, size_t k, nfagg_heavy_hitter* out, size_t* n_out) {
-    return cm_topk_core(h, which, d_records, n, k, out, n_out);
-}
-
-int nfagg_cm_topk(nfagg_handle* h, int which, const void* records, size_t n, size_t k, nfagg_heavy_hitter* out, size_t* n_out) {
-    if (!h || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_bytes(h, &h->d_hh[6], &h->d_hh_cap[6], n * kRecordBytes + 16);
-    if (rc != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_hh[6], records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    return cm_topk_core(h, which, h->d_hh[6], n, k, out, n_out);
-}
-
 // ---------------------------------------------------------------- misc
 uint64_t nfagg_key_hash(const nfagg_flow_id* id) {
     uint64_t w[5];
@@ -2173,12 +1691,6 @@ uint64_t nfagg_ip_hash(const uint8_t ip[16], uint32_t seed_index) {
     uint64_t lo, hi;
     memcpy(&lo, ip, 8); memcpy(&hi, ip + 8, 8);
     return ip_hash(lo, hi, seed_index);
-}
-
-uint64_t nfagg_metrics_group_hash(uint32_t grouping, const nfagg_metric_group* key) {
-    if (!key || grouping >= kMetMaxGroupings) return 0;
-    return met_hash(met_key_a(grouping, key->src_class, key->dst_class),
-                    met_key_b(grouping, key->src_label, key->dst_label, key->direction, key->layer, key->proto, key->is_ip));
 }
 
 int nfagg_sync(nfagg_handle* h) {
@@ -2205,1552 +1717,6 @@ int nfagg_stats_get(nfagg_handle* h, nfagg_stats* out) {
     h->stats.entries = h->live;
     h->stats.epoch_seq = h->epoch_seq;
     *out = h->stats;
-    return NFAGG_OK;
-}
-
-}  // extern "C"
-
-// The cookie table of nfagg_netev_table_create: the sorted rows and the rendered blob, on the host and (with a handle) on its device.
-struct nfagg_netev_table {
-    nfagg_handle* h = nullptr;
-    std::vector<NetevRow> rows;
-    std::vector<uint8_t> blob;
-    void* d_rows = nullptr;
-    void* d_blob = nullptr;
-};
-
-// The TLS name table of nfagg_tls_names_create (nfagg_tls.h):
-// per kind the ids ascending and a 64-byte row per id (length byte, name), on the host and (with a handle) on its device.
-struct nfagg_tls_names {
-    nfagg_handle* h = nullptr;
-    uint32_t n[kTlsKinds] = {};
-    std::vector<uint16_t> ids = std::vector<uint16_t>(kTlsKinds * kTlsMaxRows, 0);
-    std::vector<uint8_t> rows = std::vector<uint8_t>((size_t)kTlsKinds * kTlsMaxRows * kTlsRowBytes, 0);
-    void* d_mem = nullptr;        // the ids, then the rows
-};
-
-// The Kubernetes table of nfagg_k8s_table_create (nfagg_flp.h, nfagg_k8s.h): the slots, the rows and the rendered blocks, on the
-// host and (with a handle) on its device.
-struct nfagg_k8s_table {
-    nfagg_handle* h = nullptr;
-    std::vector<K8sSlot> slots;
-    std::vector<K8sRow> rows;
-    std::vector<uint8_t> blob;
-    bool has_layer = false;
-    // reinterpret_direction compares host-IP TEXT: every row's host_ip interned, 0 for the empty string, in an array of its
-    // own beside the rows (the kernels that read K8sRow do not see it); host_text finds a call's reporter
-    std::vector<uint32_t> host_ids;
-    std::unordered_map<std::string, uint32_t> host_text;
-    // nfagg_metrics_table_create groups rows by the TEXT of their fields: nine ids per row in nfagg_k8s_entry's order, 0: the
-    // field is absent as nfagg_k8s_render has it, else 1 + the interned text (the empty string has an id like any other).
-    // Host side only.
-    std::vector<uint32_t> field_ids;
-    std::unordered_map<std::string, uint32_t> field_text;
-    void* d_slots = nullptr;
-    void* d_rows = nullptr;
-    void* d_blob = nullptr;
-    void* d_host_ids = nullptr;
-};
-
-// The table of nfagg_net_table_create (nfagg_flp.h, nfagg_net.h): the normalised CIDR list, the labels' fragments, on the host
-// and (with a handle) in one allocation on its device: cidrs, meta, frags, blob, each 32-byte aligned.
-struct nfagg_net_table {
-    nfagg_handle* h = nullptr;
-    uint32_t flags = 0;
-    std::vector<NetCidr> cidrs;
-    std::vector<uint32_t> meta;
-    std::vector<NetFrag> frags;
-    std::vector<uint8_t> blob;
-    size_t off_meta = 0, off_frags = 0, off_blob = 0;
-    void* d_mem = nullptr;
-};
-
-// ---- the export encoders' host side: what protobuf, IPFIX and direct-FLP JSON do alike
-namespace {
-
-int ensure_buf(nfagg_handle* h, nfagg_handle::DevBuf& b, size_t need) { return ensure_bytes(h, &b.p, &b.cap, need); }
-
-int check_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names, uint32_t unknown_len, bool check_udn) {
-    if (unknown_len > 16 || (n_names && !names)) return fail(h, NFAGG_EINVAL, "bad namer table");
-    for (uint32_t k = 0; k < n_names; k++) {
-        if (names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
-        if (check_udn && names[k].udn_len > 63) return fail(h, NFAGG_EINVAL, "namer row %u: udn too long", k);
-    }
-    return NFAGG_OK;
-}
-
-// The kernels binary-search the table: a stable sort by if_index keeps the scan-in-table-order answer.
-int stage_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names) {
-    auto& S = h->enc;
-    int rc = ensure_buf(h, S.names, (size_t)(n_names + 1) * sizeof(nfagg_intf_name));
-    if (rc != NFAGG_OK) return rc;
-    S.h_names.assign(names, names + n_names);
-    std::stable_sort(S.h_names.begin(), S.h_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
-    if (n_names) HIP_TRY(h, hipMemcpyAsync(S.names.p, S.h_names.data(), n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
-    return NFAGG_OK;
-}
-
-void split_now(int64_t now_unix_ns, int64_t& sec, int64_t& nsec) {   // time.Time's (sec, nsec), 0 <= nsec < 1e9
-    sec = now_unix_ns / 1000000000ll; nsec = now_unix_ns % 1000000000ll;
-    if (nsec < 0) { nsec += 1000000000ll; sec -= 1; }
-}
-
-// What follows the argument checks of a device entry point: the device, the zeroed results, the answer for n == 0 (*done), the
-// scratch of the two scans, the namer table.
-int encode_begin(nfagg_handle* h, size_t n, uint64_t* d_offsets, size_t* out_bytes, const nfagg_intf_name* names, uint32_t n_names, bool* done) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    *out_bytes = 0;
-    *done = n == 0;
-    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
-    const size_t blocks = (n + 1023) / 1024;
-    int rc;
-    if ((rc = ensure_buf(h, h->enc.local_off, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, h->enc.block_sum, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, h->enc.block_base, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    return stage_namer(h, names, n_names);
-}
-
-// The two passes: size(local_off, block_sum, block_base) launches the size kernel and the scan of the block sums; the total (and
-// the FLP encoder's deferred counter) is read back; a buffer that is too small or absent ends it there, with the total in
-// *out_bytes; write(local_off, block_base, total) launches the write kernel.
-template <typename SizeLaunch, typename WriteLaunch>
-int encode_two_pass(nfagg_handle* h, size_t n, const char* what, const char* write_verb, void* d_out, size_t out_cap, size_t* out_bytes,
-                           size_t* n_deferred, SizeLaunch size, WriteLaunch write) {
-    auto& S = h->enc;
-    const size_t blocks = (n + 1023) / 1024;
-    hipError_t e = size((uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s size launch failed: %s", what, hipGetErrorString(e));
-    uint64_t total = 0;
-    uint32_t deferred = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)S.block_base.p + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
-    if (n_deferred) HIP_TRY(h, hipMemcpyAsync(&deferred, S.flp_n_deferred.p, sizeof deferred, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *out_bytes = (size_t)total;
-    if (n_deferred) *n_deferred = deferred;
-    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
-    e = write((const uint32_t*)S.local_off.p, (const uint64_t*)S.block_base.p, total);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s %s launch failed: %s", what, write_verb, hipGetErrorString(e));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-// The host-memory entry points: records in, device(d_records, d_out or null, d_offsets) = the device entry point, bytes and offsets
-// out, and the format's per-record extras (out_extra[k] -> host, `bytes` per record; skipped when the caller passed no host array).
-struct EncodeExtra { void* host; size_t bytes; };
-template <typename DeviceEntry>
-int encode_staged(nfagg_handle* h, const void* records, size_t n, void* out, size_t out_cap, uint64_t* offsets, size_t* out_bytes,
-                         std::initializer_list<EncodeExtra> extras, DeviceEntry device) {
-    auto& S = h->enc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out, out_cap + 32)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out_offsets, (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    size_t k = 0;
-    for (const EncodeExtra& x : extras) { if (x.host && (rc = ensure_buf(h, S.out_extra[k], n * x.bytes + 32)) != NFAGG_OK) return rc; k++; }
-    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    rc = device(S.in_records.p, out ? S.out.p : nullptr, (uint64_t*)S.out_offsets.p);
-    if (rc != NFAGG_OK) return rc;
-    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, S.out.p, *out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(offsets, S.out_offsets.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    k = 0;
-    for (const EncodeExtra& x : extras) { if (n && x.host) HIP_TRY(h, hipMemcpyAsync(x.host, S.out_extra[k].p, n * x.bytes, hipMemcpyDeviceToHost, h->stream)); k++; }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-// nfagg_pb_features with DEVICE pointers, checked, as the kernels take it (protobuf and direct-FLP content encoders)
-static int device_features(nfagg_handle* h, const nfagg_pb_features* feat, PbFeat* F) {
-    if (feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
-    if ((((uintptr_t)feat->additional | (uintptr_t)feat->dns | (uintptr_t)feat->drops | (uintptr_t)feat->xlat | (uintptr_t)feat->quic) & 7u) != 0)
-        return fail(h, NFAGG_EINVAL, "feature arrays must be 8-byte aligned");
-    F->present = feat->present;
-    F->additional = (const uint8_t*)feat->additional; F->dns = (const uint8_t*)feat->dns; F->drops = (const uint8_t*)feat->drops;
-    F->xlat = (const uint8_t*)feat->xlat; F->quic = (const uint8_t*)feat->quic;
-    return NFAGG_OK;
-}
-
-// The *_netev entry points' extra inputs: the flows' rows (DEVICE memory) and the table they index, into F.
-struct NetevArgs { const uint16_t* rows; const nfagg_netev_table* table; };
-static int device_netev(nfagg_handle* h, const NetevArgs* ne, size_t n, PbFeat* F) {
-    if (!ne->table || (n && !ne->rows)) return fail(h, NFAGG_EINVAL, "null network-events rows or table");
-    if (ne->table->h != h || !ne->table->d_rows) return fail(h, NFAGG_EINVAL, "the network-events table was not created for this handle");
-    if (((uintptr_t)ne->rows & 7u) != 0) return fail(h, NFAGG_EINVAL, "network-events rows must be 8-byte aligned");
-    F->ne_rows = ne->rows; F->ne_tab = (const uint8_t*)ne->table->d_rows; F->ne_blob = (const uint8_t*)ne->table->d_blob;
-    F->ne_n = (uint32_t)ne->table->rows.size();
-    return NFAGG_OK;
-}
-// The rows of a host-memory call, uploaded.
-static int stage_netev_rows(nfagg_handle* h, const NetevArgs* ne, size_t n, NetevArgs* dne) {
-    *dne = *ne;
-    if (!n || !ne->rows) return NFAGG_OK;
-    int rc = ensure_buf(h, h->enc.ne_rows, n * 8 + 16);
-    if (rc != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->enc.ne_rows.p, ne->rows, n * 8, hipMemcpyHostToDevice, h->stream));
-    dne->rows = (const uint16_t*)h->enc.ne_rows.p;
-    return NFAGG_OK;
-}
-
-// ---- record -> protobuf (nfagg_pb.hip)
-// feat (optional): DEVICE pointers. ne (optional): the network events of the *_netev entry points.
-static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                                 const nfagg_pb_options* opt,
-                                 void* d_out, size_t out_cap, uint64_t* d_frame_offsets, uint32_t* d_body_len,
-                                 void* d_kafka_keys, size_t* out_bytes) {
-    if (!h || !opt || !out_bytes || !d_frame_offsets || (n && (!d_records || !d_body_len))) return fail(h, NFAGG_EINVAL, "null argument");
-    if (opt->struct_size != sizeof(nfagg_pb_options)) return fail(h, NFAGG_EINVAL, "nfagg_pb_options.struct_size mismatch");
-    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");   // ahead of the alignment, the rows behind it
-    if ((((uintptr_t)d_records | (uintptr_t)d_out | (uintptr_t)d_kafka_keys) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
-    int rc = check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
-    if (rc != NFAGG_OK) return rc;
-    PbFeat F{};
-    if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
-    if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
-    bool done;
-    if ((rc = encode_begin(h, n, d_frame_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
-    PbParams P{};
-    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
-    P.mono_now = opt->mono_now_ns;
-    memcpy(P.agent_ip_w, opt->agent_ip, 16);
-    static const uint8_t v4pre[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xff, 0xff};
-    P.agent_is_v4 = memcmp(opt->agent_ip, v4pre, 12) == 0;     // net.IP.To4() != nil (proto.go:255-261)
-    P.names = (const nfagg_intf_name*)h->enc.names.p; P.n_names = opt->n_names;
-    P.unknown_len = opt->unknown_len; memcpy(P.unknown, opt->unknown_name, 16);
-    return encode_two_pass(h, n, "protobuf", "encode", d_out, out_cap, out_bytes, nullptr,
-        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-            return launch_pb_size(d_records, n, P, F, d_body_len, local_off, block_sum, block_base, h->stream); },
-        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t total) {
-            return launch_pb_write(d_records, n, P, F, d_body_len, local_off, block_base, d_out, d_frame_offsets, d_kafka_keys, total, h->stream); });
-}
-
-// The feature parts of a host-memory call, uploaded: *dfeat gets the device pointers.
-static int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, nfagg_pb_features* dfeat) {
-    dfeat->struct_size = sizeof *dfeat;
-    const void* src[6] = {feat->present, feat->additional, feat->dns, feat->drops, feat->xlat, feat->quic};
-    const size_t elem[6] = {1, sizeof(nfagg_additional_metrics), sizeof(nfagg_dns_metrics), sizeof(nfagg_pkt_drop_metrics),
-                            sizeof(nfagg_xlat_metrics), sizeof(nfagg_quic_metrics)};
-    void* dst[6] = {};
-    for (int k = 0; k < 6; k++) {
-        if (!src[k]) continue;
-        int rc = ensure_buf(h, h->enc.pb_feat[k], n * elem[k] + 16);
-        if (rc != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->enc.pb_feat[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
-        dst[k] = h->enc.pb_feat[k].p;
-    }
-    dfeat->present = (const uint8_t*)dst[0]; dfeat->additional = (const nfagg_additional_metrics*)dst[1];
-    dfeat->dns = (const nfagg_dns_metrics*)dst[2]; dfeat->drops = (const nfagg_pkt_drop_metrics*)dst[3];
-    dfeat->xlat = (const nfagg_xlat_metrics*)dst[4]; dfeat->quic = (const nfagg_quic_metrics*)dst[5];
-    return NFAGG_OK;
-}
-
-// feat (optional): HOST pointers
-static int encode_pb_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                               const nfagg_pb_options* opt,
-                               void* out, size_t out_cap, uint64_t* frame_offsets, uint32_t* body_len,
-                               void* kafka_keys, size_t* out_bytes) {
-    if (!h || !opt || !out_bytes || !frame_offsets || (n && (!records || !body_len))) return fail(h, NFAGG_EINVAL, "null argument");
-    if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
-    return encode_staged(h, records, n, out, out_cap, frame_offsets, out_bytes, {{body_len, sizeof(uint32_t)}, {kafka_keys, 32}},
-        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
-            nfagg_pb_features dfeat{};
-            if (feat && n) { int rc = stage_pb_features(h, feat, n, &dfeat); if (rc != NFAGG_OK) return rc; }
-            NetevArgs dne{};
-            if (ne) { int rc = stage_netev_rows(h, ne, n, &dne); if (rc != NFAGG_OK) return rc; }
-            return encode_pb_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, opt, d_out, out_cap, d_offsets,
-                                         (uint32_t*)h->enc.out_extra[0].p, kafka_keys ? h->enc.out_extra[1].p : nullptr, out_bytes); });
-}
-
-int nfagg_encode_pb_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_options* opt,
-                           void* d_out, size_t out_cap, uint64_t* d_frame_offsets, uint32_t* d_body_len,
-                           void* d_kafka_keys, size_t* out_bytes) {
-    return encode_pb_device_core(h, d_records, n, nullptr, nullptr, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
-}
-
-int nfagg_encode_pb(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_options* opt,
-                    void* out, size_t out_cap, uint64_t* frame_offsets, uint32_t* body_len,
-                    void* kafka_keys, size_t* out_bytes) {
-    return encode_pb_host_core(h, records, n, nullptr, nullptr, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
-}
-
-int nfagg_encode_pb_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
-                                   const nfagg_pb_options* opt, void* d_out, size_t out_cap, uint64_t* d_frame_offsets,
-                                   uint32_t* d_body_len, void* d_kafka_keys, size_t* out_bytes) {
-    if (!d_features) return fail(h, NFAGG_EINVAL, "null features (use nfagg_encode_pb_device)");
-    return encode_pb_device_core(h, d_records, n, d_features, nullptr, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
-}
-
-int nfagg_encode_pb_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
-                            const nfagg_pb_options* opt, void* out, size_t out_cap, uint64_t* frame_offsets,
-                            uint32_t* body_len, void* kafka_keys, size_t* out_bytes) {
-    if (!features) return fail(h, NFAGG_EINVAL, "null features (use nfagg_encode_pb)");
-    return encode_pb_host_core(h, records, n, features, nullptr, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
-}
-
-int nfagg_encode_pb_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
-                                         const uint16_t* d_rows, const nfagg_netev_table* table,
-                                         const nfagg_pb_options* opt, void* d_out, size_t out_cap, uint64_t* d_frame_offsets,
-                                         uint32_t* d_body_len, void* d_kafka_keys, size_t* out_bytes) {
-    const NetevArgs ne{d_rows, table};
-    return encode_pb_device_core(h, d_records, n, d_features, &ne, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
-}
-
-int nfagg_encode_pb_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
-                                  const uint16_t* rows, const nfagg_netev_table* table,
-                                  const nfagg_pb_options* opt, void* out, size_t out_cap, uint64_t* frame_offsets,
-                                  uint32_t* body_len, void* kafka_keys, size_t* out_bytes) {
-    const NetevArgs ne{rows, table};
-    return encode_pb_host_core(h, records, n, features, &ne, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
-}
-
-// ---- record -> IPFIX (nfagg_ipfix.hip)
-static const uint16_t kIpfixTemplateV4[19][2] = {   // ipfix.go:89-135 + AddRecordValuesToTemplate; IDs and lengths: registry_IANA.go
-    {256, 2}, {61, 1}, {56, 6}, {80, 6}, {8, 4}, {12, 4}, {4, 1}, {7, 2}, {11, 2}, {176, 1}, {177, 1},
-    {1, 8}, {6, 2}, {150, 4}, {152, 8}, {151, 4}, {153, 8}, {2, 8}, {82, 65535}};
-static const uint16_t kIpfixTemplateV6[19][2] = {   // ipfix.go:158-204 + AddRecordValuesToTemplate
-    {256, 2}, {61, 1}, {56, 6}, {80, 6}, {27, 16}, {28, 16}, {193, 1}, {7, 2}, {11, 2}, {178, 1}, {179, 1},
-    {1, 8}, {6, 2}, {150, 4}, {152, 8}, {151, 4}, {153, 8}, {2, 8}, {82, 65535}};
-static constexpr size_t kIpfixTemplateBytes = 16 + 4 + 4 + 19 * 4;
-
-static void put_be16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 8); p[1] = (uint8_t)v; }
-static void put_be32(uint8_t* p, uint32_t v) { put_be16(p, v >> 16); put_be16(p + 2, v); }
-
-int nfagg_ipfix_template(const nfagg_ipfix_options* opt, int v6, void* out, size_t cap, size_t* n_out) {
-    if (!opt || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
-    if (opt->struct_size != sizeof(nfagg_ipfix_options)) return fail(nullptr, NFAGG_EINVAL, "nfagg_ipfix_options.struct_size mismatch");
-    *n_out = kIpfixTemplateBytes;
-    if (!out || cap < kIpfixTemplateBytes) return NFAGG_TRUNCATED;
-    uint8_t* p = (uint8_t*)out;
-    put_be16(p, 10); put_be16(p + 2, (uint32_t)kIpfixTemplateBytes); put_be32(p + 4, opt->export_time_s);
-    put_be32(p + 8, opt->seq0); put_be32(p + 12, opt->obs_domain_id);
-    put_be16(p + 16, 2); put_be16(p + 18, (uint32_t)kIpfixTemplateBytes - 16);                // template set
-    put_be16(p + 20, v6 ? opt->template_id_v6 : opt->template_id_v4); put_be16(p + 22, 19);  // template record header
-    const uint16_t (*f)[2] = v6 ? kIpfixTemplateV6 : kIpfixTemplateV4;
-    for (int k = 0; k < 19; k++) { put_be16(p + 24 + 4 * k, f[k][0]); put_be16(p + 26 + 4 * k, f[k][1]); }   // enterprise bit never set
-    return NFAGG_OK;
-}
-
-// The options are checked first, before the handle: a caller learns of a bad table without any device work.
-static int encode_ipfix_check(nfagg_handle* h, const nfagg_ipfix_options* opt) {
-    if (!opt) return fail(h, NFAGG_EINVAL, "null options");
-    if (opt->struct_size != sizeof(nfagg_ipfix_options)) return fail(h, NFAGG_EINVAL, "nfagg_ipfix_options.struct_size mismatch");
-    return check_namer(h, opt->names, opt->n_names, opt->unknown_len, false);
-}
-
-int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_ipfix_options* opt,
-                              void* d_out, size_t out_cap, uint64_t* d_msg_offsets, size_t* out_bytes) {
-    int rc = encode_ipfix_check(h, opt);
-    if (rc != NFAGG_OK) return rc;
-    if (!h || !out_bytes || !d_msg_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
-    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
-    bool done;
-    if ((rc = encode_begin(h, n, d_msg_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
-    if ((rc = ensure_buf(h, h->enc.ipfix_name_rows, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    uint32_t* name_rows = (uint32_t*)h->enc.ipfix_name_rows.p;
-    IpfixParams P{};
-    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
-    P.mono_now = opt->mono_now_ns;
-    P.names = (const nfagg_intf_name*)h->enc.names.p; P.n_names = opt->n_names;
-    P.unknown_len = opt->unknown_len; memcpy(P.unknown_w, opt->unknown_name, 16);
-    P.export_time = opt->export_time_s; P.seq0 = opt->seq0; P.obs_domain = opt->obs_domain_id;
-    P.tid_v4 = opt->template_id_v4; P.tid_v6 = opt->template_id_v6;
-    return encode_two_pass(h, n, "IPFIX", "write", d_out, out_cap, out_bytes, nullptr,
-        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-            return launch_ipfix_size(d_records, n, P, name_rows, local_off, block_sum, block_base, h->stream); },
-        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-            return launch_ipfix_write(d_records, n, P, name_rows, local_off, block_base, d_out, d_msg_offsets, h->stream); });
-}
-
-int nfagg_encode_ipfix(nfagg_handle* h, const void* records, size_t n, const nfagg_ipfix_options* opt,
-                       void* out, size_t out_cap, uint64_t* msg_offsets, size_t* out_bytes) {
-    int rc = encode_ipfix_check(h, opt);
-    if (rc != NFAGG_OK) return rc;
-    if (!h || !out_bytes || !msg_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
-    return encode_staged(h, records, n, out, out_cap, msg_offsets, out_bytes, {},
-        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
-            return nfagg_encode_ipfix_device(h, d_records, n, opt, d_out, out_cap, d_offsets, out_bytes); });
-}
-
-// ---- record -> direct-FLP JSON lines (nfagg_flp.hip)
-// jsoniter's Stream.WriteString without HTML escaping (stream_str.go:311-372): the quotes, \" \\ \n \r \t, any other byte
-// below 0x20 as \u00xx in lower-case hex, every other byte (0x7f and everything from 0x80 up) as it is. Returns the length.
-static uint32_t flp_escape(const char* src, uint32_t len, uint8_t* dst) {
-    static const char hex[] = "0123456789abcdef";
-    uint32_t o = 0;
-    dst[o++] = '"';
-    for (uint32_t k = 0; k < len; k++) {
-        const uint8_t b = (uint8_t)src[k];
-        if (b == '"' || b == '\\') { dst[o++] = '\\'; dst[o++] = b; }
-        else if (b == '\n') { dst[o++] = '\\'; dst[o++] = 'n'; }
-        else if (b == '\r') { dst[o++] = '\\'; dst[o++] = 'r'; }
-        else if (b == '\t') { dst[o++] = '\\'; dst[o++] = 't'; }
-        else if (b < 0x20) { memcpy(dst + o, "\\u00", 4); o += 4; dst[o++] = (uint8_t)hex[b >> 4]; dst[o++] = (uint8_t)hex[b & 15]; }
-        else dst[o++] = b;
-    }
-    dst[o++] = '"';
-    return o;
-}
-
-static void flp_escape_row(uint8_t* row, const char* name, uint32_t name_len, const char* udn, uint32_t udn_len) {
-    const uint16_t nl = (uint16_t)flp_escape(name, name_len, row + kFlpEscNameOff), ul = (uint16_t)flp_escape(udn, udn_len, row + kFlpEscUdnOff);
-    memcpy(row, &nl, 2); memcpy(row + 2, &ul, 2);
-}
-
-// The options are checked first, before the handle: a caller learns of a bad table without any device work.
-static int encode_flp_check(nfagg_handle* h, const nfagg_flp_options* opt) {
-    if (!opt) return fail(h, NFAGG_EINVAL, "null options");
-    if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
-    return check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
-}
-
-// What the FLP device entry points stage after encode_begin: the size pass's rows, the escaped namer table, the deferred counter
-// (zeroed), the kernels' parameters.
-static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, FlpParams* Pout, uint32_t** rows_out) {
-    int rc;
-    auto& S = h->enc;
-    const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
-    if ((rc = ensure_buf(h, S.flp_rows, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.flp_esc, esc_bytes)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.flp_n_deferred, 16)) != NFAGG_OK) return rc;
-    // names and UDNs are escaped here, once per row of the sorted table: neither kernel escapes per flow
-    S.h_flp_esc.assign(esc_bytes, 0);
-    flp_escape_row(S.h_flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
-    for (uint32_t k = 0; k < opt->n_names; k++) {
-        const nfagg_intf_name& e = S.h_names[k];
-        flp_escape_row(S.h_flp_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
-    }
-    HIP_TRY(h, hipMemcpyAsync(S.flp_esc.p, S.h_flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
-    *rows_out = (uint32_t*)S.flp_rows.p;
-    FlpParams& P = *Pout;
-    P = FlpParams{};
-    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
-    P.mono_now = opt->mono_now_ns;
-    P.time_received = opt->time_received_s;
-    P.names = (const nfagg_intf_name*)S.names.p; P.esc = (const uint8_t*)S.flp_esc.p; P.n_names = opt->n_names;
-    P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
-    return NFAGG_OK;
-}
-
-// The TLS entry points' extra input. With it the three TLS keys are written from the table, no record is deferred (flags and
-// counter are not used), and the network events are an option: rows and table both, or neither (*ne = nullptr).
-// with_k8s: the *_k8s entry points, whose table is required as well and whose lines carry the Kubernetes keys.
-// with_net: the *_net entry points, which take the table of the transform network rules on top of that.
-struct FlpTlsArgs {
-    const nfagg_tls_names* names; bool with_k8s = false; const nfagg_k8s_table* k8s = nullptr;
-    bool with_net = false; const nfagg_net_table* net = nullptr;
-};
-static NetDev net_dev(const nfagg_net_table* t) {
-    const uint8_t* m = (const uint8_t*)t->d_mem;
-    return NetDev{(const NetCidr*)m, (const uint32_t*)(m + t->off_meta), (const NetFrag*)(m + t->off_frags), m + t->off_blob,
-                  (uint32_t)t->cidrs.size(), (uint32_t)t->frags.size(), t->flags};
-}
-// net.IP.String() of a 16-byte address, as ip_text (nfagg_flp_line.h) prints AgentIP on the device: the dotted quad for a
-// v4-mapped one, else netip's appendTo6.
-static std::string go_ip_text(const uint8_t ip[16]) {
-    static const uint8_t v4[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xff, 0xff};
-    char buf[48];
-    if (memcmp(ip, v4, 12) == 0) { snprintf(buf, sizeof buf, "%u.%u.%u.%u", ip[12], ip[13], ip[14], ip[15]); return buf; }
-    uint32_t g[8];
-    for (int k = 0; k < 8; k++) g[k] = ((uint32_t)ip[2 * k] << 8) | ip[2 * k + 1];
-    int z0 = -1, zlen = 1, cur = 0, curlen = 0;                          // only runs of two or more zero groups count; the first longest wins
-    for (int k = 0; k < 8; k++) {
-        if (g[k] == 0) { if (curlen == 0) cur = k; curlen++; if (curlen > zlen) { z0 = cur; zlen = curlen; } }
-        else curlen = 0;
-    }
-    const int z1 = z0 < 0 ? -1 : z0 + zlen;
-    std::string o;
-    for (int k = 0; k < 8; k++) {
-        if (k == z0) o += "::";
-        else if (k < z0 || k >= z1) {
-            if (k > 0 && k != z1) o += ':';
-            snprintf(buf, sizeof buf, "%x", g[k]);
-            o += buf;
-        }
-    }
-    return o;
-}
-// The reporter of a call: the id of AgentIP's text among the table's host IPs, kNetNoHost when no row carries that text
-// (transform_network_direction.go:37-44; "<nil>" is not empty, so the rule goes on).
-static uint32_t net_reporter(const nfagg_k8s_table* k8s, const nfagg_flp_options* opt) {
-    const auto it = k8s->host_text.find(opt->agent_ip_nil ? std::string("<nil>") : go_ip_text(opt->agent_ip));
-    return it == k8s->host_text.end() ? kNetNoHost : it->second;
-}
-static K8sDev k8s_dev(const nfagg_k8s_table* t) {
-    return K8sDev{(const K8sSlot*)t->d_slots, (const K8sRow*)t->d_rows, (const uint8_t*)t->d_blob, (uint32_t)t->slots.size() - 1,
-                  (uint32_t)t->rows.size(), t->has_layer ? 1u : 0u};
-}
-static int netev_optional(nfagg_handle* h, const NetevArgs** ne, size_t n) {
-    if (!*ne) return NFAGG_OK;
-    const NetevArgs& a = **ne;
-    if ((a.rows != nullptr) != (a.table != nullptr) && (n || a.rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
-    if (!a.table) *ne = nullptr;
-    return NFAGG_OK;
-}
-
-// feat (optional): DEVICE pointers. The launchers pick the kernels' feature policy: neither feat nor ne the plain line, ne (the
-// *_netev and *_tls entry points) the one with the NetworkEvents hook, tls the TLS names on top of either.
-static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                                  const FlpTlsArgs* tls, const nfagg_flp_options* opt,
-                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
-                                  size_t* n_deferred, size_t* out_bytes) {
-    int rc;
-    if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
-    if ((rc = encode_flp_check(h, opt)) != NFAGG_OK) return rc;
-    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !d_line_offsets ||
-        (n && !d_records))
-        return fail(h, NFAGG_EINVAL, "null argument");
-    if (tls && (tls->names->h != h || !tls->names->d_mem)) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
-    const nfagg_k8s_table* k8s = tls && tls->with_k8s ? tls->k8s : nullptr;
-    if (k8s && (k8s->h != h || !k8s->d_slots)) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
-    const nfagg_net_table* net = k8s && tls->with_net ? tls->net : nullptr;
-    if (net && (net->h != h || !net->d_mem)) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
-    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
-    PbFeat F{};
-    if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
-    if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
-    if (n_deferred) *n_deferred = 0;
-    bool done;
-    if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
-    FlpParams P{};
-    uint32_t* rows;
-    if ((rc = stage_flp(h, n, opt, &P, &rows)) != NFAGG_OK) return rc;
-    uint32_t* counter = (uint32_t*)h->enc.flp_n_deferred.p;
-    TlsDev T{};
-    if (tls) {
-        T.ids = (const uint16_t*)tls->names->d_mem;
-        T.rows = (const uint8_t*)tls->names->d_mem + tls->names->ids.size() * sizeof(uint16_t);
-        for (uint32_t k = 0; k < kTlsKinds; k++) T.n[k] = tls->names->n[k];
-    }
-    const PbFeat* Fp = (feat || ne) ? &F : nullptr;                   // neither: the plain line
-    const TlsDev* Tp = tls ? &T : nullptr;
-    if (k8s) {
-        if ((rc = ensure_buf(h, h->enc.k8s_rows, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-        uint32_t* k8s_rows = (uint32_t*)h->enc.k8s_rows.p;
-        const K8sDev K = k8s_dev(k8s);
-        hipError_t e = launch_k8s_resolve(d_records, n, K, k8s_rows, h->stream);
-        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
-        if (net) {
-            if ((rc = ensure_buf(h, h->enc.net_rows, n * sizeof(uint2))) != NFAGG_OK) return rc;
-            const uint2* net_rows = (const uint2*)h->enc.net_rows.p;
-            const NetDev N = net_dev(net);
-            e = launch_net_resolve(d_records, n, N, k8s_rows, (const uint32_t*)k8s->d_host_ids, K.n_rows, net_reporter(k8s, opt), (uint2*)h->enc.net_rows.p,
-                                   h->stream);
-            if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
-            return encode_two_pass(h, n, "FLP JSON with transform network keys", "write", d_out, out_cap, out_bytes, nullptr,
-                [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-                    return launch_flp_net_size(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_sum, block_base, h->stream); },
-                [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-                    return launch_flp_net_write(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_base, d_out, d_line_offsets,
-                                                h->stream); });
-        }
-        return encode_two_pass(h, n, "FLP JSON with Kubernetes keys", "write", d_out, out_cap, out_bytes, nullptr,
-            [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-                return launch_flp_k8s_size(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_sum, block_base, h->stream); },
-            [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-                return launch_flp_k8s_write(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_base, d_out, d_line_offsets, h->stream); });
-    }
-    size_t deferred_unused;
-    return encode_two_pass(h, n, tls ? "FLP JSON with TLS names" : Fp ? "FLP JSON content" : "FLP JSON", "write", d_out, out_cap, out_bytes,
-        tls ? nullptr : n_deferred ? n_deferred : &deferred_unused,
-        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-            return launch_flp_size(d_records, n, P, Fp, Tp, rows, local_off, block_sum, block_base, counter, h->stream); },
-        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-            return launch_flp_write(d_records, n, P, Fp, Tp, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
-}
-
-// feat (optional): HOST pointers, uploaded beside the records, as are the rows of ne
-static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                                const FlpTlsArgs* tls, const nfagg_flp_options* opt,
-                                void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
-                                size_t* n_deferred, size_t* out_bytes) {
-    int rc = encode_flp_check(h, opt);
-    if (rc != NFAGG_OK) return rc;
-    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !line_offsets ||
-        (n && !records))
-        return fail(h, NFAGG_EINVAL, "null argument");
-    if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
-    if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
-    return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
-        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
-            nfagg_pb_features dfeat{};
-            if (feat && n) { int rc2 = stage_pb_features(h, feat, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
-            NetevArgs dne{};
-            if (ne) { int rc2 = stage_netev_rows(h, ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
-            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, tls, opt, d_out, out_cap, d_offsets,
-                                          deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
-}
-
-int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
-                                 void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
-                                 size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_device_core(h, d_records, n, nullptr, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
-}
-
-int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
-                          void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
-                          size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_host_core(h, records, n, nullptr, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
-}
-
-// features == NULL: the flows carry no parts, the call is nfagg_encode_flp_json[_device]
-int nfagg_encode_flp_json_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
-                                         const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
-                                         uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_device_core(h, d_records, n, d_features, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
-}
-
-int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
-                                  const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
-                                  uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_host_core(h, records, n, features, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
-}
-
-int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
-                                               const uint16_t* d_rows, const nfagg_netev_table* table,
-                                               const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
-                                               uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
-    const NetevArgs ne{d_rows, table};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
-}
-
-int nfagg_encode_flp_json_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
-                                        const uint16_t* rows, const nfagg_netev_table* table,
-                                        const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
-                                        uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
-    const NetevArgs ne{rows, table};
-    return encode_flp_host_core(h, records, n, features, &ne, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
-}
-
-}  // extern "C"
-
-// ---- network events: the cookie table and the resolve kernel (nfagg_netev.hip)
-namespace {
-
-struct NetevStr { const char* p; uint32_t len; };
-// networkevents.ToMap (network_events.go:38-52), keys in byte order. Returns the number of pairs, 0 for an undecodable entry.
-int netev_pairs(const nfagg_netev_entry& e, const char* (&keys)[6], NetevStr (&vals)[6]) {
-    if (e.kind == NFAGG_NETEV_ACL) {
-        static const char* const k[6] = {"Action", "Direction", "Feature", "Name", "Namespace", "Type"};
-        const NetevStr v[6] = {{e.action, e.action_len}, {e.direction, e.direction_len}, {"acl", 3}, {e.name, e.name_len},
-                               {e.namespace_, e.namespace_len}, {e.actor, e.actor_len}};
-        for (int q = 0; q < 6; q++) { keys[q] = k[q]; vals[q] = v[q]; }
-        return 6;
-    }
-    if (e.kind == NFAGG_NETEV_OTHER) { keys[0] = "Message"; vals[0] = {e.string, e.string_len}; return 1; }
-    return 0;
-}
-
-bool netev_strings_ok(const nfagg_netev_entry& e) {
-    const NetevStr v[6] = {{e.action, e.action_len}, {e.actor, e.actor_len}, {e.name, e.name_len}, {e.namespace_, e.namespace_len},
-                           {e.direction, e.direction_len}, {e.string, e.string_len}};
-    for (int q = e.kind == NFAGG_NETEV_ACL ? 0 : 5; q < 6; q++)
-        if (v[q].len && !v[q].p) return false;
-    return true;
-}
-
-void put_varint_host(std::vector<uint8_t>& o, uint64_t v) {
-    while (v >= 0x80) { o.push_back((uint8_t)(v | 0x80)); v >>= 7; }
-    o.push_back((uint8_t)v);
-}
-
-// The rendered bytes of one entry. false: an undecodable entry, or a string so long that the rendering cannot fit the cap
-// (checked before anything of that size is built).
-bool netev_render(const nfagg_netev_entry& e, int format, std::vector<uint8_t>& o) {
-    const char* keys[6]; NetevStr vals[6];
-    const int np = netev_pairs(e, keys, vals);
-    o.clear();
-    if (!np) return false;
-    for (int q = 0; q < np; q++) if (vals[q].len > kNetevMaxRendered) return false;
-    if (format == NFAGG_NETEV_JSON) {
-        uint8_t buf[2 + 6 * kNetevMaxRendered];
-        o.push_back('{');
-        for (int q = 0; q < np; q++) {
-            if (q) o.push_back(',');
-            o.push_back('"'); o.insert(o.end(), keys[q], keys[q] + strlen(keys[q])); o.push_back('"'); o.push_back(':');
-            const uint32_t n = flp_escape(vals[q].p, vals[q].len, buf);
-            o.insert(o.end(), buf, buf + n);
-        }
-        o.push_back('}');
-    } else {
-        for (int q = 0; q < np; q++) {                       // map entry: key = 1, value = 2, both written even when empty
-            const size_t kl = strlen(keys[q]);
-            std::vector<uint8_t> ent;
-            ent.push_back(0x0A); put_varint_host(ent, kl); ent.insert(ent.end(), keys[q], keys[q] + kl);
-            ent.push_back(0x12); put_varint_host(ent, vals[q].len); ent.insert(ent.end(), vals[q].p, vals[q].p + vals[q].len);
-            o.push_back(0x0A); put_varint_host(o, ent.size()); o.insert(o.end(), ent.begin(), ent.end());
-        }
-    }
-    return true;
-}
-
-uint32_t netev_cause(const nfagg_netev_entry& e) {          // networkevents.ToDropReasonCode (network_events.go:121-131)
-    static const char* const causes[10] = {"Unknown", "EgressFirewall", "AdminNetworkPolicy", "BaselineAdminNetworkPolicy", "NetworkPolicy",
-                                           "MulticastNS", "MulticastCluster", "NetpolNode", "NetpolNamespace", "UDNIsolation"};
-    if (e.kind != NFAGG_NETEV_ACL || e.action_len != 4 || memcmp(e.action, "drop", 4) != 0) return 0;
-    for (uint32_t q = 0; q < 10; q++)
-        if (strlen(causes[q]) == e.actor_len && memcmp(causes[q], e.actor, e.actor_len) == 0) return (1u << 24) + q;
-    return 1u << 24;
-}
-
-uint64_t netev_cookie(const uint8_t* c) { uint64_t v; memcpy(&v, c, 8); return v; }
-
-}  // namespace
-
-extern "C" {
-
-int nfagg_netev_render(const nfagg_netev_entry* entry, int format, void* out, size_t cap, size_t* n_out) {
-    if (!entry || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
-    if (format != NFAGG_NETEV_JSON && format != NFAGG_NETEV_PB) return fail(nullptr, NFAGG_EINVAL, "unknown format %d", format);
-    if (entry->kind > NFAGG_NETEV_UNDECODABLE || !netev_strings_ok(*entry)) return fail(nullptr, NFAGG_EINVAL, "bad network-events entry");
-    std::vector<uint8_t> o;
-    if (!netev_render(*entry, format, o)) {
-        if (entry->kind == NFAGG_NETEV_UNDECODABLE) return fail(nullptr, NFAGG_EINVAL, "an undecodable entry renders to nothing");
-        return fail(nullptr, NFAGG_EINVAL, "rendered event exceeds %u bytes", kNetevMaxRendered);
-    }
-    if (o.size() > kNetevMaxRendered) return fail(nullptr, NFAGG_EINVAL, "rendered event has %zu bytes, more than %u", o.size(), kNetevMaxRendered);
-    *n_out = o.size();
-    if (!out || cap < o.size()) return NFAGG_TRUNCATED;
-    memcpy(out, o.data(), o.size());
-    return NFAGG_OK;
-}
-
-int nfagg_netev_table_create(nfagg_handle* h, const nfagg_netev_entry* entries, size_t n, nfagg_netev_table** table) {
-    if (!table || (n && !entries)) return fail(h, NFAGG_EINVAL, "null argument");
-    *table = nullptr;
-    if (n > NFAGG_NETEV_MAX_ROWS) return fail(h, NFAGG_EINVAL, "%zu network-events entries, more than %d", n, NFAGG_NETEV_MAX_ROWS);
-    std::vector<uint32_t> order(n);
-    for (size_t k = 0; k < n; k++) {
-        order[k] = (uint32_t)k;
-        if (entries[k].kind > NFAGG_NETEV_UNDECODABLE) return fail(h, NFAGG_EINVAL, "network-events entry %zu: unknown kind %u", k, entries[k].kind);
-        if (!netev_strings_ok(entries[k])) return fail(h, NFAGG_EINVAL, "network-events entry %zu: null string with a length", k);
-    }
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return netev_cookie(entries[a].cookie) < netev_cookie(entries[b].cookie); });
-    for (size_t r = 1; r < n; r++)
-        if (netev_cookie(entries[order[r]].cookie) == netev_cookie(entries[order[r - 1]].cookie))
-            return fail(h, NFAGG_EINVAL, "network-events entries %u and %u carry the same cookie", std::min(order[r - 1], order[r]), std::max(order[r - 1], order[r]));
-    nfagg_netev_table* t = new (std::nothrow) nfagg_netev_table;
-    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
-    t->h = h;
-    t->rows.resize(n);
-    std::vector<uint8_t> piece;
-    for (size_t r = 0; r < n; r++) {
-        const nfagg_netev_entry& e = entries[order[r]];
-        NetevRow& row = t->rows[r];
-        row = NetevRow{};
-        row.cookie = netev_cookie(e.cookie);
-        row.kind = (uint16_t)e.kind;
-        row.cls = (uint16_t)kNetevNoRow;
-        if (e.kind == NFAGG_NETEV_UNDECODABLE) continue;
-        row.cause = netev_cause(e);
-        row.cls = (uint16_t)r;                                      // the first row with the same String() bytes
-        for (size_t q = 0; q < r; q++) {
-            const nfagg_netev_entry& f = entries[order[q]];
-            if (f.kind != NFAGG_NETEV_UNDECODABLE && f.string_len == e.string_len && (e.string_len == 0 || memcmp(f.string, e.string, e.string_len) == 0)) {
-                row.cls = (uint16_t)q;
-                break;
-            }
-        }
-        for (int format : {NFAGG_NETEV_JSON, NFAGG_NETEV_PB}) {
-            if (!netev_render(e, format, piece) || piece.size() > kNetevMaxRendered) {
-                const size_t got = piece.size();
-                delete t;
-                return fail(h, NFAGG_EINVAL, "network-events entry %u: its %s rendering has %s%zu bytes, the cap is %u", order[r],
-                            format == NFAGG_NETEV_JSON ? "JSON" : "protobuf", got ? "" : "more than ", got ? got : (size_t)kNetevMaxRendered, kNetevMaxRendered);
-            }
-            const uint32_t off = (uint32_t)t->blob.size();
-            t->blob.insert(t->blob.end(), piece.begin(), piece.end());
-            t->blob.resize((t->blob.size() + 15) / 16 * 16, 0);      // the kernels read a piece 16 bytes at a time
-            if (format == NFAGG_NETEV_JSON) { row.json_off = off; row.json_len = (uint16_t)piece.size(); }
-            else { row.pb_off = off; row.pb_len = (uint16_t)piece.size(); }
-        }
-    }
-    if (h) {
-        auto up = [&]() -> int {
-            HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_rows, std::max<size_t>(n, 1) * sizeof(NetevRow)));
-            HIP_TRY(h, hipMalloc(&t->d_blob, std::max<size_t>(t->blob.size(), 16)));
-            if (n) HIP_TRY(h, hipMemcpy(t->d_rows, t->rows.data(), n * sizeof(NetevRow), hipMemcpyHostToDevice));
-            if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
-            return NFAGG_OK;
-        };
-        const int rc = up();
-        if (rc != NFAGG_OK) { nfagg_netev_table_destroy(t); return rc; }
-    }
-    *table = t;
-    return NFAGG_OK;
-}
-
-void nfagg_netev_table_destroy(nfagg_netev_table* t) {
-    if (!t) return;
-    if (t->h && (t->d_rows || t->d_blob)) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        if (t->d_rows) (void)hipFree(t->d_rows);
-        if (t->d_blob) (void)hipFree(t->d_blob);
-    }
-    delete t;
-}
-
-int nfagg_netev_resolve_device(nfagg_handle* h, const nfagg_netev_table* table, const uint8_t* d_present,
-                               const nfagg_network_events_metrics* d_network_events, const nfagg_pkt_drop_metrics* d_drops, size_t n,
-                               uint8_t* d_present_out, nfagg_pkt_drop_metrics* d_drops_out, uint16_t* d_rows_out,
-                               uint64_t* d_missing_set, size_t missing_cap, size_t* n_missing, int* zero_missing, int* overflow) {
-    if (!h || !table || !n_missing || !zero_missing || !overflow || (missing_cap && !d_missing_set) ||
-        (n && (!d_present || !d_present_out || !d_drops_out || !d_rows_out)))
-        return fail(h, NFAGG_EINVAL, "null argument");
-    if (table->h != h || !table->d_rows) return fail(h, NFAGG_EINVAL, "the network-events table was not created for this handle");
-    if ((((uintptr_t)d_network_events | (uintptr_t)d_drops | (uintptr_t)d_drops_out | (uintptr_t)d_rows_out | (uintptr_t)d_missing_set) & 7u) != 0)
-        return fail(h, NFAGG_EINVAL, "device arrays must be 8-byte aligned");
-    if (missing_cap > 0xffffffffull) return fail(h, NFAGG_EINVAL, "missing_cap too large");
-    *n_missing = 0; *zero_missing = 0; *overflow = 0;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_buf(h, h->enc.ne_info, 16);
-    if (rc != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->enc.ne_info.p, 0, 16, h->stream));
-    if (missing_cap) HIP_TRY(h, hipMemsetAsync(d_missing_set, 0, missing_cap * sizeof(uint64_t), h->stream));
-    if (n) {
-        hipError_t e = launch_netev_resolve(d_present, (const uint8_t*)d_network_events, (const uint8_t*)d_drops, n, (const NetevRow*)table->d_rows,
-                                            (uint32_t)table->rows.size(), d_present_out, (uint8_t*)d_drops_out, d_rows_out, d_missing_set,
-                                            (uint32_t)missing_cap, (uint32_t*)h->enc.ne_info.p, h->stream);
-        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "network-events resolve launch failed: %s", hipGetErrorString(e));
-    }
-    uint32_t info[4] = {};
-    HIP_TRY(h, hipMemcpyAsync(info, h->enc.ne_info.p, sizeof info, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *n_missing = info[0]; *overflow = info[1] ? 1 : 0; *zero_missing = info[2] ? 1 : 0;
-    return NFAGG_OK;
-}
-
-int nfagg_netev_resolve(nfagg_handle* h, const nfagg_netev_table* table, const uint8_t* present,
-                        const nfagg_network_events_metrics* network_events, const nfagg_pkt_drop_metrics* drops, size_t n,
-                        uint8_t* present_out, nfagg_pkt_drop_metrics* drops_out, uint16_t* rows_out,
-                        uint8_t (*missing)[8], size_t missing_cap, size_t* n_missing, int* overflow) {
-    if (!h || !table || !n_missing || !overflow || (missing_cap && !missing) || (n && (!present || !present_out || !drops_out || !rows_out)))
-        return fail(h, NFAGG_EINVAL, "null argument");
-    auto& S = h->enc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const void* src[3] = {present, network_events, drops};
-    const size_t elem[3] = {1, sizeof(nfagg_network_events_metrics), sizeof(nfagg_pkt_drop_metrics)}, out_elem[3] = {1, sizeof(nfagg_pkt_drop_metrics), 8};
-    int rc;
-    for (int k = 0; k < 3; k++) {
-        if ((rc = ensure_buf(h, S.ne_out[k], n * out_elem[k] + 16)) != NFAGG_OK) return rc;
-        if (!src[k] || !n) continue;
-        if ((rc = ensure_buf(h, S.ne_in[k], n * elem[k] + 16)) != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(S.ne_in[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
-    }
-    if ((rc = ensure_buf(h, S.ne_missing, missing_cap * sizeof(uint64_t) + 16)) != NFAGG_OK) return rc;
-    size_t stored = 0; int zero = 0;
-    rc = nfagg_netev_resolve_device(h, table, (const uint8_t*)S.ne_in[0].p, network_events ? (const nfagg_network_events_metrics*)S.ne_in[1].p : nullptr,
-                                    drops ? (const nfagg_pkt_drop_metrics*)S.ne_in[2].p : nullptr, n, (uint8_t*)S.ne_out[0].p,
-                                    (nfagg_pkt_drop_metrics*)S.ne_out[1].p, (uint16_t*)S.ne_out[2].p, missing_cap ? (uint64_t*)S.ne_missing.p : nullptr,
-                                    missing_cap, &stored, &zero, overflow);
-    if (rc != NFAGG_OK) return rc;
-    void* dst[3] = {present_out, drops_out, rows_out};
-    for (int k = 0; k < 3; k++)
-        if (n) HIP_TRY(h, hipMemcpyAsync(dst[k], S.ne_out[k].p, n * out_elem[k], hipMemcpyDeviceToHost, h->stream));
-    std::vector<uint64_t> set(missing_cap);
-    if (missing_cap) HIP_TRY(h, hipMemcpyAsync(set.data(), S.ne_missing.p, missing_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    size_t m = 0;
-    for (uint64_t v : set) if (v) memcpy(missing[m++], &v, 8);
-    if (zero) { if (m < missing_cap) memset(missing[m++], 0, 8); else *overflow = 1; }    // the all-zero cookie takes a place of the list like any other
-    *n_missing = m;
-    return NFAGG_OK;
-}
-
-}  // extern "C"
-
-// ---- TLS names: the caller's table (nfagg_tls.h) and the direct-FLP entry points that write the three keys
-extern "C" {
-
-int nfagg_tls_names_create(nfagg_handle* h, const nfagg_tls_name_entry* entries, size_t n, nfagg_tls_names** table) {
-    if (!table || (n && !entries)) return fail(h, NFAGG_EINVAL, "null argument");
-    *table = nullptr;
-    size_t count[kTlsKinds] = {};
-    std::vector<uint32_t> order(n);
-    for (size_t k = 0; k < n; k++) {
-        const nfagg_tls_name_entry& e = entries[k];
-        order[k] = (uint32_t)k;
-        if (e.kind >= kTlsKinds) return fail(h, NFAGG_EINVAL, "TLS name entry %zu: unknown kind %u", k, (unsigned)e.kind);
-        if (e.name_len == 0 || !e.name) return fail(h, NFAGG_EINVAL, "TLS name entry %zu: empty name", k);
-        if (e.name_len > NFAGG_TLS_NAME_MAX) return fail(h, NFAGG_EINVAL, "TLS name entry %zu: a name of %u bytes, the cap is %d", k, e.name_len, NFAGG_TLS_NAME_MAX);
-        for (uint32_t b = 0; b < e.name_len; b++) {
-            const uint8_t c = (uint8_t)e.name[b];
-            if (c < 0x20 || c == '"' || c == '\\') return fail(h, NFAGG_EINVAL, "TLS name entry %zu: byte 0x%02x at %u would need escaping", k, c, b);
-        }
-        if (++count[e.kind] > kTlsMaxRows) return fail(h, NFAGG_EINVAL, "TLS name entry %zu: more than %u rows of kind %u", k, kTlsMaxRows, (unsigned)e.kind);
-    }
-    auto key = [&](uint32_t k) { return ((uint32_t)entries[k].kind << 16) | entries[k].id; };
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) != key(b) ? key(a) < key(b) : a < b; });
-    for (size_t r = 1; r < n; r++)
-        if (key(order[r]) == key(order[r - 1]))
-            return fail(h, NFAGG_EINVAL, "TLS name entries %u and %u carry the same kind %u and id 0x%04x", order[r - 1], order[r],
-                        (unsigned)entries[order[r]].kind, (unsigned)entries[order[r]].id);
-    nfagg_tls_names* t = new (std::nothrow) nfagg_tls_names;
-    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
-    t->h = h;
-    for (size_t r = 0; r < n; r++) {
-        const nfagg_tls_name_entry& e = entries[order[r]];
-        const size_t slot = (size_t)e.kind * kTlsMaxRows + t->n[e.kind]++;
-        t->ids[slot] = e.id;
-        uint8_t* row = t->rows.data() + slot * kTlsRowBytes;
-        row[0] = (uint8_t)e.name_len;
-        memcpy(row + 1, e.name, e.name_len);
-    }
-    if (h) {
-        const size_t id_bytes = t->ids.size() * sizeof(uint16_t);
-        static_assert(kTlsKinds * kTlsMaxRows * sizeof(uint16_t) % 16 == 0, "the rows start 16-byte aligned");
-        auto up = [&]() -> int {
-            HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_mem, id_bytes + t->rows.size()));
-            HIP_TRY(h, hipMemcpy(t->d_mem, t->ids.data(), id_bytes, hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy((uint8_t*)t->d_mem + id_bytes, t->rows.data(), t->rows.size(), hipMemcpyHostToDevice));
-            return NFAGG_OK;
-        };
-        const int rc = up();
-        if (rc != NFAGG_OK) { nfagg_tls_names_destroy(t); return rc; }
-    }
-    *table = t;
-    return NFAGG_OK;
-}
-
-void nfagg_tls_names_destroy(nfagg_tls_names* t) {
-    if (!t) return;
-    if (t->h && t->d_mem) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        (void)hipFree(t->d_mem);
-    }
-    delete t;
-}
-
-int nfagg_tls_names_render(const nfagg_tls_names* t, int kind, uint16_t id, int mismatch, void* out, size_t cap, size_t* n_out) {
-    if (!t || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
-    if (kind < 0 || kind >= (int)kTlsKinds) return fail(nullptr, NFAGG_EINVAL, "unknown kind %d", kind);
-    char buf[2 + NFAGG_TLS_NAME_MAX + 1];
-    size_t len = 0;
-    if (kind == NFAGG_TLS_VERSION && mismatch) { buf[0] = '~'; buf[1] = ' '; len = 2; }
-    const uint16_t* ids = t->ids.data() + (size_t)kind * kTlsMaxRows;
-    const uint16_t* hit = std::lower_bound(ids, ids + t->n[kind], id);
-    if (hit != ids + t->n[kind] && *hit == id) {
-        const uint8_t* row = t->rows.data() + ((size_t)kind * kTlsMaxRows + (size_t)(hit - ids)) * kTlsRowBytes;
-        memcpy(buf + len, row + 1, row[0]);
-        len += row[0];
-    } else {
-        len += (size_t)snprintf(buf + len, sizeof buf - len, kind == NFAGG_TLS_GROUP ? "CurveID(%u)" : "0x%04X", (unsigned)id);
-    }
-    *n_out = len;
-    if (!out || cap < len) return NFAGG_TRUNCATED;
-    memcpy(out, buf, len);
-    return NFAGG_OK;
-}
-
-uint32_t nfagg_flp_json_tls_max_line(int policy) { return flp_tls_max_line(policy); }
-
-int nfagg_encode_flp_json_tls_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
-                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
-                                     const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
-    const NetevArgs ne{d_rows, netev_table};
-    const FlpTlsArgs tls{tls_names};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
-}
-
-int nfagg_encode_flp_json_tls(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
-                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
-                              const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
-    const NetevArgs ne{rows, netev_table};
-    const FlpTlsArgs tls{tls_names};
-    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
-}
-
-}  // extern "C"
-
-// ---- Kubernetes enrichment: the caller's table (nfagg_k8s.h), the hash join alone, and the direct-FLP entry points with the keys
-namespace {
-
-struct K8sStr { const char* p; uint32_t len; };
-
-// One side's block. false: a null string with a length (*bad_string), or a value so long that the block cannot fit the cap
-// (checked before anything of that size is built).
-bool k8s_render(const nfagg_k8s_entry& e, int side, std::vector<uint8_t>& o, bool* bad_string) {
-    // enrich.go:51-87 in the byte order of the keys (transform_network.go:153-162)
-    const bool host_ip = e.host_ip_len != 0;
-    const struct { const char* key; K8sStr v; bool on; } kv[9] = {
-        {"HostIP", {e.host_ip, e.host_ip_len}, host_ip}, {"HostName", {e.host_name, e.host_name_len}, host_ip && e.host_name_len != 0},
-        {"Name", {e.name, e.name_len}, true}, {"Namespace", {e.namespace_, e.namespace_len}, e.namespace_len != 0},
-        {"NetworkName", {e.network_name, e.network_name_len}, true}, {"OwnerName", {e.owner_name, e.owner_name_len}, true},
-        {"OwnerType", {e.owner_kind, e.owner_kind_len}, true}, {"Type", {e.kind, e.kind_len}, true},
-        {"Zone", {e.zone, e.has_zone ? e.zone_len : 0u}, e.has_zone != 0}};
-    o.clear();
-    *bad_string = false;
-    for (const auto& q : kv) if (q.v.len && !q.v.p) { *bad_string = true; return false; }
-    for (const auto& q : kv) if (q.on && q.v.len > kK8sMaxRendered) return false;
-    uint8_t buf[2 + 6 * kK8sMaxRendered];
-    for (const auto& q : kv) {
-        if (!q.on) continue;
-        const char* head = side ? ",\"DstK8S_" : ",\"SrcK8S_";
-        o.insert(o.end(), head, head + 9);
-        o.insert(o.end(), q.key, q.key + strlen(q.key));
-        o.push_back('"'); o.push_back(':');
-        const uint32_t n = flp_escape(q.v.p, q.v.len, buf);
-        o.insert(o.end(), buf, buf + n);
-    }
-    return true;
-}
-
-// enrich.go:143-165 for one row: EnrichLayer asks only about a side whose namespace is not empty
-bool k8s_is_app(const nfagg_k8s_entry& e, const nfagg_k8s_layer& l) {
-    if (!e.namespace_len) return false;
-    for (uint32_t k = 0; k < l.n_prefixes; k++) {
-        const size_t pl = strlen(l.infra_prefixes[k]);
-        if (pl <= e.namespace_len && memcmp(e.namespace_, l.infra_prefixes[k], pl) == 0) return false;
-    }
-    for (uint32_t k = 0; k < l.n_refs; k++) {
-        const char *ns = l.infra_refs[2 * k], *nm = l.infra_refs[2 * k + 1];
-        if (strlen(ns) == e.namespace_len && memcmp(ns, e.namespace_, e.namespace_len) == 0 && strlen(nm) == e.name_len &&
-            (e.name_len == 0 || memcmp(nm, e.name, e.name_len) == 0))
-            return false;
-    }
-    return true;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nfagg_k8s_render(const nfagg_k8s_entry* entry, int side, void* out, size_t cap, size_t* n_out) {
-    if (!entry || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
-    if (side != 0 && side != 1) return fail(nullptr, NFAGG_EINVAL, "unknown side %d", side);
-    std::vector<uint8_t> o;
-    bool bad_string;
-    if (!k8s_render(*entry, side, o, &bad_string))
-        return bad_string ? fail(nullptr, NFAGG_EINVAL, "null string with a length") : fail(nullptr, NFAGG_EINVAL, "rendered block exceeds %u bytes", kK8sMaxRendered);
-    if (o.size() > kK8sMaxRendered) return fail(nullptr, NFAGG_EINVAL, "rendered block has %zu bytes, more than %u", o.size(), kK8sMaxRendered);
-    *n_out = o.size();
-    if (!out || cap < o.size()) return NFAGG_TRUNCATED;
-    memcpy(out, o.data(), o.size());
-    return NFAGG_OK;
-}
-
-int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size_t n, const nfagg_k8s_layer* layer, nfagg_k8s_table** table) {
-    if (!table || (n && !entries)) return fail(h, NFAGG_EINVAL, "null argument");
-    *table = nullptr;
-    if (layer) {
-        if (layer->struct_size != sizeof(nfagg_k8s_layer)) return fail(h, NFAGG_EINVAL, "nfagg_k8s_layer.struct_size mismatch");
-        if ((layer->n_prefixes && !layer->infra_prefixes) || (layer->n_refs && !layer->infra_refs)) return fail(h, NFAGG_EINVAL, "null layer list with a count");
-        for (uint32_t k = 0; k < layer->n_prefixes; k++) if (!layer->infra_prefixes[k]) return fail(h, NFAGG_EINVAL, "layer prefix %u is null", k);
-        for (uint32_t k = 0; k < 2 * layer->n_refs; k++) if (!layer->infra_refs[k]) return fail(h, NFAGG_EINVAL, "layer ref %u is null", k / 2);
-    }
-    if (n > NFAGG_K8S_MAX_ROWS) return fail(h, NFAGG_EINVAL, "%zu Kubernetes entries, more than %u", n, NFAGG_K8S_MAX_ROWS);
-    nfagg_k8s_table* t = new (std::nothrow) nfagg_k8s_table;
-    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
-    t->h = h;
-    t->has_layer = layer != nullptr;
-    size_t cap = 1;
-    while (cap < 2 * n) cap <<= 1;                                       // at most half full: a probe always meets a free slot
-    K8sSlot free_slot{};
-    free_slot.row = kK8sNoRow;
-    t->slots.assign(cap, free_slot);
-    t->rows.resize(n);
-    t->host_ids.assign(n, 0u);
-    std::vector<uint8_t> piece;
-    for (size_t r = 0; r < n; r++) {
-        const nfagg_k8s_entry& e = entries[r];
-        K8sSlot key{};
-        memcpy(key.ip, e.ip, 16);
-        uint64_t lo, hi;
-        memcpy(&lo, e.ip, 8); memcpy(&hi, e.ip + 8, 8);
-        size_t s = (size_t)((uint32_t)k8s_hash(lo, hi) & (uint32_t)(cap - 1));
-        while (t->slots[s].row != kK8sNoRow) {
-            if (memcmp(t->slots[s].ip, key.ip, 16) == 0) {
-                const uint32_t first = t->slots[s].row;
-                delete t;
-                return fail(h, NFAGG_EINVAL, "Kubernetes entries %u and %zu carry the same address", first, r);
-            }
-            s = (s + 1) & (cap - 1);
-        }
-        key.row = (uint32_t)r;
-        t->slots[s] = key;
-        K8sRow& row = t->rows[r];
-        row = K8sRow{};
-        for (int side = 0; side < 2; side++) {
-            bool bad_string;
-            if (!k8s_render(e, side, piece, &bad_string) || piece.size() > kK8sMaxRendered) {
-                const size_t got = piece.size();
-                delete t;
-                if (bad_string) return fail(h, NFAGG_EINVAL, "Kubernetes entry %zu: null string with a length", r);
-                return fail(h, NFAGG_EINVAL, "Kubernetes entry %zu: its %s block has %s%zu bytes, the cap is %u", r, side ? "DstK8S" : "SrcK8S",
-                            got ? "" : "more than ", got ? got : (size_t)kK8sMaxRendered, kK8sMaxRendered);
-            }
-            const uint32_t off = (uint32_t)(t->blob.size() / 16);
-            t->blob.insert(t->blob.end(), piece.begin(), piece.end());
-            t->blob.resize((t->blob.size() + 15) / 16 * 16, 0);          // the kernels read a block 16 bytes at a time
-            if (side == 0) { row.src_off = off; row.src_len = (uint16_t)piece.size(); }
-            else { row.dst_off = off; row.dst_len = (uint16_t)piece.size(); }
-        }
-        row.flags = layer && k8s_is_app(e, *layer) ? kK8sRowApp : 0u;
-        // the text of the row's SrcK8S_HostIP / DstK8S_HostIP key, as reinterpret_direction compares it; the key is absent for ""
-        t->host_ids[r] = e.host_ip_len ? t->host_text.emplace(std::string(e.host_ip, e.host_ip_len), (uint32_t)t->host_text.size() + 1).first->second : 0u;
-        const K8sStr field[9] = {{e.namespace_, e.namespace_len}, {e.name, e.name_len}, {e.kind, e.kind_len}, {e.owner_name, e.owner_name_len},
-                                 {e.owner_kind, e.owner_kind_len}, {e.network_name, e.network_name_len}, {e.host_ip, e.host_ip_len},
-                                 {e.host_name, e.host_name_len}, {e.zone, e.zone_len}};
-        const bool present[9] = {e.namespace_len != 0, true, true, true, true, true, e.host_ip_len != 0, e.host_ip_len != 0 && e.host_name_len != 0,
-                                 e.has_zone != 0};
-        for (int f = 0; f < 9; f++)                                      // k8s_render has refused a null string with a length
-            t->field_ids.push_back(present[f] ? 1u + t->field_text.emplace(std::string(field[f].p ? field[f].p : "", field[f].len),
-                                                                           (uint32_t)t->field_text.size()).first->second : 0u);
-    }
-    if (h) {
-        auto up = [&]() -> int {
-            HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_slots, cap * sizeof(K8sSlot)));
-            HIP_TRY(h, hipMalloc(&t->d_rows, std::max<size_t>(n, 1) * sizeof(K8sRow)));
-            HIP_TRY(h, hipMalloc(&t->d_blob, std::max<size_t>(t->blob.size(), 16)));
-            HIP_TRY(h, hipMalloc(&t->d_host_ids, std::max<size_t>(n, 1) * sizeof(uint32_t)));
-            if (n) HIP_TRY(h, hipMemcpy(t->d_host_ids, t->host_ids.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy(t->d_slots, t->slots.data(), cap * sizeof(K8sSlot), hipMemcpyHostToDevice));
-            if (n) HIP_TRY(h, hipMemcpy(t->d_rows, t->rows.data(), n * sizeof(K8sRow), hipMemcpyHostToDevice));
-            if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
-            return NFAGG_OK;
-        };
-        const int rc = up();
-        if (rc != NFAGG_OK) { nfagg_k8s_table_destroy(t); return rc; }
-    }
-    *table = t;
-    return NFAGG_OK;
-}
-
-void nfagg_k8s_table_destroy(nfagg_k8s_table* t) {
-    if (!t) return;
-    if (t->h && (t->d_slots || t->d_rows || t->d_blob || t->d_host_ids)) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        if (t->d_slots) (void)hipFree(t->d_slots);
-        if (t->d_rows) (void)hipFree(t->d_rows);
-        if (t->d_blob) (void)hipFree(t->d_blob);
-        if (t->d_host_ids) (void)hipFree(t->d_host_ids);
-    }
-    delete t;
-}
-
-int nfagg_k8s_resolve_device(nfagg_handle* h, const nfagg_k8s_table* table, const void* d_records, size_t n, uint32_t* d_rows) {
-    if (!h || !table || (n && (!d_records || !d_rows))) return fail(h, NFAGG_EINVAL, "null argument");
-    if (table->h != h || !table->d_slots) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
-    if (((uintptr_t)d_records & 15u) != 0 || ((uintptr_t)d_rows & 7u) != 0) return fail(h, NFAGG_EINVAL, "device records must be 16-byte, rows 8-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (n) {
-        hipError_t e = launch_k8s_resolve(d_records, n, k8s_dev(table), d_rows, h->stream);
-        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-int nfagg_k8s_resolve(nfagg_handle* h, const nfagg_k8s_table* table, const void* records, size_t n, uint32_t* rows) {
-    if (!h || !table || (n && (!records || !rows))) return fail(h, NFAGG_EINVAL, "null argument");
-    auto& S = h->enc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = nfagg_k8s_resolve_device(h, table, S.in_records.p, n, (uint32_t*)S.k8s_rows.p)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(rows, S.k8s_rows.p, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-uint32_t nfagg_flp_json_k8s_max_line(int policy) { return flp_k8s_max_line(policy); }
-
-int nfagg_encode_flp_json_k8s_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
-                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
-                                     const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* d_out, size_t out_cap,
-                                     uint64_t* d_line_offsets, size_t* out_bytes) {
-    const NetevArgs ne{d_rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
-}
-
-int nfagg_encode_flp_json_k8s(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
-                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
-                              const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* out, size_t out_cap,
-                              uint64_t* line_offsets, size_t* out_bytes) {
-    const NetevArgs ne{rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table};
-    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
-}
-
-}  // extern "C"
-
-// ---- direction, subnet labels, TCP flag names (nfagg_net.h): the caller's rules as a table, the join alone, the entry points
-namespace {
-
-// One label's fragment, ,"SrcSubnetLabel":"<escaped>" or ,"DstSubnetLabel":"<escaped>"; empty for an empty label.
-void net_render(const char* text, uint32_t len, int side, std::vector<uint8_t>& o) {
-    o.clear();
-    if (!len) return;
-    const char* head = side ? ",\"DstSubnetLabel\":" : ",\"SrcSubnetLabel\":";
-    o.insert(o.end(), head, head + 18);
-    std::vector<uint8_t> buf(2 + 6 * (size_t)len);
-    const uint32_t n = flp_escape(text, len, buf.data());
-    o.insert(o.end(), buf.begin(), buf.begin() + n);
-}
-
-// net.CIDRMask(ones, 128) as four little-endian dwords of the 16 bytes
-void net_mask128(uint32_t ones, uint8_t m[16]) {
-    for (uint32_t k = 0; k < 16; k++) m[k] = ones >= 8 * (k + 1) ? 0xffu : ones > 8 * k ? (uint8_t)(0xff00u >> (ones - 8 * k)) : 0u;
-}
-
-}  // namespace
-
-extern "C" {
-
-int nfagg_net_table_create(nfagg_handle* h, const nfagg_net_rules* rules, nfagg_net_table** table) {
-    if (!table || !rules) return fail(h, NFAGG_EINVAL, "null argument");
-    *table = nullptr;
-    if (rules->struct_size != sizeof(nfagg_net_rules)) return fail(h, NFAGG_EINVAL, "nfagg_net_rules.struct_size mismatch");
-    const uint32_t known = NFAGG_NET_REINTERPRET_DIRECTION | NFAGG_NET_SUBNET_LABELS | NFAGG_NET_DECODE_TCP_FLAGS;
-    if (rules->flags & ~known) return fail(h, NFAGG_EINVAL, "unknown net rule flags 0x%x", rules->flags & ~known);
-    if ((rules->n_cidrs && !rules->cidrs) || (rules->n_labels && !rules->labels)) return fail(h, NFAGG_EINVAL, "null list with a count");
-    if (rules->n_cidrs > NFAGG_NET_MAX_CIDRS) return fail(h, NFAGG_EINVAL, "%u CIDRs, more than %u", rules->n_cidrs, (unsigned)NFAGG_NET_MAX_CIDRS);
-    if (rules->n_labels > NFAGG_NET_MAX_CIDRS) return fail(h, NFAGG_EINVAL, "%u labels, more than %u", rules->n_labels, (unsigned)NFAGG_NET_MAX_CIDRS);
-    nfagg_net_table* t = new (std::nothrow) nfagg_net_table;
-    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
-    t->h = h;
-    t->flags = rules->flags;
-    std::vector<uint8_t> piece;
-    for (uint32_t k = 0; k < rules->n_labels; k++) {
-        const nfagg_net_label& l = rules->labels[k];
-        if (l.len && !l.text) { delete t; return fail(h, NFAGG_EINVAL, "net label %u: null string with a length", k); }
-        if (l.len > kNetLabelMax) { delete t; return fail(h, NFAGG_EINVAL, "net label %u: its escaped value has more than %u bytes", k, kNetLabelMax); }
-        NetFrag f{};
-        for (int side = 0; side < 2; side++) {
-            net_render(l.text, l.len, side, piece);
-            if (piece.size() > kNetFragMax) {
-                const size_t got = piece.size() - (kNetFragMax - kNetLabelMax);
-                delete t;
-                return fail(h, NFAGG_EINVAL, "net label %u: its escaped value has %zu bytes, the cap is %u", k, got, kNetLabelMax);
-            }
-            const uint32_t off = (uint32_t)(t->blob.size() / 16);
-            t->blob.insert(t->blob.end(), piece.begin(), piece.end());
-            t->blob.resize((t->blob.size() + 15) / 16 * 16, 0);          // the kernels read a fragment 16 bytes at a time
-            if (side == 0) { f.src_off = off; f.src_len = (uint32_t)piece.size(); }
-            else { f.dst_off = off; f.dst_len = (uint32_t)piece.size(); }
-        }
-        t->frags.push_back(f);
-    }
-    static const uint8_t v4_prefix[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xff, 0xff};
-    for (uint32_t k = 0; k < rules->n_cidrs; k++) {
-        const nfagg_net_cidr& c = rules->cidrs[k];
-        if (c.bits != 32 && c.bits != 128) { delete t; return fail(h, NFAGG_EINVAL, "CIDR %u: %u bits, neither 32 nor 128", k, c.bits); }
-        if (c.ones > c.bits) { delete t; return fail(h, NFAGG_EINVAL, "CIDR %u: a prefix of %u in %u bits", k, c.ones, c.bits); }
-        if (c.label >= rules->n_labels) { delete t; return fail(h, NFAGG_EINVAL, "CIDR %u: label %u of %u", k, c.label, rules->n_labels); }
-        if (c.bits == 32 && memcmp(c.ip, v4_prefix, 12) != 0) { delete t; return fail(h, NFAGG_EINVAL, "CIDR %u: 32 bits and an address that is not v4-mapped", k); }
-        // net.IPNet.Contains -> networkNumberAndMask: the network is IPv4 iff its masked address is v4-mapped, and then only
-        // the mask's last 32 bits count; the twelve 0xff in front make the compare refuse every address that is not v4-mapped
-        uint8_t mask[16], netw[16];
-        net_mask128(c.bits == 32 ? 96 + c.ones : c.ones, mask);
-        for (int b = 0; b < 16; b++) netw[b] = c.ip[b] & mask[b];
-        const bool v4 = memcmp(netw, v4_prefix, 12) == 0;
-        if (v4) memset(mask, 0xff, 12);
-        NetCidr d;
-        memcpy(d.net, netw, 16); memcpy(d.mask, mask, 16);
-        t->cidrs.push_back(d);
-        t->meta.push_back(c.label | (v4 ? 0u : kNetCidrV6));
-    }
-    auto up32 = [](size_t x) { return (x + 31) / 32 * 32; };
-    t->off_meta = up32(std::max<size_t>(t->cidrs.size(), 1) * sizeof(NetCidr));
-    t->off_frags = t->off_meta + up32(std::max<size_t>(t->meta.size(), 1) * sizeof(uint32_t));
-    t->off_blob = t->off_frags + up32(std::max<size_t>(t->frags.size(), 1) * sizeof(NetFrag));
-    if (h) {
-        auto up = [&]() -> int {
-            std::vector<uint8_t> img(t->off_blob + std::max<size_t>(t->blob.size(), 16), 0);
-            if (!t->cidrs.empty()) memcpy(img.data(), t->cidrs.data(), t->cidrs.size() * sizeof(NetCidr));
-            if (!t->meta.empty()) memcpy(img.data() + t->off_meta, t->meta.data(), t->meta.size() * sizeof(uint32_t));
-            if (!t->frags.empty()) memcpy(img.data() + t->off_frags, t->frags.data(), t->frags.size() * sizeof(NetFrag));
-            if (!t->blob.empty()) memcpy(img.data() + t->off_blob, t->blob.data(), t->blob.size());
-            HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_mem, img.size()));
-            HIP_TRY(h, hipMemcpy(t->d_mem, img.data(), img.size(), hipMemcpyHostToDevice));
-            return NFAGG_OK;
-        };
-        const int rc = up();
-        if (rc != NFAGG_OK) { nfagg_net_table_destroy(t); return rc; }
-    }
-    *table = t;
-    return NFAGG_OK;
-}
-
-void nfagg_net_table_destroy(nfagg_net_table* t) {
-    if (!t) return;
-    if (t->h && t->d_mem) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        (void)hipFree(t->d_mem);
-    }
-    delete t;
-}
-
-int nfagg_net_render(const nfagg_net_table* table, int side, uint32_t label, void* out, size_t cap, size_t* n_out) {
-    if (!table || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
-    if (side != 0 && side != 1) return fail(nullptr, NFAGG_EINVAL, "unknown side %d", side);
-    if (label >= table->frags.size()) return fail(nullptr, NFAGG_EINVAL, "label %u of %zu", label, table->frags.size());
-    const NetFrag& f = table->frags[label];
-    const size_t off = (size_t)(side ? f.dst_off : f.src_off) * 16, len = side ? f.dst_len : f.src_len;
-    *n_out = len;
-    if (len && (!out || cap < len)) return NFAGG_TRUNCATED;
-    if (len) memcpy(out, table->blob.data() + off, len);
-    return NFAGG_OK;
-}
-
-int nfagg_net_resolve_device(nfagg_handle* h, const nfagg_net_table* net_table, const nfagg_k8s_table* k8s_table, const void* d_records,
-                             size_t n, const uint32_t* d_k8s_rows, const nfagg_flp_options* opt, nfagg_net_row* d_out) {
-    if (!h || !net_table || (n && (!d_records || !d_out))) return fail(h, NFAGG_EINVAL, "null argument");
-    if (net_table->h != h || !net_table->d_mem) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
-    const bool dir = (net_table->flags & NFAGG_NET_REINTERPRET_DIRECTION) != 0;
-    if (dir) {
-        if (!k8s_table || !opt || (n && !d_k8s_rows)) return fail(h, NFAGG_EINVAL, "reinterpret_direction needs the Kubernetes table, the flows' rows and the options");
-        if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
-        if (k8s_table->h != h || !k8s_table->d_slots) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
-    }
-    if (((uintptr_t)d_records & 15u) != 0 || ((uintptr_t)d_out & 7u) != 0 || (dir && ((uintptr_t)d_k8s_rows & 7u) != 0))
-        return fail(h, NFAGG_EINVAL, "device records must be 16-byte, rows 8-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (n) {
-        hipError_t e = launch_net_resolve(d_records, n, net_dev(net_table), dir ? d_k8s_rows : nullptr, dir ? (const uint32_t*)k8s_table->d_host_ids : nullptr,
-                                          dir ? (uint32_t)k8s_table->rows.size() : 0u, dir ? net_reporter(k8s_table, opt) : kNetNoHost, (uint2*)d_out,
-                                          h->stream);
-        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
-    }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-int nfagg_net_resolve(nfagg_handle* h, const nfagg_net_table* net_table, const nfagg_k8s_table* k8s_table, const void* records, size_t n,
-                      const uint32_t* k8s_rows, const nfagg_flp_options* opt, nfagg_net_row* out) {
-    if (!h || !net_table || (n && (!records || !out))) return fail(h, NFAGG_EINVAL, "null argument");
-    const bool dir = (net_table->flags & NFAGG_NET_REINTERPRET_DIRECTION) != 0;
-    if (dir && n && !k8s_rows) return fail(h, NFAGG_EINVAL, "reinterpret_direction needs the Kubernetes table, the flows' rows and the options");
-    auto& S = h->enc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    if (n && dir) HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    if ((rc = nfagg_net_resolve_device(h, net_table, k8s_table, S.in_records.p, n, (const uint32_t*)S.k8s_rows.p, opt, (nfagg_net_row*)S.net_rows.p)) != NFAGG_OK)
-        return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(out, S.net_rows.p, n * sizeof(nfagg_net_row), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-uint32_t nfagg_flp_json_net_max_line(int policy) { return flp_net_max_line(policy); }
-
-int nfagg_encode_flp_json_net_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
-                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
-                                     const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
-                                     void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
-    const NetevArgs ne{d_rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
-}
-
-int nfagg_encode_flp_json_net(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
-                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
-                              const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
-                              void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
-    const NetevArgs ne{rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
-    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
-}
-
-}  // extern "C"
-
-// ---- flow metrics (nfagg_metrics.h): the groupings' classes over a Kubernetes table, and the fold's host side
-struct nfagg_metrics_table {
-    nfagg_handle* h = nullptr;
-    const nfagg_k8s_table* k8s = nullptr;              // not owned: the caller keeps it alive
-    uint32_t n_groupings = 0;
-    uint32_t dims[kMetMaxGroupings] = {};
-    std::vector<uint32_t> cls[kMetMaxGroupings][2];    // per row; empty: the grouping selects no field of that side
-    std::vector<uint32_t> first_row[kMetMaxGroupings][2];   // [class - 1] = the first row of that class
-    void* d_cls = nullptr;                             // the non-empty cls arrays one behind the other
-    size_t d_off[kMetMaxGroupings][2] = {};            // in words
-};
-
-extern "C" {
-
-int nfagg_metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const uint32_t* dims, uint32_t n_groupings,
-                               nfagg_metrics_table** table) {
-    if (!table || !k8s_table || !dims) return fail(h, NFAGG_EINVAL, "null argument");
-    *table = nullptr;
-    if (n_groupings < 1 || n_groupings > kMetMaxGroupings) return fail(h, NFAGG_EINVAL, "%u groupings, not 1..%u", n_groupings, kMetMaxGroupings);
-    for (uint32_t g = 0; g < n_groupings; g++)
-        if (dims[g] & ~NFAGG_DIM_ALL) return fail(h, NFAGG_EINVAL, "grouping %u: unknown dimension bits 0x%x", g, dims[g] & ~NFAGG_DIM_ALL);
-    if (k8s_table->h != h) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
-    nfagg_metrics_table* t = new (std::nothrow) nfagg_metrics_table;
-    if (!t) return fail(h, NFAGG_ENOMEM, "out of memory");
-    t->h = h;
-    t->k8s = k8s_table;
-    t->n_groupings = n_groupings;
-    const size_t n = k8s_table->rows.size();
-    size_t words = 0;
-    for (uint32_t g = 0; g < n_groupings; g++) {
-        t->dims[g] = dims[g];
-        for (int side = 0; side < 2; side++) {
-            const uint32_t sel = (dims[g] >> (9 * side)) & kMetSrcFields;
-            if (!sel) continue;
-            std::map<std::vector<uint32_t>, uint32_t> seen;
-            std::vector<uint32_t> key;
-            t->cls[g][side].resize(n);
-            for (size_t r = 0; r < n; r++) {
-                key.clear();
-                for (int f = 0; f < 9; f++) if (sel & (1u << f)) key.push_back(k8s_table->field_ids[r * 9 + f]);
-                const auto it = seen.emplace(key, (uint32_t)seen.size() + 1);
-                if (it.second) t->first_row[g][side].push_back((uint32_t)r);
-                t->cls[g][side][r] = it.first->second;
-            }
-            t->d_off[g][side] = words;
-            words += (n + 3) / 4 * 4;
-        }
-    }
-    if (h) {
-        auto up = [&]() -> int {
-            HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_cls, std::max<size_t>(words, 4) * sizeof(uint32_t)));
-            for (uint32_t g = 0; g < n_groupings; g++)
-                for (int side = 0; side < 2; side++)
-                    if (n && !t->cls[g][side].empty())
-                        HIP_TRY(h, hipMemcpy((uint32_t*)t->d_cls + t->d_off[g][side], t->cls[g][side].data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            return NFAGG_OK;
-        };
-        const int rc = up();
-        if (rc != NFAGG_OK) { nfagg_metrics_table_destroy(t); return rc; }
-    }
-    *table = t;
-    return NFAGG_OK;
-}
-
-void nfagg_metrics_table_destroy(nfagg_metrics_table* t) {
-    if (!t) return;
-    if (t->h && t->d_cls) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        (void)hipFree(t->d_cls);
-    }
-    delete t;
-}
-
-uint32_t nfagg_metrics_n_classes(const nfagg_metrics_table* table, uint32_t g, int side) {
-    if (!table || g >= table->n_groupings || (side != 0 && side != 1)) return 0;
-    return (uint32_t)table->first_row[g][side].size();
-}
-
-int nfagg_metrics_class_row(const nfagg_metrics_table* table, uint32_t g, int side, uint32_t cls, uint32_t* row) {
-    nfagg_handle* h = table ? table->h : nullptr;
-    if (!table || !row) return fail(h, NFAGG_EINVAL, "null argument");
-    if (g >= table->n_groupings || (side != 0 && side != 1)) return fail(h, NFAGG_EINVAL, "grouping %u, side %d: out of range", g, side);
-    if (cls > table->first_row[g][side].size()) return fail(h, NFAGG_EINVAL, "class %u of %zu", cls, table->first_row[g][side].size());
-    *row = cls ? table->first_row[g][side][cls - 1] : NFAGG_K8S_NO_ROW;
-    return NFAGG_OK;
-}
-
-int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table, const void* d_records, size_t n, const uint32_t* d_k8s_rows,
-                              const nfagg_net_row* d_net_rows, const uint32_t* group_cap, nfagg_metric_group* const* d_out, uint32_t* n_groups) {
-    if (!h || !table || !group_cap || !d_out || !n_groups || (n && (!d_records || !d_k8s_rows))) return fail(h, NFAGG_EINVAL, "null argument");
-    if (table->h != h || !table->d_cls) return fail(h, NFAGG_EINVAL, "the metrics table was not created for this handle");
-    const uint32_t G = table->n_groupings;
-    const uint32_t net_dims = NFAGG_DIM_SRC_SUBNET_LABEL | NFAGG_DIM_DST_SUBNET_LABEL | NFAGG_DIM_FLOW_DIRECTION;
-    MetDev M{};
-    M.n_groupings = G;
-    uint64_t blocks = 0;
-    for (uint32_t g = 0; g < G; g++) {
-        if (group_cap[g] > kMetMaxGroups) return fail(h, NFAGG_ERANGE, "grouping %u: a cap of %u groups, more than %u", g, group_cap[g], kMetMaxGroups);
-        if (group_cap[g] && !d_out[g]) return fail(h, NFAGG_EINVAL, "grouping %u: a cap without an output array", g);
-        if (((uintptr_t)d_out[g] & 15u) != 0) return fail(h, NFAGG_EINVAL, "device records and group arrays must be 16-byte, rows 8-byte aligned");
-        if (n && (table->dims[g] & net_dims) && !d_net_rows) return fail(h, NFAGG_EINVAL, "grouping %u selects a label or the direction: it needs the flows' net rows", g);
-        M.dims[g] = table->dims[g];
-        M.cap[g] = group_cap[g];
-        M.mask[g] = (uint32_t)std::max<uint64_t>(next_pow2(2ull * group_cap[g]), kMetMinSlots) - 1;
-        M.first_block[g] = (uint32_t)blocks;
-        blocks += ((uint64_t)M.mask[g] + 1) / kMetMinSlots;
-        M.out[g] = d_out[g];
-        if (M.dims[g] & NFAGG_DIM_FLOW_LAYER) M.any_layer = 1;
-        for (int side = 0; side < 2; side++)
-            M.cls[g][side] = table->cls[g][side].empty() ? nullptr : (const uint32_t*)table->d_cls + table->d_off[g][side];
-    }
-    M.first_block[G] = (uint32_t)blocks;
-    if (((uintptr_t)d_records & 15u) != 0 || ((uintptr_t)d_k8s_rows & 7u) != 0 || ((uintptr_t)d_net_rows & 7u) != 0)
-        return fail(h, NFAGG_EINVAL, "device records and group arrays must be 16-byte, rows 8-byte aligned");
-    for (uint32_t g = 0; g < G; g++) n_groups[g] = 0;
-    if (!n) return NFAGG_OK;
-    const K8sDev K = k8s_dev(table->k8s);
-    M.rows = K.rows; M.n_rows = K.n_rows; M.has_layer = K.has_layer;
-    auto& S = h->enc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    const size_t slot_bytes = (size_t)blocks * kMetMinSlots * kMetSlotWords * sizeof(uint64_t);
-    if ((rc = ensure_buf(h, S.met_slots, 256 + slot_bytes)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.local_off, (size_t)blocks * kMetMinSlots * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.block_sum, (size_t)blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.block_base, ((size_t)blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    M.ctl = (MetCtl*)S.met_slots.p;
-    uint64_t* slots = (uint64_t*)((uint8_t*)S.met_slots.p + 256);
-    for (uint32_t g = 0; g < G; g++) M.slots[g] = slots + (size_t)M.first_block[g] * kMetMinSlots * kMetSlotWords;
-    HIP_TRY(h, hipMemsetAsync(S.met_slots.p, 0, 256 + slot_bytes, h->stream));
-    hipError_t e = launch_metrics_fold(d_records, n, M, d_k8s_rows, (const uint2*)d_net_rows, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "metrics fold launch failed: %s", hipGetErrorString(e));
-    e = launch_metrics_emit(M, (uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "metrics emit launch failed: %s", hipGetErrorString(e));
-    MetCtl ctl;
-    HIP_TRY(h, hipMemcpyAsync(&ctl, M.ctl, sizeof ctl, hipMemcpyDeviceToHost, h->stream));      // the one read-back: counts and flags
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    bool over = false;
-    for (uint32_t g = 0; g < G; g++) {
-        // an overflowed grouping stopped claiming behind its cap: its count is a lower bound, and above the cap
-        n_groups[g] = ctl.over[g] ? std::max(ctl.count[g], group_cap[g] + 1) : ctl.count[g];
-        over = over || ctl.over[g];
-    }
-    return over ? NFAGG_TRUNCATED : NFAGG_OK;
-}
-
-int nfagg_metrics_fold(nfagg_handle* h, const nfagg_metrics_table* table, const void* records, size_t n, const uint32_t* k8s_rows,
-                       const nfagg_net_row* net_rows, const uint32_t* group_cap, nfagg_metric_group* const* out, uint32_t* n_groups) {
-    if (!h || !table || !group_cap || !out || !n_groups || (n && (!records || !k8s_rows))) return fail(h, NFAGG_EINVAL, "null argument");
-    const uint32_t G = table->n_groupings;
-    size_t total = 0;
-    for (uint32_t g = 0; g < G; g++) {
-        if (group_cap[g] > kMetMaxGroups) return fail(h, NFAGG_ERANGE, "grouping %u: a cap of %u groups, more than %u", g, group_cap[g], kMetMaxGroups);
-        if (group_cap[g] && !out[g]) return fail(h, NFAGG_EINVAL, "grouping %u: a cap without an output array", g);
-        total += group_cap[g];
-    }
-    auto& S = h->enc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.met_out, total * sizeof(nfagg_metric_group) + 16)) != NFAGG_OK) return rc;
-    if (n) {
-        HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        if (net_rows) HIP_TRY(h, hipMemcpyAsync(S.net_rows.p, net_rows, n * sizeof(nfagg_net_row), hipMemcpyHostToDevice, h->stream));
-    }
-    nfagg_metric_group* d_out[kMetMaxGroupings] = {};
-    size_t at = 0;
-    for (uint32_t g = 0; g < G; g++) { d_out[g] = (nfagg_metric_group*)S.met_out.p + at; at += group_cap[g]; }
-    rc = nfagg_metrics_fold_device(h, table, S.in_records.p, n, (const uint32_t*)S.k8s_rows.p, net_rows ? (const nfagg_net_row*)S.net_rows.p : nullptr, group_cap,
-                                   d_out, n_groups);
-    if (rc != NFAGG_OK) return rc;
-    for (uint32_t g = 0; g < G; g++)
-        if (n_groups[g]) HIP_TRY(h, hipMemcpyAsync(out[g], d_out[g], (size_t)n_groups[g] * sizeof(nfagg_metric_group), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
 }
 

@@ -1,0 +1,579 @@
+// nfagg_api_export.hip — the export encoders' host side of the C ABI (include/nfagg.h): evicted records to protobuf, IPFIX and
+// direct-FLP JSON, from device memory or staged from the host. The tables the *_netev, *_tls, *_k8s and *_net entry points take
+// are nfagg_api_tables.hip's.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <initializer_list>
+#include <vector>
+
+#include "../../include/nfagg.h"
+#include "nfagg_internal.h"
+#include "nfagg_handle.h"
+#include "nfagg_api_tables.h"
+#include "nfagg_pb.h"
+#include "nfagg_ipfix.h"
+#include "nfagg_flp.h"
+
+using namespace nfagg;
+
+// ---- the export encoders' host side: what protobuf, IPFIX and direct-FLP JSON do alike
+namespace {
+
+int check_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names, uint32_t unknown_len, bool check_udn) {
+    if (unknown_len > 16 || (n_names && !names)) return fail(h, NFAGG_EINVAL, "bad namer table");
+    for (uint32_t k = 0; k < n_names; k++) {
+        if (names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
+        if (check_udn && names[k].udn_len > 63) return fail(h, NFAGG_EINVAL, "namer row %u: udn too long", k);
+    }
+    return NFAGG_OK;
+}
+
+// The kernels binary-search the table: a stable sort by if_index keeps the scan-in-table-order answer.
+int stage_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names) {
+    auto& S = h->enc;
+    int rc = ensure_buf(h, S.names, (size_t)(n_names + 1) * sizeof(nfagg_intf_name));
+    if (rc != NFAGG_OK) return rc;
+    S.h_names.assign(names, names + n_names);
+    std::stable_sort(S.h_names.begin(), S.h_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
+    if (n_names) HIP_TRY(h, hipMemcpyAsync(S.names.p, S.h_names.data(), n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
+    return NFAGG_OK;
+}
+
+void split_now(int64_t now_unix_ns, int64_t& sec, int64_t& nsec) {   // time.Time's (sec, nsec), 0 <= nsec < 1e9
+    sec = now_unix_ns / 1000000000ll; nsec = now_unix_ns % 1000000000ll;
+    if (nsec < 0) { nsec += 1000000000ll; sec -= 1; }
+}
+
+// What follows the argument checks of a device entry point: the device, the zeroed results, the answer for n == 0 (*done), the
+// scratch of the two scans, the namer table.
+int encode_begin(nfagg_handle* h, size_t n, uint64_t* d_offsets, size_t* out_bytes, const nfagg_intf_name* names, uint32_t n_names, bool* done) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    *out_bytes = 0;
+    *done = n == 0;
+    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
+    const size_t blocks = (n + 1023) / 1024;
+    int rc;
+    if ((rc = ensure_buf(h, h->enc.local_off, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, h->enc.block_sum, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, h->enc.block_base, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    return stage_namer(h, names, n_names);
+}
+
+// The two passes: size(local_off, block_sum, block_base) launches the size kernel and the scan of the block sums; the total (and
+// the FLP encoder's deferred counter) is read back; a buffer that is too small or absent ends it there, with the total in
+// *out_bytes; write(local_off, block_base, total) launches the write kernel.
+template <typename SizeLaunch, typename WriteLaunch>
+int encode_two_pass(nfagg_handle* h, size_t n, const char* what, const char* write_verb, void* d_out, size_t out_cap, size_t* out_bytes,
+                           size_t* n_deferred, SizeLaunch size, WriteLaunch write) {
+    auto& S = h->enc;
+    const size_t blocks = (n + 1023) / 1024;
+    hipError_t e = size((uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s size launch failed: %s", what, hipGetErrorString(e));
+    uint64_t total = 0;
+    uint32_t deferred = 0;
+    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)S.block_base.p + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    if (n_deferred) HIP_TRY(h, hipMemcpyAsync(&deferred, S.flp_n_deferred.p, sizeof deferred, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *out_bytes = (size_t)total;
+    if (n_deferred) *n_deferred = deferred;
+    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
+    e = write((const uint32_t*)S.local_off.p, (const uint64_t*)S.block_base.p, total);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s %s launch failed: %s", what, write_verb, hipGetErrorString(e));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+// The host-memory entry points: records in, device(d_records, d_out or null, d_offsets) = the device entry point, bytes and offsets
+// out, and the format's per-record extras (out_extra[k] -> host, `bytes` per record; skipped when the caller passed no host array).
+struct EncodeExtra { void* host; size_t bytes; };
+template <typename DeviceEntry>
+int encode_staged(nfagg_handle* h, const void* records, size_t n, void* out, size_t out_cap, uint64_t* offsets, size_t* out_bytes,
+                         std::initializer_list<EncodeExtra> extras, DeviceEntry device) {
+    auto& S = h->enc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.out, out_cap + 32)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.out_offsets, (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    size_t k = 0;
+    for (const EncodeExtra& x : extras) { if (x.host && (rc = ensure_buf(h, S.out_extra[k], n * x.bytes + 32)) != NFAGG_OK) return rc; k++; }
+    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+    rc = device(S.in_records.p, out ? S.out.p : nullptr, (uint64_t*)S.out_offsets.p);
+    if (rc != NFAGG_OK) return rc;
+    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, S.out.p, *out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(offsets, S.out_offsets.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    k = 0;
+    for (const EncodeExtra& x : extras) { if (n && x.host) HIP_TRY(h, hipMemcpyAsync(x.host, S.out_extra[k].p, n * x.bytes, hipMemcpyDeviceToHost, h->stream)); k++; }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NFAGG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// nfagg_pb_features with DEVICE pointers, checked, as the kernels take it (protobuf and direct-FLP content encoders)
+static int device_features(nfagg_handle* h, const nfagg_pb_features* feat, PbFeat* F) {
+    if (feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
+    if ((((uintptr_t)feat->additional | (uintptr_t)feat->dns | (uintptr_t)feat->drops | (uintptr_t)feat->xlat | (uintptr_t)feat->quic) & 7u) != 0)
+        return fail(h, NFAGG_EINVAL, "feature arrays must be 8-byte aligned");
+    F->present = feat->present;
+    F->additional = (const uint8_t*)feat->additional; F->dns = (const uint8_t*)feat->dns; F->drops = (const uint8_t*)feat->drops;
+    F->xlat = (const uint8_t*)feat->xlat; F->quic = (const uint8_t*)feat->quic;
+    return NFAGG_OK;
+}
+
+// The *_netev entry points' extra inputs: the flows' rows (DEVICE memory) and the table they index, into F.
+struct NetevArgs { const uint16_t* rows; const nfagg_netev_table* table; };
+static int device_netev(nfagg_handle* h, const NetevArgs* ne, size_t n, PbFeat* F) {
+    if (!ne->table || (n && !ne->rows)) return fail(h, NFAGG_EINVAL, "null network-events rows or table");
+    if (ne->table->h != h || !ne->table->d_rows) return fail(h, NFAGG_EINVAL, "the network-events table was not created for this handle");
+    if (((uintptr_t)ne->rows & 7u) != 0) return fail(h, NFAGG_EINVAL, "network-events rows must be 8-byte aligned");
+    F->ne_rows = ne->rows; F->ne_tab = (const uint8_t*)ne->table->d_rows; F->ne_blob = (const uint8_t*)ne->table->d_blob;
+    F->ne_n = (uint32_t)ne->table->rows.size();
+    return NFAGG_OK;
+}
+// The rows of a host-memory call, uploaded.
+static int stage_netev_rows(nfagg_handle* h, const NetevArgs* ne, size_t n, NetevArgs* dne) {
+    *dne = *ne;
+    if (!n || !ne->rows) return NFAGG_OK;
+    int rc = ensure_buf(h, h->enc.ne_rows, n * 8 + 16);
+    if (rc != NFAGG_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->enc.ne_rows.p, ne->rows, n * 8, hipMemcpyHostToDevice, h->stream));
+    dne->rows = (const uint16_t*)h->enc.ne_rows.p;
+    return NFAGG_OK;
+}
+
+// ---- record -> protobuf (nfagg_pb.hip)
+// feat (optional): DEVICE pointers. ne (optional): the network events of the *_netev entry points.
+static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                                 const nfagg_pb_options* opt,
+                                 void* d_out, size_t out_cap, uint64_t* d_frame_offsets, uint32_t* d_body_len,
+                                 void* d_kafka_keys, size_t* out_bytes) {
+    if (!h || !opt || !out_bytes || !d_frame_offsets || (n && (!d_records || !d_body_len))) return fail(h, NFAGG_EINVAL, "null argument");
+    if (opt->struct_size != sizeof(nfagg_pb_options)) return fail(h, NFAGG_EINVAL, "nfagg_pb_options.struct_size mismatch");
+    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");   // ahead of the alignment, the rows behind it
+    if ((((uintptr_t)d_records | (uintptr_t)d_out | (uintptr_t)d_kafka_keys) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
+    int rc = check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
+    if (rc != NFAGG_OK) return rc;
+    PbFeat F{};
+    if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
+    if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
+    bool done;
+    if ((rc = encode_begin(h, n, d_frame_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
+    PbParams P{};
+    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
+    P.mono_now = opt->mono_now_ns;
+    memcpy(P.agent_ip_w, opt->agent_ip, 16);
+    static const uint8_t v4pre[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xff, 0xff};
+    P.agent_is_v4 = memcmp(opt->agent_ip, v4pre, 12) == 0;     // net.IP.To4() != nil (proto.go:255-261)
+    P.names = (const nfagg_intf_name*)h->enc.names.p; P.n_names = opt->n_names;
+    P.unknown_len = opt->unknown_len; memcpy(P.unknown, opt->unknown_name, 16);
+    return encode_two_pass(h, n, "protobuf", "encode", d_out, out_cap, out_bytes, nullptr,
+        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+            return launch_pb_size(d_records, n, P, F, d_body_len, local_off, block_sum, block_base, h->stream); },
+        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t total) {
+            return launch_pb_write(d_records, n, P, F, d_body_len, local_off, block_base, d_out, d_frame_offsets, d_kafka_keys, total, h->stream); });
+}
+
+// The feature parts of a host-memory call, uploaded: *dfeat gets the device pointers.
+static int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, nfagg_pb_features* dfeat) {
+    dfeat->struct_size = sizeof *dfeat;
+    const void* src[6] = {feat->present, feat->additional, feat->dns, feat->drops, feat->xlat, feat->quic};
+    const size_t elem[6] = {1, sizeof(nfagg_additional_metrics), sizeof(nfagg_dns_metrics), sizeof(nfagg_pkt_drop_metrics),
+                            sizeof(nfagg_xlat_metrics), sizeof(nfagg_quic_metrics)};
+    void* dst[6] = {};
+    for (int k = 0; k < 6; k++) {
+        if (!src[k]) continue;
+        int rc = ensure_buf(h, h->enc.pb_feat[k], n * elem[k] + 16);
+        if (rc != NFAGG_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->enc.pb_feat[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
+        dst[k] = h->enc.pb_feat[k].p;
+    }
+    dfeat->present = (const uint8_t*)dst[0]; dfeat->additional = (const nfagg_additional_metrics*)dst[1];
+    dfeat->dns = (const nfagg_dns_metrics*)dst[2]; dfeat->drops = (const nfagg_pkt_drop_metrics*)dst[3];
+    dfeat->xlat = (const nfagg_xlat_metrics*)dst[4]; dfeat->quic = (const nfagg_quic_metrics*)dst[5];
+    return NFAGG_OK;
+}
+
+// feat (optional): HOST pointers
+static int encode_pb_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                               const nfagg_pb_options* opt,
+                               void* out, size_t out_cap, uint64_t* frame_offsets, uint32_t* body_len,
+                               void* kafka_keys, size_t* out_bytes) {
+    if (!h || !opt || !out_bytes || !frame_offsets || (n && (!records || !body_len))) return fail(h, NFAGG_EINVAL, "null argument");
+    if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
+    return encode_staged(h, records, n, out, out_cap, frame_offsets, out_bytes, {{body_len, sizeof(uint32_t)}, {kafka_keys, 32}},
+        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
+            nfagg_pb_features dfeat{};
+            if (feat && n) { int rc = stage_pb_features(h, feat, n, &dfeat); if (rc != NFAGG_OK) return rc; }
+            NetevArgs dne{};
+            if (ne) { int rc = stage_netev_rows(h, ne, n, &dne); if (rc != NFAGG_OK) return rc; }
+            return encode_pb_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, opt, d_out, out_cap, d_offsets,
+                                         (uint32_t*)h->enc.out_extra[0].p, kafka_keys ? h->enc.out_extra[1].p : nullptr, out_bytes); });
+}
+
+int nfagg_encode_pb_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_options* opt,
+                           void* d_out, size_t out_cap, uint64_t* d_frame_offsets, uint32_t* d_body_len,
+                           void* d_kafka_keys, size_t* out_bytes) {
+    return encode_pb_device_core(h, d_records, n, nullptr, nullptr, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
+}
+
+int nfagg_encode_pb(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_options* opt,
+                    void* out, size_t out_cap, uint64_t* frame_offsets, uint32_t* body_len,
+                    void* kafka_keys, size_t* out_bytes) {
+    return encode_pb_host_core(h, records, n, nullptr, nullptr, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
+}
+
+int nfagg_encode_pb_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                   const nfagg_pb_options* opt, void* d_out, size_t out_cap, uint64_t* d_frame_offsets,
+                                   uint32_t* d_body_len, void* d_kafka_keys, size_t* out_bytes) {
+    if (!d_features) return fail(h, NFAGG_EINVAL, "null features (use nfagg_encode_pb_device)");
+    return encode_pb_device_core(h, d_records, n, d_features, nullptr, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
+}
+
+int nfagg_encode_pb_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                            const nfagg_pb_options* opt, void* out, size_t out_cap, uint64_t* frame_offsets,
+                            uint32_t* body_len, void* kafka_keys, size_t* out_bytes) {
+    if (!features) return fail(h, NFAGG_EINVAL, "null features (use nfagg_encode_pb)");
+    return encode_pb_host_core(h, records, n, features, nullptr, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
+}
+
+int nfagg_encode_pb_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                         const uint16_t* d_rows, const nfagg_netev_table* table,
+                                         const nfagg_pb_options* opt, void* d_out, size_t out_cap, uint64_t* d_frame_offsets,
+                                         uint32_t* d_body_len, void* d_kafka_keys, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, table};
+    return encode_pb_device_core(h, d_records, n, d_features, &ne, opt, d_out, out_cap, d_frame_offsets, d_body_len, d_kafka_keys, out_bytes);
+}
+
+int nfagg_encode_pb_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                  const uint16_t* rows, const nfagg_netev_table* table,
+                                  const nfagg_pb_options* opt, void* out, size_t out_cap, uint64_t* frame_offsets,
+                                  uint32_t* body_len, void* kafka_keys, size_t* out_bytes) {
+    const NetevArgs ne{rows, table};
+    return encode_pb_host_core(h, records, n, features, &ne, opt, out, out_cap, frame_offsets, body_len, kafka_keys, out_bytes);
+}
+
+// ---- record -> IPFIX (nfagg_ipfix.hip)
+static const uint16_t kIpfixTemplateV4[19][2] = {   // ipfix.go:89-135 + AddRecordValuesToTemplate; IDs and lengths: registry_IANA.go
+    {256, 2}, {61, 1}, {56, 6}, {80, 6}, {8, 4}, {12, 4}, {4, 1}, {7, 2}, {11, 2}, {176, 1}, {177, 1},
+    {1, 8}, {6, 2}, {150, 4}, {152, 8}, {151, 4}, {153, 8}, {2, 8}, {82, 65535}};
+static const uint16_t kIpfixTemplateV6[19][2] = {   // ipfix.go:158-204 + AddRecordValuesToTemplate
+    {256, 2}, {61, 1}, {56, 6}, {80, 6}, {27, 16}, {28, 16}, {193, 1}, {7, 2}, {11, 2}, {178, 1}, {179, 1},
+    {1, 8}, {6, 2}, {150, 4}, {152, 8}, {151, 4}, {153, 8}, {2, 8}, {82, 65535}};
+static constexpr size_t kIpfixTemplateBytes = 16 + 4 + 4 + 19 * 4;
+
+static void put_be16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 8); p[1] = (uint8_t)v; }
+static void put_be32(uint8_t* p, uint32_t v) { put_be16(p, v >> 16); put_be16(p + 2, v); }
+
+int nfagg_ipfix_template(const nfagg_ipfix_options* opt, int v6, void* out, size_t cap, size_t* n_out) {
+    if (!opt || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
+    if (opt->struct_size != sizeof(nfagg_ipfix_options)) return fail(nullptr, NFAGG_EINVAL, "nfagg_ipfix_options.struct_size mismatch");
+    *n_out = kIpfixTemplateBytes;
+    if (!out || cap < kIpfixTemplateBytes) return NFAGG_TRUNCATED;
+    uint8_t* p = (uint8_t*)out;
+    put_be16(p, 10); put_be16(p + 2, (uint32_t)kIpfixTemplateBytes); put_be32(p + 4, opt->export_time_s);
+    put_be32(p + 8, opt->seq0); put_be32(p + 12, opt->obs_domain_id);
+    put_be16(p + 16, 2); put_be16(p + 18, (uint32_t)kIpfixTemplateBytes - 16);                // template set
+    put_be16(p + 20, v6 ? opt->template_id_v6 : opt->template_id_v4); put_be16(p + 22, 19);  // template record header
+    const uint16_t (*f)[2] = v6 ? kIpfixTemplateV6 : kIpfixTemplateV4;
+    for (int k = 0; k < 19; k++) { put_be16(p + 24 + 4 * k, f[k][0]); put_be16(p + 26 + 4 * k, f[k][1]); }   // enterprise bit never set
+    return NFAGG_OK;
+}
+
+// The options are checked first, before the handle: a caller learns of a bad table without any device work.
+static int encode_ipfix_check(nfagg_handle* h, const nfagg_ipfix_options* opt) {
+    if (!opt) return fail(h, NFAGG_EINVAL, "null options");
+    if (opt->struct_size != sizeof(nfagg_ipfix_options)) return fail(h, NFAGG_EINVAL, "nfagg_ipfix_options.struct_size mismatch");
+    return check_namer(h, opt->names, opt->n_names, opt->unknown_len, false);
+}
+
+int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_ipfix_options* opt,
+                              void* d_out, size_t out_cap, uint64_t* d_msg_offsets, size_t* out_bytes) {
+    int rc = encode_ipfix_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !out_bytes || !d_msg_offsets || (n && !d_records)) return fail(h, NFAGG_EINVAL, "null argument");
+    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
+    bool done;
+    if ((rc = encode_begin(h, n, d_msg_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
+    if ((rc = ensure_buf(h, h->enc.ipfix_name_rows, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    uint32_t* name_rows = (uint32_t*)h->enc.ipfix_name_rows.p;
+    IpfixParams P{};
+    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
+    P.mono_now = opt->mono_now_ns;
+    P.names = (const nfagg_intf_name*)h->enc.names.p; P.n_names = opt->n_names;
+    P.unknown_len = opt->unknown_len; memcpy(P.unknown_w, opt->unknown_name, 16);
+    P.export_time = opt->export_time_s; P.seq0 = opt->seq0; P.obs_domain = opt->obs_domain_id;
+    P.tid_v4 = opt->template_id_v4; P.tid_v6 = opt->template_id_v6;
+    return encode_two_pass(h, n, "IPFIX", "write", d_out, out_cap, out_bytes, nullptr,
+        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+            return launch_ipfix_size(d_records, n, P, name_rows, local_off, block_sum, block_base, h->stream); },
+        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+            return launch_ipfix_write(d_records, n, P, name_rows, local_off, block_base, d_out, d_msg_offsets, h->stream); });
+}
+
+int nfagg_encode_ipfix(nfagg_handle* h, const void* records, size_t n, const nfagg_ipfix_options* opt,
+                       void* out, size_t out_cap, uint64_t* msg_offsets, size_t* out_bytes) {
+    int rc = encode_ipfix_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || !out_bytes || !msg_offsets || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
+    return encode_staged(h, records, n, out, out_cap, msg_offsets, out_bytes, {},
+        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
+            return nfagg_encode_ipfix_device(h, d_records, n, opt, d_out, out_cap, d_offsets, out_bytes); });
+}
+
+// ---- record -> direct-FLP JSON lines (nfagg_flp.hip)
+static void flp_escape_row(uint8_t* row, const char* name, uint32_t name_len, const char* udn, uint32_t udn_len) {
+    const uint16_t nl = (uint16_t)flp_escape(name, name_len, row + kFlpEscNameOff), ul = (uint16_t)flp_escape(udn, udn_len, row + kFlpEscUdnOff);
+    memcpy(row, &nl, 2); memcpy(row + 2, &ul, 2);
+}
+
+// The options are checked first, before the handle: a caller learns of a bad table without any device work.
+static int encode_flp_check(nfagg_handle* h, const nfagg_flp_options* opt) {
+    if (!opt) return fail(h, NFAGG_EINVAL, "null options");
+    if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
+    return check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
+}
+
+// What the FLP device entry points stage after encode_begin: the size pass's rows, the escaped namer table, the deferred counter
+// (zeroed), the kernels' parameters.
+static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, FlpParams* Pout, uint32_t** rows_out) {
+    int rc;
+    auto& S = h->enc;
+    const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
+    if ((rc = ensure_buf(h, S.flp_rows, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.flp_esc, esc_bytes)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.flp_n_deferred, 16)) != NFAGG_OK) return rc;
+    // names and UDNs are escaped here, once per row of the sorted table: neither kernel escapes per flow
+    S.h_flp_esc.assign(esc_bytes, 0);
+    flp_escape_row(S.h_flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
+    for (uint32_t k = 0; k < opt->n_names; k++) {
+        const nfagg_intf_name& e = S.h_names[k];
+        flp_escape_row(S.h_flp_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
+    }
+    HIP_TRY(h, hipMemcpyAsync(S.flp_esc.p, S.h_flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
+    *rows_out = (uint32_t*)S.flp_rows.p;
+    FlpParams& P = *Pout;
+    P = FlpParams{};
+    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
+    P.mono_now = opt->mono_now_ns;
+    P.time_received = opt->time_received_s;
+    P.names = (const nfagg_intf_name*)S.names.p; P.esc = (const uint8_t*)S.flp_esc.p; P.n_names = opt->n_names;
+    P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
+    return NFAGG_OK;
+}
+
+// The TLS entry points' extra input. With it the three TLS keys are written from the table, no record is deferred (flags and
+// counter are not used), and the network events are an option: rows and table both, or neither (*ne = nullptr).
+// with_k8s: the *_k8s entry points, whose table is required as well and whose lines carry the Kubernetes keys.
+// with_net: the *_net entry points, which take the table of the transform network rules on top of that.
+struct FlpTlsArgs {
+    const nfagg_tls_names* names; bool with_k8s = false; const nfagg_k8s_table* k8s = nullptr;
+    bool with_net = false; const nfagg_net_table* net = nullptr;
+};
+static int netev_optional(nfagg_handle* h, const NetevArgs** ne, size_t n) {
+    if (!*ne) return NFAGG_OK;
+    const NetevArgs& a = **ne;
+    if ((a.rows != nullptr) != (a.table != nullptr) && (n || a.rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
+    if (!a.table) *ne = nullptr;
+    return NFAGG_OK;
+}
+
+// feat (optional): DEVICE pointers. The launchers pick the kernels' feature policy: neither feat nor ne the plain line, ne (the
+// *_netev and *_tls entry points) the one with the NetworkEvents hook, tls the TLS names on top of either.
+static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                                  const FlpTlsArgs* tls, const nfagg_flp_options* opt,
+                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
+                                  size_t* n_deferred, size_t* out_bytes) {
+    int rc;
+    if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
+    if ((rc = encode_flp_check(h, opt)) != NFAGG_OK) return rc;
+    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !d_line_offsets ||
+        (n && !d_records))
+        return fail(h, NFAGG_EINVAL, "null argument");
+    if (tls && (tls->names->h != h || !tls->names->d_mem)) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
+    const nfagg_k8s_table* k8s = tls && tls->with_k8s ? tls->k8s : nullptr;
+    if (k8s && (k8s->h != h || !k8s->d_slots)) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
+    const nfagg_net_table* net = k8s && tls->with_net ? tls->net : nullptr;
+    if (net && (net->h != h || !net->d_mem)) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
+    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
+    PbFeat F{};
+    if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
+    if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
+    if (n_deferred) *n_deferred = 0;
+    bool done;
+    if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
+    FlpParams P{};
+    uint32_t* rows;
+    if ((rc = stage_flp(h, n, opt, &P, &rows)) != NFAGG_OK) return rc;
+    uint32_t* counter = (uint32_t*)h->enc.flp_n_deferred.p;
+    TlsDev T{};
+    if (tls) {
+        T.ids = (const uint16_t*)tls->names->d_mem;
+        T.rows = (const uint8_t*)tls->names->d_mem + tls->names->ids.size() * sizeof(uint16_t);
+        for (uint32_t k = 0; k < kTlsKinds; k++) T.n[k] = tls->names->n[k];
+    }
+    const PbFeat* Fp = (feat || ne) ? &F : nullptr;                   // neither: the plain line
+    const TlsDev* Tp = tls ? &T : nullptr;
+    if (k8s) {
+        if ((rc = ensure_buf(h, h->enc.k8s_rows, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+        uint32_t* k8s_rows = (uint32_t*)h->enc.k8s_rows.p;
+        const K8sDev K = k8s_dev(k8s);
+        hipError_t e = launch_k8s_resolve(d_records, n, K, k8s_rows, h->stream);
+        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
+        if (net) {
+            if ((rc = ensure_buf(h, h->enc.net_rows, n * sizeof(uint2))) != NFAGG_OK) return rc;
+            const uint2* net_rows = (const uint2*)h->enc.net_rows.p;
+            const NetDev N = net_dev(net);
+            e = launch_net_resolve(d_records, n, N, k8s_rows, (const uint32_t*)k8s->d_host_ids, K.n_rows, net_reporter(k8s, opt), (uint2*)h->enc.net_rows.p,
+                                   h->stream);
+            if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
+            return encode_two_pass(h, n, "FLP JSON with transform network keys", "write", d_out, out_cap, out_bytes, nullptr,
+                [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+                    return launch_flp_net_size(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_sum, block_base, h->stream); },
+                [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+                    return launch_flp_net_write(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_base, d_out, d_line_offsets,
+                                                h->stream); });
+        }
+        return encode_two_pass(h, n, "FLP JSON with Kubernetes keys", "write", d_out, out_cap, out_bytes, nullptr,
+            [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+                return launch_flp_k8s_size(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_sum, block_base, h->stream); },
+            [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+                return launch_flp_k8s_write(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_base, d_out, d_line_offsets, h->stream); });
+    }
+    size_t deferred_unused;
+    return encode_two_pass(h, n, tls ? "FLP JSON with TLS names" : Fp ? "FLP JSON content" : "FLP JSON", "write", d_out, out_cap, out_bytes,
+        tls ? nullptr : n_deferred ? n_deferred : &deferred_unused,
+        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+            return launch_flp_size(d_records, n, P, Fp, Tp, rows, local_off, block_sum, block_base, counter, h->stream); },
+        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+            return launch_flp_write(d_records, n, P, Fp, Tp, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
+}
+
+// feat (optional): HOST pointers, uploaded beside the records, as are the rows of ne
+static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
+                                const FlpTlsArgs* tls, const nfagg_flp_options* opt,
+                                void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
+                                size_t* n_deferred, size_t* out_bytes) {
+    int rc = encode_flp_check(h, opt);
+    if (rc != NFAGG_OK) return rc;
+    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !line_offsets ||
+        (n && !records))
+        return fail(h, NFAGG_EINVAL, "null argument");
+    if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
+    if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
+    return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
+        [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
+            nfagg_pb_features dfeat{};
+            if (feat && n) { int rc2 = stage_pb_features(h, feat, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
+            NetevArgs dne{};
+            if (ne) { int rc2 = stage_netev_rows(h, ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
+            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, tls, opt, d_out, out_cap, d_offsets,
+                                          deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
+}
+
+int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
+                                 void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
+                                 size_t* n_deferred, size_t* out_bytes) {
+    return encode_flp_device_core(h, d_records, n, nullptr, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+}
+
+int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
+                          void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
+                          size_t* n_deferred, size_t* out_bytes) {
+    return encode_flp_host_core(h, records, n, nullptr, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+}
+
+// features == NULL: the flows carry no parts, the call is nfagg_encode_flp_json[_device]
+int nfagg_encode_flp_json_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                         const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
+                                         uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
+    return encode_flp_device_core(h, d_records, n, d_features, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+}
+
+int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                  const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
+                                  uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
+    return encode_flp_host_core(h, records, n, features, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+}
+
+int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                               const uint16_t* d_rows, const nfagg_netev_table* table,
+                                               const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
+                                               uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, table};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+}
+
+int nfagg_encode_flp_json_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                                        const uint16_t* rows, const nfagg_netev_table* table,
+                                        const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
+                                        uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
+    const NetevArgs ne{rows, table};
+    return encode_flp_host_core(h, records, n, features, &ne, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+}
+
+// ---- direct-FLP JSON with the TLS names, the Kubernetes keys, the transform network keys: the tables are nfagg_api_tables.hip's
+uint32_t nfagg_flp_json_tls_max_line(int policy) { return flp_tls_max_line(policy); }
+
+int nfagg_encode_flp_json_tls_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, netev_table};
+    const FlpTlsArgs tls{tls_names};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+}
+
+int nfagg_encode_flp_json_tls(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{rows, netev_table};
+    const FlpTlsArgs tls{tls_names};
+    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+}
+
+uint32_t nfagg_flp_json_k8s_max_line(int policy) { return flp_k8s_max_line(policy); }
+
+int nfagg_encode_flp_json_k8s_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* d_out, size_t out_cap,
+                                     uint64_t* d_line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+}
+
+int nfagg_encode_flp_json_k8s(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* out, size_t out_cap,
+                              uint64_t* line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table};
+    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+}
+
+uint32_t nfagg_flp_json_net_max_line(int policy) { return flp_net_max_line(policy); }
+
+int nfagg_encode_flp_json_net_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                     const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                     const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
+                                     void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+}
+
+int nfagg_encode_flp_json_net(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                              const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                              const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
+                              void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
+    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+}
+
+}  // extern "C"

@@ -8,7 +8,7 @@
 
 namespace nfagg {
 
-// One row of the escaped namer table the host builds when it stages the table (nfagg_api.hip): the row's name and UDN
+// One row of the escaped namer table the host builds when it stages the table (nfagg_api_export.hip): the row's name and UDN
 // as JSON strings, quotes included, escaped once per call and not per flow. Row 0 is the unknown name (UDN ""), row
 // k + 1 is row k of the sorted table. name: at most 2 + 6 x 16 bytes, udn: at most 2 + 6 x 63.
 constexpr uint32_t kFlpEscRowBytes = 512;

@@ -134,7 +134,7 @@ template <typename S> NF_DEV void table_str(S& s, uint32_t idx) {
     }
 }
 
-// jsoniter's WriteString escaping (stream_str.go:311-372, as flp_escape of nfagg_api.hip does for the namer table), one
+// jsoniter's WriteString escaping (stream_str.go:311-372, as flp_escape of nfagg_api_tables.hip does for the namer table), one
 // byte at a time in front of another sink: the DNS name is the one string of a line that the host has not seen.
 template <typename S> struct EscSink {
     S& s;

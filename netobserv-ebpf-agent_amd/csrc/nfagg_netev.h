@@ -1,5 +1,5 @@
 // nfagg_netev.h — the network-events cookie table as the kernels see it, and the launch interface of the resolve kernel
-// (nfagg_netev.hip). The table is built and rendered on the host (nfagg_api.hip, nfagg_netev_table_create).
+// (nfagg_netev.hip). The table is built and rendered on the host (nfagg_api_tables.hip, nfagg_netev_table_create).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

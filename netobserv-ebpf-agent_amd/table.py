@@ -954,31 +954,25 @@ def netev_render(event, fmt: int) -> bytes:
     return buf[: n.value].tobytes()
 
 
-class NetevTable:
-    """The OVN sample decoder's answers as a table (nfagg_netev_table_create): entries = [(cookie8, event)], event as
-    _netev_entry takes it. With a FlowTable the table lives on its device and serves netev_resolve and the *_netev encoders;
-    with table=None it is built and checked on the host only. Row r, as netev_resolve reports it, is cookies[r]: the cookies
-    in ascending order of their little-endian 64-bit value."""
+class _CallerTable:
+    """What the five caller tables share: the library's table `_t`, the FlowTable it was created for (`_owner`; None: a table
+    built and checked on the host only) and the table's life cycle."""
 
-    def __init__(self, entries, table: "FlowTable" = None):
-        entries = list(entries)
-        arr = (L.NetevEntry * max(len(entries), 1))(*[_netev_entry(c, ev) for c, ev in entries])
+    def _create(self, table, destroy, create):
+        """create(h, out) calls the library's create function with the owner's handle (or None) and the place for the table;
+        `destroy` is the function that frees it."""
         self._t = C.c_void_p()
         h = table._h if table is not None else None
-        rc = L.lib.nfagg_netev_table_create(h, arr, len(entries), C.byref(self._t))
+        rc = create(h, C.byref(self._t))
         if rc != L.OK:
             self._t = None
             raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
-        self._owner = table                       # the handle must outlive the table
-        self.cookies = sorted((bytes(c) for c, _ in entries), key=lambda c: int.from_bytes(c, "little"))
-
-    def __len__(self):
-        return len(self.cookies)
+        self._owner, self._destroy = table, destroy      # the handle must outlive the table
 
     def close(self):
         if getattr(self, "_t", None):
             if self._owner is None or self._owner._h:
-                L.lib.nfagg_netev_table_destroy(self._t)
+                self._destroy(self._t)
             self._t = None
 
     def __del__(self):
@@ -992,6 +986,22 @@ class NetevTable:
 
     def __exit__(self, *a):
         self.close()
+
+
+class NetevTable(_CallerTable):
+    """The OVN sample decoder's answers as a table (nfagg_netev_table_create): entries = [(cookie8, event)], event as
+    _netev_entry takes it. With a FlowTable the table lives on its device and serves netev_resolve and the *_netev encoders;
+    with table=None it is built and checked on the host only. Row r, as netev_resolve reports it, is cookies[r]: the cookies
+    in ascending order of their little-endian 64-bit value."""
+
+    def __init__(self, entries, table: "FlowTable" = None):
+        entries = list(entries)
+        arr = (L.NetevEntry * max(len(entries), 1))(*[_netev_entry(c, ev) for c, ev in entries])
+        self._create(table, L.lib.nfagg_netev_table_destroy, lambda h, out: L.lib.nfagg_netev_table_create(h, arr, len(entries), out))
+        self.cookies = sorted((bytes(c) for c, _ in entries), key=lambda c: int.from_bytes(c, "little"))
+
+    def __len__(self):
+        return len(self.cookies)
 
 
 # Go's crypto/tls names as product data: tls.VersionName of 0x0300..0x0304, tls.CipherSuiteName of CipherSuites() and
@@ -1013,7 +1023,7 @@ GO_TLS_NAMES = (
     [(L.TLS_GROUP, i, n) for i, n in ((23, "CurveP256"), (24, "CurveP384"), (25, "CurveP521"), (29, "X25519"), (4588, "X25519MLKEM768"))])
 
 
-class TlsNames:
+class TlsNames(_CallerTable):
     """The names of TLS versions, cipher suites and groups as a table (nfagg_tls_names_create): entries = [(kind, id, name)],
     kind one of L.TLS_VERSION / L.TLS_CIPHER_SUITE / L.TLS_GROUP, name str or bytes (plain: nothing a JSON string escapes).
     With a FlowTable the table lives on its device and serves encode_flp_json_tls; with table=None it is built and
@@ -1033,13 +1043,7 @@ class TlsNames:
         arr = (L.TlsNameEntry * max(len(entries), 1))()
         for e, (k, i, n) in zip(arr, entries):
             e.kind, e.id, e.name, e.name_len = k, i, n, len(n)        # not len(e.name): reading a c_char_p back stops at a NUL
-        self._t = C.c_void_p()
-        h = table._h if table is not None else None
-        rc = L.lib.nfagg_tls_names_create(h, arr, len(entries), C.byref(self._t))
-        if rc != L.OK:
-            self._t = None
-            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
-        self._owner = table                       # the handle must outlive the table
+        self._create(table, L.lib.nfagg_tls_names_destroy, lambda h, out: L.lib.nfagg_tls_names_create(h, arr, len(entries), out))
         self.n = len(entries)
 
     def __len__(self):
@@ -1055,24 +1059,6 @@ class TlsNames:
         if rc != L.OK:
             raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
         return buf[: n.value].tobytes()
-
-    def close(self):
-        if getattr(self, "_t", None):
-            if self._owner is None or self._owner._h:
-                L.lib.nfagg_tls_names_destroy(self._t)
-            self._t = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def _encode_options(cls, now_unix_ns, mono_now_ns, names, unknown):
@@ -1195,7 +1181,7 @@ def k8s_render(ip, info: dict, side: int) -> bytes:
     return buf[:n.value].tobytes()
 
 
-class K8sTable:
+class K8sTable(_CallerTable):
     """The Kubernetes informers' answers as a table (nfagg_k8s_table_create): entries = [(ip, info)], ip as 16 bytes, 4 bytes
     or text, info as _k8s_entry takes it (what IndexLookup(nil, ip) returned, plus the zone fillInK8sZone would pick).
     layer: None (no K8S_FlowLayer key) or (infra_prefixes, infra_refs) of the add_kubernetes_infra rule. With a FlowTable
@@ -1207,36 +1193,13 @@ class K8sTable:
         made = [_k8s_entry(ip, info) for ip, info in entries]
         arr = (L.K8sEntry * max(len(made), 1))(*[e for e, _ in made])
         lay, keep = _k8s_layer(layer) if layer is not None else (None, None)
-        self._t = C.c_void_p()
-        h = table._h if table is not None else None
-        rc = L.lib.nfagg_k8s_table_create(h, arr, len(made), C.byref(lay) if lay is not None else None, C.byref(self._t))
-        if rc != L.OK:
-            self._t = None
-            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
-        self._owner = table                       # the handle must outlive the table
+        self._create(table, L.lib.nfagg_k8s_table_destroy,
+                     lambda h, out: L.lib.nfagg_k8s_table_create(h, arr, len(made), C.byref(lay) if lay is not None else None, out))
         self.n, self.has_layer = len(made), layer is not None
         self.entries = entries                    # row r is entries[r]: PromCounters turns a class back into texts
 
     def __len__(self):
         return self.n
-
-    def close(self):
-        if getattr(self, "_t", None):
-            if self._owner is None or self._owner._h:
-                L.lib.nfagg_k8s_table_destroy(self._t)
-            self._t = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 NET_ROW = np.dtype([("src_label", "<u2"), ("dst_label", "<u2"), ("direction", "u1"), ("pad_", "u1", (3,))])      # nfagg_net_row
@@ -1276,7 +1239,7 @@ def _net_rules(flags, cidrs, labels):
     return L.NetRules(C.sizeof(L.NetRules), flags, ca, la, len(cidrs), len(texts)), (ca, la, texts)
 
 
-class NetTable:
+class NetTable(_CallerTable):
     """Three rules of the FLP `transform network` stage as a table (nfagg_net_table_create). flags: L.NET_REINTERPRET_DIRECTION |
     L.NET_SUBNET_LABELS | L.NET_DECODE_TCP_FLAGS, each rule on its own. categories: the stage's subnetLabels, [(name, [CIDR
     text])] in configuration order (net_cidrs), or with raw=True the flat (cidrs, labels) lists themselves. With a FlowTable
@@ -1286,33 +1249,9 @@ class NetTable:
     def __init__(self, flags: int = 0, categories=(), table: "FlowTable" = None, raw: bool = False):
         cidrs, labels = categories if raw else net_cidrs(categories)
         rules, keep = _net_rules(flags, list(cidrs), list(labels))
-        self._t = C.c_void_p()
-        h = table._h if table is not None else None
-        rc = L.lib.nfagg_net_table_create(h, C.byref(rules), C.byref(self._t))
-        if rc != L.OK:
-            self._t = None
-            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
-        self._owner = table                       # the handle must outlive the table
+        self._create(table, L.lib.nfagg_net_table_destroy, lambda h, out: L.lib.nfagg_net_table_create(h, C.byref(rules), out))
         self.flags, self.n_cidrs, self.n_labels = flags, rules.n_cidrs, rules.n_labels
         self.labels = list(keep[2])               # label k's text, as nfagg_net_row's indexes name it
-
-    def close(self):
-        if getattr(self, "_t", None):
-            if self._owner is None or self._owner._h:
-                L.lib.nfagg_net_table_destroy(self._t)
-            self._t = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def net_render(net: "NetTable", side: int, label: int) -> bytes:
@@ -1332,7 +1271,7 @@ METRIC_GROUP = np.dtype([("src_class", "<u4"), ("dst_class", "<u4"), ("src_label
 assert METRIC_GROUP.itemsize == 64
 
 
-class MetricsTable:
+class MetricsTable(_CallerTable):
     """The groupings of the `encode prom` counters over a Kubernetes table (nfagg_metrics_table_create). groupings: up to
     L.MET_MAX_GROUPINGS masks of L.DIM_SRC_K8S(f) / L.DIM_DST_K8S(f) (f: index into K8S_FIELDS), L.DIM_SRC_SUBNET_LABEL,
     L.DIM_DST_SUBNET_LABEL, L.DIM_FLOW_DIRECTION, L.DIM_FLOW_LAYER, L.DIM_PROTO. Every row of `k8s` gets a class per grouping
@@ -1343,13 +1282,8 @@ class MetricsTable:
     def __init__(self, k8s: "K8sTable", groupings, table: "FlowTable" = None):
         self.groupings = [int(g) for g in groupings]
         arr = (C.c_uint32 * max(len(self.groupings), 1))(*[g & 0xFFFFFFFF for g in self.groupings])
-        self._t = C.c_void_p()
-        h = table._h if table is not None else None
-        rc = L.lib.nfagg_metrics_table_create(h, k8s._t, arr, len(self.groupings), C.byref(self._t))
-        if rc != L.OK:
-            self._t = None
-            raise NfaggError(rc, (L.lib.nfagg_last_error(h) or b"").decode())
-        self._owner, self.k8s = table, k8s        # the handle and the Kubernetes table must outlive this one
+        self._create(table, L.lib.nfagg_metrics_table_destroy, lambda h, out: L.lib.nfagg_metrics_table_create(h, k8s._t, arr, len(self.groupings), out))
+        self.k8s = k8s                            # the Kubernetes table must outlive this one, as the handle must
 
     def n_classes(self, g: int, side: int) -> int:
         return L.lib.nfagg_metrics_n_classes(self._t, g, side)
@@ -1361,24 +1295,6 @@ class MetricsTable:
         if rc != L.OK:
             raise NfaggError(rc, (L.lib.nfagg_last_error(self._owner._h if self._owner is not None else None) or b"").decode())
         return row.value
-
-    def close(self):
-        if getattr(self, "_t", None):
-            if self._owner is None or self._owner._h:
-                L.lib.nfagg_metrics_table_destroy(self._t)
-            self._t = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def ip_hash(ip16: bytes, seed_index: int) -> int:

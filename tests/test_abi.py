@@ -30,6 +30,18 @@ def test_library_exports_every_declared_symbol(nf):
     assert set(names) == set(nf._lib.SIGNATURES)
 
 
+def test_library_exports_nothing_but_declared_functions(nf):
+    """The converse: csrc/nfagg.map exports `nfagg_*`, and the host side is several translation units that share helpers with
+    external linkage. Every defined dynamic symbol of libnfagg.so is a function include/nfagg.h declares."""
+    out = subprocess.check_output(["nm", "-D", "--defined-only", nf._lib.LIB_PATH], text=True)
+    defined = {line.split()[-1].split("@")[0]: line.split()[-2] for line in out.splitlines() if line.strip()}
+    assert len(defined) >= 30
+    extra = sorted(set(defined) - set(declared_functions()))
+    assert not extra, "libnfagg.so exports symbols include/nfagg.h does not declare: %r" % extra
+    not_code = sorted(n for n, kind in defined.items() if kind != "T")
+    assert not not_code, "exported, but not as functions: %r" % not_code
+
+
 def test_abi_version(nf):
     assert nf._lib.lib.nfagg_abi_version() == 2
 

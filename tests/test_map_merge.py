@@ -219,7 +219,7 @@ CRAFTED = ("same64", "one_home_ones", "one_home_m5", "one_home_ones_min", "one_h
 
 
 def merge_mask(total_rows):
-    """The join's table (csrc/nfagg_api.hip, map_merge_device_core: `n_slots = 1024; while (n_slots < 2 * total) n_slots <<= 1`):
+    """The join's table (csrc/nfagg_api_aux.hip, map_merge_device_core: `n_slots = 1024; while (n_slots < 2 * total) n_slots <<= 1`):
     the smallest power of two that is at least max(1024, 2 * total rows), minus one. k_merge_build's home slot is
     (uint32_t)key_hash & mask."""
     n_slots = 1024
