@@ -1321,9 +1321,11 @@ uint32_t nfagg_flp_json_net_max_line(int policy);
 /*    depend on the order of the flows and are not restated;            */
 /*  - sums are exact integers: a valueScale is applied by the host to   */
 /*    the sum, not per flow;                                            */
-/*  - counters only: gauges, histograms, `flatten`, and keys outside    */
-/*    the dimension list (Interfaces, the DNS, drop and RTT keys, Dscp, */
-/*    ...) stay on the host path.                                       */
+/*  - counters and histograms: the RTT, DNS, drop and IPsec keys of a   */
+/*    MapTracer flow are value sources and extra dimensions of          */
+/*    nfagg_metrics_fold_content (below); gauges (last write wins),     */
+/*    agg_histogram, `flatten` and the other keys outside the dimension */
+/*    list (Interfaces, Dscp, ...) stay on the host path.               */
 /* ------------------------------------------------------------------ */
 
 /* One grouping is a mask of dimensions. Bit f (0..8): field f of the src row in nfagg_k8s_entry's order (namespace, name,
@@ -1389,6 +1391,99 @@ int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table,
                               const uint32_t* d_k8s_rows, const nfagg_net_row* d_net_rows, const uint32_t* group_cap,
                               nfagg_metric_group* const* d_out, uint32_t* n_groups);
 
+/* ---- Histograms, and the values and labels of the feature parts (MapTracer flows).
+ * A histogram (metrics_common.go:144-159, encode_prom.go:78-86, client_golang's histogram.Observe) is a GROUP BY over
+ * (key, bucket) with two sums, the observation count and the sum of the values: the bucket index is one more key dimension, and
+ * the hash aggregation above carries it without a bucket array per slot. The values are the integers RecordToMap writes
+ * (decode_protobuf.go:130-182, record.go:116-125); a valueScale and the float bounds of a metric are the host's business: it
+ * turns each float bound into the largest integer of the source's domain that the reference's float comparison still accepts,
+ * which is exact because float(x) / scale does not decrease with x. Sums are exact integers as above, so the host applies the
+ * scale once to a series' sum, not per flow.
+ *
+ * "Part present" below is nfagg_encode_pb_content's rule: the array is non-NULL and present[i] has the NFAGG_FEAT_* bit. */
+#define NFAGG_MET_VALUE_NONE 0
+#define NFAGG_MET_VALUE_RTT_NS 1          /* TimeFlowRttNs: additional part present and flow_rtt != 0; (int64)flow_rtt */
+#define NFAGG_MET_VALUE_DNS_LATENCY_MS 2  /* DnsLatencyMs: dns part present and id != 0; (int64)latency / 1000000, truncating toward zero (a latency of 0 is a value) */
+#define NFAGG_MET_VALUE_DROP_BYTES 3      /* PktDropBytes: drops part present and latest_drop_cause != 0; the 16-bit count (0 is a value) */
+#define NFAGG_MET_VALUE_DROP_PACKETS 4    /* PktDropPackets: likewise */
+#define NFAGG_MET_VALUE_BYTES 5           /* the record's bytes when not 0, for a histogram over them */
+#define NFAGG_MET_VALUE_PACKETS 6         /* the record's packets when not 0 */
+#define NFAGG_MET_VALUE_LAST 6
+
+/* Extra dimensions, a mask of their own beside NFAGG_DIM_*. */
+#define NFAGG_XDIM_DNS_RCODE 1u      /* DnsFlagsResponseCode: flags & 0xF; 0xFF unless DnsId exists (dns part present and id != 0) */
+#define NFAGG_XDIM_DROP_CAUSE 2u     /* PktDropLatestDropCause: the raw 32-bit latest_drop_cause; 0: none (the drop keys exist only with a cause) */
+#define NFAGG_XDIM_DROP_STATE 4u     /* PktDropLatestState: the raw latest_state; 0xFFFF unless the drop keys exist */
+#define NFAGG_XDIM_IPSEC_STATUS 8u   /* IPSecStatus: 2 "error" when ipsec_encrypted_ret != 0, else 1 "success" when ipsec_encrypted, else 0: none */
+#define NFAGG_XDIM_ALL 15u
+
+#define NFAGG_MET_MAX_BOUNDS 32
+#define NFAGG_MET_NO_BUCKET 0xFF     /* the flow has no value to bucket, or the grouping has no histogram */
+
+/* One grouping: the dimensions, up to two value sources summed per group, and optionally the buckets of one of them. A flow's
+ * bucket is the first k with value <= bounds[k], or n_bounds (+Inf); bounds are integer thresholds in the value's own unit and
+ * must not decrease (equal neighbours occur when a scale folds several float bounds onto one integer: the first of them takes
+ * the flows). A flow without value[hist - 1] gets NFAGG_MET_NO_BUCKET and is still counted in `flows`. A BYTES value above
+ * INT64_MAX goes to +Inf. */
+typedef struct nfagg_metric_spec {
+    uint32_t struct_size;            /* sizeof(nfagg_metric_spec) */
+    uint32_t dims;                   /* NFAGG_DIM_* */
+    uint32_t xdims;                  /* NFAGG_XDIM_* */
+    uint8_t value[2];                /* NFAGG_MET_VALUE_*; 0: the slot is empty */
+    uint8_t hist;                    /* 0: no histogram; 1 / 2: bucket value[hist - 1] */
+    uint8_t pad_;                    /* 0 */
+    uint32_t n_bounds;               /* 1..NFAGG_MET_MAX_BOUNDS with a histogram; ignored without */
+    uint32_t pad2_;
+    int64_t bounds[NFAGG_MET_MAX_BOUNDS];
+} nfagg_metric_spec;
+
+/* nfagg_metrics_table_create over specs: the same opaque table, h == NULL as there. NFAGG_EINVAL, with a message that names the
+ * grouping and the field, for unknown bits in dims or xdims, an unknown value source, hist > 2 or naming an empty value slot,
+ * n_bounds outside 1..NFAGG_MET_MAX_BOUNDS with a histogram, bounds that decrease, a wrong struct_size. nfagg_metrics_fold[_device]
+ * refuses a table made this way (NFAGG_EINVAL): its groups do not fit nfagg_metric_group. */
+int nfagg_metrics_table_create_specs(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const nfagg_metric_spec* specs, uint32_t n_groupings,
+                                     nfagg_metrics_table** table);
+
+/* One group of one spec, 128 bytes. The first 16 bytes are nfagg_metric_group's key fields; a dimension the grouping does not
+ * select carries its "none" value. */
+typedef struct nfagg_metric_group_content {
+    uint32_t src_class, dst_class;
+    uint16_t src_label, dst_label;
+    uint8_t direction, layer, proto, is_ip;
+    uint32_t drop_cause;              /* 0: none */
+    uint16_t drop_state;              /* 0xFFFF: none */
+    uint8_t dns_rcode;                /* 0xFF: none */
+    uint8_t ipsec_status;             /* 0: none, 1: success, 2: error */
+    uint8_t bucket;                   /* 0..n_bounds, or NFAGG_MET_NO_BUCKET */
+    uint8_t pad_[7];                  /* 0 */
+    uint64_t flows, bytes, packets, flows_with_bytes, flows_with_packets;      /* as nfagg_metric_group */
+    uint64_t value_sum[2];            /* the sum of value[k] over the flows that have it: two's complement, modulo 2^64 */
+    uint64_t flows_with_value[2];     /* the flows that have value[k]: extractGenericValue skips the others before their labels are registered */
+    uint64_t pad2_[3];                /* 0 */
+} nfagg_metric_group_content;
+
+/* nfagg_metrics_fold over specs and the flows' feature parts. records, k8s_rows, net_rows, group_cap, n_groups, truncation,
+ * NFAGG_ERANGE and n == 0 exactly as nfagg_metrics_fold; features as nfagg_encode_pb_content takes them (the struct in host
+ * memory), NULL: no flow has a part. A table of nfagg_metrics_table_create is served too: each mask is a spec without values,
+ * and the first 16 bytes and the five sums of a group are those nfagg_metrics_fold writes. A caller with an OVN decoder passes
+ * the present / drops that nfagg_netev_resolve wrote: an injected drop counts like any other. All pointers HOST memory: */
+int nfagg_metrics_fold_content(nfagg_handle* h, const nfagg_metrics_table* table, const void* records, size_t n,
+                               const nfagg_pb_features* features, const uint32_t* k8s_rows, const nfagg_net_row* net_rows,
+                               const uint32_t* group_cap, nfagg_metric_group_content* const* out, uint32_t* n_groups);
+/* Same with records, the arrays inside d_features, the rows and every out[g] in DEVICE memory (records and out[g] 16-byte, the
+ * rows and the feature arrays 8-byte aligned); the features struct and the three arrays of n_groupings stay in host memory. */
+int nfagg_metrics_fold_content_device(nfagg_handle* h, const nfagg_metrics_table* table, const void* d_records, size_t n,
+                                      const nfagg_pb_features* d_features, const uint32_t* d_k8s_rows, const nfagg_net_row* d_net_rows,
+                                      const uint32_t* group_cap, nfagg_metric_group_content* const* d_out, uint32_t* n_groups);
+
+/* The text the direct-FLP JSON encoders print for a raw value (DNSRcodeToStr, TCPStateToStr, PktDropCauseToStr and the
+ * "NetworkEvent_" causes): the label values of the groups above. *len = the text's length; NFAGG_TRUNCATED when cap is smaller
+ * (nothing written), NFAGG_EINVAL for an unknown kind or a null len. Not NUL-terminated. Pure CPU. */
+#define NFAGG_FLP_ENUM_DNS_RCODE 0
+#define NFAGG_FLP_ENUM_TCP_STATE 1
+#define NFAGG_FLP_ENUM_DROP_CAUSE 2
+int nfagg_flp_enum_name(int kind, uint32_t raw, void* out, size_t cap, size_t* len);
+
 /* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */
 /* ------------------------------------------------------------------ */
@@ -1411,6 +1506,13 @@ uint64_t nfagg_ip_hash(const uint8_t ip[16], uint32_t seed_index);
  * and the hash is fmix64((rotl64(A * K, 27) ^ B) * K) with K = 0x9E3779B97F4A7C15 and MurmurHash3's 64-bit finalizer
  * fmix64. A table of 2^k slots is probed linearly from the hash's low k bits. key == NULL or a grouping out of range: 0. */
 uint64_t nfagg_metrics_group_hash(uint32_t grouping, const nfagg_metric_group* key);
+/* The same for a group of nfagg_metrics_fold_content; the thirteen key fields of *key are read. Three 64-bit words, A and B as
+ * above and
+ *   C = 1<<63 | grouping<<56 | (bucket & 0x3F)<<48 | ipsec_status<<46 | (dns_rcode & 0x1F)<<41 | (drop_state & 0x1FF)<<32 | drop_cause
+ * (the masks keep the "none" values apart from every real one: a bucket is at most 32, a response code at most 15, a state at
+ * most 255), and the hash is fmix64((rotl64(H, 27) ^ C) * K) with H the two-word hash above. key == NULL, a grouping out of
+ * range, a bucket above NFAGG_MET_MAX_BOUNDS other than NFAGG_MET_NO_BUCKET or an ipsec_status above 2: 0. */
+uint64_t nfagg_metrics_group_hash_content(uint32_t grouping, const nfagg_metric_group_content* key);
 
 int nfagg_stats_get(nfagg_handle* h, nfagg_stats* out);
 int nfagg_stats_reset_profile(nfagg_handle* h);

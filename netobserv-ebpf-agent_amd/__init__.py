@@ -15,7 +15,8 @@ from .records import (FLOW_ID, FLOW_METRICS, FLOW_RECORD, ADDITIONAL, DNS, PKT_D
 from .table import (FlowTable, FlowGroup, NfaggError, PinnedRecords, key_hash, shard_of, ip_hash, hll_estimate_from_histogram, record_times,
                     host_threads, host_info, device_numa_node, ipfix_template, ipfix_options, IPFIX_TEMPLATE_ID_V4,
                     IPFIX_TEMPLATE_ID_V6, flp_options, NetevTable, netev_render, TlsNames, GO_TLS_NAMES, K8sTable, k8s_render,
-                    NetTable, net_render, net_cidrs, NET_ROW, MetricsTable, METRIC_GROUP, metrics_group_hash, K8S_FIELDS)
+                    NetTable, net_render, net_cidrs, NET_ROW, MetricsTable, METRIC_GROUP, metrics_group_hash, K8S_FIELDS,
+                    METRIC_GROUP_CONTENT, metrics_group_hash_content, flp_enum_name)
 from .accounter import (Accounter, NewAccounter, NewRecord, Record, IntfDirUdn, NewIntfDirUdn, Metrics, NoOp, CLOSE,
                         SetInterfaceNamer, SetGlobalIP)
 from . import synth
@@ -24,4 +25,4 @@ from .pipeline import (CapacityLimiter, RecordToMap, DirectFLPStdout, BpfFlowCon
                        FlowsToPBMessages, IPFIX, StartIPFIXExporter, DirectFLPJSON, StartDirectFLPJSON)
 from . import distributed
 from . import metrics
-from .metrics import PromCounters
+from .metrics import PromCounters, PromMetrics

@@ -157,6 +157,17 @@ DIM_SRC_K8S, DIM_DST_K8S = (lambda f: 1 << f), (lambda f: 1 << (9 + f))      # f
 DIM_SRC_SUBNET_LABEL, DIM_DST_SUBNET_LABEL, DIM_FLOW_DIRECTION, DIM_FLOW_LAYER, DIM_PROTO = 1 << 18, 1 << 19, 1 << 20, 1 << 21, 1 << 22
 DIM_ALL = (1 << 23) - 1
 MET_MAX_GROUPINGS, MET_MAX_GROUPS = 8, 1 << 20
+# the content fold (nfagg_metrics_fold_content): value sources, extra dimensions, buckets
+MET_VALUE_NONE, MET_VALUE_RTT_NS, MET_VALUE_DNS_LATENCY_MS, MET_VALUE_DROP_BYTES, MET_VALUE_DROP_PACKETS, MET_VALUE_BYTES, MET_VALUE_PACKETS = range(7)
+XDIM_DNS_RCODE, XDIM_DROP_CAUSE, XDIM_DROP_STATE, XDIM_IPSEC_STATUS, XDIM_ALL = 1, 2, 4, 8, 15
+MET_MAX_BOUNDS, MET_NO_BUCKET = 32, 0xFF
+FLP_ENUM_DNS_RCODE, FLP_ENUM_TCP_STATE, FLP_ENUM_DROP_CAUSE = 0, 1, 2
+
+
+class MetricSpec(C.Structure):
+    """nfagg_metric_spec (include/nfagg.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("dims", C.c_uint32), ("xdims", C.c_uint32), ("value", C.c_uint8 * 2), ("hist", C.c_uint8),
+                ("pad_", C.c_uint8), ("n_bounds", C.c_uint32), ("pad2_", C.c_uint32), ("bounds", C.c_int64 * 32)]
 
 TLS_VERSION, TLS_CIPHER_SUITE, TLS_GROUP = 0, 1, 2
 TLS_NAME_MAX, TLS_MAX_ROWS = 63, 256
@@ -271,11 +282,17 @@ SIGNATURES = {
     "nfagg_metrics_class_row": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nfagg_metrics_fold": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(C.c_uint32)]),
     "nfagg_metrics_fold_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    "nfagg_metrics_table_create_specs": (C.c_int, [_vp, _vp, C.POINTER(MetricSpec), C.c_uint32, C.POINTER(_vp)]),
+    "nfagg_metrics_fold_content": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    "nfagg_metrics_fold_content_device": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp),
+                                                    C.POINTER(C.c_uint32)]),
+    "nfagg_flp_enum_name": (C.c_int, [C.c_int, C.c_uint32, _vp, _sz, _psz]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),
     "nfagg_ip_hash": (C.c_uint64, [_vp, C.c_uint32]),
     "nfagg_metrics_group_hash": (C.c_uint64, [C.c_uint32, _vp]),
+    "nfagg_metrics_group_hash_content": (C.c_uint64, [C.c_uint32, _vp]),
     "nfagg_stats_get": (C.c_int, [_vp, C.POINTER(Stats)]),
     "nfagg_stats_reset_profile": (C.c_int, [_vp]),
     "nfagg_sync": (C.c_int, [_vp]),

@@ -115,7 +115,7 @@ int encode_staged(nfagg_handle* h, const void* records, size_t n, void* out, siz
 extern "C" {
 
 // nfagg_pb_features with DEVICE pointers, checked, as the kernels take it (protobuf and direct-FLP content encoders)
-static int device_features(nfagg_handle* h, const nfagg_pb_features* feat, PbFeat* F) {
+int device_features(nfagg_handle* h, const nfagg_pb_features* feat, PbFeat* F) {
     if (feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
     if ((((uintptr_t)feat->additional | (uintptr_t)feat->dns | (uintptr_t)feat->drops | (uintptr_t)feat->xlat | (uintptr_t)feat->quic) & 7u) != 0)
         return fail(h, NFAGG_EINVAL, "feature arrays must be 8-byte aligned");
@@ -179,7 +179,7 @@ static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t 
 }
 
 // The feature parts of a host-memory call, uploaded: *dfeat gets the device pointers.
-static int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, nfagg_pb_features* dfeat) {
+int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, nfagg_pb_features* dfeat) {
     dfeat->struct_size = sizeof *dfeat;
     const void* src[6] = {feat->present, feat->additional, feat->dns, feat->drops, feat->xlat, feat->quic};
     const size_t elem[6] = {1, sizeof(nfagg_additional_metrics), sizeof(nfagg_dns_metrics), sizeof(nfagg_pkt_drop_metrics),

@@ -12,6 +12,7 @@
 #include "nfagg_flp.h"
 #include "nfagg_netev.h"
 #include "nfagg_metrics.h"
+#include "nfagg_pb.h"
 
 // The cookie table of nfagg_netev_table_create: the sorted rows and the rendered blob, on the host and (with a handle) on its device.
 struct nfagg_netev_table {
@@ -78,6 +79,9 @@ struct nfagg_metrics_table {
     std::vector<uint32_t> first_row[nfagg::kMetMaxGroupings][2];   // [class - 1] = the first row of that class
     void* d_cls = nullptr;                             // the non-empty cls arrays one behind the other
     size_t d_off[nfagg::kMetMaxGroupings][2] = {};            // in words
+    // nfagg_metrics_table_create_specs: the checked specs (a plain table's are its masks without values, for the content fold)
+    bool has_specs = false;
+    nfagg_metric_spec specs[nfagg::kMetMaxGroupings] = {};
 };
 
 namespace nfagg {
@@ -92,3 +96,11 @@ K8sDev k8s_dev(const nfagg_k8s_table* t);
 uint32_t net_reporter(const nfagg_k8s_table* k8s, const nfagg_flp_options* opt);
 
 }  // namespace nfagg
+
+// The feature parts of a content call (nfagg_api_export.hip), shared by the encoders and the content metrics fold:
+// device_features checks a nfagg_pb_features with DEVICE pointers into the kernels' PbFeat; stage_pb_features uploads the parts
+// of a host-memory call into the handle's scratch and fills *dfeat with the device pointers.
+extern "C" {
+int device_features(nfagg_handle* h, const nfagg_pb_features* feat, nfagg::PbFeat* F);
+int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, nfagg_pb_features* dfeat);
+}

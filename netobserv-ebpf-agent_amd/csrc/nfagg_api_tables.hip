@@ -18,6 +18,7 @@
 #include "nfagg_flp.h"
 #include "nfagg_netev.h"
 #include "nfagg_metrics.h"
+#include "nfagg_flp_names.h"
 
 using namespace nfagg;
 
@@ -783,10 +784,9 @@ int nfagg_net_resolve(nfagg_handle* h, const nfagg_net_table* net_table, const n
 // ---- flow metrics (nfagg_metrics.h): the groupings' classes over a Kubernetes table, and the fold's host side
 extern "C" {
 
-int nfagg_metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const uint32_t* dims, uint32_t n_groupings,
-                               nfagg_metrics_table** table) {
-    if (!table || !k8s_table || !dims) return fail(h, NFAGG_EINVAL, "null argument");
-    *table = nullptr;
+// specs == nullptr: the plain table of dims.
+static int metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const uint32_t* dims, const nfagg_metric_spec* specs, uint32_t n_groupings,
+                                nfagg_metrics_table** table) {
     if (n_groupings < 1 || n_groupings > kMetMaxGroupings) return fail(h, NFAGG_EINVAL, "%u groupings, not 1..%u", n_groupings, kMetMaxGroupings);
     for (uint32_t g = 0; g < n_groupings; g++)
         if (dims[g] & ~NFAGG_DIM_ALL) return fail(h, NFAGG_EINVAL, "grouping %u: unknown dimension bits 0x%x", g, dims[g] & ~NFAGG_DIM_ALL);
@@ -796,6 +796,11 @@ int nfagg_metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table
     t->h = h;
     t->k8s = k8s_table;
     t->n_groupings = n_groupings;
+    t->has_specs = specs != nullptr;
+    for (uint32_t g = 0; g < n_groupings; g++) {
+        if (specs) t->specs[g] = specs[g];
+        else { t->specs[g].struct_size = sizeof(nfagg_metric_spec); t->specs[g].dims = dims[g]; }
+    }
     const size_t n = k8s_table->rows.size();
     size_t words = 0;
     for (uint32_t g = 0; g < n_groupings; g++) {
@@ -834,6 +839,37 @@ int nfagg_metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table
     return NFAGG_OK;
 }
 
+int nfagg_metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const uint32_t* dims, uint32_t n_groupings,
+                               nfagg_metrics_table** table) {
+    if (!table || !k8s_table || !dims) return fail(h, NFAGG_EINVAL, "null argument");
+    *table = nullptr;
+    return metrics_table_create(h, k8s_table, dims, nullptr, n_groupings, table);
+}
+
+int nfagg_metrics_table_create_specs(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const nfagg_metric_spec* specs, uint32_t n_groupings,
+                                     nfagg_metrics_table** table) {
+    if (!table || !k8s_table || !specs) return fail(h, NFAGG_EINVAL, "null argument");
+    *table = nullptr;
+    if (n_groupings < 1 || n_groupings > kMetMaxGroupings) return fail(h, NFAGG_EINVAL, "%u groupings, not 1..%u", n_groupings, kMetMaxGroupings);
+    uint32_t dims[kMetMaxGroupings] = {};
+    for (uint32_t g = 0; g < n_groupings; g++) {
+        const nfagg_metric_spec& sp = specs[g];
+        if (sp.struct_size != sizeof(nfagg_metric_spec)) return fail(h, NFAGG_EINVAL, "grouping %u: struct_size %u, not %zu", g, sp.struct_size, sizeof(nfagg_metric_spec));
+        if (sp.xdims & ~NFAGG_XDIM_ALL) return fail(h, NFAGG_EINVAL, "grouping %u: unknown xdims bits 0x%x", g, sp.xdims & ~NFAGG_XDIM_ALL);
+        for (int k = 0; k < 2; k++)
+            if (sp.value[k] > NFAGG_MET_VALUE_LAST) return fail(h, NFAGG_EINVAL, "grouping %u: value[%d]: unknown source %u", g, k, sp.value[k]);
+        if (sp.hist > 2) return fail(h, NFAGG_EINVAL, "grouping %u: hist %u, not 0, 1 or 2", g, sp.hist);
+        if (sp.hist) {
+            if (sp.value[sp.hist - 1] == NFAGG_MET_VALUE_NONE) return fail(h, NFAGG_EINVAL, "grouping %u: hist %u names the empty value[%u]", g, sp.hist, sp.hist - 1u);
+            if (sp.n_bounds < 1 || sp.n_bounds > NFAGG_MET_MAX_BOUNDS) return fail(h, NFAGG_EINVAL, "grouping %u: n_bounds %u, not 1..%u", g, sp.n_bounds, NFAGG_MET_MAX_BOUNDS);
+            for (uint32_t k = 1; k < sp.n_bounds; k++)
+                if (sp.bounds[k] < sp.bounds[k - 1]) return fail(h, NFAGG_EINVAL, "grouping %u: bounds[%u] is below bounds[%u]: bounds must not decrease", g, k, k - 1);
+        }
+        dims[g] = sp.dims;
+    }
+    return metrics_table_create(h, k8s_table, dims, specs, n_groupings, table);
+}
+
 void nfagg_metrics_table_destroy(nfagg_metrics_table* t) {
     if (!t) return;
     if (t->h && t->d_cls) {
@@ -850,6 +886,27 @@ uint64_t nfagg_metrics_group_hash(uint32_t grouping, const nfagg_metric_group* k
                     met_key_b(grouping, key->src_label, key->dst_label, key->direction, key->layer, key->proto, key->is_ip));
 }
 
+uint64_t nfagg_metrics_group_hash_content(uint32_t grouping, const nfagg_metric_group_content* key) {
+    if (!key || grouping >= kMetMaxGroupings || key->ipsec_status > 2 || (key->bucket > NFAGG_MET_MAX_BOUNDS && key->bucket != NFAGG_MET_NO_BUCKET)) return 0;
+    return met_hash(met_key_a(grouping, key->src_class, key->dst_class),
+                    met_key_b(grouping, key->src_label, key->dst_label, key->direction, key->layer, key->proto, key->is_ip),
+                    met_key_c(grouping, key->drop_cause, key->drop_state, key->dns_rcode, key->ipsec_status, key->bucket));
+}
+
+int nfagg_flp_enum_name(int kind, uint32_t raw, void* out, size_t cap, size_t* len) {
+    if (!len) return fail(nullptr, NFAGG_EINVAL, "null argument");
+    uint32_t idx;
+    if (kind == NFAGG_FLP_ENUM_DNS_RCODE) idx = rcode_name(raw);
+    else if (kind == NFAGG_FLP_ENUM_TCP_STATE) idx = tcp_state_name(raw);
+    else if (kind == NFAGG_FLP_ENUM_DROP_CAUSE) idx = drop_cause_name(raw);
+    else return fail(nullptr, NFAGG_EINVAL, "unknown enum kind %d", kind);
+    const size_t n = strlen(kFlpNames[idx]);
+    *len = n;
+    if (!out || cap < n) return NFAGG_TRUNCATED;
+    memcpy(out, kFlpNames[idx], n);
+    return NFAGG_OK;
+}
+
 uint32_t nfagg_metrics_n_classes(const nfagg_metrics_table* table, uint32_t g, int side) {
     if (!table || g >= table->n_groupings || (side != 0 && side != 1)) return 0;
     return (uint32_t)table->first_row[g][side].size();
@@ -864,12 +921,17 @@ int nfagg_metrics_class_row(const nfagg_metrics_table* table, uint32_t g, int si
     return NFAGG_OK;
 }
 
-int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table, const void* d_records, size_t n, const uint32_t* d_k8s_rows,
-                              const nfagg_net_row* d_net_rows, const uint32_t* group_cap, nfagg_metric_group* const* d_out, uint32_t* n_groups) {
+// The device side of both folds. X == nullptr: nfagg_metrics_fold_device (d_out: nfagg_metric_group arrays); else the content
+// fold over X's specs and feature arrays (d_out: nfagg_metric_group_content arrays).
+static int metrics_fold_device_core(nfagg_handle* h, const nfagg_metrics_table* table, const void* d_records, size_t n, MetSpecDev* X,
+                                    const uint32_t* d_k8s_rows, const nfagg_net_row* d_net_rows, const uint32_t* group_cap, void* const* d_out,
+                                    uint32_t* n_groups) {
     if (!h || !table || !group_cap || !d_out || !n_groups || (n && (!d_records || !d_k8s_rows))) return fail(h, NFAGG_EINVAL, "null argument");
     if (table->h != h || !table->d_cls) return fail(h, NFAGG_EINVAL, "the metrics table was not created for this handle");
+    if (!X && table->has_specs) return fail(h, NFAGG_EINVAL, "the metrics table was created from specs: use nfagg_metrics_fold_content");
     const uint32_t G = table->n_groupings;
     const uint32_t net_dims = NFAGG_DIM_SRC_SUBNET_LABEL | NFAGG_DIM_DST_SUBNET_LABEL | NFAGG_DIM_FLOW_DIRECTION;
+    const uint32_t words = X ? kMetcSlotWords : kMetSlotWords;
     MetDev M{};
     M.n_groupings = G;
     uint64_t blocks = 0;
@@ -887,7 +949,22 @@ int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table,
         if (M.dims[g] & NFAGG_DIM_FLOW_LAYER) M.any_layer = 1;
         for (int side = 0; side < 2; side++)
             M.cls[g][side] = table->cls[g][side].empty() ? nullptr : (const uint32_t*)table->d_cls + table->d_off[g][side];
+        if (X) {
+            const nfagg_metric_spec& sp = table->specs[g];
+            X->xdims[g] = sp.xdims; X->value[g][0] = sp.value[0]; X->value[g][1] = sp.value[1];
+            X->hist[g] = sp.hist; X->n_bounds[g] = sp.hist ? (uint8_t)sp.n_bounds : 0;
+            for (uint32_t k = 0; k < X->n_bounds[g]; k++) X->bounds[g][k] = sp.bounds[k];
+            uint32_t need = 0;
+            for (int k = 0; k < 2; k++)
+                need |= sp.value[k] == NFAGG_MET_VALUE_RTT_NS ? kMetNeedAdditional : sp.value[k] == NFAGG_MET_VALUE_DNS_LATENCY_MS ? kMetNeedDns :
+                        (sp.value[k] == NFAGG_MET_VALUE_DROP_BYTES || sp.value[k] == NFAGG_MET_VALUE_DROP_PACKETS) ? kMetNeedDrops : 0u;
+            need |= (sp.xdims & NFAGG_XDIM_IPSEC_STATUS ? kMetNeedAdditional : 0u) | (sp.xdims & NFAGG_XDIM_DNS_RCODE ? kMetNeedDns : 0u) |
+                    (sp.xdims & (NFAGG_XDIM_DROP_CAUSE | NFAGG_XDIM_DROP_STATE) ? kMetNeedDrops : 0u);
+            X->need |= need;
+        }
     }
+    if (X)      // a part whose array is missing, or all of them without the present bytes, is absent for every flow
+        X->need &= !X->present ? 0u : (X->additional ? kMetNeedAdditional : 0u) | (X->dns ? kMetNeedDns : 0u) | (X->drops ? kMetNeedDrops : 0u);
     M.first_block[G] = (uint32_t)blocks;
     if (((uintptr_t)d_records & 15u) != 0 || ((uintptr_t)d_k8s_rows & 7u) != 0 || ((uintptr_t)d_net_rows & 7u) != 0)
         return fail(h, NFAGG_EINVAL, "device records and group arrays must be 16-byte, rows 8-byte aligned");
@@ -898,18 +975,19 @@ int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table,
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    const size_t slot_bytes = (size_t)blocks * kMetMinSlots * kMetSlotWords * sizeof(uint64_t);
+    const size_t slot_bytes = (size_t)blocks * kMetMinSlots * words * sizeof(uint64_t);
     if ((rc = ensure_buf(h, S.met_slots, 256 + slot_bytes)) != NFAGG_OK) return rc;
     if ((rc = ensure_buf(h, S.local_off, (size_t)blocks * kMetMinSlots * sizeof(uint32_t))) != NFAGG_OK) return rc;
     if ((rc = ensure_buf(h, S.block_sum, (size_t)blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
     if ((rc = ensure_buf(h, S.block_base, ((size_t)blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
     M.ctl = (MetCtl*)S.met_slots.p;
     uint64_t* slots = (uint64_t*)((uint8_t*)S.met_slots.p + 256);
-    for (uint32_t g = 0; g < G; g++) M.slots[g] = slots + (size_t)M.first_block[g] * kMetMinSlots * kMetSlotWords;
+    for (uint32_t g = 0; g < G; g++) M.slots[g] = slots + (size_t)M.first_block[g] * kMetMinSlots * words;
     HIP_TRY(h, hipMemsetAsync(S.met_slots.p, 0, 256 + slot_bytes, h->stream));
-    hipError_t e = launch_metrics_fold(d_records, n, M, d_k8s_rows, (const uint2*)d_net_rows, h->stream);
+    hipError_t e = X ? launch_metrics_fold_content(d_records, n, M, *X, d_k8s_rows, (const uint2*)d_net_rows, h->stream)
+                     : launch_metrics_fold(d_records, n, M, d_k8s_rows, (const uint2*)d_net_rows, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "metrics fold launch failed: %s", hipGetErrorString(e));
-    e = launch_metrics_emit(M, (uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p, h->stream);
+    e = launch_metrics_emit(M, X != nullptr, (uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "metrics emit launch failed: %s", hipGetErrorString(e));
     MetCtl ctl;
     HIP_TRY(h, hipMemcpyAsync(&ctl, M.ctl, sizeof ctl, hipMemcpyDeviceToHost, h->stream));      // the one read-back: counts and flags
@@ -923,10 +1001,14 @@ int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table,
     return over ? NFAGG_TRUNCATED : NFAGG_OK;
 }
 
-int nfagg_metrics_fold(nfagg_handle* h, const nfagg_metrics_table* table, const void* records, size_t n, const uint32_t* k8s_rows,
-                       const nfagg_net_row* net_rows, const uint32_t* group_cap, nfagg_metric_group* const* out, uint32_t* n_groups) {
+// The host-memory side of both folds: stage the inputs, run the device core on the staged copies, fetch the groups. feat: HOST
+// pointers; content selects the entry point (feat may be nullptr there: no flow has a part).
+static int metrics_fold_host_core(nfagg_handle* h, const nfagg_metrics_table* table, const void* records, size_t n, bool content, const nfagg_pb_features* feat,
+                                  const uint32_t* k8s_rows, const nfagg_net_row* net_rows, const uint32_t* group_cap, void* const* out, uint32_t* n_groups) {
     if (!h || !table || !group_cap || !out || !n_groups || (n && (!records || !k8s_rows))) return fail(h, NFAGG_EINVAL, "null argument");
+    if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
     const uint32_t G = table->n_groupings;
+    const size_t group_bytes = content ? sizeof(nfagg_metric_group_content) : sizeof(nfagg_metric_group);
     size_t total = 0;
     for (uint32_t g = 0; g < G; g++) {
         if (group_cap[g] > kMetMaxGroups) return fail(h, NFAGG_ERANGE, "grouping %u: a cap of %u groups, more than %u", g, group_cap[g], kMetMaxGroups);
@@ -939,22 +1021,57 @@ int nfagg_metrics_fold(nfagg_handle* h, const nfagg_metrics_table* table, const 
     if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
     if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
     if ((rc = ensure_buf(h, S.net_rows, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.met_out, total * sizeof(nfagg_metric_group) + 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.met_out, total * group_bytes + 16)) != NFAGG_OK) return rc;
     if (n) {
         HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
         if (net_rows) HIP_TRY(h, hipMemcpyAsync(S.net_rows.p, net_rows, n * sizeof(nfagg_net_row), hipMemcpyHostToDevice, h->stream));
     }
-    nfagg_metric_group* d_out[kMetMaxGroupings] = {};
+    void* d_out[kMetMaxGroupings] = {};
     size_t at = 0;
-    for (uint32_t g = 0; g < G; g++) { d_out[g] = (nfagg_metric_group*)S.met_out.p + at; at += group_cap[g]; }
-    rc = nfagg_metrics_fold_device(h, table, S.in_records.p, n, (const uint32_t*)S.k8s_rows.p, net_rows ? (const nfagg_net_row*)S.net_rows.p : nullptr, group_cap,
-                                   d_out, n_groups);
+    for (uint32_t g = 0; g < G; g++) { d_out[g] = (uint8_t*)S.met_out.p + at * group_bytes; at += group_cap[g]; }
+    const nfagg_net_row* d_net = net_rows ? (const nfagg_net_row*)S.net_rows.p : nullptr;
+    if (content) {
+        nfagg_pb_features dfeat{};
+        if (feat && n && (rc = stage_pb_features(h, feat, n, &dfeat)) != NFAGG_OK) return rc;
+        rc = nfagg_metrics_fold_content_device(h, table, S.in_records.p, n, (feat && n) ? &dfeat : nullptr, (const uint32_t*)S.k8s_rows.p, d_net, group_cap,
+                                               (nfagg_metric_group_content* const*)d_out, n_groups);
+    } else
+        rc = nfagg_metrics_fold_device(h, table, S.in_records.p, n, (const uint32_t*)S.k8s_rows.p, d_net, group_cap, (nfagg_metric_group* const*)d_out, n_groups);
     if (rc != NFAGG_OK) return rc;
     for (uint32_t g = 0; g < G; g++)
-        if (n_groups[g]) HIP_TRY(h, hipMemcpyAsync(out[g], d_out[g], (size_t)n_groups[g] * sizeof(nfagg_metric_group), hipMemcpyDeviceToHost, h->stream));
+        if (n_groups[g]) HIP_TRY(h, hipMemcpyAsync(out[g], d_out[g], (size_t)n_groups[g] * group_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
+}
+
+int nfagg_metrics_fold_device(nfagg_handle* h, const nfagg_metrics_table* table, const void* d_records, size_t n, const uint32_t* d_k8s_rows,
+                              const nfagg_net_row* d_net_rows, const uint32_t* group_cap, nfagg_metric_group* const* d_out, uint32_t* n_groups) {
+    return metrics_fold_device_core(h, table, d_records, n, nullptr, d_k8s_rows, d_net_rows, group_cap, (void* const*)d_out, n_groups);
+}
+
+int nfagg_metrics_fold(nfagg_handle* h, const nfagg_metrics_table* table, const void* records, size_t n, const uint32_t* k8s_rows,
+                       const nfagg_net_row* net_rows, const uint32_t* group_cap, nfagg_metric_group* const* out, uint32_t* n_groups) {
+    return metrics_fold_host_core(h, table, records, n, false, nullptr, k8s_rows, net_rows, group_cap, (void* const*)out, n_groups);
+}
+
+int nfagg_metrics_fold_content_device(nfagg_handle* h, const nfagg_metrics_table* table, const void* d_records, size_t n,
+                                      const nfagg_pb_features* d_features, const uint32_t* d_k8s_rows, const nfagg_net_row* d_net_rows,
+                                      const uint32_t* group_cap, nfagg_metric_group_content* const* d_out, uint32_t* n_groups) {
+    MetSpecDev X{};
+    if (d_features) {
+        PbFeat F{};
+        const int rc = device_features(h, d_features, &F);
+        if (rc != NFAGG_OK) return rc;
+        X.present = F.present; X.additional = F.additional; X.dns = F.dns; X.drops = F.drops;
+    }
+    return metrics_fold_device_core(h, table, d_records, n, &X, d_k8s_rows, d_net_rows, group_cap, (void* const*)d_out, n_groups);
+}
+
+int nfagg_metrics_fold_content(nfagg_handle* h, const nfagg_metrics_table* table, const void* records, size_t n,
+                               const nfagg_pb_features* features, const uint32_t* k8s_rows, const nfagg_net_row* net_rows,
+                               const uint32_t* group_cap, nfagg_metric_group_content* const* out, uint32_t* n_groups) {
+    return metrics_fold_host_core(h, table, records, n, true, features, k8s_rows, net_rows, group_cap, (void* const*)out, n_groups);
 }
 
 }  // extern "C"

@@ -22,63 +22,13 @@
 // and the DNS name in a 32-byte LDS slot of its own. The names of response codes, TCP states and drop causes sit in one
 // constant blob with an offset and a length per name; the counting pass reads only the lengths.
 #include "nfagg_flp_line.h"
+#include "nfagg_flp_names.h"
 #include "nfagg_netev.h"
 #include "nfagg_tls.h"
 #include "nfagg_k8s.h"
 #include "nfagg_net.h"
 
 namespace nfagg {
-
-// ---- the name tables: DNSRcodeToStr, TCPStateToStr, PktDropCauseToStr (decode_protobuf.go:199-464) and the causes of
-// networkevents.DropReasonCodeToString (network_events.go:17-28,133-138) behind their "NetworkEvent_" prefix
-constexpr const char* const kFlpNames[] = {
-    // DNSRcodeToStr of a 4-bit value: 0..10, everything else "UnDefined" (its cases 16..21 cannot match)
-    "NoError", "FormErr", "ServFail", "NXDomain", "NotImp", "Refused", "YXDomain", "YXRRSet", "NXRRSet", "NotAuth", "NotZone",
-    "UnDefined",
-    // TCPStateToStr: the fallback, then states 1..11
-    "TCP_INVALID_STATE", "TCP_ESTABLISHED", "TCP_SYN_SENT", "TCP_SYN_RECV", "TCP_FIN_WAIT1", "TCP_FIN_WAIT2", "TCP_CLOSE",
-    "TCP_CLOSE_WAIT", "TCP_LAST_ACK", "TCP_LISTEN", "TCP_CLOSING", "TCP_NEW_SYN_RECV",
-    // PktDropCauseToStr: the core subsystem's causes 2..80
-    "SKB_DROP_REASON_NOT_SPECIFIED", "SKB_DROP_REASON_NO_SOCKET", "SKB_DROP_REASON_PKT_TOO_SMALL", "SKB_DROP_REASON_TCP_CSUM",
-    "SKB_DROP_REASON_SOCKET_FILTER", "SKB_DROP_REASON_UDP_CSUM", "SKB_DROP_REASON_NETFILTER_DROP", "SKB_DROP_REASON_OTHERHOST",
-    "SKB_DROP_REASON_IP_CSUM", "SKB_DROP_REASON_IP_INHDR", "SKB_DROP_REASON_IP_RPFILTER",
-    "SKB_DROP_REASON_UNICAST_IN_L2_MULTICAST", "SKB_DROP_REASON_XFRM_POLICY", "SKB_DROP_REASON_IP_NOPROTO",
-    "SKB_DROP_REASON_SOCKET_RCVBUFF", "SKB_DROP_REASON_PROTO_MEM", "SKB_DROP_REASON_TCP_MD5NOTFOUND",
-    "SKB_DROP_REASON_TCP_MD5UNEXPECTED", "SKB_DROP_REASON_TCP_MD5FAILURE", "SKB_DROP_REASON_SOCKET_BACKLOG",
-    "SKB_DROP_REASON_TCP_FLAGS", "SKB_DROP_REASON_TCP_ZEROWINDOW", "SKB_DROP_REASON_TCP_OLD_DATA",
-    "SKB_DROP_REASON_TCP_OVERWINDOW", "SKB_DROP_REASON_TCP_OFOMERGE", "SKB_DROP_REASON_TCP_RFC7323_PAWS",
-    "SKB_DROP_REASON_TCP_INVALID_SEQUENCE", "SKB_DROP_REASON_TCP_RESET", "SKB_DROP_REASON_TCP_INVALID_SYN",
-    "SKB_DROP_REASON_TCP_CLOSE", "SKB_DROP_REASON_TCP_FASTOPEN", "SKB_DROP_REASON_TCP_OLD_ACK",
-    "SKB_DROP_REASON_TCP_TOO_OLD_ACK", "SKB_DROP_REASON_TCP_ACK_UNSENT_DATA", "SKB_DROP_REASON_TCP_OFO_QUEUE_PRUNE",
-    "SKB_DROP_REASON_TCP_OFO_DROP", "SKB_DROP_REASON_IP_OUTNOROUTES", "SKB_DROP_REASON_BPF_CGROUP_EGRESS",
-    "SKB_DROP_REASON_IPV6DISABLED", "SKB_DROP_REASON_NEIGH_CREATEFAIL", "SKB_DROP_REASON_NEIGH_FAILED",
-    "SKB_DROP_REASON_NEIGH_QUEUEFULL", "SKB_DROP_REASON_NEIGH_DEAD", "SKB_DROP_REASON_TC_EGRESS", "SKB_DROP_REASON_QDISC_DROP",
-    "SKB_DROP_REASON_CPU_BACKLOG", "SKB_DROP_REASON_XDP", "SKB_DROP_REASON_TC_INGRESS", "SKB_DROP_REASON_UNHANDLED_PROTO",
-    "SKB_DROP_REASON_SKB_CSUM", "SKB_DROP_REASON_SKB_GSO_SEG", "SKB_DROP_REASON_SKB_UCOPY_FAULT", "SKB_DROP_REASON_DEV_HDR",
-    "SKB_DROP_REASON_DEV_READY", "SKB_DROP_REASON_FULL_RING", "SKB_DROP_REASON_NOMEM", "SKB_DROP_REASON_HDR_TRUNC",
-    "SKB_DROP_REASON_TAP_FILTER", "SKB_DROP_REASON_TAP_TXFILTER", "SKB_DROP_REASON_ICMP_CSUM", "SKB_DROP_REASON_INVALID_PROTO",
-    "SKB_DROP_REASON_IP_INADDRERRORS", "SKB_DROP_REASON_IP_INNOROUTES", "SKB_DROP_REASON_PKT_TOO_BIG", "SKB_DROP_REASON_DUP_FRAG",
-    "SKB_DROP_REASON_FRAG_REASM_TIMEOUT", "SKB_DROP_REASON_FRAG_TOO_FAR", "SKB_DROP_REASON_TCP_MINTTL",
-    "SKB_DROP_REASON_IPV6_BAD_EXTHDR", "SKB_DROP_REASON_IPV6_NDISC_FRAG", "SKB_DROP_REASON_IPV6_NDISC_HOP_LIMIT",
-    "SKB_DROP_REASON_IPV6_NDISC_BAD_CODE", "SKB_DROP_REASON_IPV6_NDISC_BAD_OPTIONS", "SKB_DROP_REASON_IPV6_NDISC_NS_OTHERHOST",
-    "SKB_DROP_REASON_QUEUE_PURGE", "SKB_DROP_REASON_TC_COOKIE_ERROR", "SKB_DROP_REASON_PACKET_SOCK_ERROR",
-    "SKB_DROP_REASON_TC_CHAIN_NOTFOUND", "SKB_DROP_REASON_TC_RECLASSIFY_LOOP",
-    // the Open vSwitch subsystem's causes (3 << 16) + 1..11
-    "OVS_DROP_LAST_ACTION", "OVS_DROP_ACTION_ERROR", "OVS_DROP_EXPLICIT", "OVS_DROP_EXPLICIT_WITH_ERROR", "OVS_DROP_METER",
-    "OVS_DROP_RECURSION_LIMIT", "OVS_DROP_DEFERRED_LIMIT", "OVS_DROP_FRAG_L2_TOO_LONG", "OVS_DROP_FRAG_INVALID_PROTO",
-    "OVS_DROP_CONNTRACK", "OVS_DROP_IP_TTL",
-    // network-event causes (1 << 24) + 0..9
-    "NetworkEvent_Unknown", "NetworkEvent_EgressFirewall", "NetworkEvent_AdminNetworkPolicy",
-    "NetworkEvent_BaselineAdminNetworkPolicy", "NetworkEvent_NetworkPolicy", "NetworkEvent_MulticastNS",
-    "NetworkEvent_MulticastCluster", "NetworkEvent_NetpolNode", "NetworkEvent_NetpolNamespace", "NetworkEvent_UDNIsolation",
-    "SKB_DROP_UNKNOWN_CAUSE"};
-constexpr uint32_t kFlpNameCount = sizeof(kFlpNames) / sizeof(kFlpNames[0]);
-constexpr uint32_t kNameRcode = 0, kNameRcodeUndefined = 11, kNameTcpInvalid = 12;
-constexpr uint32_t kNameCore = 24, kCoreFirst = 2, kCoreLast = 80;
-constexpr uint32_t kNameOvs = kNameCore + (kCoreLast - kCoreFirst + 1), kOvsBase = (3u << 16) + 1, kOvsCount = 11;
-constexpr uint32_t kNameNetEvent = kNameOvs + kOvsCount, kNetEventBase = 1u << 24, kNetEventCount = 10;
-constexpr uint32_t kNameUnknownCause = kNameNetEvent + kNetEventCount;
-static_assert(kNameUnknownCause + 1 == kFlpNameCount, "name table layout");
 
 constexpr uint32_t cstr_len(const char* p) { uint32_t n = 0; while (p[n]) n++; return n; }
 constexpr uint32_t flp_names_dwords() {
@@ -109,13 +59,6 @@ constexpr FlpNameTab make_flp_names() {
     return t;
 }
 __constant__ FlpNameTab d_flp_names = make_flp_names();
-
-NF_DEV uint32_t drop_cause_name(uint32_t cause) {
-    if (cause - kCoreFirst <= kCoreLast - kCoreFirst) return kNameCore + (cause - kCoreFirst);
-    if (cause - kOvsBase < kOvsCount) return kNameOvs + (cause - kOvsBase);
-    if (cause - kNetEventBase < kNetEventCount) return kNameNetEvent + (cause - kNetEventBase);
-    return kNameUnknownCause;
-}
 
 // "name" of the table, quotes included. No name needs escaping.
 template <typename S> NF_DEV void table_str(S& s, uint32_t idx) {
@@ -226,7 +169,7 @@ struct FlpContent {
         if (!id) return;
         lit(s, ",\"DnsFlags\":"); dec<5>(s, flags);
         const uint32_t rc = flags & 15u;
-        lit(s, ",\"DnsFlagsResponseCode\":"); table_str(s, rc <= 10 ? kNameRcode + rc : kNameRcodeUndefined);
+        lit(s, ",\"DnsFlagsResponseCode\":"); table_str(s, rcode_name(rc));
         lit(s, ",\"DnsId\":"); dec<5>(s, id);
         // record.go:116-120 + Duration.Milliseconds(): int64(latency) / 1e6, truncating towards zero
         lit(s, ",\"DnsLatencyMs\":"); dec_i64(s, (int64_t)((uint64_t)dnsw[0] | ((uint64_t)dnsw[1] << 32)) / 1000000ll);
@@ -251,7 +194,7 @@ struct FlpContent {
         lit(s, ",\"PktDropLatestDropCause\":"); table_str(s, drop_cause_name(drp[1]));
         lit(s, ",\"PktDropLatestFlags\":"); dec<5>(s, drp[2] & 0xffffu);
         const uint32_t st = drp[3] & 0xffu;
-        lit(s, ",\"PktDropLatestState\":"); table_str(s, kNameTcpInvalid + (st <= 11 ? st : 0u));
+        lit(s, ",\"PktDropLatestState\":"); table_str(s, tcp_state_name(st));
         lit(s, ",\"PktDropPackets\":"); dec<5>(s, drp[0] >> 16);
     }
     template <typename S> NF_DEV void quic(S& s) const {                // decode_protobuf.go:188-192, record.go:259-270

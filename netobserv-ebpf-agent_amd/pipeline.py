@@ -227,8 +227,9 @@ class MapTracer:
         nothing is deferred and the result is (buf, line_offsets) as FlowTable.encode_flp_json_tls gives it. With k8s (a K8sTable of the
         fetcher's table; needs tls_names) the lines carry what the `transform network` stage's Kubernetes rules add as well
         (FlowTable.encode_flp_json_k8s). With net (a NetTable; needs k8s) also what its reinterpret_direction, add_subnet_label and
-        decode_tcp_flags rules add (FlowTable.encode_flp_json_net). With metrics (a PromCounters; needs k8s) the `encode prom` counters
-        observe the same flows (PromCounters.observe)."""
+        decode_tcp_flags rules add (FlowTable.encode_flp_json_net). With metrics (a PromCounters or a PromMetrics; needs k8s) the
+        `encode prom` metrics observe the same flows; a PromMetrics is handed the flows' feature parts as well, with a sample
+        decoder those nfagg_netev_resolve wrote, so that an injected drop counts like any other."""
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         if net is not None and k8s is None:
@@ -241,9 +242,12 @@ class MapTracer:
         recs, present, parts, _dups = table.map_merge(main_ids, main_vals, feats, n_cpu)
         names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         mono = monotonic_now & ((1 << 64) - 1)
-        if metrics is not None:
+        content = hasattr(metrics, "histograms")                        # a PromMetrics reads the feature parts
+        if metrics is not None and not content:
             metrics.observe(table, recs, k8s, net, agent_ip)
         if self.sampleDecoder is None:                                  # s == nil: no events, no injected drops (record.go:126)
+            if content:
+                metrics.observe(table, recs, k8s, net, agent_ip, features=(present, parts))
             if net is not None:
                 return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, present, parts)
             if k8s is not None:
@@ -252,6 +256,8 @@ class MapTracer:
                 return table.encode_flp_json_tls(recs, tls_names, current, mono, names, agent_ip, time_received, unknown, present, parts)
             return table.encode_flp_json_content(recs, present, parts, current, mono, names, agent_ip, time_received, unknown)
         p_out, parts, rows, tab = self.resolveNetworkEvents(present, parts)
+        if content:
+            metrics.observe(table, recs, k8s, net, agent_ip, features=(p_out, parts))
         if net is not None:
             return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         if k8s is not None:
@@ -374,8 +380,9 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
     `tls_names`) the lines are those of the pipeline NetObserv ships, with the Kubernetes rules of its `transform network` stage in
     front of the writer (FlowTable.encode_flp_json_k8s). With `net` on top (a NetTable of `table`; needs `k8s`) the stage's
     reinterpret_direction, add_subnet_label and decode_tcp_flags rules are applied too (FlowTable.encode_flp_json_net), and no host pass
-    over the lines is left. With `metrics` (a PromCounters; needs `k8s`) the `encode prom` counters observe every eviction too
-    (PromCounters.observe): the pipeline's other output, from the same records.
+    over the lines is left. With `metrics` (a PromCounters or a PromMetrics; needs `k8s`) the `encode prom` metrics observe every
+    eviction too (observe): the pipeline's other output, from the same records. Evicted records carry no feature parts, so a
+    PromMetrics sees none here; MapTracer.evictFlowsJSON hands it those of its merged flows.
 
     One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
 

@@ -755,6 +755,48 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, [int(x) for x in n_a]
 
+    def metrics_table_specs(self, k8s: "K8sTable", specs) -> "MetricsTable":
+        """A metrics table of specs (dicts of dims, xdims, value, hist, bounds: MetricsTable.spec) on this handle's device, for
+        metrics_fold_content."""
+        return MetricsTable(k8s, None, self, specs=specs)
+
+    def _fold_content_args(self, met, caps):
+        G = len(met.groupings)
+        caps = [int(caps)] * G if np.isscalar(caps) else [int(c) for c in caps]
+        return G, caps, (C.c_uint32 * G)(*caps), (C.c_uint32 * G)()
+
+    def metrics_fold_content(self, met: "MetricsTable", records: np.ndarray, k8s_rows: np.ndarray, net_rows: np.ndarray = None, caps=4096, features=None):
+        """nfagg_metrics_fold_content: metrics_fold over a table of specs (or a plain one) and the flows' feature parts.
+        features: (present, parts) as map_merge returns and encode_flp_json_content takes them, or None: no flow has a part.
+        Returns (rc, groups, n_groups) with METRIC_GROUP_CONTENT arrays."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        G, caps, cap_a, n_a = self._fold_content_args(met, caps)
+        kr = np.ascontiguousarray(k8s_rows, dtype=np.uint32)
+        nr = np.ascontiguousarray(net_rows, dtype=NET_ROW) if net_rows is not None else None
+        feat, keep = (None, None)
+        if features is not None and features[0] is not None:
+            feat, keep = self._pb_features(n, features[0], {k: v for k, v in self._content_parts(features[1]).items() if v is not None})
+        outs = [np.zeros(min(c, L.MET_MAX_GROUPS), dtype=METRIC_GROUP_CONTENT) for c in caps]
+        ptrs = (C.c_void_p * G)(*[o.ctypes.data if o.size else None for o in outs])
+        rc = L.lib.nfagg_metrics_fold_content(self._h, met._t, r.ctypes.data_as(C.c_void_p) if n else None, n, C.byref(feat) if feat is not None else None,
+                                              kr.ctypes.data_as(C.c_void_p) if n else None,
+                                              nr.ctypes.data_as(C.c_void_p) if nr is not None and n else None, cap_a, ptrs, n_a)
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        counts = [int(x) for x in n_a]
+        return rc, [o[:c if rc == L.OK else 0] for o, c in zip(outs, counts)], counts
+
+    def metrics_fold_content_device(self, met: "MetricsTable", d_records: int, n: int, d_k8s_rows: int, d_net_rows: int, caps, d_outs, d_features=None):
+        """Device-resident variant (raw device pointers; d_features = (d_present, {part: pointer}) or None; d_outs[g]: room for
+        caps[g] groups of 128 bytes, 16-byte aligned). Returns (rc, n_groups)."""
+        G, caps, cap_a, n_a = self._fold_content_args(met, caps)
+        ptrs = (C.c_void_p * G)(*[p or None for p in d_outs])
+        feat = self._pb_features(n, d_features[0], self._content_parts(d_features[1]), device=True)[0] if d_features is not None else None
+        rc = L.lib.nfagg_metrics_fold_content_device(self._h, met._t, C.c_void_p(d_records or None), n, C.byref(feat) if feat is not None else None,
+                                                     C.c_void_p(d_k8s_rows or None), C.c_void_p(d_net_rows or None), cap_a, ptrs, n_a)
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, [int(x) for x in n_a]
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -1269,6 +1311,12 @@ METRIC_GROUP = np.dtype([("src_class", "<u4"), ("dst_class", "<u4"), ("src_label
                          ("proto", "u1"), ("is_ip", "u1"), ("flows", "<u8"), ("bytes", "<u8"), ("packets", "<u8"), ("flows_with_bytes", "<u8"),
                          ("flows_with_packets", "<u8"), ("pad_", "<u8")])                                           # nfagg_metric_group
 assert METRIC_GROUP.itemsize == 64
+METRIC_GROUP_CONTENT = np.dtype([("src_class", "<u4"), ("dst_class", "<u4"), ("src_label", "<u2"), ("dst_label", "<u2"), ("direction", "u1"), ("layer", "u1"),
+                                 ("proto", "u1"), ("is_ip", "u1"), ("drop_cause", "<u4"), ("drop_state", "<u2"), ("dns_rcode", "u1"), ("ipsec_status", "u1"),
+                                 ("bucket", "u1"), ("pad_", "u1", (7,)), ("flows", "<u8"), ("bytes", "<u8"), ("packets", "<u8"), ("flows_with_bytes", "<u8"),
+                                 ("flows_with_packets", "<u8"), ("value_sum", "<u8", (2,)), ("flows_with_value", "<u8", (2,)),
+                                 ("pad2_", "<u8", (3,))])                                                                   # nfagg_metric_group_content
+assert METRIC_GROUP_CONTENT.itemsize == 128
 
 
 class MetricsTable(_CallerTable):
@@ -1277,12 +1325,35 @@ class MetricsTable(_CallerTable):
     L.DIM_DST_SUBNET_LABEL, L.DIM_FLOW_DIRECTION, L.DIM_FLOW_LAYER, L.DIM_PROTO. Every row of `k8s` gets a class per grouping
     and side: the dense id, from 1, of the tuple of its selected fields; class_row turns a class back into a row of the
     caller's entries. With a FlowTable (the one `k8s` lives on) the table serves metrics_fold; with table=None (and a host-only
-    `k8s`) it is built and checked on the host alone. Rebuild it when the Kubernetes table is rebuilt."""
+    `k8s`) it is built and checked on the host alone. Rebuild it when the Kubernetes table is rebuilt.
 
-    def __init__(self, k8s: "K8sTable", groupings, table: "FlowTable" = None):
-        self.groupings = [int(g) for g in groupings]
-        arr = (C.c_uint32 * max(len(self.groupings), 1))(*[g & 0xFFFFFFFF for g in self.groupings])
-        self._create(table, L.lib.nfagg_metrics_table_destroy, lambda h, out: L.lib.nfagg_metrics_table_create(h, k8s._t, arr, len(self.groupings), out))
+    With specs (nfagg_metrics_table_create_specs; `groupings` is then ignored) every grouping is a dict as spec() takes it:
+    dims, xdims (L.XDIM_*), value (up to two L.MET_VALUE_*), hist (0, or 1 / 2: the value slot to bucket) and bounds (integer
+    thresholds that do not decrease). Such a table serves metrics_fold_content only."""
+
+    @staticmethod
+    def spec(dims=0, xdims=0, value=(), hist=0, bounds=(), struct_size=None, n_bounds=None) -> "L.MetricSpec":
+        sp = L.MetricSpec()
+        sp.struct_size = C.sizeof(L.MetricSpec) if struct_size is None else struct_size
+        sp.dims, sp.xdims, sp.hist = dims & 0xFFFFFFFF, xdims & 0xFFFFFFFF, hist
+        for k, v in enumerate(list(value)[:2]):
+            sp.value[k] = v
+        sp.n_bounds = len(bounds) if n_bounds is None else n_bounds
+        for k, b in enumerate(list(bounds)[: L.MET_MAX_BOUNDS]):
+            sp.bounds[k] = b
+        return sp
+
+    def __init__(self, k8s: "K8sTable", groupings, table: "FlowTable" = None, specs=None):
+        if specs is not None:
+            self.specs = [sp if isinstance(sp, L.MetricSpec) else self.spec(**sp) for sp in specs]
+            self.groupings = [int(sp.dims) for sp in self.specs]
+            arr = (L.MetricSpec * max(len(self.specs), 1))(*self.specs)
+            self._create(table, L.lib.nfagg_metrics_table_destroy, lambda h, out: L.lib.nfagg_metrics_table_create_specs(h, k8s._t, arr, len(self.specs), out))
+        else:
+            self.specs = None
+            self.groupings = [int(g) for g in groupings]
+            arr = (C.c_uint32 * max(len(self.groupings), 1))(*[g & 0xFFFFFFFF for g in self.groupings])
+            self._create(table, L.lib.nfagg_metrics_table_destroy, lambda h, out: L.lib.nfagg_metrics_table_create(h, k8s._t, arr, len(self.groupings), out))
         self.k8s = k8s                            # the Kubernetes table must outlive this one, as the handle must
 
     def n_classes(self, g: int, side: int) -> int:
@@ -1308,6 +1379,24 @@ def metrics_group_hash(grouping: int, groups) -> np.ndarray:
     g = np.ascontiguousarray(np.atleast_1d(groups), dtype=METRIC_GROUP)
     base = g.ctypes.data
     return np.fromiter((L.lib.nfagg_metrics_group_hash(grouping, base + METRIC_GROUP.itemsize * i) for i in range(len(g))), dtype=np.uint64, count=len(g))
+
+
+def metrics_group_hash_content(grouping: int, groups) -> np.ndarray:
+    """nfagg_metrics_group_hash_content of every METRIC_GROUP_CONTENT in `groups` (the thirteen key fields are read). Pure CPU."""
+    g = np.ascontiguousarray(np.atleast_1d(groups), dtype=METRIC_GROUP_CONTENT)
+    base = g.ctypes.data
+    return np.fromiter((L.lib.nfagg_metrics_group_hash_content(grouping, base + METRIC_GROUP_CONTENT.itemsize * i) for i in range(len(g))), dtype=np.uint64,
+                       count=len(g))
+
+
+def flp_enum_name(kind: int, raw: int) -> bytes:
+    """nfagg_flp_enum_name: the text the direct-FLP JSON encoders print for a raw DNS response code (L.FLP_ENUM_DNS_RCODE), TCP
+    state (L.FLP_ENUM_TCP_STATE) or drop cause (L.FLP_ENUM_DROP_CAUSE). Pure CPU."""
+    buf, n = C.create_string_buffer(64), C.c_size_t(0)
+    rc = L.lib.nfagg_flp_enum_name(kind, raw & 0xFFFFFFFF, buf, 64, C.byref(n))
+    if rc != L.OK:
+        raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
+    return buf.raw[: n.value]
 
 
 def hll_estimate_from_histogram(hist, p: int) -> float:

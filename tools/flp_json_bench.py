@@ -33,7 +33,14 @@ nfagg_encode_flp_json_net_device with reinterpret_direction, add_subnet_label an
 nfagg_metrics_fold_device with two groupings, the namespace pair + layer + both subnet labels, and owner / type / namespace of both sides
 + direction. Reported: the median wall time of a whole call (the memset of the tables, fold, count, scan, emit, the read-back), the
 group counts, the bytes a flow's lane reads by this tool's own count, and that read rate as a fraction of a read-stream rate measured in
-the same run (a sum over 1 GiB). --k8s-trace covers the k_metrics_* kernels and the memset's fill kernel."""
+the same run (a sum over 1 GiB). --k8s-trace covers the k_metrics_* kernels and the memset's fill kernel.
+
+--content (with --k8s --net --metrics): the content metrics leg on top, on the same records, rows and net rows in the same run:
+nfagg_metrics_fold_content_device with synthetic feature parts on about half of the flows and three groupings shaped like the
+operator's: the namespace pair + an RTT histogram of ten bounds, the namespace pair + the response code + a DNS-latency histogram,
+the namespace pair + drop cause + drop state with both drop sums. It prints beside the plain --metrics leg's time; that time and the
+read-stream rate are what its number is read against. NFAGG_LIB selects the library, so a build with another LDS table size
+(-DNFAGG_METC_LDS_SLOTS) is measured by a second process of the same command."""
 import io
 import os
 import queue
@@ -187,6 +194,41 @@ def metrics_leg(tab, k8s, d_ev, m, d_rows, d_net):
           f"measured here ({rate / 1e9:.0f} GB/s over 1 GiB)")
 
 
+def metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net):
+    L = nf._lib
+    ns = L.DIM_SRC_K8S(0) | L.DIM_DST_K8S(0)
+    rtt = [int(b * 1e9) for b in (.005, .01, .025, .05, .1, .25, .5, 1, 2.5, 5)]
+    dns = [int(b * 1000) for b in (.005, .01, .025, .05, .1, .25, .5, 1, 2.5, 5, 10)]
+    specs = [dict(dims=ns, value=(L.MET_VALUE_RTT_NS,), hist=1, bounds=rtt),
+             dict(dims=ns, xdims=L.XDIM_DNS_RCODE, value=(L.MET_VALUE_DNS_LATENCY_MS,), hist=1, bounds=dns),
+             dict(dims=ns, xdims=L.XDIM_DROP_CAUSE | L.XDIM_DROP_STATE, value=(L.MET_VALUE_DROP_BYTES, L.MET_VALUE_DROP_PACKETS))]
+    d_present, d_parts = device_parts(m)
+    feat = (d_present.data_ptr(), {k: d_parts[k].data_ptr() for k in ("additional", "dns", "drops")})
+    caps = [1 << 16] * 3
+    with tab.metrics_table_specs(k8s, specs) as met:
+        while True:
+            d_groups = [torch.empty(c * 128, dtype=torch.uint8, device="cuda") for c in caps]
+            fold = lambda: tab.metrics_fold_content_device(met, d_ev.data_ptr(), m, d_rows.data_ptr(), d_net.data_ptr(), caps,  # noqa: E731
+                                                           [g.data_ptr() for g in d_groups], feat)
+            rc, counts = fold()
+            if rc == nf.OK:
+                break
+            caps = [min(4 * c, L.MET_MAX_GROUPS) if n > c else c for n, c in zip(counts, caps)]
+        (rc, counts), dt = timed(fold)
+        assert rc == nf.OK
+        groups = [g[: c * 128].cpu().numpy().view(nf.METRIC_GROUP_CONTENT) for g, c in zip(d_groups, counts)]
+        assert all(int(g["flows"].sum()) == m for g in groups)
+    with_parts = int((d_present != 0).sum())
+    # a lane reads the three 16-byte units of its record, its 8 bytes of Kubernetes rows, its 8 bytes of net row (unused by these
+    # groupings, loaded all the same), two class words per grouping, its present byte and, with the parts, one 16-byte unit of each of three
+    per_flow = 48 + 8 + 8 + 3 * 8 + 1 + 48 * with_parts / m
+    rate = read_stream_rate()
+    print(f"  metrics content ({os.path.basename(L.LIB_PATH)}) {m} flows, parts on {with_parts} -> {' + '.join(str(c) for c in counts)} groups "
+          f"(caps {', '.join(str(c) for c in caps)}) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s; "
+          f"{per_flow:.0f} B read per flow = {per_flow * m / dt / 1e9:.1f} GB/s per call, {per_flow * m / dt / rate:.3f} of the read-stream rate "
+          f"measured here ({rate / 1e9:.0f} GB/s over 1 GiB)")
+
+
 def per_byte(what, m, dt, wrote):
     print(f"  {what:8s} {m} flows -> {wrote} bytes ({wrote / m:.1f} B/line) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s, "
           f"{dt / wrote * 1e12:.3f} ps per output byte")
@@ -210,7 +252,7 @@ def line(what, m, dt, wrote, extra_per_flow):
     return dt
 
 
-for flows in ((10_000_000,) if CONTENT or TLS else (1_000_000, 10_000_000)):
+for flows in ((10_000_000,) if (CONTENT or TLS) and not K8S else (1_000_000, 10_000_000)):
     if K8S:
         torch.cuda.empty_cache()
     n = 4 * flows
@@ -268,6 +310,8 @@ for flows in ((10_000_000,) if CONTENT or TLS else (1_000_000, 10_000_000)):
                         del d_out
                         if METRICS:
                             metrics_leg(tab, k8s, d_ev, m, d_rows, d_net)
+                            if CONTENT:
+                                metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net)
                     del d_net
             del d_ev, d_off, d_rows
             continue
