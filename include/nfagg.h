@@ -1485,6 +1485,96 @@ int nfagg_metrics_fold_content_device(nfagg_handle* h, const nfagg_metrics_table
 int nfagg_flp_enum_name(int kind, uint32_t raw, void* out, size_t cap, size_t* len);
 
 /* ------------------------------------------------------------------ */
+/* Conversation tracking — the per-call fold under flowlogs-pipeline's  */
+/* `extract conntrack` (pkg/pipeline/extract/conntrack: conntrack.go    */
+/* 59-142 Extract, hash.go 41-110 computeHash, aggregator.go 144-199).  */
+/* The reference walks every flow: six gob encoders and three FNV-64a   */
+/* hashes, a map lookup by the 64-bit total, the aggregators, one or    */
+/* two list moves. Here the device does what is per flow and order-free */
+/* (the filter, the three hashes, the GROUP BY connection, the sums,    */
+/* the minimum and the maximum) and the host visits CONNECTIONS: it     */
+/* keeps what depends on order and on the clock (the store, the         */
+/* timeouts, maxConnectionsTracked, the newConnection / heartbeat /     */
+/* endConnection records). Three positions per connection make the host */
+/* part exact without seeing the flows: the call's first tracked flow   */
+/* of the connection (who creates it, and in which order connections    */
+/* are admitted), its last one (where it ends up in the expiry list)    */
+/* and its first one with FIN (where it goes terminating).              */
+/*                                                                      */
+/* The key definition is the one NetObserv's operator generates, fixed  */
+/* here: field groups src = [SrcAddr, SrcPort], dst = [DstAddr,         */
+/* DstPort], common = [Proto]; the hash over [common], A = src, B =     */
+/* dst. A flow is tracked only if RecordToMap writes Proto (ethertype   */
+/* 0x0800 or 0x86DD) and the protocol is 6, 17 or 132 (conntrack.go     */
+/* 59-64). A field's bytes are those of a fresh gob encoder:            */
+/*   [count][type id, zigzag][0x00][value]                              */
+/* with 0x0c for a string (uint length, bytes: the text net.IP.String() */
+/* prints) and 0x06 for the uint16 ports and the uint8 protocol (a gob  */
+/* uint below 128 is one byte, else the negated byte count and the      */
+/* minimal big-endian bytes). FNV-64a (offset 0xcbf29ce484222325, prime */
+/* 0x100000001b3) over a group's fields gives its hash; the total is    */
+/* FNV-64a over the 8 big-endian bytes of the common hash, of           */
+/* min(hashA, hashB) and of the other one. These bytes are written from */
+/* encoding/gob's documentation and pinned to the restatement of        */
+/* tests/conntrack_ref.py, not to a Go run (tools/go/conntrack_hash_dump */
+/* prints Go's values on a host that has Go).                           */
+/*                                                                      */
+/* Differences from the reference, by design:                           */
+/*  - one `now` per call: the reference reads its clock several times   */
+/*    per Extract;                                                      */
+/*  - sums are exact integers, so above 2^53 a result is the correctly  */
+/*    rounded sum and the reference's running float64 is not;           */
+/*  - two endpoint pairs whose 64-bit totals collide are one connection */
+/*    on both sides (the reference's store is keyed by the total        */
+/*    alone); only the AB / BA split of such a merged connection may    */
+/*    differ.                                                           */
+/* Not here: conversation records and _HashId / _RecordType in the      */
+/* device's JSON lines; a store that lives in device memory across      */
+/* calls; a least and a greatest Bytes / Packets, and extremes per      */
+/* direction (the partial carries one least start, one greatest end).   */
+/* ------------------------------------------------------------------ */
+
+#define NFAGG_CONN_MAX_CONNS (1u << 22)
+#define NFAGG_CONN_NO_IDX 0xFFFFFFFFu
+
+typedef struct nfagg_conn_options {
+    uint32_t struct_size;             /* sizeof(nfagg_conn_options) */
+    uint32_t reserved_;               /* 0 */
+    int64_t now_unix_ns;              /* currentTime and the monotonic clock at that instant, as in nfagg_flp_options: */
+    uint64_t mono_now_ns;             /*   TimeFlowStartMs / TimeFlowEndMs are record.go:90-97's times in milliseconds */
+} nfagg_conn_options;
+
+/* What one call's tracked flows of one connection fold to, 128 bytes. "Same" (index 0) are the flows whose hashA equals
+ * first_hash_a, "other" (index 1) the rest: the host maps them to AB / BA by comparing first_hash_a with the connection's
+ * stored hashA. */
+typedef struct nfagg_conn_partial {
+    uint64_t hash_total;              /* the connection's 64-bit total (_HashId is its lower-case hex) */
+    uint64_t first_hash_a;            /* hashA of the flow at first_idx */
+    uint32_t first_idx, last_idx;     /* least and greatest position of the connection's tracked flows in this call */
+    uint32_t first_fin_idx;           /* least position of a TCP flow with FIN (0x01) in Flags, else NFAGG_CONN_NO_IDX */
+    uint32_t flags_or;                /* OR of the TCP flows' Flags (only protocol 6 has the key) */
+    uint64_t flows[2], bytes[2], packets[2];   /* exact integer sums (modulo 2^64) */
+    int64_t start_ms_min, end_ms_max; /* least TimeFlowStartMs, greatest TimeFlowEndMs */
+    uint64_t pad_[4];                 /* 0 */
+} nfagg_conn_partial;
+
+/* Fold n records (HOST memory). hash_ids (n values, may be NULL) receives every flow's total, 0 for a flow the filter
+ * discards; *n_discarded their number. out has room for cap (<= NFAGG_CONN_MAX_CONNS, else NFAGG_ERANGE) partials and
+ * receives the call's connections in unspecified order (first_idx is unique per connection: sort by it), *n_conns their
+ * number. More connections than cap: NFAGG_TRUNCATED, nothing is written to out, *n_conns is some value greater than cap (a
+ * lower bound), hash_ids and *n_discarded are complete. n == 0 is valid: NFAGG_OK, nothing written. n above 2^32 - 2:
+ * NFAGG_ERANGE. The connections live in an open-addressed table of max(1024, the power of two >= 2 * min(cap, n)) slots,
+ * probed linearly from the low bits of fmix64(hash_total) (MurmurHash3's 64-bit finalizer). */
+int nfagg_conn_fold(nfagg_handle* h, const void* records, size_t n, const nfagg_conn_options* opt, uint64_t* hash_ids, uint32_t cap,
+                    nfagg_conn_partial* out, uint32_t* n_conns, uint32_t* n_discarded);
+/* Same with records, hash_ids and out in DEVICE memory (records and out 16-byte, hash_ids 8-byte aligned). */
+int nfagg_conn_fold_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_conn_options* opt, uint64_t* d_hash_ids,
+                           uint32_t cap, nfagg_conn_partial* d_out, uint32_t* n_conns, uint32_t* n_discarded);
+/* The three hashes of one 144-byte record as the fold computes them: returns the total, *hash_a and *hash_b (either may be
+ * NULL) the endpoint hashes. A record the filter discards, or record == NULL: 0, and 0 in both. Pure CPU, no handle. */
+uint64_t nfagg_conn_hash(const void* record, uint64_t* hash_a, uint64_t* hash_b);
+
+/* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */
 /* ------------------------------------------------------------------ */
 

@@ -169,6 +169,23 @@ class MetricSpec(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("dims", C.c_uint32), ("xdims", C.c_uint32), ("value", C.c_uint8 * 2), ("hist", C.c_uint8),
                 ("pad_", C.c_uint8), ("n_bounds", C.c_uint32), ("pad2_", C.c_uint32), ("bounds", C.c_int64 * 32)]
 
+
+# conversation tracking (nfagg_conn_*)
+CONN_MAX_CONNS, CONN_NO_IDX = 1 << 22, 0xFFFFFFFF
+
+
+class ConnOptions(C.Structure):
+    """nfagg_conn_options (include/nfagg.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved_", C.c_uint32), ("now_unix_ns", C.c_int64), ("mono_now_ns", C.c_uint64)]
+
+
+class ConnPartial(C.Structure):
+    """nfagg_conn_partial (include/nfagg.h), 128 bytes; table.CONN_PARTIAL is the numpy view."""
+    _fields_ = [("hash_total", C.c_uint64), ("first_hash_a", C.c_uint64), ("first_idx", C.c_uint32), ("last_idx", C.c_uint32),
+                ("first_fin_idx", C.c_uint32), ("flags_or", C.c_uint32), ("flows", C.c_uint64 * 2), ("bytes", C.c_uint64 * 2),
+                ("packets", C.c_uint64 * 2), ("start_ms_min", C.c_int64), ("end_ms_max", C.c_int64), ("pad_", C.c_uint64 * 4)]
+
+
 TLS_VERSION, TLS_CIPHER_SUITE, TLS_GROUP = 0, 1, 2
 TLS_NAME_MAX, TLS_MAX_ROWS = 63, 256
 
@@ -287,6 +304,9 @@ SIGNATURES = {
     "nfagg_metrics_fold_content_device": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp),
                                                     C.POINTER(C.c_uint32)]),
     "nfagg_flp_enum_name": (C.c_int, [C.c_int, C.c_uint32, _vp, _sz, _psz]),
+    "nfagg_conn_fold": (C.c_int, [_vp, _vp, _sz, C.POINTER(ConnOptions), _vp, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nfagg_conn_fold_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(ConnOptions), _vp, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nfagg_conn_hash": (C.c_uint64, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

@@ -75,13 +75,16 @@ struct nfagg_handle {
         DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record
         DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record
         DevBuf met_slots, met_out;                   // nfagg_metrics_fold: control words and the groupings' tables; the host entry point's groups
+        DevBuf conn_slots, conn_flow;                // nfagg_conn_fold: control words and the connection table; per flow hashA and slot
+        DevBuf conn_ids, conn_out;                   //   the host entry point's hash ids and partials
         std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
         std::vector<uint8_t> h_flp_esc;
         template <typename F> void each(F f) {
             for (DevBuf* b : {&local_off, &block_sum, &block_base, &names, &ipfix_name_rows, &flp_rows, &flp_esc, &flp_n_deferred,
                               &in_records, &out, &out_offsets, &out_extra[0], &out_extra[1]}) f(*b);
             for (DevBuf& b : pb_feat) f(b);
-            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows, &net_rows, &met_slots, &met_out}) f(*b);
+            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows, &net_rows, &met_slots, &met_out,
+                              &conn_slots, &conn_flow, &conn_ids, &conn_out}) f(*b);
         }
     } enc;
     // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch

@@ -797,6 +797,33 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, [int(x) for x in n_a]
 
+    # -- conversation tracking (nfagg_conn_*): the per-call fold under FLP's `extract conntrack`; conntrack.ConnTrack is the host side
+    def conn_fold(self, records: np.ndarray, now_unix_ns: int, mono_now_ns: int, cap: int = 4096, hash_ids: bool = True):
+        """nfagg_conn_fold. Returns (rc, partials, n_conns, hash_ids, n_discarded): partials is a CONN_PARTIAL array in unspecified
+        order (sort by first_idx); with rc == L.TRUNCATED it is empty and n_conns is a lower bound above cap. hash_ids: uint64
+        per record, 0 for a discarded flow, or None when not asked for."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        opt = L.ConnOptions(struct_size=C.sizeof(L.ConnOptions), now_unix_ns=now_unix_ns, mono_now_ns=mono_now_ns)
+        out = np.zeros(min(int(cap), L.CONN_MAX_CONNS), dtype=CONN_PARTIAL)
+        ids = np.zeros(n, dtype=np.uint64) if hash_ids else None
+        n_conns, n_disc = C.c_uint32(0), C.c_uint32(0)
+        rc = L.lib.nfagg_conn_fold(self._h, r.ctypes.data_as(C.c_void_p) if n else None, n, C.byref(opt),
+                                   ids.ctypes.data_as(C.c_void_p) if hash_ids and n else None, int(cap),
+                                   out.ctypes.data_as(C.c_void_p) if out.size else None, C.byref(n_conns), C.byref(n_disc))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, out[:n_conns.value if rc == L.OK else 0], n_conns.value, ids, n_disc.value
+
+    def conn_fold_device(self, d_records: int, n: int, now_unix_ns: int, mono_now_ns: int, d_hash_ids: int, cap: int, d_out: int):
+        """Device-resident variant (raw device pointers; d_hash_ids = 0: none; d_out: room for cap partials of 128 bytes, 16-byte
+        aligned). Returns (rc, n_conns, n_discarded)."""
+        opt = L.ConnOptions(struct_size=C.sizeof(L.ConnOptions), now_unix_ns=now_unix_ns, mono_now_ns=mono_now_ns)
+        n_conns, n_disc = C.c_uint32(0), C.c_uint32(0)
+        rc = L.lib.nfagg_conn_fold_device(self._h, C.c_void_p(d_records or None), n, C.byref(opt), C.c_void_p(d_hash_ids or None), int(cap),
+                                          C.c_void_p(d_out or None), C.byref(n_conns), C.byref(n_disc))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, n_conns.value, n_disc.value
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -1317,6 +1344,19 @@ METRIC_GROUP_CONTENT = np.dtype([("src_class", "<u4"), ("dst_class", "<u4"), ("s
                                  ("flows_with_packets", "<u8"), ("value_sum", "<u8", (2,)), ("flows_with_value", "<u8", (2,)),
                                  ("pad2_", "<u8", (3,))])                                                                   # nfagg_metric_group_content
 assert METRIC_GROUP_CONTENT.itemsize == 128
+
+
+CONN_PARTIAL = np.dtype([("hash_total", "<u8"), ("first_hash_a", "<u8"), ("first_idx", "<u4"), ("last_idx", "<u4"), ("first_fin_idx", "<u4"),
+                         ("flags_or", "<u4"), ("flows", "<u8", (2,)), ("bytes", "<u8", (2,)), ("packets", "<u8", (2,)), ("start_ms_min", "<i8"),
+                         ("end_ms_max", "<i8"), ("pad_", "<u8", (4,))])                                              # nfagg_conn_partial
+assert CONN_PARTIAL.itemsize == 128 == C.sizeof(L.ConnPartial)
+
+
+def conn_hash(record) -> tuple:
+    """nfagg_conn_hash of one 144-byte record: (hashTotal, hashA, hashB); (0, 0, 0) for a record the conntrack filter discards."""
+    buf = (C.c_uint8 * 144).from_buffer_copy(bytes(record)[:144])
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    return L.lib.nfagg_conn_hash(buf, C.byref(a), C.byref(b)), a.value, b.value
 
 
 class MetricsTable(_CallerTable):

@@ -40,7 +40,12 @@ nfagg_metrics_fold_content_device with synthetic feature parts on about half of 
 operator's: the namespace pair + an RTT histogram of ten bounds, the namespace pair + the response code + a DNS-latency histogram,
 the namespace pair + drop cause + drop state with both drop sums. It prints beside the plain --metrics leg's time; that time and the
 read-stream rate are what its number is read against. NFAGG_LIB selects the library, so a build with another LDS table size
-(-DNFAGG_METC_LDS_SLOTS) is measured by a second process of the same command."""
+(-DNFAGG_METC_LDS_SLOTS) is measured by a second process of the same command.
+
+--conntrack (with --k8s --net --metrics): the conversation fold on top, on the same records in the same run, beside the plain metrics
+fold: nfagg_conn_fold_device with hash ids. Reported: the median wall time of a whole call (the memset of the table, claim, finish,
+count, scan, emit, the read-back), the connections and the discarded flows, and the bytes a flow's lanes read and write by this
+tool's own count. --k8s-trace covers the k_conn_* kernels."""
 import io
 import os
 import queue
@@ -66,6 +71,7 @@ TLS = "--tls" in sys.argv[1:]
 K8S = "--k8s" in sys.argv[1:]
 NET = "--net" in sys.argv[1:]
 METRICS = "--metrics" in sys.argv[1:]
+CONNTRACK = "--conntrack" in sys.argv[1:]
 NET_CATEGORIES = [("cat-%d" % c, ["172.%d.%d.0/24" % (16 + c, k) for k in range(8)] + ["2001:db8:%x::/48" % (16 * c + k) for k in range(1)]) for c in range(5)] + \
                  [("pods", ["100.64.0.0/10"]), ("everything", ["0.0.0.0/0", "::/0"])]
 K8S_ROWS = 100_000
@@ -138,7 +144,7 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|fillBuffer|scan", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|fillBuffer|scan", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
             grid = int(row.get("Grid_Size_X") or row.get("Grid_Size") or 0)
@@ -147,9 +153,13 @@ def k8s_trace(root):
     for (short, grid), tv in sorted(spans.items(), key=lambda kv: (kv[0][1] > 4_000_000, kv[0][0], kv[0][1])):
         v = [us for _, us in tv]
         print(f"  {short:48s} grid {grid:9d}: {float(np.median(v)):9.1f}  min {min(v):9.1f}  max {max(v):9.1f}  ({len(v)} launches)")
+    # the conversation table's memset is among the many fills of one grid: the longest fills, which are the largest tables'
+    for (short, grid), tv in sorted(spans.items()):
+        if "fillBuffer" in short and len(tv) > 8:
+            print(f"  {short} grid {grid}, the twelve longest launches: " + " ".join("%.1f" % us for us in sorted((us for _, us in tv), reverse=True)[:12]))
     # the metrics fold's grid is capped, so both sizes of the leg launch the same one: its launches in start order, the smaller size first
     for (short, grid), tv in sorted(spans.items()):
-        if short.startswith("k_metrics_fold"):
+        if short.startswith("k_metrics_fold") or short.startswith("k_conn_claim"):     # k_conn_claim: the tool's overflowed first attempts come first
             print(f"  {short} grid {grid}, launches in start order: " + " ".join("%.1f" % us for _, us in sorted(tv)))
 
 
@@ -192,6 +202,32 @@ def metrics_leg(tab, k8s, d_ev, m, d_rows, d_net):
     print(f"  metrics  {m} flows -> {counts[0]} + {counts[1]} groups (caps {caps[0]}, {caps[1]}) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s; "
           f"{per_flow} B read per flow = {per_flow * m / dt / 1e9:.1f} GB/s per call, {per_flow * m / dt / rate:.3f} of the read-stream rate "
           f"measured here ({rate / 1e9:.0f} GB/s over 1 GiB)")
+
+
+def conntrack_leg(tab, d_ev, m):
+    L = nf._lib
+    cap = 1 << 18
+    d_ids = torch.empty(m, dtype=torch.int64, device="cuda")
+    while True:
+        d_out = torch.empty(cap * 128, dtype=torch.uint8, device="cuda")
+        fold = lambda: tab.conn_fold_device(d_ev.data_ptr(), m, NOW, MONO, d_ids.data_ptr(), cap, d_out.data_ptr())  # noqa: E731
+        rc, n_conns, n_disc = fold()
+        if rc == nf.OK:
+            break
+        assert cap < L.CONN_MAX_CONNS, "more connections than NFAGG_CONN_MAX_CONNS"
+        cap = min(max(4 * cap, n_conns), L.CONN_MAX_CONNS)
+    (rc, n_conns, n_disc), dt = timed(fold)
+    assert rc == nf.OK
+    parts = d_out[: n_conns * 128].cpu().numpy().view(nf.CONN_PARTIAL)
+    assert int(parts["flows"].sum()) == m - n_disc and int((d_ids == 0).sum()) >= n_disc
+    # k_conn_claim reads five 16-byte units of the record and writes the hash id, hashA and the slot; k_conn_finish reads the slot,
+    # hashA, two units of the record again and, for a flow that is not its connection's first, that flow's hashA
+    later = m - n_disc - n_conns
+    read, wrote = 80 + 12 + 32 + 8 * later / m, 20
+    slots = max(1024, 1 << (2 * min(cap, m) - 1).bit_length())
+    print(f"  conntrack {m} flows -> {n_conns} connections, {n_disc} discarded (cap {cap}, {slots} slots = {slots * 128 >> 20} MiB zeroed per call) "
+          f"in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s; {read:.0f} B read + {wrote} B written per flow by this tool's count = "
+          f"{(read + wrote) * m / dt / 1e9:.1f} GB/s per call")
 
 
 def metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net):
@@ -310,6 +346,8 @@ for flows in ((10_000_000,) if (CONTENT or TLS) and not K8S else (1_000_000, 10_
                         del d_out
                         if METRICS:
                             metrics_leg(tab, k8s, d_ev, m, d_rows, d_net)
+                            if CONNTRACK:
+                                conntrack_leg(tab, d_ev, m)
                             if CONTENT:
                                 metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net)
                     del d_net
