@@ -63,9 +63,9 @@ def records(nf, flows):
     return r
 
 
-def maps(recs):
+def maps(recs, now=NOW, mono=MONO):
     raw = np.ascontiguousarray(recs).view(np.uint8).reshape(-1, 144)
-    return [R.record_to_map(raw[i].tobytes(), NOW, MONO, [], AGENT, RECEIVED) for i in range(len(raw))]
+    return [R.record_to_map(raw[i].tobytes(), now, mono, [], AGENT, RECEIVED) for i in range(len(raw))]
 
 
 def norm(v):

@@ -2,7 +2,11 @@
 of the restatement (tests/conntrack_ref.py) on the seeded stream of test_flp_json_gpu.py, through the host and the device entry
 point; streams built for the edges (three interfaces, two spellings of one address, src == dst, 5 000 flows of one
 connection, the cap and one below it, a cap above the maximum); the crafted table collisions of
-tests/golden/conntrack_collisions.json in both arrival orders; and ConnTrack.extract over four calls against the restatement."""
+tests/golden/conntrack_collisions.json in both arrival orders; and ConnTrack.extract over four calls against the restatement.
+
+The collisions here are folded by one wave of one workgroup. tests/test_crafted_conntrack_gpu.py has the contended cases: crafted
+homes and first key words scattered over seven workgroups, probe chains that wrap, full tables, a table above 2^20 slots, the wave
+ballots' lane patterns, and other clocks than this file's one."""
 import json
 import os
 import sys
@@ -32,16 +36,16 @@ def by_first(parts):
     return parts[np.argsort(parts["first_idx"], kind="stable")]
 
 
-def fold_both(nf, tab, recs, cap=4096):
+def fold_both(nf, tab, recs, cap=4096, now=T.NOW, mono=T.MONO):
     """The host call, then the device call into a buffer of exactly the cap with 0xAB canaries over it and 128 bytes behind.
     Both must agree; returns (rc, partials by first_idx, n_conns, hash ids, n_discarded)."""
     import torch
     n = len(recs)
-    rc, parts, n_conns, ids, n_disc = tab.conn_fold(recs, T.NOW, T.MONO, cap=cap)
+    rc, parts, n_conns, ids, n_disc = tab.conn_fold(recs, now, mono, cap=cap)
     d_recs = E.dev(recs) if n else None
     d_ids = torch.full((n * 8 + 8,), 0xAB, dtype=torch.uint8, device="cuda")
     d_out = torch.full((cap * 128 + 128,), 0xAB, dtype=torch.uint8, device="cuda")
-    rc_d, n_conns_d, n_disc_d = tab.conn_fold_device(d_recs.data_ptr() if n else 0, n, T.NOW, T.MONO, d_ids.data_ptr(), cap, d_out.data_ptr())
+    rc_d, n_conns_d, n_disc_d = tab.conn_fold_device(d_recs.data_ptr() if n else 0, n, now, mono, d_ids.data_ptr(), cap, d_out.data_ptr())
     torch.cuda.synchronize()
     assert (rc_d, n_disc_d) == (rc, n_disc)
     assert n_conns_d == n_conns if rc == nf.OK else (n_conns > cap and n_conns_d > cap)
@@ -54,9 +58,9 @@ def fold_both(nf, tab, recs, cap=4096):
     return rc, got, n_conns, ids, n_disc
 
 
-def check_fold(nf, tab, recs, cap=4096):
-    parts, ids, n_disc = CT.fold(T.maps(recs), T.KD)
-    rc, got, n_conns, got_ids, got_disc = fold_both(nf, tab, recs, cap)
+def check_fold(nf, tab, recs, cap=4096, now=T.NOW, mono=T.MONO):
+    parts, ids, n_disc = CT.fold(T.maps(recs, now, mono), T.KD)
+    rc, got, n_conns, got_ids, got_disc = fold_both(nf, tab, recs, cap, now, mono)
     assert (rc, n_conns, got_disc) == (nf.OK, len(parts), n_disc)
     assert got_ids.tolist() == ids
     want = T.partial_array(nf, parts)
