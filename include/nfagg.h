@@ -1296,6 +1296,105 @@ int nfagg_encode_flp_json_net_device(nfagg_handle* h, const void* d_records, siz
  * digits; 0 for an unknown policy. The write kernels size their LDS windows by it. */
 uint32_t nfagg_flp_json_net_max_line(int policy);
 
+/* The flow logs of flowlogs-pipeline's extract conntrack stage (pkg/pipeline/extract/conntrack/conntrack.go:70-74, 120-126,
+ * 281-287): nfagg_encode_flp_json_net (same three policies, same tables, same outputs and return codes, nothing deferred) for
+ * the flows the stage tracks, and no line for the others.
+ *   - A flow is tracked when its ethertype is 0x0800 or 0x86DD and its protocol is 6, 17 or 132: the condition under which
+ *     a line has SrcPort / DstPort, and the one nfagg_conn_fold applies. The encoder reads it from the record, never from
+ *     the id (a tracked flow's id may be 0), and knows nothing of the store: a flow turned away by maxConnectionsTracked
+ *     still has its line.
+ *   - An untracked flow's line has length zero: line_offsets[i + 1] == line_offsets[i].
+ *   - A tracked flow's line is byte for byte its nfagg_encode_flp_json_net line with
+ *     ,"_HashId":"<hex>","_RecordType":"flowLog" in front of the closing brace; <hex> is strconv.FormatUint(hash_ids[i], 16):
+ *     lower case, no padding, "0" for 0. Both keys sort behind every other key of the line.
+ * hash_ids: n values, what nfagg_conn_fold wrote for these records; NULL with n > 0 is NFAGG_EINVAL.
+ * All pointers HOST memory (hash_ids needs no alignment here: it is copied to the device): */
+int nfagg_encode_flp_json_conn(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                               const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                               const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const uint64_t* hash_ids,
+                               const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes);
+/* Same with every data pointer (d_rows, d_hash_ids and those inside d_features too) in DEVICE memory; d_hash_ids 8-byte
+ * aligned: the d_hash_ids of nfagg_conn_fold_device as they are. */
+int nfagg_encode_flp_json_conn_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                      const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                      const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const uint64_t* d_hash_ids,
+                                      const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes);
+/* The longest line nfagg_encode_flp_json_conn can write: nfagg_flp_json_net_max_line(policy) plus 53 (the two keys with
+ * sixteen hex digits); 0 for an unknown policy. The write kernels size their LDS windows by it. */
+uint32_t nfagg_flp_json_conn_max_line(int policy);
+
+/* The conversation records of extract conntrack (newConnection, endConnection, heartbeat) as JSON lines: conn.go:101-114
+ * (toGenericMap: aggregates, first / last values, the keys prevail), then addHashField / addTypeField / addIsFirstField, then
+ * the Kubernetes enrichment and the subnet labels of the stages behind conntrack, keys sorted. n conversations arrive as two
+ * parallel arrays. CARRIERS: n ordinary 144-byte flow records that carry the connection's keys: src_ip / dst_ip / src_port /
+ * dst_port as the connection stores them (after swapAB), transport_protocol, an IP ethertype; nothing else of a carrier is
+ * read, and because they are flow records the Kubernetes and the net join run on them as on flows. VALUES: one
+ * nfagg_conn_values each. A LAYOUT compiled from the stage's outputFields says which columns a line has. */
+#define NFAGG_CONN_MAX_FIELDS 32
+#define NFAGG_CONN_NAME_MAX 64
+enum { NFAGG_CONN_OP_COUNT = 0, NFAGG_CONN_OP_SUM = 1, NFAGG_CONN_OP_MIN = 2, NFAGG_CONN_OP_MAX = 3, NFAGG_CONN_OP_FIRST = 4, NFAGG_CONN_OP_LAST = 5 };
+enum { NFAGG_CONN_IN_NONE = 0, NFAGG_CONN_IN_BYTES = 1, NFAGG_CONN_IN_PACKETS = 2, NFAGG_CONN_IN_TIME_START = 3, NFAGG_CONN_IN_TIME_END = 4,
+       NFAGG_CONN_IN_SRC_ADDR = 5, NFAGG_CONN_IN_DST_ADDR = 6, NFAGG_CONN_IN_SRC_PORT = 7, NFAGG_CONN_IN_DST_PORT = 8, NFAGG_CONN_IN_PROTO = 9,
+       NFAGG_CONN_IN_SRC_MAC = 10, NFAGG_CONN_IN_DST_MAC = 11, NFAGG_CONN_IN_ETYPE = 12, NFAGG_CONN_IN_DSCP = 13, NFAGG_CONN_IN_IF_DIRECTIONS = 14 };
+enum { NFAGG_CONN_RECORD_NEW = 0, NFAGG_CONN_RECORD_END = 1, NFAGG_CONN_RECORD_HEARTBEAT = 2 };
+
+/* One outputField. Served: count (input ignored); sum over BYTES or PACKETS; min over TIME_START and max over TIME_END, not
+ * split; first / last over any input from TIME_START on, not split. */
+typedef struct nfagg_conn_field {
+    const char* name;                 /* name_len bytes, 1..NFAGG_CONN_NAME_MAX */
+    uint32_t name_len;
+    uint8_t op, input, split_ab, pad_;
+} nfagg_conn_field;
+
+/* What `first` / `last` can copy from one flow, 80 bytes. */
+typedef struct nfagg_conn_snapshot {
+    uint8_t src_ip[16], dst_ip[16];
+    uint16_t src_port, dst_port, eth_protocol;
+    uint8_t proto, dscp;
+    uint8_t src_mac[6], dst_mac[6];
+    uint8_t n_dirs, dirs[7];          /* IfDirections: n_dirs (1..7) values */
+    uint32_t pad_;
+    int64_t start_ms, end_ms;
+} nfagg_conn_snapshot;
+
+typedef struct nfagg_conn_values {    /* 256 bytes */
+    uint64_t hash_total;
+    uint8_t record_type, is_first, pad_[6];
+    uint64_t flows[2], bytes[2], packets[2];   /* AB, BA */
+    int64_t start_ms_min, end_ms_max;
+    nfagg_conn_snapshot first, last;
+    uint64_t pad2_[2];
+} nfagg_conn_values;
+
+typedef struct nfagg_conn_layout nfagg_conn_layout;
+/* Compile n_fields outputFields into a sorted column program: every key fragment (,"name": escaped as interface names are)
+ * rendered once, the columns in byte order together with the five keys, the blocks (DstK8S_*, DstSubnetLabel, K8S_FlowLayer,
+ * SrcK8S_*, SrcSubnetLabel; a block sorts as its prefix) and _HashId, _IsFirst, _RecordType. A split field gives name_AB and
+ * name_BA. A field named as a key is dropped: the keys prevail. NFAGG_EINVAL (nfagg_last_error names the field): more than
+ * NFAGG_CONN_MAX_FIELDS fields, an empty or too long name, a name beginning SrcK8S_ or DstK8S_ or equal to a block or meta
+ * column, duplicates after the _AB / _BA expansion, an operation / input pair that is not served. NFAGG_ERANGE: the layout's
+ * longest possible line exceeds what the write kernel's window leaves. h == NULL builds and checks on the host alone. */
+int nfagg_conn_layout_create(nfagg_handle* h, const nfagg_conn_field* fields, size_t n_fields, nfagg_conn_layout** layout);
+void nfagg_conn_layout_destroy(nfagg_conn_layout* layout);
+uint32_t nfagg_conn_layout_columns(const nfagg_conn_layout* layout);
+uint32_t nfagg_conn_layout_max_line(const nfagg_conn_layout* layout);
+/* Column `column`'s fragment in sorted order (nothing for a block). Host only; NFAGG_TRUNCATED with *n_out when cap is smaller. */
+int nfagg_conn_layout_render(const nfagg_conn_layout* layout, uint32_t column, void* out, size_t cap, size_t* n_out);
+
+/* One line per conversation, columns in the layout's order. Aggregates (count, sum, min, max) are float64 in the reference and
+ * omitted when zero; below 2^53 in magnitude jsoniter prints their decimal digits. A conversation with an aggregate column of
+ * magnitude >= 2^53 is DEFERRED: a zero-length line, deferred[i] = 1, the caller formats it. first / last columns are written
+ * even when 0. Outputs and return codes as nfagg_encode_flp_json_net; deferred (n bytes) and n_deferred may be NULL.
+ * All pointers HOST memory: */
+int nfagg_encode_conn_json(nfagg_handle* h, const void* carriers, const nfagg_conn_values* values, size_t n, const nfagg_conn_layout* layout,
+                           const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, void* out, size_t out_cap,
+                           uint64_t* line_offsets, uint8_t* deferred, size_t* n_deferred, size_t* out_bytes);
+/* Same with carriers, values, out, line_offsets and deferred in DEVICE memory (16-byte aligned). */
+int nfagg_encode_conn_json_device(nfagg_handle* h, const void* d_carriers, const nfagg_conn_values* d_values, size_t n,
+                                  const nfagg_conn_layout* layout, const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table,
+                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred, size_t* n_deferred,
+                                  size_t* out_bytes);
+
 /* ------------------------------------------------------------------ */
 /* Flow metrics — the GROUP BY under flowlogs-pipeline's `encode prom`  */
 /* counters (pkg/pipeline/encode/metrics_common.go:107-125 ProcessCounter, */
@@ -1528,10 +1627,13 @@ int nfagg_flp_enum_name(int kind, uint32_t raw, void* out, size_t cap, size_t* l
 /*    on both sides (the reference's store is keyed by the total        */
 /*    alone); only the AB / BA split of such a merged connection may    */
 /*    differ.                                                           */
-/* Not here: conversation records and _HashId / _RecordType in the      */
-/* device's JSON lines; a store that lives in device memory across      */
-/* calls; a least and a greatest Bytes / Packets, and extremes per      */
-/* direction (the partial carries one least start, one greatest end).   */
+/* The flow logs' _HashId / _RecordType in the device's JSON lines:      */
+/* nfagg_encode_flp_json_conn, which takes this fold's hash_ids.        */
+/* The conversation records as JSON lines: nfagg_encode_conn_json.      */
+/* Not here: a store                                                    */
+/* that lives in device memory across calls; a least and a greatest     */
+/* Bytes / Packets, and extremes per direction (the partial carries one */
+/* least start, one greatest end).                                      */
 /* ------------------------------------------------------------------ */
 
 #define NFAGG_CONN_MAX_CONNS (1u << 22)

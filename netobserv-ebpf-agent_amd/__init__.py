@@ -16,7 +16,8 @@ from .table import (FlowTable, FlowGroup, NfaggError, PinnedRecords, key_hash, s
                     host_threads, host_info, device_numa_node, ipfix_template, ipfix_options, IPFIX_TEMPLATE_ID_V4,
                     IPFIX_TEMPLATE_ID_V6, flp_options, NetevTable, netev_render, TlsNames, GO_TLS_NAMES, K8sTable, k8s_render,
                     NetTable, net_render, net_cidrs, NET_ROW, MetricsTable, METRIC_GROUP, metrics_group_hash, K8S_FIELDS,
-                    METRIC_GROUP_CONTENT, metrics_group_hash_content, flp_enum_name, CONN_PARTIAL, conn_hash)
+                    METRIC_GROUP_CONTENT, metrics_group_hash_content, flp_enum_name, CONN_PARTIAL, conn_hash,
+                    ConnLayout, CONN_VALUES, CONN_SNAPSHOT)
 from .accounter import (Accounter, NewAccounter, NewRecord, Record, IntfDirUdn, NewIntfDirUdn, Metrics, NoOp, CLOSE,
                         SetInterfaceNamer, SetGlobalIP)
 from . import synth

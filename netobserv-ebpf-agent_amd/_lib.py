@@ -174,6 +174,18 @@ class MetricSpec(C.Structure):
 CONN_MAX_CONNS, CONN_NO_IDX = 1 << 22, 0xFFFFFFFF
 
 
+CONN_MAX_FIELDS, CONN_NAME_MAX = 32, 64
+CONN_OPS = {"count": 0, "sum": 1, "min": 2, "max": 3, "first": 4, "last": 5}                                      # NFAGG_CONN_OP_*
+CONN_INPUTS = {"": 0, "Bytes": 1, "Packets": 2, "TimeFlowStartMs": 3, "TimeFlowEndMs": 4, "SrcAddr": 5, "DstAddr": 6, "SrcPort": 7, "DstPort": 8,
+               "Proto": 9, "SrcMac": 10, "DstMac": 11, "Etype": 12, "Dscp": 13, "IfDirections": 14}                 # NFAGG_CONN_IN_*
+CONN_RECORD_TYPES = {"newConnection": 0, "endConnection": 1, "heartbeat": 2}                                      # NFAGG_CONN_RECORD_*
+
+
+class ConnField(C.Structure):
+    """nfagg_conn_field (include/nfagg.h)."""
+    _fields_ = [("name", C.c_char_p), ("name_len", C.c_uint32), ("op", C.c_uint8), ("input", C.c_uint8), ("split_ab", C.c_uint8), ("pad_", C.c_uint8)]
+
+
 class ConnOptions(C.Structure):
     """nfagg_conn_options (include/nfagg.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("reserved_", C.c_uint32), ("now_unix_ns", C.c_int64), ("mono_now_ns", C.c_uint64)]
@@ -293,6 +305,9 @@ SIGNATURES = {
     "nfagg_encode_flp_json_net": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
     "nfagg_encode_flp_json_net_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
     "nfagg_flp_json_net_max_line": (C.c_uint32, [C.c_int]),
+    "nfagg_encode_flp_json_conn": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_encode_flp_json_conn_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, _sz, _vp, _psz]),
+    "nfagg_flp_json_conn_max_line": (C.c_uint32, [C.c_int]),
     "nfagg_metrics_table_create": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(_vp)]),
     "nfagg_metrics_table_destroy": (None, [_vp]),
     "nfagg_metrics_n_classes": (C.c_uint32, [_vp, C.c_uint32, C.c_int]),
@@ -306,6 +321,13 @@ SIGNATURES = {
     "nfagg_flp_enum_name": (C.c_int, [C.c_int, C.c_uint32, _vp, _sz, _psz]),
     "nfagg_conn_fold": (C.c_int, [_vp, _vp, _sz, C.POINTER(ConnOptions), _vp, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "nfagg_conn_fold_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(ConnOptions), _vp, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nfagg_conn_layout_create": (C.c_int, [_vp, C.POINTER(ConnField), _sz, C.POINTER(_vp)]),
+    "nfagg_conn_layout_destroy": (None, [_vp]),
+    "nfagg_conn_layout_columns": (C.c_uint32, [_vp]),
+    "nfagg_conn_layout_max_line": (C.c_uint32, [_vp]),
+    "nfagg_conn_layout_render": (C.c_int, [_vp, C.c_uint32, _vp, _sz, _psz]),
+    "nfagg_encode_conn_json": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _psz, _psz]),
+    "nfagg_encode_conn_json_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_conn_hash": (C.c_uint64, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),

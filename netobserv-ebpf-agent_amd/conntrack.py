@@ -20,7 +20,10 @@ their AB / BA split may differ.
 Served here: the key definition NetObserv's operator generates (src = [SrcAddr, SrcPort], dst = [DstAddr, DstPort], common =
 [Proto], hash over [common], A = src, B = dst); `count`; `sum` over Bytes or Packets; `min` over TimeFlowStartMs and `max`
 over TimeFlowEndMs, not split (the partial carries one least start and one greatest end); `first` / `last` over a key
-RecordToMap always writes and that needs no table: FIRST_LAST_FIELDS. Everything else Validate accepts raises ValueError."""
+RecordToMap always writes and that needs no table: FIRST_LAST_FIELDS. Everything else Validate accepts raises ValueError.
+
+Output: apply / extract return the records as dicts. conversations returns the conversation records as the two arrays of
+FlowTable.encode_conn_json, extract_lines the stage's whole output as the bytes of its JSON lines, encoded on the device."""
 import json
 import re
 
@@ -186,7 +189,8 @@ def _text(v) -> str:                    # conn.go:127-178: a key and a selector 
 
 
 class _Conn:
-    __slots__ = ("hash_a", "hash_total", "keys", "flows", "bytes", "packets", "start_min", "end_max", "first", "last", "expiry", "next_heartbeat", "reported")
+    __slots__ = ("hash_a", "hash_total", "keys", "flows", "bytes", "packets", "start_min", "end_max", "first", "last", "expiry", "next_heartbeat", "reported",
+                 "carrier", "snap_first", "snap_last")
 
 
 class _Lists:
@@ -224,6 +228,12 @@ class ConnTrack:
 
     def __len__(self):
         return len(self.group_of)
+
+    def layout(self, table=None):
+        """The stage's outputFields as a table.ConnLayout for FlowTable.encode_conn_json: on table's device, or checked on the host
+        alone with table=None."""
+        from .table import ConnLayout
+        return ConnLayout([dict(name=f["name"], operation=f["op"], input=f["inp"], splitAB=f["split"]) for f in self.fields], table)
 
     # ---- a record's values, as RecordToMap writes them
     @staticmethod
@@ -290,10 +300,9 @@ class ConnTrack:
             return g["active"].rec[h], g, True
         return g["terminating"].rec[h], g, False
 
-    def apply(self, partials, records, now: int, now_unix_ns: int, mono_now_ns: int, hash_ids=None, flow_maps=None) -> list:
-        """Extract over one call's partials (CONN_PARTIAL, any order) and the records they were folded from. now: the call's
-        clock in nanoseconds. With the flowLog type on, hash_ids (the fold's) is needed, and flow_maps[i], when given, is the
-        map of flow i to copy into its record; without it a flowLog record is {"_flow": i} beside the two meta fields."""
+    def _walk(self, partials, records, now: int, now_unix_ns: int, mono_now_ns: int, emit):
+        """Extract's pass over one call's partials and the store. emit(c, rtype, is_first) renders a conversation record as the
+        connection stands at that moment. Returns ({first_idx: newConnection record}, [end records, then heartbeats])."""
         self.now = now
         recs = np.ascontiguousarray(records).view(FLOW_RECORD).reshape(-1)
         parts = np.asarray(partials)
@@ -313,6 +322,7 @@ class ConnTrack:
                 swap = self.swap_ab and tcp and (int(r0["metrics"]["flags"]) & SYN_ACK) == SYN_ACK
                 c = _Conn()
                 c.hash_a, c.hash_total, c.reported = (hb if swap else ha), h, False
+                c.carrier, c.snap_first = _carrier(r0, swap), _snapshot(r0, now_unix_ns, mono_now_ns)
                 c.keys = {k: self._field(r0, k, now_unix_ns, mono_now_ns) for k in KEY_FIELDS}
                 if swap:
                     c.keys["SrcAddr"], c.keys["DstAddr"] = c.keys["DstAddr"], c.keys["SrcAddr"]
@@ -332,9 +342,10 @@ class ConnTrack:
                 c.start_min = self._field(r0, "TimeFlowStartMs", now_unix_ns, mono_now_ns)
                 c.end_max = self._field(r0, "TimeFlowEndMs", now_unix_ns, mono_now_ns)
                 c.last = {f["name"]: self._field(r0, f["inp"], now_unix_ns, mono_now_ns) for f in self.fields if f["op"] == "last"}
+                c.snap_last = c.snap_first
                 if "newConnection" in self.out_types:
                     c.reported = True
-                    new_at[first_idx] = self._meta(self._to_map(c), h, "newConnection", True)
+                    new_at[first_idx] = emit(c, "newConnection", True)
                 c.flows, c.bytes, c.packets = [0, 0], [0, 0], [0, 0]
                 c.start_min, c.end_max = int(p["start_ms_min"]), int(p["end_ms_max"])
             else:
@@ -345,6 +356,7 @@ class ConnTrack:
                 dst[1] += ba[k]
             rl = recs[last_idx]
             c.last = {f["name"]: self._field(rl, f["inp"], now_unix_ns, mono_now_ns) for f in self.fields if f["op"] == "last"}
+            c.snap_last = _snapshot(rl, now_unix_ns, mono_now_ns)
             if active:                                                 # a terminating connection stays where it is (store.go:114-117, 143-146)
                 if self.detect_end and fin_idx != L.CONN_NO_IDX:
                     to_term.append((fin_idx, h))
@@ -360,20 +372,7 @@ class ConnTrack:
             c.expiry = now + g["end"]
             del g["active"].expiry[h]
             g["active"].expiry[h] = None
-        out = []
-        if "flowLog" in self.out_types:
-            if hash_ids is None:
-                raise ValueError("the flowLog record type needs the fold's hash_ids")
-            k, m = recs["id"], recs["metrics"]
-            tracked = np.isin(m["eth_protocol"], (0x0800, 0x86DD)) & np.isin(k["transport_protocol"], (6, 17, 132))
-            for i in np.nonzero(tracked)[0].tolist():
-                if i in new_at:
-                    out.append(new_at[i])
-                fl = dict(flow_maps[i]) if flow_maps is not None else {"_flow": i}
-                out.append(self._meta(fl, int(hash_ids[i]), "flowLog"))
-        else:
-            out += [new_at[i] for i in sorted(new_at)]
-        ended = []
+        tail, ended = [], []
         for g in self.groups:                                          # store.go:213-229: per group, terminating before active, front to back
             for lists in (g["terminating"], g["active"]):
                 for h in list(lists.expiry):
@@ -386,7 +385,7 @@ class ConnTrack:
         if "endConnection" in self.out_types:
             for c in ended:
                 first, c.reported = not c.reported, True
-                out.append(self._meta(self._to_map(c), c.hash_total, "endConnection", first))
+                tail.append(emit(c, "endConnection", first))
         if "heartbeat" in self.out_types:
             for g in self.groups:                                      # store.go:231-251
                 lists = g["active"]
@@ -398,21 +397,212 @@ class ConnTrack:
                     del lists.heartbeat[h]
                     lists.heartbeat[h] = None
                     first, c.reported = not c.reported, True
-                    out.append(self._meta(self._to_map(c), c.hash_total, "heartbeat", first))
-        return out
+                    tail.append(emit(c, "heartbeat", first))
+        return new_at, tail
 
-    def extract(self, table, records, now: int, now_unix_ns: int, mono_now_ns: int, cap: int = 4096, flow_maps=None) -> list:
-        """Extract(flowLogs) for the records of one call: the fold on table's device, then apply(). cap doubles while the call
-        has more connections than it, up to L.CONN_MAX_CONNS."""
+    def apply(self, partials, records, now: int, now_unix_ns: int, mono_now_ns: int, hash_ids=None, flow_maps=None) -> list:
+        """Extract over one call's partials (CONN_PARTIAL, any order) and the records they were folded from. now: the call's
+        clock in nanoseconds. With the flowLog type on, hash_ids (the fold's) is needed, and flow_maps[i], when given, is the
+        map of flow i to copy into its record; without it a flowLog record is {"_flow": i} beside the two meta fields."""
+        new_at, tail = self._walk(partials, records, now, now_unix_ns, mono_now_ns,
+                                  lambda c, rtype, is_first: self._meta(self._to_map(c), c.hash_total, rtype, is_first))
+        out = []
+        if "flowLog" in self.out_types:
+            if hash_ids is None:
+                raise ValueError("the flowLog record type needs the fold's hash_ids")
+            for i in np.nonzero(_tracked(records))[0].tolist():
+                if i in new_at:
+                    out.append(new_at[i])
+                fl = dict(flow_maps[i]) if flow_maps is not None else {"_flow": i}
+                out.append(self._meta(fl, int(hash_ids[i]), "flowLog"))
+        else:
+            out += [new_at[i] for i in sorted(new_at)]
+        return out + tail
+
+    def _fold(self, table, records, now_unix_ns: int, mono_now_ns: int, cap: int):
+        """(partials, hash_ids or None) of one call; cap doubles while the call has more connections than it."""
         want_ids = "flowLog" in self.out_types
         while True:
             rc, parts, n_conns, ids, _ = table.conn_fold(records, now_unix_ns, mono_now_ns, cap=cap, hash_ids=want_ids)
             if rc == L.OK:
-                break
+                return parts, ids
             if cap >= L.CONN_MAX_CONNS:
                 raise ValueError("more than %d connections in one call" % L.CONN_MAX_CONNS)
             cap = min(max(2 * cap, n_conns), L.CONN_MAX_CONNS)
+
+    def extract(self, table, records, now: int, now_unix_ns: int, mono_now_ns: int, cap: int = 4096, flow_maps=None) -> list:
+        """Extract(flowLogs) for the records of one call: the fold on table's device, then apply(). cap doubles while the call
+        has more connections than it, up to L.CONN_MAX_CONNS."""
+        parts, ids = self._fold(table, records, now_unix_ns, mono_now_ns, cap)
         return self.apply(parts, records, now, now_unix_ns, mono_now_ns, hash_ids=ids, flow_maps=flow_maps)
+
+    # ---- the conversation records as the arrays FlowTable.encode_conn_json takes, and the stage's output as lines
+    def conversations(self, partials, records, now: int, now_unix_ns: int, mono_now_ns: int):
+        """apply() with the call's conversation records as arrays instead of dicts: (carriers FLOW_RECORD[m], values CONN_VALUES[m],
+        order int64[m]), in the order Extract emits them. order[j] is the index of the flow in front of whose record a
+        newConnection record goes; it is the number of records for an endConnection or heartbeat record, which follow every
+        flow. Flow logs are not part of it: they are the records themselves (FlowTable.encode_flp_json_conn)."""
+        from .table import CONN_VALUES
+        n = np.ascontiguousarray(records).nbytes // 144
+
+        def row(c, rtype, is_first):
+            v = np.zeros((), dtype=CONN_VALUES)
+            v["hash_total"], v["record_type"], v["is_first"] = c.hash_total, L.CONN_RECORD_TYPES[rtype], 1 if is_first else 0
+            for name, src in (("flows", c.flows), ("bytes", c.bytes), ("packets", c.packets)):
+                if max(src) > _M64:
+                    raise OverflowError("connection %x: %s above 2^64" % (c.hash_total, name))
+                v[name] = src
+            v["start_ms_min"], v["end_ms_max"], v["first"], v["last"] = c.start_min, c.end_max, c.snap_first, c.snap_last
+            return c.carrier, v
+
+        new_at, tail = self._walk(partials, records, now, now_unix_ns, mono_now_ns, row)
+        rows = [(i, new_at[i]) for i in sorted(new_at)] + [(n, r) for r in tail]
+        carriers, values = np.zeros(len(rows), dtype=FLOW_RECORD), np.zeros(len(rows), dtype=CONN_VALUES)
+        for j, (_, (car, val)) in enumerate(rows):
+            carriers[j], values[j] = car, val
+        return carriers, values, np.array([i for i, _ in rows], dtype=np.int64)
+
+    def format_deferred(self, table, carrier, values, layout, k8s, net) -> bytes:
+        """The line of a conversation the device deferred (an aggregate of magnitude >= 2^53), formatted here. Only the aggregate
+        columns need the shortest-float digits, so the device writes the line once more with the aggregates zeroed, which omits
+        exactly those columns, and the host puts them back in their places in the sorted order: the layout's key fragment and
+        the digits of jsoniter's WriteFloat64 (strconv 'f', precision -1: the shortest digits that round-trip, padded with zeros)."""
+        v = np.array(values, dtype=values.dtype).reshape(1)
+        agg = {(src, side): _agg_value(v[0], src, side) for src in _AGG_SOURCES for side in (0, 1, 2)}
+        for name in _AGG_SOURCES:
+            v[name] = 0
+        buf, off, deferred = table.encode_conn_json(np.array(carrier, dtype=FLOW_RECORD).reshape(1), v, layout, k8s, net)
+        assert not deferred[0] and off[1] == len(buf)
+        members = _members(bytes(buf[:-2]))                          # without }\n
+        out, at = [], 0
+        for k, (name, kind, arg) in enumerate(self._columns()):
+            if kind == "agg":
+                if agg[arg] != 0:
+                    out.append(layout.render(k)[1:] + _float_f(agg[arg]))
+            elif kind == "block":                                     # no field name may begin with a block's: its members are contiguous
+                while at < len(members) and members[at].startswith(b'"' + name):
+                    out.append(members[at])
+                    at += 1
+            else:
+                out.append(members[at])
+                at += 1
+        assert at == len(members) and k + 1 == layout.n_columns
+        return b"{" + b",".join(out) + b"}\n"
+
+    def _columns(self):
+        """The columns of a conversation line in the layout's order (byte order; a block sorts as its prefix): [(name, kind, arg)],
+        kind "agg" with arg (source, side: 0 both, 1 AB, 2 BA), "block", or "one" for a column that is always one member."""
+        cols = [(k.encode(), "one", None) for k in KEY_FIELDS + ("_HashId", "_IsFirst", "_RecordType")]
+        cols += [(k, "block", None) for k in (b"DstK8S_", b"DstSubnetLabel", b"K8S_FlowLayer", b"SrcK8S_", b"SrcSubnetLabel")]
+        for f in self.fields:
+            name = f["name"].encode("latin-1")
+            if f["op"] in ("first", "last"):
+                cols.append((name, "one", None))
+                continue
+            src = "flows" if f["op"] == "count" else "start_ms_min" if f["op"] == "min" else "end_ms_max" if f["op"] == "max" else f["inp"].lower()
+            cols += [(name + b"_AB", "agg", (src, 1)), (name + b"_BA", "agg", (src, 2))] if f["split"] else [(name, "agg", (src, 0))]
+        keys = [k.encode() for k in KEY_FIELDS]
+        return sorted(c for k, c in enumerate(cols) if k < len(keys) or c[0] not in keys)      # the keys prevail
+
+    def extract_lines(self, table, records, now: int, now_unix_ns: int, mono_now_ns: int, names, tls_names, k8s, net, agent_ip=None,
+                      time_received: int = 0, unknown: bytes = b"unknown", layout=None, cap: int = 4096, present=None, parts=None, rows=None,
+                      netev_table=None) -> bytes:
+        """Extract for the records of one call as the bytes a direct-FLP pipeline writes behind it: the fold and apply, the flow logs
+        through FlowTable.encode_flp_json_conn (when the flowLog type is on), the conversation records through
+        FlowTable.encode_conn_json, a deferred one through format_deferred, and the lines in Extract's order: a newConnection
+        record in front of its first flow's line, behind the flows the endConnection records, then the heartbeats. names,
+        agent_ip, time_received, unknown, present .. netev_table: as encode_flp_json_conn takes them. layout: self.layout(table),
+        built for the call when not given."""
+        own = layout is None
+        layout = self.layout(table) if own else layout
+        try:
+            folded, ids = self._fold(table, records, now_unix_ns, mono_now_ns, cap)
+            carriers, values, order = self.conversations(folded, records, now, now_unix_ns, mono_now_ns)
+            buf, off, deferred = table.encode_conn_json(carriers, values, layout, k8s, net)
+            buf = buf.tobytes()
+            conv = [buf[int(off[j]):int(off[j + 1])] if not deferred[j] else self.format_deferred(table, carriers[j], values[j], layout, k8s, net)
+                    for j in range(len(order))]
+            if "flowLog" not in self.out_types:
+                return b"".join(conv)
+            fbuf, foff = table.encode_flp_json_conn(records, tls_names, k8s, net, ids, now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown,
+                                                    present=present, parts=parts, rows=rows, netev_table=netev_table)
+            fbuf, out, at = fbuf.tobytes(), [], 0
+            for j, i in enumerate(order.tolist()):                   # the flows' lines up to flow i, then conversation j
+                out += [fbuf[int(foff[at]):int(foff[i])], conv[j]]
+                at = i
+            return b"".join(out) + fbuf[int(foff[at]):]
+        finally:
+            if own:
+                layout.close()
+
+
+_AGG_SOURCES = ("flows", "bytes", "packets", "start_ms_min", "end_ms_max")
+
+
+def _agg_value(v, src, side) -> int:
+    """An aggregate column's integer: side 0 both (or the time), 1 AB, 2 BA."""
+    if src in ("start_ms_min", "end_ms_max"):
+        return int(v[src])
+    return int(v[src][0]) + int(v[src][1]) if side == 0 else int(v[src][side - 1])
+
+
+def _float_f(v: int) -> bytes:
+    """strconv.FormatFloat(float64(v), 'f', -1, 64): repr() has the shortest digits that round-trip; 'f' pads them with zeros."""
+    from decimal import Decimal
+    return format(Decimal(repr(float(v))), "f").split(".")[0].encode()
+
+
+def _members(body: bytes) -> list:
+    """The members of one JSON object's text without its closing brace, split at the commas outside strings and arrays."""
+    out, start, depth, k = [], 1, 0, 1
+    while k < len(body):
+        ch = body[k]
+        if ch == 0x22:                                                # a string: to its closing quote, over escapes
+            k += 1
+            while body[k] != 0x22:
+                k += 2 if body[k] == 0x5C else 1
+        elif ch in (0x5B, 0x7B):
+            depth += 1
+        elif ch in (0x5D, 0x7D):
+            depth -= 1
+        elif ch == 0x2C and depth == 0:
+            out.append(body[start:k])
+            start = k + 1
+        k += 1
+    return out + [body[start:]]
+
+
+def _tracked(records):
+    """The flows the stage's filter keeps (an IP ethertype and protocol 6, 17 or 132): those with SrcPort and DstPort."""
+    recs = np.ascontiguousarray(records).view(FLOW_RECORD).reshape(-1)
+    return np.isin(recs["metrics"]["eth_protocol"], (0x0800, 0x86DD)) & np.isin(recs["id"]["transport_protocol"], (6, 17, 132))
+
+
+def _carrier(r0, swap: bool):
+    """The flow record that carries a connection's keys: the addresses and ports of its first flow (swapped by swapAB), the
+    protocol and the ethertype."""
+    c = np.zeros((), dtype=FLOW_RECORD)
+    a, b = ("dst", "src") if swap else ("src", "dst")
+    c["id"]["src_ip"], c["id"]["dst_ip"] = r0["id"][a + "_ip"], r0["id"][b + "_ip"]
+    c["id"]["src_port"], c["id"]["dst_port"] = r0["id"][a + "_port"], r0["id"][b + "_port"]
+    c["id"]["transport_protocol"], c["metrics"]["eth_protocol"] = r0["id"]["transport_protocol"], r0["metrics"]["eth_protocol"]
+    return c
+
+
+def _snapshot(rec, now_unix_ns: int, mono_now_ns: int):
+    """nfagg_conn_snapshot of one flow: what FIRST_LAST_FIELDS can copy from it."""
+    from .table import CONN_SNAPSHOT
+    k, m = rec["id"], rec["metrics"]
+    s = np.zeros((), dtype=CONN_SNAPSHOT)
+    for name in ("src_ip", "dst_ip", "src_port", "dst_port"):
+        s[name] = k[name]
+    s["proto"], s["eth_protocol"], s["dscp"], s["src_mac"], s["dst_mac"] = k["transport_protocol"], m["eth_protocol"], m["dscp"], m["src_mac"], m["dst_mac"]
+    dirs = ConnTrack._field(rec, "IfDirections", now_unix_ns, mono_now_ns)
+    s["n_dirs"] = len(dirs)
+    s["dirs"][:len(dirs)] = dirs
+    s["start_ms"] = unix_milli(now_unix_ns, mono_now_ns, int(m["start_mono_time_ts"]))
+    s["end_ms"] = unix_milli(now_unix_ns, mono_now_ns, int(m["end_mono_time_ts"]))
+    return s
 
 
 def _conn_hash(rec):

@@ -6,6 +6,7 @@
 #include <string.h>
 #include <algorithm>
 #include <initializer_list>
+#include <string>
 #include <vector>
 
 #include "../../include/nfagg.h"
@@ -371,9 +372,11 @@ static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, Fl
 // counter are not used), and the network events are an option: rows and table both, or neither (*ne = nullptr).
 // with_k8s: the *_k8s entry points, whose table is required as well and whose lines carry the Kubernetes keys.
 // with_net: the *_net entry points, which take the table of the transform network rules on top of that.
+// with_conn: the *_conn entry points, which take the flows' hash ids on top of that (DEVICE memory in the device core).
 struct FlpTlsArgs {
     const nfagg_tls_names* names; bool with_k8s = false; const nfagg_k8s_table* k8s = nullptr;
     bool with_net = false; const nfagg_net_table* net = nullptr;
+    bool with_conn = false; const uint64_t* hash_ids = nullptr;
 };
 static int netev_optional(nfagg_handle* h, const NetevArgs** ne, size_t n) {
     if (!*ne) return NFAGG_OK;
@@ -393,8 +396,9 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
     if ((rc = encode_flp_check(h, opt)) != NFAGG_OK) return rc;
     if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !d_line_offsets ||
-        (n && !d_records))
+        (n && !d_records) || (tls && tls->with_conn && n && !tls->hash_ids))
         return fail(h, NFAGG_EINVAL, "null argument");
+    if (tls && tls->with_conn && ((uintptr_t)tls->hash_ids & 7u) != 0) return fail(h, NFAGG_EINVAL, "hash ids must be 8-byte aligned");
     if (tls && (tls->names->h != h || !tls->names->d_mem)) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
     const nfagg_k8s_table* k8s = tls && tls->with_k8s ? tls->k8s : nullptr;
     if (k8s && (k8s->h != h || !k8s->d_slots)) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
@@ -432,6 +436,15 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
             e = launch_net_resolve(d_records, n, N, k8s_rows, (const uint32_t*)k8s->d_host_ids, K.n_rows, net_reporter(k8s, opt), (uint2*)h->enc.net_rows.p,
                                    h->stream);
             if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
+            if (tls->with_conn) {
+                const uint64_t* ids = tls->hash_ids;
+                return encode_two_pass(h, n, "FLP JSON flow logs of extract conntrack", "write", d_out, out_cap, out_bytes, nullptr,
+                    [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+                        return launch_flp_conn_size(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, ids, rows, local_off, block_sum, block_base, h->stream); },
+                    [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+                        return launch_flp_conn_write(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, ids, rows, local_off, block_base, d_out,
+                                                     d_line_offsets, h->stream); });
+            }
             return encode_two_pass(h, n, "FLP JSON with transform network keys", "write", d_out, out_cap, out_bytes, nullptr,
                 [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
                     return launch_flp_net_size(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_sum, block_base, h->stream); },
@@ -462,7 +475,7 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
     int rc = encode_flp_check(h, opt);
     if (rc != NFAGG_OK) return rc;
     if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !line_offsets ||
-        (n && !records))
+        (n && !records) || (tls && tls->with_conn && n && !tls->hash_ids))
         return fail(h, NFAGG_EINVAL, "null argument");
     if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
     if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
@@ -472,7 +485,17 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
             if (feat && n) { int rc2 = stage_pb_features(h, feat, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
             NetevArgs dne{};
             if (ne) { int rc2 = stage_netev_rows(h, ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
-            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, tls, opt, d_out, out_cap, d_offsets,
+            FlpTlsArgs dtls = tls ? *tls : FlpTlsArgs{};
+            if (dtls.with_conn) {                                         // the hash ids, uploaded
+                dtls.hash_ids = nullptr;
+                if (n) {
+                    int rc2 = ensure_buf(h, h->enc.conn_ids, n * sizeof(uint64_t));
+                    if (rc2 != NFAGG_OK) return rc2;
+                    HIP_TRY(h, hipMemcpyAsync(h->enc.conn_ids.p, tls->hash_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+                    dtls.hash_ids = (const uint64_t*)h->enc.conn_ids.p;
+                }
+            }
+            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, tls ? &dtls : nullptr, opt, d_out, out_cap, d_offsets,
                                           deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
 }
 
@@ -574,6 +597,208 @@ int nfagg_encode_flp_json_net(nfagg_handle* h, const void* records, size_t n, co
     const NetevArgs ne{rows, netev_table};
     const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
     return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+}
+
+// ---- extract conntrack's flow logs: the *_net line with _HashId and _RecordType, no line for a flow the stage does not track
+uint32_t nfagg_flp_json_conn_max_line(int policy) { return flp_conn_max_line(policy); }
+
+int nfagg_encode_flp_json_conn_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                      const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                                      const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const uint64_t* d_hash_ids,
+                                      const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{d_rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table, true, d_hash_ids};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+}
+
+int nfagg_encode_flp_json_conn(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                               const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                               const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const uint64_t* hash_ids,
+                               const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
+    const NetevArgs ne{rows, netev_table};
+    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table, true, hash_ids};
+    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+}
+
+// ---- extract conntrack's conversation records as JSON lines (nfagg_conn_json.hip): the layout, then the two entry points
+int nfagg_conn_layout_create(nfagg_handle* h, const nfagg_conn_field* fields, size_t n_fields, nfagg_conn_layout** layout) {
+    if (!layout || (n_fields && !fields)) return fail(h, NFAGG_EINVAL, "null argument");
+    *layout = nullptr;
+    if (n_fields > NFAGG_CONN_MAX_FIELDS) return fail(h, NFAGG_EINVAL, "%zu output fields, more than %d", n_fields, NFAGG_CONN_MAX_FIELDS);
+    struct Named { std::string name; ConnCol col; uint32_t value_max; };
+    std::vector<Named> cols;
+    static const char* const kKeys[5] = {"SrcAddr", "DstAddr", "SrcPort", "DstPort", "Proto"};
+    static const uint32_t kKeyMax[5] = {kConnAddrMax, kConnAddrMax, 5, 5, 3};
+    for (uint32_t k = 0; k < 5; k++) cols.push_back({kKeys[k], {kConnColKey, k, 0, 0}, kKeyMax[k]});
+    static const char* const kBlocks[5] = {"DstK8S_", "DstSubnetLabel", "K8S_FlowLayer", "SrcK8S_", "SrcSubnetLabel"};
+    const uint32_t layer_max = sizeof(",\"K8S_FlowLayer\":\"infra\"") - 1;
+    const uint32_t block_max[5] = {kK8sMaxRendered, kNetFragMax, layer_max, kK8sMaxRendered, kNetFragMax};
+    for (uint32_t k = 0; k < 5; k++) cols.push_back({kBlocks[k], {kConnColBlock, k, 0, 0}, block_max[k]});
+    static const char* const kMeta[3] = {"_HashId", "_IsFirst", "_RecordType"};
+    static const uint32_t kMetaMax[3] = {kConnHashIdMax, kConnIsFirstMax, kConnRecordTypeMax};
+    for (uint32_t k = 0; k < 3; k++) cols.push_back({kMeta[k], {kConnColMeta, k, 0, 0}, kMetaMax[k]});
+    for (size_t k = 0; k < n_fields; k++) {
+        const nfagg_conn_field& f = fields[k];
+        if (!f.name_len || !f.name) return fail(h, NFAGG_EINVAL, "output field %zu: empty name", k);
+        if (f.name_len > NFAGG_CONN_NAME_MAX) return fail(h, NFAGG_EINVAL, "output field %zu: name of %u bytes, more than %d", k, f.name_len, NFAGG_CONN_NAME_MAX);
+        const std::string name(f.name, f.name_len);
+        if (name.compare(0, 7, "SrcK8S_") == 0 || name.compare(0, 7, "DstK8S_") == 0)
+            return fail(h, NFAGG_EINVAL, "output field %zu (%s): the name begins with a Kubernetes block's prefix", k, name.c_str());
+        for (const char* r : {"K8S_FlowLayer", "SrcSubnetLabel", "DstSubnetLabel", "_HashId", "_IsFirst", "_RecordType"})
+            if (name == r) return fail(h, NFAGG_EINVAL, "output field %zu (%s): the name is a column of the line's own", k, name.c_str());
+        const bool split = f.split_ab != 0;
+        uint32_t src = 0, vmax = kConnAggMax, kind = kConnColAgg;
+        switch (f.op) {
+        case NFAGG_CONN_OP_COUNT: src = 0; break;
+        case NFAGG_CONN_OP_SUM:
+            if (f.input != NFAGG_CONN_IN_BYTES && f.input != NFAGG_CONN_IN_PACKETS)
+                return fail(h, NFAGG_EINVAL, "output field %zu (%s): sum is served over Bytes and Packets", k, name.c_str());
+            src = f.input == NFAGG_CONN_IN_BYTES ? 1 : 2;
+            break;
+        case NFAGG_CONN_OP_MIN:
+            if (f.input != NFAGG_CONN_IN_TIME_START || split) return fail(h, NFAGG_EINVAL, "output field %zu (%s): min is served over TimeFlowStartMs, not split", k, name.c_str());
+            src = 3;
+            break;
+        case NFAGG_CONN_OP_MAX:
+            if (f.input != NFAGG_CONN_IN_TIME_END || split) return fail(h, NFAGG_EINVAL, "output field %zu (%s): max is served over TimeFlowEndMs, not split", k, name.c_str());
+            src = 4;
+            break;
+        case NFAGG_CONN_OP_FIRST: case NFAGG_CONN_OP_LAST:
+            if (f.input < NFAGG_CONN_IN_TIME_START || f.input > NFAGG_CONN_IN_IF_DIRECTIONS || split)
+                return fail(h, NFAGG_EINVAL, "output field %zu (%s): first / last take one of the snapshot's inputs, not split", k, name.c_str());
+            kind = kConnColSnap;
+            src = f.input | (f.op == NFAGG_CONN_OP_LAST ? 1u << 8 : 0u);
+            vmax = (f.input == NFAGG_CONN_IN_SRC_ADDR || f.input == NFAGG_CONN_IN_DST_ADDR) ? kConnAddrMax
+                   : (f.input == NFAGG_CONN_IN_SRC_MAC || f.input == NFAGG_CONN_IN_DST_MAC) ? kConnMacMax
+                   : f.input == NFAGG_CONN_IN_IF_DIRECTIONS ? kConnDirsMax : kConnI64Max;
+            break;
+        default: return fail(h, NFAGG_EINVAL, "output field %zu (%s): unknown operation %u", k, name.c_str(), f.op);
+        }
+        for (uint32_t side = split ? 1 : 0; side <= (split ? 2u : 0u); side++) {
+            const std::string full = name + (side == 1 ? "_AB" : side == 2 ? "_BA" : "");
+            bool is_key = false;
+            for (const Named& c : cols) {
+                if (c.name != full) continue;
+                if (c.col.kind != kConnColKey) return fail(h, NFAGG_EINVAL, "output field %zu: duplicate name %s", k, full.c_str());
+                is_key = true;                                      // conn.go:109-112: the keys prevail
+            }
+            if (!is_key) cols.push_back({full, {kind, kind == kConnColAgg ? src | side << 8 : src, 0, 0}, vmax});
+        }
+    }
+    std::stable_sort(cols.begin(), cols.end(), [](const Named& a, const Named& b) { return a.name < b.name; });
+    nfagg_conn_layout* t = new nfagg_conn_layout;
+    t->h = h;
+    size_t longest = 2;                                             // the closing brace and the newline; the opening brace takes a comma's place
+    for (Named& c : cols) {
+        if (c.col.kind != kConnColBlock) {
+            uint8_t esc[2 + 6 * (NFAGG_CONN_NAME_MAX + 3)];
+            const uint32_t el = flp_escape(c.name.data(), (uint32_t)c.name.size(), esc);
+            c.col.frag_off = (uint32_t)t->blob.size();
+            c.col.frag_len = el + 2;
+            t->blob.push_back(',');
+            t->blob.insert(t->blob.end(), esc, esc + el);
+            t->blob.push_back(':');
+            t->blob.resize((t->blob.size() + 15) / 16 * 16, 0);
+        }
+        longest += c.col.frag_len + c.value_max;
+        t->cols.push_back(c.col);
+    }
+    t->max_line = (uint32_t)longest;
+    if (longest > kConnLineCap) {
+        delete t;
+        return fail(h, NFAGG_ERANGE, "the layout's longest line has %zu bytes, more than %u", longest, kConnLineCap);
+    }
+    if (h) {
+        auto up = [&]() -> int {
+            const size_t cols_bytes = t->cols.size() * sizeof(ConnCol);            // a multiple of 16
+            std::vector<uint8_t> img(cols_bytes + t->blob.size() + 16, 0);
+            memcpy(img.data(), t->cols.data(), cols_bytes);
+            memcpy(img.data() + cols_bytes, t->blob.data(), t->blob.size());
+            HIP_TRY(h, hipSetDevice(h->device));
+            HIP_TRY(h, hipMalloc(&t->d_mem, img.size()));
+            HIP_TRY(h, hipMemcpy(t->d_mem, img.data(), img.size(), hipMemcpyHostToDevice));
+            return NFAGG_OK;
+        };
+        const int rc = up();
+        if (rc != NFAGG_OK) { nfagg_conn_layout_destroy(t); return rc; }
+    }
+    *layout = t;
+    return NFAGG_OK;
+}
+
+void nfagg_conn_layout_destroy(nfagg_conn_layout* t) {
+    if (!t) return;
+    if (t->h && t->d_mem) {
+        (void)hipSetDevice(t->h->device);
+        (void)hipStreamSynchronize(t->h->stream);
+        (void)hipFree(t->d_mem);
+    }
+    delete t;
+}
+
+uint32_t nfagg_conn_layout_columns(const nfagg_conn_layout* t) { return t ? (uint32_t)t->cols.size() : 0u; }
+uint32_t nfagg_conn_layout_max_line(const nfagg_conn_layout* t) { return t ? t->max_line : 0u; }
+
+int nfagg_conn_layout_render(const nfagg_conn_layout* t, uint32_t column, void* out, size_t cap, size_t* n_out) {
+    if (!t || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
+    if (column >= t->cols.size()) return fail(nullptr, NFAGG_EINVAL, "column %u of %zu", column, t->cols.size());
+    const ConnCol& c = t->cols[column];
+    *n_out = c.frag_len;
+    if (c.frag_len > cap || (c.frag_len && !out)) return NFAGG_TRUNCATED;
+    if (c.frag_len) memcpy(out, t->blob.data() + c.frag_off, c.frag_len);
+    return NFAGG_OK;
+}
+
+int nfagg_encode_conn_json_device(nfagg_handle* h, const void* d_carriers, const nfagg_conn_values* d_values, size_t n,
+                                  const nfagg_conn_layout* layout, const nfagg_k8s_table* k8s, const nfagg_net_table* net,
+                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred, size_t* n_deferred,
+                                  size_t* out_bytes) {
+    if (!h || !layout || !k8s || !net || !out_bytes || !d_line_offsets || (n && (!d_carriers || !d_values))) return fail(h, NFAGG_EINVAL, "null argument");
+    if (layout->h != h || !layout->d_mem) return fail(h, NFAGG_EINVAL, "the layout was not created for this handle");
+    if (k8s->h != h || !k8s->d_slots) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
+    if (net->h != h || !net->d_mem) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
+    if ((((uintptr_t)d_carriers | (uintptr_t)d_values | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
+    if (n_deferred) *n_deferred = 0;
+    int rc;
+    bool done;
+    if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, nullptr, 0, &done)) != NFAGG_OK || done) return rc;
+    auto& S = h->enc;
+    if ((rc = ensure_buf(h, S.flp_rows, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.flp_n_deferred, 16)) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(uint2))) != NFAGG_OK) return rc;
+    HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
+    uint32_t* lens = (uint32_t*)S.flp_rows.p;
+    uint32_t* k8s_rows = (uint32_t*)S.k8s_rows.p;
+    const K8sDev K = k8s_dev(k8s);
+    const NetDev N = net_dev(net);
+    const ConnLayoutDev L{(const ConnCol*)layout->d_mem, (const uint8_t*)layout->d_mem + layout->cols.size() * sizeof(ConnCol), (uint32_t)layout->cols.size()};
+    // the carriers are flow records: both joins run on them unchanged. A conversation has no AgentIP, so no reporter and no direction.
+    hipError_t e = launch_k8s_resolve(d_carriers, n, K, k8s_rows, h->stream);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
+    e = launch_net_resolve(d_carriers, n, N, k8s_rows, (const uint32_t*)k8s->d_host_ids, K.n_rows, kNetNoHost, (uint2*)S.net_rows.p, h->stream);
+    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
+    size_t deferred_unused;
+    return encode_two_pass(h, n, "conversation JSON", "write", d_out, out_cap, out_bytes, n_deferred ? n_deferred : &deferred_unused,
+        [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
+            return launch_conn_json_size(d_carriers, d_values, n, L, K, N, k8s_rows, (const uint2*)S.net_rows.p, lens, local_off, block_sum, block_base,
+                                         (uint32_t*)S.flp_n_deferred.p, h->stream); },
+        [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
+            return launch_conn_json_write(d_carriers, d_values, n, L, K, N, k8s_rows, (const uint2*)S.net_rows.p, lens, local_off, block_base, d_out,
+                                          d_line_offsets, d_deferred, h->stream); });
+}
+
+int nfagg_encode_conn_json(nfagg_handle* h, const void* carriers, const nfagg_conn_values* values, size_t n, const nfagg_conn_layout* layout,
+                           const nfagg_k8s_table* k8s, const nfagg_net_table* net, void* out, size_t out_cap,
+                           uint64_t* line_offsets, uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
+    if (!h || !layout || !k8s || !net || !out_bytes || !line_offsets || (n && (!carriers || !values))) return fail(h, NFAGG_EINVAL, "null argument");
+    return encode_staged(h, carriers, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
+        [&](const void* d_carriers, void* d_out, uint64_t* d_offsets) {
+            int rc = ensure_buf(h, h->enc.conn_out, n * sizeof(nfagg_conn_values) + 16);
+            if (rc != NFAGG_OK) return rc;
+            if (n) HIP_TRY(h, hipMemcpyAsync(h->enc.conn_out.p, values, n * sizeof(nfagg_conn_values), hipMemcpyHostToDevice, h->stream));
+            return nfagg_encode_conn_json_device(h, d_carriers, (const nfagg_conn_values*)h->enc.conn_out.p, n, layout, k8s, net, d_out, out_cap, d_offsets,
+                                                 deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "nfagg_netev.h"
 #include "nfagg_metrics.h"
 #include "nfagg_pb.h"
+#include "nfagg_conn_json.h"
 
 // The cookie table of nfagg_netev_table_create: the sorted rows and the rendered blob, on the host and (with a handle) on its device.
 struct nfagg_netev_table {
@@ -82,6 +83,16 @@ struct nfagg_metrics_table {
     // nfagg_metrics_table_create_specs: the checked specs (a plain table's are its masks without values, for the content fold)
     bool has_specs = false;
     nfagg_metric_spec specs[nfagg::kMetMaxGroupings] = {};
+};
+
+// The layout of nfagg_conn_layout_create (nfagg_conn_json.h): the sorted column program and the rendered key fragments, on the
+// host and (with a handle) in one allocation on its device: the columns, then the blob.
+struct nfagg_conn_layout {
+    nfagg_handle* h = nullptr;
+    std::vector<nfagg::ConnCol> cols;
+    std::vector<uint8_t> blob;
+    uint32_t max_line = 0;
+    void* d_mem = nullptr;
 };
 
 namespace nfagg {

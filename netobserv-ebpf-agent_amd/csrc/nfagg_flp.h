@@ -111,4 +111,15 @@ hipError_t launch_flp_net_write(const void* d_recs, uint64_t n, const FlpParams&
                                 const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s);
 uint32_t flp_net_max_line(int policy);
 
+// The same two passes as extract conntrack's flow logs (nfagg_conn_meta.h): d_hash_ids holds one id per record, as
+// launch_conn_fold wrote them. A flow the stage does not track gets a zero-length line; the others end in _HashId and _RecordType.
+hipError_t launch_flp_conn_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                                const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint64_t* d_hash_ids, uint32_t* d_rows,
+                                uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s);
+hipError_t launch_flp_conn_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                                 const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint64_t* d_hash_ids,
+                                 const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out,
+                                 uint64_t* d_line_offsets, hipStream_t s);
+uint32_t flp_conn_max_line(int policy);
+
 }  // namespace nfagg

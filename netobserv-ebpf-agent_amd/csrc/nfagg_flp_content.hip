@@ -17,7 +17,8 @@
 // Same two passes, same window scheme, same encode_line and the same two kernels as nfagg_flp.hip (k_flp_size<Feat>,
 // k_flp_write<Feat> of nfagg_flp_line.h), with FlpContent as the feature policy: this file compiles them for FlpContent,
 // FlpContentNetev and FlpTls (nfagg_tls.h) over those two and over FlpPlain, and selects; it also compiles the kernel pair of
-// nfagg_k8s.h for FlpK8s over the three TLS policies, and that of nfagg_net.h for FlpNet over those. A lane reads the parts its
+// nfagg_k8s.h for FlpK8s over the three TLS policies, that of nfagg_net.h for FlpNet over those, and that of nfagg_conn_meta.h
+// for FlpConnMeta over those. A lane reads the parts its
 // present byte names with 16- and 8-byte loads before anything is emitted, keeps the fields the line needs in registers
 // and the DNS name in a 32-byte LDS slot of its own. The names of response codes, TCP states and drop causes sit in one
 // constant blob with an offset and a length per name; the counting pass reads only the lengths.
@@ -27,6 +28,7 @@
 #include "nfagg_tls.h"
 #include "nfagg_k8s.h"
 #include "nfagg_net.h"
+#include "nfagg_conn_meta.h"
 
 namespace nfagg {
 
@@ -232,6 +234,7 @@ struct FlpContent {
     template <typename S> NF_DEV void dst_subnet(S&) const {}
     template <typename S> NF_DEV void flow_direction(S&) const {}
     template <typename S> NF_DEV void src_subnet(S&) const {}
+    template <typename S> NF_DEV void conn_meta(S&) const {}                 // FlpConnMeta (nfagg_conn_meta.h) has extract conntrack's keys
 };
 
 // FlpContent plus the flow's network events: the table rows nfagg_netev_resolve wrote (PbFeat::ne_rows), each row's JSON
@@ -326,6 +329,31 @@ hipError_t launch_flp_net_write(const void* d_recs, uint64_t n, const FlpParams&
         return net_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_rows, d_local_off,
                                                              d_block_base, d_out, d_line_offsets, s); });
 }
+
+// extract conntrack's flow logs: FlpConnMeta over the three net policies, in the kernel pair of nfagg_conn_meta.h.
+template <typename Fn> static hipError_t flp_conn_select(const PbFeat* F, Fn fn) {
+    return !F ? fn(FlpPolicy<FlpConnMeta<FlpNet<FlpK8s<FlpTls<FlpPlain>>>>>{})
+              : F->ne_rows ? fn(FlpPolicy<FlpConnMeta<FlpNet<FlpK8s<FlpTls<FlpContentNetev>>>>>{}) : fn(FlpPolicy<FlpConnMeta<FlpNet<FlpK8s<FlpTls<FlpContent>>>>>{});
+}
+
+hipError_t launch_flp_conn_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                                const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint64_t* d_hash_ids, uint32_t* d_rows,
+                                uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s) {
+    return flp_conn_select(F, [&](auto policy) {
+        return connlog_size_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_hash_ids, d_rows,
+                                                                d_local_off, d_block_sum, d_block_base, s); });
+}
+
+hipError_t launch_flp_conn_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
+                                 const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint64_t* d_hash_ids,
+                                 const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out,
+                                 uint64_t* d_line_offsets, hipStream_t s) {
+    return flp_conn_select(F, [&](auto policy) {
+        return connlog_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_hash_ids, d_rows,
+                                                                 d_local_off, d_block_base, d_out, d_line_offsets, s); });
+}
+
+uint32_t flp_conn_max_line(int policy) { return flp_net_max_line(policy) ? flp_net_max_line(policy) + kConnMetaLineMax : 0u; }
 
 uint32_t flp_net_max_line(int policy) { return flp_k8s_max_line(policy) ? flp_k8s_max_line(policy) + kNetLineMax : 0u; }
 

@@ -30,6 +30,10 @@ struct FlpLds {
 template <typename S> struct is_count { static constexpr bool value = false; };
 template <> struct is_count<CountSink> { static constexpr bool value = true; };
 
+// A literal. Not for the arms of a run-time choice between texts of different lengths (if / else if / else with a lit() each):
+// the arms then differ only in constant stores and in the constant added to the sink's pointer, and hipcc 7.2 (clang 22.0.0git)
+// was seen to compute the default arm's end pointer under the execution mask of the other lanes. Choose the
+// text first and write it with one call (put_text in nfagg_conn_json.hip).
 template <typename S, size_t N> NF_DEV void lit(S& s, const char (&a)[N]) {
     if constexpr (is_count<S>::value) s.n += (uint32_t)(N - 1);
     else {
@@ -177,6 +181,8 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
 // The three Kubernetes hooks are empty in all of these; FlpK8s (nfagg_k8s.h) fills them, in kernels of its own. So are the
 // three hooks of the transform network rules (FlowDirection, the two subnet labels); kFlagNames = false keeps dec<5> as the
 // value of Flags, and no call stands in its place. FlpNet (nfagg_net.h) fills the hooks and names the flags, in kernels of its own.
+// The last hook, in front of the closing brace, takes the two keys extract conntrack adds to a flow log; FlpConnMeta
+// (nfagg_conn_meta.h) fills it, in kernels of its own.
 //
 // What k_flp_size<Feat> and k_flp_write<Feat> ask of a policy beside the hooks, all of it known when they are compiled:
 //   kWindow   line starts a window of the write kernel takes, from its 16-byte aligned base
@@ -207,6 +213,7 @@ struct NoFeat {
     template <typename S> NF_DEV void dst_subnet(S&) const {}      // DstSubnetLabel after DstPort
     template <typename S> NF_DEV void flow_direction(S&) const {}  // FlowDirection  after Flags
     template <typename S> NF_DEV void src_subnet(S&) const {}      // SrcSubnetLabel after SrcPort
+    template <typename S> NF_DEV void conn_meta(S&) const {}       // _HashId _RecordType  behind ZoneId: '_' sorts above every letter a key starts with
 };
 // The plain policy: the line of the records Accounter.evict produces.
 struct FlpPlain : NoFeat {
@@ -308,6 +315,7 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
     s.put(']');
     f.xlat(s);
     f.zone(s);
+    f.conn_meta(s);
     lit(s, "}\n");
 }
 

@@ -76,7 +76,8 @@ struct nfagg_handle {
         DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record
         DevBuf met_slots, met_out;                   // nfagg_metrics_fold: control words and the groupings' tables; the host entry point's groups
         DevBuf conn_slots, conn_flow;                // nfagg_conn_fold: control words and the connection table; per flow hashA and slot
-        DevBuf conn_ids, conn_out;                   //   the host entry point's hash ids and partials
+        DevBuf conn_ids, conn_out;                   //   the host entry point's hash ids and partials; the host entry points of the two
+                                                     //   conntrack encoders stage their ids / values here too (one stream: calls serialise)
         std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
         std::vector<uint8_t> h_flp_esc;
         template <typename F> void each(F f) {

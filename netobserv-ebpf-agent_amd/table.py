@@ -456,11 +456,11 @@ class FlowTable:
         return rc, need.value
 
     # -- export encode (record -> direct-FLP JSON lines), nfagg_encode_flp_json*
-    def _flp_json(self, records, options, features=None, rows=None, netev_table=None, tls_names=None, k8s=None, net=None):
+    def _flp_json(self, records, options, features=None, rows=None, netev_table=None, tls_names=None, k8s=None, net=None, hash_ids=None):
         """The host-memory entry points. options: flp_options(...). features: None (nfagg_encode_flp_json) or (present, parts)
         (the *_content ones; present None: no flow carries a part). rows and netev_table: the *_netev one. tls_names:
         nfagg_encode_flp_json_tls, which takes the others as options and defers nothing; k8s (with tls_names): nfagg_encode_flp_json_k8s;
-        net (with k8s): nfagg_encode_flp_json_net. Returns (buf, line_offsets, deferred)."""
+        net (with k8s): nfagg_encode_flp_json_net; hash_ids (with net): nfagg_encode_flp_json_conn. Returns (buf, line_offsets, deferred)."""
         r = np.ascontiguousarray(records)
         n = r.nbytes // 144
         o, keep = options
@@ -480,6 +480,10 @@ class FlowTable:
                 fn, head = L.lib.nfagg_encode_flp_json_k8s, head + (k8s._t,)
                 if net is not None:
                     fn, head = L.lib.nfagg_encode_flp_json_net, head + (net._t,)
+                    if hash_ids is not None:
+                        ids = np.ascontiguousarray(hash_ids, dtype=np.uint64)
+                        assert ids.size == n
+                        fn, head = L.lib.nfagg_encode_flp_json_conn, head + (ids.ctypes.data_as(C.c_void_p) if n else None,)
         else:
             flags = (deferred.ctypes.data_as(C.c_void_p), C.byref(n_def))
             if netev_table is not None:
@@ -494,7 +498,7 @@ class FlowTable:
         return buf, off, deferred
 
     def _flp_json_device(self, d_records, n, options, d_out, out_cap, d_line_offsets, d_deferred=0, features=None, d_rows=0,
-                         netev_table=None, tls_names=None, k8s=None, net=None):
+                         netev_table=None, tls_names=None, k8s=None, net=None, d_hash_ids=None):
         """The device entry points (raw device pointers); the optionals select as in _flp_json, features = (d_present, d_parts).
         Returns (rc, bytes needed/written, deferred records)."""
         o, keep = options
@@ -512,6 +516,8 @@ class FlowTable:
                 fn, head = L.lib.nfagg_encode_flp_json_k8s_device, head + (k8s._t,)
                 if net is not None:
                     fn, head = L.lib.nfagg_encode_flp_json_net_device, head + (net._t,)
+                    if d_hash_ids is not None:
+                        fn, head = L.lib.nfagg_encode_flp_json_conn_device, head + (C.c_void_p(d_hash_ids or None),)
         elif netev_table is not None:
             fn, head = L.lib.nfagg_encode_flp_json_content_netev_device, head + f_arg + ne_args
         elif features is not None:
@@ -718,6 +724,57 @@ class FlowTable:
         return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
                                      d_out, out_cap, d_line_offsets, 0, (d_present, d_parts) if d_present else None, d_rows, netev_table,
                                      tls_names, k8s, net)[:2]
+
+    # -- extract conntrack's flow logs (nfagg_encode_flp_json_conn): the *_net line with _HashId and _RecordType
+    def encode_flp_json_conn(self, records: np.ndarray, tls_names: "TlsNames", k8s: "K8sTable", net: "NetTable", hash_ids: np.ndarray,
+                             now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip=None, time_received: int = 0,
+                             unknown: bytes = b"unknown", present=None, parts=None, rows=None, netev_table: "NetevTable" = None):
+        """encode_flp_json_net as extract conntrack emits its flow logs (nfagg_encode_flp_json_conn): a flow the stage does not
+        track (no IP ethertype, or a protocol other than 6, 17, 132) has an empty line, every other line ends in
+        "_HashId":"<hex of hash_ids[i]>","_RecordType":"flowLog". hash_ids: uint64[n], what conn_fold returned for these
+        records. Returns (buf, line_offsets)."""
+        return self._flp_json(records, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown), (present, parts),
+                              rows, netev_table, tls_names, k8s, net, hash_ids)[:2]
+
+    def encode_flp_json_conn_device(self, d_records: int, n: int, tls_names: "TlsNames", k8s: "K8sTable", net: "NetTable", d_hash_ids: int,
+                                    now_unix_ns: int, mono_now_ns: int, names: np.ndarray, agent_ip, time_received: int, d_out: int,
+                                    out_cap: int, d_line_offsets: int, unknown: bytes = b"unknown", d_present: int = 0, d_parts=None,
+                                    d_rows: int = 0, netev_table: "NetevTable" = None):
+        """Device-resident variant (raw device pointers; d_hash_ids: the d_hash_ids of conn_fold_device; d_present = 0: no
+        parts; d_out = 0 asks for the size). Returns (rc, bytes needed/written)."""
+        return self._flp_json_device(d_records, n, flp_options(now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown),
+                                     d_out, out_cap, d_line_offsets, 0, (d_present, d_parts) if d_present else None, d_rows, netev_table,
+                                     tls_names, k8s, net, d_hash_ids)[:2]
+
+    # -- extract conntrack's conversation records (nfagg_encode_conn_json): one JSON line per conversation
+    def conn_layout(self, fields) -> "ConnLayout":
+        """A ConnLayout on this handle's device; fields as ConnLayout takes them."""
+        return ConnLayout(fields, self)
+
+    def encode_conn_json(self, carriers: np.ndarray, values: np.ndarray, layout: "ConnLayout", k8s: "K8sTable", net: "NetTable"):
+        """The conversation records' lines (nfagg_encode_conn_json). carriers: FLOW_RECORD[n] with the connections' keys; values:
+        CONN_VALUES[n]. Returns (buf, line_offsets, deferred): deferred[i] == 1 marks a conversation with an aggregate of
+        magnitude >= 2^53, whose line is empty and which the caller formats itself."""
+        r = np.ascontiguousarray(carriers)
+        v = np.ascontiguousarray(values, dtype=CONN_VALUES)
+        n = r.nbytes // 144
+        assert v.size == n
+        off, deferred, n_def = np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.uint8), C.c_size_t(0)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if n else None  # noqa: E731
+        buf = self._encode_grown(n, 1024, lambda p, cap, need: L.lib.nfagg_encode_conn_json(
+            self._h, ptr(r), ptr(v), n, layout._t, k8s._t, net._t, p, cap, off.ctypes.data_as(C.c_void_p), ptr(deferred), C.byref(n_def), need))
+        assert int(deferred.sum()) == n_def.value
+        return buf, off, deferred
+
+    def encode_conn_json_device(self, d_carriers: int, d_values: int, n: int, layout: "ConnLayout", k8s: "K8sTable", net: "NetTable", d_out: int,
+                                out_cap: int, d_line_offsets: int, d_deferred: int = 0):
+        """Device-resident variant (raw device pointers; d_out = 0 asks for the size). Returns (rc, bytes needed/written, deferred)."""
+        need, n_def = C.c_size_t(0), C.c_size_t(0)
+        rc = L.lib.nfagg_encode_conn_json_device(self._h, C.c_void_p(d_carriers or None), C.c_void_p(d_values or None), n, layout._t, k8s._t, net._t,
+                                                 C.c_void_p(d_out or None), out_cap, C.c_void_p(d_line_offsets or None), C.c_void_p(d_deferred or None),
+                                                 C.byref(n_def), C.byref(need))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, need.value, n_def.value
 
     # -- flow metrics (nfagg_metrics_*): the GROUP BY under the `encode prom` counters
     def metrics_table(self, k8s: "K8sTable", groupings) -> "MetricsTable":
@@ -1350,6 +1407,44 @@ CONN_PARTIAL = np.dtype([("hash_total", "<u8"), ("first_hash_a", "<u8"), ("first
                          ("flags_or", "<u4"), ("flows", "<u8", (2,)), ("bytes", "<u8", (2,)), ("packets", "<u8", (2,)), ("start_ms_min", "<i8"),
                          ("end_ms_max", "<i8"), ("pad_", "<u8", (4,))])                                              # nfagg_conn_partial
 assert CONN_PARTIAL.itemsize == 128 == C.sizeof(L.ConnPartial)
+CONN_SNAPSHOT = np.dtype([("src_ip", "u1", (16,)), ("dst_ip", "u1", (16,)), ("src_port", "<u2"), ("dst_port", "<u2"), ("eth_protocol", "<u2"),
+                          ("proto", "u1"), ("dscp", "u1"), ("src_mac", "u1", (6,)), ("dst_mac", "u1", (6,)), ("n_dirs", "u1"), ("dirs", "u1", (7,)),
+                          ("pad_", "<u4"), ("start_ms", "<i8"), ("end_ms", "<i8")])                                  # nfagg_conn_snapshot
+CONN_VALUES = np.dtype([("hash_total", "<u8"), ("record_type", "u1"), ("is_first", "u1"), ("pad_", "u1", (6,)), ("flows", "<u8", (2,)),
+                        ("bytes", "<u8", (2,)), ("packets", "<u8", (2,)), ("start_ms_min", "<i8"), ("end_ms_max", "<i8"), ("first", CONN_SNAPSHOT),
+                        ("last", CONN_SNAPSHOT), ("pad2_", "<u8", (2,))])                                            # nfagg_conn_values
+assert CONN_SNAPSHOT.itemsize == 80 and CONN_VALUES.itemsize == 256 and C.sizeof(L.ConnField) == 16
+
+
+class ConnLayout(_CallerTable):
+    """extract conntrack's outputFields compiled into the sorted column program of a conversation line (nfagg_conn_layout_create).
+    fields: [dict(name=.., operation=.., input=.., splitAB=..)] as the stage's configuration has them (input defaults to the name;
+    count takes none). With a FlowTable the layout lives on its device and serves encode_conn_json; with table=None it is built and
+    checked on the host only."""
+
+    def __init__(self, fields, table: "FlowTable" = None):
+        arr = (L.ConnField * max(len(fields), 1))()
+        keep = []
+        for k, f in enumerate(fields):
+            name = f.get("name", "")
+            name = name.encode("latin-1") if isinstance(name, str) else bytes(name)
+            op = f.get("operation", "")
+            inp = "" if op == "count" else (f.get("input", "") or f.get("name", ""))
+            inp = inp.decode("latin-1") if isinstance(inp, bytes) else inp
+            keep.append(name)
+            arr[k].name, arr[k].name_len = name, len(name)
+            arr[k].op, arr[k].input = L.CONN_OPS.get(op, 255), L.CONN_INPUTS.get(inp, 255)
+            arr[k].split_ab = 1 if f.get("splitAB", False) else 0
+        self._create(table, L.lib.nfagg_conn_layout_destroy, lambda h, out: L.lib.nfagg_conn_layout_create(h, arr, len(fields), out))
+        self.n_columns, self.max_line = L.lib.nfagg_conn_layout_columns(self._t), L.lib.nfagg_conn_layout_max_line(self._t)
+
+    def render(self, column: int) -> bytes:
+        """Column `column`'s key fragment (,"name":) in sorted order; b"" for a block."""
+        buf, n = np.zeros(8 + 6 * 80, dtype=np.uint8), C.c_size_t(0)
+        rc = L.lib.nfagg_conn_layout_render(self._t, column, buf.ctypes.data_as(C.c_void_p), buf.size, C.byref(n))
+        if rc != L.OK:
+            raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
+        return buf[:n.value].tobytes()
 
 
 def conn_hash(record) -> tuple:

@@ -45,7 +45,11 @@ read-stream rate are what its number is read against. NFAGG_LIB selects the libr
 --conntrack (with --k8s --net --metrics): the conversation fold on top, on the same records in the same run, beside the plain metrics
 fold: nfagg_conn_fold_device with hash ids. Reported: the median wall time of a whole call (the memset of the table, claim, finish,
 count, scan, emit, the read-back), the connections and the discarded flows, and the bytes a flow's lanes read and write by this
-tool's own count. --k8s-trace covers the k_conn_* kernels."""
+tool's own count. --k8s-trace covers the k_conn_* kernels. The flow logs follow on the same records and ids in the same run:
+nfagg_encode_flp_json_conn_device with the tables of the --net leg, whose _net line above is what its time per output byte is read
+against; --k8s-trace covers the k_connlog_* kernels. Then the conversation records, one per connection of the fold
+(nfagg_encode_conn_json_device, seven output fields of which two are split): each connection's first flow as its carrier, the
+partial's sums as its values; --k8s-trace covers the k_conn_json_* kernels (they match k_conn_)."""
 import io
 import os
 import queue
@@ -144,7 +148,7 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|fillBuffer|scan", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_connlog_|fillBuffer|scan", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
             grid = int(row.get("Grid_Size_X") or row.get("Grid_Size") or 0)
@@ -204,7 +208,7 @@ def metrics_leg(tab, k8s, d_ev, m, d_rows, d_net):
           f"measured here ({rate / 1e9:.0f} GB/s over 1 GiB)")
 
 
-def conntrack_leg(tab, d_ev, m):
+def conntrack_leg(tab, d_ev, m, tls, k8s, net, d_off):
     L = nf._lib
     cap = 1 << 18
     d_ids = torch.empty(m, dtype=torch.int64, device="cuda")
@@ -228,6 +232,39 @@ def conntrack_leg(tab, d_ev, m):
     print(f"  conntrack {m} flows -> {n_conns} connections, {n_disc} discarded (cap {cap}, {slots} slots = {slots * 128 >> 20} MiB zeroed per call) "
           f"in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s; {read:.0f} B read + {wrote} B written per flow by this tool's count = "
           f"{(read + wrote) * m / dt / 1e9:.1f} GB/s per call")
+    del d_out
+    # the flow logs: the _net line plus _HashId and _RecordType for the flows the stage tracks, no line for the others
+    args = (d_ev.data_ptr(), m, tls, k8s, net, d_ids.data_ptr(), NOW, MONO, names, agent, 1_700_000_000)
+    rc, need = tab.encode_flp_json_conn_device(*args, 0, 0, d_off.data_ptr())
+    d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+    (rc, wrote), dt = timed(lambda: tab.encode_flp_json_conn_device(*args, d_out.data_ptr(), need, d_off.data_ptr()))
+    assert rc == nf.OK and wrote == need
+    per_byte("_conn", m, dt, wrote)
+    print(f"           flow logs: {m - n_disc} of {m} flows tracked, {wrote / max(m - n_disc, 1):.1f} B per line that is written")
+    del d_out
+    # the conversation records at the leg's connection count: every connection's first flow is its carrier, the values are the partials'
+    # sums with synthetic all-zero snapshots. The byte sums are masked to 40 bits so that no conversation is deferred (the synthetic
+    # flows' byte counts are random 64-bit values): the leg times the encoder writing every line. The fields are the operator's usual
+    # ones by name and width; `FlowDirection` is only a name here, a `first` column that reads the snapshot's Dscp (a conversation has
+    # no FlowDirection of its own)
+    fields = [dict(name="Bytes", operation="sum", splitAB=True), dict(name="Packets", operation="sum", splitAB=True),
+              dict(name="numFlowLogs", operation="count"), dict(name="TimeFlowStart", operation="min", input="TimeFlowStartMs"),
+              dict(name="TimeFlowEnd", operation="max", input="TimeFlowEndMs"), dict(name="FlowDirection", operation="first", input="Dscp"),
+              dict(name="IfDirection", operation="first", input="IfDirections")]
+    vals = np.zeros(n_conns, dtype=nf.CONN_VALUES)
+    vals["hash_total"], vals["flows"], vals["bytes"], vals["packets"] = parts["hash_total"], parts["flows"], parts["bytes"] & ((1 << 40) - 1), parts["packets"]
+    vals["start_ms_min"], vals["end_ms_max"], vals["is_first"] = parts["start_ms_min"], parts["end_ms_max"], 1
+    vals["first"]["n_dirs"] = vals["last"]["n_dirs"] = 1
+    d_vals = torch.from_numpy(vals.view(np.uint8).reshape(-1)).cuda()
+    d_car = d_ev.view(torch.uint8)[: m * 144].view(m, 144)[torch.from_numpy(parts["first_idx"].astype(np.int64)).cuda()].contiguous()
+    with tab.conn_layout(fields) as lay:
+        cargs = (d_car.data_ptr(), d_vals.data_ptr(), n_conns, lay, k8s, net)
+        rc, need, n_def = tab.encode_conn_json_device(*cargs, 0, 0, d_off.data_ptr())
+        d_out = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+        (rc, wrote, n_def), dt = timed(lambda: tab.encode_conn_json_device(*cargs, d_out.data_ptr(), need, d_off.data_ptr()))
+        assert rc == nf.OK and wrote == need
+        per_byte("conv", n_conns, dt, wrote)
+        print(f"           conversation records: {lay.n_columns} columns, longest possible line {lay.max_line} B, {n_def} deferred")
 
 
 def metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net):
@@ -347,7 +384,7 @@ for flows in ((10_000_000,) if (CONTENT or TLS) and not K8S else (1_000_000, 10_
                         if METRICS:
                             metrics_leg(tab, k8s, d_ev, m, d_rows, d_net)
                             if CONNTRACK:
-                                conntrack_leg(tab, d_ev, m)
+                                conntrack_leg(tab, d_ev, m, tls, k8s, net, d_off)
                             if CONTENT:
                                 metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net)
                     del d_net
