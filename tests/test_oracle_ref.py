@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import dedupcraft
 from conftest import assert_records_equal, dedup_stream
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_dedup_golden.json")
@@ -57,6 +58,11 @@ def direct_case(O):
     return recs, agg
 
 
+def script_family_case(name):
+    """tests/dedupcraft.py: every order of events over the merge's small alphabets, flow after flow, nothing evicted early."""
+    return dedupcraft.family(name).recs, 1 << 20
+
+
 STYLES, MAX_ENTRIES, HOT = [0, 1, 2, 3], [1 << 20, 50, 1], [(6, 1), (7, 2)]
 
 
@@ -70,6 +76,8 @@ def stream_cases(O):
         cases["hot_flow[seed=%d,style=%d]" % (seed, style)] = lambda seed=seed, style=style: hot_flow_case(O, seed, style)
     cases["single_packet"] = lambda: single_packet_case(O)
     cases["missed_counter"] = lambda: missed_counter_case(O)
+    for name in dedupcraft.FAMILIES:
+        cases["scripts[%s]" % name] = lambda name=name: script_family_case(name)
     return cases
 
 
@@ -127,6 +135,15 @@ def test_single_packet_records_need_no_packet_fixup(O, ref, golden):
     """With packets == 1 per record the shim's `packets - 1` top-up is zero: the reference's arithmetic alone."""
     recs, m = single_packet_case(O)
     same(O, ref, golden, "single_packet", recs, m)
+
+
+@pytest.mark.parametrize("family", dedupcraft.FAMILIES)
+def test_oracle_dedup_equals_reference_on_the_script_families(O, ref, golden, family):
+    """The families the device tests of kernel-dedup mode are judged by (tests/test_crafted_dedup_gpu.py): the oracle is the
+    reference on every one of their flows."""
+    recs, m = script_family_case(family)
+    got = same(O, ref, golden, "scripts[%s]" % family, recs, m)
+    assert [r for r, _ in got] == ["closing"] and len(got[0][1]) == dedupcraft.family(family).n_scripts
 
 
 def test_reference_function_directly(O, ref, golden):
