@@ -340,7 +340,9 @@ const char* nfagg_last_error(const nfagg_handle* h);
 /* records: n x 144-byte flow_record_t in HOST memory (what
  * model.ReadFrom decodes, pkg/model/record.go:227-231), in arrival order.
  * The records are folded in exactly that order. *consumed = number of
- * leading records folded; returns NFAGG_FULL when it stopped early. */
+ * leading records folded; returns NFAGG_FULL when it stopped early.
+ * One limit: start_mono_time_ts = 2^64 - 1 is folded as 0 ("not set"): the
+ * slots keep ~start with 0 for "no start yet" (tagged words). */
 int nfagg_ingest(nfagg_handle* h, const void* records, size_t n, size_t* consumed);
 
 /* Same, records already in DEVICE memory of cfg.device (16-byte aligned). ASYNCHRONOUS when the batch cannot fill the table
