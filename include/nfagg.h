@@ -1679,6 +1679,236 @@ int nfagg_conn_fold_device(nfagg_handle* h, const void* d_records, size_t n, con
 uint64_t nfagg_conn_hash(const void* record, uint64_t* hash_a, uint64_t* hash_b);
 
 /* ------------------------------------------------------------------ */
+/* transform filter — flowlogs-pipeline's `transform filter` stage      */
+/* (paths under flowlogs-pipeline's pkg/: pipeline/transform/           */
+/* transform_filter.go, dsl/lexer.go, dsl/expr.y, dsl/eval.go,          */
+/* utils/filters/filters.go, utils/convert.go) for the flows of         */
+/* decode.RecordToMap (the agent's pkg/decode/decode_protobuf.go:57-195) */
+/* behind the Kubernetes and the transform network enrichment above.    */
+/* The reference walks every flow through a predicate tree: a map       */
+/* lookup per atom, reflection in ConvertToInt. Every predicate of      */
+/* filters.go is a function of a handful of keys, and those keys are on */
+/* the device as small integers already (the metrics section above): a  */
+/* filter is a short boolean program, the same for every flow, and a    */
+/* stable compaction behind it. Every encoder and fold then runs        */
+/* unchanged on the kept flows.                                         */
+/*                                                                      */
+/* Stage order (transform_filter.go:55-95 Transform, 234-261 configure): */
+/*  - configure splits the rules: every keep_entry_query goes to        */
+/*    KeepRules in configuration order, wherever it stands; the others  */
+/*    keep their order (243-254).                                       */
+/*  - With at least one keep rule a flow survives only if some rule's   */
+/*    predicate is true and that rule's roll succeeds (62-73, 192-206   */
+/*    applyKeepPredicate). A flow sampled out of rule r is still        */
+/*    offered to rule r + 1: applyKeepPredicate returns false and the   */
+/*    loop goes on. The first admitting rule ends the loop.             */
+/*  - Then the remaining rules, in order; the first that removes the    */
+/*    flow ends it (74-78).                                             */
+/* Sampling (217-232): rollSampling passes for value 0, else one chance */
+/* in `value`. storeSampling runs only for an admitting keep rule with  */
+/* keepEntrySampling > 0 and a samplingField: Sampling becomes          */
+/* max(Sampling, 1) * value, an absent key counting as 1.               */
+/* conditional_sampling never stores (208-215). The rules behind the    */
+/* keep rules see the multiplied value.                                 */
+/* The other rule types (99-122, 168-171, 181-189):                     */
+/*  - remove_entry_if_exists / _if_doesnt_exist: the key's presence;    */
+/*  - remove_entry_if_equal / _if_not_equal compare interface{} values  */
+/*    with == / != (113, 119): a YAML number (int or float64) never     */
+/*    equals a uint8 / uint16 / uint32 / uint64 / int64 map value, so   */
+/*    if_equal with a number is constant false and if_not_equal with a  */
+/*    number removes whenever the key exists; only strings compare;     */
+/*  - remove_entry_all_satisfied: the AND of its entries;               */
+/*  - conditional_sampling: the first condition whose rules are all     */
+/*    satisfied decides: its value is rolled, a failed roll drops.      */
+/* The query language (dsl): text/scanner tokens in its default mode    */
+/* (identifiers, decimal integers, "..." through strconv.Unquote, raw   */
+/* strings, comments skipped; a float is an error, lexer.go:187-189;    */
+/* 0x10 scans as an Int and fails ParseInt(s, 10, 64), 178-184); the    */
+/* two-character operators by peeking one rune (203-209); and / or /    */
+/* with / without in any letter case (211). There is no unary minus: a  */
+/* leading '-' is an NF_FIELD token and a syntax error. expr.y:16-17    */
+/* declares %left AND before %left OR, and yacc gives a LATER line the  */
+/* higher precedence: OR binds tighter than AND, `a and b or c` is      */
+/* `a and (b or c)`; both are left-associative. The generated tables   */
+/* of expr.y.go agree: the state behind `expr AND expr` shifts on OR.   */
+/* Predicates (filters.go, convertString == false as lexer.go:61,67     */
+/* pass it): `=` with a string is true only for a key whose value is a  */
+/* Go string equal to it (57-62), so constant false on a numeric key;   */
+/* `!=` is its negation (65-68), true for an absent key. The six        */
+/* numeric comparisons go through ConvertToInt (94-103; convert.go      */
+/* 178-213): every integer type converts, uint64 wraps into int, a      */
+/* string goes through ParseInt, a slice fails and the predicate is     */
+/* false. =~ / !~ match unanchored over ConvertToString (105-121). A    */
+/* $(Key) variable in an `=` value (29-44) is not served.               */
+/* Division of labour, as for nfagg_metrics_table_create's classes: a   */
+/* predicate over a STRING key (a Kubernetes field, a subnet label, the */
+/* flow layer, the DNS response code, the IPsec status) is evaluated by */
+/* the caller once per table row, whatever its operator, because only   */
+/* the caller has a regex engine; the device looks the answer up.       */
+/*                                                                      */
+/* Differences from the reference, by design:                           */
+/*  - the roll: Go's generator is seeded from the clock                 */
+/*    (transform_filter.go:39), so there is no sequence to reproduce.   */
+/*    Here a roll is a pure function of (seed, flow index, step), see   */
+/*    nfagg_filter_roll;                                                */
+/*  - Sampling is stored in the record's 32 bits: a product that does   */
+/*    not fit defers the flow to the host (keep = 2);                   */
+/*  - field-mutating rules (add_*, remove_field, the label rules) are   */
+/*    not served: such a stage stays on the host path.                  */
+/* ------------------------------------------------------------------ */
+
+#define NFAGG_FILTER_MAX_ATOMS 64
+#define NFAGG_FILTER_MAX_OPS   256
+#define NFAGG_FILTER_MAX_STEPS 32
+#define NFAGG_FILTER_MAX_STACK 32
+#define NFAGG_FILTER_NO_RULE   0xFFu
+
+enum { NFAGG_FILTER_ATOM_CONST = 0,     /* value_const != 0 */
+       NFAGG_FILTER_ATOM_NUM = 1,       /* the key `field` exists, is a number, and (int)value_of_key `cmp` value */
+       NFAGG_FILTER_ATOM_PRESENT = 2,   /* the key `field` exists */
+       NFAGG_FILTER_ATOM_TABLE = 3,     /* truth[the flow's index in dimension `dim`] != 0 */
+       NFAGG_FILTER_ATOM_ADDR = 4,      /* SrcAddr (side 0) / DstAddr (side 1) exists and its 16 bytes equal bytes[0..16) */
+       NFAGG_FILTER_ATOM_MAC = 5 };     /* SrcMac / DstMac: its 6 bytes equal bytes[0..6) */
+enum { NFAGG_FILTER_CMP_EQ = 0, NFAGG_FILTER_CMP_NE = 1, NFAGG_FILTER_CMP_LT = 2, NFAGG_FILTER_CMP_GT = 3, NFAGG_FILTER_CMP_LE = 4,
+       NFAGG_FILTER_CMP_GE = 5 };
+/* Fields of NUM and PRESENT atoms: when the key exists (decode_protobuf.go:63-182 and the enrichment rules above) and the
+ * int ConvertToInt gives. "IP": eth_protocol 0x0800 or 0x86DD. A part is present as nfagg_encode_pb_content has it. */
+enum { NFAGG_FILTER_F_ETYPE = 0,             /* always; eth_protocol */
+       NFAGG_FILTER_F_BYTES = 1,             /* bytes != 0; (int64)bytes: 2^63 and above is negative */
+       NFAGG_FILTER_F_PACKETS = 2,           /* packets != 0 */
+       NFAGG_FILTER_F_SAMPLING = 3,          /* sampling != 0, or an admitting keep rule stored it; the stored value */
+       NFAGG_FILTER_F_PROTO = 4,             /* IP */
+       NFAGG_FILTER_F_DSCP = 5,              /* IP */
+       NFAGG_FILTER_F_SRC_PORT = 6,          /* IP and protocol 6, 17 or 132 */
+       NFAGG_FILTER_F_DST_PORT = 7,
+       NFAGG_FILTER_F_ICMP_TYPE = 8,         /* IP and protocol 1 or 58 */
+       NFAGG_FILTER_F_ICMP_CODE = 9,
+       NFAGG_FILTER_F_FLAGS = 10,            /* IP and protocol 6. With NFAGG_NET_DECODE_TCP_FLAGS in the net table the value is a
+                                                []string: the key exists, every NUM atom on it is false */
+       NFAGG_FILTER_F_TIME_FLOW_START_MS = 11,   /* always; opt's clocks as nfagg_record_times, in milliseconds (time.Time.UnixMilli) */
+       NFAGG_FILTER_F_TIME_FLOW_END_MS = 12,
+       NFAGG_FILTER_F_FLOW_DIRECTION = 13,   /* the net row's direction is 0, 1 or 2 */
+       NFAGG_FILTER_F_TIME_FLOW_RTT_NS = 14, /* additional part, flow_rtt != 0; (int64)flow_rtt */
+       NFAGG_FILTER_F_DNS_LATENCY_MS = 15,   /* dns part, id != 0; (int64)latency / 1000000 */
+       NFAGG_FILTER_F_DNS_ID = 16,           /* dns part, id != 0 */
+       NFAGG_FILTER_F_DNS_FLAGS = 17,        /* dns part, id != 0 */
+       NFAGG_FILTER_F_DNS_ERRNO = 18,        /* dns part, errno != 0 */
+       NFAGG_FILTER_F_PKT_DROP_BYTES = 19,   /* drops part, latest_drop_cause != 0 */
+       NFAGG_FILTER_F_PKT_DROP_PACKETS = 20,
+       NFAGG_FILTER_F_PKT_DROP_LATEST_FLAGS = 21,
+       NFAGG_FILTER_F_IPSEC_RET_CODE = 22,   /* additional part, ipsec_encrypted_ret != 0 or ipsec_encrypted; the int32 */
+       NFAGG_FILTER_F_NUM_LAST = 22,
+       /* presence only: a NUM atom on them is refused */
+       NFAGG_FILTER_F_SRC_ADDR = 23,         /* IP */
+       NFAGG_FILTER_F_DST_ADDR = 24,
+       NFAGG_FILTER_F_SRC_MAC = 25,          /* always */
+       NFAGG_FILTER_F_DST_MAC = 26,
+       NFAGG_FILTER_F_LAST = 26 };
+/* Dimensions of TABLE atoms and their truth entries; the last entry is the answer for "none". */
+enum { NFAGG_FILTER_DIM_SRC_K8S_ROW = 0,     /* k8s table rows + 1: the flow's src row as nfagg_k8s_resolve wrote it; last: no row */
+       NFAGG_FILTER_DIM_DST_K8S_ROW = 1,
+       NFAGG_FILTER_DIM_SRC_SUBNET_LABEL = 2,/* net table labels + 1: the net row's src_label; last: NFAGG_NET_NO_LABEL */
+       NFAGG_FILTER_DIM_DST_SUBNET_LABEL = 3,
+       NFAGG_FILTER_DIM_FLOW_LAYER = 4,      /* 3: [0] infra, [1] app, [2] no key (a table without a layer) */
+       NFAGG_FILTER_DIM_DNS_RCODE = 5,       /* 17: flags & 0xF where DnsId exists; [16] no key */
+       NFAGG_FILTER_DIM_IPSEC_STATUS = 6,    /* 3: [0] success, [1] error, [2] no key */
+       NFAGG_FILTER_DIM_LAST = 6 };
+/* The postfix stream: a byte below NFAGG_FILTER_MAX_ATOMS pushes that atom's value. */
+enum { NFAGG_FILTER_OP_AND = 0x80, NFAGG_FILTER_OP_OR = 0x81, NFAGG_FILTER_OP_NOT = 0x82 };
+enum { NFAGG_FILTER_STEP_KEEP = 0,           /* a keep_entry_query; value: keepEntrySampling. KEEP steps come first */
+       NFAGG_FILTER_STEP_REMOVE = 1,         /* the flow is dropped when the predicate is true */
+       NFAGG_FILTER_STEP_SAMPLE_IF = 2 };    /* one condition of a conditional_sampling rule `group` (0..31): within a group the
+                                                first true predicate decides, its value is rolled, a failed roll drops */
+#define NFAGG_FILTER_STORE_SAMPLING 1u       /* samplingField == "Sampling" */
+
+typedef struct nfagg_filter_atom {           /* 48 bytes */
+    uint8_t kind;                            /* NFAGG_FILTER_ATOM_* */
+    uint8_t field;                           /* NUM, PRESENT */
+    uint8_t cmp;                             /* NUM */
+    uint8_t dim;                             /* TABLE */
+    uint8_t side;                            /* ADDR, MAC: 0 src, 1 dst */
+    uint8_t value_const;                     /* CONST */
+    uint8_t pad_[2];                         /* 0 */
+    int64_t value;                           /* NUM */
+    uint8_t bytes[16];                       /* ADDR: net.IP.To16(); MAC: the first 6 */
+    const uint8_t* truth;                    /* TABLE: HOST memory, n_truth bytes, read during nfagg_filter_create only */
+    uint32_t n_truth;
+    uint32_t pad2_;
+} nfagg_filter_atom;
+
+typedef struct nfagg_filter_step {           /* 8 bytes */
+    uint8_t kind;                            /* NFAGG_FILTER_STEP_* */
+    uint8_t group;                           /* SAMPLE_IF */
+    uint16_t value;                          /* KEEP, SAMPLE_IF: the sampling value, 0: always passes */
+    uint16_t op_begin, op_count;             /* the step's slice of ops: it leaves exactly one value on the stack */
+} nfagg_filter_step;
+
+typedef struct nfagg_filter_spec {
+    uint32_t struct_size;                    /* sizeof(nfagg_filter_spec) */
+    uint32_t flags;                          /* NFAGG_FILTER_STORE_SAMPLING */
+    uint32_t n_atoms, n_ops, n_steps, pad_;
+    const nfagg_filter_atom* atoms;
+    const uint8_t* ops;
+    const nfagg_filter_step* steps;
+} nfagg_filter_spec;
+
+typedef struct nfagg_filter nfagg_filter;
+
+/* Check and compile a spec. k8s_table / net_table: the tables whose rows the TABLE atoms index (either may be NULL when no atom
+ * needs it; the flow layer needs k8s_table, FlowDirection neither); NFAGG_NET_DECODE_TCP_FLAGS of net_table decides what Flags
+ * is. Errors (NFAGG_EINVAL, nfagg_last_error names the atom, op or step): more atoms, ops or steps than the limits, an unknown
+ * kind, field, comparison, dimension, side, op or step kind, a NUM atom on a presence-only field, a TABLE atom whose table is
+ * NULL, whose truth is NULL or whose n_truth is not what its dimension has, an op that names an atom beyond n_atoms, a slice
+ * beyond n_ops, a stack that underflows, grows beyond NFAGG_FILTER_MAX_STACK or does not end with exactly one value, a KEEP
+ * step behind another kind, a group above 31, non-zero padding, a wrong struct_size. A spec with no steps is valid: it keeps
+ * everything. With a handle (the tables must be of the same handle) the program and the truth bytes are uploaded; h == NULL
+ * checks on the host alone (tables built with h == NULL; errors through nfagg_last_error(NULL)), and nfagg_filter_apply
+ * refuses such a filter. The tables must outlive the filter. */
+int nfagg_filter_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_filter_spec* spec,
+                        nfagg_filter** filter);
+void nfagg_filter_destroy(nfagg_filter* filter);
+
+/* The roll: sampled in (1) or out (0). value 0: 1. Else with fmix64 MurmurHash3's 64-bit finalizer and K = 0x9E3779B97F4A7C15
+ * (all arithmetic modulo 2^64)
+ *   u = fmix64(fmix64(seed + K * flow_index) ^ (K * (step + 1)))
+ * and the flow is in iff u % value == 0. flow_index = first_index + the flow's position in the call, step = the index of the
+ * KEEP or SAMPLE_IF step in the spec. Pure CPU; the device computes the same. */
+int nfagg_filter_roll(uint64_t seed, uint64_t flow_index, uint32_t step, uint32_t value);
+
+/* Run the filter over n records and compact. features (optional) as nfagg_encode_pb_content takes them: NULL, or a part's
+ * array NULL, means no flow has it. k8s_rows / net_rows: what nfagg_k8s_resolve / nfagg_net_resolve wrote for these records;
+ * required (NFAGG_EINVAL) when the program reads them, else ignored. opt: its now_unix_ns / mono_now_ns are read, and only by
+ * a program that names TimeFlowStartMs / TimeFlowEndMs (then required). seed, first_index: the roll's; pass first_index = the
+ * flows handed to earlier calls so that consecutive calls do not reuse rolls.
+ *   keep[i]      0 dropped, 1 kept, 2 kept and DEFERRED: an admitting keep rule stores max(sampling, 1) * value and the product
+ *                does not fit the record's 32 bits; the record is copied with sampling unchanged and the caller formats it.
+ *   rule[i]      the admitting KEEP step, NFAGG_FILTER_NO_RULE if none (no keep rule, or the flow was not admitted)
+ *   kept_idx[j]  the index of the j-th kept flow, ascending: the compaction is stable
+ *   out_records  (optional) the kept records, dense, sampling rewritten where a keep rule stored it
+ * keep and rule have n entries, kept_idx and out_records room for cap; any of the four may be NULL. *n_kept (required) is
+ * exact always; *n_deferred (optional). NFAGG_TRUNCATED when *n_kept > cap and kept_idx or out_records is asked for: neither is
+ * written, keep and rule are. n == 0 is valid; n above 2^32 - 2: NFAGG_ERANGE. All pointers HOST memory: */
+int nfagg_filter_apply(nfagg_handle* h, const nfagg_filter* filter, const void* records, size_t n, const nfagg_pb_features* features,
+                       const uint32_t* k8s_rows, const nfagg_net_row* net_rows, const nfagg_flp_options* opt, uint64_t seed, uint64_t first_index,
+                       uint8_t* keep, uint8_t* rule, uint32_t* kept_idx, void* out_records, size_t cap, size_t* n_kept, size_t* n_deferred);
+/* Same with records, the arrays inside d_features, the rows and the four outputs in DEVICE memory (records and out_records
+ * 16-byte, the rows and the feature arrays 8-byte, kept_idx 4-byte aligned); the features struct is in host memory.
+ * d_out_records must not overlap d_records, nor d_kept_idx any input: the compaction reads the records of other waves while it
+ * writes, so a call in place would race. */
+int nfagg_filter_apply_device(nfagg_handle* h, const nfagg_filter* filter, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                              const uint32_t* d_k8s_rows, const nfagg_net_row* d_net_rows, const nfagg_flp_options* opt, uint64_t seed,
+                              uint64_t first_index, uint8_t* d_keep, uint8_t* d_rule, uint32_t* d_kept_idx, void* d_out_records, size_t cap,
+                              size_t* n_kept, size_t* n_deferred);
+
+/* dst[j] = src[kept_idx[j]] for the side arrays that travel with the records (k8s_rows, net_rows, hash_ids, present, the
+ * part arrays, the network-event rows): n_src elements of elem_bytes each, elem_bytes 1, 2, 4, 8 or a multiple of 8 up to 64
+ * (else NFAGG_EINVAL). An index from n_src up yields a zeroed element. n_kept == 0 is valid. All pointers HOST memory: */
+int nfagg_gather(nfagg_handle* h, const void* src, size_t n_src, size_t elem_bytes, const uint32_t* kept_idx, size_t n_kept, void* dst);
+/* Same in DEVICE memory: src and dst aligned to elem_bytes for 1, 2, 4, to 8 otherwise (16 lets a multiple of 16 move in
+ * 16-byte units), kept_idx to 4. */
+int nfagg_gather_device(nfagg_handle* h, const void* d_src, size_t n_src, size_t elem_bytes, const uint32_t* d_kept_idx, size_t n_kept, void* d_dst);
+
+/* ------------------------------------------------------------------ */
 /* Sharding, stats, sync                                                */
 /* ------------------------------------------------------------------ */
 

@@ -27,5 +27,8 @@ from .pipeline import (CapacityLimiter, RecordToMap, DirectFLPStdout, BpfFlowCon
 from . import distributed
 from . import metrics
 from .metrics import PromCounters, PromMetrics
+from . import filter
+from .filter import TransformFilter, StageFilter, parse_query
+from .table import Filter, filter_roll
 from . import conntrack
 from .conntrack import ConnTrack

@@ -198,6 +198,29 @@ class ConnPartial(C.Structure):
                 ("packets", C.c_uint64 * 2), ("start_ms_min", C.c_int64), ("end_ms_max", C.c_int64), ("pad_", C.c_uint64 * 4)]
 
 
+# transform filter (nfagg_filter_*)
+FILTER_MAX_ATOMS, FILTER_MAX_OPS, FILTER_MAX_STEPS, FILTER_MAX_STACK, FILTER_NO_RULE = 64, 256, 32, 32, 0xFF
+FILTER_STORE_SAMPLING = 1
+
+
+class FilterAtom(C.Structure):
+    """nfagg_filter_atom (include/nfagg.h), 48 bytes."""
+    _fields_ = [("kind", C.c_uint8), ("field", C.c_uint8), ("cmp", C.c_uint8), ("dim", C.c_uint8), ("side", C.c_uint8), ("value_const", C.c_uint8),
+                ("pad_", C.c_uint8 * 2), ("value", C.c_int64), ("bytes", C.c_uint8 * 16), ("truth", C.c_void_p), ("n_truth", C.c_uint32),
+                ("pad2_", C.c_uint32)]
+
+
+class FilterStep(C.Structure):
+    """nfagg_filter_step (include/nfagg.h), 8 bytes."""
+    _fields_ = [("kind", C.c_uint8), ("group", C.c_uint8), ("value", C.c_uint16), ("op_begin", C.c_uint16), ("op_count", C.c_uint16)]
+
+
+class FilterSpec(C.Structure):
+    """nfagg_filter_spec (include/nfagg.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_atoms", C.c_uint32), ("n_ops", C.c_uint32), ("n_steps", C.c_uint32),
+                ("pad_", C.c_uint32), ("atoms", C.c_void_p), ("ops", C.c_void_p), ("steps", C.c_void_p)]
+
+
 TLS_VERSION, TLS_CIPHER_SUITE, TLS_GROUP = 0, 1, 2
 TLS_NAME_MAX, TLS_MAX_ROWS = 63, 256
 
@@ -329,6 +352,15 @@ SIGNATURES = {
     "nfagg_encode_conn_json": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_encode_conn_json_device": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _psz, _psz]),
     "nfagg_conn_hash": (C.c_uint64, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "nfagg_filter_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(FilterSpec), C.POINTER(_vp)]),
+    "nfagg_filter_destroy": (None, [_vp]),
+    "nfagg_filter_roll": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "nfagg_filter_apply": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpOptions), C.c_uint64, C.c_uint64, _vp, _vp, _vp,
+                                     _vp, _sz, _psz, _psz]),
+    "nfagg_filter_apply_device": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpOptions), C.c_uint64, C.c_uint64, _vp, _vp,
+                                            _vp, _vp, _sz, _psz, _psz]),
+    "nfagg_gather": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
+    "nfagg_gather_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),

@@ -220,7 +220,7 @@ class MapTracer:
             self._netevTable = None
 
     def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None, k8s=None, net=None,
-                       metrics=None):
+                       metrics=None, filter=None):
         """evictFlows for a direct-FLP `write: stdout, format: json` stage, without a Record per flow: the drained maps are merged,
         decorated with the sample decoder's network events and encoded on the GPU. Returns (buf, line_offsets, deferred) as
         FlowTable.encode_flp_json_content does; with tls_names (a TlsNames of the fetcher's table) the TLS keys are written too,
@@ -229,7 +229,12 @@ class MapTracer:
         (FlowTable.encode_flp_json_k8s). With net (a NetTable; needs k8s) also what its reinterpret_direction, add_subnet_label and
         decode_tcp_flags rules add (FlowTable.encode_flp_json_net). With metrics (a PromCounters or a PromMetrics; needs k8s) the
         `encode prom` metrics observe the same flows; a PromMetrics is handed the flows' feature parts as well, with a sample
-        decoder those nfagg_netev_resolve wrote, so that an injected drop counts like any other."""
+        decoder those nfagg_netev_resolve wrote, so that an injected drop counts like any other. With filter (a filter.StageFilter;
+        needs tls_names) the `transform filter` stage runs on the merged flows first: the metrics and the lines are those of the kept
+        flows, a third result lists the lines the caller formats itself (their stored Sampling overflows 32 bits) as (position, the
+        admitting keep step, the Sampling the reference stores), as StageFilter.apply returns them."""
+        if filter is not None and tls_names is None:
+            raise ValueError("filter needs tls_names")
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         if net is not None and k8s is None:
@@ -243,6 +248,19 @@ class MapTracer:
         names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         mono = monotonic_now & ((1 << 64) - 1)
         content = hasattr(metrics, "histograms")                        # a PromMetrics reads the feature parts
+        if filter is not None:
+            rows = tab = None
+            if self.sampleDecoder is not None:
+                present, parts, rows, tab = self.resolveNetworkEvents(present, parts)
+            recs, present, parts, rows, held = filter.apply(table, recs, k8s, net, agent_ip, current, mono, present, parts, rows)
+            if metrics is not None:
+                metrics.observe(table, recs, k8s, net, agent_ip, **(dict(features=(present, parts)) if content else {}))
+            args = (current, mono, names, agent_ip, time_received, unknown, present, parts, rows, tab)
+            if net is not None:
+                return table.encode_flp_json_net(recs, tls_names, k8s, net, *args) + (held,)
+            if k8s is not None:
+                return table.encode_flp_json_k8s(recs, tls_names, k8s, *args) + (held,)
+            return table.encode_flp_json_tls(recs, tls_names, *args) + (held,)
         if metrics is not None and not content:
             metrics.observe(table, recs, k8s, net, agent_ip)
         if self.sampleDecoder is None:                                  # s == nil: no events, no injected drops (record.go:126)
@@ -387,14 +405,18 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
     One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
 
     def __init__(self, table, stream, names=None, agent_ip=None, unknown: bytes = b"unknown", time_received: Callable[[], int] = None,
-                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None, metrics=None):
+                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None, metrics=None, filter=None):
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         if net is not None and k8s is None:
             raise ValueError("net needs k8s: reinterpret_direction reads the Kubernetes keys")
         if metrics is not None and k8s is None:
             raise ValueError("metrics needs k8s: the counters group by the Kubernetes keys")
-        self.table, self.stream, self.metrics = table, stream, metrics
+        if filter is not None and tls_names is None:
+            raise ValueError("filter needs tls_names: only a flow whose stored Sampling overflows is left to the fallback")
+        # with a filter the fallback is called as fallback(record, now_ns, mono_ns, sampling=<the Sampling the reference stores>):
+        # the record's 32 bits cannot carry it, so the record keeps its own and the line's value arrives beside it
+        self.table, self.stream, self.metrics, self.filter = table, stream, metrics, filter
         self.names = names if names is not None else np.zeros(0, dtype=INTF_NAME)
         self.agent_ip, self.unknown = agent_ip, unknown
         self.time_received = time_received or (lambda: int(time.time()))   # time.Now().Unix()
@@ -410,6 +432,12 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         n = len(raw)
         if n == 0:
             return 0
+        held = []
+        if self.filter is not None:                       # `transform filter`: behind the resolves, in front of every encoder and fold
+            raw, _, _, _, held = self.filter.apply(self.table, raw, self.k8s, self.net, self.agent_ip, now_ns, mono_ns)
+            n = len(raw)
+            if n == 0:
+                return 0
         if self.metrics is not None:
             self.metrics.observe(self.table, raw, self.k8s, self.net, self.agent_ip)
         if self.tls_names is not None:
@@ -422,8 +450,14 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
             else:
                 buf, off = self.table.encode_flp_json_tls(raw, self.tls_names, now_ns, mono_ns & ((1 << 64) - 1), self.names, self.agent_ip,
                                                           self.time_received(), self.unknown)
-            self.stream.write(memoryview(np.ascontiguousarray(buf))[:int(off[n])])
+            raw_buf, start = memoryview(np.ascontiguousarray(buf)), 0
+            for j, _, stored in held:                     # a kept flow whose stored Sampling needs more than 32 bits: the host's line
+                self.stream.write(raw_buf[start:int(off[j])])
+                self.stream.write(self.fallback(raw[j], now_ns, mono_ns, sampling=stored))
+                start = int(off[j + 1])
+            self.stream.write(raw_buf[start:int(off[n])])
             self.lines += n
+            self.deferred += len(held)
             return n
         buf, off, deferred = self._encode(raw, now_ns, mono_ns & ((1 << 64) - 1), self.names, self.agent_ip, self.time_received(),
                                           self.unknown)

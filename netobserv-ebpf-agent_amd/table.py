@@ -881,6 +881,68 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, n_conns.value, n_disc.value
 
+    # -- transform filter (nfagg_filter_*): FLP's `transform filter` stage as a device program, the stable compaction, the gather
+    def filter(self, spec, k8s: "K8sTable" = None, net: "NetTable" = None) -> "Filter":
+        """A compiled filter on this handle's device; spec: a filter.TransformFilter (or anything with its spec())."""
+        return Filter(spec, k8s, net, self)
+
+    def filter_apply(self, flt: "Filter", records: np.ndarray, k8s_rows: np.ndarray = None, net_rows: np.ndarray = None, features=None,
+                     now_unix_ns: int = 0, mono_now_ns: int = 0, seed: int = 0, first_index: int = 0, cap: int = None, out_records: bool = True):
+        """nfagg_filter_apply. features: (present, parts) as encode_flp_json_content takes them, or None. cap: room for the kept
+        (default: every flow). Returns (rc, keep uint8[n], rule uint8[n], kept_idx uint32[n_kept], out_records FLOW_RECORD[n_kept] or
+        None, n_kept, n_deferred); with rc == L.TRUNCATED kept_idx and out_records are empty and n_kept is exact."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        cap = n if cap is None else int(cap)
+        kr = np.ascontiguousarray(k8s_rows, dtype=np.uint32) if k8s_rows is not None else None
+        nr = np.ascontiguousarray(net_rows, dtype=NET_ROW) if net_rows is not None else None
+        feat, keep_alive = (None, None)
+        if features is not None and features[0] is not None:
+            feat, keep_alive = self._pb_features(n, features[0], {k: v for k, v in self._content_parts(features[1]).items() if v is not None})
+        keep, rule = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        idx = np.zeros(min(cap, n), dtype=np.uint32)
+        out = np.zeros(min(cap, n), dtype=FLOW_RECORD) if out_records else None
+        o, _ = flp_options(now_unix_ns, mono_now_ns)
+        n_kept, n_def = C.c_size_t(0), C.c_size_t(0)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        rc = L.lib.nfagg_filter_apply(self._h, flt._t, ptr(r), n, C.byref(feat) if feat is not None else None, ptr(kr), ptr(nr), C.byref(o),
+                                      seed, first_index, ptr(keep), ptr(rule), ptr(idx), ptr(out), cap, C.byref(n_kept), C.byref(n_def))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        k = n_kept.value if rc == L.OK else 0
+        return rc, keep, rule, idx[:k], (out[:k] if out is not None else None), n_kept.value, n_def.value
+
+    def filter_apply_device(self, flt: "Filter", d_records: int, n: int, d_k8s_rows: int = 0, d_net_rows: int = 0, d_features=None,
+                            now_unix_ns: int = 0, mono_now_ns: int = 0, seed: int = 0, first_index: int = 0, d_keep: int = 0, d_rule: int = 0,
+                            d_kept_idx: int = 0, d_out_records: int = 0, cap: int = 0):
+        """Device-resident variant (raw device pointers; d_features = (d_present, {part: pointer}) or None). Returns (rc, n_kept,
+        n_deferred)."""
+        feat = self._pb_features(n, d_features[0], self._content_parts(d_features[1]), device=True)[0] if d_features is not None else None
+        o, _ = flp_options(now_unix_ns, mono_now_ns)
+        n_kept, n_def = C.c_size_t(0), C.c_size_t(0)
+        rc = L.lib.nfagg_filter_apply_device(self._h, flt._t, C.c_void_p(d_records or None), n, C.byref(feat) if feat is not None else None,
+                                             C.c_void_p(d_k8s_rows or None), C.c_void_p(d_net_rows or None), C.byref(o), seed, first_index,
+                                             C.c_void_p(d_keep or None), C.c_void_p(d_rule or None), C.c_void_p(d_kept_idx or None),
+                                             C.c_void_p(d_out_records or None), cap, C.byref(n_kept), C.byref(n_def))
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, n_kept.value, n_def.value
+
+    def gather(self, src: np.ndarray, kept_idx: np.ndarray) -> np.ndarray:
+        """nfagg_gather: src[kept_idx] along the first axis for a side array that travels with the records (rows, hash ids, present
+        bits, parts); an element is 1, 2, 4, 8 or a multiple of 8 up to 64 bytes."""
+        a = np.ascontiguousarray(src)
+        idx = np.ascontiguousarray(kept_idx, dtype=np.uint32)
+        elem = a.nbytes // len(a) if len(a) else (a.dtype.itemsize * int(np.prod(a.shape[1:], dtype=np.int64)))
+        out = np.zeros((idx.size,) + a.shape[1:], dtype=a.dtype)
+        self._check(L.lib.nfagg_gather(self._h, a.ctypes.data_as(C.c_void_p) if a.size else None, len(a), elem,
+                                       idx.ctypes.data_as(C.c_void_p) if idx.size else None, idx.size,
+                                       out.ctypes.data_as(C.c_void_p) if idx.size else None))
+        return out
+
+    def gather_device(self, d_src: int, n_src: int, elem_bytes: int, d_kept_idx: int, n_kept: int, d_dst: int) -> None:
+        """Device-resident variant (raw device pointers)."""
+        self._check(L.lib.nfagg_gather_device(self._h, C.c_void_p(d_src or None), n_src, elem_bytes, C.c_void_p(d_kept_idx or None), n_kept,
+                                              C.c_void_p(d_dst or None)))
+
     def stats(self) -> L.Stats:
         s = L.Stats()
         self._check(L.lib.nfagg_stats_get(self._h, C.byref(s)))
@@ -1389,6 +1451,24 @@ def net_render(net: "NetTable", side: int, label: int) -> bytes:
     if rc != L.OK:
         raise NfaggError(rc, (L.lib.nfagg_last_error(None) or b"").decode())
     return buf[:n.value].tobytes()
+
+
+class Filter(_CallerTable):
+    """A compiled `transform filter` stage (nfagg_filter_create). spec: a filter.TransformFilter; k8s / net: the tables whose rows
+    its TABLE atoms index, which must outlive it. With a FlowTable the program lives on its device and serves filter_apply; with
+    table=None (and tables built the same way) the spec is checked on the host only."""
+
+    def __init__(self, spec, k8s: "K8sTable" = None, net: "NetTable" = None, table: "FlowTable" = None):
+        s, keep = spec.spec() if hasattr(spec, "spec") else spec
+        self._create(table, L.lib.nfagg_filter_destroy,
+                     lambda h, out: L.lib.nfagg_filter_create(h, k8s._t if k8s is not None else None, net._t if net is not None else None, C.byref(s), out))
+        self._tables = (k8s, net)
+        self.steps = list(getattr(spec, "steps", ()))     # (kind, group, value, op_begin, op_count): StageFilter reads a keep step's value
+
+
+def filter_roll(seed: int, flow_index: int, step: int, value: int) -> bool:
+    """nfagg_filter_roll: the device path's roll of step `step` for the flow with running index flow_index. Pure CPU."""
+    return bool(L.lib.nfagg_filter_roll(seed & (2**64 - 1), flow_index & (2**64 - 1), step, value))
 
 
 METRIC_GROUP = np.dtype([("src_class", "<u4"), ("dst_class", "<u4"), ("src_label", "<u2"), ("dst_label", "<u2"), ("direction", "u1"), ("layer", "u1"),

@@ -49,7 +49,15 @@ tool's own count. --k8s-trace covers the k_conn_* kernels. The flow logs follow 
 nfagg_encode_flp_json_conn_device with the tables of the --net leg, whose _net line above is what its time per output byte is read
 against; --k8s-trace covers the k_connlog_* kernels. Then the conversation records, one per connection of the fold
 (nfagg_encode_conn_json_device, seven output fields of which two are split): each connection's first flow as its carrier, the
-partial's sums as its values; --k8s-trace covers the k_conn_json_* kernels (they match k_conn_)."""
+partial's sums as its values; --k8s-trace covers the k_conn_json_* kernels (they match k_conn_).
+
+--filter (with --k8s --net): the transform filter leg on top, on the same records, rows and tables in the same run: a keep_entry_query
+of three atoms, (SrcPort < p or DstPort < q) and with(Bytes), with p the median source port and q the 0.3 quantile of the destination ports of the evicted flows, so that about
+half of the flows stay, once without sampling and once with keepEntrySampling 10 and samplingField Sampling. Reported: the median wall
+time of nfagg_filter_apply_device (eval, the scan, the read-back of the count, the compaction with its records), of the two
+nfagg_gather_device calls for the Kubernetes rows and the net rows, and of nfagg_encode_flp_json_net_device on the kept flows, beside
+the unfiltered _net call and the net join of the same run; the bytes a flow moves by this tool's own count as a fraction of the
+read-stream rate measured in the same run. --k8s-trace covers the k_filter_* and k_gather kernels."""
 import io
 import os
 import queue
@@ -76,6 +84,7 @@ K8S = "--k8s" in sys.argv[1:]
 NET = "--net" in sys.argv[1:]
 METRICS = "--metrics" in sys.argv[1:]
 CONNTRACK = "--conntrack" in sys.argv[1:]
+FILTER = "--filter" in sys.argv[1:]
 NET_CATEGORIES = [("cat-%d" % c, ["172.%d.%d.0/24" % (16 + c, k) for k in range(8)] + ["2001:db8:%x::/48" % (16 * c + k) for k in range(1)]) for c in range(5)] + \
                  [("pods", ["100.64.0.0/10"]), ("everything", ["0.0.0.0/0", "::/0"])]
 K8S_ROWS = 100_000
@@ -148,7 +157,7 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_connlog_|fillBuffer|scan", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_connlog_|k_filter_|k_gather|fillBuffer|scan", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
             grid = int(row.get("Grid_Size_X") or row.get("Grid_Size") or 0)
@@ -302,6 +311,45 @@ def metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net):
           f"measured here ({rate / 1e9:.0f} GB/s over 1 GiB)")
 
 
+def filter_leg(tab, d_ev, m, tls, k8s, net, d_rows, d_net, d_off, dt_net_join, dt_net_encode):
+    recs = d_ev[: m * 144].cpu().numpy().view(nf.FLOW_RECORD)
+    p, q = int(np.quantile(recs["id"]["src_port"], 0.5)), int(np.quantile(recs["id"]["dst_port"], 0.3))
+    query = "(SrcPort < %d or DstPort < %d) and with(Bytes)" % (p, q)
+    del recs
+    rate = read_stream_rate()
+    d_keep, d_rule = torch.empty(m, dtype=torch.uint8, device="cuda"), torch.empty(m, dtype=torch.uint8, device="cuda")
+    d_idx, d_out = torch.empty(m, dtype=torch.int32, device="cuda"), torch.empty(m * 144 + 16, dtype=torch.uint8, device="cuda")
+    print(f"  filter   keep_entry_query: {query}; the unfiltered _net call {dt_net_encode * 1e3:.3f} ms, the net join {dt_net_join * 1e3:.3f} ms, "
+          f"read stream {rate / 1e9:.0f} GB/s over 1 GiB")
+    for sampling in (0, 10):
+        cfg = dict(samplingField="Sampling", rules=[dict(type="keep_entry_query", keepEntryQuery=query, keepEntrySampling=sampling)])
+        with tab.filter(nf.TransformFilter(cfg)) as flt:
+            apply = lambda: tab.filter_apply_device(flt, d_ev.data_ptr(), m, d_rows.data_ptr(), d_net.data_ptr(), None, NOW, MONO, 1, 0, d_keep.data_ptr(),  # noqa: E731
+                                                    d_rule.data_ptr(), d_idx.data_ptr(), d_out.data_ptr(), m)
+            (rc, kept, n_def), dt_apply = timed(apply)
+            (_, kept0, _), dt_eval = timed(lambda: tab.filter_apply_device(flt, d_ev.data_ptr(), m, 0, 0, None, NOW, MONO, 1, 0, d_keep.data_ptr(), d_rule.data_ptr()))
+            assert rc == nf.OK and kept0 == kept and int((d_keep != 0).sum()) == kept
+            d_rows2, d_net2 = torch.empty((max(kept, 1), 2), dtype=torch.int32, device="cuda"), torch.empty((max(kept, 1), 2), dtype=torch.int32, device="cuda")
+            _, dt_gather = timed(lambda: (tab.gather_device(d_rows.data_ptr(), m, 8, d_idx.data_ptr(), kept, d_rows2.data_ptr()),
+                                          tab.gather_device(d_net.data_ptr(), m, 8, d_idx.data_ptr(), kept, d_net2.data_ptr())))
+            rc, need = tab.encode_flp_json_net_device(d_out.data_ptr(), kept, tls, k8s, net, NOW, MONO, names, agent, 1_700_000_000, 0, 0, d_off.data_ptr())
+            d_lines = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+            (rc, wrote), dt_enc = timed(lambda: tab.encode_flp_json_net_device(d_out.data_ptr(), kept, tls, k8s, net, NOW, MONO, names, agent, 1_700_000_000,
+                                                                              d_lines.data_ptr(), need, d_off.data_ptr()))
+            assert rc == nf.OK and wrote == need
+            del d_lines
+        # eval: a lane reads its record and writes keep, rule, the sampling and its scan offset; compact: per flow the scan offsets of a
+        # flow and its successor, per kept flow the record read and written, the sampling read, the index written
+        ev_bytes, co_bytes = m * (144 + 1 + 1 + 4 + 4), m * 8 + kept * (2 * 144 + 4 + 4)
+        dt_compact = max(dt_apply - dt_eval, 1e-9)
+        print(f"  filter   sampling {sampling:2d}: {kept} of {m} flows kept ({kept / m:.3f}), {n_def} deferred; apply {dt_apply * 1e3:.3f} ms per call = "
+              f"{m / dt_apply / 1e6:.1f} M flows/s ({dt_apply / dt_net_join:.2f} x the net join); without the compaction {dt_eval * 1e3:.3f} ms = "
+              f"{ev_bytes / dt_eval / 1e9:.1f} GB/s, {ev_bytes / dt_eval / rate:.3f} of the read stream; the compaction's share {dt_compact * 1e3:.3f} ms = "
+              f"{co_bytes / dt_compact / 1e9:.1f} GB/s, {co_bytes / dt_compact / rate:.3f} of the read stream")
+        print(f"           gather of both row arrays {dt_gather * 1e3:.3f} ms; _net on the kept flows {dt_enc * 1e3:.3f} ms for {wrote} bytes "
+              f"({dt_enc / dt_net_encode:.3f} of the unfiltered call); apply + gather + encode = {(dt_apply + dt_gather + dt_enc) / dt_net_encode:.3f} of it")
+
+
 def per_byte(what, m, dt, wrote):
     print(f"  {what:8s} {m} flows -> {wrote} bytes ({wrote / m:.1f} B/line) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s, "
           f"{dt / wrote * 1e12:.3f} ps per output byte")
@@ -381,6 +429,8 @@ for flows in ((10_000_000,) if (CONTENT or TLS) and not K8S else (1_000_000, 10_
                               f"{int((got['src_label'] != nf._lib.NET_NO_LABEL).sum() + (got['dst_label'] != nf._lib.NET_NO_LABEL).sum())} of {2 * m} endpoints labelled, "
                               f"{int((got['direction'] != nf._lib.NET_NO_DIRECTION).sum())} of {m} flows with a direction; the join alone: {dt_net * 1e3:.3f} ms per call")
                         del d_out
+                        if FILTER:
+                            filter_leg(tab, d_ev, m, tls, k8s, net, d_rows, d_net, d_off, dt_net, dt)
                         if METRICS:
                             metrics_leg(tab, k8s, d_ev, m, d_rows, d_net)
                             if CONNTRACK:
