@@ -2078,6 +2078,11 @@ int nfagg_window_restart_device(nfagg_handle* h, uint32_t n_shards, uint32_t sha
 int nfagg_debug_skip_sequence(nfagg_handle* h, uint64_t records);
 int nfagg_group_debug_skip_sequence(nfagg_group* g, uint64_t records);   /* the group's common position (local fold) / every member's */
 
+/* Testing aid: the device and page-locked allocations of the library that are alive in this process (handles, caller tables,
+ * filters, layouts, groups; not nfagg_host_alloc's buffers, which are the caller's). Every object returns to the count it
+ * found when it is destroyed; a grow-only scratch buffer that grows replaces its block and leaves the count as it was. */
+uint64_t nfagg_debug_live_buffers(void);
+
 #ifdef __cplusplus
 }
 #endif

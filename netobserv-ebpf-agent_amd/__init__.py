@@ -13,7 +13,7 @@ from ._lib import (OK, FULL, TRUNCATED, REASON_TIMEOUT, REASON_FULL, REASON_CLOS
 from .records import (FLOW_ID, FLOW_METRICS, FLOW_RECORD, ADDITIONAL, DNS, PKT_DROP, NETWORK_EVENTS, XLAT, QUIC,
                       ROLLUP_KINDS, sort_by_key, INTF_NAME, intf_table)
 from .table import (FlowTable, FlowGroup, NfaggError, PinnedRecords, key_hash, shard_of, ip_hash, hll_estimate_from_histogram, record_times,
-                    host_threads, host_info, device_numa_node, ipfix_template, ipfix_options, IPFIX_TEMPLATE_ID_V4,
+                    host_threads, host_info, device_numa_node, debug_live_buffers, ipfix_template, ipfix_options, IPFIX_TEMPLATE_ID_V4,
                     IPFIX_TEMPLATE_ID_V6, flp_options, NetevTable, netev_render, TlsNames, GO_TLS_NAMES, K8sTable, k8s_render,
                     NetTable, net_render, net_cidrs, NET_ROW, MetricsTable, METRIC_GROUP, metrics_group_hash, K8S_FIELDS,
                     METRIC_GROUP_CONTENT, metrics_group_hash_content, flp_enum_name, CONN_PARTIAL, conn_hash,

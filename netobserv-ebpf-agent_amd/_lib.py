@@ -372,6 +372,7 @@ SIGNATURES = {
     "nfagg_sync": (C.c_int, [_vp]),
     "nfagg_stream": (_vp, [_vp]),
     "nfagg_debug_skip_sequence": (C.c_int, [_vp, C.c_uint64]),
+    "nfagg_debug_live_buffers": (C.c_uint64, []),
     "nfagg_set_sequence": (C.c_int, [_vp, C.c_uint64]),
     "nfagg_partial_bytes": (C.c_size_t, [_vp]),
     "nfagg_partials_export_device": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _sz, C.POINTER(C.c_uint64), _psz]),

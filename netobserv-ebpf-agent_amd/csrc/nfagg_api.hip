@@ -1,8 +1,11 @@
 // nfagg_api.hip — the flow table behind the C ABI of libnfagg (include/nfagg.h): handle, pinned
 // staging ring, batch control flow of Accounter.Account
 // (pkg/flow/account.go:58-100) around the kernels. No CPU fallback: without a
-// gfx950 device nfagg_create fails. The rest of the ABI's host side: nfagg_api_export.hip (the encoders),
-// nfagg_api_tables.hip (the caller tables), nfagg_api_aux.hip (rollups, map merge, sketches).
+// gfx950 device nfagg_create fails. The handle owns its resources through the owner types of nfagg_handle.h: nothing is
+// freed by hand here, nfagg_destroy deletes the handle. The rest of the ABI's host side: nfagg_api_account.hip (nfagg_account*:
+// the record arm with its evictions on full) and nfagg_api_group.hip (the multi-GPU group), which drive the handle through the
+// functions declared in nfagg_api_core.h; nfagg_api_export.hip (the encoders), nfagg_api_tables.hip (the caller tables),
+// nfagg_api_aux.hip (rollups, map merge, sketches).
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -19,6 +22,7 @@
 #include "../../include/nfagg.h"
 #include "nfagg_internal.h"
 #include "nfagg_handle.h"
+#include "nfagg_api_core.h"
 #include "nfagg_hostpool.h"
 
 using namespace nfagg;
@@ -39,7 +43,7 @@ thread_local std::string g_create_error;
 
 }  // namespace
 
-// Declared in nfagg_handle.h: the other host files of the ABI report errors and grow scratch through these.
+// Declared in nfagg_handle.h: the other host files of the ABI report errors through this.
 namespace nfagg {
 
 int fail(nfagg_handle* h, int code, const char* fmt, ...) {
@@ -52,24 +56,10 @@ int fail(nfagg_handle* h, int code, const char* fmt, ...) {
     return code;
 }
 
-int ensure_bytes(nfagg_handle* h, void** p, size_t* cap, size_t need) {
-    if (*cap >= need) return NFAGG_OK;
-    if (*p) { hipFree(*p); *p = nullptr; *cap = 0; }
-    size_t want = need + need / 4 + 4096;
-    hipError_t e = hipMalloc(p, want);
-    if (e != hipSuccess) return fail(h, NFAGG_ENOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-    *cap = want;
-    return NFAGG_OK;
-}
-
-}  // namespace nfagg
-
-namespace {
-
 // --- profiling: HIP events on the handle's stream around the dominant kernels
 void prof_begin(nfagg_handle* h, EventPair& ep, int kind) {
     if (h->ev_free.empty()) {
-        hipEventCreate(&ep.a); hipEventCreate(&ep.b);
+        for (hipEvent_t* e : {&ep.a, &ep.b}) { h->ev_pool.emplace_back(); h->ev_pool.back().create(hipEventDefault); *e = h->ev_pool.back(); }
     } else { ep = h->ev_free.back(); h->ev_free.pop_back(); }
     ep.kind = kind;
     hipEventRecord(ep.a, h->stream);
@@ -105,13 +95,13 @@ int launch_ingest_profiled(nfagg_handle* h, const void* d, uint64_t n, uint64_t 
         if (qcap > h->tv.spill.qcap || ovf_cap > h->tv.spill.ovf_cap) {
             if (qcap < h->tv.spill.qcap) qcap = h->tv.spill.qcap;
             const size_t qbytes = (size_t)kSpillParts * qcap * sizeof(uint32_t);
-            int rc = ensure_bytes(h, &h->d_spill, &h->d_spill_cap, qbytes + ovf_cap * sizeof(uint32_t));
+            int rc = h->spill_queues.ensure(h, qbytes + ovf_cap * sizeof(uint32_t));
             if (rc != NFAGG_OK) return rc;
-            h->tv.spill.queue = (uint32_t*)h->d_spill;
+            h->tv.spill.queue = h->spill_queues.as<uint32_t>();
             h->tv.spill.qcap = (uint32_t)qcap;
-            h->tv.spill.ovf = (uint32_t*)((char*)h->d_spill + qbytes);
-            h->tv.spill.ovf_cap = (uint32_t)((h->d_spill_cap - qbytes) / sizeof(uint32_t) > 0xfffffff0ull ? 0xfffffff0ull
-                                             : ((h->d_spill_cap - qbytes) / sizeof(uint32_t)) & ~3ull);
+            h->tv.spill.ovf = (uint32_t*)(h->spill_queues.as<char>() + qbytes);
+            h->tv.spill.ovf_cap = (uint32_t)((h->spill_queues.cap - qbytes) / sizeof(uint32_t) > 0xfffffff0ull ? 0xfffffff0ull
+                                             : ((h->spill_queues.cap - qbytes) / sizeof(uint32_t)) & ~3ull);
         }
         if (h->cfg.mode == NFAGG_MODE_KERNEL_DEDUP) {
             // the partition pass sorts its items by sub-partition first when a partition's flows will not fit one cache (1024
@@ -120,11 +110,9 @@ int launch_ingest_profiled(nfagg_handle* h, const void* d, uint64_t n, uint64_t 
             h->tv.spill.sort_first = h->cfg.ingest_variant == kVariantDedupSortFirst ? 2u : (guess > 2500000ull ? 1u : 0u);    // 2: whatever the partition's size (tests)      // ~1200 sub-flows per partition: one cache (and its retry round) still holds them
         }
         if (h->cfg.mode == NFAGG_MODE_KERNEL_DEDUP && !h->tv.spill.xp) {     // exported cache entries of the streaming pass (38 MB)
-            size_t cap = 0;
-            void* p = nullptr;
-            int rc = ensure_bytes(h, &p, &cap, (size_t)kDedupXpBytes);
+            int rc = h->spill_xp.ensure(h, (size_t)kDedupXpBytes);
             if (rc != NFAGG_OK) return rc;
-            h->tv.spill.xp = (uint4*)p;
+            h->tv.spill.xp = h->spill_xp.as<uint4>();
         }
     }
     if (prof) { if (h->ev_pending.size() >= 8192) prof_resolve(h); prof_begin(h, ep, 0); }
@@ -205,9 +193,9 @@ int snapshot_sketches(nfagg_handle* h, bool restore) {
     if (!h->sk.flags) return NFAGG_OK;
     const size_t cmb = (h->sk.flags & NFAGG_SKETCH_CM) ? ((size_t)h->sk.cm_depth << h->sk.cm_log2w) * sizeof(uint64_t) : 0;
     const size_t hlb = (h->sk.flags & NFAGG_SKETCH_HLL) ? ((size_t)1 << h->sk.hll_p) : 0;      // one byte per register
-    int rc = ensure_bytes(h, &h->d_opt[1], &h->d_opt_cap[1], 2 * (cmb + hlb));
+    int rc = h->opt.sketches.ensure(h, 2 * (cmb + hlb));
     if (rc != NFAGG_OK) return rc;
-    char* snap = (char*)h->d_opt[1];
+    char* snap = h->opt.sketches.as<char>();
     for (int k = 0; k < 2; k++) {
         if (cmb) HIP_TRY(h, restore ? hipMemcpyAsync(h->sk.cm[k], snap + k * cmb, cmb, hipMemcpyDeviceToDevice, h->stream)
                                     : hipMemcpyAsync(snap + k * cmb, h->sk.cm[k], cmb, hipMemcpyDeviceToDevice, h->stream));
@@ -217,7 +205,7 @@ int snapshot_sketches(nfagg_handle* h, bool restore) {
     return NFAGG_OK;
 }
 
-// The pieces of an optimistic fold (also driven member by member by the multi-GPU group, nfagg_group.inc):
+// The pieces of an optimistic fold (also driven member by member by the multi-GPU group, nfagg_api_group.hip):
 //   opt_begin    raw copy of the live slots and of the sketches (h->live exact on entry: the caller refreshed the counters)
 //   opt_fold     the fold itself, asynchronous, sequence numbers from h->epoch_seq
 //   opt_result   waits; did the chunk cross max_entries / was it aborted; if it crossed: the index (relative to the
@@ -225,12 +213,6 @@ int snapshot_sketches(nfagg_handle* h, bool restore) {
 //                number among the slots the chunk claimed
 //   opt_commit   the fold stands: account for it
 //   opt_rollback table, sketches and counters as opt_begin found them
-struct OptState {
-    uint64_t old_live = 0, seq0 = 0, room = 0, n_after = 0;
-    DevCounters before{};
-    bool was_unclustered = false;
-};
-
 int opt_begin(nfagg_handle* h, OptState& st) {
     const uint64_t maxe = h->cfg.max_entries;
     st.old_live = h->live; st.seq0 = h->epoch_seq;
@@ -239,8 +221,8 @@ int opt_begin(nfagg_handle* h, OptState& st) {
     st.was_unclustered = h->epoch_unclustered;
     int rc;
     if (st.old_live) {
-        if ((rc = ensure_bytes(h, &h->d_opt[0], &h->d_opt_cap[0], snapshot_bytes(h->tv, st.old_live))) != NFAGG_OK) return rc;
-        hipError_t e = launch_snapshot(h->tv, st.old_live, h->d_opt[0], false, h->stream);
+        if ((rc = h->opt.slots.ensure(h, snapshot_bytes(h->tv, st.old_live))) != NFAGG_OK) return rc;
+        hipError_t e = launch_snapshot(h->tv, st.old_live, h->opt.slots.p, false, h->stream);
         if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "snapshot launch failed: %s", hipGetErrorString(e));
     }
     return snapshot_sketches(h, false);
@@ -264,11 +246,11 @@ int opt_result(nfagg_handle* h, OptState& st, uint64_t chunk, bool* crossed, boo
     size_t temp_bytes = 0;
     hipError_t e = launch_sort_u32(nullptr, nullptr, m, nullptr, &temp_bytes, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "sort size query failed: %s", hipGetErrorString(e));
-    if ((rc = ensure_bytes(h, &h->d_opt[2], &h->d_opt_cap[2], 2 * m * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_opt[3], &h->d_opt_cap[3], temp_bytes + 16)) != NFAGG_OK) return rc;
-    uint32_t* seqs = (uint32_t*)h->d_opt[2];
+    if ((rc = h->opt.first_seqs.ensure(h, 2 * m * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = h->opt.sort_tmp.ensure(h, temp_bytes + 16)) != NFAGG_OK) return rc;
+    uint32_t* seqs = h->opt.first_seqs.as<uint32_t>();
     e = launch_first_seqs(h->tv, st.old_live, st.n_after, seqs, h->stream);
-    if (e == hipSuccess) e = launch_sort_u32(seqs, seqs + m, m, h->d_opt[3], &temp_bytes, h->stream);
+    if (e == hipSuccess) e = launch_sort_u32(seqs, seqs + m, m, h->opt.sort_tmp.p, &temp_bytes, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "split search failed: %s", hipGetErrorString(e));
     uint32_t split_seq = 0;
     HIP_TRY(h, hipMemcpyAsync(&split_seq, seqs + m + st.room, sizeof split_seq, hipMemcpyDeviceToHost, h->stream));
@@ -291,7 +273,7 @@ void opt_commit(nfagg_handle* h, const OptState& st, uint64_t chunk) {
 int opt_rollback(nfagg_handle* h, const OptState& st) {
     h->stats.optimistic_rollbacks++;
     hipError_t e = launch_discard(h->tv, st.old_live, st.n_after, h->stream);
-    if (e == hipSuccess && st.old_live) e = launch_snapshot(h->tv, st.old_live, h->d_opt[0], true, h->stream);
+    if (e == hipSuccess && st.old_live) e = launch_snapshot(h->tv, st.old_live, h->opt.slots.p, true, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "rollback launch failed: %s", hipGetErrorString(e));
     int rc = snapshot_sketches(h, true);
     if (rc != NFAGG_OK) return rc;
@@ -424,8 +406,8 @@ int ingest_device_core(nfagg_handle* h, const void* d_records, size_t n, size_t*
         const uint64_t chunk = rem < h->careful_chunk ? rem : h->careful_chunk;
         const uint64_t seq0 = h->epoch_seq;
         h->epoch_unclustered = true;
-        hipError_t e = launch_claim(h->tv, d, chunk, seq0 - h->seq_origin, h->d_slot_idx, h->stream);
-        if (e == hipSuccess) e = launch_first_flags(h->tv, h->d_slot_idx, chunk, seq0 - h->seq_origin, h->d_flags, h->d_block_counts, h->stream);
+        hipError_t e = launch_claim(h->tv, d, chunk, seq0 - h->seq_origin, h->d_slot_idx.as<uint32_t>(), h->stream);
+        if (e == hipSuccess) e = launch_first_flags(h->tv, h->d_slot_idx.as<uint32_t>(), chunk, seq0 - h->seq_origin, h->d_flags.as<uint8_t>(), h->d_block_counts.as<uint32_t>(), h->stream);
         if (e != hipSuccess) { rc = fail(h, NFAGG_EDEVICE, "claim launch failed: %s", hipGetErrorString(e)); break; }
         const uint64_t nblk = (chunk + kFlagBlock - 1) / kFlagBlock;
         h->h_block_counts.resize(nblk);
@@ -433,8 +415,8 @@ int ingest_device_core(nfagg_handle* h, const void* d_records, size_t n, size_t*
         // small chunks (every chunk of a stream with tiny epochs): counts and flags come back together, one round trip
         const bool one_trip = chunk <= kCarefulMaxBatch;
         uint32_t* counts_dst = one_trip ? reinterpret_cast<uint32_t*>(h->h_careful) : h->h_block_counts.data();
-        e = hipMemcpyAsync(counts_dst, h->d_block_counts, nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess && one_trip) e = hipMemcpyAsync(h->h_careful + kCarefulCountsBytes, h->d_flags, chunk, hipMemcpyDeviceToHost, h->stream);
+        e = hipMemcpyAsync(counts_dst, h->d_block_counts.p, nblk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess && one_trip) e = hipMemcpyAsync(h->h_careful + kCarefulCountsBytes, h->d_flags.p, chunk, hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) { rc = fail(h, NFAGG_EDEVICE, "claim sync failed: %s", hipGetErrorString(e)); break; }
         if (one_trip) memcpy(h->h_block_counts.data(), counts_dst, nblk * sizeof(uint32_t));
@@ -457,7 +439,7 @@ int ingest_device_core(nfagg_handle* h, const void* d_records, size_t n, size_t*
         const uint8_t* fl = fl_buf;
         if (one_trip) fl = h->h_careful + kCarefulCountsBytes + off;
         else {
-            e = hipMemcpy(fl_buf, h->d_flags + off, cnt, hipMemcpyDeviceToHost);
+            e = hipMemcpy(fl_buf, h->d_flags.as<uint8_t>() + off, cnt, hipMemcpyDeviceToHost);
             if (e != hipSuccess) { rc = fail(h, NFAGG_EDEVICE, "flag copy failed: %s", hipGetErrorString(e)); break; }
         }
         uint64_t split = off;
@@ -487,16 +469,19 @@ int subflow_join_table(nfagg_handle* h) {
     TableView& J = h->jv;
     if (J.ctr) return NFAGG_OK;
     const uint64_t slots = h->slots;
-    if (!J.hot) HIP_TRY(h, hipMalloc((void**)&J.hot, slots * sizeof(SlotHot)));
-    if (!J.cold) HIP_TRY(h, hipMalloc((void**)&J.cold, slots * sizeof(SlotCold)));
-    if (!J.aux) HIP_TRY(h, hipMalloc((void**)&J.aux, slots * sizeof(SlotAux)));
-    if (!J.live_list) HIP_TRY(h, hipMalloc((void**)&J.live_list, slots * sizeof(uint32_t)));
-    if (!h->h_jctr) HIP_TRY(h, hipHostMalloc((void**)&h->h_jctr, sizeof(DevCounters), hipHostMallocDefault));
-    DevCounters* c = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&c, sizeof(DevCounters)));
+    TableMem& M = h->jtable;                                    // (a call that failed half way leaves what it allocated, the next one completes it)
+    if (!M.hot) HIP_TRY(h, M.hot.alloc(slots * sizeof(SlotHot)));
+    if (!M.cold) HIP_TRY(h, M.cold.alloc(slots * sizeof(SlotCold)));
+    if (!M.aux) HIP_TRY(h, M.aux.alloc(slots * sizeof(SlotAux)));
+    if (!M.live_list) HIP_TRY(h, M.live_list.alloc(slots * sizeof(uint32_t)));
+    if (!h->jctr_mirror) HIP_TRY(h, h->jctr_mirror.alloc(sizeof(DevCounters)));
+    h->h_jctr = h->jctr_mirror.as<DevCounters>();
+    J.hot = M.hot.as<SlotHot>(); J.cold = M.cold.as<SlotCold>(); J.aux = M.aux.as<SlotAux>(); J.live_list = M.live_list.as<uint32_t>();
+    HIP_TRY(h, M.ctr.alloc(sizeof(DevCounters)));
+    DevCounters* c = M.ctr.as<DevCounters>();
     hipError_t e = hipMemsetAsync(c, 0, sizeof(DevCounters), h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(J.hot, 0, slots * sizeof(SlotHot), h->stream);       // the tags: every slot free
-    if (e != hipSuccess) { hipFree(c); return fail(h, NFAGG_EDEVICE, "join table: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { M.ctr.reset(); return fail(h, NFAGG_EDEVICE, "join table: %s", hipGetErrorString(e)); }
     J.mask = slots - 1; J.claim_limit = h->tv.claim_limit; J.epoch_bits = 1ull << 48;
     J.n_shards = 1; J.shard_id = 0; J.defer_claims = 0; J.subflow = 0;
     J.ctr = c;                                                  // last: marks the table as complete
@@ -533,10 +518,10 @@ int subflow_join(nfagg_handle* h, uint32_t n_shards, uint32_t shard_id) {
     if (h->h_ctr->aborted) return fail(h, NFAGG_EDEVICE, "table too small for the flows this shard owns (claims refused while merging)");
     const uint64_t claimed = h->h_ctr->n_live;
     if ((rc = subflow_join_table(h)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_join, &h->d_join_cap, (size_t)claimed * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = h->d_join.ensure(h, (size_t)claimed * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
     const uint64_t seq_limit = h->must_evict ? h->split_seq - h->seq_origin : ~0ull;
     h->join.dirty = true;
-    const hipError_t e = launch_subflow_join(h->tv, h->jv, claimed, seq_limit, n_shards, shard_id, (uint32_t*)h->d_join, h->stream);
+    const hipError_t e = launch_subflow_join(h->tv, h->jv, claimed, seq_limit, n_shards, shard_id, h->d_join.as<uint32_t>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "sub-flow join launch failed: %s", hipGetErrorString(e));
     HIP_TRY(h, hipMemcpyAsync(h->h_jctr, h->jv.ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -547,7 +532,7 @@ int subflow_join(nfagg_handle* h, uint32_t n_shards, uint32_t shard_id) {
     return NFAGG_OK;
 }
 
-}  // namespace
+}  // namespace nfagg
 
 // The NUMA node a device hangs off: /sys/bus/pci/devices/<domain:bus:dev.fn>/numa_node (-1: unknown / not a NUMA host).
 static int device_numa_node(int device) {
@@ -570,7 +555,7 @@ static void host_pool_for_device(int device) {
     std::call_once(once, [device] { (void)HostPool::get().configure(0, device_numa_node(device), /*explicit_call=*/false); });
 }
 
-extern "C" {
+// ---- the C ABI (declared extern "C" in include/nfagg.h)
 
 uint32_t nfagg_abi_version(void) { return NFAGG_ABI_VERSION; }
 
@@ -635,21 +620,25 @@ int nfagg_create(const nfagg_config* cfg_in, nfagg_handle** out) {
     } while (0)
     CREATE_TRY(hipSetDevice(h->device));
     host_pool_for_device(h->device);            // the copy workers: created with the first handle, next to its GPU (nfagg_hostpool.h)
-    CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    CREATE_TRY(hipMalloc((void**)&h->tv.hot, slots * sizeof(SlotHot)));
-    CREATE_TRY(hipMalloc((void**)&h->tv.cold, slots * sizeof(SlotCold)));
+    CREATE_TRY(h->stream.create());
+    CREATE_TRY(h->table.hot.alloc(slots * sizeof(SlotHot)));
+    CREATE_TRY(h->table.cold.alloc(slots * sizeof(SlotCold)));
     // the live list can transiently hold bogus claims of the careful path: size it by slots
-    CREATE_TRY(hipMalloc((void**)&h->tv.live_list, slots * sizeof(uint32_t)));
-    CREATE_TRY(hipMalloc((void**)&h->tv.ctr, sizeof(DevCounters)));
+    CREATE_TRY(h->table.live_list.alloc(slots * sizeof(uint32_t)));
+    CREATE_TRY(h->table.ctr.alloc(sizeof(DevCounters)));
+    h->tv.hot = h->table.hot.as<SlotHot>(); h->tv.cold = h->table.cold.as<SlotCold>();
+    h->tv.live_list = h->table.live_list.as<uint32_t>(); h->tv.ctr = h->table.ctr.as<DevCounters>();
     CREATE_TRY(hipMemsetAsync(h->tv.hot, 0, slots * sizeof(SlotHot), h->stream));
     CREATE_TRY(hipMemsetAsync(h->tv.cold, 0, slots * sizeof(SlotCold), h->stream));
     if (cfg.mode == NFAGG_MODE_KERNEL_DEDUP) {
-        CREATE_TRY(hipMalloc((void**)&h->tv.aux, slots * sizeof(SlotAux)));
+        CREATE_TRY(h->table.aux.alloc(slots * sizeof(SlotAux)));
+        h->tv.aux = h->table.aux.as<SlotAux>();
         CREATE_TRY(hipMemsetAsync(h->tv.aux, 0, slots * sizeof(SlotAux), h->stream));
     }
     CREATE_TRY(hipMemsetAsync(h->tv.ctr, 0, sizeof(DevCounters), h->stream));
-    CREATE_TRY(hipHostMalloc((void**)&h->h_ctr, sizeof(DevCounters), hipHostMallocDefault));
-    CREATE_TRY(hipHostMalloc((void**)&h->h_careful, kCarefulCountsBytes + kCarefulMaxBatch, hipHostMallocDefault));
+    CREATE_TRY(h->ctr_mirror.alloc(sizeof(DevCounters)));
+    CREATE_TRY(h->careful_mirror.alloc(kCarefulCountsBytes + kCarefulMaxBatch));
+    h->h_ctr = h->ctr_mirror.as<DevCounters>(); h->h_careful = h->careful_mirror.as<uint8_t>();
     h->tv.mask = slots - 1; h->tv.n_shards = cfg.n_shards; h->tv.shard_id = cfg.shard_id;
     // a local-fold rank in kernel-dedup mode keys its table by (flow, interface): nfagg_dedup.h, include/nfagg.h (local_fold)
     h->tv.subflow = (cfg.mode == NFAGG_MODE_KERNEL_DEDUP && cfg.local_fold) ? 1u : 0u;
@@ -661,12 +650,12 @@ int nfagg_create(const nfagg_config* cfg_in, nfagg_handle** out) {
     // careful path: never let claimed slots exceed 3/4 of the table
     h->careful_chunk = slots / 4;
     if (h->careful_chunk > (1ull << 22)) h->careful_chunk = 1ull << 22;
-    CREATE_TRY(hipMalloc((void**)&h->d_slot_idx, h->careful_chunk * sizeof(uint32_t)));
-    CREATE_TRY(hipMalloc((void**)&h->d_flags, h->careful_chunk));
-    CREATE_TRY(hipMalloc((void**)&h->d_block_counts, ((h->careful_chunk + kFlagBlock - 1) / kFlagBlock) * sizeof(uint32_t)));
-    for (int b = 0; b < 2; b++) CREATE_TRY(hipEventCreateWithFlags(&h->stage_free[b], hipEventDisableTiming));
-    for (int b = 0; b < 2; b++) CREATE_TRY(hipEventCreateWithFlags(&h->stage_up[b], hipEventDisableTiming));
-    CREATE_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    CREATE_TRY(h->d_slot_idx.alloc(h->careful_chunk * sizeof(uint32_t)));
+    CREATE_TRY(h->d_flags.alloc(h->careful_chunk));
+    CREATE_TRY(h->d_block_counts.alloc(((h->careful_chunk + kFlagBlock - 1) / kFlagBlock) * sizeof(uint32_t)));
+    for (int b = 0; b < 2; b++) CREATE_TRY(h->stage_free[b].create());
+    for (int b = 0; b < 2; b++) CREATE_TRY(h->stage_up[b].create());
+    CREATE_TRY(h->copy_stream.create());
     // sketches
     h->sk.cm_depth = cfg.cm_depth; h->sk.cm_log2w = cfg.cm_log2_width; h->sk.hll_p = cfg.hll_p;
     h->sk.flags = cfg.sketch_flags & (NFAGG_SKETCH_CM | NFAGG_SKETCH_HLL);
@@ -674,18 +663,19 @@ int nfagg_create(const nfagg_config* cfg_in, nfagg_handle** out) {
         const size_t bytes = ((size_t)cfg.cm_depth << cfg.cm_log2_width) * sizeof(uint64_t);
         for (int k = 0; k < 2; k++) {
             if (cfg.ext_sketch[k]) h->sk.cm[k] = (uint64_t*)cfg.ext_sketch[k];
-            else { CREATE_TRY(hipMalloc((void**)&h->sk.cm[k], bytes)); h->own_sketch[k] = true; CREATE_TRY(hipMemsetAsync(h->sk.cm[k], 0, bytes, h->stream)); }
+            else { CREATE_TRY(h->sketch[k].alloc(bytes)); h->sk.cm[k] = h->sketch[k].as<uint64_t>(); CREATE_TRY(hipMemsetAsync(h->sk.cm[k], 0, bytes, h->stream)); }
         }
     }
     if (h->sk.flags & NFAGG_SKETCH_HLL) {
         const size_t bytes = ((size_t)1 << cfg.hll_p);              // uint8_t registers (hll_p >= 4: a multiple of 4 bytes)
         for (int k = 0; k < 2; k++) {
             if (cfg.ext_sketch[2 + k]) h->sk.hll[k] = (uint8_t*)cfg.ext_sketch[2 + k];
-            else { CREATE_TRY(hipMalloc((void**)&h->sk.hll[k], bytes)); h->own_sketch[2 + k] = true; CREATE_TRY(hipMemsetAsync(h->sk.hll[k], 0, bytes, h->stream)); }
+            else { CREATE_TRY(h->sketch[2 + k].alloc(bytes)); h->sk.hll[k] = h->sketch[2 + k].as<uint8_t>(); CREATE_TRY(hipMemsetAsync(h->sk.hll[k], 0, bytes, h->stream)); }
         }
     }
-    CREATE_TRY(hipMalloc((void**)&h->d_hist, 65 * sizeof(uint32_t)));
-    CREATE_TRY(hipMalloc((void**)&h->tv.spill.qtail, (kSpillParts + 1) * sizeof(uint32_t)));
+    CREATE_TRY(h->d_hist.alloc(65 * sizeof(uint32_t)));
+    CREATE_TRY(h->qtail.alloc((kSpillParts + 1) * sizeof(uint32_t)));
+    h->tv.spill.qtail = h->qtail.as<uint32_t>();
     CREATE_TRY(hipMemsetAsync(h->tv.spill.qtail, 0, (kSpillParts + 1) * sizeof(uint32_t), h->stream));
     h->tv.spill.ovf_tail = h->tv.spill.qtail + kSpillParts;
     h->tv.spill.error = &h->tv.ctr->error;
@@ -706,66 +696,12 @@ int nfagg_create(const nfagg_config* cfg_in, nfagg_handle** out) {
     return NFAGG_OK;
 }
 
+// Everything the handle holds is an owner (nfagg_handle.h): deleting it frees it.
 void nfagg_destroy(nfagg_handle* h) {
     if (!h) return;
     hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
+    for (const Stream* s : {&h->stream, &h->copy_stream, &h->d2h_stream, &h->d2h_small, &h->par.stream}) if (*s) hipStreamSynchronize(*s);
     prof_resolve(h);
-    for (auto& ep : h->ev_free) { hipEventDestroy(ep.a); hipEventDestroy(ep.b); }
-    for (int b = 0; b < 2; b++) {
-        if (h->pinned[b]) hipHostFree(h->pinned[b]);
-        if (h->d_stage[b]) hipFree(h->d_stage[b]);
-        if (h->stage_free[b]) hipEventDestroy(h->stage_free[b]);
-        if (h->stage_up[b]) hipEventDestroy(h->stage_up[b]);
-    }
-    if (h->copy_stream) hipStreamDestroy(h->copy_stream);
-    for (int k = 0; k < 2; k++) {
-        if (h->own_sketch[k] && h->sk.cm[k]) hipFree(h->sk.cm[k]);
-        if (h->own_sketch[2 + k] && h->sk.hll[k]) hipFree(h->sk.hll[k]);
-    }
-    for (int k = 0; k < 3; k++) if (h->d_roll[k]) hipFree(h->d_roll[k]);
-    if (h->d_hist) hipFree(h->d_hist);
-    if (h->d_spill) hipFree(h->d_spill);
-    if (h->tv.spill.xp) hipFree(h->tv.spill.xp);
-    for (int k = 0; k < 4; k++) if (h->d_opt[k]) hipFree(h->d_opt[k]);
-    h->enc.each([](nfagg_handle::DevBuf& b) { if (b.p) hipFree(b.p); });
-    for (int k = 0; k < 2; k++) if (h->d_sort[k]) hipFree(h->d_sort[k]);
-    for (int k = 0; k < 7; k++) if (h->d_hh[k]) hipFree(h->d_hh[k]);
-    for (int k = 0; k < 28; k++) if (h->d_mm[k]) hipFree(h->d_mm[k]);
-    if (h->tv.spill.qtail) hipFree(h->tv.spill.qtail);
-    if (h->d_evict) hipFree(h->d_evict);
-    if (h->d_slot_idx) hipFree(h->d_slot_idx);
-    if (h->d_flags) hipFree(h->d_flags);
-    if (h->d_block_counts) hipFree(h->d_block_counts);
-    if (h->tv.hot) hipFree(h->tv.hot);
-    if (h->tv.cold) hipFree(h->tv.cold);
-    if (h->tv.aux) hipFree(h->tv.aux);
-    if (h->tv.live_list) hipFree(h->tv.live_list);
-    if (h->tv.ctr) hipFree(h->tv.ctr);
-    if (h->h_par) hipHostFree(h->h_par);
-    for (int k = 0; k < 8; k++) if (h->d_par[k]) hipFree(h->d_par[k]);
-    if (h->par_done) hipEventDestroy(h->par_done);
-    for (int k = 0; k < 16; k++) if (h->par_part[k]) hipEventDestroy(h->par_part[k]);
-    if (h->par_stream) hipStreamDestroy(h->par_stream);
-    if (h->jv.hot) hipFree(h->jv.hot);
-    if (h->jv.cold) hipFree(h->jv.cold);
-    if (h->jv.aux) hipFree(h->jv.aux);
-    if (h->jv.live_list) hipFree(h->jv.live_list);
-    if (h->jv.ctr) hipFree(h->jv.ctr);
-    if (h->h_jctr) hipHostFree(h->h_jctr);
-    if (h->d_join) hipFree(h->d_join);
-    if (h->h_ctr) hipHostFree(h->h_ctr);
-    if (h->h_careful) hipHostFree(h->h_careful);
-    if (h->h_exp) hipHostFree(h->h_exp);
-    if (h->d_exp) hipFree(h->d_exp);
-    for (int b = 0; b < 2; b++) { if (h->h_bounce[b]) hipHostFree(h->h_bounce[b]); if (h->bounce_ev[b]) hipEventDestroy(h->bounce_ev[b]); }
-    if (h->d2h_stream) hipStreamDestroy(h->d2h_stream);
-    if (h->d2h_small) hipStreamDestroy(h->d2h_small);
-    for (int k = 0; k < 3; k++) if (h->ep_graph[k]) hipGraphExecDestroy(h->ep_graph[k]);
-    if (h->h_ep) hipHostFree(h->h_ep);
-    if (h->d_ep_out) hipFree(h->d_ep_out);
-    for (int k = 0; k < 3; k++) if (h->d_ep[k]) hipFree(h->d_ep[k]);
-    if (h->stream) hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -776,12 +712,12 @@ int nfagg_ingest_device(nfagg_handle* h, const void* d_records, size_t n, size_t
     return ingest_device_core(h, d_records, n, consumed);
 }
 
-static int staging_alloc(nfagg_handle* h) {
-    if (h->pinned[0]) return NFAGG_OK;
+int nfagg::staging_alloc(nfagg_handle* h) {
+    if (h->d_stage[1]) return NFAGG_OK;
     const size_t bytes = (size_t)h->cfg.staging_records * kRecordBytes;
     for (int b = 0; b < 2; b++) {
-        HIP_TRY(h, hipHostMalloc(&h->pinned[b], bytes, hipHostMallocDefault));
-        HIP_TRY(h, hipMalloc(&h->d_stage[b], bytes));
+        HIP_TRY(h, h->pinned[b].alloc(bytes));
+        HIP_TRY(h, h->d_stage[b].alloc(bytes));
     }
     return NFAGG_OK;
 }
@@ -790,7 +726,7 @@ static int staging_alloc(nfagg_handle* h) {
 // link the pinned buffer feeds (~57 GB/s), so large copies are cut into parts for the process's copy workers (nfagg_hostpool.h:
 // bound to the GPU's NUMA node, non-temporal stores). threads: cfg.copy_threads — 0 = the number of parts the workers' calibration
 // found best on this host, 1 = inline.
-static void staged_copy(void* dst, const void* src, size_t bytes, unsigned threads) {
+void nfagg::staged_copy(void* dst, const void* src, size_t bytes, unsigned threads) {
     if (threads == 1) { memcpy(dst, src, bytes); return; }
     HostPool::get().copy(dst, src, bytes, threads);
 }
@@ -800,7 +736,7 @@ static void staged_copy(void* dst, const void* src, size_t bytes, unsigned threa
 // out of its bounce buffer by cfg.copy_threads threads — the mirror image of the H2D staging ring.
 // Is p page-locked host memory the device can read or write directly (nfagg_host_alloc, hipHostMalloc, hipHostRegister)? Such
 // a buffer needs no trip through the library's own pinned buffers: the DMA engine takes it as it is.
-static bool host_is_pinned(const void* p) {
+bool nfagg::host_is_pinned(const void* p) {
     if (!p) return false;
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // plain malloc memory: "invalid value"
@@ -808,7 +744,7 @@ static bool host_is_pinned(const void* p) {
 }
 
 constexpr size_t kBounceBytes = 16u << 20;
-static int d2h_copy(nfagg_handle* h, void* dst, const void* d_src, size_t bytes) {
+int nfagg::d2h_copy(nfagg_handle* h, void* dst, const void* d_src, size_t bytes) {
     if (bytes == 0) return NFAGG_OK;
     if (bytes < (4u << 20) || host_is_pinned(dst)) {
         // NOT a blocking hipMemcpy: that one runs on the legacy stream, and nfagg_account calls this from a helper thread while the
@@ -816,27 +752,27 @@ static int d2h_copy(nfagg_handle* h, void* dst, const void* d_src, size_t bytes)
         // ("operation failed due to a previous error during capture", once in ~240 soak streams: profiles/r05_soak_account.txt).
         // On a stream of ITS OWN: a copy into pageable memory on d2h_stream left that stream's later page-locked downloads at
         // a third of the link (nfagg_account from page-locked buffers 22.0 -> 28.0 ms, same box: profiles/r05_account_host_pipeline.txt)
-        if (!h->d2h_small) HIP_TRY(h, hipStreamCreateWithFlags(&h->d2h_small, hipStreamNonBlocking));
+        if (!h->d2h_small) HIP_TRY(h, h->d2h_small.create());
         HIP_TRY(h, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, h->d2h_small));
         HIP_TRY(h, hipStreamSynchronize(h->d2h_small));
         return NFAGG_OK;
     }
-    if (!h->d2h_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->d2h_stream, hipStreamNonBlocking));
+    if (!h->d2h_stream) HIP_TRY(h, h->d2h_stream.create());
     for (int b = 0; b < 2; b++) {                                // created on first use; a failure part-way is picked up by the next call
-        if (!h->h_bounce[b]) HIP_TRY(h, hipHostMalloc(&h->h_bounce[b], kBounceBytes, hipHostMallocDefault));
-        if (!h->bounce_ev[b]) HIP_TRY(h, hipEventCreateWithFlags(&h->bounce_ev[b], hipEventDisableTiming));
+        if (!h->h_bounce[b]) HIP_TRY(h, h->h_bounce[b].alloc(kBounceBytes));
+        if (!h->bounce_ev[b]) HIP_TRY(h, h->bounce_ev[b].create());
     }
     const size_t n_chunks = (bytes + kBounceBytes - 1) / kBounceBytes;
     for (size_t k = 0; k <= n_chunks; k++) {
         if (k < n_chunks) {
             const size_t off = k * kBounceBytes, len = bytes - off < kBounceBytes ? bytes - off : kBounceBytes;
-            HIP_TRY(h, hipMemcpyAsync(h->h_bounce[k & 1], (const char*)d_src + off, len, hipMemcpyDeviceToHost, h->d2h_stream));
+            HIP_TRY(h, hipMemcpyAsync(h->h_bounce[k & 1].p, (const char*)d_src + off, len, hipMemcpyDeviceToHost, h->d2h_stream));
             HIP_TRY(h, hipEventRecord(h->bounce_ev[k & 1], h->d2h_stream));
         }
         if (k > 0) {
             const size_t off = (k - 1) * kBounceBytes, len = bytes - off < kBounceBytes ? bytes - off : kBounceBytes;
             HIP_TRY(h, hipEventSynchronize(h->bounce_ev[(k - 1) & 1]));
-            staged_copy((char*)dst + off, h->h_bounce[(k - 1) & 1], len, h->cfg.copy_threads);
+            staged_copy((char*)dst + off, h->h_bounce[(k - 1) & 1].p, len, h->cfg.copy_threads);
         }
     }
     return NFAGG_OK;
@@ -846,7 +782,7 @@ static int d2h_copy(nfagg_handle* h, void* dst, const void* d_src, size_t bytes)
 // default is 5000, config.go:146) consumes one epoch per call — about epoch_len_hint records — and what was staged beyond that
 // is staged again by the next call: copy what is left of the epoch and a quarter more (a longer epoch simply takes another
 // chunk), not a whole staging buffer. Measured at max_entries 5000: 3.6 -> 36 M records/s through nfagg_ingest / nfagg_evict.
-static size_t stage_chunk(const nfagg_handle* h, size_t remaining, size_t cap) {
+size_t nfagg::stage_chunk(const nfagg_handle* h, size_t remaining, size_t cap) {
     size_t m = remaining < cap ? remaining : cap;
     if (h->epoch_len_hint) {
         const uint64_t reach = h->epoch_len_hint + h->epoch_len_hint / 4;
@@ -886,11 +822,11 @@ int nfagg_ingest(nfagg_handle* h, const void* records, size_t n, size_t* consume
                 const int b = h->stage_next;
                 HIP_TRY(h, hipEventSynchronize(h->stage_free[b]));
                 const void* up = src + off * kRecordBytes;
-                if (!pinned_src) { staged_copy(h->pinned[b], up, m * kRecordBytes, h->cfg.copy_threads); up = h->pinned[b]; }
-                HIP_TRY(h, hipMemcpyAsync(h->d_stage[b], up, m * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
+                if (!pinned_src) { staged_copy(h->pinned[b].p, up, m * kRecordBytes, h->cfg.copy_threads); up = h->pinned[b].p; }
+                HIP_TRY(h, hipMemcpyAsync(h->d_stage[b].p, up, m * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
                 HIP_TRY(h, hipEventRecord(h->stage_up[b], h->copy_stream));
                 HIP_TRY(h, hipStreamWaitEvent(h->stream, h->stage_up[b], 0));
-                rc = launch_ingest_profiled(h, h->d_stage[b], m, st.seq0 + off);
+                rc = launch_ingest_profiled(h, h->d_stage[b].p, m, st.seq0 + off);
                 HIP_TRY(h, hipEventRecord(h->stage_free[b], h->stream));
                 h->stage_next ^= 1;
                 off += m;
@@ -915,13 +851,13 @@ int nfagg_ingest(nfagg_handle* h, const void* records, size_t n, size_t* consume
         const int b = h->stage_next;
         HIP_TRY(h, hipEventSynchronize(h->stage_free[b]));
         const void* up = src + consumed * kRecordBytes;
-        if (!pinned_src) { staged_copy(h->pinned[b], up, m * kRecordBytes, h->cfg.copy_threads); up = h->pinned[b]; }
+        if (!pinned_src) { staged_copy(h->pinned[b].p, up, m * kRecordBytes, h->cfg.copy_threads); up = h->pinned[b].p; }
         // the copy runs on its own stream: the fold of the previous chunk (other buffer) is still busy on h->stream
-        HIP_TRY(h, hipMemcpyAsync(h->d_stage[b], up, m * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
+        HIP_TRY(h, hipMemcpyAsync(h->d_stage[b].p, up, m * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
         HIP_TRY(h, hipEventRecord(h->stage_up[b], h->copy_stream));
         HIP_TRY(h, hipStreamWaitEvent(h->stream, h->stage_up[b], 0));
         size_t c = 0;
-        rc = ingest_device_core(h, h->d_stage[b], m, &c);
+        rc = ingest_device_core(h, h->d_stage[b].p, m, &c);
         HIP_TRY(h, hipEventRecord(h->stage_free[b], h->stream));
         h->stage_next ^= 1;
         consumed += c;
@@ -940,7 +876,7 @@ int nfagg_staging_acquire(nfagg_handle* h, void** buf, size_t* capacity_records)
     if (rc != NFAGG_OK) return rc;
     const int b = h->stage_next;
     HIP_TRY(h, hipEventSynchronize(h->stage_free[b]));
-    *buf = h->pinned[b];
+    *buf = h->pinned[b].p;
     if (capacity_records) *capacity_records = (size_t)h->cfg.staging_records;
     h->stage_acquired = true;
     return NFAGG_OK;
@@ -953,10 +889,10 @@ int nfagg_staging_commit(nfagg_handle* h, size_t n, size_t* consumed) {
     HIP_TRY(h, hipSetDevice(h->device));
     const int b = h->stage_next;
     h->stage_acquired = false;
-    HIP_TRY(h, hipMemcpyAsync(h->d_stage[b], h->pinned[b], n * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_stage[b].p, h->pinned[b].p, n * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
     HIP_TRY(h, hipEventRecord(h->stage_up[b], h->copy_stream));
     HIP_TRY(h, hipStreamWaitEvent(h->stream, h->stage_up[b], 0));
-    int rc = ingest_device_core(h, h->d_stage[b], n, consumed);
+    int rc = ingest_device_core(h, h->d_stage[b].p, n, consumed);
     HIP_TRY(h, hipEventRecord(h->stage_free[b], h->stream));
     h->stage_next ^= 1;
     return rc;
@@ -1010,11 +946,8 @@ static int subflow_evict(nfagg_handle* h, int reason, uint32_t n_shards, uint32_
     if (flows && !out) return fail(h, NFAGG_EINVAL, "null output buffer");
     void* d_out = out;
     if (!out_is_device) {
-        size_t capb = (size_t)h->d_evict_cap;
-        rc = ensure_bytes(h, &h->d_evict, &capb, (size_t)flows * kRecordBytes + 16);
-        h->d_evict_cap = capb;
-        if (rc != NFAGG_OK) return rc;
-        d_out = h->d_evict;
+        if ((rc = h->d_evict.ensure(h, (size_t)flows * kRecordBytes + 16)) != NFAGG_OK) return rc;
+        d_out = h->d_evict.p;
     }
     HIP_TRY(h, hipMemsetAsync(&h->jv.ctr->n_out, 0, sizeof(unsigned long long), h->stream));
     EventPair ep{};
@@ -1025,7 +958,7 @@ static int subflow_evict(nfagg_handle* h, int reason, uint32_t n_shards, uint32_
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "evict launch failed: %s", hipGetErrorString(e));
     HIP_TRY(h, hipMemcpyAsync(h->h_jctr, h->jv.ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!out_is_device && flows && (rc = d2h_copy(h, out, h->d_evict, (size_t)flows * kRecordBytes)) != NFAGG_OK) return rc;
+    if (!out_is_device && flows && (rc = d2h_copy(h, out, h->d_evict.p, (size_t)flows * kRecordBytes)) != NFAGG_OK) return rc;
     h->mirror_fresh = false;
     if (h->h_jctr->error) return fail(h, NFAGG_EDEVICE, "sub-flow join table kernel bailed out (code %u)", h->h_jctr->error);
     if (h->h_jctr->n_out != flows)
@@ -1035,7 +968,7 @@ static int subflow_evict(nfagg_handle* h, int reason, uint32_t n_shards, uint32_
     return finish_epoch(h, reason, flows);
 }
 
-static int evict_core(nfagg_handle* h, int reason, void* out, bool out_is_device, size_t cap, size_t* n_out) {
+int nfagg::evict_core(nfagg_handle* h, int reason, void* out, bool out_is_device, size_t cap, size_t* n_out) {
     if (!h || !n_out || reason < 0 || reason > 2) return fail(h, NFAGG_EINVAL, "bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = NFAGG_OK;
@@ -1050,11 +983,8 @@ static int evict_core(nfagg_handle* h, int reason, void* out, bool out_is_device
     if (reason == NFAGG_REASON_TIMEOUT && legit == 0 && claimed == 0) return NFAGG_OK;  // account.go:64-66
     void* d_out = out;
     if (!out_is_device) {
-        size_t capb = (size_t)h->d_evict_cap;
-        rc = ensure_bytes(h, &h->d_evict, &capb, (size_t)legit * kRecordBytes + 16);
-        h->d_evict_cap = capb;
-        if (rc != NFAGG_OK) return rc;
-        d_out = h->d_evict;
+        if ((rc = h->d_evict.ensure(h, (size_t)legit * kRecordBytes + 16)) != NFAGG_OK) return rc;
+        d_out = h->d_evict.p;
     }
     HIP_TRY(h, hipMemsetAsync(&h->tv.ctr->n_out, 0, sizeof(unsigned long long), h->stream));
     // large table: visit the claimed slots in address order (see launch_sort_slots)
@@ -1070,15 +1000,15 @@ static int evict_core(nfagg_handle* h, int reason, void* out, bool out_is_device
         h->sort_bits = bits;
         hipError_t es = launch_sort_slots(h->tv.live_list, nullptr, claimed, bits, nullptr, &temp_bytes, h->stream);
         if (es != hipSuccess) return fail(h, NFAGG_EDEVICE, "sort size query failed: %s", hipGetErrorString(es));
-        if ((rc = ensure_bytes(h, &h->d_sort[0], &h->d_sort_cap[0], claimed * sizeof(uint32_t))) != NFAGG_OK) return rc;
-        if ((rc = ensure_bytes(h, &h->d_sort[1], &h->d_sort_cap[1], temp_bytes + 16)) != NFAGG_OK) return rc;
+        if ((rc = h->sort_live.ensure(h, claimed * sizeof(uint32_t))) != NFAGG_OK) return rc;
+        if ((rc = h->sort_tmp.ensure(h, temp_bytes + 16)) != NFAGG_OK) return rc;
     }
     EventPair ep{};
     if (h->cfg.profile) prof_begin(h, ep, 1);
     if (sort_slots) {
-        hipError_t es = launch_sort_slots(h->tv.live_list, (uint32_t*)h->d_sort[0], claimed, h->sort_bits, h->d_sort[1], &temp_bytes, h->stream);
+        hipError_t es = launch_sort_slots(h->tv.live_list, h->sort_live.as<uint32_t>(), claimed, h->sort_bits, h->sort_tmp.p, &temp_bytes, h->stream);
         if (es != hipSuccess) return fail(h, NFAGG_EDEVICE, "slot sort failed: %s", hipGetErrorString(es));
-        tv.live_list = (uint32_t*)h->d_sort[0];
+        tv.live_list = h->sort_live.as<uint32_t>();
     }
     hipError_t e = launch_evict(tv, claimed, h->must_evict ? h->split_seq - h->seq_origin : ~0ull, d_out, h->stream);
     if (h->cfg.profile) prof_end(h, ep);
@@ -1086,7 +1016,7 @@ static int evict_core(nfagg_handle* h, int reason, void* out, bool out_is_device
     // counters and (host variant) the records come back in stream order behind the kernel: one wait for both
     HIP_TRY(h, hipMemcpyAsync(h->h_ctr, h->tv.ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (!out_is_device && legit && (rc = d2h_copy(h, out, h->d_evict, (size_t)legit * kRecordBytes)) != NFAGG_OK) return rc;
+    if (!out_is_device && legit && (rc = d2h_copy(h, out, h->d_evict.p, (size_t)legit * kRecordBytes)) != NFAGG_OK) return rc;
     h->mirror_fresh = true;
     if (h->h_ctr->error)
         return fail(h, NFAGG_EDEVICE, "flow table kernel bailed out (code %u: 1 = probe overflow / table too small, 2 = claim spin limit, 5 = spill overflow list full, 6 = claimed slot without a record, 7 = partial of another shard merged)", h->h_ctr->error);
@@ -1108,18 +1038,19 @@ int nfagg_evict_device(nfagg_handle* h, int reason, void* d_out, size_t cap, siz
 }
 
 // ---------------------------------------------------------------- local fold across GPUs: partials (nfagg_combine.hip)
-// The three steps of the local-fold tick as handle calls. The one-process group (nfagg_group.inc) and one-process-per-GPU
+// The three steps of the local-fold tick as handle calls. The one-process group (nfagg_api_group.hip) and one-process-per-GPU
 // ranks (bench.py --gpus N: exchange with an RCCL all-to-all) run the same code.
 static int partials_scratch(nfagg_handle* h) {
-    int rc = ensure_bytes(h, &h->d_exp, &h->d_exp_cap, 136 * sizeof(unsigned long long));
+    int rc = h->d_exp.ensure(h, 136 * sizeof(unsigned long long));
     if (rc != NFAGG_OK) return rc;
-    if (!h->h_exp) HIP_TRY(h, hipHostMalloc((void**)&h->h_exp, 136 * sizeof(unsigned long long), hipHostMallocDefault));
+    if (!h->exp_mirror) HIP_TRY(h, h->exp_mirror.alloc(136 * sizeof(unsigned long long)));
+    h->h_exp = h->exp_mirror.as<unsigned long long>();
     return NFAGG_OK;
 }
 
 // counts[o] (host, n_shards words) = flows of segment o; *n_out = their sum. NFAGG_TRUNCATED (nothing written, state unchanged)
 // when cap is too small. The partials are complete in d_out when the call returns.
-static int partials_export_core(nfagg_handle* h, uint32_t n_shards, uint32_t self_shard, void* d_out, size_t cap, uint64_t* counts,
+int nfagg::partials_export_core(nfagg_handle* h, uint32_t n_shards, uint32_t self_shard, void* d_out, size_t cap, uint64_t* counts,
                                 size_t* n_out) {
     if (!h || !counts || !n_out) return fail(h, NFAGG_EINVAL, "null argument");
     if (n_shards == 0 || n_shards > 64) return fail(h, NFAGG_EINVAL, "n_shards must be in [1, 64]");
@@ -1133,7 +1064,7 @@ static int partials_export_core(nfagg_handle* h, uint32_t n_shards, uint32_t sel
     if ((rc = refresh_counters(h)) != NFAGG_OK) return rc;
     const uint64_t claimed = h->h_ctr->n_live;
     const uint64_t seq_limit = h->must_evict ? h->split_seq - h->seq_origin : ~0ull;
-    unsigned long long* d_counts = (unsigned long long*)h->d_exp;
+    unsigned long long* d_counts = h->d_exp.as<unsigned long long>();
     unsigned long long* d_cursor = d_counts + 64;
     hipError_t e = launch_export_count(h->tv, claimed, seq_limit, n_shards, self_shard, d_counts, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "partials count launch failed: %s", hipGetErrorString(e));
@@ -1155,7 +1086,7 @@ static int partials_export_core(nfagg_handle* h, uint32_t n_shards, uint32_t sel
 }
 
 // Asynchronous (the handle's stream); d_partials must stay valid until the handle synchronises.
-static int partials_merge_core(nfagg_handle* h, uint32_t n_shards, uint32_t shard_id, const void* d_partials, size_t n) {
+int nfagg::partials_merge_core(nfagg_handle* h, uint32_t n_shards, uint32_t shard_id, const void* d_partials, size_t n) {
     if (!h || (n && !d_partials)) return fail(h, NFAGG_EINVAL, "null argument");
     if (n_shards == 0 || n_shards > 64 || shard_id >= n_shards) return fail(h, NFAGG_EINVAL, "bad shard (n_shards in [1, 64], shard_id < n_shards)");
     if (h->cfg.mode != NFAGG_MODE_ACCOUNTER && !h->tv.subflow) return fail(h, NFAGG_EINVAL, "partials need NFAGG_MODE_ACCOUNTER or nfagg_config.local_fold");
@@ -1174,7 +1105,7 @@ static int partials_merge_core(nfagg_handle* h, uint32_t n_shards, uint32_t shar
 
 // *owned = flows of this table that (n_shards, shard_id) owns — what evict_owned_core will write. Synchronises; reports
 // claims refused by a merge.
-static int owned_count_core(nfagg_handle* h, uint32_t n_shards, uint32_t shard_id, uint64_t* owned, uint64_t* claimed_out) {
+int nfagg::owned_count_core(nfagg_handle* h, uint32_t n_shards, uint32_t shard_id, uint64_t* owned, uint64_t* claimed_out) {
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
     if (h->tv.subflow) {                                         // flows, not sub-flows: known after the join (kept for the eviction)
@@ -1190,7 +1121,7 @@ static int owned_count_core(nfagg_handle* h, uint32_t n_shards, uint32_t shard_i
     const uint64_t claimed = h->h_ctr->n_live;
     TableView tv = h->tv;
     tv.n_shards = n_shards; tv.shard_id = shard_id;
-    unsigned long long* d_owned = (unsigned long long*)h->d_exp + 128;
+    unsigned long long* d_owned = h->d_exp.as<unsigned long long>() + 128;
     const hipError_t e = launch_count_owned(tv, claimed, h->must_evict ? h->split_seq - h->seq_origin : ~0ull, d_owned, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "owned count launch failed: %s", hipGetErrorString(e));
     HIP_TRY(h, hipMemcpyAsync(h->h_exp + 128, d_owned, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
@@ -1200,7 +1131,7 @@ static int owned_count_core(nfagg_handle* h, uint32_t n_shards, uint32_t shard_i
     return NFAGG_OK;
 }
 
-static int evict_owned_core(nfagg_handle* h, int reason, uint32_t n_shards, uint32_t shard_id, void* d_out, size_t cap, size_t* n_out) {
+int nfagg::evict_owned_core(nfagg_handle* h, int reason, uint32_t n_shards, uint32_t shard_id, void* d_out, size_t cap, size_t* n_out) {
     if (!h || !n_out || reason < 0 || reason > 2) return fail(h, NFAGG_EINVAL, "bad argument");
     if (n_shards == 0 || n_shards > 64 || shard_id >= n_shards) return fail(h, NFAGG_EINVAL, "bad shard (n_shards in [1, 64], shard_id < n_shards)");
     if (h->cfg.mode != NFAGG_MODE_ACCOUNTER && !h->tv.subflow) return fail(h, NFAGG_EINVAL, "partials need NFAGG_MODE_ACCOUNTER or nfagg_config.local_fold");
@@ -1257,7 +1188,7 @@ int nfagg_set_sequence(nfagg_handle* h, uint64_t next_seq) {
 // empties itself (window_clear_core: the epoch tag, nothing is written), takes in what it owns (partials_merge_core, its own
 // segment included) and rebases the single copy it now holds (window_finish_core). No flow leaves the epoch, the sketches are
 // not touched; len(entries) of a table becomes the number of flows it owns.
-static int window_clear_core(nfagg_handle* h) {
+int nfagg::window_clear_core(nfagg_handle* h) {
     if (h->must_evict) return fail(h, NFAGG_ESTATE, "an eviction on full is pending");
     HIP_TRY(h, hipSetDevice(h->device));
     const hipError_t e = launch_reset_counters(h->tv, h->stream);
@@ -1267,7 +1198,7 @@ static int window_clear_core(nfagg_handle* h) {
     return bump_epoch(h);
 }
 
-static int window_finish_core(nfagg_handle* h, uint64_t next_seq) {
+int nfagg::window_finish_core(nfagg_handle* h, uint64_t next_seq) {
     if (next_seq < h->epoch_seq || next_seq < rebase_keep()) return fail(h, NFAGG_EINVAL, "window restart: next sequence number %llu below what the handle has reached",
                                                                          (unsigned long long)next_seq);
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1292,349 +1223,6 @@ int nfagg_window_restart_device(nfagg_handle* h, uint32_t n_shards, uint32_t sha
     if ((rc = partials_merge_core(h, n_shards, shard_id, d_partials, n)) != NFAGG_OK) return rc;
     h->ext_sequenced = true;
     return window_finish_core(h, next_seq);
-}
-
-// ---------------------------------------------------------------- nfagg_account*: the record arm WITH its evictions on "full"
-constexpr uint64_t kAccountFastMaxEntries = 32768;   // beyond that an epoch is long enough for the optimistic fold of nfagg_ingest
-
-// May the device-resident epoch loop (the kernel chain, nfagg_epoch_chain.hip) take this batch?
-static bool account_fast_ok(const nfagg_handle* h, size_t n, size_t out_cap) {
-    // (a handle that filters its input by shard takes the host-driven loop: the chain counts the records it skips per window, and a
-    // window that ends on "full" is looked at again from the split on)
-    return h->cfg.mode == NFAGG_MODE_ACCOUNTER && h->cfg.n_shards <= 1 && h->cfg.max_entries <= kAccountFastMaxEntries && !h->must_evict && !h->exported &&
-           h->cfg.max_entries + chain_window() + 16 <= h->tv.claim_limit && out_cap >= h->cfg.max_entries &&
-           h->epoch_seq - h->seq_origin + n < kSeqWindow - chain_window() && (h->tv.epoch_bits >> 48) < 0xFFFFull;
-}
-
-// One pass of the kernel chain (nfagg_epoch_chain.hip) over d[0..n). *consumed / *n_ep / *n_out: records consumed, evictions
-// performed, records written to d_out (epoch e ends at epoch_end[e] records); *stop as the control block reports it.
-// Windows are enqueued kChainWindows[k] at a time, the control block is read back after each batch of launches.
-// Windows per launch of the chain. A window takes up to chain_window() records and ends early where an epoch ends, so a call of n
-// records needs about n / chain_window() + its evictions + 1 of them; the kernels of windows beyond the call's end find `stop` set
-// and return at once — but a launch of nothing still costs ~2 us, and a shim that drains a 50-slot channel
-// (pkg/agent/agent.go:408, pkg/config/config.go:134) calls with 1 ... a few thousand records: round 5 replayed 24 windows = 96
-// launches for every call, 230 us for ONE record (profiles/r06_account_small_calls.txt). Three graphs, the shortest that covers
-// what is left is replayed.
-constexpr int kChainWindows[3] = {2, 6, 24};
-constexpr size_t kChainEndsInline = 32;                 // epoch ends that come back with the control block (more: a second copy)
-
-static int account_chain_launch(nfagg_handle* h, const void* d, size_t n, void* d_out, size_t out_cap, uint64_t* epoch_end, size_t max_epochs,
-                                size_t* consumed, size_t* n_ep, size_t* n_out, uint32_t* stop) {
-    int rc;
-    // len(entries), n_live: the host knows them after an eviction and after the last chain launch (counters_exact) — one round
-    // trip less per call; otherwise asked for
-    if (!h->counters_exact) {
-        if ((rc = refresh_counters(h)) != NFAGG_OK) return rc;
-        if (h->h_ctr->n_finalized != h->h_ctr->n_live) return fail(h, NFAGG_ESTATE, "account: unfinalized slots at the start of a batch");
-    }
-    const uint64_t n_live0 = h->live_ub;
-    const uint32_t me = max_epochs > 0xFFFFu ? 0xFFFFu : (uint32_t)max_epochs;
-    const size_t ctlb = (chain_ctl_bytes() + 63) & ~(size_t)63;
-    if ((rc = ensure_bytes(h, &h->d_ep[0], &h->d_ep_cap[0], ctlb)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_ep[1], &h->d_ep_cap[1], (size_t)(me + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_ep[2], &h->d_ep_cap[2], (size_t)(h->cfg.max_entries + chain_window() + 64) * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    const size_t hb = ctlb + (size_t)(me + 1) * sizeof(uint64_t);
-    if (h->h_ep_cap < hb) {
-        if (h->h_ep) { hipHostFree(h->h_ep); h->h_ep = nullptr; h->h_ep_cap = 0; }
-        HIP_TRY(h, hipHostMalloc(&h->h_ep, hb + 4096, hipHostMallocDefault));
-        h->h_ep_cap = hb + 4096;
-    }
-    const uint64_t seq_start = h->epoch_seq - h->seq_origin;                      // window-relative, as the slots carry it
-    chain_ctl_fill(h->h_ep, d, d_out, n, seq_start, h->live, n_live0, out_cap, h->tv.epoch_bits, h->cfg.max_entries, me);
-    HIP_TRY(h, hipMemcpyAsync(h->d_ep[0], h->h_ep, chain_ctl_bytes(), hipMemcpyHostToDevice, h->stream));
-    // kChainWindows[k] windows = 4 x that many launches whose arguments are the same in every call: captured into graphs once, one
-    // hipGraphLaunch per batch afterwards (eager launches cost the host ~8 us each here: the chain was host-bound)
-    if (!h->ep_graph_off && (!h->ep_graph[0] || h->ep_graph_key[0] != h->d_ep[0] || h->ep_graph_key[1] != h->d_ep[1] || h->ep_graph_key[2] != h->d_ep[2])) {
-        hipError_t ec = hipSuccess;
-        for (int k = 0; k < 3; k++) {
-            if (h->ep_graph[k]) { hipGraphExecDestroy(h->ep_graph[k]); h->ep_graph[k] = nullptr; }
-            hipGraph_t g = nullptr;
-            if (ec == hipSuccess) ec = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
-            else continue;
-            if (ec == hipSuccess) {
-                for (int w = 0; w < kChainWindows[k] && ec == hipSuccess; w++)
-                    ec = launch_epoch_chain_window(h->tv, h->sk, h->d_ep[0], (uint32_t*)h->d_ep[2], (uint64_t*)h->d_ep[1], h->stream);
-                const hipError_t ee = hipStreamEndCapture(h->stream, &g);
-                if (ec == hipSuccess) ec = ee;
-                if (ec == hipSuccess) ec = hipGraphInstantiate(&h->ep_graph[k], g, nullptr, nullptr, 0);
-                if (g) hipGraphDestroy(g);
-            }
-        }
-        if (ec != hipSuccess) {
-            // no graph (a capture that something in the process invalidated, an instantiation that failed): this handle launches
-            // its windows eagerly from now on — slower (~8 us of host time per launch), never wrong
-            (void)hipGetLastError();
-            for (int k = 0; k < 3; k++) if (h->ep_graph[k]) { hipGraphExecDestroy(h->ep_graph[k]); h->ep_graph[k] = nullptr; }
-            h->ep_graph_off = true;
-        } else {
-            h->ep_graph_key[0] = h->d_ep[0]; h->ep_graph_key[1] = h->d_ep[1]; h->ep_graph_key[2] = h->d_ep[2];
-        }
-    }
-    EventPair ep{};
-    if (h->cfg.profile) prof_begin(h, ep, 0);
-    uint64_t v[9];
-    uint64_t left = n, ends_inline = 0;
-    h->counters_exact = false; h->mirror_fresh = false;
-    for (;;) {
-        // windows this launch should hold: what is left in whole windows, one for every eviction an epoch of max_entries flows can
-        // end in (each ends its window early), one to spare
-        const uint64_t want = (left + chain_window() - 1) / chain_window() + left / (h->cfg.max_entries ? h->cfg.max_entries : 1) + 1;
-        int k = 0;
-        while (k < 2 && (uint64_t)kChainWindows[k] < want) k++;
-        if (h->ep_graph[k]) HIP_TRY(h, hipGraphLaunch(h->ep_graph[k], h->stream));
-        else {
-            for (int w = 0; w < kChainWindows[k]; w++) {
-                const hipError_t el = launch_epoch_chain_window(h->tv, h->sk, h->d_ep[0], (uint32_t*)h->d_ep[2], (uint64_t*)h->d_ep[1], h->stream);
-                if (el != hipSuccess) return fail(h, NFAGG_EDEVICE, "epoch chain launch failed: %s", hipGetErrorString(el));
-            }
-        }
-        // the control block, the first epoch ends and the counters behind ONE wait (round 5: three)
-        ends_inline = me < kChainEndsInline ? me : kChainEndsInline;
-        HIP_TRY(h, hipMemcpyAsync(h->h_ep, h->d_ep[0], chain_ctl_bytes(), hipMemcpyDeviceToHost, h->stream));
-        if (ends_inline) HIP_TRY(h, hipMemcpyAsync((char*)h->h_ep + ctlb, h->d_ep[1], ends_inline * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        if ((rc = refresh_counters_enqueue(h)) != NFAGG_OK) return rc;
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        chain_ctl_read(h->h_ep, v);
-        if (v[6] != 0) break;
-        left = n - v[0];
-    }
-    if (h->cfg.profile) prof_end(h, ep);
-    const uint64_t pos = v[0], seq = v[1], live = v[2], out_pos = v[3], n_epochs = v[5];
-    if (n_epochs > ends_inline) {
-        HIP_TRY(h, hipMemcpyAsync((char*)h->h_ep + ctlb + ends_inline * sizeof(uint64_t), (const uint64_t*)h->d_ep[1] + ends_inline,
-                                  (size_t)(n_epochs - ends_inline) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    if ((rc = refresh_counters_taken(h)) != NFAGG_OK) return rc;
-    if (h->h_ctr->n_live != live)
-        return fail(h, NFAGG_EDEVICE, "epoch chain: %llu claimed slots, len(entries) %llu", (unsigned long long)h->h_ctr->n_live, (unsigned long long)live);
-    for (uint64_t k = 0; k < n_epochs && k < max_epochs; k++) epoch_end[k] = ((const uint64_t*)((const char*)h->h_ep + ctlb))[k];
-    h->tv.epoch_bits = v[4];
-    // identity dwords of the slots the epoch in progress claimed in this call, from the batch
-    const bool began_here = v[8] != 0;
-    const uint64_t first_rec = began_here ? v[7] : 0, seq_at_first = began_here ? 0 : seq_start;
-    const hipError_t e = launch_finalize(h->tv, (const char*)d + first_rec * kRecordBytes, pos - first_rec, seq_at_first, h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "finalize launch failed: %s", hipGetErrorString(e));
-    if (n_epochs) h->seq_origin = 0;                            // an eviction inside the call restarted the epoch: a fresh window
-    h->epoch_seq = h->seq_origin + seq; h->live = h->live_ub = live;
-    h->counters_exact = true;
-    h->mirror_fresh = false;                                    // (k_finalize moves n_finalized behind the mirror's back)
-    h->epoch_unclustered = true;
-    h->stats.records_ingested += pos;
-    h->stats.evictions[NFAGG_REASON_FULL] += n_epochs;
-    h->stats.evicted_flows[NFAGG_REASON_FULL] += out_pos;
-    *consumed = (size_t)pos; *n_ep = (size_t)n_epochs; *n_out = (size_t)out_pos; *stop = (uint32_t)v[6];
-    return NFAGG_OK;
-}
-
-#ifdef NFAGG_DIAG
-#include <chrono>
-static double diag_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-#define NF_DIAG_T(var) const double var = diag_now_ms()
-#define NF_DIAG_PRINT(...) fprintf(stderr, __VA_ARGS__)
-#else
-#define NF_DIAG_T(var)
-#define NF_DIAG_PRINT(...)
-#endif
-
-#include "nfagg_account_par.inc"
-
-// d_out: DEVICE. epoch_end: HOST. Evictions append to d_out; *n_epochs of them, the e-th ends at record epoch_end[e].
-static int account_device_core(nfagg_handle* h, const void* d_records, size_t n, void* d_out, size_t out_cap, uint64_t* epoch_end,
-                               size_t max_epochs, size_t* n_epochs_out, size_t* consumed_out) {
-    size_t consumed = 0, n_ep = 0, out_pos = 0;
-    int rc = NFAGG_OK;
-    const char* base = static_cast<const char*>(d_records);
-    char* obase = static_cast<char*>(d_out);
-    auto evict_pending = [&]() -> int {                         // the map is full and the record that found it so is next (account.go:85-94)
-        if (n_ep >= max_epochs) return NFAGG_TRUNCATED;
-        size_t got = 0;
-        const int r = evict_core(h, NFAGG_REASON_FULL, obase + out_pos * kRecordBytes, true, out_cap - out_pos, &got);
-        if (r != NFAGG_OK) return r;                            // NFAGG_TRUNCATED: nothing evicted, the caller drains `out` and calls again
-        out_pos += got;
-        epoch_end[n_ep++] = out_pos;
-        return NFAGG_OK;
-    };
-    if (h->must_evict && n) rc = evict_pending();
-    bool par_declined = false;
-    while (rc == NFAGG_OK && consumed < n) {
-        if (!par_declined && account_par_ok(h, n - consumed, out_cap - out_pos) && n_ep < max_epochs) {
-            // the epochs of the call found first, then folded all at once (nfagg_account_par.inc)
-            size_t c = 0, e = 0, o = 0; uint32_t stop = 0;
-            rc = account_par_launch(h, base + consumed * kRecordBytes, n - consumed, obase + out_pos * kRecordBytes, out_cap - out_pos,
-                                    epoch_end + n_ep, max_epochs - n_ep, &c, &e, &o, &stop);
-            for (size_t k = 0; k < e; k++) epoch_end[n_ep + k] += out_pos;
-            consumed += c; n_ep += e; out_pos += o;
-            if (rc == kParDeclined) { rc = NFAGG_OK; par_declined = true; h->stats.account_declined++; continue; }
-            if (rc == NFAGG_OK) h->stats.account_epochs_first++;
-            if (rc != NFAGG_OK) break;
-            if (stop == 2) { rc = NFAGG_TRUNCATED; break; }
-            continue;
-        }
-        if (account_fast_ok(h, n - consumed, out_cap - out_pos) && n_ep < max_epochs) {
-            size_t c = 0, e = 0, o = 0; uint32_t stop = 0;
-            h->stats.account_chain++;
-            rc = account_chain_launch(
-                h, base + consumed * kRecordBytes, n - consumed, obase + out_pos * kRecordBytes, out_cap - out_pos,
-                epoch_end + n_ep, max_epochs - n_ep, &c, &e, &o, &stop);
-            if (rc != NFAGG_OK) break;
-            for (size_t k = 0; k < e; k++) epoch_end[n_ep + k] += out_pos;
-            consumed += c; n_ep += e; out_pos += o;
-            if (stop == 2) { rc = NFAGG_TRUNCATED; break; }     // no room for another eviction
-            if (stop != 3) continue;                            // 3: the epoch tags wrap at the next eviction — that epoch goes through the host path below
-        }
-        size_t c = 0;
-        rc = ingest_device_core(h, base + consumed * kRecordBytes, n - consumed, &c);
-        consumed += c;
-        if (rc == NFAGG_FULL) rc = evict_pending();
-    }
-    if (n_epochs_out) *n_epochs_out = n_ep;
-    if (consumed_out) *consumed_out = consumed;
-    return rc;
-}
-
-int nfagg_account_device(nfagg_handle* h, const void* d_records, size_t n, void* d_out, size_t out_cap, uint64_t* epoch_end,
-                         size_t max_epochs, size_t* n_epochs, size_t* consumed) {
-    if (!h || (!d_records && n) || !epoch_end || !n_epochs || !consumed || (!d_out && out_cap)) return fail(h, NFAGG_EINVAL, "null argument");
-    if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int rc = account_device_core(h, d_records, n, d_out, out_cap, epoch_end, max_epochs, n_epochs, consumed);
-    // synchronous, as the header says: the last launches of the call (k_finalize copies the new flows' identity dwords out of
-    // d_records; a fall-through to the plain fold is asynchronous altogether) have read the caller's buffer when it returns
-    if (rc >= 0) HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return rc;
-}
-
-int nfagg_account(nfagg_handle* h, const void* records, size_t n, void* out, size_t out_cap, uint64_t* epoch_end, size_t max_epochs,
-                  size_t* n_epochs_out, size_t* consumed_out) {
-    if (!h || (!records && n) || !epoch_end || !n_epochs_out || !consumed_out || (!out && out_cap)) return fail(h, NFAGG_EINVAL, "null argument");
-    if (h->stage_acquired) return fail(h, NFAGG_ESTATE, "a staging buffer is acquired; commit it first");
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = staging_alloc(h);
-    if (rc != NFAGG_OK) return rc;
-    const char* src = static_cast<const char*>(records);
-    const size_t cap = (size_t)h->cfg.staging_records;
-    size_t consumed = 0, n_ep = 0, out_pos = 0;
-    // Pinned ring, double buffered as in nfagg_ingest: chunk k+1 is copied into its pinned buffer and sent up on the copy
-    // stream while the device works on chunk k. A chunk that stops early (no room for another eviction) ends the call.
-    // The first chunks are short (a quarter, then half a staging buffer): nothing overlaps the first upload, so it should not be a
-    // whole buffer's (2.6 ms of a 20 ms call for 8 M records over a 57 GB/s link).
-    size_t staged_lo[2] = {0, 0}, staged_n[2] = {0, 0};
-    const bool pinned_src = host_is_pinned(records);            // page-locked caller buffer: sent up as it is, no host copy
-    const bool pinned_out = out_cap != 0 && host_is_pinned(out); // page-locked output: the evictions come down by DMA, asynchronously
-    size_t n_staged = 0;
-    // A call of about one staging buffer (the shim's batch: up to 1 Mi records) goes in up to four equal pieces, none shorter than
-    // the epochs-found-first path takes: the first upload is a quarter of the call, the others overlap the device's work
-    // (4.6 -> ~3.4 ms per 1 Mi-record call, profiles/r06_account_small_calls.txt).
-    const size_t par_min = (size_t)account_par_min_records(h->cfg.max_entries);
-    size_t piece = n;
-    {
-        size_t k = 4;
-        while (k > 1 && n / k < (par_min > 131072 ? par_min : (size_t)131072)) k--;
-        piece = ((n + k - 1) / k + 63) & ~(size_t)63;
-    }
-    auto stage = [&](int b, size_t lo) -> int {
-        size_t want = cap;
-        if (n > cap + cap / 2) { if (n_staged < 2) want = cap >> (2 - n_staged); }  // a long call ramps up: cap / 4, cap / 2, cap, cap, ...
-        else want = piece;                                                          // a call of about one staging buffer: in up to four equal pieces
-        // (never so short that the chunk leaves the epochs-found-first path, nor longer than a staging buffer)
-        if (want < par_min) want = par_min;
-        if (want > cap) want = cap;
-        n_staged++;
-        const size_t m = (n - lo) < want ? (n - lo) : want;
-        HIP_TRY(h, hipEventSynchronize(h->stage_free[b]));
-        const void* up = src + lo * kRecordBytes;
-        if (!pinned_src) { staged_copy(h->pinned[b], up, m * kRecordBytes, h->cfg.copy_threads); up = h->pinned[b]; }
-        HIP_TRY(h, hipMemcpyAsync(h->d_stage[b], up, m * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
-        HIP_TRY(h, hipEventRecord(h->stage_up[b], h->copy_stream));
-        staged_lo[b] = lo; staged_n[b] = m;
-        return NFAGG_OK;
-    };
-    int b = h->stage_next;
-    if (n && (rc = stage(b, 0)) != NFAGG_OK) return rc;
-    // Three things overlap per chunk k: this thread drives the device over chunk k (synchronous); the evictions of chunk k-1
-    // come down into the caller's buffer; chunk k+1 goes up. Two device buffers take the evictions in turn; a chunk of m records
-    // delivers at most m + max_entries flows.
-    //   page-locked output: an asynchronous copy on a stream of its own, waited for only when its device buffer comes round
-    //     again (a blocking hipMemcpy from a helper thread was served only after the upload in flight: 3 ms of every second
-    //     chunk, 27.6 ms for the 8 M-record call where the link needs 20.2 — profiles/r05_account_host_pipeline.txt);
-    //   pageable output: a helper thread (pinned bounce buffers + host copies, d2h_copy).
-    if (pinned_out) {
-        if (!h->d2h_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->d2h_stream, hipStreamNonBlocking));
-        for (int k = 0; k < 2; k++)
-            if (!h->bounce_ev[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->bounce_ev[k], hipEventDisableTiming));
-    }
-    bool down_pending[2] = {false, false};                      // pinned_out: a download from eviction buffer [k] is in flight
-    struct { bool has = false; const void* d = nullptr; size_t got = 0, at = 0; } prev;
-    auto bring_down = [&]() -> int {
-        int rd = NFAGG_OK;
-        if (prev.has && prev.got) rd = d2h_copy(h, (char*)out + prev.at * kRecordBytes, prev.d, prev.got * kRecordBytes);
-        prev.has = false;
-        return rd;
-    };
-    int ebuf = 0;
-    while (rc == NFAGG_OK && consumed < n) {
-        const size_t lo = staged_lo[b], m = staged_n[b];
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->stage_up[b], 0));
-        const bool more = lo + m < n;
-        size_t room = out_cap - out_pos;
-        // a chunk of m records delivers at most max_entries + m flows, and the device loop wants room for one more whole eviction
-        // (max_entries) whenever an epoch ends: with less it would report "no room" although the caller's buffer has some
-        if (room > m + 2 * (size_t)h->cfg.max_entries) room = m + 2 * (size_t)h->cfg.max_entries;
-        void** dbuf = ebuf ? &h->d_ep_out : &h->d_evict;
-        size_t capb = ebuf ? h->d_ep_out_cap : (size_t)h->d_evict_cap;
-        if (down_pending[ebuf]) { HIP_TRY(h, hipEventSynchronize(h->bounce_ev[ebuf])); down_pending[ebuf] = false; }   // its last download has left
-        rc = ensure_bytes(h, dbuf, &capb, room * kRecordBytes + 16);
-        if (ebuf) h->d_ep_out_cap = capb; else h->d_evict_cap = capb;
-        if (rc != NFAGG_OK) break;
-        size_t c = 0, e = 0;
-        int rc_helper = NFAGG_OK, rc_helper2 = NFAGG_OK;
-        std::thread helper, helper2;                            // one brings chunk k-1's evictions down (pageable output), one sends chunk k+1 up
-        const bool down = !pinned_out && prev.has && prev.got != 0;
-        // (a thread that cannot be created must not throw through the C boundary: its job is done here and now instead)
-        auto spawn = [](std::thread& t, auto fn) { try { t = std::thread(fn); } catch (...) { fn(); } };
-        if (down) spawn(helper, [&] { (void)hipSetDevice(h->device); rc_helper = bring_down(); });
-        else prev.has = false;
-        if (more) spawn(helper2, [&] { (void)hipSetDevice(h->device); rc_helper2 = stage(b ^ 1, lo + m); });
-        NF_DIAG_T(t_a);
-        rc = account_device_core(h, h->d_stage[b], m, *dbuf, room, epoch_end + n_ep, max_epochs - n_ep, &e, &c);
-        NF_DIAG_T(t_b);
-        if (helper.joinable()) helper.join();
-        NF_DIAG_T(t_c);
-        if (helper2.joinable()) helper2.join();
-        NF_DIAG_T(t_d);
-        NF_DIAG_PRINT("[account] chunk at %zu: %zu records, core %.2f ms (%zu evictions), wait down %.2f, wait up %.2f\n", lo, m, t_b - t_a, e, t_c - t_b, t_d - t_c);
-        if (rc_helper == NFAGG_OK) rc_helper = rc_helper2;
-        if (rc == NFAGG_OK && rc_helper != NFAGG_OK) rc = rc_helper;
-        HIP_TRY(h, hipEventRecord(h->stage_free[b], h->stream));
-        const size_t got = e ? (size_t)epoch_end[n_ep + e - 1] : 0;
-        if (pinned_out) {
-            if (got && rc >= 0) {
-                // account_device_core has synchronised the fold stream for everything it wrote into *dbuf
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                HIP_TRY(h, hipMemcpyAsync((char*)out + out_pos * kRecordBytes, *dbuf, got * kRecordBytes, hipMemcpyDeviceToHost, h->d2h_stream));
-                HIP_TRY(h, hipEventRecord(h->bounce_ev[ebuf], h->d2h_stream));
-                down_pending[ebuf] = true;
-            }
-        } else {
-            prev.has = true; prev.d = *dbuf; prev.got = got; prev.at = out_pos;
-        }
-        for (size_t k = 0; k < e; k++) epoch_end[n_ep + k] += out_pos;
-        n_ep += e; out_pos += got; consumed += c;
-        h->stage_next = b ^ 1;
-        ebuf ^= 1;
-        if (rc != NFAGG_OK || c < m) break;                     // stopped inside the chunk: what was staged beyond it is staged again by the next call
-        b ^= 1;
-    }
-    {
-        int rc_down = bring_down();
-        if (pinned_out && (down_pending[0] || down_pending[1]) && hipStreamSynchronize(h->d2h_stream) != hipSuccess)
-            rc_down = fail(h, NFAGG_EDEVICE, "eviction download failed");
-        if (rc == NFAGG_OK || rc == NFAGG_TRUNCATED) { if (rc_down != NFAGG_OK) rc = rc_down; }
-    }
-    if (pinned_src) (void)hipStreamSynchronize(h->copy_stream);       // a chunk staged ahead may still be on its way: the caller's buffer is its own again
-    *n_epochs_out = n_ep; *consumed_out = consumed;
-    return rc;
 }
 
 // Page-locked host memory for record / eviction buffers: what nfagg_ingest, nfagg_account and nfagg_evict are handed in such a
@@ -1708,6 +1296,8 @@ int nfagg_debug_skip_sequence(nfagg_handle* h, uint64_t records) {
     return NFAGG_OK;
 }
 
+uint64_t nfagg_debug_live_buffers(void) { return g_live_buffers.load(); }
+
 int nfagg_stats_get(nfagg_handle* h, nfagg_stats* out) {
     if (!h || !out) return fail(h, NFAGG_EINVAL, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1720,11 +1310,8 @@ int nfagg_stats_get(nfagg_handle* h, nfagg_stats* out) {
     return NFAGG_OK;
 }
 
-}  // extern "C"
-
-extern "C" {
-
 #ifdef NFAGG_DIAG
+extern "C" {
 // libnfagg_diag.so only: what the last epochs-found-first launch of nfagg_account saw — its control words and its cuts (host copies)
 int nfagg_debug_last_cuts(nfagg_handle* h, uint32_t ctl[8], uint32_t* cuts, size_t cap) {
     if (!h || !ctl || !h->h_par) return NFAGG_EINVAL;
@@ -1733,12 +1320,12 @@ int nfagg_debug_last_cuts(nfagg_handle* h, uint32_t ctl[8], uint32_t* cuts, size
     return NFAGG_OK;
 }
 int nfagg_debug_last_analysis(nfagg_handle* h, uint64_t* keys_sorted, int32_t* prev, uint32_t* pos, size_t n) {
-    if (!h || !h->d_par[1]) return NFAGG_EINVAL;
+    if (!h || !h->par.keys_sorted) return NFAGG_EINVAL;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
-    if (keys_sorted) HIP_TRY(h, hipMemcpy(keys_sorted, h->d_par[1], n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (prev) HIP_TRY(h, hipMemcpy(prev, h->d_par[2], n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (pos) HIP_TRY(h, hipMemcpy(pos, h->d_par[3], n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (keys_sorted) HIP_TRY(h, hipMemcpy(keys_sorted, h->par.keys_sorted.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (prev) HIP_TRY(h, hipMemcpy(prev, h->par.prev.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (pos) HIP_TRY(h, hipMemcpy(pos, h->par.pos.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return NFAGG_OK;
 }
 // libnfagg_diag.so only: the dense-identity timing experiment of k_finalize + k_evict (nfagg_kernels.hip g_diag_dense). on = 1: a
@@ -1763,6 +1350,7 @@ int nfagg_debug_phase_cycles(nfagg_handle* h, uint64_t out[8]) {
     for (int k = 0; k < 8; k++) out[k] = h->h_ctr->phase[k];
     return NFAGG_OK;
 }
+}  // extern "C"
 #endif
 
 int nfagg_stats_reset_profile(nfagg_handle* h) {
@@ -1773,7 +1361,3 @@ int nfagg_stats_reset_profile(nfagg_handle* h) {
     h->stats.ingest_kernel_ms = h->stats.evict_kernel_ms = h->stats.sketch_kernel_ms = 0.0;
     return NFAGG_OK;
 }
-
-}  // extern "C"
-
-#include "nfagg_group.inc"

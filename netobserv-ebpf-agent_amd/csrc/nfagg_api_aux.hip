@@ -25,15 +25,15 @@ static int rollup_core(nfagg_handle* h, int kind, const void* partials, size_t n
     const size_t ssz = rollup_struct_size(kind);
     const size_t pb = n_flows * n_cpu * ssz, bb = n_flows * sizeof(nfagg_flow_metrics), fb = n_flows * ssz;
     int rc;
-    if ((rc = ensure_bytes(h, &h->d_roll[0], &h->d_roll_cap[0], pb)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_roll[1], &h->d_roll_cap[1], bb)) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_roll[2], &h->d_roll_cap[2], fb)) != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_roll[0], partials, pb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_roll[1], base, bb, hipMemcpyHostToDevice, h->stream));
-    hipError_t e = launch_rollup(kind, h->d_roll[0], n_flows, n_cpu, h->d_roll[1], h->d_roll[2], h->stream);
+    if ((rc = h->roll.partials.ensure(h, pb)) != NFAGG_OK) return rc;
+    if ((rc = h->roll.base.ensure(h, bb)) != NFAGG_OK) return rc;
+    if ((rc = h->roll.folded.ensure(h, fb)) != NFAGG_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->roll.partials.p, partials, pb, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->roll.base.p, base, bb, hipMemcpyHostToDevice, h->stream));
+    hipError_t e = launch_rollup(kind, h->roll.partials.p, n_flows, n_cpu, h->roll.base.p, h->roll.folded.p, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "rollup launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(base, h->d_roll[1], bb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(folded, h->d_roll[2], fb, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(base, h->roll.base.p, bb, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(folded, h->roll.folded.p, fb, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
 }
@@ -85,28 +85,28 @@ static int map_merge_device_core(nfagg_handle* h, const nfagg_map_view* mm, cons
     while ((uint64_t)n_slots < 2 * total) n_slots <<= 1;
     const size_t blocks = (total + 1023) / 1024;
     int rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[0], &h->d_mm_cap[0], (size_t)n_slots * merge_slot_bytes())) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[1], &h->d_mm_cap[1], total * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[2], &h->d_mm_cap[2], total * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[3], &h->d_mm_cap[3], blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[4], &h->d_mm_cap[4], (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_mm[5], &h->d_mm_cap[5], 16)) != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemsetAsync(h->d_mm[0], 0xFF, (size_t)n_slots * merge_slot_bytes(), h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_mm[5], 0, 16, h->stream));
-    hipError_t e = launch_merge_build(in, h->d_mm[0], n_slots, (uint32_t*)h->d_mm[1], (unsigned int*)h->d_mm[5],
-                                      (uint32_t*)h->d_mm[2], (uint32_t*)h->d_mm[3], h->stream);
+    if ((rc = h->mm.slots.ensure(h, (size_t)n_slots * merge_slot_bytes())) != NFAGG_OK) return rc;
+    if ((rc = h->mm.slot_of.ensure(h, total * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = h->mm.local_off.ensure(h, total * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = h->mm.block_sum.ensure(h, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = h->mm.block_base.ensure(h, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = h->mm.n_dup.ensure(h, 16)) != NFAGG_OK) return rc;
+    HIP_TRY(h, hipMemsetAsync(h->mm.slots.p, 0xFF, (size_t)n_slots * merge_slot_bytes(), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->mm.n_dup.p, 0, 16, h->stream));
+    hipError_t e = launch_merge_build(in, h->mm.slots.p, n_slots, h->mm.slot_of.as<uint32_t>(), h->mm.n_dup.as<unsigned int>(),
+                                      h->mm.local_off.as<uint32_t>(), h->mm.block_sum.as<uint32_t>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "map merge build launch failed: %s", hipGetErrorString(e));
-    e = launch_scan_block_sums((const uint32_t*)h->d_mm[3], (uint32_t)blocks, (uint64_t*)h->d_mm[4], h->stream);
+    e = launch_scan_block_sums(h->mm.block_sum.as<const uint32_t>(), (uint32_t)blocks, h->mm.block_base.as<uint64_t>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "map merge scan launch failed: %s", hipGetErrorString(e));
     uint64_t flows = 0; unsigned int dups = 0;
-    HIP_TRY(h, hipMemcpyAsync(&flows, (uint64_t*)h->d_mm[4] + blocks, sizeof flows, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&dups, h->d_mm[5], sizeof dups, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&flows, h->mm.block_base.as<uint64_t>() + blocks, sizeof flows, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&dups, h->mm.n_dup.p, sizeof dups, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *n_out = (size_t)flows;
     if (n_dup) *n_dup = dups;
     if (flows > cap) return NFAGG_TRUNCATED;
     MergeOut o{out->records, out->present, out->additional, out->dns, out->drops, out->network_events, out->xlat, out->quic};
-    e = launch_merge_fold(in, o, h->d_mm[0], (const uint32_t*)h->d_mm[1], (const uint32_t*)h->d_mm[2], (const uint64_t*)h->d_mm[4], h->stream);
+    e = launch_merge_fold(in, o, h->mm.slots.p, h->mm.slot_of.as<const uint32_t>(), h->mm.local_off.as<const uint32_t>(), h->mm.block_base.as<const uint64_t>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "map merge fold launch failed: %s", hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
@@ -131,11 +131,11 @@ int nfagg_map_merge(nfagg_handle* h, const nfagg_map_view* main_map, const nfagg
         if (!v.n) continue;
         if (!v.ids || !v.values) return fail(h, NFAGG_EINVAL, "map %d: null ids/values", q);
         const size_t vb = q == 0 ? v.n * sizeof(nfagg_flow_metrics) : v.n * n_cpu * rollup_struct_size(q - 1);
-        if ((rc = ensure_bytes(h, &h->d_mm[6 + q], &h->d_mm_cap[6 + q], v.n * sizeof(nfagg_flow_id))) != NFAGG_OK) return rc;
-        if ((rc = ensure_bytes(h, &h->d_mm[13 + q], &h->d_mm_cap[13 + q], vb)) != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->d_mm[6 + q], v.ids, v.n * sizeof(nfagg_flow_id), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->d_mm[13 + q], v.values, vb, hipMemcpyHostToDevice, h->stream));
-        d.ids = (const nfagg_flow_id*)h->d_mm[6 + q]; d.values = h->d_mm[13 + q];
+        if ((rc = h->mm.ids[q].ensure(h, v.n * sizeof(nfagg_flow_id))) != NFAGG_OK) return rc;
+        if ((rc = h->mm.vals[q].ensure(h, vb)) != NFAGG_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->mm.ids[q].p, v.ids, v.n * sizeof(nfagg_flow_id), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->mm.vals[q].p, v.values, vb, hipMemcpyHostToDevice, h->stream));
+        d.ids = h->mm.ids[q].as<const nfagg_flow_id>(); d.values = h->mm.vals[q].p;
     }
     void* host_out[8] = {out->records, out->present, out->additional, out->dns, out->drops, out->network_events, out->xlat, out->quic};
     const size_t elem[8] = {sizeof(nfagg_flow_record), 1, sizeof(nfagg_additional_metrics), sizeof(nfagg_dns_metrics), sizeof(nfagg_pkt_drop_metrics),
@@ -143,8 +143,8 @@ int nfagg_map_merge(nfagg_handle* h, const nfagg_map_view* main_map, const nfagg
     void* dev_out[8] = {};
     for (int k = 0; k < 8; k++) {
         if (!host_out[k] || !cap) continue;
-        if ((rc = ensure_bytes(h, &h->d_mm[20 + k], &h->d_mm_cap[20 + k], cap * elem[k] + 16)) != NFAGG_OK) return rc;
-        dev_out[k] = h->d_mm[20 + k];
+        if ((rc = h->mm.out[k].ensure(h, cap * elem[k] + 16)) != NFAGG_OK) return rc;
+        dev_out[k] = h->mm.out[k].p;
     }
     nfagg_merged_flows dout{(nfagg_flow_record*)dev_out[0], (uint8_t*)dev_out[1], (nfagg_additional_metrics*)dev_out[2], (nfagg_dns_metrics*)dev_out[3],
                             (nfagg_pkt_drop_metrics*)dev_out[4], (nfagg_network_events_metrics*)dev_out[5], (nfagg_xlat_metrics*)dev_out[6],
@@ -185,13 +185,7 @@ int nfagg_sketch_snapshot(nfagg_handle* h, int which, void* out, size_t out_byte
     void* p; size_t bytes;
     int rc = sketch_info(h, which, &p, &bytes);
     if (rc != NFAGG_OK) return rc;
-    if (which == NFAGG_CM_SRC || which == NFAGG_CM_DST) {
-        if (out_bytes < bytes) return NFAGG_TRUNCATED;
-        HIP_TRY(h, hipMemcpyAsync(out, p, bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return NFAGG_OK;
-    }
-    if (out_bytes < bytes) return NFAGG_TRUNCATED;                   // the device registers ARE the snapshot layout: one byte each
+    if (out_bytes < bytes) return NFAGG_TRUNCATED;                   // the device arrays ARE the snapshot layout (HLL: one byte per register)
     HIP_TRY(h, hipMemcpyAsync(out, p, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
@@ -236,10 +230,10 @@ int nfagg_hll_estimate(nfagg_handle* h, int which, double* estimate) {
     void* p; size_t bytes;
     int rc = sketch_info(h, which, &p, &bytes);
     if (rc != NFAGG_OK) return rc;
-    hipError_t e = launch_hll_histogram((const uint8_t*)p, h->sk.hll_p, h->d_hist, h->stream);
+    hipError_t e = launch_hll_histogram((const uint8_t*)p, h->sk.hll_p, h->d_hist.as<uint32_t>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "hll histogram launch failed: %s", hipGetErrorString(e));
     uint32_t hist[65];
-    HIP_TRY(h, hipMemcpyAsync(hist, h->d_hist, sizeof hist, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(hist, h->d_hist.p, sizeof hist, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *estimate = nfagg_hll_estimate_from_histogram(hist, h->sk.hll_p);
     return NFAGG_OK;
@@ -284,14 +278,14 @@ static int cm_topk_core(nfagg_handle* h, int which, const void* d_records, size_
     size_t temp_bytes = 0;
     hipError_t e = launch_cm_sort_desc(nullptr, nullptr, nullptr, nullptr, n, nullptr, &temp_bytes, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "sort size query failed: %s", hipGetErrorString(e));
-    if ((rc = ensure_bytes(h, &h->d_hh[0], &h->d_hh_cap[0], n * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_hh[1], &h->d_hh_cap[1], n * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_hh[2], &h->d_hh_cap[2], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_hh[3], &h->d_hh_cap[3], n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_bytes(h, &h->d_hh[4], &h->d_hh_cap[4], temp_bytes + 16)) != NFAGG_OK) return rc;
-    e = launch_cm_estimate((const uint64_t*)cm, h->sk.cm_depth, h->sk.cm_log2w, side, d_records, n, (uint64_t*)h->d_hh[0], (uint32_t*)h->d_hh[2], h->stream);
-    if (e == hipSuccess) e = launch_cm_sort_desc((const uint64_t*)h->d_hh[0], (uint64_t*)h->d_hh[1], (const uint32_t*)h->d_hh[2], (uint32_t*)h->d_hh[3], n,
-                                                 h->d_hh[4], &temp_bytes, h->stream);
+    if ((rc = h->hh.est.ensure(h, n * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = h->hh.est_sorted.ensure(h, n * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = h->hh.idx.ensure(h, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = h->hh.idx_sorted.ensure(h, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = h->hh.sort_tmp.ensure(h, temp_bytes + 16)) != NFAGG_OK) return rc;
+    e = launch_cm_estimate((const uint64_t*)cm, h->sk.cm_depth, h->sk.cm_log2w, side, d_records, n, h->hh.est.as<uint64_t>(), h->hh.idx.as<uint32_t>(), h->stream);
+    if (e == hipSuccess) e = launch_cm_sort_desc(h->hh.est.as<const uint64_t>(), h->hh.est_sorted.as<uint64_t>(), h->hh.idx.as<const uint32_t>(), h->hh.idx_sorted.as<uint32_t>(), n,
+                                                 h->hh.sort_tmp.p, &temp_bytes, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "heavy-hitter launch failed: %s", hipGetErrorString(e));
     struct Row { uint64_t lo, hi, est; };
     std::vector<Row> rows, best;                         // best: distinct addresses in order of appearance (estimate descending)
@@ -300,11 +294,11 @@ static int cm_topk_core(nfagg_handle* h, int which, const void* d_records, size_
     size_t seen = 0, m = k * 16 < 4096 ? 4096 : k * 16;
     for (;;) {
         if (m > n) m = n;
-        if ((rc = ensure_bytes(h, &h->d_hh[5], &h->d_hh_cap[5], m * sizeof(Row))) != NFAGG_OK) return rc;
-        e = launch_cm_gather(d_records, side, (const uint64_t*)h->d_hh[1], (const uint32_t*)h->d_hh[3], m, (uint64_t*)h->d_hh[5], h->stream);
+        if ((rc = h->hh.rows.ensure(h, m * sizeof(Row))) != NFAGG_OK) return rc;
+        e = launch_cm_gather(d_records, side, h->hh.est_sorted.as<const uint64_t>(), h->hh.idx_sorted.as<const uint32_t>(), m, h->hh.rows.as<uint64_t>(), h->stream);
         if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "heavy-hitter gather failed: %s", hipGetErrorString(e));
         rows.resize(m);
-        HIP_TRY(h, hipMemcpyAsync(rows.data(), h->d_hh[5], m * sizeof(Row), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(rows.data(), h->hh.rows.p, m * sizeof(Row), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         bool done = false;
         for (; seen < m; seen++) {
@@ -334,10 +328,10 @@ int nfagg_cm_topk_device(nfagg_handle* h, int which, const void* d_records, size
 int nfagg_cm_topk(nfagg_handle* h, int which, const void* records, size_t n, size_t k, nfagg_heavy_hitter* out, size_t* n_out) {
     if (!h || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_bytes(h, &h->d_hh[6], &h->d_hh_cap[6], n * kRecordBytes + 16);
+    int rc = h->hh.records.ensure(h, n * kRecordBytes + 16);
     if (rc != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_hh[6], records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    return cm_topk_core(h, which, h->d_hh[6], n, k, out, n_out);
+    if (n) HIP_TRY(h, hipMemcpyAsync(h->hh.records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+    return cm_topk_core(h, which, h->hh.records.p, n, k, out, n_out);
 }
 
 }  // extern "C"

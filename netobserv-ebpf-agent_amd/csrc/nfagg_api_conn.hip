@@ -94,19 +94,19 @@ int nfagg_conn_fold_device(nfagg_handle* h, const void* d_records, size_t n, con
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure_buf(h, S.conn_slots, 256 + slot_bytes)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.conn_flow, n * (sizeof(uint64_t) + sizeof(uint32_t)) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.local_off, slots * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.block_sum, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.block_base, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    D.ctl = (ConnCtl*)S.conn_slots.p;
-    D.slots = (uint64_t*)((uint8_t*)S.conn_slots.p + 256);
-    D.hash_a = (uint64_t*)S.conn_flow.p;                        // n hashes, then n slot indexes
+    if ((rc = S.conn_slots.ensure(h, 256 + slot_bytes)) != NFAGG_OK) return rc;
+    if ((rc = S.conn_flow.ensure(h, n * (sizeof(uint64_t) + sizeof(uint32_t)) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.local_off.ensure(h, slots * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.block_sum.ensure(h, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.block_base.ensure(h, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    D.ctl = S.conn_slots.as<ConnCtl>();
+    D.slots = (uint64_t*)(S.conn_slots.as<uint8_t>() + 256);
+    D.hash_a = S.conn_flow.as<uint64_t>();                        // n hashes, then n slot indexes
     D.slot_of = (uint32_t*)(D.hash_a + n);
     HIP_TRY(h, hipMemsetAsync(S.conn_slots.p, 0, 256 + slot_bytes, h->stream));
     hipError_t e = launch_conn_claim(d_records, n, D, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "conn claim launch failed: %s", hipGetErrorString(e));
-    e = launch_conn_finish(d_records, n, D, (uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p, h->stream);
+    e = launch_conn_finish(d_records, n, D, S.local_off.as<uint32_t>(), S.block_sum.as<uint32_t>(), S.block_base.as<uint64_t>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "conn finish launch failed: %s", hipGetErrorString(e));
     ConnCtl ctl;
     HIP_TRY(h, hipMemcpyAsync(&ctl, D.ctl, sizeof ctl, hipMemcpyDeviceToHost, h->stream));      // the one read-back: counts and flags
@@ -126,11 +126,11 @@ int nfagg_conn_fold(nfagg_handle* h, const void* records, size_t n, const nfagg_
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.conn_ids, n * sizeof(uint64_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.conn_out, std::min<size_t>(cap, n) * sizeof(nfagg_conn_partial) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.conn_ids.ensure(h, n * sizeof(uint64_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.conn_out.ensure(h, std::min<size_t>(cap, n) * sizeof(nfagg_conn_partial) + 16)) != NFAGG_OK) return rc;
     if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    rc = nfagg_conn_fold_device(h, S.in_records.p, n, opt, hash_ids ? (uint64_t*)S.conn_ids.p : nullptr, cap, (nfagg_conn_partial*)S.conn_out.p, n_conns,
+    rc = nfagg_conn_fold_device(h, S.in_records.p, n, opt, hash_ids ? S.conn_ids.as<uint64_t>() : nullptr, cap, S.conn_out.as<nfagg_conn_partial>(), n_conns,
                                 n_discarded);
     if (rc != NFAGG_OK && rc != NFAGG_TRUNCATED) return rc;
     if (n && hash_ids) HIP_TRY(h, hipMemcpyAsync(hash_ids, S.conn_ids.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));

@@ -34,7 +34,7 @@ int check_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names,
 // The kernels binary-search the table: a stable sort by if_index keeps the scan-in-table-order answer.
 int stage_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names) {
     auto& S = h->enc;
-    int rc = ensure_buf(h, S.names, (size_t)(n_names + 1) * sizeof(nfagg_intf_name));
+    int rc = S.names.ensure(h, (size_t)(n_names + 1) * sizeof(nfagg_intf_name));
     if (rc != NFAGG_OK) return rc;
     S.h_names.assign(names, names + n_names);
     std::stable_sort(S.h_names.begin(), S.h_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
@@ -56,9 +56,9 @@ int encode_begin(nfagg_handle* h, size_t n, uint64_t* d_offsets, size_t* out_byt
     if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
     const size_t blocks = (n + 1023) / 1024;
     int rc;
-    if ((rc = ensure_buf(h, h->enc.local_off, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, h->enc.block_sum, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, h->enc.block_base, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = h->enc.local_off.ensure(h, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = h->enc.block_sum.ensure(h, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = h->enc.block_base.ensure(h, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
     return stage_namer(h, names, n_names);
 }
 
@@ -70,17 +70,17 @@ int encode_two_pass(nfagg_handle* h, size_t n, const char* what, const char* wri
                            size_t* n_deferred, SizeLaunch size, WriteLaunch write) {
     auto& S = h->enc;
     const size_t blocks = (n + 1023) / 1024;
-    hipError_t e = size((uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p);
+    hipError_t e = size(S.local_off.as<uint32_t>(), S.block_sum.as<uint32_t>(), S.block_base.as<uint64_t>());
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s size launch failed: %s", what, hipGetErrorString(e));
     uint64_t total = 0;
     uint32_t deferred = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, (uint64_t*)S.block_base.p + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&total, S.block_base.as<uint64_t>() + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
     if (n_deferred) HIP_TRY(h, hipMemcpyAsync(&deferred, S.flp_n_deferred.p, sizeof deferred, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *out_bytes = (size_t)total;
     if (n_deferred) *n_deferred = deferred;
     if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
-    e = write((const uint32_t*)S.local_off.p, (const uint64_t*)S.block_base.p, total);
+    e = write(S.local_off.as<const uint32_t>(), S.block_base.as<const uint64_t>(), total);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s %s launch failed: %s", what, write_verb, hipGetErrorString(e));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
@@ -95,13 +95,13 @@ int encode_staged(nfagg_handle* h, const void* records, size_t n, void* out, siz
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out, out_cap + 32)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out_offsets, (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.out.ensure(h, out_cap + 32)) != NFAGG_OK) return rc;
+    if ((rc = S.out_offsets.ensure(h, (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
     size_t k = 0;
-    for (const EncodeExtra& x : extras) { if (x.host && (rc = ensure_buf(h, S.out_extra[k], n * x.bytes + 32)) != NFAGG_OK) return rc; k++; }
+    for (const EncodeExtra& x : extras) { if (x.host && (rc = S.out_extra[k].ensure(h, n * x.bytes + 32)) != NFAGG_OK) return rc; k++; }
     if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    rc = device(S.in_records.p, out ? S.out.p : nullptr, (uint64_t*)S.out_offsets.p);
+    rc = device(S.in_records.p, out ? S.out.p : nullptr, S.out_offsets.as<uint64_t>());
     if (rc != NFAGG_OK) return rc;
     if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, S.out.p, *out_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(offsets, S.out_offsets.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
@@ -132,7 +132,7 @@ static int device_netev(nfagg_handle* h, const NetevArgs* ne, size_t n, PbFeat* 
     if (!ne->table || (n && !ne->rows)) return fail(h, NFAGG_EINVAL, "null network-events rows or table");
     if (ne->table->h != h || !ne->table->d_rows) return fail(h, NFAGG_EINVAL, "the network-events table was not created for this handle");
     if (((uintptr_t)ne->rows & 7u) != 0) return fail(h, NFAGG_EINVAL, "network-events rows must be 8-byte aligned");
-    F->ne_rows = ne->rows; F->ne_tab = (const uint8_t*)ne->table->d_rows; F->ne_blob = (const uint8_t*)ne->table->d_blob;
+    F->ne_rows = ne->rows; F->ne_tab = ne->table->d_rows.as<const uint8_t>(); F->ne_blob = ne->table->d_blob.as<const uint8_t>();
     F->ne_n = (uint32_t)ne->table->rows.size();
     return NFAGG_OK;
 }
@@ -140,10 +140,10 @@ static int device_netev(nfagg_handle* h, const NetevArgs* ne, size_t n, PbFeat* 
 static int stage_netev_rows(nfagg_handle* h, const NetevArgs* ne, size_t n, NetevArgs* dne) {
     *dne = *ne;
     if (!n || !ne->rows) return NFAGG_OK;
-    int rc = ensure_buf(h, h->enc.ne_rows, n * 8 + 16);
+    int rc = h->enc.ne_rows.ensure(h, n * 8 + 16);
     if (rc != NFAGG_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->enc.ne_rows.p, ne->rows, n * 8, hipMemcpyHostToDevice, h->stream));
-    dne->rows = (const uint16_t*)h->enc.ne_rows.p;
+    dne->rows = h->enc.ne_rows.as<const uint16_t>();
     return NFAGG_OK;
 }
 
@@ -170,7 +170,7 @@ static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t 
     memcpy(P.agent_ip_w, opt->agent_ip, 16);
     static const uint8_t v4pre[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xff, 0xff};
     P.agent_is_v4 = memcmp(opt->agent_ip, v4pre, 12) == 0;     // net.IP.To4() != nil (proto.go:255-261)
-    P.names = (const nfagg_intf_name*)h->enc.names.p; P.n_names = opt->n_names;
+    P.names = h->enc.names.as<const nfagg_intf_name>(); P.n_names = opt->n_names;
     P.unknown_len = opt->unknown_len; memcpy(P.unknown, opt->unknown_name, 16);
     return encode_two_pass(h, n, "protobuf", "encode", d_out, out_cap, out_bytes, nullptr,
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
@@ -188,7 +188,7 @@ int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, 
     void* dst[6] = {};
     for (int k = 0; k < 6; k++) {
         if (!src[k]) continue;
-        int rc = ensure_buf(h, h->enc.pb_feat[k], n * elem[k] + 16);
+        int rc = h->enc.pb_feat[k].ensure(h, n * elem[k] + 16);
         if (rc != NFAGG_OK) return rc;
         HIP_TRY(h, hipMemcpyAsync(h->enc.pb_feat[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
         dst[k] = h->enc.pb_feat[k].p;
@@ -213,7 +213,7 @@ static int encode_pb_host_core(nfagg_handle* h, const void* records, size_t n, c
             NetevArgs dne{};
             if (ne) { int rc = stage_netev_rows(h, ne, n, &dne); if (rc != NFAGG_OK) return rc; }
             return encode_pb_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, opt, d_out, out_cap, d_offsets,
-                                         (uint32_t*)h->enc.out_extra[0].p, kafka_keys ? h->enc.out_extra[1].p : nullptr, out_bytes); });
+                                         h->enc.out_extra[0].as<uint32_t>(), kafka_keys ? h->enc.out_extra[1].p : nullptr, out_bytes); });
 }
 
 int nfagg_encode_pb_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_options* opt,
@@ -300,12 +300,12 @@ int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, 
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
     bool done;
     if ((rc = encode_begin(h, n, d_msg_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
-    if ((rc = ensure_buf(h, h->enc.ipfix_name_rows, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    uint32_t* name_rows = (uint32_t*)h->enc.ipfix_name_rows.p;
+    if ((rc = h->enc.ipfix_name_rows.ensure(h, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    uint32_t* name_rows = h->enc.ipfix_name_rows.as<uint32_t>();
     IpfixParams P{};
     split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
     P.mono_now = opt->mono_now_ns;
-    P.names = (const nfagg_intf_name*)h->enc.names.p; P.n_names = opt->n_names;
+    P.names = h->enc.names.as<const nfagg_intf_name>(); P.n_names = opt->n_names;
     P.unknown_len = opt->unknown_len; memcpy(P.unknown_w, opt->unknown_name, 16);
     P.export_time = opt->export_time_s; P.seq0 = opt->seq0; P.obs_domain = opt->obs_domain_id;
     P.tid_v4 = opt->template_id_v4; P.tid_v6 = opt->template_id_v6;
@@ -345,9 +345,9 @@ static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, Fl
     int rc;
     auto& S = h->enc;
     const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
-    if ((rc = ensure_buf(h, S.flp_rows, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.flp_esc, esc_bytes)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.flp_n_deferred, 16)) != NFAGG_OK) return rc;
+    if ((rc = S.flp_rows.ensure(h, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.flp_esc.ensure(h, esc_bytes)) != NFAGG_OK) return rc;
+    if ((rc = S.flp_n_deferred.ensure(h, 16)) != NFAGG_OK) return rc;
     // names and UDNs are escaped here, once per row of the sorted table: neither kernel escapes per flow
     S.h_flp_esc.assign(esc_bytes, 0);
     flp_escape_row(S.h_flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
@@ -357,13 +357,13 @@ static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, Fl
     }
     HIP_TRY(h, hipMemcpyAsync(S.flp_esc.p, S.h_flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
-    *rows_out = (uint32_t*)S.flp_rows.p;
+    *rows_out = S.flp_rows.as<uint32_t>();
     FlpParams& P = *Pout;
     P = FlpParams{};
     split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
     P.mono_now = opt->mono_now_ns;
     P.time_received = opt->time_received_s;
-    P.names = (const nfagg_intf_name*)S.names.p; P.esc = (const uint8_t*)S.flp_esc.p; P.n_names = opt->n_names;
+    P.names = S.names.as<const nfagg_intf_name>(); P.esc = S.flp_esc.as<const uint8_t>(); P.n_names = opt->n_names;
     P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
     return NFAGG_OK;
 }
@@ -414,26 +414,26 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     FlpParams P{};
     uint32_t* rows;
     if ((rc = stage_flp(h, n, opt, &P, &rows)) != NFAGG_OK) return rc;
-    uint32_t* counter = (uint32_t*)h->enc.flp_n_deferred.p;
+    uint32_t* counter = h->enc.flp_n_deferred.as<uint32_t>();
     TlsDev T{};
     if (tls) {
-        T.ids = (const uint16_t*)tls->names->d_mem;
-        T.rows = (const uint8_t*)tls->names->d_mem + tls->names->ids.size() * sizeof(uint16_t);
+        T.ids = tls->names->d_mem.as<const uint16_t>();
+        T.rows = tls->names->d_mem.as<const uint8_t>() + tls->names->ids.size() * sizeof(uint16_t);
         for (uint32_t k = 0; k < kTlsKinds; k++) T.n[k] = tls->names->n[k];
     }
     const PbFeat* Fp = (feat || ne) ? &F : nullptr;                   // neither: the plain line
     const TlsDev* Tp = tls ? &T : nullptr;
     if (k8s) {
-        if ((rc = ensure_buf(h, h->enc.k8s_rows, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-        uint32_t* k8s_rows = (uint32_t*)h->enc.k8s_rows.p;
+        if ((rc = h->enc.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+        uint32_t* k8s_rows = h->enc.k8s_rows.as<uint32_t>();
         const K8sDev K = k8s_dev(k8s);
         hipError_t e = launch_k8s_resolve(d_records, n, K, k8s_rows, h->stream);
         if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
         if (net) {
-            if ((rc = ensure_buf(h, h->enc.net_rows, n * sizeof(uint2))) != NFAGG_OK) return rc;
-            const uint2* net_rows = (const uint2*)h->enc.net_rows.p;
+            if ((rc = h->enc.net_rows.ensure(h, n * sizeof(uint2))) != NFAGG_OK) return rc;
+            const uint2* net_rows = h->enc.net_rows.as<const uint2>();
             const NetDev N = net_dev(net);
-            e = launch_net_resolve(d_records, n, N, k8s_rows, (const uint32_t*)k8s->d_host_ids, K.n_rows, net_reporter(k8s, opt), (uint2*)h->enc.net_rows.p,
+            e = launch_net_resolve(d_records, n, N, k8s_rows, k8s->d_host_ids.as<const uint32_t>(), K.n_rows, net_reporter(k8s, opt), h->enc.net_rows.as<uint2>(),
                                    h->stream);
             if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
             if (tls->with_conn) {
@@ -489,14 +489,14 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
             if (dtls.with_conn) {                                         // the hash ids, uploaded
                 dtls.hash_ids = nullptr;
                 if (n) {
-                    int rc2 = ensure_buf(h, h->enc.conn_ids, n * sizeof(uint64_t));
+                    int rc2 = h->enc.conn_ids.ensure(h, n * sizeof(uint64_t));
                     if (rc2 != NFAGG_OK) return rc2;
                     HIP_TRY(h, hipMemcpyAsync(h->enc.conn_ids.p, tls->hash_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-                    dtls.hash_ids = (const uint64_t*)h->enc.conn_ids.p;
+                    dtls.hash_ids = h->enc.conn_ids.as<const uint64_t>();
                 }
             }
             return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, tls ? &dtls : nullptr, opt, d_out, out_cap, d_offsets,
-                                          deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
+                                          deferred ? h->enc.out_extra[0].as<uint8_t>() : nullptr, n_deferred, out_bytes); });
 }
 
 int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
@@ -715,8 +715,8 @@ int nfagg_conn_layout_create(nfagg_handle* h, const nfagg_conn_field* fields, si
             memcpy(img.data(), t->cols.data(), cols_bytes);
             memcpy(img.data() + cols_bytes, t->blob.data(), t->blob.size());
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_mem, img.size()));
-            HIP_TRY(h, hipMemcpy(t->d_mem, img.data(), img.size(), hipMemcpyHostToDevice));
+            HIP_TRY(h, t->d_mem.alloc(img.size()));
+            HIP_TRY(h, hipMemcpy(t->d_mem.p, img.data(), img.size(), hipMemcpyHostToDevice));
             return NFAGG_OK;
         };
         const int rc = up();
@@ -726,15 +726,7 @@ int nfagg_conn_layout_create(nfagg_handle* h, const nfagg_conn_field* fields, si
     return NFAGG_OK;
 }
 
-void nfagg_conn_layout_destroy(nfagg_conn_layout* t) {
-    if (!t) return;
-    if (t->h && t->d_mem) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        (void)hipFree(t->d_mem);
-    }
-    delete t;
-}
+void nfagg_conn_layout_destroy(nfagg_conn_layout* t) { destroy_on_handle(t); }
 
 uint32_t nfagg_conn_layout_columns(const nfagg_conn_layout* t) { return t ? (uint32_t)t->cols.size() : 0u; }
 uint32_t nfagg_conn_layout_max_line(const nfagg_conn_layout* t) { return t ? t->max_line : 0u; }
@@ -763,28 +755,28 @@ int nfagg_encode_conn_json_device(nfagg_handle* h, const void* d_carriers, const
     bool done;
     if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, nullptr, 0, &done)) != NFAGG_OK || done) return rc;
     auto& S = h->enc;
-    if ((rc = ensure_buf(h, S.flp_rows, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.flp_n_deferred, 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(uint2))) != NFAGG_OK) return rc;
+    if ((rc = S.flp_rows.ensure(h, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.flp_n_deferred.ensure(h, 16)) != NFAGG_OK) return rc;
+    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.net_rows.ensure(h, n * sizeof(uint2))) != NFAGG_OK) return rc;
     HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
-    uint32_t* lens = (uint32_t*)S.flp_rows.p;
-    uint32_t* k8s_rows = (uint32_t*)S.k8s_rows.p;
+    uint32_t* lens = S.flp_rows.as<uint32_t>();
+    uint32_t* k8s_rows = S.k8s_rows.as<uint32_t>();
     const K8sDev K = k8s_dev(k8s);
     const NetDev N = net_dev(net);
-    const ConnLayoutDev L{(const ConnCol*)layout->d_mem, (const uint8_t*)layout->d_mem + layout->cols.size() * sizeof(ConnCol), (uint32_t)layout->cols.size()};
+    const ConnLayoutDev L{layout->d_mem.as<const ConnCol>(), layout->d_mem.as<const uint8_t>() + layout->cols.size() * sizeof(ConnCol), (uint32_t)layout->cols.size()};
     // the carriers are flow records: both joins run on them unchanged. A conversation has no AgentIP, so no reporter and no direction.
     hipError_t e = launch_k8s_resolve(d_carriers, n, K, k8s_rows, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
-    e = launch_net_resolve(d_carriers, n, N, k8s_rows, (const uint32_t*)k8s->d_host_ids, K.n_rows, kNetNoHost, (uint2*)S.net_rows.p, h->stream);
+    e = launch_net_resolve(d_carriers, n, N, k8s_rows, k8s->d_host_ids.as<const uint32_t>(), K.n_rows, kNetNoHost, S.net_rows.as<uint2>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
     size_t deferred_unused;
     return encode_two_pass(h, n, "conversation JSON", "write", d_out, out_cap, out_bytes, n_deferred ? n_deferred : &deferred_unused,
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-            return launch_conn_json_size(d_carriers, d_values, n, L, K, N, k8s_rows, (const uint2*)S.net_rows.p, lens, local_off, block_sum, block_base,
-                                         (uint32_t*)S.flp_n_deferred.p, h->stream); },
+            return launch_conn_json_size(d_carriers, d_values, n, L, K, N, k8s_rows, S.net_rows.as<const uint2>(), lens, local_off, block_sum, block_base,
+                                         S.flp_n_deferred.as<uint32_t>(), h->stream); },
         [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-            return launch_conn_json_write(d_carriers, d_values, n, L, K, N, k8s_rows, (const uint2*)S.net_rows.p, lens, local_off, block_base, d_out,
+            return launch_conn_json_write(d_carriers, d_values, n, L, K, N, k8s_rows, S.net_rows.as<const uint2>(), lens, local_off, block_base, d_out,
                                           d_line_offsets, d_deferred, h->stream); });
 }
 
@@ -794,11 +786,11 @@ int nfagg_encode_conn_json(nfagg_handle* h, const void* carriers, const nfagg_co
     if (!h || !layout || !k8s || !net || !out_bytes || !line_offsets || (n && (!carriers || !values))) return fail(h, NFAGG_EINVAL, "null argument");
     return encode_staged(h, carriers, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
         [&](const void* d_carriers, void* d_out, uint64_t* d_offsets) {
-            int rc = ensure_buf(h, h->enc.conn_out, n * sizeof(nfagg_conn_values) + 16);
+            int rc = h->enc.conn_out.ensure(h, n * sizeof(nfagg_conn_values) + 16);
             if (rc != NFAGG_OK) return rc;
             if (n) HIP_TRY(h, hipMemcpyAsync(h->enc.conn_out.p, values, n * sizeof(nfagg_conn_values), hipMemcpyHostToDevice, h->stream));
-            return nfagg_encode_conn_json_device(h, d_carriers, (const nfagg_conn_values*)h->enc.conn_out.p, n, layout, k8s, net, d_out, out_cap, d_offsets,
-                                                 deferred ? (uint8_t*)h->enc.out_extra[0].p : nullptr, n_deferred, out_bytes); });
+            return nfagg_encode_conn_json_device(h, d_carriers, h->enc.conn_out.as<const nfagg_conn_values>(), n, layout, k8s, net, d_out, out_cap, d_offsets,
+                                                 deferred ? h->enc.out_extra[0].as<uint8_t>() : nullptr, n_deferred, out_bytes); });
 }
 
 }  // extern "C"

@@ -18,9 +18,8 @@ struct nfagg_filter {
     const nfagg_net_table* net = nullptr;
     FilterProg prog{};
     std::vector<uint8_t> truth;
-    void* d_prog = nullptr;                    // the program, then the truth bytes from kTruthOff on
-    void* d_samp = nullptr;                    // u32[n], and one counter in front
-    size_t d_samp_cap = 0;
+    DevBuf d_prog;                             // the program, then the truth bytes from kTruthOff on
+    DevBuf d_samp;                             // u32[n], and one counter in front
 };
 
 namespace {
@@ -101,7 +100,7 @@ int compile_atom(nfagg_handle* h, uint32_t k, const nfagg_filter_atom& a, const 
     }
 }
 
-int grow_samp(nfagg_handle* h, nfagg_filter* f, size_t n) { return ensure_bytes(h, &f->d_samp, &f->d_samp_cap, 16 + (n + 4) * sizeof(uint32_t)); }
+int grow_samp(nfagg_handle* h, nfagg_filter* f, size_t n) { return f->d_samp.ensure(h, 16 + (n + 4) * sizeof(uint32_t)); }
 
 }  // namespace
 
@@ -170,8 +169,8 @@ int nfagg_filter_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const
             memcpy(img.data(), &f->prog, sizeof(FilterProg));
             if (!f->truth.empty()) memcpy(img.data() + kTruthOff, f->truth.data(), f->truth.size());
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&f->d_prog, img.size()));
-            HIP_TRY(h, hipMemcpy(f->d_prog, img.data(), img.size(), hipMemcpyHostToDevice));
+            HIP_TRY(h, f->d_prog.alloc(img.size()));
+            HIP_TRY(h, hipMemcpy(f->d_prog.p, img.data(), img.size(), hipMemcpyHostToDevice));
             return NFAGG_OK;
         };
         rc = up();
@@ -181,16 +180,7 @@ int nfagg_filter_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const
     return NFAGG_OK;
 }
 
-void nfagg_filter_destroy(nfagg_filter* f) {
-    if (!f) return;
-    if (f->h && (f->d_prog || f->d_samp)) {
-        (void)hipSetDevice(f->h->device);
-        (void)hipStreamSynchronize(f->h->stream);
-        if (f->d_prog) (void)hipFree(f->d_prog);
-        if (f->d_samp) (void)hipFree(f->d_samp);
-    }
-    delete f;
-}
+void nfagg_filter_destroy(nfagg_filter* f) { destroy_on_handle(f); }
 
 int nfagg_filter_apply_device(nfagg_handle* h, const nfagg_filter* filter, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                               const uint32_t* d_k8s_rows, const nfagg_net_row* d_net_rows, const nfagg_flp_options* opt, uint64_t seed,
@@ -223,21 +213,21 @@ int nfagg_filter_apply_device(nfagg_handle* h, const nfagg_filter* filter, const
     nfagg_filter* f = const_cast<nfagg_filter*>(filter);          // the scratch alone
     const size_t blocks = (n + kFilterScanBlock - 1) / kFilterScanBlock;
     int rc;
-    if ((rc = ensure_buf(h, S.local_off, (n + 1) * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.block_sum, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.block_base, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    if ((rc = S.local_off.ensure(h, (n + 1) * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.block_sum.ensure(h, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.block_base.ensure(h, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
     if ((rc = grow_samp(h, f, n)) != NFAGG_OK) return rc;
-    uint32_t* d_counter = (uint32_t*)f->d_samp;
+    uint32_t* d_counter = f->d_samp.as<uint32_t>();
     uint32_t* d_samp = d_counter + 4;
     HIP_TRY(h, hipMemsetAsync(d_counter, 0, 16, h->stream));
     const K8sDev K = (P.need & kFilterNeedK8sRow) ? k8s_dev(filter->k8s) : K8sDev{};
-    hipError_t e = launch_filter_eval(d_records, n, (const FilterProg*)f->d_prog, (const uint8_t*)f->d_prog + kTruthOff, F, d_k8s_rows, K,
-                                      (const uint2*)d_net_rows, clk, seed, first_index, d_keep, d_rule, d_samp, (uint32_t*)S.local_off.p,
-                                      (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p, d_counter, h->stream);
+    hipError_t e = launch_filter_eval(d_records, n, f->d_prog.as<const FilterProg>(), f->d_prog.as<const uint8_t>() + kTruthOff, F, d_k8s_rows, K,
+                                      (const uint2*)d_net_rows, clk, seed, first_index, d_keep, d_rule, d_samp, S.local_off.as<uint32_t>(),
+                                      S.block_sum.as<uint32_t>(), S.block_base.as<uint64_t>(), d_counter, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "filter eval launch failed: %s", hipGetErrorString(e));
     uint64_t total = 0;
     uint32_t deferred = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, (const uint64_t*)S.block_base.p + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&total, S.block_base.as<const uint64_t>() + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(&deferred, d_counter, sizeof deferred, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *n_kept = (size_t)total;
@@ -245,7 +235,7 @@ int nfagg_filter_apply_device(nfagg_handle* h, const nfagg_filter* filter, const
     if (!d_kept_idx && !d_out_records) return NFAGG_OK;
     if (total > cap) return NFAGG_TRUNCATED;
     if (total) {
-        e = launch_filter_compact(d_records, n, d_samp, (const uint32_t*)S.local_off.p, (const uint64_t*)S.block_base.p, d_kept_idx, d_out_records, h->stream);
+        e = launch_filter_compact(d_records, n, d_samp, S.local_off.as<const uint32_t>(), S.block_base.as<const uint64_t>(), d_kept_idx, d_out_records, h->stream);
         if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "filter compact launch failed: %s", hipGetErrorString(e));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
@@ -264,13 +254,13 @@ int nfagg_filter_apply(nfagg_handle* h, const nfagg_filter* filter, const void* 
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t room = cap < n ? cap : n;              // never more kept than flows
     int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out_extra[0], n + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out_extra[1], n + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out_offsets, room * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if (out_records && (rc = ensure_buf(h, S.out, room * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.net_rows.ensure(h, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.out_extra[0].ensure(h, n + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.out_extra[1].ensure(h, n + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.out_offsets.ensure(h, room * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if (out_records && (rc = S.out.ensure(h, room * kRecordBytes + 16)) != NFAGG_OK) return rc;
     nfagg_pb_features dfeat{};
     if (n) {
         HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
@@ -279,9 +269,9 @@ int nfagg_filter_apply(nfagg_handle* h, const nfagg_filter* filter, const void* 
         if (features && (rc = stage_pb_features(h, features, n, &dfeat)) != NFAGG_OK) return rc;
     }
     const bool compact = kept_idx || out_records;
-    rc = nfagg_filter_apply_device(h, filter, S.in_records.p, n, (features && n) ? &dfeat : nullptr, k8s_rows ? (const uint32_t*)S.k8s_rows.p : nullptr,
-                                   net_rows ? (const nfagg_net_row*)S.net_rows.p : nullptr, opt, seed, first_index, (uint8_t*)S.out_extra[0].p,
-                                   (uint8_t*)S.out_extra[1].p, compact ? (uint32_t*)S.out_offsets.p : nullptr, out_records ? S.out.p : nullptr, room,
+    rc = nfagg_filter_apply_device(h, filter, S.in_records.p, n, (features && n) ? &dfeat : nullptr, k8s_rows ? S.k8s_rows.as<const uint32_t>() : nullptr,
+                                   net_rows ? S.net_rows.as<const nfagg_net_row>() : nullptr, opt, seed, first_index, S.out_extra[0].as<uint8_t>(),
+                                   S.out_extra[1].as<uint8_t>(), compact ? S.out_offsets.as<uint32_t>() : nullptr, out_records ? S.out.p : nullptr, room,
                                    n_kept, n_deferred);
     if (rc != NFAGG_OK && rc != NFAGG_TRUNCATED) return rc;
     if (n && keep) HIP_TRY(h, hipMemcpyAsync(keep, S.out_extra[0].p, n, hipMemcpyDeviceToHost, h->stream));
@@ -327,12 +317,12 @@ int nfagg_gather(nfagg_handle* h, const void* src, size_t n_src, size_t elem_byt
     HIP_TRY(h, hipSetDevice(h->device));
     if (!n_kept) return NFAGG_OK;
     int rc;
-    if ((rc = ensure_buf(h, S.in_records, n_src * elem_bytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out_offsets, n_kept * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.out, n_kept * elem_bytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.in_records.ensure(h, n_src * elem_bytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.out_offsets.ensure(h, n_kept * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.out.ensure(h, n_kept * elem_bytes + 16)) != NFAGG_OK) return rc;
     if (n_src) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, src, n_src * elem_bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(S.out_offsets.p, kept_idx, n_kept * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    if ((rc = nfagg_gather_device(h, S.in_records.p, n_src, elem_bytes, (const uint32_t*)S.out_offsets.p, n_kept, S.out.p)) != NFAGG_OK) return rc;
+    if ((rc = nfagg_gather_device(h, S.in_records.p, n_src, elem_bytes, S.out_offsets.as<const uint32_t>(), n_kept, S.out.p)) != NFAGG_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(dst, S.out.p, n_kept * elem_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;

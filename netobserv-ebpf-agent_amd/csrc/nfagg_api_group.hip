@@ -1,5 +1,5 @@
-// nfagg_group.inc — the multi-GPU group (included at the end of nfagg_api.hip: it drives the members through the
-// handle's internals). include/nfagg.h documents the entry points.
+// nfagg_api_group.hip — the multi-GPU group: it drives the members through the handle's internals (nfagg_api_core.h).
+// include/nfagg.h documents the entry points.
 //
 // The Go agent is ONE process (pkg/agent/agent.go:387-442 builds one pipeline around one Accounter, constructed at
 // agent.go:208-212), so N GPUs are driven from one process: every member is an ordinary nfagg_handle owning the flows
@@ -13,11 +13,22 @@
 // Capacity: CACHE_MAX_FLOWS is divided evenly, each shard holds at most ceil(max_entries / N) flows. A record whose new
 // key finds ITS shard full stops the group exactly there (NFAGG_FULL + consumed, as account.go:85-94 stops at the record
 // that finds the map full), and the caller evicts the whole group — the reference evicts its whole map.
+#include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <rccl/rccl.h>
+#include <stdarg.h>
+#include <stdio.h>
 #include <atomic>
 #include <mutex>
+#include <new>
+#include <set>
+#include <string>
 #include <thread>
+#include <vector>
+
+#include "nfagg_api_core.h"
+
+using namespace nfagg;
 
 namespace {
 
@@ -64,17 +75,16 @@ struct nfagg_group {
     bool distinct = true;             // every member on its own device: RCCL. All on ONE device (test rig): local kernels.
     RcclApi rccl;
     std::vector<ncclComm_t> comm;
-    struct Dst { void* d_bucket = nullptr; size_t cap = 0; hipEvent_t arrived = nullptr, folded = nullptr; };
+    struct Dst { DevBuf bucket; Event arrived, folded; };     // bucket: on the OWNER's device (freed with that device current)
     struct Src {                      // member i as SOURCE of a routed chunk: partition scratch on its device, its own stream for the
                                       // partition and the peer copies (the member's fold stream is busy with the buckets it owns), and
                                       // per owner j the landing area on j's device + the events that order its reuse. Everything
                                       // here is touched by ONE host thread at a time (the one feeding member i), outside fold_mu.
-        void* d_out = nullptr; size_t out_cap = 0;
-        void* d_orig = nullptr; size_t orig_cap = 0;
-        void* d_scratch = nullptr; size_t scratch_cap = 0;
-        void* d_count = nullptr; size_t count_cap = 0;     // [0..64) bucket sizes, [64..128) prefix counts
-        uint64_t* h_count = nullptr;                       // pinned, 128 words
-        hipStream_t pstream = nullptr;
+        DevBuf out, orig, scratch;
+        DevBuf count;                                      // [0..64) bucket sizes, [64..128) prefix counts
+        PinnedBuf count_mirror;
+        uint64_t* h_count = nullptr;                       // = count_mirror, 128 words
+        Stream pstream;
         std::vector<Dst> to;                               // [owner]
     };
     std::vector<Src> src;
@@ -96,7 +106,7 @@ struct nfagg_group {
     uint64_t consolidations = 0;
     bool merged = false;              // the members' slots have been merged into their owners; only the eviction may follow
     struct Raw {                      // member i's live flows as partials grouped by owner, on its own device, at the eviction
-        void* d = nullptr; size_t cap = 0;
+        DevBuf d;
         uint64_t counts[64] = {}, off[64] = {};
         uint64_t owned = 0;
     };
@@ -111,7 +121,7 @@ namespace {
 int gfail(nfagg_group* g, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (g) { std::lock_guard<std::mutex> lk(g->err_mu); g->err = buf; } else g_create_error = buf;
+    if (g) { std::lock_guard<std::mutex> lk(g->err_mu); g->err = buf; } else return fail(nullptr, code, "%s", buf);
     return code;
 }
 int group_refuse_failed(nfagg_group* g) {
@@ -126,13 +136,10 @@ int member_fail(nfagg_group* g, uint32_t j, int rc) { return gfail(g, rc, "membe
     do { hipError_t e_ = (expr);                                                                                 \
          if (e_ != hipSuccess) return gfail((g), NFAGG_EDEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
-int g_ensure(nfagg_group* g, void** p, size_t* cap, size_t need) {
-    if (*cap >= need) return NFAGG_OK;
-    if (*p) { hipFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = need + need / 8 + 4096;
-    if (hipMalloc(p, want) != hipSuccess) return gfail(g, NFAGG_ENOMEM, "hipMalloc(%zu) failed", want);
-    *cap = want;
-    return NFAGG_OK;
+// Grow-only scratch of the group on member j's device (current): the member reports, the group passes it on.
+int g_ensure(nfagg_group* g, uint32_t j, DevBuf& b, size_t need) {
+    const int rc = b.ensure(g->m[j], need);
+    return rc == NFAGG_OK ? rc : member_fail(g, j, rc);
 }
 
 // Fold the first cnt[j] records of every member's bucket; all members optimistic when any of them might cross its share.
@@ -237,9 +244,9 @@ int group_local_merge(nfagg_group* g) {
         for (uint32_t o = 0; o < 64; o++) { R.counts[o] = 0; R.off[o] = 0; }
         if (N == 1) continue;
         if ((rc = refresh_counters(h)) != NFAGG_OK) return member_fail(g, i, rc);
-        if ((rc = g_ensure(g, &R.d, &R.cap, (size_t)h->h_ctr->n_live * pbytes + 64)) != NFAGG_OK) return rc;
+        if ((rc = g_ensure(g, i, R.d, (size_t)h->h_ctr->n_live * pbytes + 64)) != NFAGG_OK) return rc;
         size_t n_exp = 0;
-        if ((rc = partials_export_core(h, N, i, R.d, (size_t)h->h_ctr->n_live, R.counts, &n_exp)) != NFAGG_OK) return member_fail(g, i, rc);
+        if ((rc = partials_export_core(h, N, i, R.d.p, (size_t)h->h_ctr->n_live, R.counts, &n_exp)) != NFAGG_OK) return member_fail(g, i, rc);
         uint64_t at = 0;
         for (uint32_t o = 0; o < N; o++) { R.off[o] = at; at += R.counts[o]; }
     }
@@ -248,7 +255,7 @@ int group_local_merge(nfagg_group* g) {
             if (i == j || g->dev[i] == g->dev[j] || !g->raw[i].counts[j]) continue;
             G_TRY(g, hipSetDevice(g->dev[j]));
             nfagg_group::Dst& P = g->peer[(size_t)j * N + i];
-            if ((rc = g_ensure(g, &P.d_bucket, &P.cap, (size_t)g->raw[i].counts[j] * pbytes + 64)) != NFAGG_OK) return rc;
+            if ((rc = g_ensure(g, j, P.bucket, (size_t)g->raw[i].counts[j] * pbytes + 64)) != NFAGG_OK) return rc;
         }
     // ---- stage B: the tables change from here on
     auto merge_all = [&]() -> int {
@@ -260,11 +267,11 @@ int group_local_merge(nfagg_group* g) {
                 if (cnt == 0) continue;
                 nfagg_handle* h = g->m[j];
                 G_TRY(g, hipSetDevice(g->dev[j]));
-                const char* at = (const char*)R.d + R.off[j] * pbytes;      // complete: the export synchronised
+                const char* at = R.d.as<const char>() + R.off[j] * pbytes;      // complete: the export synchronised
                 if (g->dev[i] != g->dev[j]) {
                     nfagg_group::Dst& P = g->peer[(size_t)j * N + i];
-                    G_TRY(g, hipMemcpyPeerAsync(P.d_bucket, g->dev[j], at, g->dev[i], (size_t)cnt * pbytes, h->stream));
-                    at = (const char*)P.d_bucket;
+                    G_TRY(g, hipMemcpyPeerAsync(P.bucket.p, g->dev[j], at, g->dev[i], (size_t)cnt * pbytes, h->stream));
+                    at = P.bucket.as<const char>();
                 }
                 if ((rc = partials_merge_core(h, N, j, at, (size_t)cnt)) != NFAGG_OK) return member_fail(g, j, rc);
             }
@@ -295,9 +302,9 @@ int group_consolidate(nfagg_group* g) {
         G_TRY(g, hipSetDevice(g->dev[i]));
         if (h->must_evict) return gfail(g, NFAGG_ESTATE, "member %u has an eviction on full pending", i);
         if ((rc = refresh_counters(h)) != NFAGG_OK) return member_fail(g, i, rc);
-        if ((rc = g_ensure(g, &R.d, &R.cap, (size_t)h->h_ctr->n_live * kPartialBytes + 64)) != NFAGG_OK) return rc;
+        if ((rc = g_ensure(g, i, R.d, (size_t)h->h_ctr->n_live * kPartialBytes + 64)) != NFAGG_OK) return rc;
         size_t n_exp = 0;
-        if ((rc = partials_export_core(h, N, NFAGG_SHARD_NONE, R.d, (size_t)h->h_ctr->n_live, R.counts, &n_exp)) != NFAGG_OK) return member_fail(g, i, rc);
+        if ((rc = partials_export_core(h, N, NFAGG_SHARD_NONE, R.d.p, (size_t)h->h_ctr->n_live, R.counts, &n_exp)) != NFAGG_OK) return member_fail(g, i, rc);
         uint64_t at = 0;
         for (uint32_t o = 0; o < N; o++) { R.off[o] = at; at += R.counts[o]; }
     }
@@ -306,7 +313,7 @@ int group_consolidate(nfagg_group* g) {
             if (g->dev[i] == g->dev[j] || !g->raw[i].counts[j]) continue;
             G_TRY(g, hipSetDevice(g->dev[j]));
             nfagg_group::Dst& P = g->peer[(size_t)j * N + i];
-            if ((rc = g_ensure(g, &P.d_bucket, &P.cap, (size_t)g->raw[i].counts[j] * kPartialBytes + 64)) != NFAGG_OK) return rc;
+            if ((rc = g_ensure(g, j, P.bucket, (size_t)g->raw[i].counts[j] * kPartialBytes + 64)) != NFAGG_OK) return rc;
         }
     const uint64_t next_seq = g->seq.load();
     auto restart = [&]() -> int {                                  // stage B: the tables change
@@ -319,11 +326,11 @@ int group_consolidate(nfagg_group* g) {
                 if (cnt == 0) continue;
                 nfagg_handle* h = g->m[j];
                 G_TRY(g, hipSetDevice(g->dev[j]));
-                const char* at = (const char*)R.d + R.off[j] * kPartialBytes;
+                const char* at = R.d.as<const char>() + R.off[j] * kPartialBytes;
                 if (g->dev[i] != g->dev[j]) {
                     nfagg_group::Dst& P = g->peer[(size_t)j * N + i];
-                    G_TRY(g, hipMemcpyPeerAsync(P.d_bucket, g->dev[j], at, g->dev[i], (size_t)cnt * kPartialBytes, h->stream));
-                    at = (const char*)P.d_bucket;
+                    G_TRY(g, hipMemcpyPeerAsync(P.bucket.p, g->dev[j], at, g->dev[i], (size_t)cnt * kPartialBytes, h->stream));
+                    at = P.bucket.as<const char>();
                 }
                 if ((rc = partials_merge_core(h, N, j, at, (size_t)cnt)) != NFAGG_OK) return member_fail(g, j, rc);
             }
@@ -377,12 +384,12 @@ int group_ingest_device_core(nfagg_group* g, uint32_t s, const void* d_records, 
     // ---- partition on the source device (buffers are reused: wait until the previous call's consumers are done)
     G_TRY(g, hipSetDevice(g->dev[s]));
     for (uint32_t j = 0; j < N; j++) G_TRY(g, hipStreamWaitEvent(S.pstream, S.to[j].folded, 0));
-    if ((rc = g_ensure(g, &S.d_out, &S.out_cap, n * kRecordBytes)) != NFAGG_OK) return rc;
-    if ((rc = g_ensure(g, &S.d_orig, &S.orig_cap, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = g_ensure(g, &S.d_scratch, &S.scratch_cap, partition_scratch_bytes(n, N))) != NFAGG_OK) return rc;
-    if ((rc = g_ensure(g, &S.d_count, &S.count_cap, 128 * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    uint64_t* d_count = (uint64_t*)S.d_count;
-    hipError_t e = launch_partition(d_records, n, N, S.d_out, (uint32_t*)S.d_orig, d_count, S.d_scratch, S.pstream);
+    if ((rc = g_ensure(g, s, S.out, n * kRecordBytes)) != NFAGG_OK) return rc;
+    if ((rc = g_ensure(g, s, S.orig, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = g_ensure(g, s, S.scratch, partition_scratch_bytes(n, N))) != NFAGG_OK) return rc;
+    if ((rc = g_ensure(g, s, S.count, 128 * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    uint64_t* d_count = S.count.as<uint64_t>();
+    hipError_t e = launch_partition(d_records, n, N, S.out.p, S.orig.as<uint32_t>(), d_count, S.scratch.p, S.pstream);
     if (e != hipSuccess) return gfail(g, NFAGG_EDEVICE, "partition launch failed: %s", hipGetErrorString(e));
     G_TRY(g, hipMemcpyAsync(S.h_count, d_count, N * sizeof(uint64_t), hipMemcpyDeviceToHost, S.pstream));
     G_TRY(g, hipStreamSynchronize(S.pstream));                 // the partition of THIS chunk only: nobody's folds are waited for
@@ -394,17 +401,17 @@ int group_ingest_device_core(nfagg_group* g, uint32_t s, const void* d_records, 
     std::vector<const void*> bucket(N);
     std::vector<char> remote(N, 0);
     for (uint32_t j = 0; j < N; j++) {
-        const char* at = (const char*)S.d_out + off[j] * kRecordBytes;
+        const char* at = S.out.as<const char>() + off[j] * kRecordBytes;
         if (g->dev[j] == g->dev[s]) { bucket[j] = at; continue; }
         if (cnt[j]) {
             G_TRY(g, hipSetDevice(g->dev[j]));
-            if ((rc = g_ensure(g, &S.to[j].d_bucket, &S.to[j].cap, cnt[j] * kRecordBytes)) != NFAGG_OK) return rc;
+            if ((rc = g_ensure(g, j, S.to[j].bucket, cnt[j] * kRecordBytes)) != NFAGG_OK) return rc;
             G_TRY(g, hipSetDevice(g->dev[s]));
-            G_TRY(g, hipMemcpyPeerAsync(S.to[j].d_bucket, g->dev[j], at, g->dev[s], cnt[j] * kRecordBytes, S.pstream));
+            G_TRY(g, hipMemcpyPeerAsync(S.to[j].bucket.p, g->dev[j], at, g->dev[s], cnt[j] * kRecordBytes, S.pstream));
             G_TRY(g, hipEventRecord(S.to[j].arrived, S.pstream));
             remote[j] = 1;
         }
-        bucket[j] = S.to[j].d_bucket;
+        bucket[j] = S.to[j].bucket.p;
     }
     // ---- from here on the members' tables: one call at a time
     std::lock_guard<std::mutex> fold_lock(g->fold_mu);
@@ -448,7 +455,7 @@ int group_ingest_device_core(nfagg_group* g, uint32_t s, const void* d_records, 
             for (uint32_t j = 0; j < N; j++) {
                 if (!hit[j]) continue;
                 uint32_t orig = 0;
-                G_TRY(g, hipMemcpyAsync(&orig, (const uint32_t*)S.d_orig + off[j] + stop[j], sizeof orig, hipMemcpyDeviceToHost, S.pstream));
+                G_TRY(g, hipMemcpyAsync(&orig, S.orig.as<const uint32_t>() + off[j] + stop[j], sizeof orig, hipMemcpyDeviceToHost, S.pstream));
                 G_TRY(g, hipStreamSynchronize(S.pstream));
                 if (orig < next) next = orig;
             }
@@ -456,7 +463,7 @@ int group_ingest_device_core(nfagg_group* g, uint32_t s, const void* d_records, 
         prefix = next;
         // bucket prefixes that make up records [0, prefix) of the call
         G_TRY(g, hipSetDevice(g->dev[s]));
-        e = launch_partition_prefix_counts((const uint32_t*)S.d_orig, d_count, N, prefix, d_count + 64, S.pstream);
+        e = launch_partition_prefix_counts(S.orig.as<const uint32_t>(), d_count, N, prefix, d_count + 64, S.pstream);
         if (e != hipSuccess) return gfail(g, NFAGG_EDEVICE, "prefix count launch failed: %s", hipGetErrorString(e));
         G_TRY(g, hipMemcpyAsync(S.h_count + 64, d_count + 64, N * sizeof(uint64_t), hipMemcpyDeviceToHost, S.pstream));
         G_TRY(g, hipStreamSynchronize(S.pstream));
@@ -522,13 +529,13 @@ int nfagg_group_create(const nfagg_config* cfg_in, const int32_t* devices, uint3
         hipSetDevice(devices[j]);
         nfagg_group::Src& S = g->src[j];
         S.to.resize(n_devices);
-        bool ok = hipStreamCreateWithFlags(&S.pstream, hipStreamNonBlocking) == hipSuccess &&
-                  hipHostMalloc((void**)&S.h_count, 128 * sizeof(uint64_t), hipHostMallocDefault) == hipSuccess;
+        bool ok = S.pstream.create() == hipSuccess && S.count_mirror.alloc(128 * sizeof(uint64_t)) == hipSuccess;
+        S.h_count = S.count_mirror.as<uint64_t>();
         // an event belongs to the device that is current when it is created and can only be recorded on a stream of that device
         // (any stream may WAIT for it): `arrived` is recorded on this source's stream, `folded` on owner k's fold stream
         for (uint32_t k = 0; ok && k < n_devices; k++) {
-            ok = hipSetDevice(devices[j]) == hipSuccess && hipEventCreateWithFlags(&S.to[k].arrived, hipEventDisableTiming) == hipSuccess &&
-                 hipSetDevice(devices[k]) == hipSuccess && hipEventCreateWithFlags(&S.to[k].folded, hipEventDisableTiming) == hipSuccess;
+            ok = hipSetDevice(devices[j]) == hipSuccess && S.to[k].arrived.create() == hipSuccess &&
+                 hipSetDevice(devices[k]) == hipSuccess && S.to[k].folded.create() == hipSuccess;
         }
         hipSetDevice(devices[j]);
         if (!ok) {
@@ -567,34 +574,16 @@ void nfagg_group_destroy(nfagg_group* g) {
     if (!g) return;
     for (uint32_t j = 0; j < g->m.size(); j++) { hipSetDevice(g->dev[j]); hipStreamSynchronize(g->m[j]->stream); }
     for (auto c : g->comm) if (c) g->rccl.CommDestroy(c);
-    for (uint32_t j = 0; j < g->src.size(); j++) {
-        if (j < g->dev.size()) hipSetDevice(g->dev[j]);
-        nfagg_group::Src& S = g->src[j];
-        if (S.d_out) hipFree(S.d_out);
-        if (S.d_orig) hipFree(S.d_orig);
-        if (S.d_scratch) hipFree(S.d_scratch);
-        if (S.d_count) hipFree(S.d_count);
-        if (S.pstream) { hipStreamSynchronize(S.pstream); hipStreamDestroy(S.pstream); }
-        if (S.h_count) hipHostFree(S.h_count);
-        for (uint32_t k = 0; k < S.to.size(); k++) {
-            nfagg_group::Dst& D = S.to[k];
-            if (D.d_bucket) { if (k < g->dev.size()) hipSetDevice(g->dev[k]); hipFree(D.d_bucket); }
-            if (D.arrived) hipEventDestroy(D.arrived);
-            if (D.folded) hipEventDestroy(D.folded);
-        }
-        if (j < g->dev.size()) hipSetDevice(g->dev[j]);
-        if (j < g->raw.size()) {
-            nfagg_group::Raw& R = g->raw[j];
-            if (R.d) hipFree(R.d);
-            for (uint32_t i = 0; i < g->n && (size_t)j * g->n + i < g->peer.size(); i++)
-                if (g->peer[(size_t)j * g->n + i].d_bucket) hipFree(g->peer[(size_t)j * g->n + i].d_bucket);
-        }
-    }
+    for (auto& S : g->src) if (S.pstream) hipStreamSynchronize(S.pstream);
+    // the landing areas lie on their OWNERS' devices: each is freed with its own device current; everything else goes with the group
+    for (auto& S : g->src)
+        for (uint32_t k = 0; k < S.to.size() && k < g->dev.size(); k++) { hipSetDevice(g->dev[k]); S.to[k].bucket.reset(); }
+    for (size_t q = 0; q < g->peer.size() && q / g->n < g->dev.size(); q++) { hipSetDevice(g->dev[q / g->n]); g->peer[q].bucket.reset(); }
     for (auto h : g->m) nfagg_destroy(h);
     delete g;
 }
 
-const char* nfagg_group_last_error(const nfagg_group* g) { return g ? g->err.c_str() : g_create_error.c_str(); }
+const char* nfagg_group_last_error(const nfagg_group* g) { return g ? g->err.c_str() : nfagg_last_error(nullptr); }
 
 uint32_t nfagg_group_size(const nfagg_group* g) { return g ? g->n : 0; }
 
@@ -621,13 +610,13 @@ int nfagg_group_ingest(nfagg_group* g, const void* records, size_t n, size_t* co
         const size_t mrec = g->local ? stage_chunk(h, n - consumed, cap) : ((n - consumed) < cap ? (n - consumed) : cap);
         const int b = h->stage_next;
         G_TRY(g, hipEventSynchronize(h->stage_free[b]));
-        staged_copy(h->pinned[b], srcp + consumed * kRecordBytes, mrec * kRecordBytes, h->cfg.copy_threads);
-        G_TRY(g, hipMemcpyAsync(h->d_stage[b], h->pinned[b], mrec * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
+        staged_copy(h->pinned[b].p, srcp + consumed * kRecordBytes, mrec * kRecordBytes, h->cfg.copy_threads);
+        G_TRY(g, hipMemcpyAsync(h->d_stage[b].p, h->pinned[b].p, mrec * kRecordBytes, hipMemcpyHostToDevice, h->copy_stream));
         G_TRY(g, hipEventRecord(h->stage_up[b], h->copy_stream));
         G_TRY(g, hipStreamWaitEvent(h->stream, h->stage_up[b], 0));
         if (!g->local) G_TRY(g, hipStreamWaitEvent(g->src[s].pstream, h->stage_up[b], 0));   // routed: the partition reads the chunk on the source's own stream
         size_t c = 0;
-        rc = group_ingest_device_core(g, s, h->d_stage[b], mrec, &c);
+        rc = group_ingest_device_core(g, s, h->d_stage[b].p, mrec, &c);
         G_TRY(g, hipSetDevice(g->dev[s]));
         G_TRY(g, hipEventRecord(h->stage_free[b], h->stream));
         h->stage_next ^= 1;
@@ -720,12 +709,9 @@ int nfagg_group_evict(nfagg_group* g, int reason, void* out, size_t cap, size_t*
             nfagg_handle* h = g->m[j];
             const size_t nj = (size_t)g->raw[j].owned;
             G_TRY(g, hipSetDevice(g->dev[j]));
-            size_t capb = (size_t)h->d_evict_cap;
-            rc = ensure_bytes(h, &h->d_evict, &capb, nj * kRecordBytes + 16);
-            h->d_evict_cap = capb;
-            if (rc != NFAGG_OK) return member_fail(g, j, rc);
-            if ((rc = group_local_evict_member(g, j, reason, h->d_evict)) != NFAGG_OK) return rc;
-            if (nj) G_TRY(g, hipMemcpy((char*)out + at * kRecordBytes, h->d_evict, nj * kRecordBytes, hipMemcpyDeviceToHost));
+            if ((rc = h->d_evict.ensure(h, nj * kRecordBytes + 16)) != NFAGG_OK) return member_fail(g, j, rc);
+            if ((rc = group_local_evict_member(g, j, reason, h->d_evict.p)) != NFAGG_OK) return rc;
+            if (nj) G_TRY(g, hipMemcpy((char*)out + at * kRecordBytes, h->d_evict.p, nj * kRecordBytes, hipMemcpyDeviceToHost));
             at += nj;
         }
         group_local_epoch_done(g);

@@ -20,8 +20,8 @@ struct nfagg_netev_table {
     nfagg_handle* h = nullptr;
     std::vector<nfagg::NetevRow> rows;
     std::vector<uint8_t> blob;
-    void* d_rows = nullptr;
-    void* d_blob = nullptr;
+    nfagg::DevBuf d_rows;
+    nfagg::DevBuf d_blob;
 };
 
 // The TLS name table of nfagg_tls_names_create (nfagg_tls.h):
@@ -31,7 +31,7 @@ struct nfagg_tls_names {
     uint32_t n[nfagg::kTlsKinds] = {};
     std::vector<uint16_t> ids = std::vector<uint16_t>(nfagg::kTlsKinds * nfagg::kTlsMaxRows, 0);
     std::vector<uint8_t> rows = std::vector<uint8_t>((size_t)nfagg::kTlsKinds * nfagg::kTlsMaxRows * nfagg::kTlsRowBytes, 0);
-    void* d_mem = nullptr;        // the ids, then the rows
+    nfagg::DevBuf d_mem;        // the ids, then the rows
 };
 
 // The Kubernetes table of nfagg_k8s_table_create (nfagg_flp.h, nfagg_k8s.h): the slots, the rows and the rendered blocks, on the
@@ -51,10 +51,10 @@ struct nfagg_k8s_table {
     // Host side only.
     std::vector<uint32_t> field_ids;
     std::unordered_map<std::string, uint32_t> field_text;
-    void* d_slots = nullptr;
-    void* d_rows = nullptr;
-    void* d_blob = nullptr;
-    void* d_host_ids = nullptr;
+    nfagg::DevBuf d_slots;
+    nfagg::DevBuf d_rows;
+    nfagg::DevBuf d_blob;
+    nfagg::DevBuf d_host_ids;
 };
 
 // The table of nfagg_net_table_create (nfagg_flp.h, nfagg_net.h): the normalised CIDR list, the labels' fragments, on the host
@@ -67,7 +67,7 @@ struct nfagg_net_table {
     std::vector<nfagg::NetFrag> frags;
     std::vector<uint8_t> blob;
     size_t off_meta = 0, off_frags = 0, off_blob = 0;
-    void* d_mem = nullptr;
+    nfagg::DevBuf d_mem;
 };
 
 // The table of nfagg_metrics_table_create (nfagg_metrics.h): per grouping and side the class of every row of a Kubernetes table.
@@ -78,7 +78,7 @@ struct nfagg_metrics_table {
     uint32_t dims[nfagg::kMetMaxGroupings] = {};
     std::vector<uint32_t> cls[nfagg::kMetMaxGroupings][2];    // per row; empty: the grouping selects no field of that side
     std::vector<uint32_t> first_row[nfagg::kMetMaxGroupings][2];   // [class - 1] = the first row of that class
-    void* d_cls = nullptr;                             // the non-empty cls arrays one behind the other
+    nfagg::DevBuf d_cls;                             // the non-empty cls arrays one behind the other
     size_t d_off[nfagg::kMetMaxGroupings][2] = {};            // in words
     // nfagg_metrics_table_create_specs: the checked specs (a plain table's are its masks without values, for the content fold)
     bool has_specs = false;
@@ -92,7 +92,7 @@ struct nfagg_conn_layout {
     std::vector<nfagg::ConnCol> cols;
     std::vector<uint8_t> blob;
     uint32_t max_line = 0;
-    void* d_mem = nullptr;
+    nfagg::DevBuf d_mem;
 };
 
 namespace nfagg {

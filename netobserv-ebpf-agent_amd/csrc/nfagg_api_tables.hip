@@ -75,13 +75,13 @@ uint32_t flp_escape(const char* src, uint32_t len, uint8_t* dst) {
 }
 
 NetDev net_dev(const nfagg_net_table* t) {
-    const uint8_t* m = (const uint8_t*)t->d_mem;
+    const uint8_t* m = t->d_mem.as<const uint8_t>();
     return NetDev{(const NetCidr*)m, (const uint32_t*)(m + t->off_meta), (const NetFrag*)(m + t->off_frags), m + t->off_blob,
                   (uint32_t)t->cidrs.size(), (uint32_t)t->frags.size(), t->flags};
 }
 
 K8sDev k8s_dev(const nfagg_k8s_table* t) {
-    return K8sDev{(const K8sSlot*)t->d_slots, (const K8sRow*)t->d_rows, (const uint8_t*)t->d_blob, (uint32_t)t->slots.size() - 1,
+    return K8sDev{t->d_slots.as<const K8sSlot>(), t->d_rows.as<const K8sRow>(), t->d_blob.as<const uint8_t>(), (uint32_t)t->slots.size() - 1,
                   (uint32_t)t->rows.size(), t->has_layer ? 1u : 0u};
 }
 
@@ -238,10 +238,10 @@ int nfagg_netev_table_create(nfagg_handle* h, const nfagg_netev_entry* entries, 
     if (h) {
         auto up = [&]() -> int {
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_rows, std::max<size_t>(n, 1) * sizeof(NetevRow)));
-            HIP_TRY(h, hipMalloc(&t->d_blob, std::max<size_t>(t->blob.size(), 16)));
-            if (n) HIP_TRY(h, hipMemcpy(t->d_rows, t->rows.data(), n * sizeof(NetevRow), hipMemcpyHostToDevice));
-            if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
+            HIP_TRY(h, t->d_rows.alloc(std::max<size_t>(n, 1) * sizeof(NetevRow)));
+            HIP_TRY(h, t->d_blob.alloc(std::max<size_t>(t->blob.size(), 16)));
+            if (n) HIP_TRY(h, hipMemcpy(t->d_rows.p, t->rows.data(), n * sizeof(NetevRow), hipMemcpyHostToDevice));
+            if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob.p, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
             return NFAGG_OK;
         };
         const int rc = up();
@@ -251,16 +251,7 @@ int nfagg_netev_table_create(nfagg_handle* h, const nfagg_netev_entry* entries, 
     return NFAGG_OK;
 }
 
-void nfagg_netev_table_destroy(nfagg_netev_table* t) {
-    if (!t) return;
-    if (t->h && (t->d_rows || t->d_blob)) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        if (t->d_rows) (void)hipFree(t->d_rows);
-        if (t->d_blob) (void)hipFree(t->d_blob);
-    }
-    delete t;
-}
+void nfagg_netev_table_destroy(nfagg_netev_table* t) { destroy_on_handle(t); }
 
 int nfagg_netev_resolve_device(nfagg_handle* h, const nfagg_netev_table* table, const uint8_t* d_present,
                                const nfagg_network_events_metrics* d_network_events, const nfagg_pkt_drop_metrics* d_drops, size_t n,
@@ -275,14 +266,14 @@ int nfagg_netev_resolve_device(nfagg_handle* h, const nfagg_netev_table* table, 
     if (missing_cap > 0xffffffffull) return fail(h, NFAGG_EINVAL, "missing_cap too large");
     *n_missing = 0; *zero_missing = 0; *overflow = 0;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = ensure_buf(h, h->enc.ne_info, 16);
+    int rc = h->enc.ne_info.ensure(h, 16);
     if (rc != NFAGG_OK) return rc;
     HIP_TRY(h, hipMemsetAsync(h->enc.ne_info.p, 0, 16, h->stream));
     if (missing_cap) HIP_TRY(h, hipMemsetAsync(d_missing_set, 0, missing_cap * sizeof(uint64_t), h->stream));
     if (n) {
-        hipError_t e = launch_netev_resolve(d_present, (const uint8_t*)d_network_events, (const uint8_t*)d_drops, n, (const NetevRow*)table->d_rows,
+        hipError_t e = launch_netev_resolve(d_present, (const uint8_t*)d_network_events, (const uint8_t*)d_drops, n, table->d_rows.as<const NetevRow>(),
                                             (uint32_t)table->rows.size(), d_present_out, (uint8_t*)d_drops_out, d_rows_out, d_missing_set,
-                                            (uint32_t)missing_cap, (uint32_t*)h->enc.ne_info.p, h->stream);
+                                            (uint32_t)missing_cap, h->enc.ne_info.as<uint32_t>(), h->stream);
         if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "network-events resolve launch failed: %s", hipGetErrorString(e));
     }
     uint32_t info[4] = {};
@@ -304,16 +295,16 @@ int nfagg_netev_resolve(nfagg_handle* h, const nfagg_netev_table* table, const u
     const size_t elem[3] = {1, sizeof(nfagg_network_events_metrics), sizeof(nfagg_pkt_drop_metrics)}, out_elem[3] = {1, sizeof(nfagg_pkt_drop_metrics), 8};
     int rc;
     for (int k = 0; k < 3; k++) {
-        if ((rc = ensure_buf(h, S.ne_out[k], n * out_elem[k] + 16)) != NFAGG_OK) return rc;
+        if ((rc = S.ne_out[k].ensure(h, n * out_elem[k] + 16)) != NFAGG_OK) return rc;
         if (!src[k] || !n) continue;
-        if ((rc = ensure_buf(h, S.ne_in[k], n * elem[k] + 16)) != NFAGG_OK) return rc;
+        if ((rc = S.ne_in[k].ensure(h, n * elem[k] + 16)) != NFAGG_OK) return rc;
         HIP_TRY(h, hipMemcpyAsync(S.ne_in[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
     }
-    if ((rc = ensure_buf(h, S.ne_missing, missing_cap * sizeof(uint64_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.ne_missing.ensure(h, missing_cap * sizeof(uint64_t) + 16)) != NFAGG_OK) return rc;
     size_t stored = 0; int zero = 0;
-    rc = nfagg_netev_resolve_device(h, table, (const uint8_t*)S.ne_in[0].p, network_events ? (const nfagg_network_events_metrics*)S.ne_in[1].p : nullptr,
-                                    drops ? (const nfagg_pkt_drop_metrics*)S.ne_in[2].p : nullptr, n, (uint8_t*)S.ne_out[0].p,
-                                    (nfagg_pkt_drop_metrics*)S.ne_out[1].p, (uint16_t*)S.ne_out[2].p, missing_cap ? (uint64_t*)S.ne_missing.p : nullptr,
+    rc = nfagg_netev_resolve_device(h, table, S.ne_in[0].as<const uint8_t>(), network_events ? S.ne_in[1].as<const nfagg_network_events_metrics>() : nullptr,
+                                    drops ? S.ne_in[2].as<const nfagg_pkt_drop_metrics>() : nullptr, n, S.ne_out[0].as<uint8_t>(),
+                                    S.ne_out[1].as<nfagg_pkt_drop_metrics>(), S.ne_out[2].as<uint16_t>(), missing_cap ? S.ne_missing.as<uint64_t>() : nullptr,
                                     missing_cap, &stored, &zero, overflow);
     if (rc != NFAGG_OK) return rc;
     void* dst[3] = {present_out, drops_out, rows_out};
@@ -373,9 +364,9 @@ int nfagg_tls_names_create(nfagg_handle* h, const nfagg_tls_name_entry* entries,
         static_assert(kTlsKinds * kTlsMaxRows * sizeof(uint16_t) % 16 == 0, "the rows start 16-byte aligned");
         auto up = [&]() -> int {
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_mem, id_bytes + t->rows.size()));
-            HIP_TRY(h, hipMemcpy(t->d_mem, t->ids.data(), id_bytes, hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy((uint8_t*)t->d_mem + id_bytes, t->rows.data(), t->rows.size(), hipMemcpyHostToDevice));
+            HIP_TRY(h, t->d_mem.alloc(id_bytes + t->rows.size()));
+            HIP_TRY(h, hipMemcpy(t->d_mem.p, t->ids.data(), id_bytes, hipMemcpyHostToDevice));
+            HIP_TRY(h, hipMemcpy(t->d_mem.as<uint8_t>() + id_bytes, t->rows.data(), t->rows.size(), hipMemcpyHostToDevice));
             return NFAGG_OK;
         };
         const int rc = up();
@@ -385,15 +376,7 @@ int nfagg_tls_names_create(nfagg_handle* h, const nfagg_tls_name_entry* entries,
     return NFAGG_OK;
 }
 
-void nfagg_tls_names_destroy(nfagg_tls_names* t) {
-    if (!t) return;
-    if (t->h && t->d_mem) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        (void)hipFree(t->d_mem);
-    }
-    delete t;
-}
+void nfagg_tls_names_destroy(nfagg_tls_names* t) { destroy_on_handle(t); }
 
 int nfagg_tls_names_render(const nfagg_tls_names* t, int kind, uint16_t id, int mismatch, void* out, size_t cap, size_t* n_out) {
     if (!t || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
@@ -556,14 +539,14 @@ int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size
     if (h) {
         auto up = [&]() -> int {
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_slots, cap * sizeof(K8sSlot)));
-            HIP_TRY(h, hipMalloc(&t->d_rows, std::max<size_t>(n, 1) * sizeof(K8sRow)));
-            HIP_TRY(h, hipMalloc(&t->d_blob, std::max<size_t>(t->blob.size(), 16)));
-            HIP_TRY(h, hipMalloc(&t->d_host_ids, std::max<size_t>(n, 1) * sizeof(uint32_t)));
-            if (n) HIP_TRY(h, hipMemcpy(t->d_host_ids, t->host_ids.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(h, hipMemcpy(t->d_slots, t->slots.data(), cap * sizeof(K8sSlot), hipMemcpyHostToDevice));
-            if (n) HIP_TRY(h, hipMemcpy(t->d_rows, t->rows.data(), n * sizeof(K8sRow), hipMemcpyHostToDevice));
-            if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
+            HIP_TRY(h, t->d_slots.alloc(cap * sizeof(K8sSlot)));
+            HIP_TRY(h, t->d_rows.alloc(std::max<size_t>(n, 1) * sizeof(K8sRow)));
+            HIP_TRY(h, t->d_blob.alloc(std::max<size_t>(t->blob.size(), 16)));
+            HIP_TRY(h, t->d_host_ids.alloc(std::max<size_t>(n, 1) * sizeof(uint32_t)));
+            if (n) HIP_TRY(h, hipMemcpy(t->d_host_ids.p, t->host_ids.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(h, hipMemcpy(t->d_slots.p, t->slots.data(), cap * sizeof(K8sSlot), hipMemcpyHostToDevice));
+            if (n) HIP_TRY(h, hipMemcpy(t->d_rows.p, t->rows.data(), n * sizeof(K8sRow), hipMemcpyHostToDevice));
+            if (!t->blob.empty()) HIP_TRY(h, hipMemcpy(t->d_blob.p, t->blob.data(), t->blob.size(), hipMemcpyHostToDevice));
             return NFAGG_OK;
         };
         const int rc = up();
@@ -573,18 +556,7 @@ int nfagg_k8s_table_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size
     return NFAGG_OK;
 }
 
-void nfagg_k8s_table_destroy(nfagg_k8s_table* t) {
-    if (!t) return;
-    if (t->h && (t->d_slots || t->d_rows || t->d_blob || t->d_host_ids)) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        if (t->d_slots) (void)hipFree(t->d_slots);
-        if (t->d_rows) (void)hipFree(t->d_rows);
-        if (t->d_blob) (void)hipFree(t->d_blob);
-        if (t->d_host_ids) (void)hipFree(t->d_host_ids);
-    }
-    delete t;
-}
+void nfagg_k8s_table_destroy(nfagg_k8s_table* t) { destroy_on_handle(t); }
 
 int nfagg_k8s_resolve_device(nfagg_handle* h, const nfagg_k8s_table* table, const void* d_records, size_t n, uint32_t* d_rows) {
     if (!h || !table || (n && (!d_records || !d_rows))) return fail(h, NFAGG_EINVAL, "null argument");
@@ -604,10 +576,10 @@ int nfagg_k8s_resolve(nfagg_handle* h, const nfagg_k8s_table* table, const void*
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
     if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = nfagg_k8s_resolve_device(h, table, S.in_records.p, n, (uint32_t*)S.k8s_rows.p)) != NFAGG_OK) return rc;
+    if ((rc = nfagg_k8s_resolve_device(h, table, S.in_records.p, n, S.k8s_rows.as<uint32_t>())) != NFAGG_OK) return rc;
     if (n) HIP_TRY(h, hipMemcpyAsync(rows, S.k8s_rows.p, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
@@ -703,8 +675,8 @@ int nfagg_net_table_create(nfagg_handle* h, const nfagg_net_rules* rules, nfagg_
             if (!t->frags.empty()) memcpy(img.data() + t->off_frags, t->frags.data(), t->frags.size() * sizeof(NetFrag));
             if (!t->blob.empty()) memcpy(img.data() + t->off_blob, t->blob.data(), t->blob.size());
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_mem, img.size()));
-            HIP_TRY(h, hipMemcpy(t->d_mem, img.data(), img.size(), hipMemcpyHostToDevice));
+            HIP_TRY(h, t->d_mem.alloc(img.size()));
+            HIP_TRY(h, hipMemcpy(t->d_mem.p, img.data(), img.size(), hipMemcpyHostToDevice));
             return NFAGG_OK;
         };
         const int rc = up();
@@ -714,15 +686,7 @@ int nfagg_net_table_create(nfagg_handle* h, const nfagg_net_rules* rules, nfagg_
     return NFAGG_OK;
 }
 
-void nfagg_net_table_destroy(nfagg_net_table* t) {
-    if (!t) return;
-    if (t->h && t->d_mem) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        (void)hipFree(t->d_mem);
-    }
-    delete t;
-}
+void nfagg_net_table_destroy(nfagg_net_table* t) { destroy_on_handle(t); }
 
 int nfagg_net_render(const nfagg_net_table* table, int side, uint32_t label, void* out, size_t cap, size_t* n_out) {
     if (!table || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
@@ -750,7 +714,7 @@ int nfagg_net_resolve_device(nfagg_handle* h, const nfagg_net_table* net_table, 
         return fail(h, NFAGG_EINVAL, "device records must be 16-byte, rows 8-byte aligned");
     HIP_TRY(h, hipSetDevice(h->device));
     if (n) {
-        hipError_t e = launch_net_resolve(d_records, n, net_dev(net_table), dir ? d_k8s_rows : nullptr, dir ? (const uint32_t*)k8s_table->d_host_ids : nullptr,
+        hipError_t e = launch_net_resolve(d_records, n, net_dev(net_table), dir ? d_k8s_rows : nullptr, dir ? k8s_table->d_host_ids.as<const uint32_t>() : nullptr,
                                           dir ? (uint32_t)k8s_table->rows.size() : 0u, dir ? net_reporter(k8s_table, opt) : kNetNoHost, (uint2*)d_out,
                                           h->stream);
         if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
@@ -767,12 +731,12 @@ int nfagg_net_resolve(nfagg_handle* h, const nfagg_net_table* net_table, const n
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.net_rows.ensure(h, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
     if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
     if (n && dir) HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    if ((rc = nfagg_net_resolve_device(h, net_table, k8s_table, S.in_records.p, n, (const uint32_t*)S.k8s_rows.p, opt, (nfagg_net_row*)S.net_rows.p)) != NFAGG_OK)
+    if ((rc = nfagg_net_resolve_device(h, net_table, k8s_table, S.in_records.p, n, S.k8s_rows.as<const uint32_t>(), opt, S.net_rows.as<nfagg_net_row>())) != NFAGG_OK)
         return rc;
     if (n) HIP_TRY(h, hipMemcpyAsync(out, S.net_rows.p, n * sizeof(nfagg_net_row), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -825,11 +789,11 @@ static int metrics_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_tabl
     if (h) {
         auto up = [&]() -> int {
             HIP_TRY(h, hipSetDevice(h->device));
-            HIP_TRY(h, hipMalloc(&t->d_cls, std::max<size_t>(words, 4) * sizeof(uint32_t)));
+            HIP_TRY(h, t->d_cls.alloc(std::max<size_t>(words, 4) * sizeof(uint32_t)));
             for (uint32_t g = 0; g < n_groupings; g++)
                 for (int side = 0; side < 2; side++)
                     if (n && !t->cls[g][side].empty())
-                        HIP_TRY(h, hipMemcpy((uint32_t*)t->d_cls + t->d_off[g][side], t->cls[g][side].data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+                        HIP_TRY(h, hipMemcpy(t->d_cls.as<uint32_t>() + t->d_off[g][side], t->cls[g][side].data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
             return NFAGG_OK;
         };
         const int rc = up();
@@ -870,15 +834,7 @@ int nfagg_metrics_table_create_specs(nfagg_handle* h, const nfagg_k8s_table* k8s
     return metrics_table_create(h, k8s_table, dims, specs, n_groupings, table);
 }
 
-void nfagg_metrics_table_destroy(nfagg_metrics_table* t) {
-    if (!t) return;
-    if (t->h && t->d_cls) {
-        (void)hipSetDevice(t->h->device);
-        (void)hipStreamSynchronize(t->h->stream);
-        (void)hipFree(t->d_cls);
-    }
-    delete t;
-}
+void nfagg_metrics_table_destroy(nfagg_metrics_table* t) { destroy_on_handle(t); }
 
 uint64_t nfagg_metrics_group_hash(uint32_t grouping, const nfagg_metric_group* key) {
     if (!key || grouping >= kMetMaxGroupings) return 0;
@@ -948,7 +904,7 @@ static int metrics_fold_device_core(nfagg_handle* h, const nfagg_metrics_table* 
         M.out[g] = d_out[g];
         if (M.dims[g] & NFAGG_DIM_FLOW_LAYER) M.any_layer = 1;
         for (int side = 0; side < 2; side++)
-            M.cls[g][side] = table->cls[g][side].empty() ? nullptr : (const uint32_t*)table->d_cls + table->d_off[g][side];
+            M.cls[g][side] = table->cls[g][side].empty() ? nullptr : table->d_cls.as<const uint32_t>() + table->d_off[g][side];
         if (X) {
             const nfagg_metric_spec& sp = table->specs[g];
             X->xdims[g] = sp.xdims; X->value[g][0] = sp.value[0]; X->value[g][1] = sp.value[1];
@@ -976,18 +932,18 @@ static int metrics_fold_device_core(nfagg_handle* h, const nfagg_metrics_table* 
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
     const size_t slot_bytes = (size_t)blocks * kMetMinSlots * words * sizeof(uint64_t);
-    if ((rc = ensure_buf(h, S.met_slots, 256 + slot_bytes)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.local_off, (size_t)blocks * kMetMinSlots * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.block_sum, (size_t)blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.block_base, ((size_t)blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    M.ctl = (MetCtl*)S.met_slots.p;
-    uint64_t* slots = (uint64_t*)((uint8_t*)S.met_slots.p + 256);
+    if ((rc = S.met_slots.ensure(h, 256 + slot_bytes)) != NFAGG_OK) return rc;
+    if ((rc = S.local_off.ensure(h, (size_t)blocks * kMetMinSlots * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.block_sum.ensure(h, (size_t)blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.block_base.ensure(h, ((size_t)blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    M.ctl = S.met_slots.as<MetCtl>();
+    uint64_t* slots = (uint64_t*)(S.met_slots.as<uint8_t>() + 256);
     for (uint32_t g = 0; g < G; g++) M.slots[g] = slots + (size_t)M.first_block[g] * kMetMinSlots * words;
     HIP_TRY(h, hipMemsetAsync(S.met_slots.p, 0, 256 + slot_bytes, h->stream));
     hipError_t e = X ? launch_metrics_fold_content(d_records, n, M, *X, d_k8s_rows, (const uint2*)d_net_rows, h->stream)
                      : launch_metrics_fold(d_records, n, M, d_k8s_rows, (const uint2*)d_net_rows, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "metrics fold launch failed: %s", hipGetErrorString(e));
-    e = launch_metrics_emit(M, X != nullptr, (uint32_t*)S.local_off.p, (uint32_t*)S.block_sum.p, (uint64_t*)S.block_base.p, h->stream);
+    e = launch_metrics_emit(M, X != nullptr, S.local_off.as<uint32_t>(), S.block_sum.as<uint32_t>(), S.block_base.as<uint64_t>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "metrics emit launch failed: %s", hipGetErrorString(e));
     MetCtl ctl;
     HIP_TRY(h, hipMemcpyAsync(&ctl, M.ctl, sizeof ctl, hipMemcpyDeviceToHost, h->stream));      // the one read-back: counts and flags
@@ -1018,10 +974,10 @@ static int metrics_fold_host_core(nfagg_handle* h, const nfagg_metrics_table* ta
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = ensure_buf(h, S.in_records, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.k8s_rows, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.net_rows, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
-    if ((rc = ensure_buf(h, S.met_out, total * group_bytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.net_rows.ensure(h, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
+    if ((rc = S.met_out.ensure(h, total * group_bytes + 16)) != NFAGG_OK) return rc;
     if (n) {
         HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
@@ -1029,15 +985,15 @@ static int metrics_fold_host_core(nfagg_handle* h, const nfagg_metrics_table* ta
     }
     void* d_out[kMetMaxGroupings] = {};
     size_t at = 0;
-    for (uint32_t g = 0; g < G; g++) { d_out[g] = (uint8_t*)S.met_out.p + at * group_bytes; at += group_cap[g]; }
-    const nfagg_net_row* d_net = net_rows ? (const nfagg_net_row*)S.net_rows.p : nullptr;
+    for (uint32_t g = 0; g < G; g++) { d_out[g] = S.met_out.as<uint8_t>() + at * group_bytes; at += group_cap[g]; }
+    const nfagg_net_row* d_net = net_rows ? S.net_rows.as<const nfagg_net_row>() : nullptr;
     if (content) {
         nfagg_pb_features dfeat{};
         if (feat && n && (rc = stage_pb_features(h, feat, n, &dfeat)) != NFAGG_OK) return rc;
-        rc = nfagg_metrics_fold_content_device(h, table, S.in_records.p, n, (feat && n) ? &dfeat : nullptr, (const uint32_t*)S.k8s_rows.p, d_net, group_cap,
+        rc = nfagg_metrics_fold_content_device(h, table, S.in_records.p, n, (feat && n) ? &dfeat : nullptr, S.k8s_rows.as<const uint32_t>(), d_net, group_cap,
                                                (nfagg_metric_group_content* const*)d_out, n_groups);
     } else
-        rc = nfagg_metrics_fold_device(h, table, S.in_records.p, n, (const uint32_t*)S.k8s_rows.p, d_net, group_cap, (nfagg_metric_group* const*)d_out, n_groups);
+        rc = nfagg_metrics_fold_device(h, table, S.in_records.p, n, S.k8s_rows.as<const uint32_t>(), d_net, group_cap, (nfagg_metric_group* const*)d_out, n_groups);
     if (rc != NFAGG_OK) return rc;
     for (uint32_t g = 0; g < G; g++)
         if (n_groups[g]) HIP_TRY(h, hipMemcpyAsync(out[g], d_out[g], (size_t)n_groups[g] * group_bytes, hipMemcpyDeviceToHost, h->stream));

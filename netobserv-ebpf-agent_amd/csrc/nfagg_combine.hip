@@ -1,7 +1,7 @@
 // nfagg_combine.hip — flow PARTIALS: exporting the live slots of a table grouped by the shard that owns them, and merging
 // such partials into the owner's table. This is the tick-time exchange of the local-fold mode (SURVEY.md §8(e) "hot-key
 // replication with commutative partials merged at tick ... order-dependent fields need the seq tags"), used by the
-// one-process group (nfagg_group.inc, NFAGG_GROUP_LOCAL_FOLD) and, through nfagg_partials_export_device /
+// one-process group (nfagg_api_group.hip, NFAGG_GROUP_LOCAL_FOLD) and, through nfagg_partials_export_device /
 // nfagg_partials_merge_device / nfagg_evict_owned_device, by one-process-per-GPU ranks (bench.py --gpus N).
 //
 // In that mode every GPU folds whatever arrives at it — no per-record routing, a flow may live on several GPUs at once —

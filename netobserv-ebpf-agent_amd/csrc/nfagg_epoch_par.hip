@@ -1,6 +1,6 @@
 // nfagg_epoch_par.hip — the evict-on-full loop of Accounter.Account (pkg/flow/account.go:81-96) WITHOUT its sequential chain: the
 // epochs of a call are found first, then every complete epoch is folded on its own, all of them at once, with no flow table at all.
-// What nfagg_account[_device] runs for calls of more than a few epochs (host side: nfagg_account_par.inc; the rule
+// What nfagg_account[_device] runs for calls of more than a few epochs (host side: nfagg_api_account.hip; the rule
 // is pinned on the CPU by tests/test_epoch_boundaries.py).
 //
 // The loop is sequential only in WHERE its epochs end. With prev(i) = the index of the previous record of record i's flow in the
@@ -392,7 +392,7 @@ NF_DEV void cut_block(int32_t cur[kCutPer], uint32_t wave_base_v, CutState& st, 
 // The walk is RESUMABLE: a launch covers the blocks [b_begin, b_end) and leaves its state (the epoch in progress: where it began,
 // how many new flows it has seen, which cut comes next) in ctl[8..12]; a launch with b_begin > 0 picks it up. The host runs the walk
 // in a few such parts and hands the epochs each part has completed to the segment folds while the next part walks on: the walk
-// keeps ONE compute unit busy, the folds the other 255 (nfagg_account_par.inc). Nothing else changes: a block boundary is an
+// keeps ONE compute unit busy, the folds the other 255 (nfagg_api_account.hip). Nothing else changes: a block boundary is an
 // ordinary place for an epoch to go on across (the records of a block before the epoch's start were dead anyway).
 __global__ __launch_bounds__(kCutBlock) void k_par_cuts(const int32_t* __restrict__ prev, uint64_t n, uint32_t max_entries, uint32_t live0,
                                                         uint32_t* __restrict__ cuts, uint32_t max_cuts, uint32_t* __restrict__ ctl,

@@ -1,11 +1,14 @@
-// nfagg_handle.h — what the host translation units of the C ABI share (nfagg_api.hip: the flow table; nfagg_api_export.hip,
-// nfagg_api_tables.hip, nfagg_api_aux.hip: the encoders, the caller tables, the side operations): the handle behind
-// nfagg_handle*, error reporting, the grow-only device buffers. Private to csrc/; nothing here is exported (nfagg.map).
+// nfagg_handle.h — what the host translation units of the C ABI share (nfagg_api.hip: the flow table; nfagg_api_account.hip:
+// nfagg_account*; nfagg_api_group.hip: the multi-GPU group; nfagg_api_export.hip, nfagg_api_tables.hip, nfagg_api_filter.hip,
+// nfagg_api_conn.hip, nfagg_api_aux.hip: the encoders, the caller tables, the side operations): error reporting, the owner types
+// — every device / pinned allocation, stream, event and graph of the library lives in one and is released by its destructor —
+// and the handle behind nfagg_handle*, which holds nothing but owners and plain state: `delete h` frees all of it.
+// Private to csrc/; nothing here is exported (nfagg.map).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <initializer_list>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -15,88 +18,168 @@
 
 namespace nfagg {
 
-struct EventPair { hipEvent_t a, b; int kind; };
+// Sets the handle's error text (without a handle: the calling thread's create error, nfagg_last_error(NULL)) and returns `code`.
+// Defined once, in nfagg_api.hip, beside the create-error string: every translation unit reports into the same one.
+int fail(nfagg_handle* h, int code, const char* fmt, ...);
+
+inline uint64_t next_pow2(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
+
+// Device and pinned allocations of this library that are alive (nfagg_debug_live_buffers): counted where they are made and freed
+inline std::atomic<uint64_t> g_live_buffers{0};
+
+// Device memory (DevBuf) and page-locked host memory (PinnedBuf). alloc: a fixed size, once (flags: as hipHostMalloc takes them,
+// page-locked memory only). ensure: grow-only scratch — at least `need` bytes afterwards; the contents do not survive a growth
+// (the old block is freed first; the new one has 4 KiB to spare, device memory a quarter more).
+template <bool kPinned> struct Buf {
+    void* p = nullptr;
+    size_t cap = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    ~Buf() { reset(); }
+    void reset() { if (p) { (void)(kPinned ? hipHostFree(p) : hipFree(p)); g_live_buffers--; p = nullptr; cap = 0; } }
+    hipError_t alloc(size_t bytes, unsigned flags = hipHostMallocDefault) {
+        reset();
+        const hipError_t e = kPinned ? hipHostMalloc(&p, bytes, flags) : hipMalloc(&p, bytes);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = bytes; g_live_buffers++;
+        return hipSuccess;
+    }
+    int ensure(nfagg_handle* h, size_t need) { return cap >= need ? NFAGG_OK : grow(h, need); }
+    int grow(nfagg_handle* h, size_t need) {
+        const size_t want = need + (kPinned ? 0 : need / 4) + 4096;
+        const hipError_t e = alloc(want);
+        return e == hipSuccess ? NFAGG_OK : fail(h, kPinned ? NFAGG_EDEVICE : NFAGG_ENOMEM, "%s(%zu) failed: %s", kPinned ? "hipHostMalloc" : "hipMalloc", want, hipGetErrorString(e));
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+    explicit operator bool() const { return p != nullptr; }
+};
+using DevBuf = Buf<false>;
+using PinnedBuf = Buf<true>;
+
+// A stream, an event, an instantiated graph: created on first use by the code that needs them, read through the conversion.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create(unsigned flags = hipStreamNonBlocking) { return hipStreamCreateWithFlags(&s, flags); }
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDisableTiming) { return hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+struct GraphExec {
+    hipGraphExec_t g = nullptr;
+    GraphExec() = default;
+    GraphExec(GraphExec&& o) noexcept : g(o.g) { o.g = nullptr; }
+    ~GraphExec() { reset(); }
+    void reset() { if (g) { (void)hipGraphExecDestroy(g); g = nullptr; } }
+    operator hipGraphExec_t() const { return g; }
+};
+
+struct EventPair { hipEvent_t a, b; int kind; };     // borrowed from nfagg_handle::ev_pool
+
+// The arrays a TableView points into
+struct TableMem { DevBuf hot, cold, aux, live_list, ctr; };
+
+// export encoders (protobuf, IPFIX, direct-FLP JSON): one scratch, they serialise on the stream and synchronise before returning
+struct EncodeScratch {
+    DevBuf local_off, block_sum, block_base;     // the two scans: u32[n], u32[blocks], u64[blocks + 1] (the total last)
+    DevBuf names;                                // the namer table, stably sorted by if_index
+    DevBuf ipfix_name_rows;                      // size pass -> write pass: u32[n]
+    DevBuf flp_rows;                             // size pass -> write pass: 8 x u32 per record (seven rows, the line's length)
+    DevBuf flp_esc, flp_n_deferred;              // the escaped table; the deferred counter
+    DevBuf in_records, out, out_offsets;         // host-memory entry points: staged records, output bytes, offsets
+    DevBuf out_extra[2];                         //   protobuf: body lengths, kafka keys; FLP: deferred flags
+    DevBuf pb_feat[6];                           //   protobuf: present bits and the five feature parts
+    DevBuf ne_rows;                              //   *_netev: the flows' table rows
+    DevBuf ne_in[3], ne_out[3], ne_missing, ne_info;   // nfagg_netev_resolve: staged inputs and outputs, the missing set, its counters
+    DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record
+    DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record
+    DevBuf met_slots, met_out;                   // nfagg_metrics_fold: control words and the groupings' tables; the host entry point's groups
+    DevBuf conn_slots, conn_flow;                // nfagg_conn_fold: control words and the connection table; per flow hashA and slot
+    DevBuf conn_ids, conn_out;                   //   the host entry point's hash ids and partials; the host entry points of the two
+                                                 //   conntrack encoders stage their ids / values here too (one stream: calls serialise)
+    std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
+    std::vector<uint8_t> h_flp_esc;
+};
+
+// nfagg_rollup_*
+struct RollupScratch { DevBuf partials, base, folded; };
+
+// nfagg_map_merge*: the join's slots and scans; the host variant's staged maps (main map, then the six feature maps) and outputs
+struct MergeScratch {
+    DevBuf slots, slot_of, local_off, block_sum, block_base, n_dup;
+    DevBuf ids[7], vals[7], out[8];
+};
+
+// nfagg_cm_topk*
+struct TopkScratch { DevBuf est, est_sorted, idx, idx_sorted, sort_tmp, rows, records; };    // records: the host variant's
+
+// optimistic fold: raw slot snapshot, sketch snapshot, first sequence numbers (+ sorted), sort scratch
+struct OptScratch { DevBuf slots, sketches, first_seqs, sort_tmp; };
+
+// nfagg_account*, the kernel chain: control block, epoch ends, live-list scratch (device); pinned: control block, then the epoch ends
+struct ChainScratch { DevBuf ctl, ends, live; PinnedBuf host; };
+
+// nfagg_account*, the epochs found first (nfagg_api_account.hip): the analysis arrays, the pinned control words and cuts, the stream
+// the middle epochs are folded on while the table takes the first and the last
+struct ParScratch {
+    DevBuf keys, keys_sorted, prev, pos, long_segs, sort_tmp, ctl, rank_tiles;   // ctl: control words, then the cuts
+    PinnedBuf host;                     // control words, the cuts, the walk parts' state
+    Stream stream;
+    Event done;
+    Event part[16];                     // one behind every part of the cut walk (kParWalkPartsMax)
+};
 
 }  // namespace nfagg
 
 struct nfagg_handle {
     nfagg_config cfg{};
     int device = 0;
-    hipStream_t stream = nullptr;
+    // streams first: destroyed after everything that was used on them
+    nfagg::Stream stream;
+    nfagg::Stream copy_stream;      // H2D copies of the staging ring: chunk k+1 goes up while chunk k is folded on `stream`
+    nfagg::Stream d2h_stream;
+    nfagg::Stream d2h_small;        // small / one-off downloads (d2h_copy): not the stream the pipelined page-locked downloads use
     uint64_t slots = 0;
-    nfagg::TableView tv{};
-    nfagg::SketchView sk{};
-    bool own_sketch[4] = {false, false, false, false};
-    nfagg::DevCounters* h_ctr = nullptr;      // pinned mirror
+    nfagg::TableView tv{};          // points into `table`, `spill_queues`, `spill_xp`, `qtail`
+    nfagg::TableMem table;
+    nfagg::SketchView sk{};         // points into `sketch` or at the caller's buffers (cfg.ext_sketch)
+    nfagg::DevBuf sketch[4];        // Count-Min src, dst; HyperLogLog src, dst — the ones the caller did not supply
+    nfagg::PinnedBuf ctr_mirror; nfagg::DevCounters* h_ctr = nullptr;        // the counters' pinned mirror, and how the code reads it
     // staging ring (host ingest path)
-    void* pinned[2] = {nullptr, nullptr};
-    void* d_stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_free[2] = {nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;   // H2D copies of the staging ring: chunk k+1 goes up while chunk k is folded on `stream`
-    hipEvent_t stage_up[2] = {nullptr, nullptr};
+    nfagg::PinnedBuf pinned[2];
+    nfagg::DevBuf d_stage[2];
+    nfagg::Event stage_free[2], stage_up[2];
     int stage_next = 0;
     bool stage_acquired = false;
     // careful-path scratch
     uint64_t careful_chunk = 0;
-    uint32_t* d_slot_idx = nullptr;
-    uint8_t* d_flags = nullptr;
-    uint32_t* d_block_counts = nullptr;
+    nfagg::DevBuf d_slot_idx, d_flags, d_block_counts;
     std::vector<uint32_t> h_block_counts;
-    // eviction buffer (device)
-    void* d_evict = nullptr;
-    uint64_t d_evict_cap = 0;
-    // rollup scratch
-    void* d_roll[3] = {nullptr, nullptr, nullptr};
-    size_t d_roll_cap[3] = {0, 0, 0};
-    uint32_t* d_hist = nullptr;
-    // map merge scratch: [0] slots [1] slot_of [2] local_off [3] block_sum [4] block_base [5] dup counter,
-    // (host variant) [6..12] ids, [13..19] values, [20..27] outputs
-    void* d_mm[28] = {};
-    size_t d_mm_cap[28] = {};
-    void* d_hh[7] = {};            // heavy hitters: est, est sorted, idx, idx sorted, sort scratch, gathered rows, (host variant) records
-    size_t d_hh_cap[7] = {};
-    void* d_sort[2] = {};          // eviction: live list in slot order, radix-sort scratch
-    size_t d_sort_cap[2] = {};
+    nfagg::PinnedBuf careful_mirror; uint8_t* h_careful = nullptr;   // block counts + flags of a claim + flag chunk of up to kCarefulMaxBatch records
+    nfagg::DevBuf d_evict;          // eviction buffer (device)
+    nfagg::DevBuf d_ep_out;         // second device buffer for evictions (nfagg_account alternates with d_evict)
+    nfagg::RollupScratch roll;
+    nfagg::DevBuf d_hist;
+    nfagg::MergeScratch mm;
+    nfagg::TopkScratch hh;
+    nfagg::DevBuf sort_live, sort_tmp;   // eviction: live list in slot order, radix-sort scratch
     int sort_bits = 0;
     bool epoch_unclustered = false; // a batch of this epoch claimed slots in arrival order (single-pass / direct / dedup kernels)
-    // export encoders (protobuf, IPFIX, direct-FLP JSON): one scratch, they serialise on the stream and synchronise before returning
-    struct DevBuf { void* p = nullptr; size_t cap = 0; };
-    struct EncodeScratch {
-        DevBuf local_off, block_sum, block_base;     // the two scans: u32[n], u32[blocks], u64[blocks + 1] (the total last)
-        DevBuf names;                                // the namer table, stably sorted by if_index
-        DevBuf ipfix_name_rows;                      // size pass -> write pass: u32[n]
-        DevBuf flp_rows;                             // size pass -> write pass: 8 x u32 per record (seven rows, the line's length)
-        DevBuf flp_esc, flp_n_deferred;              // the escaped table; the deferred counter
-        DevBuf in_records, out, out_offsets;         // host-memory entry points: staged records, output bytes, offsets
-        DevBuf out_extra[2];                         //   protobuf: body lengths, kafka keys; FLP: deferred flags
-        DevBuf pb_feat[6];                           //   protobuf: present bits and the five feature parts
-        DevBuf ne_rows;                              //   *_netev: the flows' table rows
-        DevBuf ne_in[3], ne_out[3], ne_missing, ne_info;   // nfagg_netev_resolve: staged inputs and outputs, the missing set, its counters
-        DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record
-        DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record
-        DevBuf met_slots, met_out;                   // nfagg_metrics_fold: control words and the groupings' tables; the host entry point's groups
-        DevBuf conn_slots, conn_flow;                // nfagg_conn_fold: control words and the connection table; per flow hashA and slot
-        DevBuf conn_ids, conn_out;                   //   the host entry point's hash ids and partials; the host entry points of the two
-                                                     //   conntrack encoders stage their ids / values here too (one stream: calls serialise)
-        std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
-        std::vector<uint8_t> h_flp_esc;
-        template <typename F> void each(F f) {
-            for (DevBuf* b : {&local_off, &block_sum, &block_base, &names, &ipfix_name_rows, &flp_rows, &flp_esc, &flp_n_deferred,
-                              &in_records, &out, &out_offsets, &out_extra[0], &out_extra[1]}) f(*b);
-            for (DevBuf& b : pb_feat) f(b);
-            for (DevBuf* b : {&ne_rows, &ne_in[0], &ne_in[1], &ne_in[2], &ne_out[0], &ne_out[1], &ne_out[2], &ne_missing, &ne_info, &k8s_rows, &net_rows, &met_slots, &met_out,
-                              &conn_slots, &conn_flow, &conn_ids, &conn_out}) f(*b);
-        }
-    } enc;
-    // optimistic fold: [0] raw slot snapshot, [1] sketch snapshot, [2] first sequence numbers (+ sorted), [3] sort scratch
-    void* d_opt[4] = {};
-    size_t d_opt_cap[4] = {};
+    nfagg::EncodeScratch enc;
+    nfagg::OptScratch opt;
     uint64_t epoch_len_hint = 0;   // records the last epoch that ended on "full" took (0 = this stream has not stopped on full)
     uint64_t last_epoch_flows = 0; // slots the last epoch had claimed when it ended (flows; sub-flows on a sub-flow table): what the next one is sized by
     uint64_t abort_cap = 0;        // largest chunk worth trying after the kernels refused claims (0 = no limit known)
-    // spill queues of the two-pass ingest
-    void* d_spill = nullptr;
-    size_t d_spill_cap = 0;
+    // spill queues of the two-pass ingest: partition queues + overflow list; the streaming pass's exported cache entries; the tails
+    nfagg::DevBuf spill_queues, spill_xp, qtail;
     // accounting
     uint64_t epoch_seq = 0;         // sequence number of the next record, counted from the start of the epoch (64 bits: never runs out)
     uint64_t seq_origin = 0;        // the device sees epoch_seq - seq_origin: a 32-bit window, moved by a rebase (nfagg_rebase.hip)
@@ -109,66 +192,44 @@ struct nfagg_handle {
     // asynchronous fold clears it. mirror_fresh: *h_ctr equals the device counters (what the optimistic fold's rollback restores).
     bool counters_exact = false;
     bool mirror_fresh = false;
-    uint8_t* h_careful = nullptr;   // pinned: block counts + flags of a claim + flag chunk of up to kCarefulMaxBatch records
     bool must_evict = false; // a "full" split is pending (account.go:85-94)
     uint64_t split_seq = 0;
     // local fold across GPUs (nfagg_partials_*): the flows of other shards have been exported to their owners; nothing may be
     // folded on top of them before the eviction (they would be exported twice)
     bool exported = false;
-    void* d_exp = nullptr;          // 64 owner counts + 64 segment cursors + the owned-flows count
-    size_t d_exp_cap = 0;
-    unsigned long long* h_exp = nullptr;   // pinned mirror of the counts
-    // nfagg_account*: control block of the epoch kernel chain (device + pinned mirror), epoch ends, slot scratch
-    void* d_ep[3] = {};             // [0] control block, [1] epoch ends, [2] live-list scratch
-    size_t d_ep_cap[3] = {};
-    void* d_ep_out = nullptr;       // second device buffer for evictions (nfagg_account alternates with d_evict)
-    size_t d_ep_out_cap = 0;
-    void* h_ep = nullptr;           // pinned: control block, then the epoch ends
-    size_t h_ep_cap = 0;
+    nfagg::DevBuf d_exp;            // 64 owner counts + 64 segment cursors + the owned-flows count
+    nfagg::PinnedBuf exp_mirror; unsigned long long* h_exp = nullptr;   // pinned mirror of the counts
+    nfagg::ChainScratch chain;
     // device -> pageable host memory through two pinned bounce buffers (d2h_copy): a plain hipMemcpy to pageable memory runs at
     // ~13 GB/s here, this at the PCIe rate
-    void* h_bounce[2] = {nullptr, nullptr};
-    hipStream_t d2h_stream = nullptr;
-    hipStream_t d2h_small = nullptr;     // small / one-off downloads (d2h_copy): not the stream the pipelined page-locked downloads use
-    hipEvent_t bounce_ev[2] = {nullptr, nullptr};
-    hipGraphExec_t ep_graph[3] = {nullptr, nullptr, nullptr};   // kChainWindows[k] windows of the epoch kernel chain, captured once (their arguments never change)
+    nfagg::PinnedBuf h_bounce[2];
+    nfagg::Event bounce_ev[2];
+    nfagg::GraphExec ep_graph[3];        // kChainWindows[k] windows of the epoch kernel chain, captured once (their arguments never change)
     bool ep_graph_off = false;           // the capture or the instantiation failed once: this handle launches its windows eagerly
     void* ep_graph_key[3] = {};          // the buffers the captured launches point at: re-capture when one was re-allocated
     // sub-flow table (kernel-dedup mode of a local-fold rank, nfagg_dedup.h): the flow-keyed table its epochs are joined into
     // (nfagg_dedup_join.hip), allocated at the first eviction; scratch; the join that has been made and not yet evicted
-    nfagg::TableView jv{};
-    nfagg::DevCounters* h_jctr = nullptr; // pinned mirror of jv.ctr
-    void* d_join = nullptr;         // slot_of[]: the J slot of every live sub-flow
-    size_t d_join_cap = 0;
+    nfagg::TableView jv{};          // points into `jtable`
+    nfagg::TableMem jtable;
+    nfagg::PinnedBuf jctr_mirror; nfagg::DevCounters* h_jctr = nullptr;   // pinned mirror of jv.ctr
+    nfagg::DevBuf d_join;           // slot_of[]: the J slot of every live sub-flow
     struct { bool valid = false, dirty = false; uint32_t n_shards = 0, shard_id = 0; uint64_t flows = 0, claimed = 0; } join;   // dirty: J may hold claims
-    // the evict-on-full loop with its epochs found first (nfagg_account_par.inc): analysis arrays, pinned mirror, the stream the
-    // middle epochs are folded on while the table takes the first and the last
-    uint32_t* h_par = nullptr;      // pinned: control words, then the cuts
-    void* d_par[8] = {};            // sort keys, sorted keys, prev, pos, long segments, sort scratch, control + cuts, rank tile counts
-    size_t d_par_cap[8] = {};
-    hipStream_t par_stream = nullptr;
-    hipEvent_t par_done = nullptr;
-    hipEvent_t par_part[16] = {};   // one behind every part of the cut walk (kParWalkPartsMax)
+    nfagg::ParScratch par; uint32_t* h_par = nullptr;           // (h_par: par.host as the code reads it)
     nfagg_stats stats{};
+    std::vector<nfagg::Event> ev_pool;        // profiling: every event ever created for this handle
     std::vector<nfagg::EventPair> ev_pending;
     std::vector<nfagg::EventPair> ev_free;
     std::mutex err_mu;              // nfagg_account's helper threads report through fail() too
     std::string err;
 };
 
-namespace nfagg {
-
-// Sets the handle's error text (without a handle: the calling thread's create error, nfagg_last_error(NULL)) and returns `code`.
-// Defined once, in nfagg_api.hip, beside the create-error string: every translation unit reports into the same one.
-int fail(nfagg_handle* h, int code, const char* fmt, ...);
-
-// Grow-only device scratch: (*p, *cap) holds at least `need` bytes afterwards; the contents do not survive a growth (nfagg_api.hip).
-int ensure_bytes(nfagg_handle* h, void** p, size_t* cap, size_t need);
-inline int ensure_buf(nfagg_handle* h, nfagg_handle::DevBuf& b, size_t need) { return ensure_bytes(h, &b.p, &b.cap, need); }
-
-inline uint64_t next_pow2(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
-
-}  // namespace nfagg
+// The end of an object that lives on a handle's device (caller tables, filters, layouts): the handle's stream may still be reading
+// its buffers, so it is waited for; the object's owners free them.
+template <typename T> void destroy_on_handle(T* t) {
+    if (!t) return;
+    if (t->h) { (void)hipSetDevice(t->h->device); (void)hipStreamSynchronize(t->h->stream); }
+    delete t;
+}
 
 #define HIP_TRY(h, expr)                                                                      \
     do {                                                                                      \

@@ -160,7 +160,7 @@ constexpr bool kDiagBuild = false;
 #endif
 hipError_t launch_ingest_part(const TableView& t, const SketchView& sk, const SpillView& q, const void* d_records, uint64_t n,
                               uint64_t seq_base, int variant, hipStream_t s);
-// nfagg_epoch_par.hip / nfagg_account_par.inc: the evict-on-full loop of nfagg_account with its epochs found first — sort keys
+// nfagg_epoch_par.hip / nfagg_api_account.hip: the evict-on-full loop of nfagg_account with its epochs found first — sort keys
 // ((top 40 hash bits) << 24 | index), their sort, previous-occurrence links, live flags, the cut walk (resumable: run in parts);
 // then the complete epochs of the
 // middle: positions and segment folds (no table)

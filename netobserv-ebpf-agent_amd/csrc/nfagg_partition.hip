@@ -1,5 +1,5 @@
 // nfagg_partition.hip — stable partition of a record batch by flow-key shard (the device-side router of the multi-GPU
-// group, nfagg_group.inc; SURVEY.md §8(e): "a GPU partition kernel + P2P scatter").
+// group, nfagg_api_group.hip; SURVEY.md §8(e): "a GPU partition kernel + P2P scatter").
 //
 // Records shard by nfagg_shard_of(key, n_shards) (nfagg_hash.h; the Go agent is ONE process in front of N GPUs,
 // pkg/agent/agent.go:387-442). The partition is STABLE — within a bucket the records keep their arrival order — because the

@@ -19,7 +19,7 @@
 //
 // Across GPUs (local fold: one flow on several GPUs, tags compared when the partials meet at the owner) collapsing each GPU's
 // tags on its own would lose the order between GPUs: there the flows are first brought together at their owners (partials
-// exported, table emptied by the epoch tag, partials merged back at the owner: nfagg_group.inc group_consolidate,
+// exported, table emptied by the epoch tag, partials merged back at the owner: nfagg_api_group.hip group_consolidate,
 // nfagg_window_restart_device), and the owner's single copy is rebased.
 #include "nfagg_device.h"
 

@@ -65,6 +65,11 @@ def host_info() -> dict:
             "calibrated_GBs": round(info.calibrated_gbs, 1)}
 
 
+def debug_live_buffers() -> int:
+    """Device and page-locked allocations of the library alive in this process (testing aid: tests/test_lifecycle_gpu.py)."""
+    return int(L.lib.nfagg_debug_live_buffers())
+
+
 def device_numa_node(device: int = 0) -> int:
     return int(L.lib.nfagg_device_numa_node(device))
 

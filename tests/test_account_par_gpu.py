@@ -1,6 +1,6 @@
 """nfagg_account[_device] on calls of more than a few epochs: the evict-on-full loop of Accounter.Account
 (pkg/flow/account.go:81-96) with its epochs FOUND FIRST (previous-occurrence links, tests/test_epoch_boundaries.py) and every
-complete epoch folded on its own from the sorted call — csrc/nfagg_epoch_par.hip, csrc/nfagg_account_par.inc; the default path of
+complete epoch folded on its own from the sorted call — csrc/nfagg_epoch_par.hip, csrc/nfagg_api_account.hip; the default path of
 such calls. `variant` 30 forces the kernel chain (its fallback) over the same streams. Same contract either way: every eviction
 bit-identical, in order, to the oracle's."""
 import numpy as np

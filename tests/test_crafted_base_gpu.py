@@ -330,7 +330,7 @@ def test_evict_on_full_inside_the_stream(nf, O, lab, family, small, layout, batc
 
 
 # ---------------------------------------------------------------- 6: nfagg_account
-PAR_FAMILIES = ("times", "lastnz", "macs")                   # calls large enough for csrc/nfagg_account_par.inc (account_par_min_records)
+PAR_FAMILIES = ("times", "lastnz", "macs")                   # calls large enough for csrc/nfagg_api_account.hip (account_par_min_records)
 ACCOUNT_SIZES = [(f, third) for f in bc.FAMILIES for third in (False, True) if not (third and f == "hot")]      # eight flows: a third is two
 
 

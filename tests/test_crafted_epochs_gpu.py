@@ -1,5 +1,5 @@
 """nfagg_account on CRAFTED calls (tests/epochcraft.py): the evict-on-full loop with its epochs found first
-(csrc/nfagg_epoch_par.hip, csrc/nfagg_account_par.inc) and its fallback, the kernel chain (csrc/nfagg_epoch_chain.hip,
+(csrc/nfagg_epoch_par.hip, csrc/nfagg_api_account.hip) and its fallback, the kernel chain (csrc/nfagg_epoch_chain.hip,
 ingest_variant 30), driven to the places where their designs have edges. The seeded Zipf streams of tests/test_account_par_gpu.py
 leave to chance where a cut falls inside a block, a wave, a row or a group of four records of the cut walk, how long a flow's
 segment is relative to kSegShort, kSegHuge and kHugeChunk, and which record of a 5 000-record segment carries the only non-zero DSCP.

@@ -3,7 +3,7 @@ N > 1 path of `bench.py --gpus N` calls, executed with backend "nccl" (= RCCL) a
 device id, the sketch all-reduces (int64 SUM for Count-Min, uint8 MAX for the HyperLogLog registers), all_to_all_single with split
 sizes on device tensors, partials export / merge, evict_owned — so that the first real 8-GPU run is not the first time these
 calls execute. And the process that holds BOTH RCCLs: torch's bundled librccl.so (torch.distributed) and the one libnfagg's group
-API dlopens itself (csrc/nfagg_group.inc), side by side."""
+API dlopens itself (csrc/nfagg_api_group.hip), side by side."""
 import json
 import os
 import subprocess

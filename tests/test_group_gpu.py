@@ -1,4 +1,4 @@
-"""The multi-GPU group (include/nfagg.h nfagg_group_*, csrc/nfagg_group.inc) on ONE GPU: several members on device 0
+"""The multi-GPU group (include/nfagg.h nfagg_group_*, csrc/nfagg_api_group.hip) on ONE GPU: several members on device 0
 exercise the stable device partition, the routing, per-shard folds, the stop-on-full logic and the sketch merge (local
 kernels instead of RCCL when members share a device); a one-member group on a distinct device goes through the RCCL
 calls themselves (ncclCommInitAll / ncclAllReduce at N = 1), from Python and from plain C."""

@@ -1,4 +1,4 @@
-"""Local-fold mode of the multi-GPU group (NFAGG_GROUP_LOCAL_FOLD; csrc/nfagg_group.inc, csrc/nfagg_combine.hip) on ONE GPU:
+"""Local-fold mode of the multi-GPU group (NFAGG_GROUP_LOCAL_FOLD; csrc/nfagg_api_group.hip, csrc/nfagg_combine.hip) on ONE GPU:
 several members on device 0 fold the chunks that arrive at them — no routing, a flow lives on several members — and the
 eviction merges the members' raw slots into their owners. The result must be bit-identical to ONE sequential Accounter over
 the same records (oracle), whatever the split of the stream over the members."""
