@@ -2083,6 +2083,124 @@ int nfagg_group_debug_skip_sequence(nfagg_group* g, uint64_t records);   /* the 
  * found when it is destroyed; a grow-only scratch buffer that grows replaces its block and leaves the count as it was. */
 uint64_t nfagg_debug_live_buffers(void);
 
+/* ---------------------------------------------------------------------- */
+/* write loki on the device: streams, batches and push-request bodies      */
+/* ---------------------------------------------------------------------- */
+/* flowlogs-pipeline's `write loki` (pkg/pipeline/write/write_loki.go) and the batching of loki-client-go, for the flows
+ * of one call: every flow's JSON line WITHOUT the keys the stage takes out of it (splitLabelsLines, :223-251) and without a
+ * trailing newline (formatter "json", write_stdout.go:42-51), its timestamp (extractTimestamp, :253-277), its stream (the
+ * label VALUES it carries), the batches of the client (client.go:154-172: a batch starts with an entry whatever its size and
+ * is sent when bytes + len(line) > BatchSize, bytes counting line bytes only, batch.go:39-40, 63-65), and every batch as the
+ * body of one logproto.PushRequest (pkg/logproto/types.go:88-144, timestamp.go:59-106):
+ *   PushRequest   0x0a len Stream                                    per stream, ascending stream id
+ *   Stream        0x0a len labels, then 0x12 len Entry               per entry, in arrival order (batch.go:39-54, 96-107)
+ *   Entry         0x0a len Timestamp (always, even with len 0), then 0x12 len line
+ *   Timestamp     0x08 seconds when not 0 (negative: a ten-byte varint), 0x10 nanos when not 0
+ * Stream order in a request is Go map order in the reference; ascending stream id is one admissible order. Snappy and the
+ * HTTP / gRPC send stay with the caller.
+ *
+ * Keys that can be named as a label or as ignored are those the line policies write through a hook: the nine SrcK8S_* and
+ * nine DstK8S_* fields (the bits of NFAGG_DIM_SRC_K8S / NFAGG_DIM_DST_K8S), SrcSubnetLabel, DstSubnetLabel, FlowDirection,
+ * K8S_FlowLayer (NFAGG_DIM_*), _RecordType and _HashId (below). No other key is expressible: such a stage stays on the host.
+ * A key named in both masks is ignored (the ignore list is looked at first). _HashId as a LABEL is refused: it would make
+ * a stream per conversation. */
+#define NFAGG_LOKI_KEY_RECORD_TYPE (1u << 23)
+#define NFAGG_LOKI_KEY_HASH_ID (1u << 24)
+#define NFAGG_LOKI_KEY_ALL ((NFAGG_DIM_ALL & ~NFAGG_DIM_PROTO) | NFAGG_LOKI_KEY_RECORD_TYPE | NFAGG_LOKI_KEY_HASH_ID)
+#define NFAGG_LOKI_TS_NOW 0u                 /* TimestampLabel "": timeNow() */
+#define NFAGG_LOKI_TS_TIME_FLOW_END_MS 1u
+#define NFAGG_LOKI_TS_TIME_FLOW_START_MS 2u
+#define NFAGG_LOKI_MAX_STREAMS (1u << 20)
+#define NFAGG_LOKI_LABELS_MAX 4096u          /* one stream's LabelSet.String() */
+
+typedef struct {
+    uint32_t struct_size;
+    uint32_t label_keys;                     /* NFAGG_DIM_* / NFAGG_LOKI_KEY_*: keys that become labels */
+    uint32_t ignore_keys;                    /* keys of the ignore list */
+    uint32_t timestamp_source;               /* NFAGG_LOKI_TS_* */
+    double timestamp_scale;                  /* float64(time.ParseDuration(TimestampScale)): 1e6 for "1ms" */
+    uint32_t batch_size;                     /* 1 .. 2^31 - 1 */
+    uint32_t pad_;
+} nfagg_loki_spec;
+
+/* A stream of a plan: what tells its label values. A class is that of nfagg_loki_class_row (0: the side has no row, or no
+ * label field of the row is present); a label is the net table's label index (0xFFFF: none, or the key is no label);
+ * direction 0..2 (255: none); layer 0 none, 1 infra, 2 app; record_type 1: "flowLog". first_flow: the first flow of the
+ * call that belongs to it; stream ids ascend with it. */
+typedef struct {
+    uint32_t src_class, dst_class;
+    uint16_t src_label, dst_label;
+    uint8_t direction, layer, record_type, pad_;
+    uint32_t first_flow;
+} nfagg_loki_stream;
+
+/* One (batch, stream) of a plan, ascending by batch, then stream. entry_bytes: the stream's framed entries (every 0x12 len
+ * Entry), what a Stream holds behind its labels. */
+typedef struct {
+    uint32_t batch, stream, n_entries, pad_;
+    uint64_t entry_bytes;
+} nfagg_loki_group;
+
+typedef struct { uint32_t n_streams, n_groups, n_batches, n_deferred; } nfagg_loki_counts;
+
+typedef struct nfagg_loki_table nfagg_loki_table;
+
+/* Over the rows of k8s_table (kept alive by the caller): (a) both sides' rendered blocks once more with the label and the
+ * ignored keys left out, in the shape of the table's own; (b) one class per row and side over the LABEL fields, by
+ * nfagg_metrics_table_create's (text, presence) rule with one addition: a field whose text is not valid UTF-8 counts as
+ * absent, and is left out of the line as well (write_loki.go:240-243). Subnet labels of net_table with equal text share a
+ * stream; one whose text is not valid UTF-8 is dropped likewise. NFAGG_EINVAL: a spec with unknown bits, _HashId as a label,
+ * an unknown timestamp source, a scale that is not finite and positive, batch_size outside 1 .. 2^31 - 1. h == NULL builds and
+ * checks on the host alone (tables built with h == NULL; errors through nfagg_last_error(NULL)); the plan refuses such a table. */
+int nfagg_loki_table_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table,
+                            const nfagg_loki_spec* spec, nfagg_loki_table** table);
+void nfagg_loki_table_destroy(nfagg_loki_table* table);
+/* Classes of a side (0 src, 1 dst), numbered from 1, and the first row of a class: its label fields are the class's values. */
+uint32_t nfagg_loki_n_classes(const nfagg_loki_table* table, int side);
+int nfagg_loki_class_row(const nfagg_loki_table* table, int side, uint32_t cls, uint32_t* row);
+/* One side's block of row `row` as the lines of this table carry it. */
+int nfagg_loki_render(const nfagg_loki_table* table, int side, uint32_t row, void* out, size_t cap, size_t* n_out);
+
+/* The plan of one call. Arguments as nfagg_encode_flp_json_conn takes them, then the table and timeNow(). hash_ids NULL: no
+ * conntrack stage in front, every flow has a line and neither _RecordType nor _HashId; otherwise a flow the stage does not
+ * track has no line and takes part in nothing. All three line policies are served: features NULL the plain line, features
+ * the parts of full flow contents, rows and netev_table (both or neither; they need features) their network events.
+ * A flow whose timestamp product leaves int64, or whose time lies outside [year 1, year 10000) (validateTimestamp), is
+ * DEFERRED: deferred[i] = 1, and it is kept out of every batch and every cut; the caller formats it. (The reference would
+ * lose the whole batch.)
+ * Stream ids are dense, in order of each stream's first flow. Batches are cut over the flows in order, from an empty batch.
+ * streams / groups: room for stream_cap / group_cap; with more, NFAGG_TRUNCATED, counts hold what is needed and nothing is
+ * written to streams and groups (stream_cap at most NFAGG_LOKI_MAX_STREAMS). deferred: n bytes, or NULL; it is written whatever
+ * the return code. The handle keeps the plan, and the
+ * records and tables must stay as they are, until nfagg_loki_write ran or the next plan. All pointers HOST memory: */
+int nfagg_loki_plan(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
+                    const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                    const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const uint64_t* hash_ids,
+                    const nfagg_flp_options* opt, const nfagg_loki_table* table, int64_t now_unix_ns,
+                    nfagg_loki_stream* streams, uint32_t stream_cap, nfagg_loki_group* groups, uint32_t group_cap,
+                    uint8_t* deferred, nfagg_loki_counts* counts);
+/* Same with d_records, d_hash_ids, d_streams, d_groups and d_deferred in DEVICE memory (records 16-byte, the others 8-byte
+ * aligned, d_rows and the arrays inside d_features as the *_conn_device encoder takes them); counts stays on the host. */
+int nfagg_loki_plan_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                           const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
+                           const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const uint64_t* d_hash_ids,
+                           const nfagg_flp_options* opt, const nfagg_loki_table* table, int64_t now_unix_ns,
+                           nfagg_loki_stream* d_streams, uint32_t stream_cap, nfagg_loki_group* d_groups, uint32_t group_cap,
+                           uint8_t* d_deferred, nfagg_loki_counts* counts);
+/* The bodies of the handle's plan, back to back. labels: every stream's LabelSet.String() (labelset_string.go:23-43), stream
+ * s at labels[label_offsets[s] .. label_offsets[s + 1]), each 2 .. NFAGG_LOKI_LABELS_MAX bytes; the caller renders it once per
+ * stream. batch_offsets: n_batches + 1 values, batch_entries: n_batches. NFAGG_TRUNCATED with *out_bytes = bytes needed when
+ * out_cap is smaller or out is NULL (offsets and entries are written all the same); NFAGG_EINVAL without a plan, or with a
+ * plan that was truncated; NFAGG_ERANGE when the label texts come to 2^32 bytes or more. All pointers HOST memory: */
+int nfagg_loki_write(nfagg_handle* h, const void* labels, const uint64_t* label_offsets, void* out, size_t out_cap,
+                     uint64_t* batch_offsets, uint32_t* batch_entries, size_t* out_bytes);
+/* Same with d_out (16-byte aligned), d_batch_offsets and d_batch_entries in DEVICE memory; the label text stays on the host. */
+int nfagg_loki_write_device(nfagg_handle* h, const void* labels, const uint64_t* label_offsets, void* d_out, size_t out_cap,
+                            uint64_t* d_batch_offsets, uint32_t* d_batch_entries, size_t* out_bytes);
+/* The longest framed entry (0x12 len Entry) a flow can take: nfagg_flp_json_conn_max_line(policy) - 1 (no newline) plus 27
+ * bytes of framing; 0 for an unknown policy. */
+uint32_t nfagg_loki_max_entry(int policy);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,3 +32,5 @@ from .filter import TransformFilter, StageFilter, parse_query
 from .table import Filter, filter_roll
 from . import conntrack
 from .conntrack import ConnTrack
+from . import loki
+from .loki import WriteLoki, LokiTable, LokiWriter, labelset_string, LOKI_STREAM, LOKI_GROUP

@@ -170,6 +170,24 @@ class MetricSpec(C.Structure):
                 ("pad_", C.c_uint8), ("n_bounds", C.c_uint32), ("pad2_", C.c_uint32), ("bounds", C.c_int64 * 32)]
 
 
+# write loki (nfagg_loki_*): maskable keys are the NFAGG_DIM_* bits without Proto, and two of their own
+LOKI_KEY_RECORD_TYPE, LOKI_KEY_HASH_ID = 1 << 23, 1 << 24
+LOKI_KEY_ALL = (DIM_ALL & ~DIM_PROTO) | LOKI_KEY_RECORD_TYPE | LOKI_KEY_HASH_ID
+LOKI_TS_NOW, LOKI_TS_TIME_FLOW_END_MS, LOKI_TS_TIME_FLOW_START_MS = 0, 1, 2
+LOKI_MAX_STREAMS, LOKI_LABELS_MAX = 1 << 20, 4096
+
+
+class LokiSpec(C.Structure):
+    """nfagg_loki_spec (include/nfagg.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("label_keys", C.c_uint32), ("ignore_keys", C.c_uint32), ("timestamp_source", C.c_uint32),
+                ("timestamp_scale", C.c_double), ("batch_size", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class LokiCounts(C.Structure):
+    """nfagg_loki_counts (include/nfagg.h)."""
+    _fields_ = [("n_streams", C.c_uint32), ("n_groups", C.c_uint32), ("n_batches", C.c_uint32), ("n_deferred", C.c_uint32)]
+
+
 # conversation tracking (nfagg_conn_*)
 CONN_MAX_CONNS, CONN_NO_IDX = 1 << 22, 0xFFFFFFFF
 
@@ -359,6 +377,18 @@ SIGNATURES = {
                                      _vp, _sz, _psz, _psz]),
     "nfagg_filter_apply_device": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpOptions), C.c_uint64, C.c_uint64, _vp, _vp,
                                             _vp, _vp, _sz, _psz, _psz]),
+    "nfagg_loki_table_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(LokiSpec), C.POINTER(_vp)]),
+    "nfagg_loki_table_destroy": (None, [_vp]),
+    "nfagg_loki_n_classes": (C.c_uint32, [_vp, C.c_int]),
+    "nfagg_loki_class_row": (C.c_int, [_vp, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "nfagg_loki_render": (C.c_int, [_vp, C.c_int, C.c_uint32, _vp, _sz, _psz]),
+    "nfagg_loki_plan": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, C.c_int64, _vp,
+                                  C.c_uint32, _vp, C.c_uint32, _vp, C.POINTER(LokiCounts)]),
+    "nfagg_loki_plan_device": (C.c_int, [_vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(FlpOptions), _vp, C.c_int64, _vp,
+                                         C.c_uint32, _vp, C.c_uint32, _vp, C.POINTER(LokiCounts)]),
+    "nfagg_loki_write": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _psz]),
+    "nfagg_loki_write_device": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _psz]),
+    "nfagg_loki_max_entry": (C.c_uint32, [C.c_int]),
     "nfagg_gather": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
     "nfagg_gather_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),

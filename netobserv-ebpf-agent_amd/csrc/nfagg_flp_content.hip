@@ -29,6 +29,7 @@
 #include "nfagg_k8s.h"
 #include "nfagg_net.h"
 #include "nfagg_conn_meta.h"
+#include "nfagg_loki_line.h"
 
 namespace nfagg {
 
@@ -351,6 +352,17 @@ hipError_t launch_flp_conn_write(const void* d_recs, uint64_t n, const FlpParams
     return flp_conn_select(F, [&](auto policy) {
         return connlog_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_hash_ids, d_rows,
                                                                  d_local_off, d_block_base, d_out, d_line_offsets, s); });
+}
+
+// write loki (nfagg_loki_line.h): FlpLoki over the two content policies, in the kernel pair of that header.
+hipError_t launch_loki_key_content(const LokiArgs& A, const LokiDev& L, const LokiPlanDev& D, hipStream_t s) {
+    return A.F.ne_rows ? loki_key_as<LokiOver<FlpContentNetev>>(A, L, D, s) : loki_key_as<LokiOver<FlpContent>>(A, L, D, s);
+}
+hipError_t launch_loki_write_content(const LokiArgs& A, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint8_t* d_out, hipStream_t s) {
+    return A.F.ne_rows ? loki_write_as<LokiOver<FlpContentNetev>>(A, L, D, W, m, d_out, s) : loki_write_as<LokiOver<FlpContent>>(A, L, D, W, m, d_out, s);
+}
+uint32_t loki_max_entry_content(int policy) {
+    return policy == 1 ? LokiOver<FlpContent>::kMaxEntry : policy == 2 ? LokiOver<FlpContentNetev>::kMaxEntry : 0u;
 }
 
 uint32_t flp_conn_max_line(int policy) { return flp_net_max_line(policy) ? flp_net_max_line(policy) + kConnMetaLineMax : 0u; }

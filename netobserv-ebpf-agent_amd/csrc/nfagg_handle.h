@@ -9,6 +9,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -124,6 +125,10 @@ struct TopkScratch { DevBuf est, est_sorted, idx, idx_sorted, sort_tmp, rows, re
 // optimistic fold: raw slot snapshot, sketch snapshot, first sequence numbers (+ sorted), sort scratch
 struct OptScratch { DevBuf slots, sketches, first_seqs, sort_tmp; };
 
+// nfagg_loki_plan / nfagg_loki_write (nfagg_api_loki.hip): the plan's arrays and state, kept until the next plan. Defined there;
+// the handle owns it through the deleter that file installs.
+struct LokiPlan;
+
 // nfagg_account*, the kernel chain: control block, epoch ends, live-list scratch (device); pinned: control block, then the epoch ends
 struct ChainScratch { DevBuf ctl, ends, live; PinnedBuf host; };
 
@@ -175,6 +180,7 @@ struct nfagg_handle {
     bool epoch_unclustered = false; // a batch of this epoch claimed slots in arrival order (single-pass / direct / dedup kernels)
     nfagg::EncodeScratch enc;
     nfagg::OptScratch opt;
+    std::unique_ptr<nfagg::LokiPlan, void (*)(nfagg::LokiPlan*)> loki{nullptr, nullptr};
     uint64_t epoch_len_hint = 0;   // records the last epoch that ended on "full" took (0 = this stream has not stopped on full)
     uint64_t last_epoch_flows = 0; // slots the last epoch had claimed when it ended (flows; sub-flows on a sub-flow table): what the next one is sized by
     uint64_t abort_cap = 0;        // largest chunk worth trying after the kernels refused claims (0 = no limit known)

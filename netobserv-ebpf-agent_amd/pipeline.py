@@ -220,7 +220,7 @@ class MapTracer:
             self._netevTable = None
 
     def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None, k8s=None, net=None,
-                       metrics=None, filter=None):
+                       metrics=None, filter=None, loki=None):
         """evictFlows for a direct-FLP `write: stdout, format: json` stage, without a Record per flow: the drained maps are merged,
         decorated with the sample decoder's network events and encoded on the GPU. Returns (buf, line_offsets, deferred) as
         FlowTable.encode_flp_json_content does; with tls_names (a TlsNames of the fetcher's table) the TLS keys are written too,
@@ -232,9 +232,14 @@ class MapTracer:
         decoder those nfagg_netev_resolve wrote, so that an injected drop counts like any other. With filter (a filter.StageFilter;
         needs tls_names) the `transform filter` stage runs on the merged flows first: the metrics and the lines are those of the kept
         flows, a third result lists the lines the caller formats itself (their stored Sampling overflows 32 bits) as (position, the
-        admitting keep step, the Sampling the reference stores), as StageFilter.apply returns them."""
+        admitting keep step, the Sampling the reference stores), as StageFilter.apply returns them. With loki (a loki.LokiWriter over
+        the same tables; needs net) the pipeline ends in `write loki`: the result is (bodies, deferred, held), the PushRequest bodies
+        of the merged (and kept) flows with their feature parts and network events, the positions the caller formats itself because
+        of their timestamp, and the filter's held flows as above (with their stored Sampling), which are in no body."""
         if filter is not None and tls_names is None:
             raise ValueError("filter needs tls_names")
+        if loki is not None and net is None:
+            raise ValueError("loki needs tls_names, k8s and net: the stage's labels are keys of the transform network stage")
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         if net is not None and k8s is None:
@@ -256,6 +261,8 @@ class MapTracer:
             if metrics is not None:
                 metrics.observe(table, recs, k8s, net, agent_ip, **(dict(features=(present, parts)) if content else {}))
             args = (current, mono, names, agent_ip, time_received, unknown, present, parts, rows, tab)
+            if loki is not None:
+                return self._loki(loki, recs, current, mono, time_received, present, parts, rows, tab, held)
             if net is not None:
                 return table.encode_flp_json_net(recs, tls_names, k8s, net, *args) + (held,)
             if k8s is not None:
@@ -266,6 +273,8 @@ class MapTracer:
         if self.sampleDecoder is None:                                  # s == nil: no events, no injected drops (record.go:126)
             if content:
                 metrics.observe(table, recs, k8s, net, agent_ip, features=(present, parts))
+            if loki is not None:
+                return self._loki(loki, recs, current, mono, time_received, present, parts, None, None, [])
             if net is not None:
                 return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, present, parts)
             if k8s is not None:
@@ -276,6 +285,8 @@ class MapTracer:
         p_out, parts, rows, tab = self.resolveNetworkEvents(present, parts)
         if content:
             metrics.observe(table, recs, k8s, net, agent_ip, features=(p_out, parts))
+        if loki is not None:
+            return self._loki(loki, recs, current, mono, time_received, p_out, parts, rows, tab, [])
         if net is not None:
             return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         if k8s is not None:
@@ -283,6 +294,18 @@ class MapTracer:
         if tls_names is not None:
             return table.encode_flp_json_tls(recs, tls_names, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         return table.encode_flp_json_netev(recs, p_out, parts, rows, tab, current, mono, names, agent_ip, time_received, unknown)
+
+    @staticmethod
+    def _loki(loki, recs, now_ns, mono, time_received, present, parts, rows, tab, held):
+        """The merged flows through a LokiWriter; the filter's held flows (their stored Sampling does not fit the record) are taken out
+        first and returned with their stored values."""
+        n = len(recs)
+        at = [j for j, _, _ in held]
+        kept = np.delete(np.arange(n), at) if at else None
+        take = (lambda a: a[kept] if a is not None else None) if at else (lambda a: a)
+        sub_parts = {k: take(v) for k, v in parts.items()} if parts is not None else None
+        bodies, late = loki.ExportEvicted(take(recs), now_ns, mono, time_received, present=take(present), parts=sub_parts, rows=take(rows), netev_table=tab)
+        return bodies, [int(kept[i]) if at else i for i in late], held
 
     def evictFlows(self, forwardFlows: "queue.Queue"):                  # :103-146
         monotonic_now, current = self.monoClock(), self.clock()
@@ -405,7 +428,9 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
     One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
 
     def __init__(self, table, stream, names=None, agent_ip=None, unknown: bytes = b"unknown", time_received: Callable[[], int] = None,
-                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None, metrics=None, filter=None):
+                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None, metrics=None, filter=None, loki=None):
+        if loki is not None and net is None:
+            raise ValueError("loki needs tls_names, k8s and net: the stage's labels are keys of the transform network stage")
         if k8s is not None and tls_names is None:
             raise ValueError("k8s needs tls_names: the enriched encoder defers nothing")
         if net is not None and k8s is None:
@@ -425,6 +450,11 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         # encode(raw, now_ns, mono_ns, names, agent_ip, time_received, unknown) -> (buf, line_offsets, deferred)
         self._encode = encode or table.encode_flp_json
         self.tls_names, self.k8s, self.net = tls_names, k8s, net
+        # loki (a loki.LokiWriter over the same tables): the pipeline ends in `write loki` instead of `write stdout`. Nothing is
+        # written to `stream`; the bodies go to the writer's send and stay in loki_bodies until the next eviction, loki_deferred
+        # lists the flows of that eviction (positions among the kept) the caller formats itself, loki_held the filter's held flows
+        # among them as (position, keep step, the Sampling the reference stores), what the stdout path hands its fallback.
+        self.loki, self.loki_bodies, self.loki_deferred, self.loki_held = loki, [], [], []
 
     def ExportEvicted(self, raw, now_ns: int, mono_ns: int) -> int:
         """One eviction's lines. now_ns / mono_ns: the eviction's currentTime / monotonicCurrentTime (account.go:103-104).
@@ -440,6 +470,14 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
                 return 0
         if self.metrics is not None:
             self.metrics.observe(self.table, raw, self.k8s, self.net, self.agent_ip)
+        if self.loki is not None:                         # filter first, then conntrack's ids, then Loki (both inside the writer)
+            held_at = [j for j, _, _ in held]
+            kept = np.delete(np.arange(n), held_at) if held_at else np.arange(n)
+            self.loki_bodies, late = self.loki.ExportEvicted(raw[kept] if held_at else raw, now_ns, mono_ns, self.time_received())
+            self.loki_deferred, self.loki_held = sorted(held_at + [int(kept[i]) for i in late]), list(held)
+            self.lines += n
+            self.deferred += len(self.loki_deferred)
+            return n
         if self.tls_names is not None:
             if self.net is not None:
                 buf, off = self.table.encode_flp_json_net(raw, self.tls_names, self.k8s, self.net, now_ns, mono_ns & ((1 << 64) - 1), self.names,

@@ -886,6 +886,28 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, n_conns.value, n_disc.value
 
+    # -- write loki (nfagg_loki_*; loki.py): the stage's table, the plan of one call, its PushRequest bodies
+    def loki_table(self, writer, k8s: "K8sTable", net: "NetTable"):
+        """A loki.LokiTable on this handle's device; writer: a loki.WriteLoki."""
+        from .loki import LokiTable
+        return LokiTable(writer, k8s, net, self)
+
+    def loki_plan(self, records: np.ndarray, tls_names: "TlsNames", k8s: "K8sTable", net: "NetTable", loki, now_unix_ns: int, mono_now_ns: int,
+                  names: np.ndarray, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", hash_ids=None, loki_now_ns: int = None,
+                  stream_cap: int = None, group_cap: int = None, present=None, parts=None, rows=None, netev_table: "NetevTable" = None):
+        """nfagg_loki_plan: streams, batches and groups of one call's flows (loki.loki_plan); present / parts / rows / netev_table as
+        encode_flp_json_conn takes them. Returns (rc, streams, groups,
+        deferred, counts); the handle keeps the plan for loki_write."""
+        from .loki import loki_plan
+        return loki_plan(self, records, tls_names, k8s, net, loki, now_unix_ns, mono_now_ns, names, agent_ip, time_received, unknown, hash_ids,
+                         loki_now_ns, stream_cap, group_cap, present, parts, rows, netev_table)
+
+    def loki_write(self, label_texts, n_batches: int, out_cap: int = None):
+        """nfagg_loki_write: the plan's batches as PushRequest bodies, back to back (loki.loki_write). label_texts: every stream's
+        LabelSet.String(). Returns (rc, buf, batch_offsets, batch_entries)."""
+        from .loki import loki_write
+        return loki_write(self, label_texts, n_batches, out_cap)
+
     # -- transform filter (nfagg_filter_*): FLP's `transform filter` stage as a device program, the stable compaction, the gather
     def filter(self, spec, k8s: "K8sTable" = None, net: "NetTable" = None) -> "Filter":
         """A compiled filter on this handle's device; spec: a filter.TransformFilter (or anything with its spec())."""

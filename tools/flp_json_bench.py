@@ -57,7 +57,14 @@ half of the flows stay, once without sampling and once with keepEntrySampling 10
 time of nfagg_filter_apply_device (eval, the scan, the read-back of the count, the compaction with its records), of the two
 nfagg_gather_device calls for the Kubernetes rows and the net rows, and of nfagg_encode_flp_json_net_device on the kept flows, beside
 the unfiltered _net call and the net join of the same run; the bytes a flow moves by this tool's own count as a fraction of the
-read-stream rate measured in the same run. --k8s-trace covers the k_filter_* and k_gather kernels."""
+read-stream rate measured in the same run. --k8s-trace covers the k_filter_* and k_gather kernels.
+
+--loki (with --k8s --net --metrics --conntrack): the write loki leg on top, on the same records, tables and hash ids in the same run,
+beside the _conn call: the operator's label set (namespace, owner name and owner kind of both sides, K8S_FlowLayer, FlowDirection,
+_RecordType), TimeFlowEndMs at a scale of 1ms, at batch sizes of 100 KiB and 10 MiB. Reported per batch size: the median wall time of
+nfagg_loki_plan_device, of rendering the streams' label texts on the host (once per stream), of nfagg_loki_write_device, and their sum
+(the whole call), with the streams, groups, batches and bytes; the yardstick is the _conn call plus the host loop it replaces.
+--k8s-trace covers the k_loki_* kernels, the cut walk (k_loki_cuts) among them. --flows N runs one table size instead of the two."""
 import io
 import os
 import queue
@@ -85,6 +92,8 @@ NET = "--net" in sys.argv[1:]
 METRICS = "--metrics" in sys.argv[1:]
 CONNTRACK = "--conntrack" in sys.argv[1:]
 FILTER = "--filter" in sys.argv[1:]
+LOKI = "--loki" in sys.argv[1:]
+FLOWS = int(sys.argv[sys.argv.index("--flows") + 1]) if "--flows" in sys.argv[1:] else 0
 NET_CATEGORIES = [("cat-%d" % c, ["172.%d.%d.0/24" % (16 + c, k) for k in range(8)] + ["2001:db8:%x::/48" % (16 * c + k) for k in range(1)]) for c in range(5)] + \
                  [("pods", ["100.64.0.0/10"]), ("everything", ["0.0.0.0/0", "::/0"])]
 K8S_ROWS = 100_000
@@ -157,9 +166,12 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_connlog_|k_filter_|k_gather|fillBuffer|scan", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_connlog_|k_filter_|k_gather|k_loki_|fillBuffer|scan|[Ss]ort|onesweep", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
+            if "rocprim" in name:                           # the library's scan and sort kernels: their configuration's name and value types
+                m = re.search(r"wrapped_(\w+?)_config<.*?, (unsigned \w+(?:, unsigned \w+)?)>", name) or re.search(r"detail::(\w+?)<", name)
+                short = "rocprim " + " ".join(m.groups()) if m else "rocprim"
             grid = int(row.get("Grid_Size_X") or row.get("Grid_Size") or 0)
             spans.setdefault((short, grid), []).append((int(row["Start_Timestamp"]), (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3))
     print("device time per launch from the kernel trace, median over the launches of one size, us:")
@@ -251,6 +263,8 @@ def conntrack_leg(tab, d_ev, m, tls, k8s, net, d_off):
     per_byte("_conn", m, dt, wrote)
     print(f"           flow logs: {m - n_disc} of {m} flows tracked, {wrote / max(m - n_disc, 1):.1f} B per line that is written")
     del d_out
+    if LOKI:
+        loki_leg(tab, d_ev, m, tls, k8s, net, d_ids, dt)
     # the conversation records at the leg's connection count: every connection's first flow is its carrier, the values are the partials'
     # sums with synthetic all-zero snapshots. The byte sums are masked to 40 bits so that no conversation is deferred (the synthetic
     # flows' byte counts are random 64-bit values): the leg times the encoder writing every line. The fields are the operator's usual
@@ -274,6 +288,49 @@ def conntrack_leg(tab, d_ev, m, tls, k8s, net, d_off):
         assert rc == nf.OK and wrote == need
         per_byte("conv", n_conns, dt, wrote)
         print(f"           conversation records: {lay.n_columns} columns, longest possible line {lay.max_line} B, {n_def} deferred")
+
+
+def loki_leg(tab, d_ev, m, tls, k8s, net, d_ids, dt_conn):
+    import ctypes as C
+    L = nf._lib
+    o, keep = nf.flp_options(NOW, MONO, names, agent, 1_700_000_000, b"unknown")
+    labels = ["SrcK8S_Namespace", "SrcK8S_OwnerName", "SrcK8S_OwnerType", "DstK8S_Namespace", "DstK8S_OwnerName", "DstK8S_OwnerType", "K8S_FlowLayer", "FlowDirection",
+              "_RecordType"]
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    for batch_size in (100 * 1024, 10 << 20):
+        w = nf.WriteLoki(dict(labels=labels, timestampLabel="TimeFlowEndMs", timestampScale="1ms", batchSize=batch_size, staticLabels={"app": "netobserv-flowcollector"}))
+        with tab.loki_table(w, k8s, net) as lt:
+            cap_s, cap_g = min(m, L.LOKI_MAX_STREAMS), m
+            d_streams = torch.empty(cap_s * 20 + 16, dtype=torch.uint8, device="cuda")
+            d_groups = torch.empty(cap_g * 24 + 16, dtype=torch.uint8, device="cuda")
+            counts = L.LokiCounts()
+            plan = lambda: L.lib.nfagg_loki_plan_device(tab._h, ptr(d_ev), m, None, None, None, tls._t, k8s._t, net._t, ptr(d_ids), C.byref(o), lt._t, NOW, ptr(d_streams),  # noqa: E731
+                                                        cap_s, ptr(d_groups), cap_g, None, C.byref(counts))
+            rc, dt_plan = timed(plan)
+            if rc != L.OK:
+                print(f"  _loki    batch size {batch_size}: the plan is refused ({(L.lib.nfagg_last_error(tab._h) or b'').decode()})")
+                continue
+            streams = d_streams[: counts.n_streams * 20].cpu().numpy().view(nf.LOKI_STREAM)
+            t0 = time.perf_counter()
+            texts = lt.labels_of(streams)
+            dt_labels = time.perf_counter() - t0
+            blob = b"".join(texts)
+            off = np.zeros(len(texts) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(t) for t in texts], dtype=np.uint64)
+            d_boff = torch.empty(counts.n_batches + 1, dtype=torch.int64, device="cuda")
+            d_bent = torch.empty(counts.n_batches + 1, dtype=torch.int32, device="cuda")
+            need = C.c_size_t(0)
+            rc = L.lib.nfagg_loki_write_device(tab._h, blob, off.ctypes.data_as(C.c_void_p), None, 0, ptr(d_boff), ptr(d_bent), C.byref(need))
+            total = need.value
+            d_out = torch.empty(total + 16, dtype=torch.uint8, device="cuda")
+            rc, dt_write = timed(lambda: L.lib.nfagg_loki_write_device(tab._h, blob, off.ctypes.data_as(C.c_void_p), ptr(d_out), total, ptr(d_boff), ptr(d_bent), C.byref(need)))
+            assert rc == L.OK and need.value == total and int(d_boff[counts.n_batches]) == total
+            whole = dt_plan + dt_labels + dt_write
+            print(f"  _loki    batch size {batch_size}: {m} flows -> {counts.n_streams} streams, {counts.n_groups} groups, {counts.n_batches} batches, {counts.n_deferred} deferred, "
+                  f"{total} bytes; plan {dt_plan * 1e3:.3f} ms, label texts on the host {dt_labels * 1e3:.3f} ms ({len(blob)} B), write {dt_write * 1e3:.3f} ms, "
+                  f"whole call {whole * 1e3:.3f} ms = {m / whole / 1e6:.2f} M flows/s, {dt_write / max(total, 1) * 1e12:.3f} ps per output byte of the write; "
+                  f"plan + write = {(dt_plan + dt_write) / dt_conn:.2f} of the _conn call of this run ({dt_conn * 1e3:.3f} ms)")
+            del d_out, d_streams, d_groups
 
 
 def metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net):
@@ -373,7 +430,7 @@ def line(what, m, dt, wrote, extra_per_flow):
     return dt
 
 
-for flows in ((10_000_000,) if (CONTENT or TLS) and not K8S else (1_000_000, 10_000_000)):
+for flows in ((FLOWS,) if FLOWS else (10_000_000,) if (CONTENT or TLS) and not K8S else (1_000_000, 10_000_000)):
     if K8S:
         torch.cuda.empty_cache()
     n = 4 * flows
