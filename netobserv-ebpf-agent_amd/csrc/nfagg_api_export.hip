@@ -126,9 +126,8 @@ int device_features(nfagg_handle* h, const nfagg_pb_features* feat, PbFeat* F) {
     return NFAGG_OK;
 }
 
-// The *_netev entry points' extra inputs: the flows' rows (DEVICE memory) and the table they index, into F.
-struct NetevArgs { const uint16_t* rows; const nfagg_netev_table* table; };
-static int device_netev(nfagg_handle* h, const NetevArgs* ne, size_t n, PbFeat* F) {
+// The *_netev entry points' extra inputs: the flows' rows (DEVICE memory) and the table they index, checked, into F.
+int device_netev(nfagg_handle* h, const NetevArgs* ne, size_t n, PbFeat* F) {
     if (!ne->table || (n && !ne->rows)) return fail(h, NFAGG_EINVAL, "null network-events rows or table");
     if (ne->table->h != h || !ne->table->d_rows) return fail(h, NFAGG_EINVAL, "the network-events table was not created for this handle");
     if (((uintptr_t)ne->rows & 7u) != 0) return fail(h, NFAGG_EINVAL, "network-events rows must be 8-byte aligned");
@@ -326,158 +325,142 @@ int nfagg_encode_ipfix(nfagg_handle* h, const void* records, size_t n, const nfa
             return nfagg_encode_ipfix_device(h, d_records, n, opt, d_out, out_cap, d_offsets, out_bytes); });
 }
 
-// ---- record -> direct-FLP JSON lines (nfagg_flp.hip)
-static void flp_escape_row(uint8_t* row, const char* name, uint32_t name_len, const char* udn, uint32_t udn_len) {
-    const uint16_t nl = (uint16_t)flp_escape(name, name_len, row + kFlpEscNameOff), ul = (uint16_t)flp_escape(udn, udn_len, row + kFlpEscUdnOff);
-    memcpy(row, &nl, 2); memcpy(row + 2, &ul, 2);
-}
-
+// ---- record -> direct-FLP JSON lines (nfagg_flp.hip), and what write loki's plan (nfagg_api_loki.hip) sets up in the same way
 // The options are checked first, before the handle: a caller learns of a bad table without any device work.
-static int encode_flp_check(nfagg_handle* h, const nfagg_flp_options* opt) {
+int check_flp_options(nfagg_handle* h, const nfagg_flp_options* opt) {
     if (!opt) return fail(h, NFAGG_EINVAL, "null options");
     if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
     return check_namer(h, opt->names, opt->n_names, opt->unknown_len, true);
 }
 
-// What the FLP device entry points stage after encode_begin: the size pass's rows, the escaped namer table, the deferred counter
-// (zeroed), the kernels' parameters.
-static int stage_flp(nfagg_handle* h, size_t n, const nfagg_flp_options* opt, FlpParams* Pout, uint32_t** rows_out) {
-    int rc;
-    auto& S = h->enc;
-    const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
-    if ((rc = S.flp_rows.ensure(h, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.flp_esc.ensure(h, esc_bytes)) != NFAGG_OK) return rc;
-    if ((rc = S.flp_n_deferred.ensure(h, 16)) != NFAGG_OK) return rc;
-    // names and UDNs are escaped here, once per row of the sorted table: neither kernel escapes per flow
-    S.h_flp_esc.assign(esc_bytes, 0);
-    flp_escape_row(S.h_flp_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
-    for (uint32_t k = 0; k < opt->n_names; k++) {
-        const nfagg_intf_name& e = S.h_names[k];
-        flp_escape_row(S.h_flp_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
-    }
-    HIP_TRY(h, hipMemcpyAsync(S.flp_esc.p, S.h_flp_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
-    *rows_out = S.flp_rows.as<uint32_t>();
-    FlpParams& P = *Pout;
-    P = FlpParams{};
-    split_now(opt->now_unix_ns, P.now_sec, P.now_nsec);
-    P.mono_now = opt->mono_now_ns;
-    P.time_received = opt->time_received_s;
-    P.names = S.names.as<const nfagg_intf_name>(); P.esc = S.flp_esc.as<const uint8_t>(); P.n_names = opt->n_names;
-    P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(P.agent_ip_w, opt->agent_ip, 16);
+int check_flp_tables(nfagg_handle* h, const FlpLineTables& t) {
+    if (t.level >= FlpLevel::Tls && (t.tls->h != h || !t.tls->d_mem)) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
+    if (t.level >= FlpLevel::K8s && (t.k8s->h != h || !t.k8s->d_slots)) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
+    if (t.level >= FlpLevel::Net && (t.net->h != h || !t.net->d_mem)) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
     return NFAGG_OK;
 }
 
-// The TLS entry points' extra input. With it the three TLS keys are written from the table, no record is deferred (flags and
-// counter are not used), and the network events are an option: rows and table both, or neither (*ne = nullptr).
-// with_k8s: the *_k8s entry points, whose table is required as well and whose lines carry the Kubernetes keys.
-// with_net: the *_net entry points, which take the table of the transform network rules on top of that.
-// with_conn: the *_conn entry points, which take the flows' hash ids on top of that (DEVICE memory in the device core).
-struct FlpTlsArgs {
-    const nfagg_tls_names* names; bool with_k8s = false; const nfagg_k8s_table* k8s = nullptr;
-    bool with_net = false; const nfagg_net_table* net = nullptr;
-    bool with_conn = false; const uint64_t* hash_ids = nullptr;
-};
+int netev_together(nfagg_handle* h, const NetevArgs& ne, size_t n) {
+    if ((ne.rows != nullptr) != (ne.table != nullptr) && (n || ne.rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
+    return NFAGG_OK;
+}
+
+static void flp_escape_row(uint8_t* row, const char* name, uint32_t name_len, const char* udn, uint32_t udn_len) {
+    const uint16_t nl = (uint16_t)flp_escape(name, name_len, row + kFlpEscNameOff), ul = (uint16_t)flp_escape(udn, udn_len, row + kFlpEscUdnOff);
+    memcpy(row, &nl, 2); memcpy(row + 2, &ul, 2);
+}
+
+int stage_flp_line(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt, const PbFeat& F, const FlpLineTables& t,
+                          const FlpLineStage& st, FlpLineArgs* args) {
+    int rc;
+    const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
+    if ((rc = st.names.ensure(h, (size_t)(opt->n_names + 1) * sizeof(nfagg_intf_name))) != NFAGG_OK) return rc;
+    if ((rc = st.esc.ensure(h, esc_bytes)) != NFAGG_OK) return rc;
+    // the kernels binary-search the table: a stable sort by if_index keeps the scan-in-table-order answer. Names and UDNs are
+    // escaped here, once per row of the sorted table: no kernel escapes per flow
+    st.h_names.assign(opt->names, opt->names + opt->n_names);
+    std::stable_sort(st.h_names.begin(), st.h_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
+    st.h_esc.assign(esc_bytes, 0);
+    flp_escape_row(st.h_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
+    for (uint32_t k = 0; k < opt->n_names; k++) {
+        const nfagg_intf_name& e = st.h_names[k];
+        flp_escape_row(st.h_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
+    }
+    if (opt->n_names) HIP_TRY(h, hipMemcpyAsync(st.names.p, st.h_names.data(), opt->n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(st.esc.p, st.h_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
+    FlpLineArgs& A = *args;
+    A = FlpLineArgs{};
+    A.recs = d_records; A.n = n; A.F = F; A.hash_ids = t.hash_ids;
+    split_now(opt->now_unix_ns, A.P.now_sec, A.P.now_nsec);
+    A.P.mono_now = opt->mono_now_ns;
+    A.P.time_received = opt->time_received_s;
+    A.P.names = st.names.as<const nfagg_intf_name>(); A.P.esc = st.esc.as<const uint8_t>(); A.P.n_names = opt->n_names;
+    A.P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(A.P.agent_ip_w, opt->agent_ip, 16);
+    if (t.level >= FlpLevel::Tls) {
+        A.T.ids = t.tls->d_mem.as<const uint16_t>();
+        A.T.rows = t.tls->d_mem.as<const uint8_t>() + t.tls->ids.size() * sizeof(uint16_t);
+        for (uint32_t k = 0; k < kTlsKinds; k++) A.T.n[k] = t.tls->n[k];
+    }
+    if (t.level >= FlpLevel::K8s) {
+        if ((rc = st.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+        A.K = k8s_dev(t.k8s); A.k8s_rows = st.k8s_rows.as<const uint32_t>();
+        const hipError_t e = launch_k8s_resolve(d_records, n, A.K, st.k8s_rows.as<uint32_t>(), h->stream);
+        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
+    }
+    if (t.level >= FlpLevel::Net) {
+        if ((rc = st.net_rows.ensure(h, n * sizeof(uint2))) != NFAGG_OK) return rc;
+        A.N = net_dev(t.net); A.net_rows = st.net_rows.as<const uint2>();
+        const hipError_t e = launch_net_resolve(d_records, n, A.N, A.k8s_rows, t.k8s->d_host_ids.as<const uint32_t>(), A.K.n_rows, net_reporter(t.k8s, opt),
+                                                st.net_rows.as<uint2>(), h->stream);
+        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
+    }
+    return NFAGG_OK;
+}
+
+// From *_tls up the network events are an option: rows and table both, or neither (*ne = nullptr).
 static int netev_optional(nfagg_handle* h, const NetevArgs** ne, size_t n) {
     if (!*ne) return NFAGG_OK;
-    const NetevArgs& a = **ne;
-    if ((a.rows != nullptr) != (a.table != nullptr) && (n || a.rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
-    if (!a.table) *ne = nullptr;
-    return NFAGG_OK;
+    const int rc = netev_together(h, **ne, n);
+    if (rc == NFAGG_OK && !(*ne)->table) *ne = nullptr;
+    return rc;
 }
 
-// feat (optional): DEVICE pointers. The launchers pick the kernels' feature policy: neither feat nor ne the plain line, ne (the
-// *_netev and *_tls entry points) the one with the NetworkEvents hook, tls the TLS names on top of either.
+// t.level says which tables the entry point takes; one it takes is required. A pointer t has above its level is not looked at.
+static bool flp_null_argument(const nfagg_handle* h, const FlpLineTables& t, const void* records, size_t n, const void* offsets, const size_t* out_bytes) {
+    return !h || (t.level >= FlpLevel::Tls && !t.tls) || (t.level >= FlpLevel::K8s && !t.k8s) || (t.level >= FlpLevel::Net && !t.net) || !out_bytes ||
+           !offsets || (n && !records) || (t.level == FlpLevel::Conn && n && !t.hash_ids);
+}
+
+// feat (optional): DEVICE pointers. The launchers pick the kernels' feature policy from the parts: neither feat nor ne the plain
+// line, ne (the *_netev entry points, and from *_tls up) the one with the NetworkEvents hook; t.level puts the TLS names, the
+// Kubernetes keys, the transform network keys and extract conntrack's keys on top (hash ids in DEVICE memory). From FlpLevel::Tls
+// on no record is deferred: flags and counter are not used.
 static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                                  const FlpTlsArgs* tls, const nfagg_flp_options* opt,
+                                  const FlpLineTables& t, const nfagg_flp_options* opt,
                                   void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
                                   size_t* n_deferred, size_t* out_bytes) {
+    const bool tls = t.level >= FlpLevel::Tls;
     int rc;
     if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
-    if ((rc = encode_flp_check(h, opt)) != NFAGG_OK) return rc;
-    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !d_line_offsets ||
-        (n && !d_records) || (tls && tls->with_conn && n && !tls->hash_ids))
-        return fail(h, NFAGG_EINVAL, "null argument");
-    if (tls && tls->with_conn && ((uintptr_t)tls->hash_ids & 7u) != 0) return fail(h, NFAGG_EINVAL, "hash ids must be 8-byte aligned");
-    if (tls && (tls->names->h != h || !tls->names->d_mem)) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
-    const nfagg_k8s_table* k8s = tls && tls->with_k8s ? tls->k8s : nullptr;
-    if (k8s && (k8s->h != h || !k8s->d_slots)) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
-    const nfagg_net_table* net = k8s && tls->with_net ? tls->net : nullptr;
-    if (net && (net->h != h || !net->d_mem)) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
+    if ((rc = check_flp_options(h, opt)) != NFAGG_OK) return rc;
+    if (flp_null_argument(h, t, d_records, n, d_line_offsets, out_bytes)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (t.level == FlpLevel::Conn && ((uintptr_t)t.hash_ids & 7u) != 0) return fail(h, NFAGG_EINVAL, "hash ids must be 8-byte aligned");
+    if ((rc = check_flp_tables(h, t)) != NFAGG_OK) return rc;
     if ((((uintptr_t)d_records | (uintptr_t)d_out) & 15u) != 0) return fail(h, NFAGG_EINVAL, "device buffers must be 16-byte aligned");
     PbFeat F{};
     if (feat && (rc = device_features(h, feat, &F)) != NFAGG_OK) return rc;
     if (ne && (rc = device_netev(h, ne, n, &F)) != NFAGG_OK) return rc;
     if (n_deferred) *n_deferred = 0;
     bool done;
-    if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, opt->names, opt->n_names, &done)) != NFAGG_OK || done) return rc;
-    FlpParams P{};
-    uint32_t* rows;
-    if ((rc = stage_flp(h, n, opt, &P, &rows)) != NFAGG_OK) return rc;
-    uint32_t* counter = h->enc.flp_n_deferred.as<uint32_t>();
-    TlsDev T{};
-    if (tls) {
-        T.ids = tls->names->d_mem.as<const uint16_t>();
-        T.rows = tls->names->d_mem.as<const uint8_t>() + tls->names->ids.size() * sizeof(uint16_t);
-        for (uint32_t k = 0; k < kTlsKinds; k++) T.n[k] = tls->names->n[k];
-    }
-    const PbFeat* Fp = (feat || ne) ? &F : nullptr;                   // neither: the plain line
-    const TlsDev* Tp = tls ? &T : nullptr;
-    if (k8s) {
-        if ((rc = h->enc.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-        uint32_t* k8s_rows = h->enc.k8s_rows.as<uint32_t>();
-        const K8sDev K = k8s_dev(k8s);
-        hipError_t e = launch_k8s_resolve(d_records, n, K, k8s_rows, h->stream);
-        if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
-        if (net) {
-            if ((rc = h->enc.net_rows.ensure(h, n * sizeof(uint2))) != NFAGG_OK) return rc;
-            const uint2* net_rows = h->enc.net_rows.as<const uint2>();
-            const NetDev N = net_dev(net);
-            e = launch_net_resolve(d_records, n, N, k8s_rows, k8s->d_host_ids.as<const uint32_t>(), K.n_rows, net_reporter(k8s, opt), h->enc.net_rows.as<uint2>(),
-                                   h->stream);
-            if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
-            if (tls->with_conn) {
-                const uint64_t* ids = tls->hash_ids;
-                return encode_two_pass(h, n, "FLP JSON flow logs of extract conntrack", "write", d_out, out_cap, out_bytes, nullptr,
-                    [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-                        return launch_flp_conn_size(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, ids, rows, local_off, block_sum, block_base, h->stream); },
-                    [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-                        return launch_flp_conn_write(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, ids, rows, local_off, block_base, d_out,
-                                                     d_line_offsets, h->stream); });
-            }
-            return encode_two_pass(h, n, "FLP JSON with transform network keys", "write", d_out, out_cap, out_bytes, nullptr,
-                [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-                    return launch_flp_net_size(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_sum, block_base, h->stream); },
-                [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-                    return launch_flp_net_write(d_records, n, P, Fp, T, K, N, k8s_rows, net_rows, rows, local_off, block_base, d_out, d_line_offsets,
-                                                h->stream); });
-        }
-        return encode_two_pass(h, n, "FLP JSON with Kubernetes keys", "write", d_out, out_cap, out_bytes, nullptr,
-            [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-                return launch_flp_k8s_size(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_sum, block_base, h->stream); },
-            [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-                return launch_flp_k8s_write(d_records, n, P, Fp, T, K, k8s_rows, rows, local_off, block_base, d_out, d_line_offsets, h->stream); });
-    }
+    if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, nullptr, 0, &done)) != NFAGG_OK || done) return rc;
+    auto& S = h->enc;
+    if ((rc = S.flp_rows.ensure(h, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+    if ((rc = S.flp_n_deferred.ensure(h, 16)) != NFAGG_OK) return rc;
+    HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
+    FlpLineArgs A;
+    if ((rc = stage_flp_line(h, d_records, n, opt, F, t, FlpLineStage{S.names, S.flp_esc, S.k8s_rows, S.net_rows, S.h_names, S.h_flp_esc}, &A)) != NFAGG_OK) return rc;
+    uint32_t* rows = S.flp_rows.as<uint32_t>();
+    uint32_t* counter = S.flp_n_deferred.as<uint32_t>();
+    static const char* const kWhat[5] = {"FLP JSON", "FLP JSON with TLS names", "FLP JSON with Kubernetes keys", "FLP JSON with transform network keys",
+                                         "FLP JSON flow logs of extract conntrack"};
+    const char* what = !tls && (feat || ne) ? "FLP JSON content" : kWhat[(int)t.level];
     size_t deferred_unused;
-    return encode_two_pass(h, n, tls ? "FLP JSON with TLS names" : Fp ? "FLP JSON content" : "FLP JSON", "write", d_out, out_cap, out_bytes,
-        tls ? nullptr : n_deferred ? n_deferred : &deferred_unused,
+    return encode_two_pass(h, n, what, "write", d_out, out_cap, out_bytes, tls ? nullptr : n_deferred ? n_deferred : &deferred_unused,
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
-            return launch_flp_size(d_records, n, P, Fp, Tp, rows, local_off, block_sum, block_base, counter, h->stream); },
+            return launch_flp_size(A, t.level, rows, local_off, block_sum, block_base, counter, h->stream); },
         [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
-            return launch_flp_write(d_records, n, P, Fp, Tp, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
+            return launch_flp_write(A, t.level, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
 }
 
-// feat (optional): HOST pointers, uploaded beside the records, as are the rows of ne
+// feat (optional): HOST pointers, uploaded beside the records, as are the rows of ne and the hash ids of FlpLevel::Conn
 static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* feat, const NetevArgs* ne,
-                                const FlpTlsArgs* tls, const nfagg_flp_options* opt,
+                                const FlpLineTables& t, const nfagg_flp_options* opt,
                                 void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
                                 size_t* n_deferred, size_t* out_bytes) {
-    int rc = encode_flp_check(h, opt);
+    int rc = check_flp_options(h, opt);
     if (rc != NFAGG_OK) return rc;
-    if (!h || (tls && !tls->names) || (tls && tls->with_k8s && !tls->k8s) || (tls && tls->with_net && !tls->net) || !out_bytes || !line_offsets ||
-        (n && !records) || (tls && tls->with_conn && n && !tls->hash_ids))
-        return fail(h, NFAGG_EINVAL, "null argument");
-    if (tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
+    if (flp_null_argument(h, t, records, n, line_offsets, out_bytes)) return fail(h, NFAGG_EINVAL, "null argument");
+    if (t.level >= FlpLevel::Tls && (rc = netev_optional(h, &ne, n)) != NFAGG_OK) return rc;
     if (feat && feat->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
     return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
         [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
@@ -485,43 +468,43 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
             if (feat && n) { int rc2 = stage_pb_features(h, feat, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
             NetevArgs dne{};
             if (ne) { int rc2 = stage_netev_rows(h, ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
-            FlpTlsArgs dtls = tls ? *tls : FlpTlsArgs{};
-            if (dtls.with_conn) {                                         // the hash ids, uploaded
-                dtls.hash_ids = nullptr;
+            FlpLineTables dt = t;
+            if (t.level == FlpLevel::Conn) {                              // the hash ids, uploaded
+                dt.hash_ids = nullptr;
                 if (n) {
                     int rc2 = h->enc.conn_ids.ensure(h, n * sizeof(uint64_t));
                     if (rc2 != NFAGG_OK) return rc2;
-                    HIP_TRY(h, hipMemcpyAsync(h->enc.conn_ids.p, tls->hash_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-                    dtls.hash_ids = h->enc.conn_ids.as<const uint64_t>();
+                    HIP_TRY(h, hipMemcpyAsync(h->enc.conn_ids.p, t.hash_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+                    dt.hash_ids = h->enc.conn_ids.as<const uint64_t>();
                 }
             }
-            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, tls ? &dtls : nullptr, opt, d_out, out_cap, d_offsets,
+            return encode_flp_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, dt, opt, d_out, out_cap, d_offsets,
                                           deferred ? h->enc.out_extra[0].as<uint8_t>() : nullptr, n_deferred, out_bytes); });
 }
 
 int nfagg_encode_flp_json_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt,
                                  void* d_out, size_t out_cap, uint64_t* d_line_offsets, uint8_t* d_deferred,
                                  size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_device_core(h, d_records, n, nullptr, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+    return encode_flp_device_core(h, d_records, n, nullptr, nullptr, FlpLineTables{}, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json(nfagg_handle* h, const void* records, size_t n, const nfagg_flp_options* opt,
                           void* out, size_t out_cap, uint64_t* line_offsets, uint8_t* deferred,
                           size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_host_core(h, records, n, nullptr, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+    return encode_flp_host_core(h, records, n, nullptr, nullptr, FlpLineTables{}, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
 
 // features == NULL: the flows carry no parts, the call is nfagg_encode_flp_json[_device]
 int nfagg_encode_flp_json_content_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                          const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
                                          uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_device_core(h, d_records, n, d_features, nullptr, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+    return encode_flp_device_core(h, d_records, n, d_features, nullptr, FlpLineTables{}, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json_content(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
                                   const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
                                   uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
-    return encode_flp_host_core(h, records, n, features, nullptr, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+    return encode_flp_host_core(h, records, n, features, nullptr, FlpLineTables{}, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
@@ -529,7 +512,7 @@ int nfagg_encode_flp_json_content_netev_device(nfagg_handle* h, const void* d_re
                                                const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets,
                                                uint8_t* d_deferred, size_t* n_deferred, size_t* out_bytes) {
     const NetevArgs ne{d_rows, table};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, nullptr, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, FlpLineTables{}, opt, d_out, out_cap, d_line_offsets, d_deferred, n_deferred, out_bytes);
 }
 
 int nfagg_encode_flp_json_content_netev(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
@@ -537,37 +520,37 @@ int nfagg_encode_flp_json_content_netev(nfagg_handle* h, const void* records, si
                                         const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets,
                                         uint8_t* deferred, size_t* n_deferred, size_t* out_bytes) {
     const NetevArgs ne{rows, table};
-    return encode_flp_host_core(h, records, n, features, &ne, nullptr, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
+    return encode_flp_host_core(h, records, n, features, &ne, FlpLineTables{}, opt, out, out_cap, line_offsets, deferred, n_deferred, out_bytes);
 }
 
 // ---- direct-FLP JSON with the TLS names, the Kubernetes keys, the transform network keys: the tables are nfagg_api_tables.hip's
-uint32_t nfagg_flp_json_tls_max_line(int policy) { return flp_tls_max_line(policy); }
+uint32_t nfagg_flp_json_tls_max_line(int policy) { return flp_max_line(FlpLevel::Tls, policy); }
 
 int nfagg_encode_flp_json_tls_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                      const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
                                      const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
     const NetevArgs ne{d_rows, netev_table};
-    const FlpTlsArgs tls{tls_names};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+    const FlpLineTables t{FlpLevel::Tls, tls_names};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, t, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
 }
 
 int nfagg_encode_flp_json_tls(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
                               const uint16_t* rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
                               const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
     const NetevArgs ne{rows, netev_table};
-    const FlpTlsArgs tls{tls_names};
-    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+    const FlpLineTables t{FlpLevel::Tls, tls_names};
+    return encode_flp_host_core(h, records, n, features, &ne, t, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
 }
 
-uint32_t nfagg_flp_json_k8s_max_line(int policy) { return flp_k8s_max_line(policy); }
+uint32_t nfagg_flp_json_k8s_max_line(int policy) { return flp_max_line(FlpLevel::K8s, policy); }
 
 int nfagg_encode_flp_json_k8s_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                      const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
                                      const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* d_out, size_t out_cap,
                                      uint64_t* d_line_offsets, size_t* out_bytes) {
     const NetevArgs ne{d_rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+    const FlpLineTables t{FlpLevel::K8s, tls_names, k8s_table};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, t, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
 }
 
 int nfagg_encode_flp_json_k8s(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
@@ -575,19 +558,19 @@ int nfagg_encode_flp_json_k8s(nfagg_handle* h, const void* records, size_t n, co
                               const nfagg_k8s_table* k8s_table, const nfagg_flp_options* opt, void* out, size_t out_cap,
                               uint64_t* line_offsets, size_t* out_bytes) {
     const NetevArgs ne{rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table};
-    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+    const FlpLineTables t{FlpLevel::K8s, tls_names, k8s_table};
+    return encode_flp_host_core(h, records, n, features, &ne, t, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
 }
 
-uint32_t nfagg_flp_json_net_max_line(int policy) { return flp_net_max_line(policy); }
+uint32_t nfagg_flp_json_net_max_line(int policy) { return flp_max_line(FlpLevel::Net, policy); }
 
 int nfagg_encode_flp_json_net_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                      const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
                                      const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
                                      void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
     const NetevArgs ne{d_rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+    const FlpLineTables t{FlpLevel::Net, tls_names, k8s_table, net_table};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, t, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
 }
 
 int nfagg_encode_flp_json_net(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
@@ -595,20 +578,20 @@ int nfagg_encode_flp_json_net(nfagg_handle* h, const void* records, size_t n, co
                               const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_flp_options* opt,
                               void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
     const NetevArgs ne{rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table};
-    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+    const FlpLineTables t{FlpLevel::Net, tls_names, k8s_table, net_table};
+    return encode_flp_host_core(h, records, n, features, &ne, t, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
 }
 
 // ---- extract conntrack's flow logs: the *_net line with _HashId and _RecordType, no line for a flow the stage does not track
-uint32_t nfagg_flp_json_conn_max_line(int policy) { return flp_conn_max_line(policy); }
+uint32_t nfagg_flp_json_conn_max_line(int policy) { return flp_max_line(FlpLevel::Conn, policy); }
 
 int nfagg_encode_flp_json_conn_device(nfagg_handle* h, const void* d_records, size_t n, const nfagg_pb_features* d_features,
                                       const uint16_t* d_rows, const nfagg_netev_table* netev_table, const nfagg_tls_names* tls_names,
                                       const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const uint64_t* d_hash_ids,
                                       const nfagg_flp_options* opt, void* d_out, size_t out_cap, uint64_t* d_line_offsets, size_t* out_bytes) {
     const NetevArgs ne{d_rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table, true, d_hash_ids};
-    return encode_flp_device_core(h, d_records, n, d_features, &ne, &tls, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
+    const FlpLineTables t{FlpLevel::Conn, tls_names, k8s_table, net_table, d_hash_ids};
+    return encode_flp_device_core(h, d_records, n, d_features, &ne, t, opt, d_out, out_cap, d_line_offsets, nullptr, nullptr, out_bytes);
 }
 
 int nfagg_encode_flp_json_conn(nfagg_handle* h, const void* records, size_t n, const nfagg_pb_features* features,
@@ -616,8 +599,8 @@ int nfagg_encode_flp_json_conn(nfagg_handle* h, const void* records, size_t n, c
                                const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const uint64_t* hash_ids,
                                const nfagg_flp_options* opt, void* out, size_t out_cap, uint64_t* line_offsets, size_t* out_bytes) {
     const NetevArgs ne{rows, netev_table};
-    const FlpTlsArgs tls{tls_names, true, k8s_table, true, net_table, true, hash_ids};
-    return encode_flp_host_core(h, records, n, features, &ne, &tls, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
+    const FlpLineTables t{FlpLevel::Conn, tls_names, k8s_table, net_table, hash_ids};
+    return encode_flp_host_core(h, records, n, features, &ne, t, opt, out, out_cap, line_offsets, nullptr, nullptr, out_bytes);
 }
 
 // ---- extract conntrack's conversation records as JSON lines (nfagg_conn_json.hip): the layout, then the two entry points

@@ -44,7 +44,7 @@ struct LokiPlan {
     size_t tmp_bytes = 0;
     bool valid = false, content = false;
     DevBuf in_ne_rows;
-    LokiArgs A{};
+    FlpLineArgs A{};
     LokiDev L{};
     LokiPlanDev D{};
     LokiCtl counts{};
@@ -256,29 +256,19 @@ int nfagg_loki_plan_device(nfagg_handle* h, const void* d_records, size_t n, con
                            const nfagg_net_table* net, const uint64_t* d_hash_ids, const nfagg_flp_options* opt, const nfagg_loki_table* table,
                            int64_t now_unix_ns, nfagg_loki_stream* d_streams, uint32_t stream_cap, nfagg_loki_group* d_groups, uint32_t group_cap,
                            uint8_t* d_deferred, nfagg_loki_counts* counts) {
-    if (!opt) return fail(h, NFAGG_EINVAL, "null options");
-    if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
-    if (opt->unknown_len > 16 || (opt->n_names && !opt->names)) return fail(h, NFAGG_EINVAL, "bad namer table");
-    for (uint32_t k = 0; k < opt->n_names; k++) {
-        if (opt->names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
-        if (opt->names[k].udn_len > 63) return fail(h, NFAGG_EINVAL, "namer row %u: udn too long", k);
-    }
+    int rc = check_flp_options(h, opt);
+    if (rc != NFAGG_OK) return rc;
     if (!h || !tls_names || !k8s || !net || !table || !counts || (n && !d_records) || (stream_cap && !d_streams) || (group_cap && !d_groups))
         return fail(h, NFAGG_EINVAL, "null argument");
-    if ((d_rows != nullptr) != (netev_table != nullptr) && (n || d_rows)) return fail(h, NFAGG_EINVAL, "network-events rows and table go together");
+    const NetevArgs ne{d_rows, netev_table};
+    if ((rc = netev_together(h, ne, n)) != NFAGG_OK) return rc;
     if (d_rows && !d_features) return fail(h, NFAGG_EINVAL, "network-events rows without the flows' feature parts");
-    if (netev_table && (netev_table->h != h || !netev_table->d_rows)) return fail(h, NFAGG_EINVAL, "the network-events table was not created for this handle");
-    if (((uintptr_t)d_rows & 7u) != 0) return fail(h, NFAGG_EINVAL, "network-events rows must be 8-byte aligned");
     PbFeat F{};
-    if (d_features) { const int rcf = device_features(h, d_features, &F); if (rcf != NFAGG_OK) return rcf; }
-    if (d_rows && netev_table) {
-        F.ne_rows = d_rows; F.ne_tab = netev_table->d_rows.as<const uint8_t>(); F.ne_blob = netev_table->d_blob.as<const uint8_t>();
-        F.ne_n = (uint32_t)netev_table->rows.size();
-    }
+    if (netev_table && (rc = device_netev(h, &ne, n, &F)) != NFAGG_OK) return rc;
+    if (d_features && (rc = device_features(h, d_features, &F)) != NFAGG_OK) return rc;
     const bool content = d_features != nullptr;
-    if (tls_names->h != h || !tls_names->d_mem) return fail(h, NFAGG_EINVAL, "the TLS name table was not created for this handle");
-    if (k8s->h != h || !k8s->d_slots) return fail(h, NFAGG_EINVAL, "the Kubernetes table was not created for this handle");
-    if (net->h != h || !net->d_mem) return fail(h, NFAGG_EINVAL, "the net table was not created for this handle");
+    const FlpLineTables t{FlpLevel::Conn, tls_names, k8s, net, d_hash_ids};       // d_hash_ids nullptr: no conntrack stage
+    if ((rc = check_flp_tables(h, t)) != NFAGG_OK) return rc;
     if (table->h != h || !table->d_rows) return fail(h, NFAGG_EINVAL, "the Loki table was not created for this handle");
     if (table->k8s != k8s || table->net != net) return fail(h, NFAGG_EINVAL, "the Loki table was built over other tables than the call's");
     if (stream_cap > kLokiMaxStreams) return fail(h, NFAGG_ERANGE, "a cap of %u streams, more than %u", stream_cap, kLokiMaxStreams);
@@ -289,47 +279,22 @@ int nfagg_loki_plan_device(nfagg_handle* h, const void* d_records, size_t n, con
     LokiPlan& S = *plan_of(h);
     S.valid = false;
     S.counts = LokiCtl{};
-    if (!n) { S.valid = true; S.A = LokiArgs{}; S.content = false; return NFAGG_OK; }
+    if (!n) { S.valid = true; S.A = FlpLineArgs{}; S.content = false; return NFAGG_OK; }
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t slots = (size_t)std::max<uint64_t>(next_pow2(2ull * std::min<uint64_t>(n, kLokiMaxStreams)), kLokiMinSlots);
     const size_t n_streams_max = std::min<size_t>(n, kLokiMaxStreams);
     S.tmp_bytes = loki_tmp_bytes(n);
-    int rc;
     struct { DevBuf* b; size_t bytes; } need[] = {
         {&S.ctl, 256}, {&S.keys, slots * 16}, {&S.first, slots * 4}, {&S.sid, slots * 4}, {&S.slot_of, n * 4}, {&S.rows8, n * 32}, {&S.ts, n * 16},
         {&S.lens, n * 4}, {&S.deferred, n + 16}, {&S.flag, (n + 1) * 4}, {&S.rank, (n + 1) * 4}, {&S.streams, n_streams_max * sizeof(nfagg_loki_stream)},
         {&S.pinc, (n + 1) * 8}, {&S.cuts, n * 4}, {&S.key, n * 8}, {&S.key_sorted, (n + 1) * 8}, {&S.val, n * 4}, {&S.perm, n * 4}, {&S.gidx, (n + 1) * 4},
         {&S.esz, (n + 1) * 4}, {&S.E, (n + 1) * 8}, {&S.gs, n * 4}, {&S.groups, n * sizeof(nfagg_loki_group)}, {&S.tmp, S.tmp_bytes},
-        {&S.names, (size_t)(opt->n_names + 1) * sizeof(nfagg_intf_name)}, {&S.esc, (size_t)(opt->n_names + 1) * kFlpEscRowBytes},
-        {&S.k8s_rows, n * 8}, {&S.net_rows, n * 8}, {&S.scan_local, (n + 1) * 4}, {&S.scan_sum, ((n + 1) / 1024 + 2) * 4}, {&S.scan_base, ((n + 1) / 1024 + 3) * 8}};
+        {&S.scan_local, (n + 1) * 4}, {&S.scan_sum, ((n + 1) / 1024 + 2) * 4}, {&S.scan_base, ((n + 1) / 1024 + 3) * 8}};
     for (auto& q : need) if ((rc = q.b->ensure(h, q.bytes)) != NFAGG_OK) return rc;
     const LokiScan X{S.scan_local.as<uint32_t>(), S.scan_sum.as<uint32_t>(), S.scan_base.as<uint64_t>()};      // behind ensure: a growth moves the blocks
-    // the namer table, stably sorted by if_index, and its escaped rows: as the direct-FLP encoders stage them
-    S.h_names.assign(opt->names, opt->names + opt->n_names);
-    std::stable_sort(S.h_names.begin(), S.h_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
-    S.h_esc.assign((size_t)(opt->n_names + 1) * kFlpEscRowBytes, 0);
-    auto esc_row = [&](size_t k, const char* name, uint32_t name_len, const char* udn, uint32_t udn_len) {
-        uint8_t* row = S.h_esc.data() + k * kFlpEscRowBytes;
-        const uint16_t nl = (uint16_t)flp_escape(name, name_len, row + kFlpEscNameOff), ul = (uint16_t)flp_escape(udn, udn_len, row + kFlpEscUdnOff);
-        memcpy(row, &nl, 2); memcpy(row + 2, &ul, 2);
-    };
-    esc_row(0, opt->unknown_name, opt->unknown_len, "", 0);
-    for (uint32_t k = 0; k < opt->n_names; k++) esc_row(k + 1, S.h_names[k].name, S.h_names[k].name_len, S.h_names[k].udn, S.h_names[k].udn_len);
-    if (opt->n_names) HIP_TRY(h, hipMemcpyAsync(S.names.p, S.h_names.data(), opt->n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(S.esc.p, S.h_esc.data(), S.h_esc.size(), hipMemcpyHostToDevice, h->stream));
-    LokiArgs& A = S.A;
-    A = LokiArgs{};
-    A.recs = d_records; A.n = n; A.F = F;
+    FlpLineArgs& A = S.A;                                   // into the plan's own staging: the write reads both again
+    if ((rc = stage_flp_line(h, d_records, n, opt, F, t, FlpLineStage{S.names, S.esc, S.k8s_rows, S.net_rows, S.h_names, S.h_esc}, &A)) != NFAGG_OK) return rc;
     S.content = content;
-    split_now(opt->now_unix_ns, A.P.now_sec, A.P.now_nsec);
-    A.P.mono_now = opt->mono_now_ns; A.P.time_received = opt->time_received_s;
-    A.P.names = S.names.as<const nfagg_intf_name>(); A.P.esc = S.esc.as<const uint8_t>(); A.P.n_names = opt->n_names;
-    A.P.agent_nil = opt->agent_ip_nil ? 1u : 0u; memcpy(A.P.agent_ip_w, opt->agent_ip, 16);
-    A.T.ids = tls_names->d_mem.as<const uint16_t>();
-    A.T.rows = tls_names->d_mem.as<const uint8_t>() + tls_names->ids.size() * sizeof(uint16_t);
-    for (uint32_t k = 0; k < kTlsKinds; k++) A.T.n[k] = tls_names->n[k];
-    A.K = k8s_dev(k8s); A.N = net_dev(net);
-    A.k8s_rows = S.k8s_rows.as<const uint32_t>(); A.net_rows = S.net_rows.as<const uint2>(); A.hash_ids = d_hash_ids;
     LokiDev& L = S.L;
     L = LokiDev{};
     L.rows = table->d_rows.as<const K8sRow>(); L.blob = table->d_blob.as<const uint8_t>();
@@ -344,10 +309,7 @@ int nfagg_loki_plan_device(nfagg_handle* h, const void* d_records, size_t n, con
     HIP_TRY(h, hipMemsetAsync(S.ctl.p, 0, 256, h->stream));
     HIP_TRY(h, hipMemsetAsync(S.keys.p, 0, slots * 16, h->stream));
     HIP_TRY(h, hipMemsetAsync(S.first.p, 0xff, slots * 4, h->stream));
-    hipError_t e = launch_k8s_resolve(d_records, n, A.K, S.k8s_rows.as<uint32_t>(), h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
-    e = launch_net_resolve(d_records, n, A.N, A.k8s_rows, k8s->d_host_ids.as<const uint32_t>(), A.K.n_rows, net_reporter(k8s, opt), S.net_rows.as<uint2>(), h->stream);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
+    hipError_t e;
     if ((e = launch_loki_key(A, content, L, D, h->stream)) != hipSuccess) return fail(h, NFAGG_EDEVICE, "Loki key launch failed: %s", hipGetErrorString(e));
     if ((e = launch_loki_rank(n, D, S.flag.as<uint32_t>(), S.rank.as<uint32_t>(), S.streams.as<nfagg_loki_stream>(), S.tmp.p, S.tmp_bytes, h->stream)) != hipSuccess)
         return fail(h, NFAGG_EDEVICE, "Loki stream rank failed: %s", hipGetErrorString(e));

@@ -106,6 +106,20 @@ K8sDev k8s_dev(const nfagg_k8s_table* t);
 // The reporter of a call for reinterpret_direction: the id of AgentIP's text among the table's host IPs, or kNetNoHost.
 uint32_t net_reporter(const nfagg_k8s_table* k8s, const nfagg_flp_options* opt);
 
+// The network events of a call: the flows' rows (DEVICE memory where a PbFeat is filled from them) and the table they index.
+struct NetevArgs { const uint16_t* rows; const nfagg_netev_table* table; };
+// The tables and ids a call's level takes (nfagg_flp.h: FlpLevel); what lies above the level is not looked at.
+struct FlpLineTables {
+    FlpLevel level = FlpLevel::Plain;
+    const nfagg_tls_names* tls = nullptr; const nfagg_k8s_table* k8s = nullptr; const nfagg_net_table* net = nullptr;
+    const uint64_t* hash_ids = nullptr;
+};
+// The staging stage_flp_line fills and FlpLineArgs then points into: it outlives the kernels that read the arguments.
+struct FlpLineStage {
+    DevBuf& names; DevBuf& esc; DevBuf& k8s_rows; DevBuf& net_rows;
+    std::vector<nfagg_intf_name>& h_names; std::vector<uint8_t>& h_esc;      // host copies, kept until the stream has consumed them
+};
+
 }  // namespace nfagg
 
 // The feature parts of a content call (nfagg_api_export.hip), shared by the encoders and the content metrics fold:
@@ -114,4 +128,20 @@ uint32_t net_reporter(const nfagg_k8s_table* k8s, const nfagg_flp_options* opt);
 extern "C" {
 int device_features(nfagg_handle* h, const nfagg_pb_features* feat, nfagg::PbFeat* F);
 int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, nfagg_pb_features* dfeat);
+
+// What the direct-FLP JSON encoders and write loki's plan set up alike for the line kernels (nfagg_api_export.hip). The checks
+// come one by one, because the entry points make them in different orders and the first message is part of the C ABI:
+//   check_flp_options   null options, struct_size, the namer table's rows
+//   netev_together      rows and table both, or neither
+//   device_netev        rows and table present, the table this handle's, the rows aligned; then both into F
+//   check_flp_tables    the TLS, Kubernetes and net table of t's level are this handle's
+// stage_flp_line follows them: the namer table stably sorted by if_index and its escaped rows, uploaded; FlpParams; and by t's
+// level TlsDev, k8s_dev and the Kubernetes resolve launch, net_dev and the net resolve launch, the hash ids. *A comes back filled
+// for launch_flp_size / launch_flp_write or the Loki kernels.
+int check_flp_options(nfagg_handle* h, const nfagg_flp_options* opt);
+int netev_together(nfagg_handle* h, const nfagg::NetevArgs& ne, size_t n);
+int device_netev(nfagg_handle* h, const nfagg::NetevArgs* ne, size_t n, nfagg::PbFeat* F);
+int check_flp_tables(nfagg_handle* h, const nfagg::FlpLineTables& t);
+int stage_flp_line(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt, const nfagg::PbFeat& F,
+                   const nfagg::FlpLineTables& t, const nfagg::FlpLineStage& st, nfagg::FlpLineArgs* A);
 }

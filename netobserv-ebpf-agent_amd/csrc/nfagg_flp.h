@@ -55,31 +55,6 @@ struct K8sDev {
     uint32_t has_layer;           // the table was created with a layer: every line carries K8S_FlowLayer
 };
 
-// Line lengths (0 = deferred) and the seven resolved interface rows per record (d_rows: 8 dwords per record, rows 0..6
-// and the length), block-local scan, scan of the block sums: d_block_base[ceil(n / 1024)] = total bytes afterwards. Then the
-// write pass. F (optional) names the feature parts of full BpfFlowContents as it does for the protobuf encoder; with
-// F->ne_rows the line carries the flows' network events. T (optional): TLSVersion, TLSCipherSuite and TLSGroup are looked up in
-// it and written. Without T a record that has them is deferred: no line, d_deferred[i] = 1 (where given), counted in
-// *d_n_deferred (zeroed by the caller); with T neither is touched.
-hipError_t launch_flp_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev* T, uint32_t* d_rows,
-                           uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s);
-hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev* T, const uint32_t* d_rows,
-                            const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
-                            uint8_t* d_deferred, hipStream_t s);
-// The longest line each policy can write with T (0: plain, 1: content, 2: content with network events).
-uint32_t flp_tls_max_line(int policy);
-
-// The same two passes with the Kubernetes enrichment on top of T (required): d_k8s_rows holds two rows per record, as
-// launch_k8s_resolve (nfagg_k8s.hip: one lane per flow, two probes of K) wrote them. Nothing is deferred.
-hipError_t launch_k8s_resolve(const void* d_recs, uint64_t n, const K8sDev& K, uint32_t* d_rows_out, hipStream_t s);
-hipError_t launch_flp_k8s_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                               const uint32_t* d_k8s_rows, uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base,
-                               hipStream_t s);
-hipError_t launch_flp_k8s_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                                const uint32_t* d_k8s_rows, const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base,
-                                void* d_out, uint64_t* d_line_offsets, hipStream_t s);
-uint32_t flp_k8s_max_line(int policy);
-
 // The table of nfagg_net_table_create on the device (nfagg_net.h): the CIDR list in walk order, every entry normalised so
 // that one masked compare of the 16 address bytes decides Contains within the family (an IPv4 network carries the
 // v4-mapped prefix in `net` and twelve 0xff bytes in front of its mask; an IPv6 one is flagged, and a v4-mapped address
@@ -98,28 +73,40 @@ struct NetDev {
     uint32_t n_cidrs, n_labels, flags;
 };
 
-// The join of nfagg_net_resolve (nfagg_net.hip: one lane per flow): 8 bytes per record, nfagg_net_row. d_k8s_rows / d_host_ids
+// The two joins a line may carry, resolved ahead of the line kernels, one lane per flow. launch_k8s_resolve (nfagg_k8s.hip): two
+// probes of K, two rows per record. launch_net_resolve (nfagg_net.hip): 8 bytes per record, nfagg_net_row; d_k8s_rows / d_host_ids
 // / reporter: the flows' Kubernetes rows, the rows' interned host-IP ids and the reporter's id (kNetNoHost: no row has its
 // text); read only with NFAGG_NET_REINTERPRET_DIRECTION.
+hipError_t launch_k8s_resolve(const void* d_recs, uint64_t n, const K8sDev& K, uint32_t* d_rows_out, hipStream_t s);
 hipError_t launch_net_resolve(const void* d_recs, uint64_t n, const NetDev& N, const uint32_t* d_k8s_rows, const uint32_t* d_host_ids,
                               uint32_t n_k8s_rows, uint32_t reporter, uint2* d_out, hipStream_t s);
-hipError_t launch_flp_net_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                               const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, uint32_t* d_rows, uint32_t* d_local_off,
-                               uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s);
-hipError_t launch_flp_net_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                                const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint32_t* d_rows,
-                                const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s);
-uint32_t flp_net_max_line(int policy);
 
-// The same two passes as extract conntrack's flow logs (nfagg_conn_meta.h): d_hash_ids holds one id per record, as
-// launch_conn_fold wrote them. A flow the stage does not track gets a zero-length line; the others end in _HashId and _RecordType.
-hipError_t launch_flp_conn_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                                const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint64_t* d_hash_ids, uint32_t* d_rows,
-                                uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s);
-hipError_t launch_flp_conn_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                                 const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint64_t* d_hash_ids,
-                                 const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out,
-                                 uint64_t* d_line_offsets, hipStream_t s);
-uint32_t flp_conn_max_line(int policy);
+// What a line can carry, each level on top of the one before it: the TLS names of T; the Kubernetes keys of K and k8s_rows; the
+// transform network keys of N and net_rows; extract conntrack's two keys from hash_ids (one id per record, as launch_conn_fold
+// wrote them), and no line for a flow that stage does not track. Below Tls a record with TLS names is deferred.
+enum class FlpLevel : int { Plain, Tls, K8s, Net, Conn };
+
+// The arguments of the line kernels at every level, and of write loki's (nfagg_loki.h). A level reads what it names above and
+// nothing of the rest. F: every pointer null for the plain line; with F.ne_rows the line carries the flows' network events.
+struct FlpLineArgs {
+    const void* recs; uint64_t n; FlpParams P; PbFeat F; TlsDev T; K8sDev K; NetDev N;
+    const uint32_t* k8s_rows; const uint2* net_rows; const uint64_t* hash_ids;      // write loki: hash_ids nullptr, no conntrack stage
+};
+// The base policy a call's parts select (0: plain, 1: content, 2: content with network events). Parts without a present array
+// load nothing, so which of 0 and 1 runs them changes no byte.
+inline int flp_policy(const PbFeat& F) {
+    return F.ne_rows ? 2 : (F.present || F.additional || F.dns || F.drops || F.xlat || F.quic) ? 1 : 0;
+}
+
+// Line lengths (0: deferred, or not tracked) and the seven resolved interface rows per record (d_rows: 8 dwords per record, rows
+// 0..6 and the length), block-local scan, scan of the block sums: d_block_base[ceil(n / 1024)] = total bytes afterwards. Then the
+// write pass. Below Tls a deferred record gets no line, d_deferred[i] = 1 (where given), and is counted in *d_n_deferred (zeroed
+// by the caller); from Tls on neither is touched.
+hipError_t launch_flp_size(const FlpLineArgs& A, FlpLevel level, uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum,
+                           uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s);
+hipError_t launch_flp_write(const FlpLineArgs& A, FlpLevel level, const uint32_t* d_rows, const uint32_t* d_local_off,
+                            const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, uint8_t* d_deferred, hipStream_t s);
+// The longest line a level can write over each base policy; 0 for a policy there is none of.
+uint32_t flp_max_line(FlpLevel level, int policy);
 
 }  // namespace nfagg

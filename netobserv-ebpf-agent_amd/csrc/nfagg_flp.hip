@@ -22,14 +22,13 @@
 // The kernels are k_flp_size<Feat> and k_flp_write<Feat> of nfagg_flp_line.h. This file compiles them for FlpPlain, the policy
 // of the records Accounter.evict produces: every hook empty, nothing loaded. An instantiation is a kernel of its own, so this
 // path has its own code and registers (tests/test_isa_pins.py holds it to no scratch); nfagg_flp_content.hip compiles the other
-// policies and has launch_flp_size / launch_flp_write, which select among all six.
+// policies and has launch_flp_size / launch_flp_write, which select among all fifteen.
 #include "nfagg_flp_line.h"
 
 namespace nfagg {
 
-template hipError_t flp_size_as<FlpPlain>(const void*, uint64_t, const FlpParams&, const PbFeat&, const TlsDev&, uint32_t*, uint32_t*,
-                                          uint32_t*, uint64_t*, uint32_t*, hipStream_t);
-template hipError_t flp_write_as<FlpPlain>(const void*, uint64_t, const FlpParams&, const PbFeat&, const TlsDev&, const uint32_t*,
-                                           const uint32_t*, const uint64_t*, void*, uint64_t*, uint8_t*, hipStream_t);
+template hipError_t flp_size_as<FlpPlain>(const FlpLineArgs&, uint32_t*, uint32_t*, uint32_t*, uint64_t*, uint32_t*, hipStream_t);
+template hipError_t flp_write_as<FlpPlain>(const FlpLineArgs&, const uint32_t*, const uint32_t*, const uint64_t*, void*, uint64_t*, uint8_t*,
+                                           hipStream_t);
 
 }  // namespace nfagg

@@ -15,10 +15,9 @@
 // drop it injected arrives in the drops part like any other.
 //
 // Same two passes, same window scheme, same encode_line and the same two kernels as nfagg_flp.hip (k_flp_size<Feat>,
-// k_flp_write<Feat> of nfagg_flp_line.h), with FlpContent as the feature policy: this file compiles them for FlpContent,
-// FlpContentNetev and FlpTls (nfagg_tls.h) over those two and over FlpPlain, and selects; it also compiles the kernel pair of
-// nfagg_k8s.h for FlpK8s over the three TLS policies, that of nfagg_net.h for FlpNet over those, and that of nfagg_conn_meta.h
-// for FlpConnMeta over those. A lane reads the parts its
+// k_flp_write<Feat> of nfagg_flp_line.h), with FlpContent as the feature policy: this file compiles them for FlpContent and
+// FlpContentNetev, for FlpTls (nfagg_tls.h), FlpK8s (nfagg_k8s.h), FlpNet (nfagg_net.h) and FlpConnMeta (nfagg_conn_meta.h)
+// layered over those two and over FlpPlain, and selects among all fifteen. A lane reads the parts its
 // present byte names with 16- and 8-byte loads before anything is emitted, keeps the fields the line needs in registers
 // and the DNS name in a 32-byte LDS slot of its own. The names of response codes, TCP states and drop causes sit in one
 // constant blob with an offset and a length per name; the counting pass reads only the lengths.
@@ -120,7 +119,7 @@ static_assert(kFlpnLds + kFlpcNameLds <= 32768 && kFlpnWindow >= 16384, "four wa
 // and the flow's present byte has the bit) and nothing of the others.
 struct FlpContent {
     static constexpr uint32_t kWindow = kFlpcWindow, kLds = kFlpcLds, kSideLds = kFlpcNameLds, kMaxLine = kFlpcMaxLine - kFlpcLineUnreached;
-    static constexpr bool kDefers = true;
+    static constexpr bool kDefers = true, kJoins = false, kTrackedOnly = false;
     uint32_t have = 0;          // NFAGG_FEAT_* bits of the parts that were loaded
     uint32_t add[4] = {};       // additional_metrics @16: flow_rtt (2), ipsec_encrypted_ret, eth | ipsec_encrypted << 16
     uint32_t dnsw[4] = {};      // dns_metrics @16: latency (2), id | flags << 16, eth | errno << 16 | name[0] << 24
@@ -266,113 +265,51 @@ struct FlpContentNetev : FlpContent {
     }
 };
 
-// ---- the launchers. The policy a call selects: F == nullptr the plain line, F->ne_rows network events, T the TLS names.
+// ---- the launchers. The policy a call selects: its level's layers over the base policy its parts name (flp_policy).
 template <typename Feat> struct FlpPolicy { using type = Feat; };
-template <typename Fn> static hipError_t flp_select(const PbFeat* F, const TlsDev* T, Fn fn) {
-    if (T) return !F ? fn(FlpPolicy<FlpTls<FlpPlain>>{}) : F->ne_rows ? fn(FlpPolicy<FlpTls<FlpContentNetev>>{}) : fn(FlpPolicy<FlpTls<FlpContent>>{});
-    return !F ? fn(FlpPolicy<FlpPlain>{}) : F->ne_rows ? fn(FlpPolicy<FlpContentNetev>{}) : fn(FlpPolicy<FlpContent>{});
+template <typename Base, typename Fn> static hipError_t flp_select_level(FlpLevel level, Fn fn) {
+    using Tls = FlpTls<Base>; using K8s = FlpK8s<Tls>; using Net = FlpNet<K8s>;
+    switch (level) {
+    case FlpLevel::Plain: return fn(FlpPolicy<Base>{});
+    case FlpLevel::Tls: return fn(FlpPolicy<Tls>{});
+    case FlpLevel::K8s: return fn(FlpPolicy<K8s>{});
+    case FlpLevel::Net: return fn(FlpPolicy<Net>{});
+    case FlpLevel::Conn: return fn(FlpPolicy<FlpConnMeta<Net>>{});
+    }
+    return hipErrorInvalidValue;
+}
+template <typename Fn> static hipError_t flp_select(FlpLevel level, int policy, Fn fn) {
+    return policy == 0 ? flp_select_level<FlpPlain>(level, fn) : policy == 1 ? flp_select_level<FlpContent>(level, fn)
+         : policy == 2 ? flp_select_level<FlpContentNetev>(level, fn) : hipErrorInvalidValue;
 }
 
-hipError_t launch_flp_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev* T, uint32_t* d_rows,
-                           uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s) {
-    return flp_select(F, T, [&](auto policy) {
-        return flp_size_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T ? *T : TlsDev{}, d_rows, d_local_off, d_block_sum,
-                                                            d_block_base, d_n_deferred, s); });
+hipError_t launch_flp_size(const FlpLineArgs& A, FlpLevel level, uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum,
+                           uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s) {
+    return flp_select(level, flp_policy(A.F), [&](auto policy) {
+        return flp_size_as<typename decltype(policy)::type>(A, d_rows, d_local_off, d_block_sum, d_block_base, d_n_deferred, s); });
 }
 
-hipError_t launch_flp_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev* T, const uint32_t* d_rows,
-                            const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
-                            uint8_t* d_deferred, hipStream_t s) {
-    return flp_select(F, T, [&](auto policy) {
-        return flp_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T ? *T : TlsDev{}, d_rows, d_local_off, d_block_base,
-                                                             d_out, d_line_offsets, d_deferred, s); });
+hipError_t launch_flp_write(const FlpLineArgs& A, FlpLevel level, const uint32_t* d_rows, const uint32_t* d_local_off,
+                            const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, uint8_t* d_deferred, hipStream_t s) {
+    return flp_select(level, flp_policy(A.F), [&](auto policy) {
+        return flp_write_as<typename decltype(policy)::type>(A, d_rows, d_local_off, d_block_base, d_out, d_line_offsets, d_deferred, s); });
 }
 
-// The Kubernetes enrichment: FlpK8s over the three TLS policies, in the kernel pair of nfagg_k8s.h.
-template <typename Fn> static hipError_t flp_k8s_select(const PbFeat* F, Fn fn) {
-    return !F ? fn(FlpPolicy<FlpK8s<FlpTls<FlpPlain>>>{}) : F->ne_rows ? fn(FlpPolicy<FlpK8s<FlpTls<FlpContentNetev>>>{}) : fn(FlpPolicy<FlpK8s<FlpTls<FlpContent>>>{});
-}
-
-hipError_t launch_flp_k8s_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                               const uint32_t* d_k8s_rows, uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base,
-                               hipStream_t s) {
-    return flp_k8s_select(F, [&](auto policy) {
-        return k8s_size_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, d_k8s_rows, d_rows, d_local_off, d_block_sum,
-                                                            d_block_base, s); });
-}
-
-hipError_t launch_flp_k8s_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                                const uint32_t* d_k8s_rows, const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base,
-                                void* d_out, uint64_t* d_line_offsets, hipStream_t s) {
-    return flp_k8s_select(F, [&](auto policy) {
-        return k8s_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, d_k8s_rows, d_rows, d_local_off, d_block_base,
-                                                             d_out, d_line_offsets, s); });
-}
-
-// The transform network rules: FlpNet over the three Kubernetes policies, in the kernel pair of nfagg_net.h.
-template <typename Fn> static hipError_t flp_net_select(const PbFeat* F, Fn fn) {
-    return !F ? fn(FlpPolicy<FlpNet<FlpK8s<FlpTls<FlpPlain>>>>{}) : F->ne_rows ? fn(FlpPolicy<FlpNet<FlpK8s<FlpTls<FlpContentNetev>>>>{})
-                                                                               : fn(FlpPolicy<FlpNet<FlpK8s<FlpTls<FlpContent>>>>{});
-}
-
-hipError_t launch_flp_net_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                               const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, uint32_t* d_rows, uint32_t* d_local_off,
-                               uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s) {
-    return flp_net_select(F, [&](auto policy) {
-        return net_size_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_rows, d_local_off,
-                                                            d_block_sum, d_block_base, s); });
-}
-
-hipError_t launch_flp_net_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                                const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint32_t* d_rows,
-                                const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, hipStream_t s) {
-    return flp_net_select(F, [&](auto policy) {
-        return net_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_rows, d_local_off,
-                                                             d_block_base, d_out, d_line_offsets, s); });
-}
-
-// extract conntrack's flow logs: FlpConnMeta over the three net policies, in the kernel pair of nfagg_conn_meta.h.
-template <typename Fn> static hipError_t flp_conn_select(const PbFeat* F, Fn fn) {
-    return !F ? fn(FlpPolicy<FlpConnMeta<FlpNet<FlpK8s<FlpTls<FlpPlain>>>>>{})
-              : F->ne_rows ? fn(FlpPolicy<FlpConnMeta<FlpNet<FlpK8s<FlpTls<FlpContentNetev>>>>>{}) : fn(FlpPolicy<FlpConnMeta<FlpNet<FlpK8s<FlpTls<FlpContent>>>>>{});
-}
-
-hipError_t launch_flp_conn_size(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                                const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint64_t* d_hash_ids, uint32_t* d_rows,
-                                uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s) {
-    return flp_conn_select(F, [&](auto policy) {
-        return connlog_size_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_hash_ids, d_rows,
-                                                                d_local_off, d_block_sum, d_block_base, s); });
-}
-
-hipError_t launch_flp_conn_write(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat* F, const TlsDev& T, const K8sDev& K,
-                                 const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint64_t* d_hash_ids,
-                                 const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out,
-                                 uint64_t* d_line_offsets, hipStream_t s) {
-    return flp_conn_select(F, [&](auto policy) {
-        return connlog_write_as<typename decltype(policy)::type>(d_recs, n, P, F ? *F : PbFeat{}, T, K, N, d_k8s_rows, d_net_rows, d_hash_ids, d_rows,
-                                                                 d_local_off, d_block_base, d_out, d_line_offsets, s); });
+uint32_t flp_max_line(FlpLevel level, int policy) {
+    uint32_t longest = 0;
+    (void)flp_select(level, policy, [&](auto p) { longest = decltype(p)::type::kMaxLine; return hipSuccess; });
+    return longest;
 }
 
 // write loki (nfagg_loki_line.h): FlpLoki over the two content policies, in the kernel pair of that header.
-hipError_t launch_loki_key_content(const LokiArgs& A, const LokiDev& L, const LokiPlanDev& D, hipStream_t s) {
+hipError_t launch_loki_key_content(const FlpLineArgs& A, const LokiDev& L, const LokiPlanDev& D, hipStream_t s) {
     return A.F.ne_rows ? loki_key_as<LokiOver<FlpContentNetev>>(A, L, D, s) : loki_key_as<LokiOver<FlpContent>>(A, L, D, s);
 }
-hipError_t launch_loki_write_content(const LokiArgs& A, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint8_t* d_out, hipStream_t s) {
+hipError_t launch_loki_write_content(const FlpLineArgs& A, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint8_t* d_out, hipStream_t s) {
     return A.F.ne_rows ? loki_write_as<LokiOver<FlpContentNetev>>(A, L, D, W, m, d_out, s) : loki_write_as<LokiOver<FlpContent>>(A, L, D, W, m, d_out, s);
 }
 uint32_t loki_max_entry_content(int policy) {
     return policy == 1 ? LokiOver<FlpContent>::kMaxEntry : policy == 2 ? LokiOver<FlpContentNetev>::kMaxEntry : 0u;
-}
-
-uint32_t flp_conn_max_line(int policy) { return flp_net_max_line(policy) ? flp_net_max_line(policy) + kConnMetaLineMax : 0u; }
-
-uint32_t flp_net_max_line(int policy) { return flp_k8s_max_line(policy) ? flp_k8s_max_line(policy) + kNetLineMax : 0u; }
-
-uint32_t flp_k8s_max_line(int policy) { return flp_tls_max_line(policy) ? flp_tls_max_line(policy) + kK8sLineMax : 0u; }
-
-uint32_t flp_tls_max_line(int policy) {
-    return policy == 0 ? FlpTls<FlpPlain>::kMaxLine : policy == 1 ? FlpTls<FlpContent>::kMaxLine : policy == 2 ? FlpTls<FlpContentNetev>::kMaxLine : 0u;
 }
 
 }  // namespace nfagg

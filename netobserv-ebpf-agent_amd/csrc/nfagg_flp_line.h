@@ -152,6 +152,12 @@ template <typename S> NF_DEV void esc_str(S& s, const uint8_t* p, uint32_t len) 
 NF_DEV bool flp_deferred(const Rec& r) {       // ssl_version @132, tls_cipher_suite @134, tls_key_share @136
     return r.d[33] != 0 || (r.d[34] & 0xffffu) != 0;
 }
+// What extract conntrack tracks (conntrack.go:70-74): encode_line's `ports` condition and the one k_conn_claim (nfagg_conn.hip)
+// applies. Read from the record, never from the id: a tracked flow's total may be 0.
+NF_DEV bool conn_tracked(const Rec& r) {
+    const uint32_t eth = r.eth(), proto = r.d[9] & 0xffu;
+    return (eth == 0x0800u || eth == 0x86DDu) && (proto == 6 || proto == 17 || proto == 132);
+}
 NF_DEV uint32_t flp_n_intf(const Rec& r) { const uint32_t nb = r.d[24] >> 24; return 1 + (nb > 6 ? 6 : nb); }
 
 // record.go:100-114: the first-seen interface, then the observed ones, all named for (if_index, lMAC), lMAC = dst_mac
@@ -178,11 +184,11 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
 // every hook is empty and the line is the one of decode_protobuf.go:57-127. FlpContent (nfagg_flp_content.hip) holds
 // the parts of a full BpfFlowContent, FlpContentNetev adds the flow's resolved network events. The two TLS hooks take the
 // record: they are empty in all three, and a record that would need them is deferred; FlpTls (nfagg_tls.h) fills them.
-// The three Kubernetes hooks are empty in all of these; FlpK8s (nfagg_k8s.h) fills them, in kernels of its own. So are the
-// three hooks of the transform network rules (FlowDirection, the two subnet labels); kFlagNames = false keeps dec<5> as the
-// value of Flags, and no call stands in its place. FlpNet (nfagg_net.h) fills the hooks and names the flags, in kernels of its own.
-// The last hook, in front of the closing brace, takes the two keys extract conntrack adds to a flow log; FlpConnMeta
-// (nfagg_conn_meta.h) fills it, in kernels of its own.
+// The three Kubernetes hooks are empty in all of these; FlpK8s (nfagg_k8s.h) fills them. So are the three hooks of the
+// transform network rules (FlowDirection, the two subnet labels); kFlagNames = false keeps dec<5> as the value of Flags, and no
+// call stands in its place. FlpNet (nfagg_net.h) fills the hooks and names the flags. The last hook, in front of the closing
+// brace, takes the two keys extract conntrack adds to a flow log; FlpConnMeta (nfagg_conn_meta.h) fills it. Every layer runs in
+// the one kernel pair below: an instantiation per policy, so that each keeps its own code and registers.
 //
 // What k_flp_size<Feat> and k_flp_write<Feat> ask of a policy beside the hooks, all of it known when they are compiled:
 //   kWindow   line starts a window of the write kernel takes, from its 16-byte aligned base
@@ -192,6 +198,11 @@ NF_DEV uint32_t flp_dir(const Rec& r, int k) {   // direction_first_seen @96, ob
 //             `tls` that takes the kernel's TLS name table, and the record is written
 //   kMaxLine  the longest line the policy reaches; FlpTls sizes its window from it
 //   load(F, i, slot)   reads record i's feature parts, only for a line that is measured or written
+//   kJoins    the policy has load_joins(J, i), which reads what its layers join to record i (FlpK8s the Kubernetes rows, FlpNet
+//             the net row as well, FlpConnMeta the hash id too); false: no call is compiled
+//   kTrackedOnly   a flow extract conntrack does not track (conn_tracked) gets a zero-length line and is never encoded
+//             (FlpConnMeta); false: no guard is compiled (one compiled for every policy cost the TLS write kernels 0.4-0.6 %,
+//             profiles/flp_one_kernel_pair_ab.txt)
 // A policy without data members (FlpPlain) is not asked to load: handing the kernel's F to an empty function by reference is
 // enough to change the register allocation of k_flp_write<FlpPlain> (530 instructions more). The table is
 // assigned, not handed to a setter, for the same reason.
@@ -214,6 +225,7 @@ struct NoFeat {
     template <typename S> NF_DEV void flow_direction(S&) const {}  // FlowDirection  after Flags
     template <typename S> NF_DEV void src_subnet(S&) const {}      // SrcSubnetLabel after SrcPort
     template <typename S> NF_DEV void conn_meta(S&) const {}       // _HashId _RecordType  behind ZoneId: '_' sorts above every letter a key starts with
+    static constexpr bool kJoins = false, kTrackedOnly = false;
 };
 // The plain policy: the line of the records Accounter.evict produces.
 struct FlpPlain : NoFeat {
@@ -319,12 +331,19 @@ NF_DEV void encode_line(S& s, const Rec& r, const FlpParams& P, const uint32_t (
     lit(s, "}\n");
 }
 
+// What the layers above FlpTls join to a record: FlpLineArgs' last five members, as load_joins and the kernels take them. The
+// kernels keep the arguments every policy reads where they were and take the joins as one struct behind them, so the twelve
+// kernels below FlpK8s read their arguments at the offsets they had. Taking FlpLineArgs whole moved every size kernel's scalar
+// spills; so did the five members as arguments of their own, which also moved four write kernels' scratch
+// (profiles/flp_line_args_codeobj.txt).
+struct FlpJoins { K8sDev K; NetDev N; const uint32_t* k8s_rows; const uint2* net_rows; const uint64_t* hash_ids; };
+
 // ---- kernel 1: line length per record (the seven interface rows resolved once), block-local exclusive scan. rows: 8 dwords
-// per record, rows 0..6 and the length (0 = deferred).
+// per record, rows 0..6 and the length (0: deferred, or a flow extract conntrack does not track, whose rows stay 0 as well).
 template <typename Feat>
 __global__ __launch_bounds__(kScanBlock) void k_flp_size(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T,
                                                          uint32_t* __restrict__ rows, uint32_t* __restrict__ local_off,
-                                                         uint32_t* __restrict__ block_sum, uint32_t* __restrict__ n_deferred) {
+                                                         uint32_t* __restrict__ block_sum, uint32_t* __restrict__ n_deferred, FlpJoins J) {
     constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;       // a DNS name slot per lane where the policy reads one
     constexpr bool kHolds = !std::is_empty_v<Feat>;                      // the policy has members to fill
     __shared__ uint32_t wave_tot[kScanBlock / 64];
@@ -337,13 +356,16 @@ __global__ __launch_bounds__(kScanBlock) void k_flp_size(const void* __restrict_
     if (i < n) {
         Rec r;
         load_record(recs, i, r);
-        uint32_t row[7];
-        flp_rows(tab, P.n_names, r, row);
-        if constexpr (Feat::kDefers) deferred = flp_deferred(r);
-        if (!deferred) {
+        uint32_t row[7] = {};
+        bool line = true;
+        if constexpr (Feat::kTrackedOnly) line = conn_tracked(r); else flp_rows(tab, P.n_names, r, row);
+        if constexpr (Feat::kDefers) { deferred = flp_deferred(r); line = !deferred; }
+        if (line) {
+            if constexpr (Feat::kTrackedOnly) flp_rows(tab, P.n_names, r, row);
             Feat f;
             if constexpr (kHolds) f.load(F, i, name_lds + threadIdx.x * kSlot);
             if constexpr (!Feat::kDefers) f.tls = T;
+            if constexpr (Feat::kJoins) f.load_joins(J, i);
             CountSink c;
             encode_line(c, r, P, row, f);
             len = c.n;
@@ -363,14 +385,16 @@ __global__ __launch_bounds__(kScanBlock) void k_flp_size(const void* __restrict_
 // ---- kernel 3: write. One wave per 64 consecutive records; their lines are contiguous in the output. The wave moves a
 // window along its byte range [shift, span) of the image: a window starts at a line start `lo`, takes every line that
 // starts less than Feat::kWindow bytes behind its 16-byte aligned base, and ends where the last of them ends, so a line is
-// always written whole (the buffer has the longest line's bytes of slack) and exactly once.
+// always written whole (the buffer has the longest line's bytes of slack) and exactly once. A lane without a line (deferred,
+// not tracked) is passed over.
 template <typename Feat>
 __global__ __launch_bounds__(64) void k_flp_write(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T,
                                                   const uint32_t* __restrict__ rows, const uint32_t* __restrict__ local_off,
                                                   const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
-                                                  uint64_t* __restrict__ line_offsets, uint8_t* __restrict__ deferred) {
+                                                  uint64_t* __restrict__ line_offsets, uint8_t* __restrict__ deferred, FlpJoins J) {
     constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;
     constexpr bool kHolds = !std::is_empty_v<Feat>;
+    constexpr bool kSkips = Feat::kDefers || Feat::kTrackedOnly;         // a record without a line: its parts and rows are not read
     static_assert(Feat::kLds + Feat::kSideLds <= 32768, "four waves per compute unit");
     __shared__ __align__(16) uint8_t lds[Feat::kLds];
     __shared__ __align__(16) uint8_t name_lds[kSlot ? 64 * kSlot : 16];
@@ -387,7 +411,12 @@ __global__ __launch_bounds__(64) void k_flp_write(const void* __restrict__ recs,
         const uint4 a = q[0], b = q[1];
         row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w; row[4] = b.x; row[5] = b.y; row[6] = b.z;
         my_len = b.w;                                                 // every line that is written has at least its braces
-        if constexpr (kHolds) { if (!Feat::kDefers || my_len) f.load(F, i, name_lds + threadIdx.x * kSlot); }     // a deferred record's parts are not read
+        if constexpr (kHolds) {
+            if (!kSkips || my_len) {
+                f.load(F, i, name_lds + threadIdx.x * kSlot);
+                if constexpr (Feat::kJoins) f.load_joins(J, i);
+            }
+        }
         my_off = record_off(block_base, local_off, i);
         line_offsets[i] = my_off;
         if (i == n - 1) line_offsets[n] = my_off + my_len;
@@ -413,28 +442,27 @@ __global__ __launch_bounds__(64) void k_flp_write(const void* __restrict__ recs,
 // The two launches for one policy. Each instantiation lives in one translation unit: the plain one in nfagg_flp.hip (declared
 // below, so that no other file compiles it), the others in nfagg_flp_content.hip, where launch_flp_size / launch_flp_write select.
 template <typename Feat>
-__attribute__((noinline)) hipError_t flp_size_as(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const TlsDev& T,
-                                                 uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base,
-                                                 uint32_t* d_n_deferred, hipStream_t s) {
-    const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
+__attribute__((noinline)) hipError_t flp_size_as(const FlpLineArgs& A, uint32_t* d_rows, uint32_t* d_local_off, uint32_t* d_block_sum,
+                                                 uint64_t* d_block_base, uint32_t* d_n_deferred, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)((A.n + kScanBlock - 1) / kScanBlock);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_flp_size<Feat>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, T, d_rows, d_local_off, d_block_sum, d_n_deferred);
+    hipLaunchKernelGGL(k_flp_size<Feat>, dim3(blocks), dim3(kScanBlock), 0, s, A.recs, A.n, A.P, A.F, A.T, d_rows, d_local_off, d_block_sum,
+                       d_n_deferred, FlpJoins{A.K, A.N, A.k8s_rows, A.net_rows, A.hash_ids});
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
 }
 template <typename Feat>
-__attribute__((noinline)) hipError_t flp_write_as(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const TlsDev& T,
-                                                  const uint32_t* d_rows, const uint32_t* d_local_off, const uint64_t* d_block_base,
-                                                  void* d_out, uint64_t* d_line_offsets, uint8_t* d_deferred, hipStream_t s) {
+__attribute__((noinline)) hipError_t flp_write_as(const FlpLineArgs& A, const uint32_t* d_rows, const uint32_t* d_local_off,
+                                                  const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets, uint8_t* d_deferred,
+                                                  hipStream_t s) {
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_flp_write<Feat>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_recs, n, P, F, T, d_rows, d_local_off,
-                       d_block_base, (uint8_t*)d_out, d_line_offsets, d_deferred);
+    hipLaunchKernelGGL(k_flp_write<Feat>, dim3((unsigned)((A.n + 63) / 64)), dim3(64), 0, s, A.recs, A.n, A.P, A.F, A.T, d_rows, d_local_off,
+                       d_block_base, (uint8_t*)d_out, d_line_offsets, d_deferred, FlpJoins{A.K, A.N, A.k8s_rows, A.net_rows, A.hash_ids});
     return hipGetLastError();
 }
-extern template hipError_t flp_size_as<FlpPlain>(const void*, uint64_t, const FlpParams&, const PbFeat&, const TlsDev&, uint32_t*, uint32_t*,
-                                                 uint32_t*, uint64_t*, uint32_t*, hipStream_t);
-extern template hipError_t flp_write_as<FlpPlain>(const void*, uint64_t, const FlpParams&, const PbFeat&, const TlsDev&, const uint32_t*,
-                                                  const uint32_t*, const uint64_t*, void*, uint64_t*, uint8_t*, hipStream_t);
+extern template hipError_t flp_size_as<FlpPlain>(const FlpLineArgs&, uint32_t*, uint32_t*, uint32_t*, uint64_t*, uint32_t*, hipStream_t);
+extern template hipError_t flp_write_as<FlpPlain>(const FlpLineArgs&, const uint32_t*, const uint32_t*, const uint64_t*, void*, uint64_t*,
+                                                  uint8_t*, hipStream_t);
 
 }  // namespace nfagg

@@ -55,17 +55,12 @@ struct LokiPlanDev {
     uint8_t* deferred;
 };
 
-struct LokiArgs {                 // the arguments of the line kernels, as k_connlog_size takes them
-    const void* recs; uint64_t n; FlpParams P; PbFeat F; TlsDev T; K8sDev K; NetDev N;      // F: all null for the plain line
-    const uint32_t* k8s_rows; const uint2* net_rows; const uint64_t* hash_ids;      // hash_ids nullptr: no conntrack stage
-};
-
 // Scratch of the 64-bit prefix sums: u32[count], u32[blocks], u64[blocks + 1] for the longest scan of a call (n + 1 values).
 struct LokiScan { uint32_t* local_off; uint32_t* block_sum; uint64_t* block_base; };
 
 // plan
 // content: the flows carry feature parts (A.F); with A.F.ne_rows their network events too (nfagg_flp_content.hip's policies)
-hipError_t launch_loki_key(const LokiArgs& A, bool content, const LokiDev& L, const LokiPlanDev& D, hipStream_t s);
+hipError_t launch_loki_key(const FlpLineArgs& A, bool content, const LokiDev& L, const LokiPlanDev& D, hipStream_t s);
 hipError_t launch_loki_rank(uint64_t n, const LokiPlanDev& D, uint32_t* d_flag, uint32_t* d_rank, nfagg_loki_stream* d_streams, void* d_tmp,
                             size_t tmp_bytes, hipStream_t s);
 hipError_t launch_loki_cuts(uint64_t n, const LokiPlanDev& D, uint64_t* d_pinc, uint32_t batch_size, uint32_t* d_cuts, const LokiScan& X, hipStream_t s);
@@ -87,12 +82,12 @@ struct LokiWriteDev {
 };
 hipError_t launch_loki_offsets(uint32_t m, uint32_t n_groups, uint32_t n_batches, const LokiWriteDev& W, uint64_t* d_batch_offsets,
                                uint32_t* d_batch_entries, const LokiScan& X, hipStream_t s);
-hipError_t launch_loki_write(const LokiArgs& A, bool content, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint32_t n_groups,
+hipError_t launch_loki_write(const FlpLineArgs& A, bool content, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint32_t n_groups,
                              uint8_t* d_out, hipStream_t s);
 uint32_t loki_max_entry(int policy);
 // nfagg_flp_content.hip: the same two kernels over FlpContent and FlpContentNetev (A.F.ne_rows selects)
-hipError_t launch_loki_key_content(const LokiArgs& A, const LokiDev& L, const LokiPlanDev& D, hipStream_t s);
-hipError_t launch_loki_write_content(const LokiArgs& A, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint8_t* d_out, hipStream_t s);
+hipError_t launch_loki_key_content(const FlpLineArgs& A, const LokiDev& L, const LokiPlanDev& D, hipStream_t s);
+hipError_t launch_loki_write_content(const FlpLineArgs& A, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint8_t* d_out, hipStream_t s);
 uint32_t loki_max_entry_content(int policy);
 
 }  // namespace nfagg

@@ -177,7 +177,7 @@ size_t loki_tmp_bytes(uint64_t n) {
 }
 
 // The policy a call selects, as the direct-FLP launchers do: no parts the plain line (here), else nfagg_flp_content.hip's.
-hipError_t launch_loki_key(const LokiArgs& A, bool content, const LokiDev& L, const LokiPlanDev& D, hipStream_t s) {
+hipError_t launch_loki_key(const FlpLineArgs& A, bool content, const LokiDev& L, const LokiPlanDev& D, hipStream_t s) {
     return content ? launch_loki_key_content(A, L, D, s) : loki_key_as<LokiPlain>(A, L, D, s);
 }
 
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(64) void k_loki_headers(uint32_t ng, LokiWriteDev W
     for (uint32_t k = threadIdx.x; k < lab; k += 64) p[head + k] = W.labels[l0 + k];
 }
 
-hipError_t launch_loki_write(const LokiArgs& A, bool content, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint32_t n_groups,
+hipError_t launch_loki_write(const FlpLineArgs& A, bool content, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint32_t n_groups,
                              uint8_t* d_out, hipStream_t s) {
     hipError_t e = content ? launch_loki_write_content(A, L, D, W, m, d_out, s) : loki_write_as<LokiPlain>(A, L, D, W, m, d_out, s);
     if (e != hipSuccess) return e;

@@ -12,7 +12,7 @@
 namespace nfagg {
 
 // ---- the policy: FlpConnMeta<..> whose hooks write nothing for a key that is a label or ignored. The Kubernetes blocks come
-// from the Loki table's blob (the kernels hand load_k8s a K8sDev with its rows and blob), so those two hooks are the base's.
+// from the Loki table's blob (loki_load hands load_joins a K8sDev with its rows and blob), so those two hooks are the base's.
 // The line has no newline: encode_line's last byte is counted off and, in the write kernel, lands on the first framing byte of
 // the next entry, which is written after it.
 template <typename Base> struct FlpLoki : Base {
@@ -49,14 +49,15 @@ NF_DEV uint32_t entry_size(uint32_t line, int64_t sec, int64_t nsec) {
     return 1 + vlen(body) + body;
 }
 
+// What k_flp_size / k_flp_write load for a line, then FlpLoki's two fields; the id only in a call that has ids.
 template <typename Feat>
-NF_DEV void loki_load(Feat& f, const LokiArgs& A, const LokiDev& L, uint64_t i, uint8_t* name_slot) {
-    K8sDev K = A.K;
+NF_DEV void loki_load(Feat& f, const FlpLineArgs& A, const LokiDev& L, uint64_t i, uint8_t* name_slot) {
+    FlpJoins J{A.K, A.N, A.k8s_rows, A.net_rows, A.hash_ids};
     f.load(A.F, i, name_slot);
-    K.rows = L.rows; K.blob = L.blob;                       // the policy only swaps the blob
+    J.K.rows = L.rows; J.K.blob = L.blob;                   // the policy only swaps the blob
     f.tls = A.T;
-    f.load_k8s(K, A.k8s_rows, i);
-    f.load_net(A.N, A.net_rows, i);
+    typename Feat::Net& joined = f;                         // the layers below FlpConnMeta, as the line kernels fill them
+    joined.load_joins(J, i);
     f.omit = L.omit_keys;
     f.has_conn = A.hash_ids != nullptr;
     if (A.hash_ids) f.hash_id = A.hash_ids[i];
@@ -64,7 +65,7 @@ NF_DEV void loki_load(Feat& f, const LokiArgs& A, const LokiDev& L, uint64_t i, 
 
 // ---- plan: the key kernel
 template <typename Feat>
-__global__ __launch_bounds__(kScanBlock) void k_loki_key(LokiArgs A, LokiDev L, LokiPlanDev D) {
+__global__ __launch_bounds__(kScanBlock) void k_loki_key(FlpLineArgs A, LokiDev L, LokiPlanDev D) {
     constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;       // a DNS name slot per lane where the policy reads one
     __shared__ __align__(16) uint8_t name_lds[kSlot ? kScanBlock * kSlot : 16];
     __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(kScanBlock) void k_loki_key(LokiArgs A, LokiDev L, 
 // contiguous: every position's entry, and in front of a group's first position room for the group's header, which
 // k_loki_headers fills afterwards (the copy-out writes that room too, with whatever the LDS held).
 template <typename Feat>
-__global__ __launch_bounds__(64) void k_loki_write(LokiArgs A, LokiDev L, LokiPlanDev D, LokiWriteDev W, uint32_t m, uint8_t* __restrict__ out) {
+__global__ __launch_bounds__(64) void k_loki_write(FlpLineArgs A, LokiDev L, LokiPlanDev D, LokiWriteDev W, uint32_t m, uint8_t* __restrict__ out) {
     static_assert(Feat::kLds + Feat::kSideLds <= 32768, "four waves per compute unit");
     constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;
     __shared__ __align__(16) uint8_t lds[Feat::kLds];
@@ -209,13 +210,13 @@ __global__ __launch_bounds__(64) void k_loki_write(LokiArgs A, LokiDev L, LokiPl
 
 
 template <typename Feat>
-__attribute__((noinline)) hipError_t loki_key_as(const LokiArgs& A, const LokiDev& L, const LokiPlanDev& D, hipStream_t s) {
+__attribute__((noinline)) hipError_t loki_key_as(const FlpLineArgs& A, const LokiDev& L, const LokiPlanDev& D, hipStream_t s) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_loki_key<Feat>, dim3((unsigned)((A.n + kScanBlock - 1) / kScanBlock)), dim3(kScanBlock), 0, s, A, L, D);
     return hipGetLastError();
 }
 template <typename Feat>
-__attribute__((noinline)) hipError_t loki_write_as(const LokiArgs& A, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint8_t* d_out,
+__attribute__((noinline)) hipError_t loki_write_as(const FlpLineArgs& A, const LokiDev& L, const LokiPlanDev& D, const LokiWriteDev& W, uint32_t m, uint8_t* d_out,
                                                    hipStream_t s) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_loki_write<Feat>, dim3((m + 63) / 64), dim3(64), 0, s, A, L, D, W, m, d_out);

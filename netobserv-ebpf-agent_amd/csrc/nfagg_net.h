@@ -1,5 +1,5 @@
 // nfagg_net.h — three more rules of flowlogs-pipeline's transform network stage on the direct-FLP JSON line, as a feature
-// policy on top of FlpK8s<FlpTls<Base>> and the kernel pair that runs it: reinterpret_direction
+// policy on top of FlpK8s<FlpTls<Base>> that k_flp_size / k_flp_write (nfagg_flp_line.h) run: reinterpret_direction
 // (transform_network_direction.go:32-64), add_subnet_label for SrcAddr and DstAddr (transform_network.go:129-146,185-196)
 // and decode_tcp_flags in place on Flags (transform_network.go:147-156, utils/tcp_flags.go:8-48). k_net_resolve
 // (nfagg_net.hip) does the join ahead: encode_line sees two label indexes and a direction, and no table. Device code only;
@@ -64,6 +64,7 @@ template <typename Base> struct FlpNet : Base {
                 net_len[k] = k ? m.w : m.y;
             }
     }
+    NF_DEV void load_joins(const FlpJoins& J, uint64_t i) { Base::load_joins(J, i); load_net(J.N, J.net_rows, i); }
     template <typename S> NF_DEV void src_subnet(S& s) const { if (net_len[0]) put_blob(s, net_blob + (size_t)net_off[0] * 16, net_len[0]); }
     template <typename S> NF_DEV void dst_subnet(S& s) const { if (net_len[1]) put_blob(s, net_blob + (size_t)net_off[1] * 16, net_len[1]); }
     template <typename S> NF_DEV void flow_direction(S& s) const {
@@ -73,110 +74,5 @@ template <typename Base> struct FlpNet : Base {
         if (names) tcp_flag_names(s, v); else dec<5>(s, v);
     }
 };
-
-// ---- the kernel pair: k_k8s_size / k_k8s_write (nfagg_k8s.h) with the net table and the flows' net rows as two more
-// arguments, under names of their own so that the eighteen instantiations of the two other pairs stay what they are.
-// Feat = FlpNet<FlpK8s<FlpTls<..>>>, which never defers.
-template <typename Feat>
-__global__ __launch_bounds__(kScanBlock) void k_net_size(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T, K8sDev K, NetDev N,
-                                                         const uint32_t* __restrict__ k8s_rows, const uint2* __restrict__ net_rows,
-                                                         uint32_t* __restrict__ rows, uint32_t* __restrict__ local_off,
-                                                         uint32_t* __restrict__ block_sum) {
-    constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;
-    __shared__ uint32_t wave_tot[kScanBlock / 64];
-    __shared__ __align__(16) uint8_t name_lds[kSlot ? kScanBlock * kSlot : 16];
-    __shared__ uint32_t tab_lds[kNamesLdsRows * (kNameRowBytes / 4)];
-    const uint8_t* tab = stage_names<kScanBlock>(P.names, P.n_names, tab_lds);
-    const uint64_t i = (uint64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    uint32_t len = 0;
-    if (i < n) {
-        Rec r;
-        load_record(recs, i, r);
-        uint32_t row[7];
-        flp_rows(tab, P.n_names, r, row);
-        Feat f;
-        f.load(F, i, name_lds + threadIdx.x * kSlot);
-        f.tls = T;
-        f.load_k8s(K, k8s_rows, i);
-        f.load_net(N, net_rows, i);
-        CountSink c;
-        encode_line(c, r, P, row, f);
-        len = c.n;
-        uint4* o = reinterpret_cast<uint4*>(rows + i * 8);
-        o[0] = make_uint4(row[0], row[1], row[2], row[3]);
-        o[1] = make_uint4(row[4], row[5], row[6], len);
-    }
-    block_scan(len, i, n, wave_tot, local_off, block_sum);
-}
-
-template <typename Feat>
-__global__ __launch_bounds__(64) void k_net_write(const void* __restrict__ recs, uint64_t n, FlpParams P, PbFeat F, TlsDev T, K8sDev K, NetDev N,
-                                                  const uint32_t* __restrict__ k8s_rows, const uint2* __restrict__ net_rows,
-                                                  const uint32_t* __restrict__ rows, const uint32_t* __restrict__ local_off,
-                                                  const uint64_t* __restrict__ block_base, uint8_t* __restrict__ out,
-                                                  uint64_t* __restrict__ line_offsets) {
-    constexpr uint32_t kSlot = Feat::kSideLds >= 64 * 32 ? 32 : 0;
-    static_assert(Feat::kLds + Feat::kSideLds <= 32768, "four waves per compute unit");
-    __shared__ __align__(16) uint8_t lds[Feat::kLds];
-    __shared__ __align__(16) uint8_t name_lds[kSlot ? 64 * kSlot : 16];
-    const uint64_t i0 = (uint64_t)blockIdx.x * 64, i = i0 + threadIdx.x;
-    WaveImage w(block_base, local_off, i0);
-    uint64_t my_off = 0; uint32_t my_len = 0;
-    uint32_t row[7] = {};
-    Rec r;
-    Feat f;
-    f.tls = T;
-    if (i < n) {
-        load_record(recs, i, r);
-        const uint4* q = reinterpret_cast<const uint4*>(rows + i * 8);
-        const uint4 a = q[0], b = q[1];
-        row[0] = a.x; row[1] = a.y; row[2] = a.z; row[3] = a.w; row[4] = b.x; row[5] = b.y; row[6] = b.z;
-        my_len = b.w;
-        f.load(F, i, name_lds + threadIdx.x * kSlot);
-        f.load_k8s(K, k8s_rows, i);
-        f.load_net(N, net_rows, i);
-        my_off = record_off(block_base, local_off, i);
-        line_offsets[i] = my_off;
-        if (i == n - 1) line_offsets[n] = my_off + my_len;
-    }
-    w.close(my_off + my_len, out);
-    const uint32_t p0 = w.pos(my_off);                            // my line = image bytes [p0, p0 + my_len)
-    uint32_t lo = w.shift;
-    while (lo < w.span) {                                         // the window loop of k_flp_write
-        const uint32_t base = lo & ~15u;
-        const bool mine = my_len && p0 >= lo && p0 - base < Feat::kWindow;
-        if (mine) { FlpLds s{lds + (p0 - base)}; encode_line(s, r, P, row, f); }
-        uint32_t hi = mine ? p0 + my_len : lo;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(hi, d, 64); hi = o > hi ? o : hi; }
-        __syncthreads();
-        copy_image_out(w.dst, lds, base, lo, hi);
-        __syncthreads();
-        lo = hi;
-    }
-}
-
-template <typename Feat>
-__attribute__((noinline)) hipError_t net_size_as(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const TlsDev& T, const K8sDev& K,
-                                                 const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, uint32_t* d_rows,
-                                                 uint32_t* d_local_off, uint32_t* d_block_sum, uint64_t* d_block_base, hipStream_t s) {
-    const uint32_t blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_net_size<Feat>, dim3(blocks), dim3(kScanBlock), 0, s, d_recs, n, P, F, T, K, N, d_k8s_rows, d_net_rows, d_rows, d_local_off,
-                       d_block_sum);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_scan_block_sums(d_block_sum, blocks, d_block_base, s);
-}
-template <typename Feat>
-__attribute__((noinline)) hipError_t net_write_as(const void* d_recs, uint64_t n, const FlpParams& P, const PbFeat& F, const TlsDev& T, const K8sDev& K,
-                                                  const NetDev& N, const uint32_t* d_k8s_rows, const uint2* d_net_rows, const uint32_t* d_rows,
-                                                  const uint32_t* d_local_off, const uint64_t* d_block_base, void* d_out, uint64_t* d_line_offsets,
-                                                  hipStream_t s) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_net_write<Feat>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_recs, n, P, F, T, K, N, d_k8s_rows, d_net_rows, d_rows,
-                       d_local_off, d_block_base, (uint8_t*)d_out, d_line_offsets);
-    return hipGetLastError();
-}
 
 }  // namespace nfagg

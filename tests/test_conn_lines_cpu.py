@@ -57,9 +57,10 @@ def test_calls_end_at_their_argument_checks_without_a_handle(nf):
         assert need.value == 7 and not off.any()
 
 
-def test_the_new_write_kernels_hold_at_most_32_kib_of_lds_and_are_no_flp_write(tmp_path):
-    """One size and one write kernel per policy, under names of their own; read from the code objects' metadata notes as
-    tests/test_isa_pins.py reads k_flp_write's."""
+def test_the_conn_kernels_are_flp_instantiations_within_32_kib_of_lds_and_no_copied_pair_is_left(tmp_path):
+    """One size and one write kernel per policy, as instantiations of k_flp_size / k_flp_write over FlpConnMeta; read from the code
+    objects' metadata notes as tests/test_isa_pins.py reads k_flp_write's. The kernel pairs the levels above TLS once had under
+    names of their own are gone from the library."""
     objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
     readelf = os.path.join(os.path.dirname(objdump), "llvm-readelf")
     if not (os.path.exists(objdump) and os.path.exists(readelf)):
@@ -67,17 +68,21 @@ def test_the_new_write_kernels_hold_at_most_32_kib_of_lds_and_are_no_flp_write(t
     lib = os.path.join(os.path.dirname(HERE), "netobserv-ebpf-agent_amd", "lib", "libnfagg.so")
     shutil.copy(lib, tmp_path / "libnfagg.so")
     subprocess.check_call([objdump, "--offloading", "libnfagg.so"], cwd=tmp_path, stdout=subprocess.DEVNULL)
-    found = {}
+    found, names = {}, []
     for co in sorted(glob.glob(str(tmp_path / "libnfagg.so.*gfx950*"))):
         notes = subprocess.check_output([readelf, "--notes", co], text=True)
         for entry in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
             field = lambda key: re.search(r"\.%s:\s+(\S+)" % key, entry).group(1)      # noqa: E731
-            if "k_connlog_" in field("name"):
+            names.append(field("name"))
+            if re.search(r"k_flp_(size|write)I", field("name")) and "FlpConnMeta" in field("name"):
                 found[field("name")] = int(field("group_segment_fixed_size"))
-    write = {k: v for k, v in found.items() if "k_connlog_write" in k}
+    write = {k: v for k, v in found.items() if "k_flp_write" in k}
     assert len(found) == 6 and len(write) == 3, sorted(found)
     assert all("FlpConnMeta" in k and "FlpNet" in k for k in found)
     assert all(16384 < lds <= 32768 for lds in write.values()), write
+    assert len(names) > 100, "kernel names not read: %d" % len(names)
+    left = [k for k in names if re.search(r"k_k8s_size|k_k8s_write|k_net_size|k_net_write|k_connlog_", k)]
+    assert not left, left
 
 
 def test_the_splice_on_hand_written_lines(nf):

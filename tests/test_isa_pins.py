@@ -116,7 +116,8 @@ def test_the_cut_walk_keeps_twelve_loads_in_flight(disassembly):
 
 def test_the_flp_write_kernels_keep_their_registers_and_their_four_waves(tmp_path):
     """The direct-FLP JSON kernels are one template pair (csrc/nfagg_flp_line.h: k_flp_size<Feat>, k_flp_write<Feat>), compiled
-    once per feature policy. The policy of the Accounter path (FlpPlain) sits just under the register limit; what keeps it there is
+    once per feature policy: three base policies, each alone, with the TLS names, and with the Kubernetes, transform network and
+    extract conntrack layers on top of those. The policy of the Accounter path (FlpPlain) sits just under the register limit; what keeps it there is
     that each instantiation is a kernel of its own, and a policy that leaks into the shared body (a hook taken by reference, a
     member that is not dead) shows first as scratch in that kernel. Every write kernel holds a window of LDS per wave sized for four
     waves per compute unit: 32 KiB at the most. Read from the code objects' metadata notes."""
@@ -132,7 +133,10 @@ def test_the_flp_write_kernels_keep_their_registers_and_their_four_waves(tmp_pat
             field = lambda key: re.search(r"\.%s:\s+(\S+)" % key, entry).group(1)      # noqa: E731
             if re.match(r"_ZN5nfagg11k_flp_writeI", field("name")):
                 write[field("name")] = (int(field("private_segment_fixed_size")), int(field("group_segment_fixed_size")))
-    assert len(write) == 6, "one k_flp_write per policy (plain, content, network events; each with and without TLS names): %r" % sorted(write)
+    assert len(write) == 15, "one k_flp_write per policy (plain, content, network events; each at five levels): %r" % sorted(write)
+    assert len([k for k in write if "FlpK8s" not in k]) == 6, "each base policy with and without TLS names: %r" % sorted(write)
+    for layer in ("FlpK8s", "FlpNet", "FlpConnMeta"):            # outermost: the first template argument of the kernel
+        assert len([k for k in write if re.match(r"_ZN5nfagg11k_flp_writeINS_\d+%sI" % layer, k)]) == 3, (layer, sorted(write))
     plain = [k for k in write if "FlpPlain" in k and "FlpTls" not in k]
     assert len(plain) == 1 and write[plain[0]][0] == 0, "k_flp_write<FlpPlain> spills: %r" % write
     assert all(lds <= 32768 for _, lds in write.values()), write

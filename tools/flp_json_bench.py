@@ -47,7 +47,7 @@ fold: nfagg_conn_fold_device with hash ids. Reported: the median wall time of a 
 count, scan, emit, the read-back), the connections and the discarded flows, and the bytes a flow's lanes read and write by this
 tool's own count. --k8s-trace covers the k_conn_* kernels. The flow logs follow on the same records and ids in the same run:
 nfagg_encode_flp_json_conn_device with the tables of the --net leg, whose _net line above is what its time per output byte is read
-against; --k8s-trace covers the k_connlog_* kernels. Then the conversation records, one per connection of the fold
+against; --k8s-trace covers its kernels (k_flp_* over FlpConnMeta). Then the conversation records, one per connection of the fold
 (nfagg_encode_conn_json_device, seven output fields of which two are split): each connection's first flow as its carrier, the
 partial's sums as its values; --k8s-trace covers the k_conn_json_* kernels (they match k_conn_).
 
@@ -166,7 +166,7 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_connlog_|k_filter_|k_gather|k_loki_|fillBuffer|scan|[Ss]ort|onesweep", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_filter_|k_gather|k_loki_|fillBuffer|scan|[Ss]ort|onesweep", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
             if "rocprim" in name:                           # the library's scan and sort kernels: their configuration's name and value types
