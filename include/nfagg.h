@@ -2201,6 +2201,152 @@ int nfagg_loki_write_device(nfagg_handle* h, const void* labels, const uint64_t*
  * bytes of framing; 0 for an unknown policy. */
 uint32_t nfagg_loki_max_entry(int policy);
 
+/* ------------------------------------------------------------------ */
+/* write ipfix on the device — flowlogs-pipeline's `write ipfix` stage  */
+/* (pkg/pipeline/write/write_ipfix.go) behind a direct-FLP pipeline:    */
+/* the ENRICHED flow as one IPFIX message per flow, as go-ipfix's       */
+/* exporter sends it (exporter/msg.go, entities/set.go, entities/ie.go  */
+/* 624-713). This is not nfagg_encode_ipfix, which restates the agent's */
+/* own exporter (two fixed 19-field templates, no state).               */
+/*                                                                      */
+/* Input: decode.RecordToMap (decode_protobuf.go:57-192) of the flow    */
+/* plus SrcK8S_* / DstK8S_* as nfagg_k8s_render defines their presence; */
+/* only Namespace, Name and HostName are read on each side.             */
+/* Template v6 iff Etype == 0x86DD, anything else (non-IP too) v4.      */
+/* Templates (prepareTemplate): v4 = sourceIPv4Address,                 */
+/* destinationIPv4Address, icmpTypeIPv4, icmpCodeIPv4,                  */
+/* postNATSourceIPv4Address, postNATDestinationIPv4Address + the 17     */
+/* common fields; v6 = sourceIPv6Address, destinationIPv6Address,       */
+/* nextHeaderIPv6, icmpTypeIPv6, icmpCodeIPv6, the two postNAT*IPv6 +   */
+/* the 17. Common: ethernetType flowDirection sourceMacAddress          */
+/* destinationMacAddress protocolIdentifier sourceTransportPort         */
+/* destinationTransportPort octetDeltaCount flowStartMilliseconds       */
+/* flowEndMilliseconds packetDeltaCount interfaceName tcpControlBits    */
+/* postNAPTSourceTransportPort postNAPTDestinationTransportPort         */
+/* selectorAlgorithm samplingProbability. With enterprise_id != 0 nine  */
+/* enterprise elements follow: sourcePodNamespace 7733 sourcePodName    */
+/* 7734 destinationPodNamespace 7735 destinationPodName 7736            */
+/* sourceNodeName 7737 destinationNodeName 7738 (strings),              */
+/* timeFlowRttNs 7740 (unsigned64), interfaces 7741, directions 7742    */
+/* (strings). Ids, types and lengths of the IANA names:                 */
+/* registry/registry_IANA.go.                                           */
+/*                                                                      */
+/* The writer is STATEFUL: createDataRecord mutates one element list    */
+/* per family, and a key that is absent from a flow's map and has no    */
+/* Default leaves the value the last flow of that family set. Carried   */
+/* that way: Bytes, Packets, Sampling (selectorAlgorithm and            */
+/* samplingProbability), SrcAddr / DstAddr / Proto, IcmpType /          */
+/* IcmpCode, SrcPort / DstPort, Flags, XlatSrcPort, XlatDstPort,        */
+/* TimeFlowRttNs and the six Kubernetes strings, each on its own. The   */
+/* postNAT*Address elements are not carried (Default: the zero          */
+/* address); Interfaces and IfDirections are never empty for a          */
+/* model.Record (record.go:104), so they are set by every flow.         */
+/* A record FAILS and is not sent (status 1) when an Ipv4Address        */
+/* element's value has no To4(): the initial nil before the first IP    */
+/* flow of the v4 family, an address under a v4 Etype that is not       */
+/* v4-mapped, a non-mapped XlatSrcAddr / XlatDstAddr in the v4          */
+/* template; (status 2) when 16 + set length > max_msg_size. The        */
+/* setters ran before the failure: the state has moved. The sequence    */
+/* number counts sent data records only.                                */
+/* Flags: the raw uint16, or with flags_decoded (decode_tcp_flags in    */
+/* front) EncodeTCPFlags(DecodeTCPFlags(x)) = x & 0x7FF                 */
+/* (utils/tcp_flags.go). samplingProbability: 1.0 / float64(interval),  */
+/* correctly rounded, big-endian.                                       */
+/*                                                                      */
+/* The bytes are pinned to a restatement of the Go source               */
+/* (tests/flp_ipfix_ref.py), not to a Go run.                           */
+/* Differences from the reference, by design: one Export Time per call; */
+/* one strings table per call; the template refresh timer is the        */
+/* caller's and runs between calls; the conversation records of extract */
+/* conntrack are out of scope (flow logs only); a string value has at   */
+/* most NFAGG_FLP_IPFIX_MAX_STRING bytes, the table is refused beyond   */
+/* (go-ipfix's own limit is 65535).                                     */
+/* ------------------------------------------------------------------ */
+
+#define NFAGG_FLP_IPFIX_MAX_STRING 1024
+#define NFAGG_FLP_IPFIX_SENT 0          /* status values */
+#define NFAGG_FLP_IPFIX_FAIL_FAMILY 1
+#define NFAGG_FLP_IPFIX_FAIL_SIZE 2
+
+typedef struct nfagg_flp_ipfix_options {
+    uint32_t struct_size;        /* sizeof(nfagg_flp_ipfix_options)                               */
+    uint32_t n_names;
+    int64_t  now_unix_ns;        /* as nfagg_flp_options                                          */
+    uint64_t mono_now_ns;
+    const nfagg_intf_name* names;/* HOST memory: same table and lookup rule (the UDN is not used) */
+    char     unknown_name[16];
+    uint8_t  unknown_len;
+    uint8_t  flags_decoded;      /* non-zero: decode_tcp_flags ran in front of the writer          */
+    uint8_t  pad_[2];
+    uint32_t export_time_s;      /* Export Time of every message of the call                      */
+    uint32_t seq0;               /* the exporter's seqNumber at the start of the call             */
+    uint32_t obs_domain_id;      /* 1 (write_ipfix.go:598)                                        */
+    uint16_t template_id_v4;     /* 256 (NewTemplateID starts at 255)                             */
+    uint16_t template_id_v6;     /* 257                                                           */
+    uint32_t enterprise_id;      /* 0: no enterprise elements in either template                  */
+    uint32_t max_msg_size;       /* 512 for UDP without PMTU, 65535 for TCP (exporter/process.go:121-158); at most 65535 */
+} nfagg_flp_ipfix_options;
+
+/* The element values of one family as plain values. *_set == 0: the element is still the nil NewWriteIpfix created it with.
+ * str: interfaceName, sourcePodNamespace, sourcePodName, destinationPodNamespace, destinationPodName, sourceNodeName,
+ * destinationNodeName, interfaces, directions. */
+#define NFAGG_FLP_IPFIX_N_STRINGS 9
+typedef struct nfagg_flp_ipfix_elements {
+    uint32_t struct_size;
+    uint8_t  addr_set, xlat_set, mac_set, pad0_;
+    uint8_t  src_addr[16], dst_addr[16], xlat_src_addr[16], xlat_dst_addr[16];   /* net.IP.To16() */
+    uint8_t  src_mac[6], dst_mac[6];
+    uint8_t  proto, icmp_type, icmp_code, flow_direction;
+    uint16_t etype, src_port, dst_port, flags, xlat_src_port, xlat_dst_port, selector_algorithm, pad1_;
+    uint64_t bytes, packets, start_ms, end_ms, rtt_ns;
+    double   sampling_probability;
+    uint32_t str_len[NFAGG_FLP_IPFIX_N_STRINGS];
+    uint32_t pad3_[5];           /* str at 208: 16-byte aligned */
+    char     str[NFAGG_FLP_IPFIX_N_STRINGS][NFAGG_FLP_IPFIX_MAX_STRING];
+} nfagg_flp_ipfix_elements;     /* 9424 bytes */
+
+typedef struct nfagg_flp_ipfix_strings nfagg_flp_ipfix_strings;
+typedef struct nfagg_flp_ipfix_writer nfagg_flp_ipfix_writer;
+
+/* The template message NewWriteIpfix sends for a family (v6 == 0: v4): header (Export Time export_time_s, Sequence Number
+ * seq0, a template does not advance it), one template set (ID 2), the 23 / 24 IANA field specifiers and, with enterprise_id
+ * != 0, the nine enterprise ones (enterprise bit, then the 4-byte enterprise number); variable-length elements carry 65535.
+ * Host only. NFAGG_TRUNCATED with *n_out = bytes needed when cap is smaller (nothing written). */
+int nfagg_flp_ipfix_template(const nfagg_flp_ipfix_options* opt, int v6, void* out, size_t cap, size_t* n_out);
+
+/* The three strings the writer reads of every row of a Kubernetes table, from the same entries (row r = entries[r], so the
+ * rows of nfagg_k8s_resolve index it), with their presence as nfagg_k8s_render has it (Name always, Namespace when not empty,
+ * HostName when HostIP and HostName are both not empty). The bytes are kept as they go on the wire, each string 16-byte
+ * aligned; its length prefix (one byte below 255 bytes, else 0xFF and two bytes) follows from the length. NFAGG_EINVAL: a string of more than NFAGG_FLP_IPFIX_MAX_STRING bytes, a null string with a length, more than
+ * NFAGG_K8S_MAX_ROWS entries. h == NULL builds and checks on the host alone (errors through nfagg_last_error(NULL)); the write
+ * refuses such a table. */
+int nfagg_flp_ipfix_strings_create(nfagg_handle* h, const nfagg_k8s_entry* entries, size_t n, nfagg_flp_ipfix_strings** strings);
+void nfagg_flp_ipfix_strings_destroy(nfagg_flp_ipfix_strings* strings);
+
+/* The element state of both families on the handle's device, as NewWriteIpfix leaves it. String values are owned bytes: the
+ * strings table may be destroyed or rebuilt between calls. */
+int nfagg_flp_ipfix_writer_create(nfagg_handle* h, nfagg_flp_ipfix_writer** writer);
+void nfagg_flp_ipfix_writer_destroy(nfagg_flp_ipfix_writer* writer);
+int nfagg_flp_ipfix_writer_get(nfagg_flp_ipfix_writer* writer, int v6, nfagg_flp_ipfix_elements* out);
+int nfagg_flp_ipfix_writer_reset(nfagg_flp_ipfix_writer* writer);
+
+/* Write n flows in order. features NULL: records that carry only BpfFlowMetrics (no xlat, no RTT); k8s_rows NULL: no address
+ * resolved, else 2 x n rows as nfagg_k8s_resolve writes them, indexing `strings` (required then). Message i =
+ * out[msg_offsets[i], msg_offsets[i + 1]), empty for a failed flow; msg_offsets[n] = *out_bytes; status[i] one of
+ * NFAGG_FLP_IPFIX_*; message i carries seq0 + the number of sent flows before i; *n_sent their count. NFAGG_TRUNCATED with
+ * *out_bytes = bytes needed (and *n_sent) when out_cap is smaller or out is NULL: nothing is written and the writer's state
+ * stays as it was. The state advances only with a call that wrote. All pointers HOST memory: */
+int nfagg_flp_ipfix_write(nfagg_handle* h, nfagg_flp_ipfix_writer* writer, const void* records, size_t n,
+                          const nfagg_pb_features* features, const uint32_t* k8s_rows, const nfagg_flp_ipfix_strings* strings,
+                          const nfagg_flp_ipfix_options* opt, void* out, size_t out_cap, uint64_t* msg_offsets, uint8_t* status,
+                          size_t* n_sent, size_t* out_bytes);
+/* Same with d_records, the arrays inside d_features, d_k8s_rows, d_out, d_msg_offsets and d_status in DEVICE memory (records
+ * and output 16-byte, rows and offsets 8-byte aligned). */
+int nfagg_flp_ipfix_write_device(nfagg_handle* h, nfagg_flp_ipfix_writer* writer, const void* d_records, size_t n,
+                                 const nfagg_pb_features* d_features, const uint32_t* d_k8s_rows,
+                                 const nfagg_flp_ipfix_strings* strings, const nfagg_flp_ipfix_options* opt, void* d_out,
+                                 size_t out_cap, uint64_t* d_msg_offsets, uint8_t* d_status, size_t* n_sent, size_t* out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

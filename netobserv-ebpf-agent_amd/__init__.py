@@ -34,3 +34,5 @@ from . import conntrack
 from .conntrack import ConnTrack
 from . import loki
 from .loki import WriteLoki, LokiTable, LokiWriter, labelset_string, LOKI_STREAM, LOKI_GROUP
+from . import flp_ipfix
+from .flp_ipfix import WriteIpfix, IpfixStrings, IpfixWriterState, flp_ipfix_options, flp_ipfix_template

@@ -188,6 +188,35 @@ class LokiCounts(C.Structure):
     _fields_ = [("n_streams", C.c_uint32), ("n_groups", C.c_uint32), ("n_batches", C.c_uint32), ("n_deferred", C.c_uint32)]
 
 
+# write ipfix (nfagg_flp_ipfix_*)
+FLP_IPFIX_MAX_STRING, FLP_IPFIX_N_STRINGS = 1024, 9
+FLP_IPFIX_SENT, FLP_IPFIX_FAIL_FAMILY, FLP_IPFIX_FAIL_SIZE = 0, 1, 2
+
+
+class FlpIpfixOptions(C.Structure):
+    """nfagg_flp_ipfix_options (include/nfagg.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_names", C.c_uint32), ("now_unix_ns", C.c_int64), ("mono_now_ns", C.c_uint64),
+        ("names", C.c_void_p), ("unknown_name", C.c_char * 16), ("unknown_len", C.c_uint8), ("flags_decoded", C.c_uint8),
+        ("pad_", C.c_uint8 * 2), ("export_time_s", C.c_uint32), ("seq0", C.c_uint32), ("obs_domain_id", C.c_uint32),
+        ("template_id_v4", C.c_uint16), ("template_id_v6", C.c_uint16), ("enterprise_id", C.c_uint32), ("max_msg_size", C.c_uint32),
+    ]
+
+
+class FlpIpfixElements(C.Structure):
+    """nfagg_flp_ipfix_elements (include/nfagg.h), 9424 bytes."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("addr_set", C.c_uint8), ("xlat_set", C.c_uint8), ("mac_set", C.c_uint8), ("pad0_", C.c_uint8),
+        ("src_addr", C.c_uint8 * 16), ("dst_addr", C.c_uint8 * 16), ("xlat_src_addr", C.c_uint8 * 16), ("xlat_dst_addr", C.c_uint8 * 16),
+        ("src_mac", C.c_uint8 * 6), ("dst_mac", C.c_uint8 * 6),
+        ("proto", C.c_uint8), ("icmp_type", C.c_uint8), ("icmp_code", C.c_uint8), ("flow_direction", C.c_uint8),
+        ("etype", C.c_uint16), ("src_port", C.c_uint16), ("dst_port", C.c_uint16), ("flags", C.c_uint16), ("xlat_src_port", C.c_uint16),
+        ("xlat_dst_port", C.c_uint16), ("selector_algorithm", C.c_uint16), ("pad1_", C.c_uint16),
+        ("bytes", C.c_uint64), ("packets", C.c_uint64), ("start_ms", C.c_uint64), ("end_ms", C.c_uint64), ("rtt_ns", C.c_uint64),
+        ("sampling_probability", C.c_double), ("str_len", C.c_uint32 * 9), ("pad3_", C.c_uint32 * 5), ("str", (C.c_uint8 * 1024) * 9),
+    ]
+
+
 # conversation tracking (nfagg_conn_*)
 CONN_MAX_CONNS, CONN_NO_IDX = 1 << 22, 0xFFFFFFFF
 
@@ -389,6 +418,16 @@ SIGNATURES = {
     "nfagg_loki_write": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _psz]),
     "nfagg_loki_write_device": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _psz]),
     "nfagg_loki_max_entry": (C.c_uint32, [C.c_int]),
+    "nfagg_flp_ipfix_template": (C.c_int, [C.POINTER(FlpIpfixOptions), C.c_int, _vp, _sz, _psz]),
+    "nfagg_flp_ipfix_strings_create": (C.c_int, [_vp, C.POINTER(K8sEntry), _sz, C.POINTER(_vp)]),
+    "nfagg_flp_ipfix_strings_destroy": (None, [_vp]),
+    "nfagg_flp_ipfix_writer_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "nfagg_flp_ipfix_writer_destroy": (None, [_vp]),
+    "nfagg_flp_ipfix_writer_get": (C.c_int, [_vp, C.c_int, C.POINTER(FlpIpfixElements)]),
+    "nfagg_flp_ipfix_writer_reset": (C.c_int, [_vp]),
+    "nfagg_flp_ipfix_write": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpIpfixOptions), _vp, _sz, _vp, _vp, _psz, _psz]),
+    "nfagg_flp_ipfix_write_device": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.POINTER(FlpIpfixOptions), _vp, _sz, _vp, _vp, _psz,
+                                               _psz]),
     "nfagg_gather": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
     "nfagg_gather_device": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
     "nfagg_shard_of": (C.c_uint32, [_vp, C.c_uint32]),

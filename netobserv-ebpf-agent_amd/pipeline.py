@@ -220,7 +220,7 @@ class MapTracer:
             self._netevTable = None
 
     def evictFlowsJSON(self, names=None, agent_ip=None, time_received: int = 0, unknown: bytes = b"unknown", tls_names=None, k8s=None, net=None,
-                       metrics=None, filter=None, loki=None):
+                       metrics=None, filter=None, loki=None, ipfix=None):
         """evictFlows for a direct-FLP `write: stdout, format: json` stage, without a Record per flow: the drained maps are merged,
         decorated with the sample decoder's network events and encoded on the GPU. Returns (buf, line_offsets, deferred) as
         FlowTable.encode_flp_json_content does; with tls_names (a TlsNames of the fetcher's table) the TLS keys are written too,
@@ -235,7 +235,10 @@ class MapTracer:
         admitting keep step, the Sampling the reference stores), as StageFilter.apply returns them. With loki (a loki.LokiWriter over
         the same tables; needs net) the pipeline ends in `write loki`: the result is (bodies, deferred, held), the PushRequest bodies
         of the merged (and kept) flows with their feature parts and network events, the positions the caller formats itself because
-        of their timestamp, and the filter's held flows as above (with their stored Sampling), which are in no body."""
+        of their timestamp, and the filter's held flows as above (with their stored Sampling), which are in no body. With ipfix (a
+        flp_ipfix.WriteIpfix of the fetcher's table) the pipeline ends in `write ipfix`: the merged (and kept) flows with their xlat and
+        RTT parts, and with k8s their Kubernetes strings (the writer's IpfixStrings over the same entries), go to the writer's send;
+        the result is (sent, failed, held), failed as [(position, status)]."""
         if filter is not None and tls_names is None:
             raise ValueError("filter needs tls_names")
         if loki is not None and net is None:
@@ -263,6 +266,8 @@ class MapTracer:
             args = (current, mono, names, agent_ip, time_received, unknown, present, parts, rows, tab)
             if loki is not None:
                 return self._loki(loki, recs, current, mono, time_received, present, parts, rows, tab, held)
+            if ipfix is not None:
+                return self._ipfix(ipfix, table, k8s, recs, current, mono, present, parts, held)
             if net is not None:
                 return table.encode_flp_json_net(recs, tls_names, k8s, net, *args) + (held,)
             if k8s is not None:
@@ -275,6 +280,8 @@ class MapTracer:
                 metrics.observe(table, recs, k8s, net, agent_ip, features=(present, parts))
             if loki is not None:
                 return self._loki(loki, recs, current, mono, time_received, present, parts, None, None, [])
+            if ipfix is not None:
+                return self._ipfix(ipfix, table, k8s, recs, current, mono, present, parts, [])
             if net is not None:
                 return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, present, parts)
             if k8s is not None:
@@ -287,6 +294,8 @@ class MapTracer:
             metrics.observe(table, recs, k8s, net, agent_ip, features=(p_out, parts))
         if loki is not None:
             return self._loki(loki, recs, current, mono, time_received, p_out, parts, rows, tab, [])
+        if ipfix is not None:
+            return self._ipfix(ipfix, table, k8s, recs, current, mono, p_out, parts, [])
         if net is not None:
             return table.encode_flp_json_net(recs, tls_names, k8s, net, current, mono, names, agent_ip, time_received, unknown, p_out, parts, rows, tab)
         if k8s is not None:
@@ -306,6 +315,19 @@ class MapTracer:
         sub_parts = {k: take(v) for k, v in parts.items()} if parts is not None else None
         bodies, late = loki.ExportEvicted(take(recs), now_ns, mono, time_received, present=take(present), parts=sub_parts, rows=take(rows), netev_table=tab)
         return bodies, [int(kept[i]) if at else i for i in late], held
+
+    @staticmethod
+    def _ipfix(ipfix, table, k8s, recs, now_ns, mono, present, parts, held):
+        """The merged flows through a WriteIpfix; the filter's held flows are taken out first, as for Loki."""
+        n = len(recs)
+        at = [j for j, _, _ in held]
+        kept = np.delete(np.arange(n), at) if at else None
+        take = (lambda a: a[kept] if a is not None else None) if at else (lambda a: a)
+        sub = take(recs)
+        sub_parts = {k: take(v) for k, v in parts.items()} if parts is not None else None
+        rows = table.k8s_resolve(k8s, sub) if k8s is not None and len(sub) else None
+        sent = ipfix.Write(sub, now_ns, mono, present=take(present), parts=sub_parts, k8s_rows=rows)
+        return sent, [(int(kept[i]) if at else i, st) for i, st in ipfix.failed], held
 
     def evictFlows(self, forwardFlows: "queue.Queue"):                  # :103-146
         monotonic_now, current = self.monoClock(), self.clock()
@@ -428,7 +450,7 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
     One difference from the reference, by design: TimeReceived is read once per eviction, not once per flow."""
 
     def __init__(self, table, stream, names=None, agent_ip=None, unknown: bytes = b"unknown", time_received: Callable[[], int] = None,
-                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None, metrics=None, filter=None, loki=None):
+                 fallback: Callable = None, encode=None, tls_names=None, k8s=None, net=None, metrics=None, filter=None, loki=None, ipfix=None):
         if loki is not None and net is None:
             raise ValueError("loki needs tls_names, k8s and net: the stage's labels are keys of the transform network stage")
         if k8s is not None and tls_names is None:
@@ -455,6 +477,10 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
         # lists the flows of that eviction (positions among the kept) the caller formats itself, loki_held the filter's held flows
         # among them as (position, keep step, the Sampling the reference stores), what the stdout path hands its fallback.
         self.loki, self.loki_bodies, self.loki_deferred, self.loki_held = loki, [], [], []
+        # ipfix (a flp_ipfix.WriteIpfix of `table`): the pipeline ends in `write ipfix`. Nothing is written to `stream`; the messages
+        # go to the writer's send, ipfix_failed lists the flows of the last eviction that were not sent as (position, status),
+        # ipfix_held the filter's held flows, which the writer does not see.
+        self.ipfix, self.ipfix_failed, self.ipfix_held = ipfix, [], []
 
     def ExportEvicted(self, raw, now_ns: int, mono_ns: int) -> int:
         """One eviction's lines. now_ns / mono_ns: the eviction's currentTime / monotonicCurrentTime (account.go:103-104).
@@ -477,6 +503,16 @@ class DirectFLPJSON:                                      # pkg/exporter/direct_
             self.loki_deferred, self.loki_held = sorted(held_at + [int(kept[i]) for i in late]), list(held)
             self.lines += n
             self.deferred += len(self.loki_deferred)
+            return n
+        if self.ipfix is not None:                        # filter first, then the Kubernetes rows, then the writer
+            held_at = [j for j, _, _ in held]
+            kept = np.delete(np.arange(n), held_at) if held_at else np.arange(n)
+            sub = raw[kept] if held_at else raw
+            rows = self.table.k8s_resolve(self.k8s, sub) if self.k8s is not None and len(sub) else None
+            self.ipfix.Write(sub, now_ns, mono_ns, k8s_rows=rows)
+            self.ipfix_failed, self.ipfix_held = [(int(kept[i]), st) for i, st in self.ipfix.failed], list(held)
+            self.lines += n
+            self.deferred += len(held)
             return n
         if self.tls_names is not None:
             if self.net is not None:

@@ -908,6 +908,23 @@ class FlowTable:
         from .loki import loki_write
         return loki_write(self, label_texts, n_batches, out_cap)
 
+    # -- write ipfix (nfagg_flp_ipfix_*): FLP's `write ipfix` stage, the enriched flow with the writer's carried element state
+    def flp_ipfix_strings(self, entries):
+        """A flp_ipfix.IpfixStrings on this handle's device; entries as K8sTable takes them."""
+        from .flp_ipfix import IpfixStrings
+        return IpfixStrings(entries, self)
+
+    def flp_ipfix_writer(self):
+        """A flp_ipfix.IpfixWriterState on this handle's device: the element state of both families."""
+        from .flp_ipfix import IpfixWriterState
+        return IpfixWriterState(self)
+
+    def flp_ipfix_write(self, state, records: np.ndarray, options, present=None, parts=None, k8s_rows=None, strings=None, out_cap: int = None):
+        """nfagg_flp_ipfix_write: one IPFIX message per sent flow (flp_ipfix.flp_ipfix_write). options: flp_ipfix.flp_ipfix_options(...).
+        Returns (rc, buf, msg_offsets, status, n_sent)."""
+        from .flp_ipfix import flp_ipfix_write
+        return flp_ipfix_write(self, state, records, options, present, parts, k8s_rows, strings, out_cap)
+
     # -- transform filter (nfagg_filter_*): FLP's `transform filter` stage as a device program, the stable compaction, the gather
     def filter(self, spec, k8s: "K8sTable" = None, net: "NetTable" = None) -> "Filter":
         """A compiled filter on this handle's device; spec: a filter.TransformFilter (or anything with its spec())."""

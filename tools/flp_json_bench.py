@@ -64,7 +64,13 @@ beside the _conn call: the operator's label set (namespace, owner name and owner
 _RecordType), TimeFlowEndMs at a scale of 1ms, at batch sizes of 100 KiB and 10 MiB. Reported per batch size: the median wall time of
 nfagg_loki_plan_device, of rendering the streams' label texts on the host (once per stream), of nfagg_loki_write_device, and their sum
 (the whole call), with the streams, groups, batches and bytes; the yardstick is the _conn call plus the host loop it replaces.
---k8s-trace covers the k_loki_* kernels, the cut walk (k_loki_cuts) among them. --flows N runs one table size instead of the two."""
+--k8s-trace covers the k_loki_* kernels, the cut walk (k_loki_cuts) among them. --flows N runs one table size instead of the two.
+
+--ipfix (with --k8s --net): the write ipfix leg on top, on the same records, Kubernetes rows and entries in the same run, beside the
+_net call: nfagg_flp_ipfix_write_device with enterprise id 2 and a TCP-sized message limit, the strings table over the leg's 100 000
+entries, and nfagg_encode_ipfix_device (the agent's own exporter, 19 fixed fields, no state) on the same records. Reported: the median
+wall time of a whole call (presence and carry, the scan over blocks, size, the two scans, the read-back, write, state export), the sent
+and failed flows, the bytes, and the bytes a flow moves by this tool's own count. --k8s-trace covers the k_ipfix_* kernels."""
 import io
 import os
 import queue
@@ -93,6 +99,7 @@ METRICS = "--metrics" in sys.argv[1:]
 CONNTRACK = "--conntrack" in sys.argv[1:]
 FILTER = "--filter" in sys.argv[1:]
 LOKI = "--loki" in sys.argv[1:]
+IPFIX = "--ipfix" in sys.argv[1:]
 FLOWS = int(sys.argv[sys.argv.index("--flows") + 1]) if "--flows" in sys.argv[1:] else 0
 NET_CATEGORIES = [("cat-%d" % c, ["172.%d.%d.0/24" % (16 + c, k) for k in range(8)] + ["2001:db8:%x::/48" % (16 * c + k) for k in range(1)]) for c in range(5)] + \
                  [("pods", ["100.64.0.0/10"]), ("everything", ["0.0.0.0/0", "::/0"])]
@@ -166,7 +173,7 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_filter_|k_gather|k_loki_|fillBuffer|scan|[Ss]ort|onesweep", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_filter_|k_gather|k_loki_|k_ipfix_|fillBuffer|scan|[Ss]ort|onesweep", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
             if "rocprim" in name:                           # the library's scan and sort kernels: their configuration's name and value types
@@ -407,6 +414,41 @@ def filter_leg(tab, d_ev, m, tls, k8s, net, d_rows, d_net, d_off, dt_net_join, d
               f"({dt_enc / dt_net_encode:.3f} of the unfiltered call); apply + gather + encode = {(dt_apply + dt_gather + dt_enc) / dt_net_encode:.3f} of it")
 
 
+def ipfix_leg(tab, d_ev, m, entries, d_rows, d_off, dt_net_encode):
+    """nfagg_flp_ipfix_write_device on the leg's records and rows, and the agent's own IPFIX encoder beside it."""
+    import ctypes as C
+    from netobserv_ebpf_agent_amd.flp_ipfix import flp_ipfix_options
+    L = nf._lib
+    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    with tab.flp_ipfix_strings(entries) as strings, tab.flp_ipfix_writer() as state:
+        o, keep = flp_ipfix_options(NOW, MONO, names, 1_700_000_000, 0, 2, 65535)
+        d_status = torch.empty(m + 16, dtype=torch.uint8, device="cuda")
+        need, sent = C.c_size_t(0), C.c_size_t(0)
+        args = (tab._h, state._t, ptr(d_ev), m, None, ptr(d_rows), strings._t, C.byref(o))
+        for _ in range(2):        # the first call starts from NewWriteIpfix's state, every later one from the state a whole pass left: sized again
+            rc = L.lib.nfagg_flp_ipfix_write_device(*args, None, 0, ptr(d_off), ptr(d_status), C.byref(sent), C.byref(need))
+            assert rc == L.TRUNCATED, L.lib.nfagg_last_error(tab._h)
+            total = need.value
+            d_out = torch.empty(total + 16, dtype=torch.uint8, device="cuda")
+            rc = L.lib.nfagg_flp_ipfix_write_device(*args, ptr(d_out), total, ptr(d_off), ptr(d_status), C.byref(sent), C.byref(need))
+            assert rc == L.OK and need.value == total, L.lib.nfagg_last_error(tab._h)
+        rc, dt = timed(lambda: L.lib.nfagg_flp_ipfix_write_device(*args, ptr(d_out), total, ptr(d_off), ptr(d_status), C.byref(sent), C.byref(need)))
+        assert rc == L.OK and need.value == total, L.lib.nfagg_last_error(tab._h)
+        per_byte("_wipfix", m, dt, need.value)
+        # per flow: the record, 4 B of meta written and read twice, 64 B of sources written and read twice (rewritten where a source lay
+        # before the block), 32 B of interface rows written and read, 8 B of rows read three times, two 4-byte scan words written and
+        # read, the 8-byte offset and the status byte written; the strings and the source flows' records on top are not counted
+        moved = m * (2 * 144 + 3 * 4 + 3 * 64 + 2 * 32 + 3 * 8 + 4 * 4 + 8 + 1) + need.value
+        print(f"           {sent.value} of {m} flows sent, {m - sent.value} failed; {moved / dt / 1e9:.1f} GB/s by this tool's count of a flow's own bytes; "
+              f"the _net call of this run: {dt_net_encode * 1e3:.3f} ms")
+        del d_out
+    rc, need2 = tab.encode_ipfix_device(d_ev.data_ptr(), m, NOW, MONO, names, 1_700_000_000, 0, 0, 0, d_off.data_ptr())
+    d_out = torch.empty(need2 + 16, dtype=torch.uint8, device="cuda")
+    (rc, wrote), dt2 = timed(lambda: tab.encode_ipfix_device(d_ev.data_ptr(), m, NOW, MONO, names, 1_700_000_000, 0, d_out.data_ptr(), need2, d_off.data_ptr()))
+    assert rc == nf.OK and wrote == need2
+    per_byte("_ipfix", m, dt2, wrote)
+
+
 def per_byte(what, m, dt, wrote):
     print(f"  {what:8s} {m} flows -> {wrote} bytes ({wrote / m:.1f} B/line) in {dt * 1e3:.3f} ms per call = {m / dt / 1e6:.1f} M flows/s, "
           f"{dt / wrote * 1e12:.3f} ps per output byte")
@@ -486,6 +528,9 @@ for flows in ((FLOWS,) if FLOWS else (10_000_000,) if (CONTENT or TLS) and not K
                               f"{int((got['src_label'] != nf._lib.NET_NO_LABEL).sum() + (got['dst_label'] != nf._lib.NET_NO_LABEL).sum())} of {2 * m} endpoints labelled, "
                               f"{int((got['direction'] != nf._lib.NET_NO_DIRECTION).sum())} of {m} flows with a direction; the join alone: {dt_net * 1e3:.3f} ms per call")
                         del d_out
+                        if IPFIX:
+                            tab.k8s_resolve_device(k8s, d_ev.data_ptr(), m, d_rows.data_ptr())
+                            ipfix_leg(tab, d_ev, m, entries, d_rows, d_off, dt)
                         if FILTER:
                             filter_leg(tab, d_ev, m, tls, k8s, net, d_rows, d_net, d_off, dt_net, dt)
                         if METRICS:
