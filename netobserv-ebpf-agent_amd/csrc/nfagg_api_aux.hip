@@ -1,5 +1,5 @@
 // nfagg_api_aux.hip — the small side operations of the C ABI (include/nfagg.h): the per-CPU rollups, the merge of the drained
-// maps, the sketches' read side. Each stages its arguments in scratch of the handle, launches and synchronises.
+// maps, the sketches' read side. Each stages its arguments in scratch of the handle (nfagg_api_call.h), launches and synchronises.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
@@ -10,6 +10,7 @@
 #include "../../include/nfagg.h"
 #include "nfagg_internal.h"
 #include "nfagg_handle.h"
+#include "nfagg_api_call.h"
 
 using namespace nfagg;
 
@@ -24,16 +25,13 @@ static int rollup_core(nfagg_handle* h, int kind, const void* partials, size_t n
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t ssz = rollup_struct_size(kind);
     const size_t pb = n_flows * n_cpu * ssz, bb = n_flows * sizeof(nfagg_flow_metrics), fb = n_flows * ssz;
-    int rc;
-    if ((rc = h->roll.partials.ensure(h, pb)) != NFAGG_OK) return rc;
-    if ((rc = h->roll.base.ensure(h, bb)) != NFAGG_OK) return rc;
-    if ((rc = h->roll.folded.ensure(h, fb)) != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->roll.partials.p, partials, pb, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->roll.base.p, base, bb, hipMemcpyHostToDevice, h->stream));
+    API_TRY(h->roll.folded.ensure(h, fb));
+    API_TRY(stage_in(h, h->roll.partials, partials, pb));
+    API_TRY(stage_in(h, h->roll.base, base, bb));
     hipError_t e = launch_rollup(kind, h->roll.partials.p, n_flows, n_cpu, h->roll.base.p, h->roll.folded.p, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "rollup launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(base, h->roll.base.p, bb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(folded, h->roll.folded.p, fb, hipMemcpyDeviceToHost, h->stream));
+    API_TRY(fetch(h, base, h->roll.base, bb));
+    API_TRY(fetch(h, folded, h->roll.folded, fb));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
 }
@@ -84,13 +82,8 @@ static int map_merge_device_core(nfagg_handle* h, const nfagg_map_view* mm, cons
     uint32_t n_slots = 1024;
     while ((uint64_t)n_slots < 2 * total) n_slots <<= 1;
     const size_t blocks = (total + 1023) / 1024;
-    int rc;
-    if ((rc = h->mm.slots.ensure(h, (size_t)n_slots * merge_slot_bytes())) != NFAGG_OK) return rc;
-    if ((rc = h->mm.slot_of.ensure(h, total * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = h->mm.local_off.ensure(h, total * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = h->mm.block_sum.ensure(h, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = h->mm.block_base.ensure(h, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = h->mm.n_dup.ensure(h, 16)) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {{h->mm.slots, (size_t)n_slots * merge_slot_bytes()}, {h->mm.slot_of, total * sizeof(uint32_t)}, {h->mm.local_off, total * sizeof(uint32_t)},
+                           {h->mm.block_sum, blocks * sizeof(uint32_t)}, {h->mm.block_base, (blocks + 1) * sizeof(uint64_t)}, {h->mm.n_dup, 16}}));
     HIP_TRY(h, hipMemsetAsync(h->mm.slots.p, 0xFF, (size_t)n_slots * merge_slot_bytes(), h->stream));
     HIP_TRY(h, hipMemsetAsync(h->mm.n_dup.p, 0, 16, h->stream));
     hipError_t e = launch_merge_build(in, h->mm.slots.p, n_slots, h->mm.slot_of.as<uint32_t>(), h->mm.n_dup.as<unsigned int>(),
@@ -123,7 +116,6 @@ int nfagg_map_merge(nfagg_handle* h, const nfagg_map_view* main_map, const nfagg
     if (n_cpu == 0) return fail(h, NFAGG_EINVAL, "n_cpu must be >= 1");
     HIP_TRY(h, hipSetDevice(h->device));
     nfagg_map_view dm{}, df[6] = {};
-    int rc;
     for (int q = 0; q < 7; q++) {
         const nfagg_map_view& v = q == 0 ? *main_map : feature_maps[q - 1];
         nfagg_map_view& d = q == 0 ? dm : df[q - 1];
@@ -131,10 +123,8 @@ int nfagg_map_merge(nfagg_handle* h, const nfagg_map_view* main_map, const nfagg
         if (!v.n) continue;
         if (!v.ids || !v.values) return fail(h, NFAGG_EINVAL, "map %d: null ids/values", q);
         const size_t vb = q == 0 ? v.n * sizeof(nfagg_flow_metrics) : v.n * n_cpu * rollup_struct_size(q - 1);
-        if ((rc = h->mm.ids[q].ensure(h, v.n * sizeof(nfagg_flow_id))) != NFAGG_OK) return rc;
-        if ((rc = h->mm.vals[q].ensure(h, vb)) != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->mm.ids[q].p, v.ids, v.n * sizeof(nfagg_flow_id), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->mm.vals[q].p, v.values, vb, hipMemcpyHostToDevice, h->stream));
+        API_TRY(stage_in(h, h->mm.ids[q], v.ids, v.n * sizeof(nfagg_flow_id)));
+        API_TRY(stage_in(h, h->mm.vals[q], v.values, vb));
         d.ids = h->mm.ids[q].as<const nfagg_flow_id>(); d.values = h->mm.vals[q].p;
     }
     void* host_out[8] = {out->records, out->present, out->additional, out->dns, out->drops, out->network_events, out->xlat, out->quic};
@@ -143,16 +133,15 @@ int nfagg_map_merge(nfagg_handle* h, const nfagg_map_view* main_map, const nfagg
     void* dev_out[8] = {};
     for (int k = 0; k < 8; k++) {
         if (!host_out[k] || !cap) continue;
-        if ((rc = h->mm.out[k].ensure(h, cap * elem[k] + 16)) != NFAGG_OK) return rc;
+        API_TRY(h->mm.out[k].ensure(h, cap * elem[k] + kStageSlack));
         dev_out[k] = h->mm.out[k].p;
     }
     nfagg_merged_flows dout{(nfagg_flow_record*)dev_out[0], (uint8_t*)dev_out[1], (nfagg_additional_metrics*)dev_out[2], (nfagg_dns_metrics*)dev_out[3],
                             (nfagg_pkt_drop_metrics*)dev_out[4], (nfagg_network_events_metrics*)dev_out[5], (nfagg_xlat_metrics*)dev_out[6],
                             (nfagg_quic_metrics*)dev_out[7]};
-    rc = map_merge_device_core(h, &dm, df, n_cpu, &dout, cap, n_out, n_duplicate_keys);
-    if (rc != NFAGG_OK) return rc;
+    API_TRY(map_merge_device_core(h, &dm, df, n_cpu, &dout, cap, n_out, n_duplicate_keys));
     for (int k = 0; k < 8; k++)
-        if (dev_out[k] && *n_out) HIP_TRY(h, hipMemcpyAsync(host_out[k], dev_out[k], *n_out * elem[k], hipMemcpyDeviceToHost, h->stream));
+        if (dev_out[k]) API_TRY(fetch(h, host_out[k], h->mm.out[k], *n_out * elem[k]));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
 }
@@ -328,9 +317,7 @@ int nfagg_cm_topk_device(nfagg_handle* h, int which, const void* d_records, size
 int nfagg_cm_topk(nfagg_handle* h, int which, const void* records, size_t n, size_t k, nfagg_heavy_hitter* out, size_t* n_out) {
     if (!h || (n && !records)) return fail(h, NFAGG_EINVAL, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = h->hh.records.ensure(h, n * kRecordBytes + 16);
-    if (rc != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(h->hh.records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
+    API_TRY(stage_in(h, h->hh.records, records, n * kRecordBytes));
     return cm_topk_core(h, which, h->hh.records.p, n, k, out, n_out);
 }
 

@@ -9,6 +9,7 @@
 #include "../../include/nfagg.h"
 #include "nfagg_internal.h"
 #include "nfagg_handle.h"
+#include "nfagg_api_call.h"
 #include "nfagg_conn.h"
 
 using namespace nfagg;
@@ -43,11 +44,6 @@ void host_gob_addr(FnvSink& f, const uint8_t ip[16]) {
     const uint32_t len = host_ip_text(ip, text);
     gob_string_head(f, len);
     for (uint32_t k = 0; k < len; k++) f.put((uint8_t)text[k]);
-}
-
-void split_now_ns(int64_t now_unix_ns, int64_t& sec, int64_t& nsec) {   // time.Time's (sec, nsec), 0 <= nsec < 1e9
-    sec = now_unix_ns / 1000000000ll; nsec = now_unix_ns % 1000000000ll;
-    if (nsec < 0) { nsec += 1000000000ll; sec -= 1; }
 }
 
 }  // namespace
@@ -87,18 +83,14 @@ int nfagg_conn_fold_device(nfagg_handle* h, const void* d_records, size_t n, con
     // there are no more connections than flows: a large cap over a small call does not zero and scan a large table
     D.mask = (uint32_t)std::max<uint64_t>(next_pow2(2ull * std::min<uint64_t>(cap, n)), kConnMinSlots) - 1;
     D.hash_ids = d_hash_ids; D.out = d_out;
-    split_now_ns(opt->now_unix_ns, D.now_sec, D.now_nsec);
+    split_now(opt->now_unix_ns, D.now_sec, D.now_nsec);
     D.mono_now = opt->mono_now_ns;
     const size_t slots = (size_t)D.mask + 1, blocks = slots / kConnMinSlots;
     const size_t slot_bytes = slots * kConnSlotWords * sizeof(uint64_t);
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = S.conn_slots.ensure(h, 256 + slot_bytes)) != NFAGG_OK) return rc;
-    if ((rc = S.conn_flow.ensure(h, n * (sizeof(uint64_t) + sizeof(uint32_t)) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.local_off.ensure(h, slots * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.block_sum.ensure(h, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.block_base.ensure(h, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {{S.conn_slots, 256 + slot_bytes}, {S.conn_flow, n * (sizeof(uint64_t) + sizeof(uint32_t)) + 16}, {S.local_off, slots * sizeof(uint32_t)},
+                           {S.block_sum, blocks * sizeof(uint32_t)}, {S.block_base, (blocks + 1) * sizeof(uint64_t)}}));
     D.ctl = S.conn_slots.as<ConnCtl>();
     D.slots = (uint64_t*)(S.conn_slots.as<uint8_t>() + 256);
     D.hash_a = S.conn_flow.as<uint64_t>();                        // n hashes, then n slot indexes
@@ -125,16 +117,13 @@ int nfagg_conn_fold(nfagg_handle* h, const void* records, size_t n, const nfagg_
     if (cap && !out) return fail(h, NFAGG_EINVAL, "a cap without an output array");
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.conn_ids.ensure(h, n * sizeof(uint64_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.conn_out.ensure(h, std::min<size_t>(cap, n) * sizeof(nfagg_conn_partial) + 16)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    rc = nfagg_conn_fold_device(h, S.in_records.p, n, opt, hash_ids ? S.conn_ids.as<uint64_t>() : nullptr, cap, S.conn_out.as<nfagg_conn_partial>(), n_conns,
+    API_TRY(ensure_all(h, {{S.conn_ids, n * sizeof(uint64_t) + kStageSlack}, {S.conn_out, std::min<size_t>(cap, n) * sizeof(nfagg_conn_partial) + kStageSlack}}));
+    API_TRY(stage_in(h, S.in_records, records, n * kRecordBytes));
+    const int rc = nfagg_conn_fold_device(h, S.in_records.p, n, opt, hash_ids ? S.conn_ids.as<uint64_t>() : nullptr, cap, S.conn_out.as<nfagg_conn_partial>(), n_conns,
                                 n_discarded);
     if (rc != NFAGG_OK && rc != NFAGG_TRUNCATED) return rc;
-    if (n && hash_ids) HIP_TRY(h, hipMemcpyAsync(hash_ids, S.conn_ids.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    if (rc == NFAGG_OK && *n_conns) HIP_TRY(h, hipMemcpyAsync(out, S.conn_out.p, (size_t)*n_conns * sizeof(nfagg_conn_partial), hipMemcpyDeviceToHost, h->stream));
+    API_TRY(fetch(h, hash_ids, S.conn_ids, hash_ids ? n * sizeof(uint64_t) : 0));
+    if (rc == NFAGG_OK) API_TRY(fetch(h, out, S.conn_out, (size_t)*n_conns * sizeof(nfagg_conn_partial)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return rc;
 }

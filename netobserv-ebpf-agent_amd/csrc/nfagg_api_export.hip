@@ -5,113 +5,19 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
-#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "../../include/nfagg.h"
 #include "nfagg_internal.h"
 #include "nfagg_handle.h"
+#include "nfagg_api_call.h"
 #include "nfagg_api_tables.h"
 #include "nfagg_pb.h"
 #include "nfagg_ipfix.h"
 #include "nfagg_flp.h"
 
 using namespace nfagg;
-
-// ---- the export encoders' host side: what protobuf, IPFIX and direct-FLP JSON do alike
-namespace {
-
-int check_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names, uint32_t unknown_len, bool check_udn) {
-    if (unknown_len > 16 || (n_names && !names)) return fail(h, NFAGG_EINVAL, "bad namer table");
-    for (uint32_t k = 0; k < n_names; k++) {
-        if (names[k].name_len > 16) return fail(h, NFAGG_EINVAL, "namer row %u: name too long", k);
-        if (check_udn && names[k].udn_len > 63) return fail(h, NFAGG_EINVAL, "namer row %u: udn too long", k);
-    }
-    return NFAGG_OK;
-}
-
-// The kernels binary-search the table: a stable sort by if_index keeps the scan-in-table-order answer.
-int stage_namer(nfagg_handle* h, const nfagg_intf_name* names, uint32_t n_names) {
-    auto& S = h->enc;
-    int rc = S.names.ensure(h, (size_t)(n_names + 1) * sizeof(nfagg_intf_name));
-    if (rc != NFAGG_OK) return rc;
-    S.h_names.assign(names, names + n_names);
-    std::stable_sort(S.h_names.begin(), S.h_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
-    if (n_names) HIP_TRY(h, hipMemcpyAsync(S.names.p, S.h_names.data(), n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
-    return NFAGG_OK;
-}
-
-void split_now(int64_t now_unix_ns, int64_t& sec, int64_t& nsec) {   // time.Time's (sec, nsec), 0 <= nsec < 1e9
-    sec = now_unix_ns / 1000000000ll; nsec = now_unix_ns % 1000000000ll;
-    if (nsec < 0) { nsec += 1000000000ll; sec -= 1; }
-}
-
-// What follows the argument checks of a device entry point: the device, the zeroed results, the answer for n == 0 (*done), the
-// scratch of the two scans, the namer table.
-int encode_begin(nfagg_handle* h, size_t n, uint64_t* d_offsets, size_t* out_bytes, const nfagg_intf_name* names, uint32_t n_names, bool* done) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    *out_bytes = 0;
-    *done = n == 0;
-    if (n == 0) { HIP_TRY(h, hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), h->stream)); HIP_TRY(h, hipStreamSynchronize(h->stream)); return NFAGG_OK; }
-    const size_t blocks = (n + 1023) / 1024;
-    int rc;
-    if ((rc = h->enc.local_off.ensure(h, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = h->enc.block_sum.ensure(h, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = h->enc.block_base.ensure(h, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    return stage_namer(h, names, n_names);
-}
-
-// The two passes: size(local_off, block_sum, block_base) launches the size kernel and the scan of the block sums; the total (and
-// the FLP encoder's deferred counter) is read back; a buffer that is too small or absent ends it there, with the total in
-// *out_bytes; write(local_off, block_base, total) launches the write kernel.
-template <typename SizeLaunch, typename WriteLaunch>
-int encode_two_pass(nfagg_handle* h, size_t n, const char* what, const char* write_verb, void* d_out, size_t out_cap, size_t* out_bytes,
-                           size_t* n_deferred, SizeLaunch size, WriteLaunch write) {
-    auto& S = h->enc;
-    const size_t blocks = (n + 1023) / 1024;
-    hipError_t e = size(S.local_off.as<uint32_t>(), S.block_sum.as<uint32_t>(), S.block_base.as<uint64_t>());
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s size launch failed: %s", what, hipGetErrorString(e));
-    uint64_t total = 0;
-    uint32_t deferred = 0;
-    HIP_TRY(h, hipMemcpyAsync(&total, S.block_base.as<uint64_t>() + blocks, sizeof total, hipMemcpyDeviceToHost, h->stream));
-    if (n_deferred) HIP_TRY(h, hipMemcpyAsync(&deferred, S.flp_n_deferred.p, sizeof deferred, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *out_bytes = (size_t)total;
-    if (n_deferred) *n_deferred = deferred;
-    if (total > out_cap || !d_out) return NFAGG_TRUNCATED;
-    e = write(S.local_off.as<const uint32_t>(), S.block_base.as<const uint64_t>(), total);
-    if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "%s %s launch failed: %s", what, write_verb, hipGetErrorString(e));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-// The host-memory entry points: records in, device(d_records, d_out or null, d_offsets) = the device entry point, bytes and offsets
-// out, and the format's per-record extras (out_extra[k] -> host, `bytes` per record; skipped when the caller passed no host array).
-struct EncodeExtra { void* host; size_t bytes; };
-template <typename DeviceEntry>
-int encode_staged(nfagg_handle* h, const void* records, size_t n, void* out, size_t out_cap, uint64_t* offsets, size_t* out_bytes,
-                         std::initializer_list<EncodeExtra> extras, DeviceEntry device) {
-    auto& S = h->enc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out.ensure(h, out_cap + 32)) != NFAGG_OK) return rc;
-    if ((rc = S.out_offsets.ensure(h, (n + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    size_t k = 0;
-    for (const EncodeExtra& x : extras) { if (x.host && (rc = S.out_extra[k].ensure(h, n * x.bytes + 32)) != NFAGG_OK) return rc; k++; }
-    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    rc = device(S.in_records.p, out ? S.out.p : nullptr, S.out_offsets.as<uint64_t>());
-    if (rc != NFAGG_OK) return rc;
-    if (*out_bytes) HIP_TRY(h, hipMemcpyAsync(out, S.out.p, *out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(offsets, S.out_offsets.p, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    k = 0;
-    for (const EncodeExtra& x : extras) { if (n && x.host) HIP_TRY(h, hipMemcpyAsync(x.host, S.out_extra[k].p, n * x.bytes, hipMemcpyDeviceToHost, h->stream)); k++; }
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NFAGG_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -139,9 +45,7 @@ int device_netev(nfagg_handle* h, const NetevArgs* ne, size_t n, PbFeat* F) {
 static int stage_netev_rows(nfagg_handle* h, const NetevArgs* ne, size_t n, NetevArgs* dne) {
     *dne = *ne;
     if (!n || !ne->rows) return NFAGG_OK;
-    int rc = h->enc.ne_rows.ensure(h, n * 8 + 16);
-    if (rc != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->enc.ne_rows.p, ne->rows, n * 8, hipMemcpyHostToDevice, h->stream));
+    API_TRY(stage_in(h, h->enc.ne_rows, ne->rows, n * 8));
     dne->rows = h->enc.ne_rows.as<const uint16_t>();
     return NFAGG_OK;
 }
@@ -171,7 +75,7 @@ static int encode_pb_device_core(nfagg_handle* h, const void* d_records, size_t 
     P.agent_is_v4 = memcmp(opt->agent_ip, v4pre, 12) == 0;     // net.IP.To4() != nil (proto.go:255-261)
     P.names = h->enc.names.as<const nfagg_intf_name>(); P.n_names = opt->n_names;
     P.unknown_len = opt->unknown_len; memcpy(P.unknown, opt->unknown_name, 16);
-    return encode_two_pass(h, n, "protobuf", "encode", d_out, out_cap, out_bytes, nullptr,
+    return encode_two_pass(h, n, {"protobuf", "size", "encode"}, d_out, out_cap, out_bytes, {},
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
             return launch_pb_size(d_records, n, P, F, d_body_len, local_off, block_sum, block_base, h->stream); },
         [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t total) {
@@ -187,9 +91,7 @@ int stage_pb_features(nfagg_handle* h, const nfagg_pb_features* feat, size_t n, 
     void* dst[6] = {};
     for (int k = 0; k < 6; k++) {
         if (!src[k]) continue;
-        int rc = h->enc.pb_feat[k].ensure(h, n * elem[k] + 16);
-        if (rc != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->enc.pb_feat[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
+        API_TRY(stage_in(h, h->enc.pb_feat[k], src[k], n * elem[k]));
         dst[k] = h->enc.pb_feat[k].p;
     }
     dfeat->present = (const uint8_t*)dst[0]; dfeat->additional = (const nfagg_additional_metrics*)dst[1];
@@ -208,9 +110,9 @@ static int encode_pb_host_core(nfagg_handle* h, const void* records, size_t n, c
     return encode_staged(h, records, n, out, out_cap, frame_offsets, out_bytes, {{body_len, sizeof(uint32_t)}, {kafka_keys, 32}},
         [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
             nfagg_pb_features dfeat{};
-            if (feat && n) { int rc = stage_pb_features(h, feat, n, &dfeat); if (rc != NFAGG_OK) return rc; }
+            if (feat && n) API_TRY(stage_pb_features(h, feat, n, &dfeat));
             NetevArgs dne{};
-            if (ne) { int rc = stage_netev_rows(h, ne, n, &dne); if (rc != NFAGG_OK) return rc; }
+            if (ne) API_TRY(stage_netev_rows(h, ne, n, &dne));
             return encode_pb_device_core(h, d_records, n, (feat && n) ? &dfeat : nullptr, ne ? &dne : nullptr, opt, d_out, out_cap, d_offsets,
                                          h->enc.out_extra[0].as<uint32_t>(), kafka_keys ? h->enc.out_extra[1].p : nullptr, out_bytes); });
 }
@@ -264,24 +166,12 @@ static const uint16_t kIpfixTemplateV4[19][2] = {   // ipfix.go:89-135 + AddReco
 static const uint16_t kIpfixTemplateV6[19][2] = {   // ipfix.go:158-204 + AddRecordValuesToTemplate
     {256, 2}, {61, 1}, {56, 6}, {80, 6}, {27, 16}, {28, 16}, {193, 1}, {7, 2}, {11, 2}, {178, 1}, {179, 1},
     {1, 8}, {6, 2}, {150, 4}, {152, 8}, {151, 4}, {153, 8}, {2, 8}, {82, 65535}};
-static constexpr size_t kIpfixTemplateBytes = 16 + 4 + 4 + 19 * 4;
-
-static void put_be16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 8); p[1] = (uint8_t)v; }
-static void put_be32(uint8_t* p, uint32_t v) { put_be16(p, v >> 16); put_be16(p + 2, v); }
 
 int nfagg_ipfix_template(const nfagg_ipfix_options* opt, int v6, void* out, size_t cap, size_t* n_out) {
     if (!opt || !n_out) return fail(nullptr, NFAGG_EINVAL, "null argument");
     if (opt->struct_size != sizeof(nfagg_ipfix_options)) return fail(nullptr, NFAGG_EINVAL, "nfagg_ipfix_options.struct_size mismatch");
-    *n_out = kIpfixTemplateBytes;
-    if (!out || cap < kIpfixTemplateBytes) return NFAGG_TRUNCATED;
-    uint8_t* p = (uint8_t*)out;
-    put_be16(p, 10); put_be16(p + 2, (uint32_t)kIpfixTemplateBytes); put_be32(p + 4, opt->export_time_s);
-    put_be32(p + 8, opt->seq0); put_be32(p + 12, opt->obs_domain_id);
-    put_be16(p + 16, 2); put_be16(p + 18, (uint32_t)kIpfixTemplateBytes - 16);                // template set
-    put_be16(p + 20, v6 ? opt->template_id_v6 : opt->template_id_v4); put_be16(p + 22, 19);  // template record header
-    const uint16_t (*f)[2] = v6 ? kIpfixTemplateV6 : kIpfixTemplateV4;
-    for (int k = 0; k < 19; k++) { put_be16(p + 24 + 4 * k, f[k][0]); put_be16(p + 26 + 4 * k, f[k][1]); }   // enterprise bit never set
-    return NFAGG_OK;
+    return ipfix_template_message({opt->export_time_s, opt->seq0, opt->obs_domain_id, v6 ? opt->template_id_v6 : opt->template_id_v4},
+                                  {{v6 ? kIpfixTemplateV6 : kIpfixTemplateV4, 19}}, {}, 0, out, cap, n_out);      // enterprise bit never set
 }
 
 // The options are checked first, before the handle: a caller learns of a bad table without any device work.
@@ -308,7 +198,7 @@ int nfagg_encode_ipfix_device(nfagg_handle* h, const void* d_records, size_t n, 
     P.unknown_len = opt->unknown_len; memcpy(P.unknown_w, opt->unknown_name, 16);
     P.export_time = opt->export_time_s; P.seq0 = opt->seq0; P.obs_domain = opt->obs_domain_id;
     P.tid_v4 = opt->template_id_v4; P.tid_v6 = opt->template_id_v6;
-    return encode_two_pass(h, n, "IPFIX", "write", d_out, out_cap, out_bytes, nullptr,
+    return encode_two_pass(h, n, {"IPFIX", "size", "write"}, d_out, out_cap, out_bytes, {},
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
             return launch_ipfix_size(d_records, n, P, name_rows, local_off, block_sum, block_base, h->stream); },
         [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
@@ -352,21 +242,16 @@ static void flp_escape_row(uint8_t* row, const char* name, uint32_t name_len, co
 
 int stage_flp_line(nfagg_handle* h, const void* d_records, size_t n, const nfagg_flp_options* opt, const PbFeat& F, const FlpLineTables& t,
                           const FlpLineStage& st, FlpLineArgs* args) {
-    int rc;
     const size_t esc_bytes = (size_t)(opt->n_names + 1) * kFlpEscRowBytes;
-    if ((rc = st.names.ensure(h, (size_t)(opt->n_names + 1) * sizeof(nfagg_intf_name))) != NFAGG_OK) return rc;
-    if ((rc = st.esc.ensure(h, esc_bytes)) != NFAGG_OK) return rc;
-    // the kernels binary-search the table: a stable sort by if_index keeps the scan-in-table-order answer. Names and UDNs are
-    // escaped here, once per row of the sorted table: no kernel escapes per flow
-    st.h_names.assign(opt->names, opt->names + opt->n_names);
-    std::stable_sort(st.h_names.begin(), st.h_names.end(), [](const nfagg_intf_name& a, const nfagg_intf_name& b) { return a.if_index < b.if_index; });
+    API_TRY(stage_namer(h, opt->names, opt->n_names, st.names, st.h_names));
+    API_TRY(st.esc.ensure(h, esc_bytes));
+    // names and UDNs are escaped here, once per row of the sorted table: no kernel escapes per flow
     st.h_esc.assign(esc_bytes, 0);
     flp_escape_row(st.h_esc.data(), opt->unknown_name, opt->unknown_len, "", 0);
     for (uint32_t k = 0; k < opt->n_names; k++) {
         const nfagg_intf_name& e = st.h_names[k];
         flp_escape_row(st.h_esc.data() + (size_t)(k + 1) * kFlpEscRowBytes, e.name, e.name_len, e.udn, e.udn_len);
     }
-    if (opt->n_names) HIP_TRY(h, hipMemcpyAsync(st.names.p, st.h_names.data(), opt->n_names * sizeof(nfagg_intf_name), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(st.esc.p, st.h_esc.data(), esc_bytes, hipMemcpyHostToDevice, h->stream));
     FlpLineArgs& A = *args;
     A = FlpLineArgs{};
@@ -382,13 +267,13 @@ int stage_flp_line(nfagg_handle* h, const void* d_records, size_t n, const nfagg
         for (uint32_t k = 0; k < kTlsKinds; k++) A.T.n[k] = t.tls->n[k];
     }
     if (t.level >= FlpLevel::K8s) {
-        if ((rc = st.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
+        API_TRY(st.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t)));
         A.K = k8s_dev(t.k8s); A.k8s_rows = st.k8s_rows.as<const uint32_t>();
         const hipError_t e = launch_k8s_resolve(d_records, n, A.K, st.k8s_rows.as<uint32_t>(), h->stream);
         if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
     }
     if (t.level >= FlpLevel::Net) {
-        if ((rc = st.net_rows.ensure(h, n * sizeof(uint2))) != NFAGG_OK) return rc;
+        API_TRY(st.net_rows.ensure(h, n * sizeof(uint2)));
         A.N = net_dev(t.net); A.net_rows = st.net_rows.as<const uint2>();
         const hipError_t e = launch_net_resolve(d_records, n, A.N, A.k8s_rows, t.k8s->d_host_ids.as<const uint32_t>(), A.K.n_rows, net_reporter(t.k8s, opt),
                                                 st.net_rows.as<uint2>(), h->stream);
@@ -434,8 +319,7 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     bool done;
     if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, nullptr, 0, &done)) != NFAGG_OK || done) return rc;
     auto& S = h->enc;
-    if ((rc = S.flp_rows.ensure(h, n * 8 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.flp_n_deferred.ensure(h, 16)) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {{S.flp_rows, n * 8 * sizeof(uint32_t)}, {S.flp_n_deferred, 16}}));
     HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
     FlpLineArgs A;
     if ((rc = stage_flp_line(h, d_records, n, opt, F, t, FlpLineStage{S.names, S.flp_esc, S.k8s_rows, S.net_rows, S.h_names, S.h_flp_esc}, &A)) != NFAGG_OK) return rc;
@@ -444,12 +328,14 @@ static int encode_flp_device_core(nfagg_handle* h, const void* d_records, size_t
     static const char* const kWhat[5] = {"FLP JSON", "FLP JSON with TLS names", "FLP JSON with Kubernetes keys", "FLP JSON with transform network keys",
                                          "FLP JSON flow logs of extract conntrack"};
     const char* what = !tls && (feat || ne) ? "FLP JSON content" : kWhat[(int)t.level];
-    size_t deferred_unused;
-    return encode_two_pass(h, n, what, "write", d_out, out_cap, out_bytes, tls ? nullptr : n_deferred ? n_deferred : &deferred_unused,
+    uint32_t deferred = 0;
+    rc = encode_two_pass(h, n, {what, "size", "write"}, d_out, out_cap, out_bytes, tls ? ReadBack{} : ReadBack{counter, &deferred, sizeof deferred},
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
             return launch_flp_size(A, t.level, rows, local_off, block_sum, block_base, counter, h->stream); },
         [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
             return launch_flp_write(A, t.level, rows, local_off, block_base, d_out, d_line_offsets, d_deferred, h->stream); });
+    if (!tls && n_deferred) *n_deferred = deferred;
+    return rc;
 }
 
 // feat (optional): HOST pointers, uploaded beside the records, as are the rows of ne and the hash ids of FlpLevel::Conn
@@ -465,16 +351,14 @@ static int encode_flp_host_core(nfagg_handle* h, const void* records, size_t n, 
     return encode_staged(h, records, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
         [&](const void* d_records, void* d_out, uint64_t* d_offsets) {
             nfagg_pb_features dfeat{};
-            if (feat && n) { int rc2 = stage_pb_features(h, feat, n, &dfeat); if (rc2 != NFAGG_OK) return rc2; }
+            if (feat && n) API_TRY(stage_pb_features(h, feat, n, &dfeat));
             NetevArgs dne{};
-            if (ne) { int rc2 = stage_netev_rows(h, ne, n, &dne); if (rc2 != NFAGG_OK) return rc2; }
+            if (ne) API_TRY(stage_netev_rows(h, ne, n, &dne));
             FlpLineTables dt = t;
             if (t.level == FlpLevel::Conn) {                              // the hash ids, uploaded
                 dt.hash_ids = nullptr;
                 if (n) {
-                    int rc2 = h->enc.conn_ids.ensure(h, n * sizeof(uint64_t));
-                    if (rc2 != NFAGG_OK) return rc2;
-                    HIP_TRY(h, hipMemcpyAsync(h->enc.conn_ids.p, t.hash_ids, n * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+                    API_TRY(stage_in(h, h->enc.conn_ids, t.hash_ids, n * sizeof(uint64_t)));
                     dt.hash_ids = h->enc.conn_ids.as<const uint64_t>();
                 }
             }
@@ -738,10 +622,7 @@ int nfagg_encode_conn_json_device(nfagg_handle* h, const void* d_carriers, const
     bool done;
     if ((rc = encode_begin(h, n, d_line_offsets, out_bytes, nullptr, 0, &done)) != NFAGG_OK || done) return rc;
     auto& S = h->enc;
-    if ((rc = S.flp_rows.ensure(h, n * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.flp_n_deferred.ensure(h, 16)) != NFAGG_OK) return rc;
-    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.net_rows.ensure(h, n * sizeof(uint2))) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {{S.flp_rows, n * sizeof(uint32_t)}, {S.flp_n_deferred, 16}, {S.k8s_rows, n * 2 * sizeof(uint32_t)}, {S.net_rows, n * sizeof(uint2)}}));
     HIP_TRY(h, hipMemsetAsync(S.flp_n_deferred.p, 0, 16, h->stream));
     uint32_t* lens = S.flp_rows.as<uint32_t>();
     uint32_t* k8s_rows = S.k8s_rows.as<uint32_t>();
@@ -753,14 +634,16 @@ int nfagg_encode_conn_json_device(nfagg_handle* h, const void* d_carriers, const
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Kubernetes resolve launch failed: %s", hipGetErrorString(e));
     e = launch_net_resolve(d_carriers, n, N, k8s_rows, k8s->d_host_ids.as<const uint32_t>(), K.n_rows, kNetNoHost, S.net_rows.as<uint2>(), h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "net resolve launch failed: %s", hipGetErrorString(e));
-    size_t deferred_unused;
-    return encode_two_pass(h, n, "conversation JSON", "write", d_out, out_cap, out_bytes, n_deferred ? n_deferred : &deferred_unused,
+    uint32_t deferred = 0;
+    rc = encode_two_pass(h, n, {"conversation JSON", "size", "write"}, d_out, out_cap, out_bytes, {S.flp_n_deferred.p, &deferred, sizeof deferred},
         [&](uint32_t* local_off, uint32_t* block_sum, uint64_t* block_base) {
             return launch_conn_json_size(d_carriers, d_values, n, L, K, N, k8s_rows, S.net_rows.as<const uint2>(), lens, local_off, block_sum, block_base,
                                          S.flp_n_deferred.as<uint32_t>(), h->stream); },
         [&](const uint32_t* local_off, const uint64_t* block_base, uint64_t) {
             return launch_conn_json_write(d_carriers, d_values, n, L, K, N, k8s_rows, S.net_rows.as<const uint2>(), lens, local_off, block_base, d_out,
                                           d_line_offsets, d_deferred, h->stream); });
+    if (n_deferred) *n_deferred = deferred;
+    return rc;
 }
 
 int nfagg_encode_conn_json(nfagg_handle* h, const void* carriers, const nfagg_conn_values* values, size_t n, const nfagg_conn_layout* layout,
@@ -769,9 +652,7 @@ int nfagg_encode_conn_json(nfagg_handle* h, const void* carriers, const nfagg_co
     if (!h || !layout || !k8s || !net || !out_bytes || !line_offsets || (n && (!carriers || !values))) return fail(h, NFAGG_EINVAL, "null argument");
     return encode_staged(h, carriers, n, out, out_cap, line_offsets, out_bytes, {{deferred, 1}},
         [&](const void* d_carriers, void* d_out, uint64_t* d_offsets) {
-            int rc = h->enc.conn_out.ensure(h, n * sizeof(nfagg_conn_values) + 16);
-            if (rc != NFAGG_OK) return rc;
-            if (n) HIP_TRY(h, hipMemcpyAsync(h->enc.conn_out.p, values, n * sizeof(nfagg_conn_values), hipMemcpyHostToDevice, h->stream));
+            API_TRY(stage_in(h, h->enc.conn_out, values, n * sizeof(nfagg_conn_values)));
             return nfagg_encode_conn_json_device(h, d_carriers, h->enc.conn_out.as<const nfagg_conn_values>(), n, layout, k8s, net, d_out, out_cap, d_offsets,
                                                  deferred ? h->enc.out_extra[0].as<uint8_t>() : nullptr, n_deferred, out_bytes); });
 }

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "nfagg_api_tables.h"
+#include "nfagg_api_call.h"
 #include "nfagg_filter.h"
 
 using namespace nfagg;
@@ -198,8 +199,7 @@ int nfagg_filter_apply_device(nfagg_handle* h, const nfagg_filter* filter, const
     if (P.need & kFilterNeedClock) {
         if (!opt) return fail(h, NFAGG_EINVAL, "the filter reads the flow times: the options are required");
         if (opt->struct_size != sizeof(nfagg_flp_options)) return fail(h, NFAGG_EINVAL, "nfagg_flp_options.struct_size mismatch");
-        clk.now_sec = opt->now_unix_ns / 1000000000ll; clk.now_nsec = opt->now_unix_ns % 1000000000ll;       // time.Time's (sec, nsec), 0 <= nsec < 1e9
-        if (clk.now_nsec < 0) { clk.now_nsec += 1000000000ll; clk.now_sec -= 1; }
+        split_now(opt->now_unix_ns, clk.now_sec, clk.now_nsec);
         clk.mono_now = opt->mono_now_ns;
     }
     PbFeat F{};
@@ -212,11 +212,8 @@ int nfagg_filter_apply_device(nfagg_handle* h, const nfagg_filter* filter, const
     auto& S = h->enc;
     nfagg_filter* f = const_cast<nfagg_filter*>(filter);          // the scratch alone
     const size_t blocks = (n + kFilterScanBlock - 1) / kFilterScanBlock;
-    int rc;
-    if ((rc = S.local_off.ensure(h, (n + 1) * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.block_sum.ensure(h, blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.block_base.ensure(h, (blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
-    if ((rc = grow_samp(h, f, n)) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {{S.local_off, (n + 1) * sizeof(uint32_t)}, {S.block_sum, blocks * sizeof(uint32_t)}, {S.block_base, (blocks + 1) * sizeof(uint64_t)}}));
+    API_TRY(grow_samp(h, f, n));
     uint32_t* d_counter = f->d_samp.as<uint32_t>();
     uint32_t* d_samp = d_counter + 4;
     HIP_TRY(h, hipMemsetAsync(d_counter, 0, 16, h->stream));
@@ -253,32 +250,24 @@ int nfagg_filter_apply(nfagg_handle* h, const nfagg_filter* filter, const void* 
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t room = cap < n ? cap : n;              // never more kept than flows
-    int rc;
-    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.net_rows.ensure(h, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out_extra[0].ensure(h, n + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out_extra[1].ensure(h, n + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out_offsets.ensure(h, room * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if (out_records && (rc = S.out.ensure(h, room * kRecordBytes + 16)) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {{S.out_extra[0], n + kStageSlack}, {S.out_extra[1], n + kStageSlack}, {S.out_offsets, room * sizeof(uint32_t) + kStageSlack},
+                           {S.out, out_records ? room * kRecordBytes + kStageSlack : 0}}));
+    API_TRY(stage_in(h, S.in_records, records, n * kRecordBytes));
+    API_TRY(stage_in(h, S.k8s_rows, k8s_rows, k8s_rows ? n * 2 * sizeof(uint32_t) : 0));
+    API_TRY(stage_in(h, S.net_rows, net_rows, net_rows ? n * sizeof(nfagg_net_row) : 0));
     nfagg_pb_features dfeat{};
-    if (n) {
-        HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-        if (k8s_rows) HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        if (net_rows) HIP_TRY(h, hipMemcpyAsync(S.net_rows.p, net_rows, n * sizeof(nfagg_net_row), hipMemcpyHostToDevice, h->stream));
-        if (features && (rc = stage_pb_features(h, features, n, &dfeat)) != NFAGG_OK) return rc;
-    }
+    if (features && n) API_TRY(stage_pb_features(h, features, n, &dfeat));
     const bool compact = kept_idx || out_records;
-    rc = nfagg_filter_apply_device(h, filter, S.in_records.p, n, (features && n) ? &dfeat : nullptr, k8s_rows ? S.k8s_rows.as<const uint32_t>() : nullptr,
+    const int rc = nfagg_filter_apply_device(h, filter, S.in_records.p, n, (features && n) ? &dfeat : nullptr, k8s_rows ? S.k8s_rows.as<const uint32_t>() : nullptr,
                                    net_rows ? S.net_rows.as<const nfagg_net_row>() : nullptr, opt, seed, first_index, S.out_extra[0].as<uint8_t>(),
                                    S.out_extra[1].as<uint8_t>(), compact ? S.out_offsets.as<uint32_t>() : nullptr, out_records ? S.out.p : nullptr, room,
                                    n_kept, n_deferred);
     if (rc != NFAGG_OK && rc != NFAGG_TRUNCATED) return rc;
-    if (n && keep) HIP_TRY(h, hipMemcpyAsync(keep, S.out_extra[0].p, n, hipMemcpyDeviceToHost, h->stream));
-    if (n && rule) HIP_TRY(h, hipMemcpyAsync(rule, S.out_extra[1].p, n, hipMemcpyDeviceToHost, h->stream));
-    if (rc == NFAGG_OK && *n_kept) {
-        if (kept_idx) HIP_TRY(h, hipMemcpyAsync(kept_idx, S.out_offsets.p, *n_kept * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        if (out_records) HIP_TRY(h, hipMemcpyAsync(out_records, S.out.p, *n_kept * kRecordBytes, hipMemcpyDeviceToHost, h->stream));
+    API_TRY(fetch(h, keep, S.out_extra[0], keep ? n : 0));
+    API_TRY(fetch(h, rule, S.out_extra[1], rule ? n : 0));
+    if (rc == NFAGG_OK) {
+        API_TRY(fetch(h, kept_idx, S.out_offsets, kept_idx ? *n_kept * sizeof(uint32_t) : 0));
+        API_TRY(fetch(h, out_records, S.out, out_records ? *n_kept * kRecordBytes : 0));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return rc;
@@ -316,14 +305,11 @@ int nfagg_gather(nfagg_handle* h, const void* src, size_t n_src, size_t elem_byt
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
     if (!n_kept) return NFAGG_OK;
-    int rc;
-    if ((rc = S.in_records.ensure(h, n_src * elem_bytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out_offsets.ensure(h, n_kept * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out.ensure(h, n_kept * elem_bytes + 16)) != NFAGG_OK) return rc;
-    if (n_src) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, src, n_src * elem_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(S.out_offsets.p, kept_idx, n_kept * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    if ((rc = nfagg_gather_device(h, S.in_records.p, n_src, elem_bytes, S.out_offsets.as<const uint32_t>(), n_kept, S.out.p)) != NFAGG_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dst, S.out.p, n_kept * elem_bytes, hipMemcpyDeviceToHost, h->stream));
+    API_TRY(S.out.ensure(h, n_kept * elem_bytes + kStageSlack));
+    API_TRY(stage_in(h, S.in_records, src, n_src * elem_bytes));
+    API_TRY(stage_in(h, S.out_offsets, kept_idx, n_kept * sizeof(uint32_t)));
+    API_TRY(nfagg_gather_device(h, S.in_records.p, n_src, elem_bytes, S.out_offsets.as<const uint32_t>(), n_kept, S.out.p));
+    API_TRY(fetch(h, dst, S.out, n_kept * elem_bytes));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
 }

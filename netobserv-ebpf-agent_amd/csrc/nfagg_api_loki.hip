@@ -13,6 +13,7 @@
 #include "../../include/nfagg.h"
 #include "nfagg_internal.h"
 #include "nfagg_handle.h"
+#include "nfagg_api_call.h"
 #include "nfagg_api_tables.h"
 #include "nfagg_loki.h"
 
@@ -34,7 +35,9 @@ struct nfagg_loki_table {
 
 namespace nfagg {
 
-// The plan a handle keeps: the arrays the write reads again, and what the call was made with.
+// The plan a handle keeps: the arrays the write reads again, and what the call was made with. Its staging is its own, the
+// namer table and the host entry points' arrays included: the plan outlives the call that made it and nfagg_loki_write reads it
+// again, so the handle's EncodeScratch, which the next encoder call reuses, cannot hold it.
 struct LokiPlan {
     DevBuf ctl, keys, first, sid, slot_of, rows8, ts, lens, deferred;               // the key kernel's
     DevBuf flag, rank, streams, pinc, cuts, key, key_sorted, val, perm, gidx, esz, E, gs, groups, tmp;
@@ -123,11 +126,6 @@ int up(nfagg_handle* h, DevBuf& d, const void* src, size_t bytes) {
     HIP_TRY(h, d.alloc(std::max<size_t>(bytes, 16)));
     if (bytes) HIP_TRY(h, hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
     return NFAGG_OK;
-}
-
-void split_now(int64_t now_unix_ns, int64_t& sec, int64_t& nsec) {   // time.Time's (sec, nsec), 0 <= nsec < 1e9
-    sec = now_unix_ns / 1000000000ll; nsec = now_unix_ns % 1000000000ll;
-    if (nsec < 0) { nsec += 1000000000ll; sec -= 1; }
 }
 
 }  // namespace
@@ -284,13 +282,12 @@ int nfagg_loki_plan_device(nfagg_handle* h, const void* d_records, size_t n, con
     const size_t slots = (size_t)std::max<uint64_t>(next_pow2(2ull * std::min<uint64_t>(n, kLokiMaxStreams)), kLokiMinSlots);
     const size_t n_streams_max = std::min<size_t>(n, kLokiMaxStreams);
     S.tmp_bytes = loki_tmp_bytes(n);
-    struct { DevBuf* b; size_t bytes; } need[] = {
-        {&S.ctl, 256}, {&S.keys, slots * 16}, {&S.first, slots * 4}, {&S.sid, slots * 4}, {&S.slot_of, n * 4}, {&S.rows8, n * 32}, {&S.ts, n * 16},
-        {&S.lens, n * 4}, {&S.deferred, n + 16}, {&S.flag, (n + 1) * 4}, {&S.rank, (n + 1) * 4}, {&S.streams, n_streams_max * sizeof(nfagg_loki_stream)},
-        {&S.pinc, (n + 1) * 8}, {&S.cuts, n * 4}, {&S.key, n * 8}, {&S.key_sorted, (n + 1) * 8}, {&S.val, n * 4}, {&S.perm, n * 4}, {&S.gidx, (n + 1) * 4},
-        {&S.esz, (n + 1) * 4}, {&S.E, (n + 1) * 8}, {&S.gs, n * 4}, {&S.groups, n * sizeof(nfagg_loki_group)}, {&S.tmp, S.tmp_bytes},
-        {&S.scan_local, (n + 1) * 4}, {&S.scan_sum, ((n + 1) / 1024 + 2) * 4}, {&S.scan_base, ((n + 1) / 1024 + 3) * 8}};
-    for (auto& q : need) if ((rc = q.b->ensure(h, q.bytes)) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {
+        {S.ctl, 256}, {S.keys, slots * 16}, {S.first, slots * 4}, {S.sid, slots * 4}, {S.slot_of, n * 4}, {S.rows8, n * 32}, {S.ts, n * 16},
+        {S.lens, n * 4}, {S.deferred, n + 16}, {S.flag, (n + 1) * 4}, {S.rank, (n + 1) * 4}, {S.streams, n_streams_max * sizeof(nfagg_loki_stream)},
+        {S.pinc, (n + 1) * 8}, {S.cuts, n * 4}, {S.key, n * 8}, {S.key_sorted, (n + 1) * 8}, {S.val, n * 4}, {S.perm, n * 4}, {S.gidx, (n + 1) * 4},
+        {S.esz, (n + 1) * 4}, {S.E, (n + 1) * 8}, {S.gs, n * 4}, {S.groups, n * sizeof(nfagg_loki_group)}, {S.tmp, S.tmp_bytes},
+        {S.scan_local, (n + 1) * 4}, {S.scan_sum, ((n + 1) / 1024 + 2) * 4}, {S.scan_base, ((n + 1) / 1024 + 3) * 8}}));
     const LokiScan X{S.scan_local.as<uint32_t>(), S.scan_sum.as<uint32_t>(), S.scan_base.as<uint64_t>()};      // behind ensure: a growth moves the blocks
     FlpLineArgs& A = S.A;                                   // into the plan's own staging: the write reads both again
     if ((rc = stage_flp_line(h, d_records, n, opt, F, t, FlpLineStage{S.names, S.esc, S.k8s_rows, S.net_rows, S.h_names, S.h_esc}, &A)) != NFAGG_OK) return rc;
@@ -345,31 +342,28 @@ int nfagg_loki_plan(nfagg_handle* h, const void* records, size_t n, const nfagg_
     if (n > (1ull << 30)) return fail(h, NFAGG_ERANGE, "%zu flows in one call, more than 2^30", n);
     LokiPlan& S = *plan_of(h);
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.in_ids.ensure(h, n * 8 + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out_streams.ensure(h, (size_t)stream_cap * sizeof(nfagg_loki_stream) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out_groups.ensure(h, (size_t)group_cap * sizeof(nfagg_loki_group) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.out_deferred.ensure(h, n + 16)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    if (n && hash_ids) HIP_TRY(h, hipMemcpyAsync(S.in_ids.p, hash_ids, n * 8, hipMemcpyHostToDevice, h->stream));
+    API_TRY(ensure_all(h, {{S.out_streams, (size_t)stream_cap * sizeof(nfagg_loki_stream) + kStageSlack},
+                           {S.out_groups, (size_t)group_cap * sizeof(nfagg_loki_group) + kStageSlack}, {S.out_deferred, n + kStageSlack}}));
+    API_TRY(stage_in(h, S.in_records, records, n * kRecordBytes));
+    API_TRY(stage_in(h, S.in_ids, hash_ids, hash_ids ? n * 8 : 0));
     if (features && features->struct_size != sizeof(nfagg_pb_features)) return fail(h, NFAGG_EINVAL, "nfagg_pb_features.struct_size mismatch");
     nfagg_pb_features dfeat{};
-    if (features && n && (rc = stage_pb_features(h, features, n, &dfeat)) != NFAGG_OK) return rc;      // the handle's encoder staging: no other encoder call before the write
+    if (features && n) API_TRY(stage_pb_features(h, features, n, &dfeat));      // the handle's encoder staging: no other encoder call before the write
     const uint16_t* d_rows = nullptr;
     if (rows && n) {
-        if ((rc = S.in_ne_rows.ensure(h, n * 8 + 16)) != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(S.in_ne_rows.p, rows, n * 8, hipMemcpyHostToDevice, h->stream));
+        API_TRY(stage_in(h, S.in_ne_rows, rows, n * 8));
         d_rows = S.in_ne_rows.as<const uint16_t>();
     }
-    rc = nfagg_loki_plan_device(h, S.in_records.p, n, (features && n) ? &dfeat : nullptr, rows && !n ? rows : d_rows, netev_table, tls_names, k8s, net,
+    int rc = nfagg_loki_plan_device(h, S.in_records.p, n, (features && n) ? &dfeat : nullptr, rows && !n ? rows : d_rows, netev_table, tls_names, k8s, net,
                                 hash_ids ? S.in_ids.as<const uint64_t>() : nullptr, opt,
                                 table, now_unix_ns, stream_cap ? S.out_streams.as<nfagg_loki_stream>() : nullptr, stream_cap,
                                 group_cap ? S.out_groups.as<nfagg_loki_group>() : nullptr, group_cap, deferred ? S.out_deferred.as<uint8_t>() : nullptr, counts);
     if (rc != NFAGG_OK && rc != NFAGG_TRUNCATED) return rc;
-    if (n && deferred) HIP_TRY(h, hipMemcpyAsync(deferred, S.out_deferred.p, n, hipMemcpyDeviceToHost, h->stream));
-    if (rc == NFAGG_OK && counts->n_streams) HIP_TRY(h, hipMemcpyAsync(streams, S.out_streams.p, counts->n_streams * sizeof(nfagg_loki_stream), hipMemcpyDeviceToHost, h->stream));
-    if (rc == NFAGG_OK && counts->n_groups) HIP_TRY(h, hipMemcpyAsync(groups, S.out_groups.p, counts->n_groups * sizeof(nfagg_loki_group), hipMemcpyDeviceToHost, h->stream));
+    API_TRY(fetch(h, deferred, S.out_deferred, deferred ? n : 0));
+    if (rc == NFAGG_OK) {
+        API_TRY(fetch(h, streams, S.out_streams, counts->n_streams * sizeof(nfagg_loki_stream)));
+        API_TRY(fetch(h, groups, S.out_groups, counts->n_groups * sizeof(nfagg_loki_group)));
+    }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return rc;
 }
@@ -397,16 +391,16 @@ int nfagg_loki_write_device(nfagg_handle* h, const void* labels, const uint64_t*
     if (label_offsets[c.n_streams] - label_offsets[0] >= (1ull << 32)) return fail(h, NFAGG_ERANGE, "the streams' label texts come to 2^32 bytes or more");
     const uint32_t m = c.n_part, ng = c.n_groups, nb = c.n_batches;
     const size_t blocks = (m + 1023) / 1024;
-    int rc;
-    struct { DevBuf* b; size_t bytes; } need[] = {{&S.hsz, (ng + 1) * 4ull}, {&S.H, (ng + 1) * 8ull}, {&S.labels, off[c.n_streams] + 16ull}, {&S.lab_off, (c.n_streams + 1) * 4ull},
-                                                  {&S.bpos, (nb + 1) * 4ull}, {&S.local_off, m * 4ull}, {&S.block_base, (blocks + 1) * 8}};
-    for (auto& q : need) if ((rc = q.b->ensure(h, q.bytes)) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {{S.hsz, (ng + 1) * 4ull}, {S.H, (ng + 1) * 8ull}, {S.labels, off[c.n_streams] + 16ull}, {S.lab_off, (c.n_streams + 1) * 4ull},
+                           {S.bpos, (nb + 1) * 4ull}, {S.local_off, m * 4ull}, {S.block_base, (blocks + 1) * 8}}));
     HIP_TRY(h, hipMemcpyAsync(S.labels.p, (const uint8_t*)labels + label_offsets[0], off[c.n_streams], hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(S.lab_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
     LokiWriteDev W{S.ctl.as<const LokiCtl>(), S.perm.as<const uint32_t>(), S.flag.as<const uint32_t>(), S.gidx.as<const uint32_t>(), S.E.as<const uint64_t>(),
                    S.gs.as<const uint32_t>(), S.groups.as<const nfagg_loki_group>(), S.labels.as<const uint8_t>(), S.lab_off.as<const uint32_t>(),
                    S.hsz.as<uint32_t>(), S.H.as<uint64_t>(), S.local_off.as<uint32_t>(), S.block_base.as<uint64_t>(), S.bpos.as<uint32_t>()};
     const LokiScan X{S.scan_local.as<uint32_t>(), S.scan_sum.as<uint32_t>(), S.scan_base.as<uint64_t>()};     // sized by the plan: n_groups + 1 <= n + 1
+    // the two passes are written out: the scans are the plan's own (encode_two_pass hands out the handle's), the size pass has
+    // no block sums of its own, and its messages are not "<what> <verb> launch failed"
     hipError_t e = launch_loki_offsets(m, ng, nb, W, d_batch_offsets, d_batch_entries, X, h->stream);
     if (e != hipSuccess) return fail(h, NFAGG_EDEVICE, "Loki offsets failed: %s", hipGetErrorString(e));
     uint64_t total = 0;
@@ -429,15 +423,12 @@ int nfagg_loki_write(nfagg_handle* h, const void* labels, const uint64_t* label_
     const uint32_t nb = S.counts.n_batches;
     if (nb && !batch_entries) return fail(h, NFAGG_EINVAL, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = S.out.ensure(h, out_cap + 32)) != NFAGG_OK) return rc;
-    if ((rc = S.boffs.ensure(h, (nb + 1) * 8ull)) != NFAGG_OK) return rc;
-    if ((rc = S.bents.ensure(h, (nb + 1) * 4ull)) != NFAGG_OK) return rc;
-    rc = nfagg_loki_write_device(h, labels, label_offsets, out ? S.out.p : nullptr, out_cap, S.boffs.as<uint64_t>(), S.bents.as<uint32_t>(), out_bytes);
+    API_TRY(ensure_all(h, {{S.out, out_cap + kStageSlack}, {S.boffs, (nb + 1) * 8ull}, {S.bents, (nb + 1) * 4ull}}));
+    const int rc = nfagg_loki_write_device(h, labels, label_offsets, out ? S.out.p : nullptr, out_cap, S.boffs.as<uint64_t>(), S.bents.as<uint32_t>(), out_bytes);
     if (rc != NFAGG_OK && rc != NFAGG_TRUNCATED) return rc;
-    HIP_TRY(h, hipMemcpyAsync(batch_offsets, S.boffs.p, (nb + 1) * 8ull, hipMemcpyDeviceToHost, h->stream));
-    if (nb) HIP_TRY(h, hipMemcpyAsync(batch_entries, S.bents.p, nb * 4ull, hipMemcpyDeviceToHost, h->stream));
-    if (rc == NFAGG_OK && *out_bytes) HIP_TRY(h, hipMemcpyAsync(out, S.out.p, *out_bytes, hipMemcpyDeviceToHost, h->stream));
+    API_TRY(fetch(h, batch_offsets, S.boffs, (nb + 1) * 8ull));
+    API_TRY(fetch(h, batch_entries, S.bents, nb * 4ull));
+    if (rc == NFAGG_OK) API_TRY(fetch(h, out, S.out, *out_bytes));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return rc;
 }

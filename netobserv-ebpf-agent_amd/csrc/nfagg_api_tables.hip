@@ -14,6 +14,7 @@
 #include "../../include/nfagg.h"
 #include "nfagg_internal.h"
 #include "nfagg_handle.h"
+#include "nfagg_api_call.h"
 #include "nfagg_api_tables.h"
 #include "nfagg_flp.h"
 #include "nfagg_netev.h"
@@ -266,8 +267,7 @@ int nfagg_netev_resolve_device(nfagg_handle* h, const nfagg_netev_table* table, 
     if (missing_cap > 0xffffffffull) return fail(h, NFAGG_EINVAL, "missing_cap too large");
     *n_missing = 0; *zero_missing = 0; *overflow = 0;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = h->enc.ne_info.ensure(h, 16);
-    if (rc != NFAGG_OK) return rc;
+    API_TRY(h->enc.ne_info.ensure(h, 16));
     HIP_TRY(h, hipMemsetAsync(h->enc.ne_info.p, 0, 16, h->stream));
     if (missing_cap) HIP_TRY(h, hipMemsetAsync(d_missing_set, 0, missing_cap * sizeof(uint64_t), h->stream));
     if (n) {
@@ -293,25 +293,20 @@ int nfagg_netev_resolve(nfagg_handle* h, const nfagg_netev_table* table, const u
     HIP_TRY(h, hipSetDevice(h->device));
     const void* src[3] = {present, network_events, drops};
     const size_t elem[3] = {1, sizeof(nfagg_network_events_metrics), sizeof(nfagg_pkt_drop_metrics)}, out_elem[3] = {1, sizeof(nfagg_pkt_drop_metrics), 8};
-    int rc;
     for (int k = 0; k < 3; k++) {
-        if ((rc = S.ne_out[k].ensure(h, n * out_elem[k] + 16)) != NFAGG_OK) return rc;
-        if (!src[k] || !n) continue;
-        if ((rc = S.ne_in[k].ensure(h, n * elem[k] + 16)) != NFAGG_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(S.ne_in[k].p, src[k], n * elem[k], hipMemcpyHostToDevice, h->stream));
+        API_TRY(S.ne_out[k].ensure(h, n * out_elem[k] + kStageSlack));
+        if (src[k] && n) API_TRY(stage_in(h, S.ne_in[k], src[k], n * elem[k]));
     }
-    if ((rc = S.ne_missing.ensure(h, missing_cap * sizeof(uint64_t) + 16)) != NFAGG_OK) return rc;
+    API_TRY(S.ne_missing.ensure(h, missing_cap * sizeof(uint64_t) + kStageSlack));
     size_t stored = 0; int zero = 0;
-    rc = nfagg_netev_resolve_device(h, table, S.ne_in[0].as<const uint8_t>(), network_events ? S.ne_in[1].as<const nfagg_network_events_metrics>() : nullptr,
+    API_TRY(nfagg_netev_resolve_device(h, table, S.ne_in[0].as<const uint8_t>(), network_events ? S.ne_in[1].as<const nfagg_network_events_metrics>() : nullptr,
                                     drops ? S.ne_in[2].as<const nfagg_pkt_drop_metrics>() : nullptr, n, S.ne_out[0].as<uint8_t>(),
                                     S.ne_out[1].as<nfagg_pkt_drop_metrics>(), S.ne_out[2].as<uint16_t>(), missing_cap ? S.ne_missing.as<uint64_t>() : nullptr,
-                                    missing_cap, &stored, &zero, overflow);
-    if (rc != NFAGG_OK) return rc;
+                                    missing_cap, &stored, &zero, overflow));
     void* dst[3] = {present_out, drops_out, rows_out};
-    for (int k = 0; k < 3; k++)
-        if (n) HIP_TRY(h, hipMemcpyAsync(dst[k], S.ne_out[k].p, n * out_elem[k], hipMemcpyDeviceToHost, h->stream));
+    for (int k = 0; k < 3; k++) API_TRY(fetch(h, dst[k], S.ne_out[k], n * out_elem[k]));
     std::vector<uint64_t> set(missing_cap);
-    if (missing_cap) HIP_TRY(h, hipMemcpyAsync(set.data(), S.ne_missing.p, missing_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    API_TRY(fetch(h, set.data(), S.ne_missing, missing_cap * sizeof(uint64_t)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     size_t m = 0;
     for (uint64_t v : set) if (v) memcpy(missing[m++], &v, 8);
@@ -575,12 +570,10 @@ int nfagg_k8s_resolve(nfagg_handle* h, const nfagg_k8s_table* table, const void*
     if (!h || !table || (n && (!records || !rows))) return fail(h, NFAGG_EINVAL, "null argument");
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = nfagg_k8s_resolve_device(h, table, S.in_records.p, n, S.k8s_rows.as<uint32_t>())) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(rows, S.k8s_rows.p, n * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    API_TRY(S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + kStageSlack));
+    API_TRY(stage_in(h, S.in_records, records, n * kRecordBytes));
+    API_TRY(nfagg_k8s_resolve_device(h, table, S.in_records.p, n, S.k8s_rows.as<uint32_t>()));
+    API_TRY(fetch(h, rows, S.k8s_rows, n * 2 * sizeof(uint32_t)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
 }
@@ -730,15 +723,11 @@ int nfagg_net_resolve(nfagg_handle* h, const nfagg_net_table* net_table, const n
     if (dir && n && !k8s_rows) return fail(h, NFAGG_EINVAL, "reinterpret_direction needs the Kubernetes table, the flows' rows and the options");
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.net_rows.ensure(h, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-    if (n && dir) HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    if ((rc = nfagg_net_resolve_device(h, net_table, k8s_table, S.in_records.p, n, S.k8s_rows.as<const uint32_t>(), opt, S.net_rows.as<nfagg_net_row>())) != NFAGG_OK)
-        return rc;
-    if (n) HIP_TRY(h, hipMemcpyAsync(out, S.net_rows.p, n * sizeof(nfagg_net_row), hipMemcpyDeviceToHost, h->stream));
+    API_TRY(S.net_rows.ensure(h, n * sizeof(nfagg_net_row) + kStageSlack));
+    API_TRY(stage_in(h, S.in_records, records, n * kRecordBytes));
+    API_TRY(stage_in(h, S.k8s_rows, k8s_rows, dir ? n * 2 * sizeof(uint32_t) : 0));
+    API_TRY(nfagg_net_resolve_device(h, net_table, k8s_table, S.in_records.p, n, S.k8s_rows.as<const uint32_t>(), opt, S.net_rows.as<nfagg_net_row>()));
+    API_TRY(fetch(h, out, S.net_rows, n * sizeof(nfagg_net_row)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;
 }
@@ -930,12 +919,9 @@ static int metrics_fold_device_core(nfagg_handle* h, const nfagg_metrics_table* 
     M.rows = K.rows; M.n_rows = K.n_rows; M.has_layer = K.has_layer;
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc;
     const size_t slot_bytes = (size_t)blocks * kMetMinSlots * words * sizeof(uint64_t);
-    if ((rc = S.met_slots.ensure(h, 256 + slot_bytes)) != NFAGG_OK) return rc;
-    if ((rc = S.local_off.ensure(h, (size_t)blocks * kMetMinSlots * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.block_sum.ensure(h, (size_t)blocks * sizeof(uint32_t))) != NFAGG_OK) return rc;
-    if ((rc = S.block_base.ensure(h, ((size_t)blocks + 1) * sizeof(uint64_t))) != NFAGG_OK) return rc;
+    API_TRY(ensure_all(h, {{S.met_slots, 256 + slot_bytes}, {S.local_off, (size_t)blocks * kMetMinSlots * sizeof(uint32_t)},
+                           {S.block_sum, (size_t)blocks * sizeof(uint32_t)}, {S.block_base, ((size_t)blocks + 1) * sizeof(uint64_t)}}));
     M.ctl = S.met_slots.as<MetCtl>();
     uint64_t* slots = (uint64_t*)(S.met_slots.as<uint8_t>() + 256);
     for (uint32_t g = 0; g < G; g++) M.slots[g] = slots + (size_t)M.first_block[g] * kMetMinSlots * words;
@@ -973,29 +959,24 @@ static int metrics_fold_host_core(nfagg_handle* h, const nfagg_metrics_table* ta
     }
     auto& S = h->enc;
     HIP_TRY(h, hipSetDevice(h->device));
+    API_TRY(S.met_out.ensure(h, total * group_bytes + kStageSlack));
+    API_TRY(stage_in(h, S.in_records, records, n * kRecordBytes));
+    API_TRY(stage_in(h, S.k8s_rows, k8s_rows, n * 2 * sizeof(uint32_t)));
+    API_TRY(stage_in(h, S.net_rows, net_rows, net_rows ? n * sizeof(nfagg_net_row) : 0));
     int rc;
-    if ((rc = S.in_records.ensure(h, n * kRecordBytes + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.k8s_rows.ensure(h, n * 2 * sizeof(uint32_t) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.net_rows.ensure(h, n * sizeof(nfagg_net_row) + 16)) != NFAGG_OK) return rc;
-    if ((rc = S.met_out.ensure(h, total * group_bytes + 16)) != NFAGG_OK) return rc;
-    if (n) {
-        HIP_TRY(h, hipMemcpyAsync(S.in_records.p, records, n * kRecordBytes, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(S.k8s_rows.p, k8s_rows, n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        if (net_rows) HIP_TRY(h, hipMemcpyAsync(S.net_rows.p, net_rows, n * sizeof(nfagg_net_row), hipMemcpyHostToDevice, h->stream));
-    }
     void* d_out[kMetMaxGroupings] = {};
     size_t at = 0;
     for (uint32_t g = 0; g < G; g++) { d_out[g] = S.met_out.as<uint8_t>() + at * group_bytes; at += group_cap[g]; }
     const nfagg_net_row* d_net = net_rows ? S.net_rows.as<const nfagg_net_row>() : nullptr;
     if (content) {
         nfagg_pb_features dfeat{};
-        if (feat && n && (rc = stage_pb_features(h, feat, n, &dfeat)) != NFAGG_OK) return rc;
+        if (feat && n) API_TRY(stage_pb_features(h, feat, n, &dfeat));
         rc = nfagg_metrics_fold_content_device(h, table, S.in_records.p, n, (feat && n) ? &dfeat : nullptr, S.k8s_rows.as<const uint32_t>(), d_net, group_cap,
                                                (nfagg_metric_group_content* const*)d_out, n_groups);
     } else
         rc = nfagg_metrics_fold_device(h, table, S.in_records.p, n, S.k8s_rows.as<const uint32_t>(), d_net, group_cap, (nfagg_metric_group* const*)d_out, n_groups);
     if (rc != NFAGG_OK) return rc;
-    for (uint32_t g = 0; g < G; g++)
+    for (uint32_t g = 0; g < G; g++)          // each grouping's part of met_out
         if (n_groups[g]) HIP_TRY(h, hipMemcpyAsync(out[g], d_out[g], (size_t)n_groups[g] * group_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NFAGG_OK;

@@ -25,6 +25,10 @@ struct WindowSink {
 // memory is one exposed load latency per byte.
 struct Ip4w { uint32_t w[4]; };
 NF_DEV uint8_t ip_byte(const Ip4w& a, int k) { return (uint8_t)(a.w[k >> 2] >> (8 * (k & 3))); }
+// net.IP.To4() != nil: ten zero bytes, ff ff (::ffff:a.b.c.d)
+NF_DEV bool ip_v4_mapped(const Ip4w& a) { return (a.w[0] | a.w[1]) == 0 && a.w[2] == 0xffff0000u; }
+// model.AllZeroIP (record.go:233-238): all zero, or ::ffff:0.0.0.0
+NF_DEV bool ip_all_zero(const Ip4w& a) { return (a.w[0] | a.w[1] | a.w[3]) == 0 && (a.w[2] == 0 || a.w[2] == 0xffff0000u); }
 
 // currentTime.Add(-Duration(mono_now - ts)) (record.go:90-97) as time.Time's (sec, nsec), 0 <= nsec < 1e9.
 // now_sec / now_nsec: currentTime, normalised.

@@ -95,7 +95,6 @@ template <typename S> struct EscSink {
 };
 
 // model.AllZeroIP (record.go:233-238): net.IPv6zero, or net.IPv4zero in its 16-byte form ::ffff:0.0.0.0
-NF_DEV bool all_zero_ip(const Ip4w& a) { return (a.w[0] | a.w[1] | a.w[3]) == 0 && (a.w[2] == 0 || a.w[2] == 0xffff0000u); }
 
 // The longest line: every key of nfagg_flp.hip's worst case plus, in the order of the list above, 15 + 17 + 35 + 14 + 30
 // + 11 + (2 + 6 x 31: a dotted name has at most 31 bytes) for DNS, 27 + 24 for IPsec, 21 + (28 + the longest name) + 27
@@ -213,7 +212,7 @@ struct FlpContent {
         if ((have & NFAGG_FEAT_ADDITIONAL) && v) { lit(s, ",\"TimeFlowRttNs\":"); dec_i64(s, (int64_t)v); }
     }
     NF_DEV bool xlated() const {                                        // decode_protobuf.go:155-157
-        return (have & NFAGG_FEAT_XLAT) && !all_zero_ip(Ip4w{{xlt[0], xlt[1], xlt[2], xlt[3]}}) && !all_zero_ip(Ip4w{{xlt[4], xlt[5], xlt[6], xlt[7]}});
+        return (have & NFAGG_FEAT_XLAT) && !ip_all_zero(Ip4w{{xlt[0], xlt[1], xlt[2], xlt[3]}}) && !ip_all_zero(Ip4w{{xlt[4], xlt[5], xlt[6], xlt[7]}});
     }
     template <typename S> NF_DEV void xlat(S& s) const {                // decode_protobuf.go:158-167
         if (!xlated()) return;

@@ -27,9 +27,6 @@ constexpr uint32_t kIxXlatBytes = sizeof(nfagg_xlat_metrics), kIxAddBytes = size
 static_assert(kIxXlatBytes == 56 && kIxAddBytes == 32, "feature part layouts");
 static_assert(sizeof(nfagg_flp_ipfix_elements) == 9424 && offsetof(nfagg_flp_ipfix_elements, str) == 208, "state layout");
 
-NF_DEV bool ix_v4_mapped(const Ip4w& a) { return (a.w[0] | a.w[1]) == 0 && a.w[2] == 0xffff0000u; }
-// model.AllZeroIP (record.go:233-238): all zero, or ::ffff:0.0.0.0
-NF_DEV bool ix_all_zero(const Ip4w& a) { return (a.w[0] | a.w[1] | a.w[3]) == 0 && (a.w[2] == 0 || a.w[2] == 0xffff0000u); }
 NF_DEV Ip4w ix_load_ip(const uint8_t* p) { const uint32_t* q = reinterpret_cast<const uint32_t*>(p); return Ip4w{{q[0], q[1], q[2], q[3]}}; }
 // string k of the six: which side's row (0 src, 1 dst) and which of its three strings (0 namespace, 1 name, 2 host name)
 NF_DEV uint32_t ix_str_side(uint32_t k) { return k < 4 ? k >> 1 : k - 4; }
@@ -41,7 +38,7 @@ NF_DEV bool ix_xlat(const IxArgs& A, uint64_t j, Ip4w& xs, Ip4w& xd, uint32_t& p
     const uint8_t* x = A.F.xlat + j * kIxXlatBytes;
     xs = ix_load_ip(x + 16); xd = ix_load_ip(x + 32);
     ports = *reinterpret_cast<const uint32_t*>(x + 48);           // sport | dport << 16
-    return !ix_all_zero(xs) && !ix_all_zero(xd);
+    return !ip_all_zero(xs) && !ip_all_zero(xd);
 }
 NF_DEV uint64_t ix_rtt(const IxArgs& A, uint64_t j) {             // record.go:121-125: 0 = no TimeFlowRttNs key
     if (!A.F.additional || !A.F.present || !(A.F.present[j] & NFAGG_FEAT_ADDITIONAL)) return 0;
@@ -205,7 +202,7 @@ NF_DEV void ix_gather(const IxArgs& A, const Rec& r, uint64_t i, const int32_t (
         }
     }
     // entities/ie.go:683-688: an Ipv4Address element whose value has no To4() fails the record
-    M.fail = !v6 && (!addr_ok || !ix_v4_mapped(M.sip) || !ix_v4_mapped(M.dip) || (M.xset && (!ix_v4_mapped(M.xs) || !ix_v4_mapped(M.xd))));
+    M.fail = !v6 && (!addr_ok || !ip_v4_mapped(M.sip) || !ip_v4_mapped(M.dip) || (M.xset && (!ip_v4_mapped(M.xs) || !ip_v4_mapped(M.xd))));
 }
 
 template <int N, typename S> NF_DEV void ix_be(S& s, uint64_t v) {

@@ -106,7 +106,7 @@ template <typename S> NF_DEV void mac_text(S& s, uint64_t mac) {
 // netip's appendTo6: the first longest run of at least two zero groups becomes "::", groups in lower-case hex without
 // leading zeros.
 template <typename S> NF_DEV void ip_text(S& s, const Ip4w& a) {
-    if ((a.w[0] | a.w[1]) == 0 && a.w[2] == 0xffff0000u) {
+    if (ip_v4_mapped(a)) {
 #pragma unroll
         for (int k = 0; k < 4; k++) { if (k) s.put('.'); dec<3>(s, ip_byte(a, 12 + k)); }
         return;

@@ -1,6 +1,7 @@
 // nfagg_handle.h — what the host translation units of the C ABI share (nfagg_api.hip: the flow table; nfagg_api_account.hip:
 // nfagg_account*; nfagg_api_group.hip: the multi-GPU group; nfagg_api_export.hip, nfagg_api_tables.hip, nfagg_api_filter.hip,
-// nfagg_api_conn.hip, nfagg_api_aux.hip: the encoders, the caller tables, the side operations): error reporting, the owner types
+// nfagg_api_conn.hip, nfagg_api_loki.hip, nfagg_api_flp_ipfix.hip, nfagg_api_aux.hip: the encoders, the caller tables, the writers,
+// the side operations; what their entry points do alike is nfagg_api_call.h): error reporting, the owner types
 // — every device / pinned allocation, stream, event and graph of the library lives in one and is released by its destructor —
 // and the handle behind nfagg_handle*, which holds nothing but owners and plain state: `delete h` frees all of it.
 // Private to csrc/; nothing here is exported (nfagg.map).
@@ -88,25 +89,30 @@ struct EventPair { hipEvent_t a, b; int kind; };     // borrowed from nfagg_hand
 // The arrays a TableView points into
 struct TableMem { DevBuf hot, cold, aux, live_list, ctr; };
 
-// export encoders (protobuf, IPFIX, direct-FLP JSON): one scratch, they serialise on the stream and synchronise before returning
+// The export encoders (protobuf, IPFIX, direct-FLP JSON), write ipfix, the filter, conntrack, the resolves and the metrics folds:
+// one scratch, they serialise on the stream and synchronise before returning. Who stages what (nfagg_api_call.h):
 struct EncodeScratch {
-    DevBuf local_off, block_sum, block_base;     // the two scans: u32[n], u32[blocks], u64[blocks + 1] (the total last)
-    DevBuf names;                                // the namer table, stably sorted by if_index
+    DevBuf local_off, block_sum, block_base;     // encode_begin: the two scans, u32[n], u32[blocks], u64[blocks + 1] (the total last);
+                                                 //   the filter, the conversation fold and the metrics folds size them for their own scans
+    DevBuf names;                                // stage_namer: the namer table, stably sorted by if_index (write ipfix's too)
     DevBuf ipfix_name_rows;                      // size pass -> write pass: u32[n]
     DevBuf flp_rows;                             // size pass -> write pass: 8 x u32 per record (seven rows, the line's length)
     DevBuf flp_esc, flp_n_deferred;              // the escaped table; the deferred counter
-    DevBuf in_records, out, out_offsets;         // host-memory entry points: staged records, output bytes, offsets
-    DevBuf out_extra[2];                         //   protobuf: body lengths, kafka keys; FLP: deferred flags
-    DevBuf pb_feat[6];                           //   protobuf: present bits and the five feature parts
+    DevBuf in_records, out, out_offsets;         // encode_staged and the other twins: staged records, output bytes, offsets (the filter
+                                                 //   and the gather: kept indexes)
+    DevBuf out_extra[2];                         //   protobuf: body lengths, kafka keys; FLP: deferred flags; write ipfix: status bytes;
+                                                 //   the filter: keep and rule bytes
+    DevBuf pb_feat[6];                           //   stage_pb_features: present bits and the five feature parts
     DevBuf ne_rows;                              //   *_netev: the flows' table rows
     DevBuf ne_in[3], ne_out[3], ne_missing, ne_info;   // nfagg_netev_resolve: staged inputs and outputs, the missing set, its counters
-    DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record
-    DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record
+    DevBuf k8s_rows;                             // *_k8s and nfagg_k8s_resolve: the flows' two table rows, 2 x u32 per record; staged there
+                                                 //   by the twins that take them from the caller (net resolve, filter, metrics, write ipfix)
+    DevBuf net_rows;                             // *_net and nfagg_net_resolve: the flows' nfagg_net_row, 8 bytes per record; staged likewise
     DevBuf met_slots, met_out;                   // nfagg_metrics_fold: control words and the groupings' tables; the host entry point's groups
     DevBuf conn_slots, conn_flow;                // nfagg_conn_fold: control words and the connection table; per flow hashA and slot
     DevBuf conn_ids, conn_out;                   //   the host entry point's hash ids and partials; the host entry points of the two
                                                  //   conntrack encoders stage their ids / values here too (one stream: calls serialise)
-    std::vector<nfagg_intf_name> h_names;        // host copies, kept until the stream has consumed them
+    std::vector<nfagg_intf_name> h_names;        // stage_namer's and stage_flp_line's host copies, kept until the stream has consumed them
     std::vector<uint8_t> h_flp_esc;
 };
 

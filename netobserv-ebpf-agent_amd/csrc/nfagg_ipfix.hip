@@ -85,7 +85,7 @@ NF_DEV void write_message(uint8_t* p, const Rec& r, const IpfixParams& P, uint32
         for (int k = 0; k < 16; k++) { p[35 + k] = ip_byte(sip, k); p[51 + k] = ip_byte(dip, k); }
         q = p + 67;
     } else {   // model.IP(..).To4(): the v4-mapped form (::ffff:a.b.c.d) gives a.b.c.d, anything else nil -> 0.0.0.0
-        const bool sm = (sip.w[0] | sip.w[1]) == 0 && sip.w[2] == 0xffff0000u, dm = (dip.w[0] | dip.w[1]) == 0 && dip.w[2] == 0xffff0000u;
+        const bool sm = ip_v4_mapped(sip), dm = ip_v4_mapped(dip);
 #pragma unroll
         for (int k = 0; k < 4; k++) { p[35 + k] = sm ? ip_byte(sip, 12 + k) : 0; p[39 + k] = dm ? ip_byte(dip, 12 + k) : 0; }
         q = p + 43;
