@@ -173,6 +173,8 @@ enum {
                             window-relative and the window moves,
                             stats.sequence_rebases.) */
     NFAGG_TRUNCATED = 2, /* output buffer smaller than the result */
+    NFAGG_EDEFER   = 3,  /* nfagg_timebased_extract: some flow has no value for a rule of a table it enters; nothing was changed,
+                            drop those flows and call again */
     /* <0: errors */
     NFAGG_EINVAL   = -1,
     NFAGG_ENODEV   = -2, /* no HIP runtime / no gfx950 device: there is no CPU path */
@@ -2346,6 +2348,159 @@ int nfagg_flp_ipfix_write_device(nfagg_handle* h, nfagg_flp_ipfix_writer* writer
                                  const nfagg_pb_features* d_features, const uint32_t* d_k8s_rows,
                                  const nfagg_flp_ipfix_strings* strings, const nfagg_flp_ipfix_options* opt, void* d_out,
                                  size_t out_cap, uint64_t* d_msg_offsets, uint8_t* d_status, size_t* n_sent, size_t* out_bytes);
+
+/* ------------------------------------------------------------------ */
+/* extract timebased — flowlogs-pipeline's windowed GROUP BY and top-K  */
+/* (pkg/pipeline/extract/extract_timebased.go:35-59,                    */
+/* extract/timebased/{timebased,tables,filters,heap}.go,                */
+/* api/extract_timebased.go). The reference keeps, per index-key table  */
+/* and key, a list of (stamp, flow map) and walks every entry of every  */
+/* list for every rule of every call. Every entry of one call carries   */
+/* the call's one `now`, so a window is a union of whole calls: here a  */
+/* table is a persistent hash table of keys in device memory, a call    */
+/* leaves one compact SLICE of per-key partials stamped `now`, a rule   */
+/* merges the slices inside its window into one accumulator per key,    */
+/* and a float64 selection takes the K best.                            */
+/*                                                                      */
+/* Differences from the reference, by design:                           */
+/*  - a flow that enters a table but lacks the operation key of one of  */
+/*    that table's rules makes the reference panic (ConvertToFloat64 of */
+/*    a missing key, utils/convert.go:56-59): such a call is refused    */
+/*    with NFAGG_EDEFER and changes nothing;                            */
+/*  - the keys of a table are capped (options.max_keys); the reference  */
+/*    never forgets a key and has no cap. One key more than the cap     */
+/*    fails the object until nfagg_timebased_reset;                     */
+/*  - partials are integers. A sum below 2^53 of values that are not    */
+/*    negative equals the reference's float sum in any order; otherwise */
+/*    the value is the correctly rounded float64 of the exact integer   */
+/*    total and the result carries NFAGG_TB_INEXACT, because the        */
+/*    reference's own value then depends on its order of summation;     */
+/*  - ties at the K-th place are broken arbitrarily, as Go's map order  */
+/*    breaks them.                                                      */
+/* ------------------------------------------------------------------ */
+#define NFAGG_TB_MAX_TABLES 4           /* distinct index-key lists */
+#define NFAGG_TB_MAX_RULES 16
+#define NFAGG_TB_MAX_COLUMNS 4          /* index keys of one rule; together at most 40 bytes (an address: 16, anything else: 4) */
+#define NFAGG_TB_MAX_VALUES 4           /* distinct value sources of the rules of one table */
+#define NFAGG_TB_MAX_KEYS (1u << 24)    /* options.max_keys per table; a table has the power of two >= 2 * max_keys slots, at least 1024 */
+#define NFAGG_TB_MAX_TOPK 4096
+#define NFAGG_TB_MAX_SLICES 1024        /* calls with flows inside a table's largest window */
+
+#define NFAGG_TB_OP_SUM 1
+#define NFAGG_TB_OP_AVG 2
+#define NFAGG_TB_OP_MIN 3
+#define NFAGG_TB_OP_MAX 4
+#define NFAGG_TB_OP_COUNT 5
+#define NFAGG_TB_OP_LAST 6
+#define NFAGG_TB_OP_DIFF 7
+
+#define NFAGG_TB_INEXACT 1u             /* nfagg_tb_result.flags: the value is the rounded exact total; the reference's depends on its order */
+
+/* One rule of api.TimebasedFilterRule. index_keys: the names of the rule's indexKeys (or its one indexKey), the keys RecordToMap
+ * and the transforms write, with their presence rules:
+ *   SrcAddr, DstAddr                     the 16 address bytes; present with eth_protocol 0x0800 / 0x86DD
+ *   SrcPort, DstPort                     present with IP and transport_protocol 6 / 17 / 132
+ *   Proto                                present with IP
+ *   SrcK8S_<f>, DstK8S_<f>               one field of the flow's Kubernetes row, f one of Namespace, Name, Type, OwnerName,
+ *                                        OwnerType, NetworkName, HostIP, HostName, Zone, as a CLASS: the dense id of the field's
+ *                                        (text, presence) by nfagg_k8s_render's rules, what nfagg_metrics_table_create computes
+ *                                        for that one bit; present when the row has the field and its text is not empty
+ *   SrcSubnetLabel, DstSubnetLabel       the net row's label index; present when there is one and its text is not empty
+ *   FlowDirection                        the net row's direction; present unless NFAGG_NET_NO_DIRECTION
+ * A flow enters a rule's table only if every index key is present. Rules with equal key lists share a table. value: the
+ * operation key as one of NFAGG_MET_VALUE_* 1..6, with the presence rules stated there; every operation reads it, `count` too
+ * (filters.go:86-91). interval_ns: the rule's timeInterval; an entry stamped exactly `now - interval_ns` is inside the window. */
+typedef struct nfagg_tb_rule {
+    uint32_t struct_size;               /* sizeof(nfagg_tb_rule) */
+    uint32_t n_index_keys;              /* 1..NFAGG_TB_MAX_COLUMNS */
+    const char* index_keys[NFAGG_TB_MAX_COLUMNS];   /* NUL-terminated */
+    uint32_t operation;                 /* NFAGG_TB_OP_* */
+    uint32_t value;                     /* NFAGG_MET_VALUE_* 1..6 */
+    uint32_t top_k;                     /* 0: every key, in unspecified order; else at most NFAGG_TB_MAX_TOPK */
+    uint32_t reversed;                  /* 0: the K largest, descending; 1: the K smallest, ascending */
+    int64_t interval_ns;                /* >= 0 */
+} nfagg_tb_rule;
+
+typedef struct nfagg_tb_options {
+    uint32_t struct_size;               /* sizeof(nfagg_tb_options) */
+    uint32_t max_keys;                  /* per table, 1..NFAGG_TB_MAX_KEYS */
+} nfagg_tb_options;
+
+typedef struct nfagg_tb_result {
+    uint32_t key;                       /* the key's dense id in its table, in order of first claim: nfagg_timebased_keys reads it back */
+    uint32_t flags;                     /* NFAGG_TB_INEXACT */
+    double value;
+} nfagg_tb_result;
+
+/* One key's columns, in the order of its table's index keys: the 16 address bytes, or a 32-bit value in the first four bytes
+ * (little endian: a port, the protocol, a class, a label index, the direction) and zeroes. */
+typedef struct nfagg_tb_key {
+    uint8_t col[NFAGG_TB_MAX_COLUMNS][16];
+} nfagg_tb_key;
+
+typedef struct nfagg_tb_stats {
+    uint32_t n_tables, n_rules;
+    uint32_t keys[NFAGG_TB_MAX_TABLES];         /* distinct keys so far */
+    uint32_t slots[NFAGG_TB_MAX_TABLES];        /* of the table's hash table */
+    uint32_t slices[NFAGG_TB_MAX_TABLES];       /* live slices */
+    uint32_t table_of_rule[NFAGG_TB_MAX_RULES];
+    uint64_t bytes_held;                        /* device memory of the tables, the slices and the evaluation scratch */
+    int64_t last_now_ns;
+    uint32_t failed, has_clock;
+} nfagg_tb_stats;
+
+typedef struct nfagg_timebased nfagg_timebased;
+
+/* Build the rule set: n_rules 1..NFAGG_TB_MAX_RULES. k8s_table / net_table: required when a rule names a Kubernetes key / a
+ * subnet label (else may be NULL), must be of the same handle and outlive the object. NFAGG_EINVAL, with a message that names
+ * the rule and the offender: a key name outside the list above, a selected Kubernetes or label text that contains ',' (the
+ * reference joins a key's values by ',' and splits the result again), a key list wider than 40 bytes, an unknown operation or
+ * value source, top_k over NFAGG_TB_MAX_TOPK, a negative interval, more than NFAGG_TB_MAX_TABLES distinct key lists or
+ * NFAGG_TB_MAX_VALUES value sources in one table, max_keys out of range, a wrong struct_size. h == NULL builds and checks on the
+ * host alone (errors through nfagg_last_error(NULL)); extract refuses such an object. */
+int nfagg_timebased_rules_create(nfagg_handle* h, const nfagg_k8s_table* k8s_table, const nfagg_net_table* net_table, const nfagg_tb_rule* rules,
+                                 uint32_t n_rules, const nfagg_tb_options* options, nfagg_timebased** tb);
+void nfagg_timebased_destroy(nfagg_timebased* tb);
+
+/* Extract(entries) at `now_ns`: the flows enter their tables as one slice stamped now_ns, every rule is evaluated, and slices
+ * older than their table's largest interval are freed. records, features (as nfagg_metrics_fold_content takes them; NULL: no flow
+ * has a part), k8s_rows and net_rows (as the resolves wrote them; NULL when no rule reads them, else NFAGG_EINVAL) describe the n
+ * flows. result_cap, out, n_out: arrays of n_rules. out[r] receives rule r's results in the reference's order (sorted for top_k
+ * > 0, any order for 0); n_out[r] is exact always.
+ *   NFAGG_EDEFER     some entering flow lacks a value source of its table; *n_missing = their number; NOTHING has changed (no
+ *                    key, no slice, no clock). Drop them (nfagg_filter_apply with a presence query, nfagg_gather) and repeat.
+ *   NFAGG_TRUNCATED  (a) some result_cap[r] < n_out[r]: nothing is written to any out[r], but the window state HAS advanced:
+ *                    repeat with nfagg_timebased_results, not with this call. (b) a table met more distinct keys than max_keys:
+ *                    n_out is all zero, the object has failed and every later call returns NFAGG_EINVAL until
+ *                    nfagg_timebased_reset (nfagg_timebased_stats tells the two apart).
+ *   NFAGG_EINVAL     now_ns below the previous call's; a failed object; arguments.
+ *   NFAGG_ERANGE     n above 2^32 - 2; a table holds NFAGG_TB_MAX_SLICES slices that are still inside its largest window at now_ns (nothing has changed).
+ * n == 0 is a valid call: time passes, windows shrink and the trim runs. All pointers HOST memory: */
+int nfagg_timebased_extract(nfagg_handle* h, nfagg_timebased* tb, const void* records, size_t n, const nfagg_pb_features* features,
+                            const uint32_t* k8s_rows, const nfagg_net_row* net_rows, int64_t now_ns, const uint32_t* result_cap,
+                            nfagg_tb_result* const* out, uint32_t* n_out, uint64_t* n_missing);
+/* Same with d_records, the arrays inside d_features, d_k8s_rows, d_net_rows and every d_out[r] in DEVICE memory (records and
+ * results 16-byte, rows 8-byte aligned); result_cap, the array d_out itself, n_out and n_missing are host memory. */
+int nfagg_timebased_extract_device(nfagg_handle* h, nfagg_timebased* tb, const void* d_records, size_t n, const nfagg_pb_features* d_features,
+                                   const uint32_t* d_k8s_rows, const nfagg_net_row* d_net_rows, int64_t now_ns, const uint32_t* result_cap,
+                                   nfagg_tb_result* const* d_out, uint32_t* n_out, uint64_t* n_missing);
+/* Evaluate the rules again at the last call's now_ns, without adding a slice: what a caller does after NFAGG_TRUNCATED (a).
+ * NFAGG_ESTATE before the first extract. */
+int nfagg_timebased_results(nfagg_handle* h, nfagg_timebased* tb, const uint32_t* result_cap, nfagg_tb_result* const* out, uint32_t* n_out);
+int nfagg_timebased_results_device(nfagg_handle* h, nfagg_timebased* tb, const uint32_t* result_cap, nfagg_tb_result* const* d_out, uint32_t* n_out);
+
+/* The columns of n keys of table `table` (nfagg_tb_stats.table_of_rule) by their ids. The host renders them with what it has:
+ * net.IP.String() for an address, decimal for a port, the protocol and the direction, nfagg_timebased_class_row and the
+ * Kubernetes entries for a class, the label list for a label index. NFAGG_EINVAL for an id that no key has. */
+int nfagg_timebased_keys(nfagg_timebased* tb, uint32_t table, const uint32_t* keys, size_t n, nfagg_tb_key* out);
+/* The first row of the Kubernetes table whose field has class `cls` in column `column` of table `table` (a Kubernetes column). */
+int nfagg_timebased_class_row(const nfagg_timebased* tb, uint32_t table, uint32_t column, uint32_t cls, uint32_t* row);
+/* The hash that places a key in its table: the slot of first probe is hash & (slots - 1), probing is linear. Pure CPU; 0 for
+ * arguments out of range. For tests that craft collisions. */
+uint64_t nfagg_timebased_key_hash(const nfagg_timebased* tb, uint32_t table, const nfagg_tb_key* key);
+/* Forget every key, slice and the clock; a failed object works again. */
+int nfagg_timebased_reset(nfagg_timebased* tb);
+int nfagg_timebased_stats(const nfagg_timebased* tb, nfagg_tb_stats* out);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ except Exception:   # torch is optional plumbing, not a dependency of the librar
 
 lib = C.CDLL(LIB_PATH)
 
-OK, FULL, TRUNCATED = 0, 1, 2
+OK, FULL, TRUNCATED, EDEFER = 0, 1, 2, 3
 EINVAL, ENODEV, ENOMEM, EDEVICE, ESTATE, ERANGE = -1, -2, -3, -4, -5, -6
 REASON_TIMEOUT, REASON_FULL, REASON_CLOSING = 0, 1, 2
 REASON_NAMES = {0: "timeout", 1: "full", 2: "closing"}
@@ -226,6 +226,30 @@ CONN_OPS = {"count": 0, "sum": 1, "min": 2, "max": 3, "first": 4, "last": 5}    
 CONN_INPUTS = {"": 0, "Bytes": 1, "Packets": 2, "TimeFlowStartMs": 3, "TimeFlowEndMs": 4, "SrcAddr": 5, "DstAddr": 6, "SrcPort": 7, "DstPort": 8,
                "Proto": 9, "SrcMac": 10, "DstMac": 11, "Etype": 12, "Dscp": 13, "IfDirections": 14}                 # NFAGG_CONN_IN_*
 CONN_RECORD_TYPES = {"newConnection": 0, "endConnection": 1, "heartbeat": 2}                                      # NFAGG_CONN_RECORD_*
+
+
+# extract timebased (nfagg_timebased_*)
+TB_MAX_TABLES, TB_MAX_RULES, TB_MAX_COLUMNS, TB_MAX_VALUES, TB_MAX_KEYS, TB_MAX_TOPK, TB_MAX_SLICES = 4, 16, 4, 4, 1 << 24, 4096, 1024
+TB_OP_SUM, TB_OP_AVG, TB_OP_MIN, TB_OP_MAX, TB_OP_COUNT, TB_OP_LAST, TB_OP_DIFF = range(1, 8)
+TB_INEXACT = 1
+
+
+class TbRule(C.Structure):
+    """nfagg_tb_rule (include/nfagg.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_index_keys", C.c_uint32), ("index_keys", C.c_char_p * 4), ("operation", C.c_uint32),
+                ("value", C.c_uint32), ("top_k", C.c_uint32), ("reversed", C.c_uint32), ("interval_ns", C.c_int64)]
+
+
+class TbOptions(C.Structure):
+    """nfagg_tb_options (include/nfagg.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_keys", C.c_uint32)]
+
+
+class TbStats(C.Structure):
+    """nfagg_tb_stats (include/nfagg.h)."""
+    _fields_ = [("n_tables", C.c_uint32), ("n_rules", C.c_uint32), ("keys", C.c_uint32 * 4), ("slots", C.c_uint32 * 4), ("slices", C.c_uint32 * 4),
+                ("table_of_rule", C.c_uint32 * 16), ("bytes_held", C.c_uint64), ("last_now_ns", C.c_int64), ("failed", C.c_uint32),
+                ("has_clock", C.c_uint32)]
 
 
 class ConnField(C.Structure):
@@ -434,6 +458,19 @@ SIGNATURES = {
     "nfagg_shard_ids": (None, [_vp, _sz, C.c_uint32, _vp]),
     "nfagg_key_hash": (C.c_uint64, [_vp]),
     "nfagg_ip_hash": (C.c_uint64, [_vp, C.c_uint32]),
+    "nfagg_timebased_rules_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(TbRule), C.c_uint32, C.POINTER(TbOptions), C.POINTER(_vp)]),
+    "nfagg_timebased_destroy": (None, [_vp]),
+    "nfagg_timebased_extract": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(_vp),
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "nfagg_timebased_extract_device": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(PbFeatures), _vp, _vp, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(_vp),
+                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "nfagg_timebased_results": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    "nfagg_timebased_results_device": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32), C.POINTER(_vp), C.POINTER(C.c_uint32)]),
+    "nfagg_timebased_keys": (C.c_int, [_vp, C.c_uint32, _vp, _sz, _vp]),
+    "nfagg_timebased_class_row": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "nfagg_timebased_key_hash": (C.c_uint64, [_vp, C.c_uint32, _vp]),
+    "nfagg_timebased_reset": (C.c_int, [_vp]),
+    "nfagg_timebased_stats": (C.c_int, [_vp, C.POINTER(TbStats)]),
     "nfagg_metrics_group_hash": (C.c_uint64, [C.c_uint32, _vp]),
     "nfagg_metrics_group_hash_content": (C.c_uint64, [C.c_uint32, _vp]),
     "nfagg_stats_get": (C.c_int, [_vp, C.POINTER(Stats)]),

@@ -859,6 +859,70 @@ class FlowTable:
         self._check(rc, ok=(L.OK, L.TRUNCATED))
         return rc, [int(x) for x in n_a]
 
+    # -- extract timebased (nfagg_timebased_*): the windowed GROUP BY and top-K; timebased.ExtractTimebased is the host side
+    def timebased_rules(self, rules, k8s: "K8sTable" = None, net: "NetTable" = None, max_keys: int = 1 << 16) -> "TimebasedRules":
+        """The rule set on this handle's device. rules: dicts of index_keys, operation (L.TB_OP_*), value (L.MET_VALUE_* 1..6),
+        top_k, reversed, interval_ns (TimebasedRules.rule)."""
+        return TimebasedRules(rules, k8s, net, max_keys, self)
+
+    def _tb_outs(self, tb, caps):
+        R = len(tb.rules)
+        caps = [int(caps)] * R if np.isscalar(caps) else [int(c) for c in caps]
+        return R, caps, (C.c_uint32 * R)(*caps), (C.c_uint32 * R)()
+
+    def timebased_extract(self, tb: "TimebasedRules", records: np.ndarray, now_ns: int, k8s_rows: np.ndarray = None, net_rows: np.ndarray = None,
+                          features=None, caps=4096):
+        """nfagg_timebased_extract. features: (present, parts) or None. caps: one cap, or one per rule. Returns (rc, results,
+        n_out, n_missing): results[r] is a TB_RESULT array in the reference's order; with rc == L.TRUNCATED or L.EDEFER every
+        results[r] is empty (after L.TRUNCATED the windows HAVE advanced: take the results with timebased_results)."""
+        r = np.ascontiguousarray(records)
+        n = r.nbytes // 144
+        R, caps, cap_a, n_a = self._tb_outs(tb, caps)
+        kr = np.ascontiguousarray(k8s_rows, dtype=np.uint32) if k8s_rows is not None else None
+        nr = np.ascontiguousarray(net_rows, dtype=NET_ROW) if net_rows is not None else None
+        feat, keep = (None, None)
+        if features is not None and features[0] is not None:
+            feat, keep = self._pb_features(n, features[0], {k: v for k, v in self._content_parts(features[1]).items() if v is not None})
+        outs = [np.zeros(min(c, tb.max_keys), dtype=TB_RESULT) for c in caps]
+        ptrs = (C.c_void_p * R)(*[o.ctypes.data if o.size else None for o in outs])
+        missing = C.c_uint64(0)
+        rc = L.lib.nfagg_timebased_extract(self._h, tb._t, r.ctypes.data_as(C.c_void_p) if n else None, n, C.byref(feat) if feat is not None else None,
+                                           kr.ctypes.data_as(C.c_void_p) if kr is not None and n else None,
+                                           nr.ctypes.data_as(C.c_void_p) if nr is not None and n else None, now_ns, cap_a, ptrs, n_a, C.byref(missing))
+        self._check(rc, ok=(L.OK, L.TRUNCATED, L.EDEFER))
+        counts = [int(x) for x in n_a]
+        return rc, [o[:c if rc == L.OK else 0] for o, c in zip(outs, counts)], counts, int(missing.value)
+
+    def timebased_extract_device(self, tb: "TimebasedRules", d_records: int, n: int, now_ns: int, d_k8s_rows: int, d_net_rows: int, caps, d_outs,
+                                 d_features=None):
+        """Device-resident variant (raw device pointers; 0: none; d_outs[r]: room for caps[r] results of 16 bytes, 16-byte
+        aligned). Returns (rc, n_out, n_missing)."""
+        R, caps, cap_a, n_a = self._tb_outs(tb, caps)
+        ptrs = (C.c_void_p * R)(*[p or None for p in d_outs])
+        feat = self._pb_features(n, d_features[0], self._content_parts(d_features[1]), device=True)[0] if d_features is not None else None
+        missing = C.c_uint64(0)
+        rc = L.lib.nfagg_timebased_extract_device(self._h, tb._t, C.c_void_p(d_records or None), n, C.byref(feat) if feat is not None else None,
+                                                  C.c_void_p(d_k8s_rows or None), C.c_void_p(d_net_rows or None), now_ns, cap_a, ptrs, n_a, C.byref(missing))
+        self._check(rc, ok=(L.OK, L.TRUNCATED, L.EDEFER))
+        return rc, [int(x) for x in n_a], int(missing.value)
+
+    def timebased_results(self, tb: "TimebasedRules", caps=4096):
+        """nfagg_timebased_results: the rules again at the last call's now. Returns (rc, results, n_out)."""
+        R, caps, cap_a, n_a = self._tb_outs(tb, caps)
+        outs = [np.zeros(min(c, tb.max_keys), dtype=TB_RESULT) for c in caps]
+        ptrs = (C.c_void_p * R)(*[o.ctypes.data if o.size else None for o in outs])
+        rc = L.lib.nfagg_timebased_results(self._h, tb._t, cap_a, ptrs, n_a)
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        counts = [int(x) for x in n_a]
+        return rc, [o[:c if rc == L.OK else 0] for o, c in zip(outs, counts)], counts
+
+    def timebased_results_device(self, tb: "TimebasedRules", caps, d_outs):
+        R, caps, cap_a, n_a = self._tb_outs(tb, caps)
+        ptrs = (C.c_void_p * R)(*[p or None for p in d_outs])
+        rc = L.lib.nfagg_timebased_results_device(self._h, tb._t, cap_a, ptrs, n_a)
+        self._check(rc, ok=(L.OK, L.TRUNCATED))
+        return rc, [int(x) for x in n_a]
+
     # -- conversation tracking (nfagg_conn_*): the per-call fold under FLP's `extract conntrack`; conntrack.ConnTrack is the host side
     def conn_fold(self, records: np.ndarray, now_unix_ns: int, mono_now_ns: int, cap: int = 4096, hash_ids: bool = True):
         """nfagg_conn_fold. Returns (rc, partials, n_conns, hash_ids, n_discarded): partials is a CONN_PARTIAL array in unspecified
@@ -1625,6 +1689,78 @@ class MetricsTable(_CallerTable):
         if rc != L.OK:
             raise NfaggError(rc, (L.lib.nfagg_last_error(self._owner._h if self._owner is not None else None) or b"").decode())
         return row.value
+
+
+TB_RESULT = np.dtype([("key", "<u4"), ("flags", "<u4"), ("value", "<f8")])      # nfagg_tb_result
+TB_KEY = np.dtype([("col", "u1", (4, 16))])                                       # nfagg_tb_key
+
+
+class TimebasedRules(_CallerTable):
+    """The rules of `extract timebased` and their tables (nfagg_timebased_rules_create). rules: dicts as rule() takes them, or
+    L.TbRule. With a FlowTable the tables live on its device; with table=None the rules are built and checked on the host alone
+    (and `k8s` / `net` must be host-only too). The Kubernetes and the net table must outlive the object."""
+
+    @staticmethod
+    def rule(index_keys=(), operation=L.TB_OP_SUM, value=L.MET_VALUE_BYTES, top_k=0, reversed=False, interval_ns=0, struct_size=None,
+             n_index_keys=None) -> "L.TbRule":
+        ru = L.TbRule()
+        ru.struct_size = C.sizeof(L.TbRule) if struct_size is None else struct_size
+        keys = [k.encode() if isinstance(k, str) else bytes(k) for k in index_keys]
+        ru.n_index_keys = len(keys) if n_index_keys is None else n_index_keys
+        for k, name in enumerate(keys[: L.TB_MAX_COLUMNS]):
+            ru.index_keys[k] = name
+        ru.operation, ru.value, ru.top_k, ru.reversed, ru.interval_ns = operation, value, top_k, 1 if reversed else 0, interval_ns
+        return ru
+
+    def __init__(self, rules, k8s: "K8sTable" = None, net: "NetTable" = None, max_keys: int = 1 << 16, table: "FlowTable" = None, options=None):
+        self.rules = [ru if isinstance(ru, L.TbRule) else self.rule(**ru) for ru in rules]
+        arr = (L.TbRule * max(len(self.rules), 1))(*self.rules)
+        if options is None:
+            options = L.TbOptions(C.sizeof(L.TbOptions), max_keys)
+        self.max_keys = int(options.max_keys)
+        self._create(table, L.lib.nfagg_timebased_destroy,
+                     lambda h, out: L.lib.nfagg_timebased_rules_create(h, k8s._t if k8s is not None else None, net._t if net is not None else None, arr,
+                                                                       len(self.rules), C.byref(options), out))
+        self.k8s, self.net = k8s, net
+        st = self.stats()
+        self.table_of_rule = [int(st.table_of_rule[r]) for r in range(len(self.rules))]
+
+    def _err(self, rc):
+        return NfaggError(rc, (L.lib.nfagg_last_error(self._owner._h if self._owner is not None else None) or b"").decode())
+
+    def stats(self) -> "L.TbStats":
+        st = L.TbStats()
+        rc = L.lib.nfagg_timebased_stats(self._t, C.byref(st))
+        if rc != L.OK:
+            raise self._err(rc)
+        return st
+
+    def reset(self) -> None:
+        rc = L.lib.nfagg_timebased_reset(self._t)
+        if rc != L.OK:
+            raise self._err(rc)
+
+    def keys(self, table: int, ids) -> np.ndarray:
+        """nfagg_timebased_keys: the columns of the keys `ids` of table `table`, a TB_KEY array."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        out = np.zeros(len(ids), dtype=TB_KEY)
+        rc = L.lib.nfagg_timebased_keys(self._t, table, ids.ctypes.data_as(C.c_void_p), len(ids), out.ctypes.data_as(C.c_void_p))
+        if rc != L.OK:
+            raise self._err(rc)
+        return out
+
+    def class_row(self, table: int, column: int, cls: int) -> int:
+        row = C.c_uint32(0)
+        rc = L.lib.nfagg_timebased_class_row(self._t, table, column, cls, C.byref(row))
+        if rc != L.OK:
+            raise self._err(rc)
+        return row.value
+
+    def key_hash(self, table: int, keys) -> np.ndarray:
+        """nfagg_timebased_key_hash of every TB_KEY of `keys`."""
+        keys = np.ascontiguousarray(np.atleast_1d(keys), dtype=TB_KEY)
+        base = keys.ctypes.data
+        return np.array([L.lib.nfagg_timebased_key_hash(self._t, table, C.c_void_p(base + 64 * k)) for k in range(len(keys))], dtype=np.uint64)
 
 
 def ip_hash(ip16: bytes, seed_index: int) -> int:

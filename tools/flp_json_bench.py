@@ -70,7 +70,15 @@ nfagg_loki_plan_device, of rendering the streams' label texts on the host (once 
 _net call: nfagg_flp_ipfix_write_device with enterprise id 2 and a TCP-sized message limit, the strings table over the leg's 100 000
 entries, and nfagg_encode_ipfix_device (the agent's own exporter, 19 fixed fields, no state) on the same records. Reported: the median
 wall time of a whole call (presence and carry, the scan over blocks, size, the two scans, the read-back, write, state export), the sent
-and failed flows, the bytes, and the bytes a flow moves by this tool's own count. --k8s-trace covers the k_ipfix_* kernels."""
+and failed flows, the bytes, and the bytes a flow moves by this tool's own count. --k8s-trace covers the k_ipfix_* kernels.
+
+--timebased (with --k8s --net --metrics --conntrack): the extract timebased leg on top, on the same records and Kubernetes rows in
+the same run, beside the metrics fold and the conversation fold: two rules, the SrcAddr top-10 sum of Bytes and the
+SrcK8S_Namespace,DstK8S_Namespace top-10 sum of Bytes, with a window that holds 12 calls. Twelve calls fill the window; then the median
+wall time of a whole nfagg_timebased_extract_device call in the steady state (presence, its read-back, claim, fold, finish, the second
+read-back, the slice emit, per rule the merges of 12 slices, value, select and sort, the synchronisation, the trim) and of
+nfagg_timebased_results_device alone (the evaluation without a new slice). Flows without Bytes are dropped first, as the stage's
+caller must. --k8s-trace covers the k_tb_* kernels."""
 import io
 import os
 import queue
@@ -100,6 +108,9 @@ CONNTRACK = "--conntrack" in sys.argv[1:]
 FILTER = "--filter" in sys.argv[1:]
 LOKI = "--loki" in sys.argv[1:]
 IPFIX = "--ipfix" in sys.argv[1:]
+TIMEBASED = "--timebased" in sys.argv[1:]
+if TIMEBASED and not (K8S and NET and METRICS and CONNTRACK):
+    sys.exit("--timebased runs behind --k8s --net --metrics --conntrack: give them too")
 FLOWS = int(sys.argv[sys.argv.index("--flows") + 1]) if "--flows" in sys.argv[1:] else 0
 NET_CATEGORIES = [("cat-%d" % c, ["172.%d.%d.0/24" % (16 + c, k) for k in range(8)] + ["2001:db8:%x::/48" % (16 * c + k) for k in range(1)]) for c in range(5)] + \
                  [("pods", ["100.64.0.0/10"]), ("everything", ["0.0.0.0/0", "::/0"])]
@@ -173,7 +184,7 @@ def k8s_trace(root):
     for f in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
             name = row["Kernel_Name"]
-            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_filter_|k_gather|k_loki_|k_ipfix_|fillBuffer|scan|[Ss]ort|onesweep", name):
+            if not re.search(r"k_flp_|k_k8s_|k_net_|k_metrics_|k_conn_|k_filter_|k_gather|k_loki_|k_ipfix_|k_tb_|fillBuffer|scan|[Ss]ort|onesweep", name):
                 continue
             short = re.sub(r"^void nfagg::|\(.*$|nfagg::", "", name)
             if "rocprim" in name:                           # the library's scan and sort kernels: their configuration's name and value types
@@ -295,6 +306,43 @@ def conntrack_leg(tab, d_ev, m, tls, k8s, net, d_off):
         assert rc == nf.OK and wrote == need
         per_byte("conv", n_conns, dt, wrote)
         print(f"           conversation records: {lay.n_columns} columns, longest possible line {lay.max_line} B, {n_def} deferred")
+
+
+def timebased_leg(tab, k8s, d_ev, m, d_rows, n_distinct):
+    L = nf._lib
+    second, window = 10**9, 12
+    recs = d_ev.view(torch.uint8)[: m * 144].view(m, 144)
+    keep = recs[:, 56:64].contiguous().view(torch.int64).reshape(-1) != 0          # a flow without Bytes has no operation key: dropped first
+    kept = int(keep.sum())
+    rows = d_rows
+    if kept != m:
+        recs, rows = recs[keep].contiguous(), d_rows[keep].contiguous()
+    specs = [dict(index_keys=keys, operation=L.TB_OP_SUM, value=L.MET_VALUE_BYTES, top_k=10, interval_ns=(window - 1) * second)
+             for keys in (["SrcAddr"], ["SrcK8S_Namespace", "DstK8S_Namespace"])]
+    max_keys = min(L.TB_MAX_KEYS, max(1024, n_distinct))
+    d_outs = [torch.empty(10 * 16, dtype=torch.uint8, device="cuda") for _ in specs]
+    ptrs = [o.data_ptr() for o in d_outs]
+    with tab.timebased_rules(specs, k8s, None, max_keys) as tb:
+        now = [0]
+
+        def call():
+            now[0] += second
+            return tab.timebased_extract_device(tb, recs.data_ptr(), kept, now[0], rows.data_ptr(), 0, [10, 10], ptrs)
+        for _ in range(window):                                                    # fill the window: every later call merges 12 slices per rule
+            rc, counts, missing = call()
+            assert (rc, missing) == (nf.OK, 0), (rc, missing)
+        (rc, counts, missing), dt = timed(call)
+        st = tb.stats()
+        assert rc == nf.OK and counts == [min(10, st.keys[0]), min(10, st.keys[1])], (rc, counts, missing, st.failed)   # at the larger size no flow has both namespaces
+        (rc, counts), dt_eval = timed(lambda: tab.timebased_results_device(tb, [10, 10], ptrs))
+        assert rc == nf.OK
+        st = tb.stats()
+        top = [o.cpu().numpy().view(nf.TB_RESULT) for o in d_outs]
+        assert all((np.diff(t["value"]) <= 0).all() for t in top) and st.slices[0] == window and st.slices[1] in (0, window)
+    print(f"  timebased {kept} of {m} flows (the others have no Bytes) -> {st.keys[0]} addresses in {st.slots[0]} slots, {st.keys[1]} namespace pairs; "
+          f"{window} slices in the window, {st.bytes_held >> 20} MiB held; {dt * 1e3:.3f} ms per call = {kept / dt / 1e6:.1f} M flows/s; "
+          f"the evaluation alone (2 rules x {window} slices, value, select, sort): {dt_eval * 1e3:.3f} ms; "
+          f"{int(top[0]['flags'].sum())} + {int(top[1]['flags'].sum())} of the {counts[0]} + {counts[1]} results inexact (totals of 2^53 or more)")
 
 
 def loki_leg(tab, d_ev, m, tls, k8s, net, d_ids, dt_conn):
@@ -537,6 +585,9 @@ for flows in ((FLOWS,) if FLOWS else (10_000_000,) if (CONTENT or TLS) and not K
                             metrics_leg(tab, k8s, d_ev, m, d_rows, d_net)
                             if CONNTRACK:
                                 conntrack_leg(tab, d_ev, m, tls, k8s, net, d_off)
+                                if TIMEBASED:
+                                    tab.k8s_resolve_device(k8s, d_ev.data_ptr(), m, d_rows.data_ptr())
+                                    timebased_leg(tab, k8s, d_ev, m, d_rows, n_distinct)
                             if CONTENT:
                                 metrics_content_leg(tab, k8s, d_ev, m, d_rows, d_net)
                     del d_net
